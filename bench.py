@@ -9,13 +9,16 @@ S, Y, convergence_error) at BASELINE.json configs[1]:
 (jstsp19_amd.system_model, per-trial pilots => per-trial B) and resident in HBM before the
 timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Trials shard embarrassingly over ranks (weak scaling: `batch` trials per GPU, global trial
 ids keyed into the RNG so inputs do not depend on N); the only collective is one RCCL
 all-reduce of the NMSE sum (plus the timing MAX).  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the last timed step returned, so that two builds can be compared output for output on the
+same inputs (they depend on the arguments only: the generator is keyed by seed and global trial id).
 """
 from __future__ import annotations
 
@@ -41,6 +44,8 @@ MFMA_F16_PEAK_TFLOPS = 2500.0      # same guide: dense BF16/FP16 MFMA peak (2495
 # 1635-1681 for 32x32x16 on random data; one wave per SIMD: 1332 / 1624.  Reported beside the nominal roof, never instead of it.
 MFMA_F16_SUSTAINED_TFLOPS = 1678.0
 IMAX = 100
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs: all files together stay below this
+DUMP_SEED = 20190913               # --dump-outputs: the trial sample when the outputs do not fit
 
 
 def parse():
@@ -70,7 +75,41 @@ def parse():
     ap.add_argument("--no-strict-fp32", action="store_true", help="skip the informational JSTSP_H2=0 (strict complex-fp32 MFMA) rate")
     ap.add_argument("--no-configs4", action="store_true",
                     help="skip the informational BASELINE configs[4] leg (proposed_algorithm_angles at N=64 M=65536 G2=4096, 32 trials, one call)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's trials) as DIR/<name>.npy: S, Y and "
+                         "the three columns of convergence_error as convergence_error_V1 / _V2 / _v (--sweep: mean_nmse), complex "
+                         "as a trailing (real, imag) axis, at most 64 MB in all (beyond that, the same seeded sample of trials "
+                         "from each array)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: save `arrays` (name -> torch tensor or None, all with the same leading trial axis) as path/<name>.npy in
+    float32 / float64, complex as a trailing (real, imag) axis.  When the whole of them exceeds DUMP_LIMIT_BYTES, every array
+    keeps the same trials: a sorted sample drawn with DUMP_SEED, so two runs with the same arguments write the same trials.
+    Returns what the result line records about the dump."""
+    arrays = {k: torch.as_tensor(v) for k, v in arrays.items() if v is not None}
+    rows = next(iter(arrays.values())).shape[0]
+    per_row = sum(v[0].numel() * v.element_size() for v in arrays.values())
+    keep = min(rows, (DUMP_LIMIT_BYTES - 1024 * len(arrays)) // per_row)        # (1 KiB per file for the .npy header)
+    if keep < 1:
+        raise ValueError("--dump-outputs: one trial of the outputs is larger than %d bytes" % DUMP_LIMIT_BYTES)
+    idx = None if keep == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, v in arrays.items():
+        if idx is not None:
+            v = v[torch.as_tensor(idx, device=v.device)]
+        v = v.detach().cpu()
+        if v.is_complex():
+            v = torch.view_as_real(v.contiguous())
+        x = v.numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32, copy=False)
+        np.save(os.path.join(path, name + ".npy"), x)
+        shapes[name] = list(x.shape)
+    return {"dir": path, "trials": "all" if idx is None else idx.tolist(), "shapes": shapes, "seed": DUMP_SEED}
 
 
 class HipHooks:
@@ -230,6 +269,7 @@ def sweep_mode(a, rank, world, dist, device, hooks=HipHooks):
     solves = 2 * len(snrs) * a.sweep_trials
     line = None
     if rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {"mean_nmse": out}) if a.dump_outputs else None
         line = {"metric": "channel-estimates/sec (batched MC) at Nt=Nr=64,K=64; NMSE vs ref",
                 "value": round(solves / dt, 3), "unit": "channel-estimates/s", "n_gpus": world, "steps": 1, "warmup": 0,
                 "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -240,7 +280,7 @@ def sweep_mode(a, rank, world, dist, device, hooks=HipHooks):
                                                                                                    a.sweep_trials, IMAX),
                            "trials_per_call": a.batch, "parallelism": "trials sharded, dp%d" % world},
                 "snr_db": snrs, "mean_nmse_proposed": [round(v, 6) for v in out[:, 0].tolist()],
-                "mean_nmse_angles": [round(v, 6) for v in out[:, 1].tolist()]}
+                "mean_nmse_angles": [round(v, 6) for v in out[:, 1].tolist()], "dump_outputs": dumped}
     emit(line, dist, rank)
 
 
@@ -317,6 +357,15 @@ def main():
     dt = float(tmax.item())
 
     S, Y, ce = out
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        outs = {"S": S, "Y": Y}
+        if ce is not None:
+            # convergence_error (batch, Imax, 3) holds three quantities per iteration: |V1|^2 / |X|^2 (:67), |V2|^2 / |X|^2 (:69) and
+            # the change of v relative to the previous v (:51).  The last one starts from v = 0, so its first entry is Inf in every
+            # trial by definition; it is written from iteration 2 on, and every file is finite unless a computed value is not.
+            outs.update(convergence_error_V1=ce[:, :, 0], convergence_error_V2=ce[:, :, 1], convergence_error_v=ce[:, 1:, 2])
+        dumped = dump_outputs(a.dump_outputs, outs)
     # NMSE per trial (plot_errorVSsnr.m:138-141), one all-reduce of the sum (:170 takes the mean)
     nmse = hooks.nmse(S, inp)
     acc = torch.stack([nmse.sum(), torch.tensor(float(a.batch), dtype=torch.float64, device=device)])
@@ -331,7 +380,7 @@ def main():
                     "unit": "channel-estimates/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                     "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                     "dtype": "stub", "data": "stub", "config": {"workload": workload, "trials_per_gpu_per_step": a.batch},
-                    "mean_nmse": mean_nmse, "trial_ids_rank0": [ids[0], ids[-1]]}
+                    "mean_nmse": mean_nmse, "trial_ids_rank0": [ids[0], ids[-1]], "dump_outputs": dumped}
         emit(line, dist, rank)
         return
 
@@ -696,6 +745,7 @@ def main():
                        "outputs": "S,Y,convergence_error" if want_ce else "S,Y", "snr_db": a.snr_db,
                        "pilots": "shared (one B)" if a.shared_pilots else "per-trial (B per trial)", "parallelism": "trials sharded, dp%d" % world},
             "mean_nmse": mean_nmse, "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "host_path": host,
+            "dump_outputs": dumped,
         }
         line.update(extra)
     emit(line if rank == 0 else None, dist, rank)

@@ -30,6 +30,9 @@ class StubHooks:
     @staticmethod
     def device(local):
         torch.set_num_threads(2)
+        # torch.distributed.barrier() asks torch._C._get_accelerator(), which initialises the HIP runtime - and so opens the GPU - on a
+        # machine that has one, even under gloo.  The ranks of this stub are CPU processes: eight of them must not hold a shared GPU.
+        torch._C._get_accelerator = lambda: torch.device("cpu")
         return torch.device("cpu")
 
     @staticmethod
@@ -45,7 +48,11 @@ class StubHooks:
         import time
         time.sleep(0.02)                        # (so that the line's rounded ms_per_step resolves the step)
         v = trial_value(inp["ids"])
-        return v, None, None
+        ce = None
+        if want_ce:     # shaped like the library's convergence_error, including its Inf first entry of column 3 (proposed_algorithm.m:51)
+            ce = v[:, None, None] / torch.arange(1, imax + 1, dtype=torch.float64)[None, :, None] * torch.tensor([1.0, 2.0, 3.0], dtype=torch.float64)
+            ce[:, 0, 2] = float("inf")
+        return v, None, ce
 
     @staticmethod
     def nmse(S, inp):

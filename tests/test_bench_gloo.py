@@ -100,3 +100,59 @@ def test_eight_gpus_requested_on_a_smaller_node_exits_2_before_touching_the_gpu(
                        timeout=300, cwd=ROOT)
     assert r.returncode == 2, (r.returncode, r.stderr[-500:])
     assert "--gpus 8 requested" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_holds_the_last_timed_step_of_rank_0(tmp_path):
+    """--dump-outputs DIR: after the timed steps rank 0 writes what its last step returned (the stub's S: one float64 per trial,
+    a function of the global trial id; its convergence_error one file per column, finite), the line records it, and --steps sets
+    the number of timed steps."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from bench_stub import trial_value
+    batch = 5
+    for world in (1, 2):
+        d = tmp_path / ("w%d" % world)
+        j = _run(world, ["--steps", "4", "--warmup", "0", "--batch", str(batch), "--dump-outputs", str(d)])
+        assert j["steps"] == 4 and j["ms_per_step"] >= 20.0                  # (the stub's solve sleeps 20 ms)
+        assert j["dump_outputs"]["trials"] == "all"
+        assert j["dump_outputs"]["shapes"] == {"S": [batch], "convergence_error_V1": [batch, 100], "convergence_error_V2": [batch, 100],
+                                               "convergence_error_v": [batch, 99]}
+        S = np.load(d / "S.npy")
+        assert S.dtype == np.float64 and np.array_equal(S, trial_value(range(batch)).numpy())
+        c1, c2, cv = (np.load(d / ("convergence_error_%s.npy" % c)) for c in ("V1", "V2", "v"))
+        assert all(x.dtype == np.float64 and np.isfinite(x).all() for x in (c1, c2, cv))
+        it = np.arange(1, 101)
+        np.testing.assert_allclose(c1, S[:, None] / it, rtol=1e-15)
+        np.testing.assert_allclose(c2, 2 * S[:, None] / it, rtol=1e-15)
+        np.testing.assert_allclose(cv, 3 * S[:, None] / it[1:], rtol=1e-15)
+    d = tmp_path / "no_ce"
+    j = _run(1, ["--steps", "1", "--warmup", "0", "--batch", str(batch), "--no-ce", "--dump-outputs", str(d)])
+    assert sorted(os.listdir(d)) == ["S.npy"] and j["dump_outputs"]["shapes"] == {"S": [batch]}
+    j = _run(1, ["--sweep", "--small", "--sweep-trials", "3", "--batch", "2", "--dump-outputs", str(tmp_path / "sweep")])
+    m = np.load(tmp_path / "sweep" / "mean_nmse.npy")
+    assert m.dtype == np.float64 and m.shape == (11, 2)
+    np.testing.assert_allclose(m[:, 0], j["mean_nmse_proposed"], rtol=0, atol=1e-6)
+
+
+def test_dump_outputs_samples_the_same_trials_under_the_size_limit(tmp_path):
+    """Outputs larger than the limit: every array keeps the same seeded sample of trials, complex values become a trailing
+    (real, imag) axis of the matching float type, and the files stay below the limit - at BASELINE configs[1]'s shapes."""
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    from jstsp19_amd.solvers import empty_colmajor
+    g = torch.Generator().manual_seed(0)
+    S = empty_colmajor(256, 64, 512, torch.complex64, "cpu")
+    S.copy_(torch.randn(256, 64, 512, dtype=torch.complex64, generator=g))
+    Y = empty_colmajor(256, 64, 4096, torch.complex64, "cpu")
+    Y.copy_(torch.randn(256, 64, 4096, dtype=torch.complex64, generator=g))
+    ce = torch.randn(256, 100, 3, dtype=torch.float64, generator=g)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"S": S, "Y": Y, "convergence_error": ce})
+    again = bench.dump_outputs(str(tmp_path / "b"), {"S": S, "Y": Y, "convergence_error": ce, "unused": None})
+    idx = info["trials"]
+    assert idx == again["trials"] and idx == sorted(set(idx)) and 16 <= len(idx) < 256
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    s, y, c = (np.load(tmp_path / "a" / (n + ".npy")) for n in ("S", "Y", "convergence_error"))
+    assert s.dtype == y.dtype == np.float32 and c.dtype == np.float64 and sorted(os.listdir(tmp_path / "b")) == sorted(os.listdir(tmp_path / "a"))
+    assert np.array_equal(s[..., 0] + 1j * s[..., 1], S[idx].numpy()) and np.array_equal(y[..., 0] + 1j * y[..., 1], Y[idx].numpy())
+    assert np.array_equal(c, ce[idx].numpy())

@@ -136,3 +136,36 @@ def test_bench_two_ranks_real_library_on_one_gpu_over_gloo():
     assert s2["n_gpus"] == 2 and s2["scaling"] == "strong" and s1["n_gpus"] == 1
     assert s2["mean_nmse_proposed"] == pytest.approx(s1["mean_nmse_proposed"], abs=2e-6)
     assert s2["mean_nmse_angles"] == pytest.approx(s1["mean_nmse_angles"], abs=2e-6)
+
+
+def test_bench_dump_outputs_are_what_a_caller_receives(tmp_path):
+    """--dump-outputs at the reference-native shape: S, Y and the three columns of convergence_error of the last timed step, every
+    trial (they fit the limit), all finite, equal to a direct call of the library on the inputs bench.py builds for the same
+    trials.  The third column starts at iteration 2: its first entry is Inf by definition (proposed_algorithm.m:51, v starts at 0)."""
+    import numpy as np
+    import torch
+    from conftest import rel_err
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "2", "--warmup", "0", "--batch", "8",
+                        "--no-cpu-baseline", "--no-host-path", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dump_outputs"]["trials"] == "all"
+    names = ("S", "Y", "convergence_error_V1", "convergence_error_V2", "convergence_error_v")
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    S, Y, c1, c2, cv = (np.load(tmp_path / (n + ".npy")) for n in names)
+    assert S.dtype == Y.dtype == np.float32 and c1.dtype == c2.dtype == cv.dtype == np.float64
+    assert S.shape == (8, 32, 16, 2) and Y.shape == (8, 32, 140, 2) and c1.shape == c2.shape == (8, 100) and cv.shape == (8, 99)
+    assert all(np.isfinite(x).all() for x in (S, Y, c1, c2, cv))
+    sys.path.insert(0, ROOT)
+    import bench
+    from jstsp19_amd.system_model import SweepParams
+    dev = torch.device("cuda", 0)
+    inp = bench.make_inputs(SweepParams(Nt=4, Nr=32, L=4, T=35, Mr=4, snr_db=5.0), list(range(8)), dev, False)
+    So, Yo, ceo = bench.HipHooks.solve(inp, bench.IMAX, True)
+    torch.cuda.synchronize()
+    assert rel_err(S[..., 0] + 1j * S[..., 1], So.cpu().numpy()) < 1e-6
+    assert rel_err(Y[..., 0] + 1j * Y[..., 1], Yo.cpu().numpy()) < 1e-6
+    ceo = ceo.cpu().numpy()
+    assert np.isinf(ceo[:, 0, 2]).all() and np.isfinite(ceo[:, 1:, 2]).all()
+    assert rel_err(c1, ceo[:, :, 0]) < 1e-6 and rel_err(c2, ceo[:, :, 1]) < 1e-6 and rel_err(cv, ceo[:, 1:, 2]) < 1e-6
