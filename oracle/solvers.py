@@ -188,13 +188,16 @@ def proposed_algorithm_angles_literal(subY, Omega, indx_S, A, B, Imax, tau_Y, ta
 
 
 def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type_, indx_S=None,
-                       snapshots=None, want_ce=True):
+                       snapshots=None, want_ce=True, Bh=None, GB=None):
     """Structured restatement of proposed_algorithm.m:1-73 / proposed_algorithm_angles.m:1-85.
 
     Identities (SURVEY.md §0.5): ``K2*s = vec(A*S*B)``; ``K2'*k = vec(A'*K*B')``;
     ``R*v = vec((A'A)*V*(BB'))``; ``iK1*b = b ./ (Omega + 2 rho)``;
     ``K3*s = Omega_S .* S``; 'std' branch ``U\\(L\\k)`` = LS solution
     ``vec(pinv(A)*K*pinv(B))`` when K2 has full column rank.
+
+    ``Bh`` / ``GB``: optional precomputed ``B'`` and ``B*B'`` (complex128, as this function would form them) for trials that
+    share one pilot set - at BASELINE configs[4]'s full frame ``B*B'`` alone is 8.8 TFLOP.  The result is bit-identical.
     """
     subY = np.asarray(subY, dtype=np.complex128)
     Omega = np.asarray(Omega, dtype=np.float64)
@@ -212,10 +215,10 @@ def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type_, indx_S
     Xs = np.zeros((N, M), complex)                      # A*S*B of the previous iteration (:38)
     inv_d = 1.0 / (Omega + 2 * rho)                     # :14-20
     Ah = A.conj().T
-    Bh = B.conj().T
+    Bh = B.conj().T if Bh is None else Bh
     if type_ == "approximate":
         GA = Ah @ A                                     # R = K2'*K2 = (B B')^T (x) (A'A)  (:25)
-        GB = B @ Bh
+        GB = B @ Bh if GB is None else GB
         V = np.zeros((Gr, Gt), complex)
     else:
         pA = np.linalg.pinv(A)
@@ -257,10 +260,10 @@ def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type_, indx_S
 
 
 def proposed_algorithm_angles(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type_,
-                              greedy_nnz=None, snapshots=None, want_ce=True):
+                              greedy_nnz=None, snapshots=None, want_ce=True, Bh=None, GB=None):
     """Structured proposed_algorithm_angles.m:1-85."""
     return proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type_,
-                              indx_S=indx_S, snapshots=snapshots, want_ce=want_ce)
+                              indx_S=indx_S, snapshots=snapshots, want_ce=want_ce, Bh=Bh, GB=GB)
 
 
 # --------------------------------------------------------------------------- OMP

@@ -181,7 +181,7 @@ def test_cfg5_full_frame_against_the_float64_oracle():
     assert J.default_context(0).last_dictionary_block() == 256
     A_h = inp["A"].cpu().numpy().astype(np.complex128)
     B_h = B.cpu().numpy().astype(np.complex128)
-    with threadpool_limits(limits=min(32, psutil.cpu_count() or 1)):
+    with threadpool_limits(limits=min(16, psutil.cpu_count() or 1)):
         for t in (0, 9):
             So, Yo, _ = O.proposed_algorithm(_np(inp["subY"], t), _np(inp["Omega"], t, np.float64), A_h, B_h, Imax, float(ty[t]),
                                              float(tz[t]), float(rho[t]), "approximate", indx_S=inp["indx_S"][t].cpu().numpy(), want_ce=False)

@@ -56,16 +56,18 @@ def test_vamp_kron_float64_follows_the_oracle_as_far_as_float64_can_three_snr_po
             dev = np.array([rel_err(X[t], refs[t]) for t in range(nt)])
             spread = np.array([rel_err(V.vamp_literal(Ym[t].reshape(-1, order="F"), np.kron(Gb[t].T, A), 1.0, 100, nit=nit),
                                        refs[t].reshape(-1, order="F")) for t in range(nt)])
-            check_below("vamp64.kron.x.max.nit%d" % nit, dev.max(), {12: 1e-9}.get(nit, 10.0))
-            check_below("vamp64.kron.x.median.nit%d" % nit, np.median(dev), {12: 1e-9}.get(nit, 10.0))
-            check_below("vamp64.oracle_spread.max.nit%d" % nit, spread.max(), 10.0)
-            check_below("vamp64.oracle_spread.median.nit%d" % nit, np.median(spread), 10.0)
+            # (bounds: about 4 x the maxima over 16 trials per point, profiles/r06_measured_tolerances_vamp64.json - x max 2.1e-6 /
+            #  median 9.8e-8 at nit 50, 6.6e-2 / 2.8e-2 at 100; spread max 3e-12 at 12, 2.9e-6 at 50, 7.7e-2 / median 3.5e-2 at 100)
+            check_below("vamp64.kron.x.max.nit%d" % nit, dev.max(), {12: 1e-9, 50: 1e-5, 100: 0.26}[nit])
+            check_below("vamp64.kron.x.median.nit%d" % nit, np.median(dev), {12: 1e-9, 50: 5e-7, 100: 0.12}[nit])
+            check_below("vamp64.oracle_spread.max.nit%d" % nit, spread.max(), {12: 1e-11, 50: 1.2e-5, 100: 0.3}[nit])
+            check_below("vamp64.oracle_spread.median.nit%d" % nit, np.median(spread), {12: 1e-11, 50: 1.2e-5, 100: 0.14}[nit])
             # (both are draws of the same chaotic separation: compared as distributions over the trials, not trial by trial)
             assert np.median(dev) <= 10.0 * np.median(spread) + 1e-12, (db, nit, float(np.median(dev)), float(np.median(spread)))
             assert dev.max() <= 100.0 * spread.max() + 1e-12, (db, nit, float(dev.max()), float(spread.max()))
             if nit == 100:          # the estimation quality at the reference's operating point
                 e_dev = np.array([O.nmse_capped(X[t], Zb[t]) for t in range(nt)]); e_ref = np.array([O.nmse_capped(refs[t], Zb[t]) for t in range(nt)])
-                check_below("vamp64.kron.mean_nmse_diff.nit100", abs(e_dev.mean() - e_ref.mean()), 0.05)
+                check_below("vamp64.kron.mean_nmse_diff.nit100", abs(e_dev.mean() - e_ref.mean()), 0.01)    # (measured 2e-3)
 
 
 def test_vamp_dense_float64_is_the_reference_call_at_the_drivers_size():
@@ -87,7 +89,7 @@ def test_vamp_dense_float64_is_the_reference_call_at_the_drivers_size():
             lit = V.vamp_literal(y[t], Phi[t], 1.0, 100, nit=nit)
             fac = V.vamp_kron(Ym[t], A, Gb[t], 1.0, 100, nit=nit).reshape(-1, order="F")
             dev = max(dev, rel_err(x[t], lit)); spread = max(spread, rel_err(fac, lit))
-        check_below("vamp64.dense.x.nit%d" % nit, dev, {12: 1e-9}.get(nit, 1.0))
+        check_below("vamp64.dense.x.nit%d" % nit, dev, {12: 1e-9, 100: 0.15}[nit])          # (measured 3.8e-2 at nit 100)
         assert dev <= 100.0 * spread + 1e-12, (nit, dev, spread)
     # device arrays (JSTSP_DEVICE): the same bits as the host call
     xk = np.asarray(J.vamp_kron(Ym, A, Gb, 1.0, 100))

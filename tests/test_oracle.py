@@ -265,3 +265,22 @@ def test_vamp_m_greater_n_branch_literal_structured_and_golden():
         assert rel_err(V.vamp_dense(g["y"], g["A"], float(g["sigma"]), int(g["L"]), nit=int(nit)), g["x_dense"][k]) < 1e-9
         assert rel_err(V.vamp_kron(g["Y"], g["Af"], g["Gb"], float(g["sigma"]), int(g["Lk"]), nit=int(nit)), g["x_kron"][k]) < 1e-9
     assert np.max(np.abs(g["x_dense"][-1])) > 0.1                      # it estimates something
+
+
+def test_proposed_algorithm_with_precomputed_dictionary_gram_is_bit_identical():
+    """oracle.solvers.proposed_algorithm with B' and B*B' passed in (formed once for trials sharing a pilot set, as the configs[4]
+    fixture generator does) returns exactly what it returns when it forms them itself - both call forms, three outputs."""
+    rng = np.random.default_rng(5)
+    c = lambda *s: rng.standard_normal(s) + 1j * rng.standard_normal(s)
+    N, M, Gr, G2 = 8, 96, 8, 24
+    A, B = c(N, Gr) / np.sqrt(N), c(G2, M) / np.sqrt(G2)
+    Om = (rng.random((N, M)) < 0.4).astype(float)
+    subY = Om * (A @ c(Gr, G2) @ B * 0.1 + 0.05 * c(N, M))
+    Bh = B.conj().T
+    GB = B @ Bh
+    for idx in (None, rng.permutation(Gr * G2) + 1):
+        ref = O.proposed_algorithm(subY, Om, A, B, 7, 0.3, 0.01, 0.25, "approximate", indx_S=idx)
+        got = O.proposed_algorithm(subY, Om, A, B, 7, 0.3, 0.01, 0.25, "approximate", indx_S=idx, Bh=Bh, GB=GB)
+        assert np.any(ref[0] != 0)
+        for r, g in zip(ref, got):
+            assert np.array_equal(r, g)
