@@ -111,16 +111,7 @@ size_t jstsp_workspace_bytes(const jstsp_ctx *ctx);
  *                         0 never, 1 always - then every returned value is the cold one; jstsp_last_lanczos_mismatches)
  *   JSTSP_EIG128=0        general Jacobi kernel (basis in HBM) for Gram orders 65..128
  *   JSTSP_BJ_MASK=0       block Jacobi (orders above 128) without streams restricted to a subset of the compute units
- * (JSTSP_DEVICE=<id> is read by the MEX gateway, not by the library.)
- *
- * Experiments build.  The opt-in paths that rounds 2-5 measured and dropped, and every switch with a setting that leaves the
- * accuracy statement, are NOT in the shipped library since round 6: their settings are compile-time constants there
- * (csrc/common.h, JSTSP_XP) and the variables are not read.  `JSTSP_EXPERIMENTS=1 python jstsp19_amd/build.py` builds
- * libjstsp_mi355x_xp.so (loaded by the Python binding under JSTSP_EXPERIMENTS_LIB=1; tools/ only, never a reported number), in
- * which they are read again; HISTORY.md has what each one measured:
- *   JSTSP_GRAM_REFINE JSTSP_RV_REFRESH JSTSP_RV_ALWAYS JSTSP_RV_COMP JSTSP_GRAD_HEAD JSTSP_SVT_SKIP JSTSP_PASS_ACC JSTSP_INV2
- *   JSTSP_HGEMM_MAP JSTSP_HGEMM_PAIR JSTSP_OMP_REG JSTSP_OMP_GRAM JSTSP_SADMM_FUSE JSTSP_SADMM_OVERLAP JSTSP_M3_MINK JSTSP_HOST_TRACE JSTSP_BJ_TRACE
- * (and JSTSP_FUSED_DBG in a -DJSTSP_FUSED_DBG_BUILD build of fused.hip: timing experiments, results wrong). */
+ * (JSTSP_DEVICE=<id> is read by the MEX gateway, not by the library.) */
 
 /* ---- kernel-level entry points (the north-star correlation / synthesis) ------------ */
 
@@ -177,8 +168,8 @@ int jstsp_synthesize_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                          jstsp_c32 *out, int memspace);
 
 /* Res = A' * Tc - RV  and  P1 = GA * Res   (Gr x G2): the 64-term products of the gradient step - the second factor of
- * `K2'*k - R*v` and the first factor of `R*res`, proposed_algorithm.m:47-48 - exactly as the solver runs them between two
- * passes over the dictionary (N = Gr = 64, G2 a multiple of 64; else JSTSP_E_UNSUPPORTED).  These sums live in the space of
+ * `K2'*k - R*v` and the first factor of `R*res`, proposed_algorithm.m:47-48 - in one launch on the f16 matrix pipe (the solver
+ * itself forms them as fp32-MFMA products; N = Gr = 64, G2 a multiple of 64; else JSTSP_E_UNSUPPORTED).  These sums live in the space of
  * the iterate v, where the iteration forgets nothing, so they are formed to fp32-OUTPUT accuracy: operands split three ways
  * into f16 (33 bits: the fp32 values exactly), exact f16 x f16 products, float64 final sums.
  * Tc: N x G2 x batch; A: N x Gr; GA: Gr x Gr Hermitian (strides 0 = shared); RV: Gr x G2 x batch or NULL. */

@@ -184,12 +184,8 @@ template <int NT>
 __global__ __launch_bounds__(NT) void step_v_kernel(int g, const float2 *Res, const float2 *RRes,
                                                     float2 *V, float2 *S, const int32_t *rank,
                                                     int cnt, const TrialParams *prm, double *ce3,
-                                                    int Imax, int it, float2 *RV, float2 *Vlo, float2 *RVlo, int vlo_reset)
+                                                    int Imax, int it, float2 *RV)
 {
-    // Vlo / RVlo != NULL: v and R v are carried as two floats each (hi in V / RV): the sums of alpha res and alpha R res are
-    // accumulated to about 48 bits (in float64 here, split again on the way out), so that R v stays R times THE v that was
-    // accumulated instead of drifting from it by one fp32 rounding of each per iteration.  s = soft(v) sees the leading part.
-    // vlo_reset: R v has just been recomputed from the leading part of v - the stored low-order part of v is dropped.
     __shared__ double sh[NT / 64];
     const int t = blockIdx.x;
     const long long base = (long long)t * g;
@@ -222,68 +218,34 @@ __global__ __launch_bounds__(NT) void step_v_kernel(int g, const float2 *Res, co
     const float ax = (float)(num * den_re / dd);
     const float ay = (float)(-num * den_im / dd);
     const float thr = prm[t].tauS_rho;
-    if (!Vlo) {
-        for (int i0 = threadIdx.x; i0 < g; i0 += NT * UN) {
-            float2 r[UN], v[UN], rr[UN], rv[UN];
-            int rk[UN];
+    for (int i0 = threadIdx.x; i0 < g; i0 += NT * UN) {
+        float2 r[UN], v[UN], rr[UN], rv[UN];
+        int rk[UN];
 #pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = min(i0 + u * NT, g - 1);
-                r[u] = Res[base + i]; v[u] = V[base + i];
-                if (RV) { rr[u] = RRes[base + i]; rv[u] = RV[base + i]; }
-                rk[u] = rank ? rank[base + i] : 0;
-            }
+        for (int u = 0; u < UN; ++u) {
+            const int i = min(i0 + u * NT, g - 1);
+            r[u] = Res[base + i]; v[u] = V[base + i];
+            if (RV) { rr[u] = RRes[base + i]; rv[u] = RV[base + i]; }
+            rk[u] = rank ? rank[base + i] : 0;
+        }
 #pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const int i = i0 + u * NT;
-                if (i >= g) break;
-                float2 vn = v[u];
-                vn.x += ax * r[u].x - ay * r[u].y;
-                vn.y += ax * r[u].y + ay * r[u].x;
-                V[base + i] = vn;
-                if (RV) {       // R v_new = R v + alpha R res: carried between the periodic recomputations of R v (proposed.hip)
-                    float2 rn = rv[u];
-                    rn.x += ax * rr[u].x - ay * rr[u].y;
-                    rn.y += ax * rr[u].y + ay * rr[u].x;
-                    RV[base + i] = rn;
-                }
-                float2 sv = make_float2(soft1(vn.x, thr), soft1(vn.y, thr));
-                if (rank && rk[u] >= cnt) sv = make_float2(0.f, 0.f);
-                S[base + i] = sv;
+        for (int u = 0; u < UN; ++u) {
+            const int i = i0 + u * NT;
+            if (i >= g) break;
+            float2 vn = v[u];
+            vn.x += ax * r[u].x - ay * r[u].y;
+            vn.y += ax * r[u].y + ay * r[u].x;
+            V[base + i] = vn;
+            if (RV) {       // R v_new = R v + alpha R res: carried between the periodic recomputations of R v (proposed.hip)
+                float2 rn = rv[u];
+                rn.x += ax * rr[u].x - ay * rr[u].y;
+                rn.y += ax * rr[u].y + ay * rr[u].x;
+                RV[base + i] = rn;
             }
+            float2 sv = make_float2(soft1(vn.x, thr), soft1(vn.y, thr));
+            if (rank && rk[u] >= cnt) sv = make_float2(0.f, 0.f);
+            S[base + i] = sv;
         }
-    } else
-    for (int i = threadIdx.x; i < g; i += NT) {
-        const float2 r = Res[base + i];
-        float2 v = V[base + i];
-        if (Vlo) {
-            const float2 vl = vlo_reset ? make_float2(0.f, 0.f) : Vlo[base + i];
-            const double sx = ((double)v.x + (double)vl.x) + ((double)ax * r.x - (double)ay * r.y);
-            const double sy = ((double)v.y + (double)vl.y) + ((double)ax * r.y + (double)ay * r.x);
-            v = make_float2((float)sx, (float)sy);
-            Vlo[base + i] = make_float2((float)(sx - (double)v.x), (float)(sy - (double)v.y));
-            const float2 rr = RRes[base + i], rv = RV[base + i], rl = RVlo[base + i];
-            const double tx = ((double)rv.x + (double)rl.x) + ((double)ax * rr.x - (double)ay * rr.y);
-            const double ty = ((double)rv.y + (double)rl.y) + ((double)ax * rr.y + (double)ay * rr.x);
-            const float2 rn = make_float2((float)tx, (float)ty);
-            RV[base + i] = rn;
-            RVlo[base + i] = make_float2((float)(tx - (double)rn.x), (float)(ty - (double)rn.y));
-            V[base + i] = v;
-        } else {
-        v.x += ax * r.x - ay * r.y;
-        v.y += ax * r.y + ay * r.x;
-        V[base + i] = v;
-        if (RV) {       // R v_new = R v + alpha R res: carried between the periodic recomputations of R v (proposed.hip)
-            const float2 rr = RRes[base + i];
-            float2 rv = RV[base + i];
-            rv.x += ax * rr.x - ay * rr.y;
-            rv.y += ax * rr.y + ay * rr.x;
-            RV[base + i] = rv;
-        }
-        }
-        float2 s = make_float2(soft1(v.x, thr), soft1(v.y, thr));
-        if (rank && rank[base + i] >= cnt) s = make_float2(0.f, 0.f);
-        S[base + i] = s;
     }
     if (ce3 && threadIdx.x == 0) {
         // |v - v_prev|^2 = |alpha|^2 |res|^2 ; 0-divide at i = 1 gives Inf (NaN if res = 0) as in :51
@@ -370,19 +332,19 @@ int launch_update_c(jstsp_ctx *ctx, long long nm, int batch, const float2 *X, co
 }
 int launch_step_v(jstsp_ctx *ctx, int g, int batch, const float2 *Res, const float2 *RRes, float2 *V,
                   float2 *S, const int32_t *rank, int cnt, const TrialParams *prm, double *ce3,
-                  int Imax, int it, float2 *RV, int waves8, float2 *Vlo, float2 *RVlo, int vlo_reset)
+                  int Imax, int it, float2 *RV, int waves8)
 {
     // waves8 (the caller runs an eigen-decomposition beside this kernel): eight waves per problem - a workgroup that fits on a
     // CU beside a resident Jacobi, 16 waves x 106 registers do not; alone, the 16-wave form is 25 % faster
     if (g >= 8192 && waves8)
         hipLaunchKernelGGL(step_v_kernel<512>, dim3(batch), dim3(512), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV, Vlo, RVlo, vlo_reset);
+                           cnt, prm, ce3, Imax, it, RV);
     else if (g >= 8192)
         hipLaunchKernelGGL(step_v_kernel<1024>, dim3(batch), dim3(1024), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV, Vlo, RVlo, vlo_reset);
+                           cnt, prm, ce3, Imax, it, RV);
     else
         hipLaunchKernelGGL(step_v_kernel<256>, dim3(batch), dim3(256), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV, Vlo, RVlo, vlo_reset);
+                           cnt, prm, ce3, Imax, it, RV);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

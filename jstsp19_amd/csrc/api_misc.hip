@@ -696,7 +696,7 @@ int jstsp_mc_admm_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32
 }  // extern "C"
 
 // Res = A' * Tc - RV,  P1 = GA * Res   (Gr x G2 per problem; N = Gr = 64, G2 a multiple of 64): the gradient step's 64-term
-// products `K2'*k - R*v` (second factor) and the first factor of `R*res` (proposed_algorithm.m:47-48) as the solver runs them
+// products `K2'*k - R*v` (second factor) and the first factor of `R*res` (proposed_algorithm.m:47-48) in one launch
 // (csrc/hsmall.hip: three-way split-f16 operands, float64 final sums).  Tc: N x G2 x batch; A: N x Gr (strideA 0 = shared); GA: Gr x Gr
 // Hermitian (strideG 0 = shared); RV: Gr x G2 x batch or NULL.
 extern "C" int jstsp_gradient_head_c32(jstsp_ctx *ctx, int N, int Gr, int G2, int batch, const jstsp_c32 *Tc_, const jstsp_c32 *A_,
@@ -723,8 +723,7 @@ extern "C" int jstsp_gradient_head_c32(jstsp_ctx *ctx, int N, int Gr, int G2, in
     if (RV_) JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(RV_), batch * g, memspace, &RV));
     float2 *Res = ctx->arena.get<float2>(batch * g), *P1 = ctx->arena.get<float2>(batch * g);
     JSTSP_REQUIRE(Res && P1, JSTSP_E_NOMEM, "gradient_head: workspace exhausted");
-    JSTSP_TRY(launch_grad_head(ctx, G2, batch, Tc, (long long)ng, 0, 1, nullptr, nullptr, 0, A, strideA, GA, strideG, RV, nullptr, Res, P1,
-                               nullptr));
+    JSTSP_TRY(launch_grad_head(ctx, G2, batch, Tc, (long long)ng, 0, 1, nullptr, nullptr, 0, A, strideA, GA, strideG, RV, nullptr, Res, P1, nullptr));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Res_out), Res, batch * g, memspace));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(P1_out), P1, batch * g, memspace));
     if (memspace == JSTSP_HOST) JSTSP_HIP(hipStreamSynchronize(ctx->stream));

@@ -364,11 +364,6 @@ __global__ __launch_bounds__(256) void cgemm_kernel(GemmDesc d, int tiles_m, int
                         const float2 dv = Dp[gi + (long long)gj * d.ldd];
                         o.x += d.beta * dv.x;
                         o.y += d.beta * dv.y;
-                        if (d.D_lo) {       // (after the leading part: o - D is where the cancellation happens)
-                            const float2 dl = d.D_lo[(long long)t * d.sDt + gi + (long long)gj * d.ldd];
-                            o.x += d.beta * dl.x;
-                            o.y += d.beta * dl.y;
-                        }
                     }
                     const long long ix = (long long)t * d.sCt + gi + (long long)gj * d.ldc;
                     if (M64 && EPI == EPI_NONE && d.C_lo)       // what the fp32 result leaves of the float64 sum
@@ -500,8 +495,7 @@ int launch_cgemm(jstsp_ctx *ctx, const GemmDesc &d, int tag)
     JSTSP_REQUIRE(!d.C_lo || (variant == 2 && d.alpha == 1.f && !d.D), JSTSP_E_ARG, "cgemm: C_lo needs the fp64-master variant, alpha = 1, no D");
     const int bn = variant == 1 ? 128 : 64;
     // 3M where it pays and was validated: the dominant contractions, the Grams, and other products of 256 terms or more
-    static const int m3_mink = [] { const char *e = xp_getenv("JSTSP_M3_MINK"); return e ? atoi(e) : 256; }();
-    const bool m3 = tag == GEMM_CORRELATE || tag == GEMM_SYNTH || tag == GEMM_GRAM || (tag == GEMM_MISC && kper >= m3_mink);
+    const bool m3 = tag == GEMM_CORRELATE || tag == GEMM_SYNTH || tag == GEMM_GRAM || (tag == GEMM_MISC && kper >= 256);
     const int tiles_n = (d.n + bn - 1) / bn;
     const long long groups = (d.batch + 7) / 8;
     const long long grid = groups * 8 * tiles_m * tiles_n * d.splitk;

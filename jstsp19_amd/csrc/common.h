@@ -59,42 +59,20 @@ struct DeviceScope {
 // are diagnostic / opt-in settings, parsed ONCE at the entry of every API call (JSTSP_ENTER) into this struct - no switch is
 // latched in a static, none is read anywhere else - so a test can change them between two calls of one process and a call
 // sees one consistent setting from its first launch to its last.
-// Round 6: the opt-in paths that were measured and dropped (HISTORY.md), and every switch whose non-default value leaves the accuracy
-// statement of include/jstsp.h, exist only in a -DJSTSP_EXPERIMENTS build (JSTSP_EXPERIMENTS=1 python jstsp19_amd/build.py; tools/
-// only).  In the shipped library their settings are compile-time constants: the environment variable is not read, the branch is dead.
-#ifdef JSTSP_EXPERIMENTS
-#define JSTSP_XP int
-inline const char *xp_getenv(const char *name) { return getenv(name); }
-#else
-#define JSTSP_XP static constexpr int
-inline const char *xp_getenv(const char *) { return nullptr; }
-#endif
 struct Tuning {
     int h2 = 1;             // JSTSP_H2: 0 strict complex-fp32 MFMA everywhere, 1 split-f16 MFMA for big contractions, 2 always
     int fused = 1;          // JSTSP_FUSED: 0 three-kernel ADMM iteration instead of the fused pass
     int fused_parts = 0;    // JSTSP_FUSED_PARTS: column ranges per problem in the pass (0: chosen from M)
     int fused_kback = 4;    // JSTSP_FUSED_KBACK: headroom bits of the predicted k scale (test hook: negative forces the re-solve)
     int toeplitz = 2;       // JSTSP_TOEPLITZ: 0 dictionary taken as unstructured, 1 compact image only, 2 + window kernel (block 64)
-    JSTSP_XP rv_refresh = 4;     // (experiments build) JSTSP_RV_REFRESH: R v recomputed from v every this many iterations
     int overlap = -1;       // JSTSP_OVERLAP: side streams between the kernels of an iteration (-1: on with the fused pass)
-    JSTSP_XP svt_skip = 0;       // (experiments build) JSTSP_SVT_SKIP: 1 trials whose threshold is below fp32 resolution skip the eigen-decomposition (opt-in)
     int lanczos = 1;        // JSTSP_LANCZOS: 0 Householder + Sturm instead of Lanczos for the convergence_error norms
     int lanczos_warm = 1;   // JSTSP_LANCZOS_WARM: 0 every lambda_max of an ADMM loop by the cold n-step Lanczos run (rounds 2-4)
     int lanczos_verify = 32; // JSTSP_LANCZOS_VERIFY: every this many calls a warm-started lambda_max is checked against the cold run (0: never, 1: always)
     int eig128 = 1;         // JSTSP_EIG128: 0 general Jacobi kernel for Gram orders 65..128
-    JSTSP_XP omp_gram = 1;       // (experiments build) JSTSP_OMP_GRAM: 0 measurement-space OMP on a Kronecker dictionary
-    JSTSP_XP grad_head = 0;      // (experiments build) JSTSP_GRAD_HEAD: bit 0 - Res / P1 of the gradient step, bit 1 - the first factor of a recomputed R v, on the
-                            // f16 pipe in one launch (hsmall.hip) instead of fp32-MFMA products; measured: more accurate products,
-                            // +2 % channel-estimates/s, but WORSE parity (rms |dNMSE| 2.18e-7 against 1.73e-7, a +5e-8 bias): off
-    JSTSP_XP rv_comp = 0;        // (experiments build) JSTSP_RV_COMP: 1 v and R v carried as two floats each (compensated accumulation of alpha res / alpha R res)
-    JSTSP_XP rv_always = 0;      // (experiments build) JSTSP_RV_ALWAYS: R v recomputed from v in each of the first n iterations (then every JSTSP_RV_REFRESH-th)
-    JSTSP_XP inv_two_float = 1;  // (experiments build) JSTSP_INV2: 0 the pass reads 1 / (Omega + 2 rho) as one rounded float per entry (rounds 1-4)
-    JSTSP_XP pass_acc = 1;       // (experiments build; applies to the window pass fused_pass64_kernel only - fused_pass_kernel always sums per tile first) JSTSP_PASS_ACC: 0 products of K B^H straight into the window pass's running sums (rounds 2-4), 1 per-tile block sums first (fused.hip)
     int host_compact = 1;   // JSTSP_HOST_COMPACT: 0 a JSTSP_HOST dictionary is uploaded whole (no host-side block-Toeplitz test / compaction)
     int host_pipeline = 1;  // JSTSP_HOST_PIPELINE: 0 a JSTSP_HOST solve as ONE staged call (no overlap of the copies with the solve)
-    JSTSP_XP gram_refine = 1;    // (experiments build) JSTSP_GRAM_REFINE: 0 the dictionary Grams G_A, G_B as plain fp32 products, no low-order parts in R*v
     int bj_mask = 1;        // JSTSP_BJ_MASK: 0 the block Jacobi above order 128 without compute-unit masks (its sub-problems then compete with the panel products for units)
-    JSTSP_XP bj_trace = 0;       // (experiments build) JSTSP_BJ_TRACE: 1 print the block Jacobi's convergence per sweep (stderr)
 };
 const Tuning &tune();       // the calling thread's setting, as parsed by the API call in progress
 void load_tuning();
@@ -293,7 +271,6 @@ struct GemmDesc {
     // it (C_lo, same layout as C; alpha = 1, no D): C + C_lo carries the product to about 1e-9 relative
     int force_m64;
     float2 *C_lo;
-    const float2 *D_lo;                     // low-order part of D (same layout): C = alpha acc + beta (D + D_lo); NULL = none
     int herm_upper;                         // the product is Hermitian (a Gram): tiles entirely below the diagonal are skipped, the caller
                                             // mirrors them (hermitian_fill_lower)
     int sa_mode;                            // EPI_SADMM (below)
@@ -364,9 +341,8 @@ struct HGemmDesc {
 int hermitian_fill_lower(jstsp_ctx *ctx, float2 *G, long long sGt, int n, int count);
 // Gram partials of a rows x cols matrix, rows <= 64 (same layout as the GEMM_GRAM split-K output):
 // Gpart[(t*nsplit + s)*rows*rows + i + rows*j];  amax[t] bounds max(|re|,|im|) of Z[t]
-// skip_prm != nullptr: problems with prm[t].tauY_rho <= 2^-27 amax[t] are skipped (see jacobi2_kernel)
 int launch_hgram(jstsp_ctx *ctx, const float2 *Z, long long sZt, int rows, int cols, int count, int nsplit,
-                 const uint32_t *amax, float2 *Gpart, const TrialParams *skip_prm = nullptr, const float2 *Z2 = nullptr,
+                 const uint32_t *amax, float2 *Gpart, const float2 *Z2 = nullptr,
                  const TrialParams *zprm = nullptr,      // Z2: Gram of Z - zprm[t].irho * Z2 (same layout as Z)
                  bool norm_only = false);                // the Gram's only use is its lambda_max in convergence_error: high f16 plane only
 // G_x = X X^H, G_v = V1 V1^H, G_z = (X - V1/rho)(X - V1/rho)^H in one pass over X and V1 (rows <= 64)
@@ -403,7 +379,7 @@ int launch_eig_large(jstsp_ctx *ctx, int mode, int n, int batch, const float2 *G
 // Fast paths (eig2.hip): warm-started block Jacobi for n <= 64; tridiagonalisation + Sturm for lambda_max.
 int launch_eig_fast(jstsp_ctx *ctx, int mode, int n, int batch, const float2 *Gpart, long long sGt, int nsplit,
                     long long sGs, const TrialParams *prm, const float *tau, float2 *Q, float *lam_out,
-                    float2 *Uwarm, int warm, const uint32_t *skip_amax = nullptr);
+                    float2 *Uwarm, int warm);
 // Orders 65..128 (eig3.hip): G in LDS, eigenvector basis in registers as a systolic array; SVT projector only.
 int launch_eig128(jstsp_ctx *ctx, int n, int batch, const float2 *Gpart, long long sGt, int nsplit, long long sGs,
                   const TrialParams *prm, const float *tau, float2 *Q, float2 *Uwarm = nullptr, int warm = 0,
@@ -431,8 +407,7 @@ int launch_update_c(jstsp_ctx *ctx, long long nm, int batch, const float2 *X, co
                     float2 *V2, float2 *C, const TrialParams *prm);
 int launch_step_v(jstsp_ctx *ctx, int g, int batch, const float2 *Res, const float2 *RRes,
                   float2 *V, float2 *S, const int32_t *rank, int cnt, const TrialParams *prm,
-                  double *ce3, int Imax, int it, float2 *RV = nullptr, int waves8 = 0,      // RV != nullptr: RV += alpha * RRes as well
-                  float2 *Vlo = nullptr, float2 *RVlo = nullptr, int vlo_reset = 0);         // low-order parts: v and R v as two floats (admm.hip)
+                  double *ce3, int Imax, int it, float2 *RV = nullptr, int waves8 = 0);     // RV != nullptr: RV += alpha * RRes as well
 int launch_soft(jstsp_ctx *ctx, int g, int batch, const float2 *V, float2 *S, const int32_t *rank,
                 int cnt, const TrialParams *prm);
 int launch_inv_d(jstsp_ctx *ctx, long long nm, int batch, const float *Omega, float scale2rho,

@@ -433,7 +433,6 @@ int launch_eig_large(jstsp_ctx *ctx, int mode, int n, int batch, const float2 *G
         double worst = 0.0;
         for (int t = 0; t < batch; ++t) worst = std::max(worst, hs[2 * t + 1] > 0 ? std::sqrt(hs[2 * t] / hs[2 * t + 1]) : 0.0);
         last_worst = worst;
-        if (tune().bj_trace) fprintf(stderr, "block Jacobi order %d (%d blocks): sweep %d off/diag %.3e\n", n, nb, sweep, worst);
         // (orders above 1024 do not wait for the stagnation: below 1e-5 the next sweep would only meet the noise floor)
         const bool early_restart = np > 1024 && vecs && !restarted && worst < 1e-5;
         if (worst < 3e-8 * std::sqrt((double)np) || (prev >= 0 && worst > 0.5 * prev && worst < 1e-5) || early_restart) {

@@ -379,11 +379,9 @@ __global__ __launch_bounds__(256) void reduce_parts_delta_kernel(const float4 *P
     out[(long long)t * n4 + i] = make_float4((float)ax, (float)ay, (float)az, (float)aw);
 }
 
-// DBG != 0 (timing experiments only, results are wrong; not instantiated by default): 1 skips the phase-A products,
-// 2 the element-wise loads / stores, 4 the phase-B products, 8 the tile refill
 // YIN: Y = (I - Q) Z of the next iteration is formed here (Z from d.Zin, fragments of I - Q from d.Wqp) instead of read
 // TOEP: the tile comes from the compact image of a block-Toeplitz dictionary (above) instead of the full tile image
-template <int GB, int DBG, bool YIN, bool TOEP>
+template <int GB, bool YIN, bool TOEP>
 __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
 {
     constexpr int G2 = 128 * GB;
@@ -524,49 +522,47 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
         // (k-step, m-block) are read from LDS before the products of the current one are issued
         f32x4 ar[2], ai[2];
         ar[0] = ar[1] = ai[0] = ai[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (!(DBG & 1)) {
-            u32x4 wr[2][4], bfb[2][4];
-            // ONE running offset, advanced opaquely per k-step: with constant offsets the compiler materialises (and spills) an
-            // address per (k-step, plane) outside the tile loop
-            uint32_t ao = aoff;
-            asm volatile("" : "+v"(ao));
+        u32x4 wr[2][4], bfb[2][4];
+        // ONE running offset, advanced opaquely per k-step: with constant offsets the compiler materialises (and spills) an
+        // address per (k-step, plane) outside the tile loop
+        uint32_t ao = aoff;
+        asm volatile("" : "+v"(ao));
 #pragma unroll
-            for (int p = 0; p < 4; ++p) wr[0][p] = ldg<u32x4>(ast, ao + p * 1024);
-            const int goff0 = (kh * (G2 / 2) + 8 * q) * 8 + (c16 & 3) * 16;      // micro-block (m quad, g octet), row m & 3
-            const unsigned char *arow = tile + (c16 >> 2) * ROWB + goff0;         // + p 8 ROWB + mb 4 ROWB + ks 256
+        for (int p = 0; p < 4; ++p) wr[0][p] = ldg<u32x4>(ast, ao + p * 1024);
+        const int goff0 = (kh * (G2 / 2) + 8 * q) * 8 + (c16 & 3) * 16;      // micro-block (m quad, g octet), row m & 3
+        const unsigned char *arow = tile + (c16 >> 2) * ROWB + goff0;         // + p 8 ROWB + mb 4 ROWB + ks 256
 #pragma unroll
-            for (int p = 0; p < 4; ++p) bfb[0][p] = *reinterpret_cast<const u32x4 *>(arow + p * 8 * ROWB);
+        for (int p = 0; p < 4; ++p) bfb[0][p] = *reinterpret_cast<const u32x4 *>(arow + p * 8 * ROWB);
 #pragma unroll
-            for (int st = 0; st < 2 * KSH; ++st) {
-                const int ks = st >> 1, mb = st & 1;
-                if (mb == 0 && ks + 1 < KSH) {
-                    ao += 16384;
-                    asm volatile("" : "+v"(ao));
+        for (int st = 0; st < 2 * KSH; ++st) {
+            const int ks = st >> 1, mb = st & 1;
+            if (mb == 0 && ks + 1 < KSH) {
+                ao += 16384;
+                asm volatile("" : "+v"(ao));
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) wr[(ks + 1) & 1][p] = ldg<u32x4>(ast, ao + p * 1024);
-                }
-                if (!YIN && st + 1 < 2 * KSH) {
-                    const int ks1 = (st + 1) >> 1, mb1 = (st + 1) & 1;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        bfb[(st + 1) & 1][p] = *reinterpret_cast<const u32x4 *>(arow + (p * 8 + 4 * mb1) * ROWB + ks1 * 256);
-                }
-                if (YIN && st > 0) {        // (no register room for the second fragment set next to the carried Y)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        bfb[0][p] = *reinterpret_cast<const u32x4 *>(arow + (p * 8 + 4 * mb) * ROWB + ks * 256);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const u32x4 *wf = wr[ks & 1], *bf = bfb[YIN ? 0 : (st & 1)];
-                const u32x4 nwi_h = negu(wf[2]), nwi_l = negu(wf[3]);
-                // re += Br Wr - Bi Wi ; im += Br Wi + Bi Wr   (h h + h l + l h each)
-                ar[mb] = mma(bf[0], wf[0], ar[mb]); ai[mb] = mma(bf[0], wf[2], ai[mb]);
-                ar[mb] = mma(bf[0], wf[1], ar[mb]); ai[mb] = mma(bf[0], wf[3], ai[mb]);
-                ar[mb] = mma(bf[1], wf[0], ar[mb]); ai[mb] = mma(bf[1], wf[2], ai[mb]);
-                ar[mb] = mma(bf[2], nwi_h, ar[mb]); ai[mb] = mma(bf[2], wf[0], ai[mb]);
-                ar[mb] = mma(bf[2], nwi_l, ar[mb]); ai[mb] = mma(bf[2], wf[1], ai[mb]);
-                ar[mb] = mma(bf[3], nwi_h, ar[mb]); ai[mb] = mma(bf[3], wf[0], ai[mb]);
+                for (int p = 0; p < 4; ++p) wr[(ks + 1) & 1][p] = ldg<u32x4>(ast, ao + p * 1024);
             }
+            if (!YIN && st + 1 < 2 * KSH) {
+                const int ks1 = (st + 1) >> 1, mb1 = (st + 1) & 1;
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    bfb[(st + 1) & 1][p] = *reinterpret_cast<const u32x4 *>(arow + (p * 8 + 4 * mb1) * ROWB + ks1 * 256);
+            }
+            if (YIN && st > 0) {        // (no register room for the second fragment set next to the carried Y)
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    bfb[0][p] = *reinterpret_cast<const u32x4 *>(arow + (p * 8 + 4 * mb) * ROWB + ks * 256);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const u32x4 *wf = wr[ks & 1], *bf = bfb[YIN ? 0 : (st & 1)];
+            const u32x4 nwi_h = negu(wf[2]), nwi_l = negu(wf[3]);
+            // re += Br Wr - Bi Wi ; im += Br Wi + Bi Wr   (h h + h l + l h each)
+            ar[mb] = mma(bf[0], wf[0], ar[mb]); ai[mb] = mma(bf[0], wf[2], ai[mb]);
+            ar[mb] = mma(bf[0], wf[1], ar[mb]); ai[mb] = mma(bf[0], wf[3], ai[mb]);
+            ar[mb] = mma(bf[1], wf[0], ar[mb]); ai[mb] = mma(bf[1], wf[2], ai[mb]);
+            ar[mb] = mma(bf[2], nwi_h, ar[mb]); ai[mb] = mma(bf[2], wf[0], ai[mb]);
+            ar[mb] = mma(bf[2], nwi_l, ar[mb]); ai[mb] = mma(bf[2], wf[1], ai[mb]);
+            ar[mb] = mma(bf[3], nwi_h, ar[mb]); ai[mb] = mma(bf[3], wf[0], ai[mb]);
         }
         // the two g-halves meet: wave (nb, kh) keeps m-block kh and hands m-block 1 - kh to wave (nb, 1 - kh)
         {
@@ -582,7 +578,6 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const uint32_t ix = ebase + 512u * (uint32_t)(m0 + s);
-            if (DBG & 2) { ex[s] = ev1[s] = ev2[s] = esy[s] = ey[s] = make_float2(1.f, 1.f); eid[s] = 1.f; continue; }
             ex[s] = ldg_nt2(Xt, ix); ev1[s] = ldg_nt2(V1t, ix); ev2[s] = ldg_nt2(V2t, ix);
             esy[s] = ldg_nt2(sYt, ix); eid[s] = ldg_nt<float>(iDt, ix >> 1);
             if (!YIN) ey[s] = ldg_nt2(Yt, ix);
@@ -608,7 +603,7 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
                                          admm_x2(prm, ev1[s].y, ey[s].y, esy[s].y, v2.y, xs.y, rh, rl));
             const float2 kk = make_float2(admm_k(prm, x.x, v2.x), admm_k(prm, x.y, v2.y));        // (:43)
             const float2 v1 = make_float2(admm_v1(prm, ev1[s].x, ey[s].x, x.x), admm_v1(prm, ev1[s].y, ey[s].y, x.y));   // (:64)
-            if (!(DBG & 2)) { stg_nt2(V2t, ix, v2); stg_nt2(Xt, ix, x); stg_nt2(V1t, ix, v1); }
+            stg_nt2(V2t, ix, v2); stg_nt2(Xt, ix, x); stg_nt2(V1t, ix, v1);
             const float2 zn = make_float2(admm_z(prm, x.x, v1.x), admm_z(prm, x.y, v1.y));
             if (YIN) stg_nt2(Zot, ix, zn);
             if (Yot) stg(Yot, ix, ey[s]);
@@ -633,69 +628,63 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
         // wave reads its rows g in phase B, so block gb is overwritten as soon as its products are issued
         const uint32_t noff = boff + (uint32_t)min(i + 1, tpw - 1) * tile_b;         // (< 4 GiB of tiles per problem and range)
         u32x4 rf[2][4];
-        if (!(DBG & 8)) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { rf[0][c] = FUSED_BLD(noff, 0, c); if (GB > 1) rf[1][c] = FUSED_BLD(noff, (GB > 1 ? 1 : 0), c); }
-        }
+        for (int c = 0; c < 4; ++c) { rf[0][c] = FUSED_BLD(noff, 0, c); if (GB > 1) rf[1][c] = FUSED_BLD(noff, (GB > 1 ? 1 : 0), c); }
         // ================= phase B: P^T += conj(B)(g, tile) k^T(tile, :), this wave: g in [16 GB w, 16 GB (w + 1))
         // A operand: lane = g, registers = 8 of the 32 columns m - two transposing reads (ds_read_b64_tr_b16) of the
         // micro-block image: lane i' of a 16-lane group points at the four halves g = g0 + 4 (i' & 3) .. + 3 of row i' >> 2 and
         // lane i receives column g0 + i of the four rows.  
-        if (!(DBG & 4)) {
-            typedef short s16x4 __attribute__((ext_vector_type(4)));
-            typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-            const uint32_t tr0 = (uint32_t)(uintptr_t)(tile - lds) + q * ROWB + (2 * GB * w + ((c16 >> 1) & 1)) * 64 + (c16 >> 2) * 16 +
-                                 (c16 & 1) * 8;
-            auto *lbase = (__attribute__((address_space(3))) unsigned char *)lds;
+        typedef short s16x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+        const uint32_t tr0 = (uint32_t)(uintptr_t)(tile - lds) + q * ROWB + (2 * GB * w + ((c16 >> 1) & 1)) * 64 + (c16 >> 2) * 16 +
+                             (c16 & 1) * 8;
+        auto *lbase = (__attribute__((address_space(3))) unsigned char *)lds;
 #define FUSED_BFRAG(dst, gb_)                                                                                              \
-    _Pragma("unroll") for (int p = 0; p < 4; ++p)                                                                          \
-    {                                                                                                                      \
-        const uint32_t o_ = tr0 + p * 8 * ROWB + (gb_) * 128;                                                             \
-        const u32x2 lo_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_)));   \
-        const u32x2 hi_ = __builtin_bit_cast(                                                                              \
-            u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_ + 4 * ROWB)));                        \
-        dst[p] = u32x4{lo_.x, lo_.y, hi_.x, hi_.y};                                                                       \
-    }
+_Pragma("unroll") for (int p = 0; p < 4; ++p)                                                                          \
+{                                                                                                                      \
+    const uint32_t o_ = tr0 + p * 8 * ROWB + (gb_) * 128;                                                             \
+    const u32x2 lo_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_)));   \
+    const u32x2 hi_ = __builtin_bit_cast(                                                                              \
+        u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_ + 4 * ROWB)));                        \
+    dst[p] = u32x4{lo_.x, lo_.y, hi_.x, hi_.y};                                                                       \
+}
 #pragma unroll
-            for (int gb = 0; gb < GB; ++gb) {
-                // (before the products of the last block: by then one refill register set is free)
-                if (YIN && gb == GB - 1) {
-                    FUSED_ZLOAD((tile0 + min(i + 1, tpw - 1)) * 32, 0)
-                    FUSED_ZLOAD((tile0 + min(i + 1, tpw - 1)) * 32, 1)
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                u32x4 bf[4];
-                FUSED_BFRAG(bf, gb)
-#pragma unroll
-                for (int n2 = 0; n2 < 4; ++n2) {
-                    const unsigned char *kp = xch + (n2 * 6 * 64 + l) * 16;
-                    u32x4 k0 = *reinterpret_cast<const u32x4 *>(kp), k1 = *reinterpret_cast<const u32x4 *>(kp + 1024);
-                    const u32x4 k2 = *reinterpret_cast<const u32x4 *>(kp + 2048), k3 = *reinterpret_cast<const u32x4 *>(kp + 3072);
-                    // re += Br kr + Bi ki ; im += Br ki - Bi kr
-                    // (round 5: the six products of a tile's block are summed in fresh accumulators and added to the running sums
-                    //  ONCE - see fused_pass64_kernel, ACC = 1)
-                    {
-                    f32x4 tr = mma(bf[0], k0, f32x4{0.f, 0.f, 0.f, 0.f}), ti = mma(bf[0], k2, f32x4{0.f, 0.f, 0.f, 0.f});
-                    tr = mma(bf[0], k1, tr); ti = mma(bf[0], k3, ti);
-                    tr = mma(bf[1], k0, tr); ti = mma(bf[1], k2, ti);
-                    k0 = *reinterpret_cast<const u32x4 *>(kp + 4096); k1 = *reinterpret_cast<const u32x4 *>(kp + 5120);   // -kr
-                    tr = mma(bf[2], k2, tr); ti = mma(bf[2], k0, ti);
-                    tr = mma(bf[2], k3, tr); ti = mma(bf[2], k1, ti);
-                    tr = mma(bf[3], k2, tr); ti = mma(bf[3], k0, ti);
-                    pr[gb][n2] += tr; pi[gb][n2] += ti;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);      // (else the fragment reads of all four n-blocks are hoisted: spills)
-                }
-                if (!(DBG & 8)) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        *reinterpret_cast<u32x4 *>(rdst + c * 8 * ROWB + gb * 128) = rf[gb & 1][c];
-                        if (gb + 2 < GB) rf[gb & 1][c] = FUSED_BLD(noff, (gb + 2 < GB ? gb + 2 : 0), c);
-                    }
-                }
+        for (int gb = 0; gb < GB; ++gb) {
+            // (before the products of the last block: by then one refill register set is free)
+            if (YIN && gb == GB - 1) {
+                FUSED_ZLOAD((tile0 + min(i + 1, tpw - 1)) * 32, 0)
+                FUSED_ZLOAD((tile0 + min(i + 1, tpw - 1)) * 32, 1)
+                __builtin_amdgcn_sched_barrier(0);
             }
-#undef FUSED_BFRAG
+            u32x4 bf[4];
+            FUSED_BFRAG(bf, gb)
+#pragma unroll
+            for (int n2 = 0; n2 < 4; ++n2) {
+                const unsigned char *kp = xch + (n2 * 6 * 64 + l) * 16;
+                u32x4 k0 = *reinterpret_cast<const u32x4 *>(kp), k1 = *reinterpret_cast<const u32x4 *>(kp + 1024);
+                const u32x4 k2 = *reinterpret_cast<const u32x4 *>(kp + 2048), k3 = *reinterpret_cast<const u32x4 *>(kp + 3072);
+                // re += Br kr + Bi ki ; im += Br ki - Bi kr
+                // (round 5: the six products of a tile's block are summed in fresh accumulators and added to the running sums
+                //  ONCE - see fused_pass64_kernel)
+                {
+                f32x4 tr = mma(bf[0], k0, f32x4{0.f, 0.f, 0.f, 0.f}), ti = mma(bf[0], k2, f32x4{0.f, 0.f, 0.f, 0.f});
+                tr = mma(bf[0], k1, tr); ti = mma(bf[0], k3, ti);
+                tr = mma(bf[1], k0, tr); ti = mma(bf[1], k2, ti);
+                k0 = *reinterpret_cast<const u32x4 *>(kp + 4096); k1 = *reinterpret_cast<const u32x4 *>(kp + 5120);   // -kr
+                tr = mma(bf[2], k2, tr); ti = mma(bf[2], k0, ti);
+                tr = mma(bf[2], k3, tr); ti = mma(bf[2], k1, ti);
+                tr = mma(bf[3], k2, tr); ti = mma(bf[3], k0, ti);
+                pr[gb][n2] += tr; pi[gb][n2] += ti;
+                }
+                __builtin_amdgcn_sched_barrier(0);      // (else the fragment reads of all four n-blocks are hoisted: spills)
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                *reinterpret_cast<u32x4 *>(rdst + c * 8 * ROWB + gb * 128) = rf[gb & 1][c];
+                if (gb + 2 < GB) rf[gb & 1][c] = FUSED_BLD(noff, (gb + 2 < GB ? gb + 2 : 0), c);
+            }
         }
+#undef FUSED_BFRAG
         if (YIN) FUSED_YCOMP()
         __syncthreads();                        // next tile in place, k fragments dead
     }
@@ -741,8 +730,8 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
 //   * the element-wise operands of the NEXT tile (X, V1, V2, subY, 1/D: 72 KiB per tile) are fetched into an LDS staging
 //     area while phase B runs (through the 32 registers the 128-KiB refill of fused_pass_kernel needed), each wave for its
 //     own block; in fused_pass_kernel those loads sit between the two product phases with nothing to hide them (1.30 ms
-//     of products + 0.69 ms of exposed element-wise traffic = 1.98 ms per pass, measured by switching parts off:
-//     tools/pass_breakdown.py);
+//     of products + 0.69 ms of exposed element-wise traffic = 1.98 ms per pass, measured by switching parts off in a
+//     timing build of round 3: profiles/r03_pass64_sections.txt);
 //   * the svt argument Z = X - V1 / rho of Y = (I - Q) Z is formed from the staged X and V1 of the four waves of a column
 //     half instead of being written by one pass and read by the next (- 1.07 GB per pass with convergence_error; without
 //     it the Gram of the stored Z still needs the write);
@@ -753,7 +742,7 @@ __global__ __launch_bounds__(512, 1) void fused_pass_kernel(FusedDesc d)
 // The leading columns (m < ld of block ld: 28 of the 4096 x 8 column-blocks) are outside the Toeplitz part.  They enter
 // as fp32 corrections: XsD = (A S) Delta is added to Xs in the first tile (xs_delta, formed with the (A S) fragments), the
 // first L - 1 columns of k are stored, and the sum of the partial sums adds k(:, m) conj(B(g, m)) (reduce_parts_delta_kernel).
-template <int GB, int DBG, int ACC = 0>
+template <int GB>
 __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
 {
     constexpr int G2 = 128 * GB;
@@ -829,11 +818,9 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
     {                                                                                                                        \
         if ((pc_) < 3) {                                                                                                     \
             const int e_ = ws + 8 * (pc_) - ((pc_) == 2 && ws >= 4 ? 8 : 0);    /* (waves 4-7 have two pieces: the second again) */ \
-            if (!(DBG & 8)) {                                                                                                \
-                const int p_ = e_ / 5, j_ = e_ - 5 * p_;                                                                     \
-                dst_ = ldg_nt<u32x4>(Et, (uint32_t)p_ * epl + 4096u * (uint32_t)(T_) + 1024u * j_ + 16u * l);               \
-            }                                                                                                                \
-        } else if (!(DBG & 2)) {                                                                                             \
+            const int p_ = e_ / 5, j_ = e_ - 5 * p_;                                                                         \
+            dst_ = ldg_nt<u32x4>(Et, (uint32_t)p_ * epl + 4096u * (uint32_t)(T_) + 1024u * j_ + 16u * l);                   \
+        } else {                                                                                                             \
             const uint32_t o_ = so + 16384u * (uint32_t)(T_) + 4096u * F64_J(pc_);                                           \
             if ((pc_) < 11 && F64_FLD(pc_) == 0) dst_ = ldg_nt<u32x4>(Xt, o_);                                               \
             if ((pc_) < 11 && F64_FLD(pc_) == 1) dst_ = ldg_nt<u32x4>(V1t, o_);                                              \
@@ -851,11 +838,9 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
     {                                                                                                                        \
         if ((pc_) < 3) {                                                                                                     \
             const int e_ = ws + 8 * (pc_) - ((pc_) == 2 && ws >= 4 ? 8 : 0);                                                 \
-            if (!(DBG & 8)) {                                                                                                \
-                const int p_ = e_ / 5, j_ = e_ - 5 * p_;                                                                     \
-                *reinterpret_cast<u32x4 *>(lds + (buf_) * EBUF + p_ * EPL + j_ * 1024 + 16 * l) = src_;                      \
-            }                                                                                                                \
-        } else if (!(DBG & 2)) {                                                                                             \
+            const int p_ = e_ / 5, j_ = e_ - 5 * p_;                                                                         \
+            *reinterpret_cast<u32x4 *>(lds + (buf_) * EBUF + p_ * EPL + j_ * 1024 + 16 * l) = src_;                          \
+        } else {                                                                                                             \
             if ((pc_) == 11) {                                                                                               \
                 int lo_ = l;                                                                                                 \
                 asm volatile("" : "+v"(lo_));                                                                                \
@@ -911,12 +896,9 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
         _Pragma("unroll") for (int p = 0; p < 4; ++p) wq[ks][p] = ldg<u32x4>(wqt, wo_ + p * 1024);                           \
     }
     F64_WQLOAD()
-    long long t_wait = 0, t_bar = 0, t_ph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const long long t_start = (DBG & 16) ? (long long)__builtin_readcyclecounter() : 0;
     for (int i = 0; i < tpw; ++i) {
         const int m0 = (tile0 + i) * 32;
         const unsigned char *ebuf = lds + (i & 1) * EBUF;
-        long long tp = (DBG & 16) ? (long long)__builtin_readcyclecounter() : 0;
         // ================= Y^T(block) = Z^T Wq^T for this wave's element-wise block: A operand = Z^T (lane = column m, 8
         // consecutive rows n' per k-step), Z = X - V1 / rho formed from the staged operands of the four waves of this
         // column half - the svt argument is neither read from memory nor (with convergence_error) written to it;
@@ -929,8 +911,7 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
                 u32x4 zf[4];
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
-                    zf[p] = (DBG & 2) ? u32x4{0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u}
-                                      : *reinterpret_cast<const u32x4 *>(zsrc + ks * 4096 + p * 1024);
+                    zf[p] = *reinterpret_cast<const u32x4 *>(zsrc + ks * 4096 + p * 1024);
                 const u32x4 nwi_h = negu(wq[ks][2]), nwi_l = negu(wq[ks][3]);
                 yr = mma(zf[0], wq[ks][0], yr); yi = mma(zf[0], wq[ks][2], yi);
                 yr = mma(zf[0], wq[ks][1], yr); yi = mma(zf[0], wq[ks][3], yi);
@@ -943,50 +924,46 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
             for (int s = 0; s < 4; ++s) ey[s] = make_float2(yr[s] * sy, yi[s] * sy);
         }
         __builtin_amdgcn_sched_barrier(0);      // (else the first (A S) fragments of phase A are requested above these products: spills)
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[3] += tq - tp; tp = tq; }
         // ================= phase A: Xs^T(tile) = B^T (A S)^T, this wave: n-block nb, g-half kh, both m-blocks
         f32x4 ar[2], ai[2];
         ar[0] = ar[1] = ai[0] = ai[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (!(DBG & 1)) {
-            u32x4 wr[2][4], bfb[4];
-            uint32_t ao = aoff;
-            asm volatile("" : "+v"(ao));
-            int cK = cA;
+        u32x4 wr[2][4], bfb[4];
+        uint32_t ao = aoff;
+        asm volatile("" : "+v"(ao));
+        int cK = cA;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) wr[0][p] = ldg<u32x4>(ast, ao + p * 1024);
+        for (int p = 0; p < 4; ++p) wr[0][p] = ldg<u32x4>(ast, ao + p * 1024);
 #pragma unroll
-            for (int st = 0; st < 2 * KSH; ++st) {
-                const int ks = st >> 1, mb = st & 1;
-                if (mb == 0 && ks + 1 < KSH) {
-                    ao += 16384;
-                    asm volatile("" : "+v"(ao));
+        for (int st = 0; st < 2 * KSH; ++st) {
+            const int ks = st >> 1, mb = st & 1;
+            if (mb == 0 && ks + 1 < KSH) {
+                ao += 16384;
+                asm volatile("" : "+v"(ao));
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) wr[(ks + 1) & 1][p] = ldg<u32x4>(ast, ao + p * 1024);
-                }
-                {
-                    // (the column is advanced opaquely per delay block: computed up front, the addresses of all (block, octet)
-                    //  pairs are loop invariants of the tile loop and the compiler keeps - and spills - them)
-                    if (mb == 0 && (ks & 1) == 0) {
-                        if (ks > 0) cK -= 1;
-                        asm volatile("" : "+v"(cK));
-                    }
-                    const unsigned char *arow = ebuf + cK * 128 + 16 * ((4 * (ks & 1) + q) ^ eswz(cK)) + mb * 2048;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) bfb[p] = *reinterpret_cast<const u32x4 *>(arow + p * EPL);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const u32x4 *wf = wr[ks & 1];
-                const u32x4 nwi_h = negu(wf[2]), nwi_l = negu(wf[3]);
-                // re += Br Wr - Bi Wi ; im += Br Wi + Bi Wr   (h h + h l + l h each)
-                ar[mb] = mma(bfb[0], wf[0], ar[mb]); ai[mb] = mma(bfb[0], wf[2], ai[mb]);
-                ar[mb] = mma(bfb[0], wf[1], ar[mb]); ai[mb] = mma(bfb[0], wf[3], ai[mb]);
-                ar[mb] = mma(bfb[1], wf[0], ar[mb]); ai[mb] = mma(bfb[1], wf[2], ai[mb]);
-                ar[mb] = mma(bfb[2], nwi_h, ar[mb]); ai[mb] = mma(bfb[2], wf[0], ai[mb]);
-                ar[mb] = mma(bfb[2], nwi_l, ar[mb]); ai[mb] = mma(bfb[2], wf[1], ai[mb]);
-                ar[mb] = mma(bfb[3], nwi_h, ar[mb]); ai[mb] = mma(bfb[3], wf[0], ai[mb]);
+                for (int p = 0; p < 4; ++p) wr[(ks + 1) & 1][p] = ldg<u32x4>(ast, ao + p * 1024);
             }
+            {
+                // (the column is advanced opaquely per delay block: computed up front, the addresses of all (block, octet)
+                //  pairs are loop invariants of the tile loop and the compiler keeps - and spills - them)
+                if (mb == 0 && (ks & 1) == 0) {
+                    if (ks > 0) cK -= 1;
+                    asm volatile("" : "+v"(cK));
+                }
+                const unsigned char *arow = ebuf + cK * 128 + 16 * ((4 * (ks & 1) + q) ^ eswz(cK)) + mb * 2048;
+#pragma unroll
+                for (int p = 0; p < 4; ++p) bfb[p] = *reinterpret_cast<const u32x4 *>(arow + p * EPL);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const u32x4 *wf = wr[ks & 1];
+            const u32x4 nwi_h = negu(wf[2]), nwi_l = negu(wf[3]);
+            // re += Br Wr - Bi Wi ; im += Br Wi + Bi Wr   (h h + h l + l h each)
+            ar[mb] = mma(bfb[0], wf[0], ar[mb]); ai[mb] = mma(bfb[0], wf[2], ai[mb]);
+            ar[mb] = mma(bfb[0], wf[1], ar[mb]); ai[mb] = mma(bfb[0], wf[3], ai[mb]);
+            ar[mb] = mma(bfb[1], wf[0], ar[mb]); ai[mb] = mma(bfb[1], wf[2], ai[mb]);
+            ar[mb] = mma(bfb[2], nwi_h, ar[mb]); ai[mb] = mma(bfb[2], wf[0], ai[mb]);
+            ar[mb] = mma(bfb[2], nwi_l, ar[mb]); ai[mb] = mma(bfb[2], wf[1], ai[mb]);
+            ar[mb] = mma(bfb[3], nwi_h, ar[mb]); ai[mb] = mma(bfb[3], wf[0], ai[mb]);
         }
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[0] += tq - tp; tp = tq; }
         // the two g-halves meet: wave (nb, kh) keeps m-block kh and hands m-block 1 - kh to wave (nb, 1 - kh) - through the
         // window buffer that is not in use (the next window arrives there during phase B), so that the k fragments below
         // need not wait for these reads
@@ -1003,14 +980,12 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
         float eid[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            if (DBG & 2) { ex[s] = ev1[s] = ev2[s] = esy[s] = make_float2(1.f, 1.f); eid[s] = 1.f; continue; }
             const unsigned char *sp_ = stag + (4 * q + s) * SCOL + c16 * 8;
             ex[s] = *reinterpret_cast<const float2 *>(sp_);              ev1[s] = *reinterpret_cast<const float2 *>(sp_ + SFLD);
             ev2[s] = *reinterpret_cast<const float2 *>(sp_ + 2 * SFLD);  esy[s] = *reinterpret_cast<const float2 *>(sp_ + 3 * SFLD);
             eid[s] = *reinterpret_cast<const float *>(stag + SINV + (4 * q + s) * ICOL + c16 * 4);
         }
         __syncthreads();
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[4] += tq - tp; tp = tq; }
         f32x4 xr = kh ? ar[1] : ar[0], xi = kh ? ai[1] : ai[0];
         {
             const f32x4 *x4 = reinterpret_cast<const f32x4 *>(pex);
@@ -1037,7 +1012,7 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
                                          admm_x2(prm, ev1[s].y, ey[s].y, esy[s].y, v2.y, xs.y, rh, rl));
             const float2 kk = make_float2(admm_k(prm, x.x, v2.x), admm_k(prm, x.y, v2.y));        // (:43)
             const float2 v1 = make_float2(admm_v1(prm, ev1[s].x, ey[s].x, x.x), admm_v1(prm, ev1[s].y, ey[s].y, x.y));   // (:64)
-            if (!(DBG & 2)) { stg_nt2(V2t, ix, v2); stg_nt2(Xt, ix, x); stg_nt2(V1t, ix, v1); }
+            stg_nt2(V2t, ix, v2); stg_nt2(Xt, ix, x); stg_nt2(V1t, ix, v1);
             const float2 zn = make_float2(admm_z(prm, x.x, v1.x), admm_z(prm, x.y, v1.y));
             if (Zot) stg_nt2(Zot, ix, zn);
             if (Yot) stg(Yot, ix, ey[s]);
@@ -1051,7 +1026,6 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
             fsplit(kk.x * sk, h, lo); kf[0][s] = h; kf[1][s] = lo;
             fsplit(kk.y * sk, h, lo); kf[2][s] = h; kf[3][s] = lo;
         }
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[5] += tq - tp; tp = tq; }
 #pragma unroll
         for (int p = 0; p < 4; ++p)
             *reinterpret_cast<half4 *>(xch + ((nb * 6 + p) * 64 + l) * 16 + kh * 8) = kf[p];
@@ -1059,80 +1033,60 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
         *reinterpret_cast<half4 *>(xch + ((nb * 6 + 4) * 64 + l) * 16 + kh * 8) = -kf[0];
         *reinterpret_cast<half4 *>(xch + ((nb * 6 + 5) * 64 + l) * 16 + kh * 8) = -kf[1];
         __syncthreads();
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[7] += tq - tp; tp = tq; }
         // the next tile (the last one is fetched again: unconditional loads): its window goes into the other buffer, its
         // element-wise operands into this wave's staging area (every wave has read what it needs of it: Y above, the operands
         // before the first barrier).  One piece is requested behind each product group of phase B and written to LDS six
         // groups later (eight register slots): requested together, the 8 KiB per wave of all eight waves queue up at the CU's
-        // 64-byte-per-clock load path and every wave waits 1200 cycles before its first product (tools/pass_breakdown.py).
+        // 64-byte-per-clock load path and every wave waits 1200 cycles before its first product (profiles/r03_pass64_sections.txt).
         const int tn = tile0 + min(i + 1, tpw - 1);
-        if (DBG & 16) { const long long tq = __builtin_readcyclecounter(); t_ph[1] += tq - tp; tp = tq; }
         // ================= phase B: P^T += conj(B)(g, tile) k^T(tile, :), this wave: g in [16 GB w, 16 GB (w + 1))
-        if (!(DBG & 4)) {
-            typedef short s16x4 __attribute__((ext_vector_type(4)));
-            typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-            auto *lbase = (__attribute__((address_space(3))) unsigned char *)lds;
+        typedef short s16x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+        auto *lbase = (__attribute__((address_space(3))) unsigned char *)lds;
 #pragma unroll
-            for (int gb = 0; gb < GB; ++gb) {
-                // rows 16 (GB w + gb) ..: delay ld, octet pair jp of block 0; lane: window column of row 4 q + (c16 >> 2)
-                const int blk = GB * ws + gb, ld = blk >> 2, jp = 2 * (blk & 3);
-                int cB = cB0 - ld;
-                asm volatile("" : "+v"(cB));                 // (as in phase A: no address per block kept across the tile loop)
-                const uint32_t tr0 = (uint32_t)((i & 1) * EBUF) + cB * 128 + 16 * ((jp + ((c16 >> 1) & 1)) ^ eswz(cB)) + (c16 & 1) * 8;
-                u32x4 bf[4];
+        for (int gb = 0; gb < GB; ++gb) {
+            // rows 16 (GB w + gb) ..: delay ld, octet pair jp of block 0; lane: window column of row 4 q + (c16 >> 2)
+            const int blk = GB * ws + gb, ld = blk >> 2, jp = 2 * (blk & 3);
+            int cB = cB0 - ld;
+            asm volatile("" : "+v"(cB));                 // (as in phase A: no address per block kept across the tile loop)
+            const uint32_t tr0 = (uint32_t)((i & 1) * EBUF) + cB * 128 + 16 * ((jp + ((c16 >> 1) & 1)) ^ eswz(cB)) + (c16 & 1) * 8;
+            u32x4 bf[4];
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const uint32_t o_ = tr0 + p * EPL;
-                    const u32x2 lo_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_)));
-                    const u32x2 hi_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_ + 2048)));
-                    bf[p] = u32x4{lo_.x, lo_.y, hi_.x, hi_.y};
+            for (int p = 0; p < 4; ++p) {
+                const uint32_t o_ = tr0 + p * EPL;
+                const u32x2 lo_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_)));
+                const u32x2 hi_ = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(lbase + o_ + 2048)));
+                bf[p] = u32x4{lo_.x, lo_.y, hi_.x, hi_.y};
+            }
+#pragma unroll
+            for (int n2 = 0; n2 < 4; ++n2) {
+                const unsigned char *kp = xch + (n2 * 6 * 64 + l) * 16;
+                u32x4 k0 = *reinterpret_cast<const u32x4 *>(kp), k1 = *reinterpret_cast<const u32x4 *>(kp + 1024);
+                const u32x4 k2 = *reinterpret_cast<const u32x4 *>(kp + 2048), k3 = *reinterpret_cast<const u32x4 *>(kp + 3072);
+                // re += Br kr + Bi ki ; im += Br ki - Bi kr
+                // the six products of a tile's block are summed in fresh accumulators and added to the running sums ONCE (round 5) -
+                // the running sum, 32 tiles long, is rounded once per tile instead of six times: 1.0e-7 of the 1.73e-7 rms dNMSE
+                // of round 4 was this.  +3 % kernel time (the adds wait for the last product of their
+                // chain; measured slower still: the two chains one after the other, 795 vs 798 channel-estimates/s, and the adds
+                // deferred behind the next block's first products, 803 vs 815 with 4 more spilled registers)
+                f32x4 tr = mma(bf[0], k0, f32x4{0.f, 0.f, 0.f, 0.f}), ti = mma(bf[0], k2, f32x4{0.f, 0.f, 0.f, 0.f});
+                tr = mma(bf[0], k1, tr); ti = mma(bf[0], k3, ti);
+                tr = mma(bf[1], k0, tr); ti = mma(bf[1], k2, ti);
+                k0 = *reinterpret_cast<const u32x4 *>(kp + 4096); k1 = *reinterpret_cast<const u32x4 *>(kp + 5120);   // -kr
+                tr = mma(bf[2], k2, tr); ti = mma(bf[2], k0, ti);
+                tr = mma(bf[2], k3, tr); ti = mma(bf[2], k1, ti);
+                tr = mma(bf[3], k2, tr); ti = mma(bf[3], k0, ti);
+                {       // (this block's prefetch traffic is issued while the last products drain; then the sums)
+                    const int grp = 4 * gb + n2;
+                    if (grp >= 6 && grp - 6 < 12) F64_STORE(grp - 6, (i + 1) & 1, rf[((grp - 6) >> 2) & 1][(grp - 6) & 3])
+                    if (grp < 12) F64_LOAD(grp, tn, rf[(grp >> 2) & 1][grp & 3])
                 }
-#pragma unroll
-                for (int n2 = 0; n2 < 4; ++n2) {
-                    const unsigned char *kp = xch + (n2 * 6 * 64 + l) * 16;
-                    u32x4 k0 = *reinterpret_cast<const u32x4 *>(kp), k1 = *reinterpret_cast<const u32x4 *>(kp + 1024);
-                    const u32x4 k2 = *reinterpret_cast<const u32x4 *>(kp + 2048), k3 = *reinterpret_cast<const u32x4 *>(kp + 3072);
-                    // re += Br kr + Bi ki ; im += Br ki - Bi kr
-                    // ACC = 0: every product accumulates straight into the running sums (rounds 2-4).  ACC = 1 (round 5, default): the
-                    // six products of a tile's block are summed in fresh accumulators and added to the running sums ONCE - the
-                    // running sum, 32 tiles long, is rounded once per tile instead of six times: 1.0e-7 of the 1.73e-7 rms dNMSE
-                    // of round 4 was this.  +3 % kernel time (the adds wait for the last product of their
-                    // chain; measured slower still: the two chains one after the other, 795 vs 798 channel-estimates/s, and the adds
-                    // deferred behind the next block's first products, 803 vs 815 with 4 more spilled registers)
-                    if constexpr (ACC == 0) {
-                        pr[gb][n2] = mma(bf[0], k0, pr[gb][n2]); pi[gb][n2] = mma(bf[0], k2, pi[gb][n2]);
-                        pr[gb][n2] = mma(bf[0], k1, pr[gb][n2]); pi[gb][n2] = mma(bf[0], k3, pi[gb][n2]);
-                        pr[gb][n2] = mma(bf[1], k0, pr[gb][n2]); pi[gb][n2] = mma(bf[1], k2, pi[gb][n2]);
-                        k0 = *reinterpret_cast<const u32x4 *>(kp + 4096); k1 = *reinterpret_cast<const u32x4 *>(kp + 5120);   // -kr
-                        pr[gb][n2] = mma(bf[2], k2, pr[gb][n2]); pi[gb][n2] = mma(bf[2], k0, pi[gb][n2]);
-                        pr[gb][n2] = mma(bf[2], k3, pr[gb][n2]); pi[gb][n2] = mma(bf[2], k1, pi[gb][n2]);
-                        pr[gb][n2] = mma(bf[3], k2, pr[gb][n2]); pi[gb][n2] = mma(bf[3], k0, pi[gb][n2]);
-                    } else if constexpr (ACC == 1) {
-                        f32x4 tr = mma(bf[0], k0, f32x4{0.f, 0.f, 0.f, 0.f}), ti = mma(bf[0], k2, f32x4{0.f, 0.f, 0.f, 0.f});
-                        tr = mma(bf[0], k1, tr); ti = mma(bf[0], k3, ti);
-                        tr = mma(bf[1], k0, tr); ti = mma(bf[1], k2, ti);
-                        k0 = *reinterpret_cast<const u32x4 *>(kp + 4096); k1 = *reinterpret_cast<const u32x4 *>(kp + 5120);   // -kr
-                        tr = mma(bf[2], k2, tr); ti = mma(bf[2], k0, ti);
-                        tr = mma(bf[2], k3, tr); ti = mma(bf[2], k1, ti);
-                        tr = mma(bf[3], k2, tr); ti = mma(bf[3], k0, ti);
-                        {       // (this block's prefetch traffic is issued while the last products drain; then the sums)
-                            const int grp = 4 * gb + n2;
-                            if (grp >= 6 && grp - 6 < 12) F64_STORE(grp - 6, (i + 1) & 1, rf[((grp - 6) >> 2) & 1][(grp - 6) & 3])
-                            if (grp < 12) F64_LOAD(grp, tn, rf[(grp >> 2) & 1][grp & 3])
-                        }
-                        pr[gb][n2] += tr; pi[gb][n2] += ti;
-                    }
-                    if constexpr (ACC != 1) {
-                        const int grp = 4 * gb + n2;
-                        if (grp >= 6 && grp - 6 < 12) F64_STORE(grp - 6, (i + 1) & 1, rf[((grp - 6) >> 2) & 1][(grp - 6) & 3])
-                        if (grp < 12) F64_LOAD(grp, tn, rf[(grp >> 2) & 1][grp & 3])
-                    }
-                    __builtin_amdgcn_sched_barrier(0);      // (else the fragment reads of all four n-blocks are hoisted: spills)
-                }
+                pr[gb][n2] += tr; pi[gb][n2] += ti;
+                __builtin_amdgcn_sched_barrier(0);      // (else the fragment reads of all four n-blocks are hoisted: spills)
             }
         }
         {
-            constexpr int NG = (DBG & 4) ? 0 : 4 * GB;      // product groups that ran; what is left of the 12 pieces:
+            constexpr int NG = 4 * GB;      // product groups of phase B; what is left of the 12 pieces:
 #pragma unroll
             for (int pc = (NG > 6 ? NG - 6 : 0); pc < 12; ++pc) {
                 if (pc >= NG) F64_LOAD(pc, tn, rf[(pc >> 2) & 1][pc & 3])
@@ -1141,16 +1095,7 @@ __global__ __launch_bounds__(512, 1) void fused_pass64_kernel(FusedDesc d)
         }
         __builtin_amdgcn_sched_barrier(0);
         F64_WQLOAD()
-        long long tw0 = 0;
-        if (DBG & 16) { tw0 = __builtin_readcyclecounter(); t_ph[2] += tw0 - tp; }
         __syncthreads();                        // window and operands of the next tile in place for every wave; k fragments dead
-        if (DBG & 16) t_bar += __builtin_readcyclecounter() - tw0;
-    }
-    if ((DBG & 16) && l == 0) {                 // (timing experiment: cycles per section, summed over the waves of the trial)
-        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d.Kf + (long long)t * 512 + 448);
-        atomicAdd(cnt, (unsigned long long)t_wait); atomicAdd(cnt + 1, (unsigned long long)t_bar);
-        atomicAdd(cnt + 2, (unsigned long long)(__builtin_readcyclecounter() - t_start));
-        for (int z = 0; z < 9; ++z) atomicAdd(cnt + 3 + z, (unsigned long long)t_ph[z]);
     }
 #undef F64_LOAD
 #undef F64_STORE
@@ -1330,9 +1275,6 @@ int fused_pack_b(jstsp_ctx *ctx, FusedWS &f, const float2 *B, long long sBt, int
                            bmax, 1, f.Ec, f.sEc, f.Bdl);
         JSTSP_HIP(hipGetLastError());
         f.sBdl = sBt ? (long long)G2 * 8 : 0;
-#ifdef JSTSP_FUSED_DBG_BUILD
-        JSTSP_HIP(hipMemsetAsync(f.Kf, 0, 4096, ctx->stream));     // (cycle counters of the timing experiment, trial 0)
-#endif
         return 0;
     }
     if (f.gt) {
@@ -1362,52 +1304,8 @@ template <int GB> static int launch_fused64(jstsp_ctx *ctx, const FusedDesc &d)
 {
     const size_t sh = 2 * 20480 + 24576 + 8 * (4 * 16 * 128 + 16 * 80) + 16384;
     const int grid = ((d.batch + 7) / 8) * 8 * d.parts;
-#ifdef JSTSP_FUSED_DBG_BUILD
-    if (GB == 4 && getenv("JSTSP_FUSED_DBG") && atoi(getenv("JSTSP_FUSED_DBG"))) {
-#define DBG_CASE(k_)                                                                                                          \
-    case k_:                                                                                                                  \
-        JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<4, k_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh)); \
-        hipLaunchKernelGGL((fused_pass64_kernel<4, k_>), dim3(grid), dim3(512), sh, ctx->stream, d);                          \
-        return 0;
-        const int dbg = atoi(getenv("JSTSP_FUSED_DBG"));
-        if (dbg & 16) {
-            static int calls = 0;
-            if (dbg == 16) {
-                JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<4, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                hipLaunchKernelGGL((fused_pass64_kernel<4, 16>), dim3(grid), dim3(512), sh, ctx->stream, d);
-            } else {
-                JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<4, 26>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-                hipLaunchKernelGGL((fused_pass64_kernel<4, 26>), dim3(grid), dim3(512), sh, ctx->stream, d);
-            }
-            if (++calls == 7) {
-                unsigned long long c[12];
-                JSTSP_HIP(hipStreamSynchronize(ctx->stream));
-                JSTSP_HIP(hipMemcpy(c, d.Kf + 448, sizeof(c), hipMemcpyDeviceToHost));
-                const double n = 8.0 * d.parts * calls * ((d.M / 32) / d.parts);     // (waves x tiles) of trial 0 so far
-                fprintf(stderr, "pass64 timing dbg=%d (trial 0, cycles per wave and tile): phase A %.0f, [exchange+stage reads+barrier %.0f, update+stores %.0f, barrier %.0f, k fragments+barrier %.0f, "
-                        "issue %.0f], phase B %.0f, Y %.0f, load wait %.0f, barrier %.0f; loop %.0f\n", dbg, c[3] / n, c[7] / n, c[8] / n, c[9] / n,
-                        c[10] / n, c[4] / n, c[5] / n, c[6] / n, c[0] / n, c[1] / n, c[2] / n);
-                calls = 0;
-            }
-            return 0;
-        }
-        switch (atoi(getenv("JSTSP_FUSED_DBG"))) {
-            DBG_CASE(1) DBG_CASE(2) DBG_CASE(4) DBG_CASE(8) DBG_CASE(5) DBG_CASE(7) DBG_CASE(13) DBG_CASE(15) DBG_CASE(10)
-        default: break;
-        }
-#undef DBG_CASE
-    }
-#endif
-    // JSTSP_PASS_ACC: how the products of K B^H enter their running sums (see phase B of the kernel)
-#ifdef JSTSP_EXPERIMENTS
-    if (tune().pass_acc != 1) {
-        JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<GB, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL((fused_pass64_kernel<GB, 0, 0>), dim3(grid), dim3(512), sh, ctx->stream, d);
-        return 0;
-    }
-#endif
-    JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<GB, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL((fused_pass64_kernel<GB, 0, 1>), dim3(grid), dim3(512), sh, ctx->stream, d);
+    JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass64_kernel<GB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    hipLaunchKernelGGL((fused_pass64_kernel<GB>), dim3(grid), dim3(512), sh, ctx->stream, d);
     return 0;
 }
 
@@ -1415,23 +1313,8 @@ template <int GB, bool YIN, bool TOEP> static int launch_fused_gb(jstsp_ctx *ctx
 {
     const size_t sh = (size_t)32 * (128 * GB * 8 + FPAD) + 24576;
     const int grid = ((d.batch + 7) / 8) * 8 * d.parts;
-#ifdef JSTSP_FUSED_DBG_BUILD        // timing experiments (tools/pass_breakdown.py): parts of the kernel switched off, results wrong
-    if (GB == 4 && YIN && getenv("JSTSP_FUSED_DBG") && atoi(getenv("JSTSP_FUSED_DBG"))) {
-#define DBG_CASE(k_)                                                                                                          \
-    case k_:                                                                                                                  \
-        JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass_kernel<4, k_, true, TOEP>,                                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));                                  \
-        hipLaunchKernelGGL((fused_pass_kernel<4, k_, true, TOEP>), dim3(grid), dim3(512), sh, ctx->stream, d);                \
-        return 0;
-        switch (atoi(getenv("JSTSP_FUSED_DBG"))) {
-            DBG_CASE(1) DBG_CASE(2) DBG_CASE(4) DBG_CASE(8) DBG_CASE(5) DBG_CASE(7) DBG_CASE(13) DBG_CASE(15) DBG_CASE(10)
-        default: break;
-        }
-#undef DBG_CASE
-    }
-#endif
-    JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass_kernel<GB, 0, YIN, TOEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL((fused_pass_kernel<GB, 0, YIN, TOEP>), dim3(grid), dim3(512), sh, ctx->stream, d);
+    JSTSP_HIP(hipFuncSetAttribute((const void *)fused_pass_kernel<GB, YIN, TOEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    hipLaunchKernelGGL((fused_pass_kernel<GB, YIN, TOEP>), dim3(grid), dim3(512), sh, ctx->stream, d);
     return 0;
 }
 

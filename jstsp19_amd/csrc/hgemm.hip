@@ -644,7 +644,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void hgemm2_kernel(HGemmD
 //      have the same weight, see LO_SCALE).  The fold is 128 accumulator reads + adds per wave that nothing overlaps (one wave per
 //      SIMD): at 512 k per chain it costs 8 %; the rounding noise of a 65 536-term sum is within 1.4 x of hgemm_kernel's
 //      (first level 192 accumulations of partial sums up to sqrt(512) sigma, second level 128 additions: both ~1e-6 relative;
-//      measured in S after 10 ADMM iterations: mean 2.8e-7 -> 3.5e-7, tools/probe/pair_noise.py).
+//      measured in S after 10 ADMM iterations: mean 2.8e-7 -> 3.5e-7, HISTORY.md).
 constexpr int FLUSH2 = 16;
 template <int EPI, bool TWOLVL>
 __global__ __launch_bounds__(256, 1) void hgemm_pair_kernel(HGemmDesc d, int tiles_j, int npairs)
@@ -889,14 +889,12 @@ constexpr int GRAM_HONLY_MIN_COLS = 1024;     // norm-only Grams take the high f
 // allows (5e-4), and nothing feeds back into the iterates.  Half the MFMA work and no low-plane conversions.
 template <bool EVEN, bool HONLY = false>
 __global__ __launch_bounds__(256, 2) void hgram_kernel(const float2 *Z, long long sZt, int rows, int cols, int nsplit,
-                                                       const uint32_t *amax, float2 *Gpart, int batch,
-                                                       const TrialParams *skip_prm, const float2 *Z2,
+                                                       const uint32_t *amax, float2 *Gpart, int batch, const float2 *Z2,
                                                        const TrialParams *zprm)
 {
     __shared__ uint4 smem[2 * 1024];        // per stage: a blocks [it 2][ks 2][plane 4], 1 KiB each
     const int t = blockIdx.x / nsplit, split = blockIdx.x % nsplit;
     if (t >= batch) return;
-    if (skip_prm && skip_prm[t].tauY_rho <= ldexpf(__uint_as_float(amax[t]), -27)) return;   // SVT below fp32 resolution
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave & 1, wj = wave >> 1;
     const int ea = scale_exp(amax[t]);
@@ -1255,8 +1253,7 @@ int hgemm_repack(jstsp_ctx *ctx, const HPack &p, const float2 *B, long long sBt,
 }
 
 int launch_hgram(jstsp_ctx *ctx, const float2 *Z, long long sZt, int rows, int cols, int count, int nsplit,
-                 const uint32_t *amax, float2 *Gpart, const TrialParams *skip_prm, const float2 *Z2,
-                 const TrialParams *zprm, bool norm_only)
+                 const uint32_t *amax, float2 *Gpart, const float2 *Z2, const TrialParams *zprm, bool norm_only)
 {
     JSTSP_REQUIRE(rows > 0 && rows <= 64 && cols > 0 && count > 0 && nsplit > 0, JSTSP_E_SHAPE, "hgram: bad shape");
     const long long grid = (long long)count * nsplit;
@@ -1264,16 +1261,16 @@ int launch_hgram(jstsp_ctx *ctx, const float2 *Z, long long sZt, int rows, int c
     prof_begin(ctx, "gram");
     JSTSP_REQUIRE(!Z2 || zprm, JSTSP_E_NULL, "hgram: Z2 without per-problem scalars");
     // norm_only: the Gram is used for its lambda_max in convergence_error alone - high f16 plane only (hgram_kernel, HONLY)
-    if (norm_only && !Z2 && !skip_prm && cols >= GRAM_HONLY_MIN_COLS) {
+    if (norm_only && !Z2 && cols >= GRAM_HONLY_MIN_COLS) {
         if (cols % (nsplit * 2 * HBK) == 0)
-            hgram_kernel<true, true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, skip_prm, Z2, zprm);
+            hgram_kernel<true, true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, Z2, zprm);
         else
-            hgram_kernel<false, true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, skip_prm, Z2, zprm);
+            hgram_kernel<false, true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, Z2, zprm);
     } else
     if (cols % (nsplit * 2 * HBK) == 0)
-        hgram_kernel<true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, skip_prm, Z2, zprm);
+        hgram_kernel<true><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, Z2, zprm);
     else
-        hgram_kernel<false><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, skip_prm, Z2, zprm);
+        hgram_kernel<false><<<(unsigned)grid, 256, 0, ctx->stream>>>(Z, sZt, rows, cols, nsplit, amax, Gpart, count, Z2, zprm);
     prof_end(ctx, "gram");
     JSTSP_HIP(hipGetLastError());
     return 0;
@@ -1334,10 +1331,8 @@ int hermitian_fill_lower(jstsp_ctx *ctx, float2 *G, long long sGt, int n, int co
 // grid of a launch under the block map chosen for it (conc = workgroups one XCD holds at a time)
 static long long hgemm_grid(HGemmDesc &d, long long tiles, int conc)
 {
-    const char *map_env = xp_getenv("JSTSP_HGEMM_MAP");       // (read at every launch: the tests switch it)
-    const int map_on = map_env ? atoi(map_env) : 1;
     d.map_tb = d.map_tt = 0;
-    if (map_on && d.sPt == 0 && d.batch >= 2 && tiles >= 2) {
+    if (d.sPt == 0 && d.batch >= 2 && tiles >= 2) {
         // (measured at configs[4], batch 32: 2 ... 32 trials per block and half / twice as many workgroups per block are within
         //  3 % of each other — what matters is that the trials of a tile run together at all)
         d.map_tb = d.batch < 8 ? d.batch : 8;
@@ -1352,8 +1347,6 @@ static long long hgemm_grid(HGemmDesc &d, long long tiles, int conc)
 // the shapes hgemm_pair_kernel takes (given ONE dictionary for the batch): 64 rows per trial, at least one workgroup per CU
 bool hgemm_pair_shape(int m, int n, int batch)
 {
-    const char *pair_env = xp_getenv("JSTSP_HGEMM_PAIR");     // (experiments build: 0 = the per-trial kernels)
-    if (pair_env && atoi(pair_env) == 0) return false;
     return m == 64 && batch >= 2 && (long long)((batch + 1) / 2) * ((n + 127) / 128) >= 256;
 }
 

@@ -179,7 +179,6 @@ struct HeadDesc {
     const float2 *A; long long sA;                        // N x Gr = 64 x 64 (sA = 0: shared)
     const float2 *GA; long long sGA;                      // Gr x Gr Hermitian
     const float2 *RV;                                     // Gr x G2 per trial, or NULL (R v = 0)
-    const float2 *RVlo;                                   // its low-order part (R v carried as two floats), or NULL
     float2 *Tc;                                           // optional output: the summed Tc (N x G2), NULL = not stored
     float2 *Res, *P1;                                     // Gr x G2 per trial
     uint32_t *pmax;                                       // [batch] atomicMax of max(|re|, |im|) of P1 (float bits)
@@ -249,7 +248,6 @@ __global__ __launch_bounds__(256, 2) void grad_head_kernel(HeadDesc d)
         const int g = wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         float2 v = acc_value(acc, r, al1);
         if (d.RV) { const float2 rv = d.RV[obase + 64ll * g]; v.x -= rv.x; v.y -= rv.y; }
-        if (d.RVlo) { const float2 rl = d.RVlo[obase + 64ll * g]; v.x -= rl.x; v.y -= rl.y; }
         res[r] = v;
         d.Res[obase + 64ll * g] = v;
         mr = fmaxf(mr, fmaxf(fabsf(v.x), fabsf(v.y)));
@@ -287,73 +285,17 @@ __global__ __launch_bounds__(256, 2) void grad_head_kernel(HeadDesc d)
     }
 }
 
-// P1 = (G_hi + G_lo) X   (G Hermitian 64 x 64 in two floats; X 64 x G2): the first factor of R v when it is recomputed from v
-__global__ __launch_bounds__(256, 2) void left2_kernel(const float2 *Ghi, const float2 *Glo, long long sG, const float2 *X, float2 *P1,
-                                                       uint32_t *pmax, int G2)
-{
-    __shared__ uint4 lds[2 * 24 * 64];
-    __shared__ float shm[8];
-    uint4 *bufX = lds, *bufC = lds + 24 * 64;
-    const int nb = G2 >> 6;
-    const int t = blockIdx.x / nb, g0 = (blockIdx.x % nb) << 6;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wi = wave & 1, wj = wave >> 1;
-    const long long sg = 64ll * G2;
-    Rows rx, rh, rl;
-    load_rows(rx, X + (long long)t * sg + 64ll * g0, tid);
-    load_rows(rh, Ghi + (long long)t * sG, tid);
-    load_rows(rl, Glo + (long long)t * sG, tid);
-    float mx = rows_max(rx), mh = rows_max(rh), ml = rows_max(rl), dummy = 0.f;
-    block_max2(mx, mh, shm, tid);
-    block_max2(ml, dummy, shm, tid);
-    const int ex = scale_exp_s(mx), eh = scale_exp_s(mh), el = scale_exp_s(ml);
-    Acc acc;
-    product64(rx, ldexpf(1.f, ex), rh, ldexpf(1.f, eh), bufX, bufC, tid, wi, wj, acc);
-    const float a1 = ldexpf(1.f, -(ex + eh)), a2 = ldexpf(1.f, -(ex + el));
-    float2 out[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) out[r] = acc_value(acc, r, a1);
-    if (ml > 0.f) {                                        // + G_lo X (uniform over the workgroup)
-        __syncthreads();
-        product64(rx, ldexpf(1.f, ex), rl, ldexpf(1.f, el), bufX, bufC, tid, wi, wj, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { const float2 v = acc_value(acc, r, a2); out[r].x += v.x; out[r].y += v.y; }
-    }
-    const int a = wi * 32 + (lane & 31);
-    const long long obase = (long long)t * sg + a + 64ll * g0;
-    float mp = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int g = wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        P1[obase + 64ll * g] = out[r];
-        mp = fmaxf(mp, fmaxf(fabsf(out[r].x), fabsf(out[r].y)));
-    }
-    if (pmax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mp = fmaxf(mp, __shfl_xor(mp, o));
-        if (lane == 0) atomicMax(&pmax[t], __float_as_uint(mp));
-    }
-}
-
 }  // namespace
 
 bool grad_head_shape_ok(int N, int Gr, int G2) { return N == 64 && Gr == 64 && G2 >= 64 && (G2 & 63) == 0; }
 
 int launch_grad_head(jstsp_ctx *ctx, int G2, int batch, const float2 *P, long long sPt, long long sPp, int parts, const float2 *Kf,
                      const float2 *Bdl, long long sBdl, const float2 *A, long long sA, const float2 *GA, long long sGA,
-                     const float2 *RV, float2 *Tc, float2 *Res, float2 *P1, uint32_t *pmax, const float2 *RVlo)
+                     const float2 *RV, float2 *Tc, float2 *Res, float2 *P1, uint32_t *pmax)
 {
     JSTSP_REQUIRE((G2 & 63) == 0 && parts >= 1, JSTSP_E_SHAPE, "grad_head: G2 = %d, parts = %d", G2, parts);
-    HeadDesc d{P, sPt, sPp, parts, Kf, Bdl, sBdl, A, sA, GA, sGA, RV, RVlo, Tc, Res, P1, pmax, G2};
+    HeadDesc d{P, sPt, sPp, parts, Kf, Bdl, sBdl, A, sA, GA, sGA, RV, Tc, Res, P1, pmax, G2};
     hipLaunchKernelGGL(grad_head_kernel, dim3((unsigned)(batch * (G2 >> 6))), dim3(256), 0, ctx->stream, d);
-    JSTSP_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_left2(jstsp_ctx *ctx, int G2, int batch, const float2 *Ghi, const float2 *Glo, long long sG, const float2 *X, float2 *P1,
-                 uint32_t *pmax)
-{
-    JSTSP_REQUIRE((G2 & 63) == 0, JSTSP_E_SHAPE, "left2: G2 = %d", G2);
-    hipLaunchKernelGGL(left2_kernel, dim3((unsigned)(batch * (G2 >> 6))), dim3(256), 0, ctx->stream, Ghi, Glo, sG, X, P1, pmax, G2);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

@@ -559,13 +559,6 @@ __global__ __launch_bounds__(1024) void omp_step_reg_kernel(int meas, int size_d
     }
 }
 
-// JSTSP_OMP_REG=0: the step through global memory (omp_step_kernel<1024>) also where the register form applies
-static bool omp_reg_step()
-{
-    const char *e = xp_getenv("JSTSP_OMP_REG");        // (read at every call)
-    return !e || atoi(e) != 0;
-}
-
 // basis columns omp_step_reg_kernel keeps in LDS: what 160 KiB leave beside its static arrays (inner products 16 KiB, w 8 EPT KiB)
 // (-1: the opt-in to that much dynamic LDS was refused - the caller then takes omp_step_kernel<1024>, which needs none)
 static int omp_reg_qcols(int meas, int m)
@@ -856,7 +849,7 @@ int jstsp_omp_c32(jstsp_ctx *ctx, int meas, int size_d, int batch, const jstsp_c
     JSTSP_HIP(hipMemcpyAsync(s.r, v, (size_t)batch * meas * sizeof(float2), hipMemcpyDeviceToDevice, st));   // r = v (:10)
     JSTSP_HIP(hipMemsetAsync(s.nu, 0, batch * sizeof(int), st));
     JSTSP_HIP(hipMemsetAsync(s.Rm, 0, (size_t)batch * m * m * sizeof(float2), st));
-    bool reg_step = batch <= 64 && meas <= 2048 && omp_reg_step();
+    bool reg_step = batch <= 64 && meas <= 2048;
     int qc = reg_step ? omp_reg_qcols(meas, m) : 0;
     if (qc < 0) { reg_step = false; qc = 0; }
     for (int it = 0; it < m; ++it) {                                                             // :16
@@ -906,10 +899,9 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, 
     JSTSP_ENTER(ctx);
     {
         // Coefficient-domain OMP (omp_gram_kernel): one correlation, the two factor Grams, one kernel for all m
-        // iterations.  JSTSP_OMP_GRAM=0 keeps the measurement-space Gram-Schmidt below (also used when the
-        // Cholesky factor does not fit in LDS).
+        // iterations.  The measurement-space Gram-Schmidt below when the Cholesky factor does not fit in LDS.
         const size_t lds = (size_t)m * m * 16 + 3 * (size_t)m * 16 + 3 * (size_t)m * 4;
-        if (tune().omp_gram != 0 && lds <= 150 * 1024) {
+        if (lds <= 150 * 1024) {
             const int size_d = Gr * G2, nA = strideA ? batch : 1, nB = strideB ? batch : 1;
             const size_t nm = (size_t)N * M, ng = (size_t)N * G2, g = (size_t)size_d;
             const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
@@ -1000,7 +992,7 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, 
         rmax = ctx->arena.get<uint32_t>(batch);
         JSTSP_REQUIRE(rmax, JSTSP_E_NOMEM, "omp_kron: workspace exhausted");
     }
-    bool reg_step = batch <= 64 && meas <= 2048 && omp_reg_step();
+    bool reg_step = batch <= 64 && meas <= 2048;
     int qc = reg_step ? omp_reg_qcols(meas, m) : 0;
     if (qc < 0) { reg_step = false; qc = 0; }
     for (int it = 0; it < m; ++it) {

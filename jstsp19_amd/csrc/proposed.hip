@@ -8,21 +8,10 @@
 // All problems of the batch advance together; every step below is one kernel launch over
 // the whole batch on the context's stream.
 #include "solver_common.h"
-#include <chrono>
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
-
-// JSTSP_HOST_TRACE=1: wall-clock marks of the JSTSP_HOST path on stderr (ms since the first mark of the process)
-static void host_trace(const char *what, int k = -1)
-{
-    static const bool on = [] { const char *e = jstsp::xp_getenv("JSTSP_HOST_TRACE"); return e && atoi(e) != 0; }();
-    if (!on) return;
-    static const auto t0 = std::chrono::steady_clock::now();
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr, "[jstsp host] %9.2f ms  %s%s\n", ms, what, k == 0 ? " (half 0)" : (k == 1 ? " (half 1)" : ""));
-}
 
 namespace jstsp {
 
@@ -32,7 +21,6 @@ struct ProposedWS {
     float *invD;
     // Gr x G2 per problem
     float2 *V, *RV, *Res, *RRes, *S, *P1;
-    float2 *Vlo = nullptr, *RVlo = nullptr;     // low-order parts of v and R v (compensated accumulation: allocated by the solve when used)
     // N x G2 per problem
     float2 *Tc, *W;
     float2 *GA, *GB;
@@ -214,8 +202,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     const bool want_fused = allow_fused && tn.fused != 0 && approx && Imax > 1 && fused_shape_ok(N, M, G2, fparts);
     if (want_fused) need += fused_bytes(M, G2, nB, batch, fparts);
     need += 1024;                                                                 // probe flags of the block-Toeplitz test
-    if (approx && tn.gram_refine && tn.rv_comp) need += 2 * rnd256((size_t)batch * g * sizeof(float2));     // low-order parts of v, R v
-    if (approx && tn.gram_refine)      // low-order part of G_A, G_B's first block row (hi, lo)
+    if (approx)      // low-order part of G_A, G_B's first block row (hi, lo)
         need += rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + 2 * rnd256((size_t)nB * (G2 / 2 + 1) * G2 * sizeof(float2));
     // a JSTSP_HOST dictionary of some size, one per trial, contiguous: tested for the block-Toeplitz structure on the host while
     // it is staged, and uploaded as its first block + leading columns (hostpack.hip)
@@ -235,11 +222,9 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     const float2 *subY, *A, *B;
     const float *Omega;
     const int32_t *indx_S = nullptr;
-    if (memspace == JSTSP_HOST) host_trace("stage: begin");
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(subY_), batch * nm, memspace, &subY));
     JSTSP_TRY(stage_in(ctx, Omega_, batch * nm, memspace, &Omega));
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    if (memspace == JSTSP_HOST) host_trace("stage: subY, Omega, A issued");
     int known_gt = ctx->dict_block_hint;        // (a caller that expanded a block-Toeplitz dictionary itself: c64.hip)
     ctx->dict_block_hint = 0;
     if (host_compact) {
@@ -251,7 +236,6 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     } else
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(B_), szB, memspace, &B));
     if (angles) JSTSP_TRY(stage_in(ctx, indx_S_, batch * g, memspace, &indx_S));
-    if (memspace == JSTSP_HOST) host_trace("stage: dictionary issued");
     if (memspace == JSTSP_DEVICE)
         JSTSP_REQUIRE(((uintptr_t)subY % 16 == 0) && ((uintptr_t)Omega % 8 == 0), JSTSP_E_ARG,
                       "device arrays must be 16-byte aligned");
@@ -279,7 +263,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     JSTSP_HIP(hipMemsetAsync(w.ce, 0, (size_t)batch * 3 * std::max(Imax, 1) * sizeof(double), st));   // ce(:,3) stays 0 for 'std' (:6)
     JSTSP_TRY(launch_inv_d(ctx, (long long)nm, batch, Omega, 2.f, w.prm, w.invD));
     // (the fused pass forms 1 / (Omega + 2 rho) itself, as two floats, when it can read Omega with its 16-byte loads)
-    const bool omega_direct = ((uintptr_t)Omega % 16 == 0) && (nm % 4 == 0) && tn.inv_two_float != 0;
+    const bool omega_direct = ((uintptr_t)Omega % 16 == 0) && (nm % 4 == 0);
     if (angles) JSTSP_TRY(launch_rank_from_index(ctx, (int)g, batch, indx_S, w.rank));
 
     const Mat Am{A, strideA, N}, Bm{B, strideB, G2};
@@ -296,36 +280,17 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     // rounding noise.  Measured (round 4, tools/precision_study.py and tools/parity_fixture_check.py against 2560 float64
     // solves): with G_A from a 64-term fp32 chain and G_B from the split-f16 product, rms |dNMSE| 3.9e-7, max 1.95e-6; the
     // fp32 storage of every array of the iteration together contributes 0.9e-7, a G_B held to 22 bits 1.2e-7.  So, for
-    // 'approximate' (JSTSP_GRAM_REFINE=0: the round-3 products):
+    // 'approximate':
     //  * both Grams are formed in float64 from the fp32 inputs (G_A: gram64.hip, kept as TWO floats hi + lo; G_B: the fp32-MFMA
     //    product with fp64 master accumulators - of the first block row only when the dictionary is block-Toeplitz, the rest
     //    assembled in float64 - rounded once to fp32);
     //  * the iterations use G_A,hi and G_B as its 22-bit split-f16 pack for `R*res` (which only sets the step length); whenever
-    //    R v itself is recomputed from v (every JSTSP_RV_REFRESH-th iteration) it is (G_A,hi + G_A,lo) V, then times G_B as the
+    //    R v itself is recomputed from v (every 4th iteration) it is (G_A,hi + G_A,lo) V, then times G_B as the
     //    fp32-MFMA product with fp64 master accumulators.  Measured on 640 fixture trials, rms |dNMSE| / channel-estimates/s:
     //    plain refresh 2.21e-7 / 841, + fp64-master second factor 1.90e-7 / 823, + G_A,lo 1.76e-7 / 820; a low-order part of
     //    G_B on top changed nothing (1.76e-7 / 808) and is not kept.
-    const bool refine = approx && tn.gram_refine != 0;
-    // the 64-term products of the gradient step on the f16 pipe, fused into one launch (hsmall.hip)
-    const bool use_head = refine && tn.grad_head != 0 && grad_head_shape_ok(N, Gr, G2);      // (bit 0: Res / P1; bit 1: first factor of R v)
-    // JSTSP_RV_COMP=1 (opt-in): v and R v as two floats each (admm.hip: step_v_kernel): the recurrence R v += alpha R res then
-    // tracks R times the v that was actually accumulated to about 48 bits, as the float64 reference's does; the low-order part of
-    // a recomputed R v comes out of the fp64-master product (C_lo), the gradient subtracts both parts (cgemm: D_lo).  Measured
-    // (2560 / 1280 fixture trials + the bench batch): with the default recomputation every 4th iteration max
-    // |dNMSE| 7.8e-7 instead of 8.7e-7 for -1.2 % (two more arrays through the step kernel); with NO recomputation at all
-    // (JSTSP_RV_REFRESH=1000) rms 2.04e-7, max 8.6e-7 over the 2560 sweep trials but 1.2e-6 on one trial of the bench batch, at
-    // 845 instead of 810 channel-estimates/s; recomputing only now and then (every 16th, or at 0, 4, 8, 16, 32, 64) is WORSE than
-    // never (1.5e-6, 2.0e-6): an exact R v is inconsistent with the operator the recurrence's split-f16 products realise, and
-    // every recomputation is a kick of that size.
-    const bool comp = refine && tn.rv_comp != 0 && Imax > 0;
-    float2 *rv_lo_out = nullptr;
-    if (comp) {
-        w.Vlo = ctx->arena.get<float2>((size_t)batch * g);
-        w.RVlo = ctx->arena.get<float2>((size_t)batch * g);
-        JSTSP_REQUIRE(w.Vlo && w.RVlo, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (two-float accumulation)");
-    }
     float2 *GAlo = nullptr;
-    if (refine) {
+    if (approx) {
         GAlo = ctx->arena.get<float2>((size_t)nA * Gr * Gr);
         JSTSP_REQUIRE(GAlo, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (Gram refinement)");
         JSTSP_TRY(gram_f64(ctx, 'L', A, strideA, N, Gr, nA, w.GA, (long long)Gr * Gr, GAlo));
@@ -336,7 +301,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         toep_gt = known_gt;
         toep_probed = true;
     } else
-    if (toep_env != 0 && (long long)G2 * M < (1ll << 31) && refine) {
+    if (toep_env != 0 && (long long)G2 * M < (1ll << 31) && approx) {
         JSTSP_TRY(fused_probe_toeplitz(ctx, ctx->arena, B, strideB, G2, M, nB, &toep_gt));
         toep_probed = true;
     }
@@ -346,7 +311,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         // (the synthesis orientation w.Bs is packed at its first use: with the fused pass that is the last iteration of a
         //  three-output call and never in a two-output call - pack_bs below)
     }
-    if (refine) {
+    if (approx) {
         // (the assembly reads B columns below L = G2 / Gt and above M - L: it needs M >= L - a constant dictionary with fewer columns
         //  than delay blocks passes the probe and takes the full product)
         if (toep_gt && toep_env >= 2 && M >= G2 / toep_gt) {      // (JSTSP_TOEPLITZ=1 stays bit-identical to the unstructured path: full product there)
@@ -432,9 +397,12 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     // R v (`R*v` of :47) is recomputed from v every 4th iteration and carried by R v += alpha R res (the `R*res` of :48
     // is computed anyway) in between.  Measured at configs[1], 6 trials against the float64 oracle, refresh period
     // 1 / 4 / 8 / never: 514 / 529 / 533 / 536 channel-estimates/s, max |dNMSE| 2.4e-7 / 2.7e-7 / 2.7e-7 / 4.4e-7,
-    // max |dS|/max|S| 2.5e-6 / 2.8e-6 / 3.2e-6 / 4.6e-6.  JSTSP_RV_REFRESH=1 recomputes every iteration.
-    const int rv_refresh = std::max(1, tn.rv_refresh);
-    auto refresh_at = [&](int it) -> bool { return it < tn.rv_always || it % rv_refresh == 0; };      // R v recomputed at iteration `it`?
+    // max |dS|/max|S| 2.5e-6 / 2.8e-6 / 3.2e-6 / 4.6e-6.  Over 2560 fixture trials and the bench batch, no recomputation at all
+    // reached max |dNMSE| 1.2e-6 on one bench trial, and recomputing only now and then (every 16th, or at 0, 4, 8, 16, 32, 64) is
+    // worse than never (1.5e-6, 2.0e-6): an exact R v is inconsistent with the operator the recurrence's split-f16 products
+    // realise, and every recomputation is a kick of that size.
+    constexpr int rv_refresh = 4;
+    auto refresh_at = [](int it) -> bool { return it % rv_refresh == 0; };      // R v recomputed at iteration `it`?
     // With the fused pass the work between two passes is three short independent chains (Gram + eigen-decomposition of
     // the next Z | partial sums -> gradient step -> A S | spectral norms): there the side streams are on by default
     // (4.35 -> 4.21 ms per iteration at configs[1]).
@@ -450,8 +418,6 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         JSTSP_TRY(svt_prepare(ctx, w.gz, w.Zb, w.prm, nullptr, true));
     }
     const bool fz = w.gz.left;                  // fused epilogues (need the Z - Q Z orientation)
-    // opt-in: problems whose threshold is below the fp32 resolution of Z skip the Gram + eigen-decomposition (Y = Z)
-    const bool svt_skip = tn.svt_skip != 0;
     const bool hmax = w.h2 && fz && N <= 64;    // the epilogues also deliver max|X|, |V1|, |V2|, |Znext|: split-f16 Grams
     // The svt argument Z = X - V1/rho is never stored on that path: the Gram kernel and the (I - Q) Z product form it
     // from X and V1 on the fly (both were written by the kernel before and are re-read while still close), which saves
@@ -465,8 +431,6 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     // is read once per iteration instead of twice.  The next iteration then starts at the gradient step.
     // Y = (I - Q) Z is formed inside the pass
     // with convergence_error: G_z comes from the three-Gram pass over X, V1 (zfly); without: from the Z the pass stores
-    // (round 3: the opt-in short-cut JSTSP_SVT_SKIP=1 no longer switches the pass off - a skipped trial's Q = 0 becomes
-    //  I - Q = I in the pass's fragments)
     const bool fusedp = want_fused && hmax && (want_ce ? zfly : true);
     const bool fusedy = fusedp;
     FusedWS fw;
@@ -564,11 +528,11 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                 }
               }
               if (stage == 1) return 0;
-                JSTSP_TRY(svt_prepare(ctx, w.gz, w.X, w.prm, nullptr, true, w.zmax, svt_skip, nullptr, true));
+                JSTSP_TRY(svt_prepare(ctx, w.gz, w.X, w.prm, nullptr, true, w.zmax, nullptr, true));
                 // the pass at the end of this iteration forms Y = (I - Q) Z itself: fragments of I - Q
                 if (fusedy) JSTSP_TRY(fused_pack_wq(ctx, fw, w.gz.Q, batch));
             } else {
-                JSTSP_TRY(svt_prepare(ctx, w.gz, Zn, w.prm, nullptr, true, hmax ? w.zmax : nullptr, svt_skip));
+                JSTSP_TRY(svt_prepare(ctx, w.gz, Zn, w.prm, nullptr, true, hmax ? w.zmax : nullptr));
                 if (fusedy) JSTSP_TRY(fused_pack_wq(ctx, fw, w.gz.Q, batch));
             }
             JSTSP_HIP(hipEventRecord(ev_svt, s1));
@@ -581,7 +545,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         if (want_ce && !(zfly && it + 1 < Imax)) {              // s2: Gram of [X | V1]
             JSTSP_HIP(hipStreamWaitEvent(s2, ev_x, 0));
             StreamScope sc(ctx, s2);
-            JSTSP_TRY(gram_partials_range(ctx, w.gn, w.X, snm, 0, 2 * batch, hmax ? w.nmax : nullptr, nullptr, nullptr, nullptr, true));      // (norms only: high f16 plane)
+            JSTSP_TRY(gram_partials_range(ctx, w.gn, w.X, snm, 0, 2 * batch, hmax ? w.nmax : nullptr, nullptr, nullptr, true));      // (norms only: high f16 plane)
             JSTSP_HIP(hipEventRecord(ev_gxv, s2));
         }
         // -- sub 3: res = K2'*k - R*v                                                        (:47)
@@ -591,7 +555,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         //  and VALU products lose against the MFMA GEMM even at k = 64;  2. the last column range of a problem adding the
         //  partial sums inside the pass: the device-scope fence it needs writes the L2 back, 3.95 -> 4.36 ms)
         if (passed) {
-            if (!use_head) JSTSP_TRY(fused_reduce(ctx, fw, G2, M, batch, w.Tc));      // (hsmall.hip sums the partial sums itself)
+            JSTSP_TRY(fused_reduce(ctx, fw, G2, M, batch, w.Tc));
         } else if (PB) {       // 'std' with a float64 pinv of B:  Tc = K pinv(B)
             JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, M, batch, Mat{w.ZK, snm, N}, Mat{PB, strideB ? (long long)M * G2 : 0, M},
                            w.Tc, sng, N, 1.f, nullptr, 0, 0, 0.f, GEMM_CORRELATE));
@@ -610,7 +574,6 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         } else
         JSTSP_TRY(gemm(ctx, 'N', 'C', N, G2, M, batch, Mat{w.ZK, snm, N}, Bm, w.Tc, sng, N, 1.f, nullptr, 0, 0,
                        0.f, GEMM_CORRELATE));
-        auto fused_reduce_if = [&](bool p) -> int { return p ? fused_reduce(ctx, fw, G2, M, batch, w.Tc) : 0; };
         const long long cnt_ll = std::min<long long>(10 + 5ll * (it + 1), (long long)g);
         // (G_A X) G_B: the G2 x G2 factor is packed once per solve; max|G_A X| comes from the first product's epilogue.
         // exact (R v itself is being formed from v): with the low-order parts of both Grams (see the setup above), the first factor
@@ -621,7 +584,6 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             if (exact || !w.h2g) {
                 GemmDesc dr = make_gemm('N', 'N', Gr, G2, G2, batch, Mat{w.P1, sg, Gr}, GBm, out, sg, Gr);
                 dr.force_m64 = exact ? 1 : 0;
-                if (exact) dr.C_lo = rv_lo_out;         // (R v itself: what the fp32 result leaves of the float64 sums)
                 return launch_cgemm(ctx, dr, GEMM_MISC);
             }
             HGemmDesc hg{w.P1, sg, Gr, pm, w.GBp.data, strideB ? w.GBp.st : 0, w.GBp.bmax, strideB ? 1 : 0,
@@ -630,47 +592,22 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         };
         auto apply_R = [&](const float2 *Xin, float2 *out, bool exact) -> int {
             uint32_t *pm = w.pmax ? w.pmax + (size_t)(apply_no++ & 1) * batch : nullptr;      // two applies per iteration, one slot each
-            if (use_head && exact && (tn.grad_head & 2)) {
-                JSTSP_TRY(launch_left2(ctx, G2, batch, w.GA, GAlo, strideA ? (long long)Gr * Gr : 0, Xin, w.P1, pm));
-            } else {
-                const bool alo = exact;
-                if (alo) JSTSP_TRY(gemm(ctx, 'N', 'N', Gr, G2, Gr, batch, GAl, Mat{Xin, sg, Gr}, w.P1, sg, Gr));      // P1 = G_A,lo X
-                GemmDesc dp = make_gemm('N', 'N', Gr, G2, Gr, batch, GAm, Mat{Xin, sg, Gr}, w.P1, sg, Gr, 1.f, alo ? w.P1 : nullptr, sg,
-                                        Gr, alo ? 1.f : 0.f);
-                dp.amax_out = w.h2g ? pm : nullptr;
-                JSTSP_TRY(launch_cgemm(ctx, dp, GEMM_MISC));
-            }
+            if (exact) JSTSP_TRY(gemm(ctx, 'N', 'N', Gr, G2, Gr, batch, GAl, Mat{Xin, sg, Gr}, w.P1, sg, Gr));      // P1 = G_A,lo X
+            GemmDesc dp = make_gemm('N', 'N', Gr, G2, Gr, batch, GAm, Mat{Xin, sg, Gr}, w.P1, sg, Gr, 1.f, exact ? w.P1 : nullptr, sg,
+                                    Gr, exact ? 1.f : 0.f);
+            dp.amax_out = w.h2g ? pm : nullptr;
+            JSTSP_TRY(launch_cgemm(ctx, dp, GEMM_MISC));
             return second_factor(out, pm, exact);
         };
         if (approx) {
             // R v: recomputed from v every `rv_refresh` iterations, carried by R v += alpha R res in between (both are
             // `R*v` of :47; the recurrence alone drifts in fp32)
             const bool refreshed = refresh_at(it);
-            if (refreshed) {
-                rv_lo_out = comp ? w.RVlo : nullptr;
-                JSTSP_TRY(apply_R(w.V, w.RV, refine));
-                rv_lo_out = nullptr;
-            }
-            if (use_head && !(tn.grad_head & 1)) JSTSP_TRY(fused_reduce_if(passed));
-            if (use_head && (tn.grad_head & 1)) {
-                // Res = A^H Tc - R v and P1 = G_A Res in one kernel on the f16 pipe, straight from the pass's partial sums
-                uint32_t *pm = w.pmax ? w.pmax + (size_t)(apply_no++ & 1) * batch : nullptr;
-                if (passed)
-                    JSTSP_TRY(launch_grad_head(ctx, G2, batch, fw.Ppart, (long long)fw.parts * sng, sng, fw.parts, fw.v2 ? fw.Kf : nullptr,
-                                               fw.Bdl, fw.sBdl, A, strideA, w.GA, strideA ? (long long)Gr * Gr : 0, w.RV, nullptr, w.Res,
-                                               w.P1, pm, comp ? w.RVlo : nullptr));
-                else
-                    JSTSP_TRY(launch_grad_head(ctx, G2, batch, w.Tc, sng, 0, 1, nullptr, nullptr, 0, A, strideA, w.GA,
-                                               strideA ? (long long)Gr * Gr : 0, w.RV, nullptr, w.Res, w.P1, pm, comp ? w.RVlo : nullptr));
-                //    R*res for alpha = res'*res / (res'*R*res)                                (:48)
-                JSTSP_TRY(second_factor(w.RRes, pm, false));
-            } else {
-                GemmDesc dres = make_gemm('C', 'N', Gr, G2, N, batch, Am, Mat{w.Tc, sng, N}, w.Res, sg, Gr, 1.f, w.RV, sg, Gr, -1.f);
-                dres.D_lo = comp ? w.RVlo : nullptr;
-                JSTSP_TRY(launch_cgemm(ctx, dres, GEMM_MISC));
-                //    R*res for alpha = res'*res / (res'*R*res)                                (:48)
-                JSTSP_TRY(apply_R(w.Res, w.RRes, false));
-            }
+            if (refreshed) JSTSP_TRY(apply_R(w.V, w.RV, true));
+            GemmDesc dres = make_gemm('C', 'N', Gr, G2, N, batch, Am, Mat{w.Tc, sng, N}, w.Res, sg, Gr, 1.f, w.RV, sg, Gr, -1.f);
+            JSTSP_TRY(launch_cgemm(ctx, dres, GEMM_MISC));
+            //    R*res for alpha = res'*res / (res'*R*res)                                (:48)
+            JSTSP_TRY(apply_R(w.Res, w.RRes, false));
             if (svt_split) {
                 JSTSP_HIP(hipEventRecord(ev_q1, sm));
                 JSTSP_HIP(hipStreamWaitEvent(s1, ev_q1, 0));
@@ -678,8 +615,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             }
             //    v += alpha res; ce(i,3); s = soft(v) (.* Omega_S)                            (:49-56, angles :36,:68)
             JSTSP_TRY(launch_step_v(ctx, (int)g, batch, w.Res, w.RRes, w.V, w.S, w.rank, (int)cnt_ll, w.prm, w.ce,
-                                    Imax, it, (rv_refresh > 1 || comp) ? w.RV : nullptr, svt_split, comp ? w.Vlo : nullptr,
-                                    comp ? w.RVlo : nullptr, refreshed ? 1 : 0));
+                                    Imax, it, w.RV, svt_split));
         } else {
             //    v = U\(L\k) = pinv(A) K pinv(B)   [ = G_A^-1 (A^H Tc) G_B^-1 on the Gram route: GA / GB hold the inverses ]  (:53)
             float2 *left = PB ? w.V : w.P1;        // result of the A side; the B side (if any) finishes into V
@@ -751,7 +687,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             JSTSP_HIP(hipStreamWaitEvent(s2, ev_c, 0));
             if (zfly) JSTSP_HIP(hipStreamWaitEvent(s2, ev_gxv, 0));      // G_x, G_v1 came from the side stream s1
             StreamScope sc(ctx, s2);
-            JSTSP_TRY(gram_partials_range(ctx, w.gn, w.X, snm, 2 * batch, batch, hmax ? w.nmax : nullptr, nullptr, nullptr, nullptr, true));
+            JSTSP_TRY(gram_partials_range(ctx, w.gn, w.X, snm, 2 * batch, batch, hmax ? w.nmax : nullptr, nullptr, nullptr, true));
             JSTSP_HIP(hipEventRecord(ev_gv2, s2));
             if (fusedp && zfly && it + 1 < Imax) JSTSP_TRY(lmax_from_partials_range(ctx, w.gn, 2 * batch, batch, w.lam, true));
             else JSTSP_TRY(lmax_from_partials(ctx, w.gn, w.lam, true));
@@ -812,15 +748,12 @@ static int resolve_overflowed(jstsp_ctx *ctx, const std::vector<int> &ovf, int N
 static int proposed_finish(jstsp_ctx *ctx, const PendingSolve &p, jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, std::vector<int> *ovf)
 {
     JSTSP_ENTER(ctx);
-    host_trace("finish: begin");
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(S_out), p.dS, p.batch * p.g, JSTSP_HOST));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Y_out), p.dY, p.batch * p.nm, JSTSP_HOST));
     if (p.want_ce) JSTSP_TRY(stage_out(ctx, ce_out, p.dce, (size_t)p.batch * 3 * p.Imax, JSTSP_HOST));
     std::vector<uint32_t> flags(p.ovf ? p.batch : 0);
     if (p.ovf) JSTSP_HIP(hipMemcpyAsync(flags.data(), p.ovf, (size_t)p.batch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    host_trace("finish: copies issued");
     JSTSP_HIP(hipStreamSynchronize(ctx->stream));
-    host_trace("finish: synchronised");
     for (int t = 0; t < (int)flags.size(); ++t)
         if (flags[t]) ovf->push_back(t);
     return 0;
@@ -859,14 +792,12 @@ extern "C" int jstsp_proposed_algorithm_c32(jstsp_ctx *ctx, int N, int M, int Gr
         };
 #define JSTSP_TRY_PIPE(expr) do { int rc_ = drained(expr); if (rc_ != 0) return rc_; } while (0)
         for (int k = 0; k < 2; ++k) {
-            host_trace("enqueue", k);
             cx[k]->fused_fallbacks = 0; cx[k]->last_dict_block = 0;
             JSTSP_TRY_PIPE(proposed_impl(cx[k], N, M, Gr, G2, cnt[k], subY + t0[k] * nm, Omega + t0[k] * nm, A + (size_t)t0[k] * strideA, strideA,
                                     B + (size_t)t0[k] * strideB, strideB, Imax, tau_Y + t0[k], tau_S + t0[k], rho + t0[k], type,
                                     indx_S ? indx_S + t0[k] * g : nullptr, S_out + t0[k] * g, Y_out + t0[k] * nm,
                                     ce_out ? ce_out + (size_t)t0[k] * 3 * Imax : nullptr, JSTSP_HOST, true, nullptr, &pend[k]));
         }
-        host_trace("both halves enqueued");
         int fallbacks = 0;
         for (int k = 0; k < 2; ++k) {
             std::vector<int> o;
@@ -987,9 +918,7 @@ int proposed_pending_flags(jstsp_ctx *ctx, const PendingSolve &p, std::vector<in
     JSTSP_ENTER(ctx);
     std::vector<uint32_t> flags(p.ovf ? p.batch : 0);
     if (p.ovf) JSTSP_HIP(hipMemcpyAsync(flags.data(), p.ovf, (size_t)p.batch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    host_trace("finish: copies issued");
     JSTSP_HIP(hipStreamSynchronize(ctx->stream));
-    host_trace("finish: synchronised");
     for (int t = 0; t < (int)flags.size(); ++t)
         if (flags[t]) ovf->push_back(t);
     return 0;

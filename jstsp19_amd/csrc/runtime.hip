@@ -36,18 +36,6 @@ void load_tuning()
     t.bj_mask = env_int("JSTSP_BJ_MASK", t.bj_mask);
     t.host_pipeline = env_int("JSTSP_HOST_PIPELINE", t.host_pipeline);
     t.host_compact = env_int("JSTSP_HOST_COMPACT", t.host_compact);
-#ifdef JSTSP_EXPERIMENTS        // measured and dropped, or outside the accuracy statement: tools/ only (common.h)
-    t.rv_refresh = env_int("JSTSP_RV_REFRESH", t.rv_refresh);
-    t.svt_skip = env_int("JSTSP_SVT_SKIP", t.svt_skip);
-    t.omp_gram = env_int("JSTSP_OMP_GRAM", t.omp_gram);
-    t.bj_trace = env_int("JSTSP_BJ_TRACE", t.bj_trace);
-    t.gram_refine = env_int("JSTSP_GRAM_REFINE", t.gram_refine);
-    t.pass_acc = env_int("JSTSP_PASS_ACC", t.pass_acc);
-    t.inv_two_float = env_int("JSTSP_INV2", t.inv_two_float);
-    t.grad_head = env_int("JSTSP_GRAD_HEAD", t.grad_head);
-    t.rv_always = env_int("JSTSP_RV_ALWAYS", t.rv_always);
-    t.rv_comp = env_int("JSTSP_RV_COMP", t.rv_comp);
-#endif
     g_tune = t;
 }
 
@@ -158,7 +146,7 @@ GemmDesc make_gemm(char opA, char opB, int m, int n, int k, int batch, Mat A, Ma
     d.splitk = splitk < 1 ? 1 : splitk; d.sCsplit = sCsplit;
     d.epi = EPI_NONE; d.prm = nullptr; d.e_rw0 = d.e_w1 = d.e_w2 = d.e_w3 = nullptr;
     d.e_r0 = d.e_r1 = d.e_r2 = d.e_r3 = nullptr; d.e_f0 = nullptr; d.epi_store_c = 1; d.amax_out = nullptr; d.amax_x = d.amax_v1 = d.amax_z = nullptr;
-    d.force_m64 = 0; d.C_lo = nullptr; d.herm_upper = 0; d.D_lo = nullptr;
+    d.force_m64 = 0; d.C_lo = nullptr; d.herm_upper = 0;
     d.sa_mode = 0; d.sa_lr = d.sa_lt = nullptr; d.sa_rho = d.sa_thr = 0.f;
     return d;
 }
@@ -248,11 +236,11 @@ int gram_partials(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, long long sZ
 }
 
 int gram_partials_range(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, long long sZt, int t0, int count,
-                        const uint32_t *amax, const TrialParams *skip_prm, const float2 *Z2, const TrialParams *zprm, bool norm_only)
+                        const uint32_t *amax, const float2 *Z2, const TrialParams *zprm, bool norm_only)
 {
     if (amax && w.left && w.n <= 64)       // split-f16 path: amax[t0 + i] bounds problem t0 + i
         return launch_hgram(ctx, Z + (long long)t0 * sZt, sZt, w.rows, w.cols, count, w.nsplit, amax + t0,
-                            w.Gpart + (long long)t0 * w.n * w.n * w.nsplit, skip_prm ? skip_prm + t0 : nullptr,
+                            w.Gpart + (long long)t0 * w.n * w.n * w.nsplit,
                             Z2 ? Z2 + (long long)t0 * sZt : nullptr, zprm ? zprm + t0 : nullptr, norm_only);
     JSTSP_REQUIRE(!Z2, JSTSP_E_ARG, "gram_partials_range: on-the-fly Z needs the split-f16 Gram path");
     const Mat Zm{Z + (long long)t0 * sZt, sZt, w.rows};
@@ -299,18 +287,17 @@ int lmax_from_partials_range(jstsp_ctx *ctx, const GramWS &w, int first, int cou
 }
 
 int svt_prepare(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, const TrialParams *prm, const float *tau,
-                bool sequence, const uint32_t *amax, bool allow_skip, const float2 *Z2, bool gram_done)
+                bool sequence, const uint32_t *amax, const float2 *Z2, bool gram_done)
 {
     const long long sZ = (long long)w.rows * w.cols;
     const long long sG = (long long)w.n * w.n;
-    const bool skip = allow_skip && amax && prm && !tau && w.left && w.n <= 64;
     JSTSP_REQUIRE(!Z2 || (amax && prm), JSTSP_E_ARG, "svt_prepare: on-the-fly Z needs the split-f16 Gram path");
     if (gram_done) { /* nothing */ }
-    else if (amax) JSTSP_TRY(gram_partials_range(ctx, w, Z, sZ, 0, w.batch, amax, skip ? prm : nullptr, Z2, Z2 ? prm : nullptr));
+    else if (amax) JSTSP_TRY(gram_partials_range(ctx, w, Z, sZ, 0, w.batch, amax, Z2, Z2 ? prm : nullptr));
     else JSTSP_TRY(gram_partials(ctx, w, Z, sZ));
     if (w.n <= 64) {
         JSTSP_TRY(launch_eig_fast(ctx, EIG_SVT_Q, w.n, w.batch, w.Gpart, sG * w.nsplit, w.nsplit, sG, prm, tau,
-                                  w.Q, nullptr, w.Uwarm, sequence ? w.warm : 0, skip ? amax : nullptr));
+                                  w.Q, nullptr, w.Uwarm, sequence ? w.warm : 0));
         w.warm = sequence ? 1 : 0;
         return 0;
     }

@@ -29,10 +29,7 @@ int gram_f64(jstsp_ctx *ctx, char side, const float2 *X, long long sXt, int rows
 bool grad_head_shape_ok(int N, int Gr, int G2);
 int launch_grad_head(jstsp_ctx *ctx, int G2, int batch, const float2 *P, long long sPt, long long sPp, int parts, const float2 *Kf,
                      const float2 *Bdl, long long sBdl, const float2 *A, long long sA, const float2 *GA, long long sGA,
-                     const float2 *RV, float2 *Tc, float2 *Res, float2 *P1, uint32_t *pmax, const float2 *RVlo = nullptr);
-//   P1 = (G_hi + G_lo) X, G Hermitian 64 x 64 in two floats (sG = 0: shared), X and P1 64 x G2 per trial
-int launch_left2(jstsp_ctx *ctx, int G2, int batch, const float2 *Ghi, const float2 *Glo, long long sG, const float2 *X, float2 *P1,
-                 uint32_t *pmax);
+                     const float2 *RV, float2 *Tc, float2 *Res, float2 *P1, uint32_t *pmax);
 
 // Descriptor only (the caller may attach a fused epilogue before launch_cgemm).
 GemmDesc make_gemm(char opA, char opB, int m, int n, int k, int batch, Mat A, Mat B, float2 *C, long long sCt,
@@ -68,13 +65,13 @@ int svt_batched(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, const TrialPar
 // The two halves of svt_batched: Gram + eigen-decomposition -> projector Q; then Y = Z - Q Z.
 // amax != nullptr (per-problem bound on max(|re|,|im|) of Z): Gram on the split-f16 path when rows <= 64
 int svt_prepare(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, const TrialParams *prm, const float *tau,
-                bool sequence, const uint32_t *amax = nullptr, bool allow_skip = false, const float2 *Z2 = nullptr,
+                bool sequence, const uint32_t *amax = nullptr, const float2 *Z2 = nullptr,
                 bool gram_done = false);   // gram_done: the partials of G are already in the workspace
                 // Z2 (split-f16 Gram path only): the svt argument is Z - prm[t].irho * Z2, never stored
 int svt_apply(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, float2 *Y);
 // Gram partials of problems [t0, t0 + count) only (same workspace layout as gram_partials).
 int gram_partials_range(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, long long sZt, int t0, int count,
-                        const uint32_t *amax = nullptr, const TrialParams *skip_prm = nullptr, const float2 *Z2 = nullptr,
+                        const uint32_t *amax = nullptr, const float2 *Z2 = nullptr,
                         const TrialParams *zprm = nullptr, bool norm_only = false);
 // lam[t] = lambda_max of the Gram partials already in the workspace, all w.batch problems
 // The warm-start record of a norm workspace: all vectors invalid, the context's mismatch counter zeroed (on ctx->stream;

@@ -27,41 +27,6 @@ __global__ __launch_bounds__(256) void sadmm_soft_rhs_kernel(long long n, const 
     }
 }
 
-// T ./ (lr_i lt_j - rho), per problem nm = Mr*Mt
-__global__ __launch_bounds__(256) void sadmm_scale_kernel(long long total, int Mr, int Mt, float2 *T,
-                                                          const float *lr, const float *lt, float rho)
-{
-    const long long stride = (long long)gridDim.x * 256;
-    const long long nm = (long long)Mr * Mt;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const long long e = i % nm;
-        const float den = sadmm_den(lr[e % Mr], lt[e / Mr], rho);
-        const float2 v = T[i];
-        T[i] = make_float2(v.x / den, v.y / den);
-    }
-}
-
-// Z = Z + rho (R - S) (:30)
-__global__ __launch_bounds__(256) void sadmm_dual_kernel(long long n, float2 *Z, const float2 *R,
-                                                         const float2 *S, float rho)
-{
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float2 z = Z[i];
-        const float2 r = R[i], s = S[i];
-        z.x = sadmm_dual1(z.x, r.x, s.x, rho);
-        z.y = sadmm_dual1(z.y, r.y, s.y, rho);
-        Z[i] = z;
-    }
-}
-
-__global__ __launch_bounds__(256) void sadmm_diff_kernel(long long n, const float2 *a, const float2 *b, float2 *o)
-{
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-        o[i] = make_float2(a[i].x - b[i].x, a[i].y - b[i].y);
-}
-
 __global__ void sadmm_ratio_kernel(int batch, const float *num, const float *den, double *ce, int Imax, int it)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -149,30 +114,25 @@ extern "C" int jstsp_sparse_admm_c32(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
     if (want_ce) JSTSP_TRY(sigma_max_sq(ctx, wn, Htrue, den));
     if (want_ce) JSTSP_TRY(lanczos_warm_reset(ctx, wn));       // the error curve's lambda_max, warm-started from iteration to iteration
 
-    // JSTSP_SADMM_FUSE=0: every element-wise step as its own kernel.  Default: they ride on the products' epilogues (EPI_SADMM,
-    // common.h) - the diagonal solve on the second transform, the dual update AND the next iteration's soft threshold / right-hand
-    // side on the fourth (R itself is then never stored; S alternates between two buffers because convergence_error still reads
-    // this iteration's S), the difference to Htrue on the error product.  Same expressions (sadmm_*1), same bits.
-    const char *fuse_env = xp_getenv("JSTSP_SADMM_FUSE");          // (read at every call)
-    const bool fuse = !fuse_env || atoi(fuse_env) != 0;
-    float2 *Sb[2] = {S, fuse ? R : S};
+    // The element-wise steps ride on the products' epilogues (EPI_SADMM, common.h): the diagonal solve on the second transform,
+    // the dual update AND the next iteration's soft threshold / right-hand side on the fourth (R itself is then never stored;
+    // S alternates between two buffers because convergence_error still reads this iteration's S), the difference to Htrue on
+    // the error product.  Same expressions as the reference's steps (sadmm_*1).
+    float2 *Sb[2] = {S, R};
     const float2 *Sfin = S;
-    // convergence_error of iteration it needs S(it) only, the solve goes on from S(it) without it: with the fused epilogues (two
-    // S buffers) the error chain - two products, the Gram, lambda_max - runs on a side stream beside the next solve
-    // (JSTSP_SADMM_OVERLAP=0: in line).  ev_s[it & 1]: S(it) is complete; ev_r[it & 1]: the error chain has read S(it), whose
-    // buffer the epilogue of iteration it + 1 overwrites.
-    const char *ov_env = xp_getenv("JSTSP_SADMM_OVERLAP");
-    const bool overlap = fuse && want_ce && (!ov_env || atoi(ov_env) != 0);
-    if (overlap) JSTSP_TRY(ensure_side_streams(ctx));
-    hipStream_t sc = overlap ? ctx->side[0] : st;
+    // convergence_error of iteration it needs S(it) only, the solve goes on from S(it) without it: the error chain - two
+    // products, the Gram, lambda_max - runs on a side stream beside the next solve.  ev_s[it & 1]: S(it) is complete;
+    // ev_r[it & 1]: the error chain has read S(it), whose buffer the epilogue of iteration it + 1 overwrites.
+    if (want_ce) JSTSP_TRY(ensure_side_streams(ctx));
+    hipStream_t sc = want_ce ? ctx->side[0] : st;
     hipEvent_t ev_s[2] = {ctx->ev[0], ctx->ev[1]}, ev_r[2] = {ctx->ev[2], ctx->ev[3]};
     for (int it = 0; it < Imax; ++it) {                                            // :18
         float2 *Sc = Sb[it & 1], *Sn = Sb[(it + 1) & 1];
         Sfin = Sc;
-        if (!fuse || it == 0)
+        if (it == 0)
             hipLaunchKernelGGL(sadmm_soft_rhs_kernel, g1(tot), dim3(256), 0, st, tot, R, Z, AhOH, Sc, RHS, rho,
                                tau_s / rho);                                       // :21-23
-        if (overlap) {
+        if (want_ce) {                                                             // :32
             if (it == 0) JSTSP_HIP(hipEventRecord(ev_s[0], st));
             JSTSP_HIP(hipStreamWaitEvent(sc, ev_s[it & 1], 0));
             StreamScope scope(ctx, sc);
@@ -183,44 +143,22 @@ extern "C" int jstsp_sparse_admm_c32(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
             hipLaunchKernelGGL(sadmm_ratio_kernel, dim3((batch + 255) / 256), dim3(256), 0, sc, batch, num, den, ce, Imax, it);
         }
         // (the last iteration's R and Z feed nothing that is returned: S and convergence_error are complete before them)
-        if (!fuse || it + 1 < Imax) {
+        if (it + 1 < Imax) {
             // :26  R = Ur [ (Ur^H RHS conj(Ut)) ./ (lr lt^T - rho) ] Ut^T
             JSTSP_TRY(gemm(ctx, 'C', 'N', Mr, Mt, Mr, batch, Urm, Mat{RHS, snm, Mr}, P, snm, Mr));
-            if (fuse) {
-                GemmDesc d2 = make_gemm('N', 'J', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, RHS, snm, Mr);
-                d2.epi = EPI_SADMM; d2.sa_mode = 1; d2.sa_lr = lr; d2.sa_lt = lt; d2.sa_rho = rho;
-                JSTSP_TRY(launch_cgemm(ctx, d2, GEMM_MISC));
-            } else {
-                JSTSP_TRY(gemm(ctx, 'N', 'J', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, RHS, snm, Mr));
-                hipLaunchKernelGGL(sadmm_scale_kernel, g1(tot), dim3(256), 0, st, tot, Mr, Mt, RHS, lr, lt, rho);
-            }
+            GemmDesc d2 = make_gemm('N', 'J', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, RHS, snm, Mr);
+            d2.epi = EPI_SADMM; d2.sa_mode = 1; d2.sa_lr = lr; d2.sa_lt = lt; d2.sa_rho = rho;
+            JSTSP_TRY(launch_cgemm(ctx, d2, GEMM_MISC));
             JSTSP_TRY(gemm(ctx, 'N', 'N', Mr, Mt, Mr, batch, Urm, Mat{RHS, snm, Mr}, P, snm, Mr));
-            if (fuse) {
-                GemmDesc d4 = make_gemm('N', 'T', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, RHS, snm, Mr);   // (C unused: R is not stored)
-                d4.epi = EPI_SADMM; d4.sa_mode = 2; d4.sa_rho = rho; d4.sa_thr = tau_s / rho;
-                d4.e_rw0 = Z; d4.e_r0 = Sc; d4.e_w1 = Sn; d4.e_r2 = AhOH; d4.e_w2 = RHS;
-                if (overlap && it > 0) JSTSP_HIP(hipStreamWaitEvent(st, ev_r[(it + 1) & 1], 0));    // S(it - 1) has been read
-                JSTSP_TRY(launch_cgemm(ctx, d4, GEMM_MISC));
-                if (overlap) JSTSP_HIP(hipEventRecord(ev_s[(it + 1) & 1], st));
-            } else {
-                JSTSP_TRY(gemm(ctx, 'N', 'T', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, R, snm, Mr));
-                hipLaunchKernelGGL(sadmm_dual_kernel, g1(tot), dim3(256), 0, st, tot, Z, R, Sc, rho);   // :30
-            }
-        }
-        if (want_ce && !overlap) {                                                 // :32
-            JSTSP_TRY(gemm(ctx, 'N', 'N', Mr, Mt, Mr, batch, Drm, Mat{Sc, snm, Mr}, P, snm, Mr));
-            if (fuse)
-                JSTSP_TRY(gemm(ctx, 'N', 'C', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Dtm, Dd, snm, Mr, 1.f, Htrue, snm, Mr, -1.f));
-            else {
-                JSTSP_TRY(gemm(ctx, 'N', 'C', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Dtm, Dd, snm, Mr));
-                hipLaunchKernelGGL(sadmm_diff_kernel, g1(tot), dim3(256), 0, st, tot, Dd, Htrue, Dd);
-            }
-            JSTSP_TRY(sigma_max_sq(ctx, wn, Dd, num, true));
-            hipLaunchKernelGGL(sadmm_ratio_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, num, den, ce,
-                               Imax, it);
+            GemmDesc d4 = make_gemm('N', 'T', Mr, Mt, Mt, batch, Mat{P, snm, Mr}, Utm, RHS, snm, Mr);   // (C unused: R is not stored)
+            d4.epi = EPI_SADMM; d4.sa_mode = 2; d4.sa_rho = rho; d4.sa_thr = tau_s / rho;
+            d4.e_rw0 = Z; d4.e_r0 = Sc; d4.e_w1 = Sn; d4.e_r2 = AhOH; d4.e_w2 = RHS;           // :30, then :21-23 of it + 1
+            if (want_ce && it > 0) JSTSP_HIP(hipStreamWaitEvent(st, ev_r[(it + 1) & 1], 0));    // S(it - 1) has been read
+            JSTSP_TRY(launch_cgemm(ctx, d4, GEMM_MISC));
+            if (want_ce) JSTSP_HIP(hipEventRecord(ev_s[(it + 1) & 1], st));
         }
     }
-    if (overlap && Imax > 0) {          // the error chain joins the main stream
+    if (want_ce && Imax > 0) {          // the error chain joins the main stream
         JSTSP_HIP(hipEventRecord(ev_r[0], sc));
         JSTSP_HIP(hipStreamWaitEvent(st, ev_r[0], 0));
     }

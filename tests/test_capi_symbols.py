@@ -80,31 +80,36 @@ def test_device_code_has_no_packed_fp32_instructions(tmp_path):
     assert mfma >= 5        # the disassembly really is the kernels'
 
 
-def test_every_environment_switch_the_library_reads_is_documented_in_the_header():
-    """include/jstsp.h lists the JSTSP_* switches of the SHIPPED library: at most 15, every name that a getenv / env_int call of
-    jstsp19_amd/csrc reads outside `#ifdef JSTSP_EXPERIMENTS` must be in that list, and every one must be toggled by a test.
-    The switches of the experiments build (xp_getenv, or env_int inside `#ifdef JSTSP_EXPERIMENTS`) must be named in the
-    header's "Experiments build" paragraph - and nowhere in tests/ (the tests run the shipped library)."""
+# The switches of the experiments that were measured and dropped (HISTORY.md): their code is gone from the library.
+REMOVED_SWITCHES = ("JSTSP_GRAM_REFINE", "JSTSP_RV_REFRESH", "JSTSP_RV_ALWAYS", "JSTSP_RV_COMP", "JSTSP_GRAD_HEAD", "JSTSP_SVT_SKIP",
+                    "JSTSP_PASS_ACC", "JSTSP_INV2", "JSTSP_HGEMM_MAP", "JSTSP_HGEMM_PAIR", "JSTSP_OMP_REG", "JSTSP_OMP_GRAM",
+                    "JSTSP_SADMM_FUSE", "JSTSP_SADMM_OVERLAP", "JSTSP_M3_MINK", "JSTSP_HOST_TRACE", "JSTSP_BJ_TRACE", "JSTSP_FUSED_DBG")
+
+
+def test_one_build_and_every_environment_switch_is_documented_and_tested():
+    """The library has one build, and include/jstsp.h lists its JSTSP_* switches: 10 to 15 of them, every name that a getenv /
+    env_int call of jstsp19_amd/csrc reads must be in that list, and every one must be toggled by a test.  One build: no
+    xp_getenv, JSTSP_EXPERIMENTS or JSTSP_PK_FP32_FILES in jstsp19_amd/csrc or its build script, no "Experiments build"
+    paragraph in the header, and no switch of a dropped experiment named in jstsp19_amd/csrc, the header or tests/."""
     import glob
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    shipped, xp = set(), set()
+    shipped = set()
     pat = r'(?<![a-z_])(?:getenv|env_int|env_flt)\("(JSTSP_[A-Z0-9_]+)"'
-    for f in glob.glob(os.path.join(root, "jstsp19_amd", "csrc", "*.hip")) + glob.glob(os.path.join(root, "jstsp19_amd", "csrc", "*.h")):
+    srcs = glob.glob(os.path.join(root, "jstsp19_amd", "csrc", "*.hip")) + glob.glob(os.path.join(root, "jstsp19_amd", "csrc", "*.h"))
+    for f in srcs + [os.path.join(root, "jstsp19_amd", "build.py"), os.path.join(root, "jstsp19_amd", "_lib.py")]:
         src = open(f).read()
-        xp |= set(re.findall(r'xp_getenv\("(JSTSP_[A-Z0-9_]+)"', src))
-        for blk in re.findall(r'#ifdef JSTSP_(?:EXPERIMENTS|FUSED_DBG_BUILD)\b(.*?)#endif', src, flags=re.S):
-            xp |= set(re.findall(pat, blk))
-        src = re.sub(r'#ifdef JSTSP_(?:EXPERIMENTS|FUSED_DBG_BUILD)\b.*?#endif', '', src, flags=re.S)
-        shipped |= set(re.findall(pat, src))
+        for name in ("xp_getenv", "JSTSP_EXPERIMENTS", "JSTSP_PK_FP32_FILES") + REMOVED_SWITCHES:
+            assert name not in src, (os.path.basename(f), name)
+        if f in srcs:
+            shipped |= set(re.findall(pat, src))
     header = open(os.path.join(root, "include", "jstsp.h")).read()
     env = header[header.index("---- Environment"):header.index("---- kernel-level entry points")]
-    main, exper = env.split("Experiments build.")
+    assert "Experiments build" not in header
+    assert not [n for n in REMOVED_SWITCHES if n in header], [n for n in REMOVED_SWITCHES if n in header]
     assert 10 <= len(shipped) <= 15, sorted(shipped)
-    assert not [n for n in shipped if ("  " + n) not in main], sorted(shipped)
-    assert not [n for n in xp if n not in exper], sorted(xp)
-    assert not (shipped & xp)
+    assert not [n for n in shipped if ("  " + n) not in env], sorted(shipped)
+    assert not (shipped & set(REMOVED_SWITCHES))
     tests = "".join(open(f).read() for f in glob.glob(os.path.join(root, "tests", "test_*.py")) if not f.endswith("test_capi_symbols.py"))
     assert not [n for n in shipped if n not in tests], [n for n in shipped if n not in tests]
-    assert not [n for n in xp if n in tests], [n for n in xp if n in tests]
-
+    assert not [n for n in REMOVED_SWITCHES if n in tests], [n for n in REMOVED_SWITCHES if n in tests]

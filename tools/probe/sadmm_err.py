@@ -23,4 +23,4 @@ for t in range(B):
     So, ceo = O.sparse_admm(H[t].cpu().numpy().astype(np.complex128), OH[t].cpu().numpy().astype(np.complex128), Dn, Dn, 100)
     es.append(np.max(np.abs(S[t].cpu().numpy() - So)) / np.max(np.abs(So)))
     ec.append(np.max(np.abs(ce[t].cpu().numpy() - ceo) / np.abs(ceo)))
-print("JSTSP_M3_MINK=%s: S max %.3e mean %.3e; ce max %.3e mean %.3e" % (os.environ.get("JSTSP_M3_MINK"), max(es), np.mean(es), max(ec), np.mean(ec)))
+print("S max %.3e mean %.3e; ce max %.3e mean %.3e" % (max(es), np.mean(es), max(ec), np.mean(ec)))

@@ -3,7 +3,7 @@
 // in 256 registers per lane) when their operands really come from where the pass gets them - the 64 x 39 window of the
 // block-Toeplitz dictionary in LDS (ds_read_b128 for (A S) B, ds_read_b64_tr_b16 for K B^H), the (A S) fragments from global
 // memory / L2, the k fragments from LDS - and nothing else runs (no element-wise section, no Y, no prefetch of state)?
-// Compare with `tools/pass_breakdown.py` dbg = 10 ("products only") of the shipped 8-wave fused_pass64_kernel: 1.125 ms per
+// Compare with "products only" (dbg = 10, profiles/r03_pass64_sections.txt) of the shipped 8-wave fused_pass64_kernel: 1.125 ms per
 // launch at BASELINE configs[1] (256 trials x 4 column ranges x 32 tiles).  The numbers decide whether the rewrite can pay:
 // the 4-wave design only wins if its product phases are at least as fast as the 8-wave kernel's, because what it can hide is
 // the 0.5 ms the 8-wave kernel spends outside them.
