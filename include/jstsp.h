@@ -294,13 +294,25 @@ int jstsp_svt_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32 *Y,
 /* [x_hat, indexSet, v, targetMatrix] = OMP(A, v, m, snr)   benchmark_algorithms/OMP.m:1-32
  * Dense dictionary A: measures x size_d (strideA 0 = shared); v: measures x batch.
  * x_hat: size_d x batch; index_out: m x batch int32 (1-based); target_out: measures x m x batch
- * (may be NULL).  `snr` is unused by the reference and has no parameter here. */
+ * (may be NULL).  `snr` is unused by the reference and has no parameter here.
+ * Selection (OMP.m:17, [~, idx] = max(abs(A'*r))), the same for jstsp_omp_kron_c32: |c|^2 is compared in float64 formed
+ * from the fp32 correlation (no overflow or underflow for any finite fp32 input); every atom within 1e-5 of the largest
+ * |c| (at most 8 of them) is rescored in float64 by one routine shared by every path, and the largest score wins, the
+ * first index among equal ones (MATLAB max; NaN never wins).  So the index set does not depend on the batch size, on
+ * whether the dictionary is shared, or on the correlation kernel (gemv, fp32 MFMA, split-f16) wherever the float64
+ * margin of every selection is above the orthogonalisation round-off, about 1e-6 relative: exact and near ties of the
+ * first iteration, a residual that is exactly 0 (index 1 is then re-selected), v = 0, and inputs scaled by any power of
+ * two that keeps them finite are decided as the float64 reference decides them.  A later-iteration near-tie below that
+ * round-off can still go either way: the Gram-Schmidt variants (CGS2 for up to 64 problems, MGS above, the Cholesky
+ * update of the coefficient-domain Kronecker path) differ in the last bits of the residual. */
 int jstsp_omp_c32(jstsp_ctx *ctx, int measures, int size_d, int batch,
                   const jstsp_c32 *A, long long strideA, const jstsp_c32 *v, int m,
                   jstsp_c32 *x_hat, int32_t *index_out, jstsp_c32 *target_out, int memspace);
 
 /* OMP on the Kronecker dictionary Phi = kron(Bf.', Af) given by its factors (never formed):
- * Af: N x Gr, Bf: G2 x M, y: N*M x batch, atoms indexed g + Gr*h (1-based in index_out). */
+ * Af: N x Gr, Bf: G2 x M, y: N*M x batch, atoms indexed g + Gr*h (1-based in index_out).
+ * In the coefficient domain (Cholesky of the factor Grams) while the factor fits 150 KiB of LDS (m <= 96), with
+ * measurement-space Gram-Schmidt above; the selection contract is jstsp_omp_c32's. */
 int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
                        const jstsp_c32 *Af, long long strideA, const jstsp_c32 *Bf,
                        long long strideB, const jstsp_c32 *y, int m,

@@ -3,7 +3,8 @@
 // Per iteration (OMP.m:16-24):
 //   [~, idx] = max(abs(A'*r))          -> correlation on the MFMA GEMM (dense dictionary) or as
 //                                         A^H R B^H (Kronecker dictionary kron(Bf.', Af), never formed),
-//                                         then a wave64-shuffle argmax with first-index tie-break
+//                                         then omp_select: argmax of |c|^2 in float64 with first-index tie-break,
+//                                         near-ties rescored in float64 the same way on every path
 //   targetMatrix = [targetMatrix, A(:,idx)];  x = pinv(targetMatrix)*v;  r = v - targetMatrix*x
 //                                      -> the least squares is carried incrementally: the selected
 //                                         atoms are orthonormalised (Gram-Schmidt with re-orthogonalisation,
@@ -37,6 +38,112 @@ __device__ __forceinline__ double2 block_sum2_4w(double2 v, double *sh)
     return make_double2(sh[0] + sh[2] + sh[4] + sh[6], sh[1] + sh[3] + sh[5] + sh[7]);
 }
 
+__device__ __forceinline__ double2 wave_sum2(double2 v)
+{
+    for (int o = 32; o > 0; o >>= 1) { v.x += __shfl_xor(v.x, o); v.y += __shfl_xor(v.y, o); }
+    return v;
+}
+
+// ---- the selection of OMP.m:17, [~, idx] = max(abs(A'*r)), shared by every path -------------------------------------------
+// |c|^2 of an fp32 correlation, formed in float64: the products are exact and nothing overflows or underflows for any finite
+// fp32 input (sqrtf(x*x + y*y) in fp32 is inf above |c| ~ 1.8e19 and 0 below ~1e-19: false ties, won by the first index).
+// NaN scores -1: it never wins unless everything is NaN.
+__device__ __forceinline__ double omp_mag2(float2 c)
+{
+    const double a = (double)c.x * c.x + (double)c.y * c.y;
+    return a == a ? a : -1.0;
+}
+// MATLAB max: the larger value, the smaller index among equal ones
+__device__ __forceinline__ void omp_best(double &b, int &bi, double ob, int oi)
+{
+    if (ob > b || (ob == b && oi < bi)) { b = ob; bi = oi; }
+}
+
+// The fp32 correlation of each path (gemv, fp32 MFMA GEMM, split-f16 GEMM, the coefficient-domain refresh) carries its own
+// rounding, about 1e-6 of |c| apart from path to path.  Every atom within OMP_WINDOW of the largest |c|^2 is therefore rescored
+// in float64 by one wave, by routines whose summation order does not depend on the kernel or its block size, and the best
+// rescored atom wins (first index among equal scores).  More than OMP_RESCORE candidates (for instance a residual that is
+// exactly 0: every |c| ties) keep the fp32 choice.
+constexpr int OMP_RESCORE = 8;
+constexpr double OMP_WINDOW = 2e-5;              // on |c|^2, i.e. 1e-5 on |c|
+
+template <int NT> struct OmpSelect {
+    double bv[NT / 64];
+    int bi[NT / 64];
+    int cand[OMP_RESCORE];
+    double sc[OMP_RESCORE];
+    int n;
+};
+
+// float64 atom_j^H r: lane l sums the measurements l, l + 64, ... with explicit fmas, then a fixed xor tree.  Dense atom
+// A(:, j) (A of this problem); Kronecker (Bf != nullptr) atom(i + N k) = Af(i, g) Bf(h, k), j = g + Gr h, its float64
+// entries exact products of the fp32 factors.
+__device__ double2 omp_atom_dot(int meas, int j, const float2 *A, const float2 *Bf, int N, int Gr, int G2, const float2 *r,
+                                int lane)
+{
+    double2 d = make_double2(0, 0);
+    if (Bf) {
+        const float2 *a = A + (long long)N * (j % Gr), *b = Bf + j / Gr;
+        for (int e = lane; e < meas; e += 64) {
+            const float2 x = a[e % N], y = b[(long long)G2 * (e / N)], rr = r[e];
+            const double ax = fma((double)x.x, (double)y.x, -((double)x.y * y.y));
+            const double ay = fma((double)x.x, (double)y.y, (double)x.y * y.x);
+            d.x = fma(ax, (double)rr.x, fma(ay, (double)rr.y, d.x));                 // conj(atom) * r
+            d.y = fma(ax, (double)rr.y, fma(-ay, (double)rr.x, d.y));
+        }
+    } else {
+        const float2 *a = A + (long long)meas * j;
+        for (int e = lane; e < meas; e += 64) {
+            const float2 x = a[e], rr = r[e];
+            d.x = fma((double)x.x, (double)rr.x, fma((double)x.y, (double)rr.y, d.x));
+            d.y = fma((double)x.x, (double)rr.y, fma(-(double)x.y, (double)rr.x, d.y));
+        }
+    }
+    return wave_sum2(d);
+}
+
+// Block-wide selection.  On entry each thread holds the best (omp_mag2, index) of its own share of c[0, size_d); returns the
+// selected 0-based index to every thread.  score(j, lane) is called by all 64 lanes of a wave and returns the wave's float64
+// correlation of atom j.  Three barriers; `sh` may be reused after the next barrier of the caller.
+template <int NT, class Score>
+__device__ int omp_select(const float2 *c, int size_d, double best, int bi, OmpSelect<NT> &sh, Score score)
+{
+    constexpr int NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        omp_best(best, bi, ob, oi);
+    }
+    __syncthreads();                                // (sh of the previous call is read no more)
+    if (lane == 0) { sh.bv[wave] = best; sh.bi[wave] = bi; }
+    if (tid == 0) sh.n = 0;
+    __syncthreads();
+    best = sh.bv[0]; bi = sh.bi[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) omp_best(best, bi, sh.bv[k], sh.bi[k]);
+    if (bi == 0x7fffffff) bi = 0;
+    if (!(best > 0)) return bi;                     // all zero (or NaN): max of equal values, the first index
+    const double thr = best * (1.0 - OMP_WINDOW);
+    for (int i = tid; i < size_d; i += NT)
+        if (omp_mag2(c[i]) >= thr) {
+            const int k = atomicAdd(&sh.n, 1);
+            if (k < OMP_RESCORE) sh.cand[k] = i;
+        }
+    __syncthreads();
+    const int n = sh.n;
+    if (n < 2 || n > OMP_RESCORE) return bi;
+    for (int k = wave; k < n; k += NW) {
+        const double2 d = score(sh.cand[k], lane);
+        if (lane == 0) sh.sc[k] = d.x * d.x + d.y * d.y;
+    }
+    __syncthreads();
+    double b2 = -1.0;
+    int i2 = 0x7fffffff;
+    for (int k = 0; k < n; ++k) omp_best(b2, i2, sh.sc[k], sh.cand[k]);
+    return i2;
+}
+
 // MANY problems (more than 64 per call): one workgroup of four waves per problem, modified Gram-Schmidt with block-wide
 // reductions - at a batch that fills the chip what counts is instructions per problem, not the latency of one (batch 1024 at
 // BASELINE configs[0]: 14.8 ms per call against 21.4 for the wave-parallel form below, which is 1.9x faster for ONE problem).
@@ -48,31 +155,22 @@ __global__ __launch_bounds__(256) void omp_step_mgs_kernel(int meas, int size_d,
                                                        long long strideB, int N, int Gr, int G2, OmpState s)
 {
     __shared__ double sh[8];
-    __shared__ float shv[4];
-    __shared__ int shi[4];
+    __shared__ OmpSelect<256> ssel;
     __shared__ int s_idx, s_dup;
     const int t = blockIdx.x, tid = threadIdx.x;
     // ---- argmax of |corr| with first-index tie-break (MATLAB max) -------------------------------
     const float2 *c = corr + (long long)t * size_d;
-    float best = -1.f;
+    double best = -1.0;
     int bi = 0x7fffffff;
     for (int i = tid; i < size_d; i += 256) {
-        const float2 v = c[i];
-        float a = sqrtf(v.x * v.x + v.y * v.y);
-        if (a != a) a = -1.f;                       // NaN never wins unless everything is NaN
+        const double a = omp_mag2(c[i]);
         if (a > best) { best = a; bi = i; }         // strided scan keeps the smallest index per thread
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if ((tid & 63) == 0) { shv[tid >> 6] = best; shi[tid >> 6] = bi; }
-    __syncthreads();
+    const float2 *At = A + (long long)t * strideA, *Bt = Bf ? Bf + (long long)t * strideB : nullptr;
+    const float2 *rt = s.r + (long long)t * meas;
+    bi = omp_select<256>(c, size_d, best, bi, ssel,
+                         [&](int j, int ln) { return omp_atom_dot(meas, j, At, Bt, N, Gr, G2, rt, ln); });
     if (tid == 0) {
-        for (int k = 1; k < 4; ++k)
-            if (shv[k] > best || (shv[k] == best && shi[k] < bi)) { best = shv[k]; bi = shi[k]; }
-        if (bi == 0x7fffffff) bi = 0;
         s_idx = bi;
         s.sel[(long long)t * m + it] = bi;
         int dup = -1;
@@ -169,11 +267,6 @@ __global__ __launch_bounds__(256) void omp_step_mgs_kernel(int meas, int size_d,
     }
 }
 
-__device__ __forceinline__ double2 wave_sum2(double2 v)
-{
-    for (int o = 32; o > 0; o >>= 1) { v.x += __shfl_xor(v.x, o); v.y += __shfl_xor(v.y, o); }
-    return v;
-}
 template <int NT> __device__ __forceinline__ double2 block_sum2(double2 v, double *sh)
 {
     constexpr int NW = NT / 64;
@@ -201,32 +294,25 @@ __global__ __launch_bounds__(NT) void omp_step_kernel(int meas, int size_d, int 
 {
     constexpr int NW = NT / 64;
     __shared__ double sh[2 * NW];
-    __shared__ float shv[NW];
-    __shared__ int shi[NW];
+    __shared__ OmpSelect<NT> ssel;
     __shared__ int s_idx, s_dup;
     __shared__ float2 dsh[1024];                    // inner products of a pass (m <= 1024)
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- argmax of |corr| with first-index tie-break (MATLAB max) -------------------------------
     const float2 *c = corr + (long long)t * size_d;
-    float best = -1.f;
+    double best = -1.0;
     int bi = 0x7fffffff;
     for (int i = tid; i < size_d; i += NT) {
-        const float2 v = c[i];
-        float a = sqrtf(v.x * v.x + v.y * v.y);
-        if (a != a) a = -1.f;                       // NaN never wins unless everything is NaN
+        const double a = omp_mag2(c[i]);
         if (a > best) { best = a; bi = i; }         // strided scan keeps the smallest index per thread
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    {
+        const float2 *At = A + (long long)t * strideA, *Bt = Bf ? Bf + (long long)t * strideB : nullptr;
+        const float2 *rt = s.r + (long long)t * meas;
+        bi = omp_select<NT>(c, size_d, best, bi, ssel,
+                            [&](int j, int ln) { return omp_atom_dot(meas, j, At, Bt, N, Gr, G2, rt, ln); });
     }
-    if (lane == 0) { shv[wave] = best; shi[wave] = bi; }
-    __syncthreads();
     if (tid == 0) {
-        for (int k = 1; k < NW; ++k)
-            if (shv[k] > best || (shv[k] == best && shi[k] < bi)) { best = shv[k]; bi = shi[k]; }
-        if (bi == 0x7fffffff) bi = 0;
         s_idx = bi;
         s.sel[(long long)t * m + it] = bi;
         int dup = -1;
@@ -340,8 +426,7 @@ __global__ __launch_bounds__(1024) void omp_step_reg_kernel(int meas, int size_d
     extern __shared__ float2 qsh[];                 // the first qc basis columns (one workgroup reads Q through one CU's 64 B per
                                                     // clock: four sweeps over 24 columns were 5 us of an iteration)
     __shared__ double sh[2 * NW];
-    __shared__ float shv[NW];
-    __shared__ int shi[NW];
+    __shared__ OmpSelect<NT> ssel;
     __shared__ int s_dup;
     __shared__ float2 dsh[2][1024];                 // inner products of the two passes (m <= 1024)
     __shared__ float2 wsh[NT * EPT];
@@ -368,35 +453,19 @@ __global__ __launch_bounds__(1024) void omp_step_reg_kernel(int meas, int size_d
 #pragma unroll
             for (int i = 0; i < PRE; ++i) qpre[k][i] = Q[(long long)meas * min(i, uc - 1) + min(tid + NT * k, meas - 1)];
     }
-    float best = -1.f;
+    double best = -1.0;
     int bi = 0x7fffffff;
-    if (tid < size_d) {
-        float a = sqrtf(c0.x * c0.x + c0.y * c0.y);
-        if (a != a) a = -1.f;
-        best = a; bi = tid;
-    }
+    if (tid < size_d) { best = omp_mag2(c0); bi = tid; }
     for (int i = tid + NT; i < size_d; i += NT) {
-        const float2 v = c[i];
-        float a = sqrtf(v.x * v.x + v.y * v.y);
-        if (a != a) a = -1.f;
+        const double a = omp_mag2(c[i]);
         if (a > best) { best = a; bi = i; }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { shv[wave] = best; shi[wave] = bi; }
     if (tid == 0) s_dup = 0x7fffffff;
-    __syncthreads();
-    best = shv[0]; bi = shi[0];
-#pragma unroll
-    for (int k = 1; k < NW; ++k) {
-        const float ob = shv[k];
-        const int oi = shi[k];
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    {
+        const float2 *At = A + (long long)t * strideA, *Bt = Bf ? Bf + (long long)t * strideB : nullptr;
+        bi = omp_select<NT>(c, size_d, best, bi, ssel,
+                            [&](int j, int ln) { return omp_atom_dot(meas, j, At, Bt, N, Gr, G2, r, ln); });
     }
-    if (bi == 0x7fffffff) bi = 0;
     const int idx = bi;
     for (int j = tid; j < u; j += NT)
         if (s.uniq[(long long)t * m + j] == idx) atomicMin(&s_dup, j);
@@ -632,47 +701,51 @@ __global__ __launch_bounds__(256) void omp_finish_kernel(int meas, int size_d, i
 // One workgroup per problem runs ALL m iterations (OMP.m:16-24): argmax with first-index tie-break, duplicate
 // check (multiplicities, :18 never excludes an atom), Cholesky append in fp64, two triangular solves, and the
 // refresh of c (size_d x |U| complex MACs).  No per-iteration launches, no meas-sized traffic.
+// The selection rescores its candidates as Phi(:, j)^H y - G(j, U) x_U in float64: Phi(:, j)^H y by omp_atom_dot from y and
+// the factors (the same bits as the measurement-space path's first iteration), G(j, U) x_U as the refresh below forms it.
 template <int NT>
 __global__ __launch_bounds__(NT) void omp_gram_kernel(int size_d, int m, int Gr, int G2, const float2 *c0_, float2 *cw_,
                                                       const float2 *GA_, long long sGA, const float2 *GB_, long long sGB,
-                                                      float2 *x_hat, int32_t *index_out)
+                                                      float2 *x_hat, int32_t *index_out, int N, int meas, const float2 *y_,
+                                                      const float2 *Af_, long long strideA, const float2 *Bf_,
+                                                      long long strideB)
 {
     extern __shared__ double lds[];
     // LDS: L (m*m double2, row-major lower), xu (m double2), cu (m double2), work (m double2), ia/ib/mult (3*m int)
     double2 *L = reinterpret_cast<double2 *>(lds);
     double2 *xu = L + (size_t)m * m, *cu = xu + m, *wk = cu + m;
     int *ia = reinterpret_cast<int *>(wk + m), *ib = ia + m, *mult = ib + m;
-    __shared__ float shv[NT / 64];
-    __shared__ int shi[NT / 64];
+    __shared__ OmpSelect<NT> ssel;
     __shared__ int s_nu, s_new;
     const int t = blockIdx.x, tid = threadIdx.x;
     const float2 *c0 = c0_ + (long long)t * size_d;
     float2 *cw = cw_ + (long long)t * size_d;
     const float2 *GA = GA_ + (long long)t * sGA, *GB = GB_ + (long long)t * sGB;
+    const float2 *yt = y_ + (long long)t * meas, *At = Af_ + (long long)t * strideA, *Bt = Bf_ + (long long)t * strideB;
     if (tid == 0) s_nu = 0;
     for (int i = tid; i < size_d; i += NT) cw[i] = c0[i];
     __syncthreads();
     for (int it = 0; it < m; ++it) {
         // ---- argmax |c| with first-index tie-break (MATLAB max)                                      OMP.m:17
-        float best = -1.f;
+        double best = -1.0;
         int bi = 0x7fffffff;
         for (int i = tid; i < size_d; i += NT) {
-            const float2 v = cw[i];
-            float a = sqrtf(v.x * v.x + v.y * v.y);
-            if (a != a) a = -1.f;
+            const double a = omp_mag2(cw[i]);
             if (a > best) { best = a; bi = i; }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        if ((tid & 63) == 0) { shv[tid >> 6] = best; shi[tid >> 6] = bi; }
-        __syncthreads();
+        const int nu0 = s_nu;
+        bi = omp_select<NT>(cw, size_d, best, bi, ssel, [&](int j, int ln) {
+            double2 d = omp_atom_dot(meas, j, At, Bt, N, Gr, G2, yt, ln);
+            const int a = j % Gr, b = j / Gr;
+            for (int u = 0; u < nu0; ++u) {
+                const float2 p = GA[a + (long long)Gr * ia[u]], q = GB[ib[u] + (long long)G2 * b];
+                const double gx = (double)p.x * q.x - (double)p.y * q.y, gy = (double)p.x * q.y + (double)p.y * q.x;
+                d.x -= gx * xu[u].x - gy * xu[u].y;
+                d.y -= gx * xu[u].y + gy * xu[u].x;
+            }
+            return d;
+        });
         if (tid == 0) {
-            for (int k = 1; k < NT / 64; ++k)
-                if (shv[k] > best || (shv[k] == best && shi[k] < bi)) { best = shv[k]; bi = shi[k]; }
-            if (bi == 0x7fffffff) bi = 0;
             index_out[(long long)t * m + it] = bi + 1;                     // 1-based indexSet
             const int a = bi % Gr, b = bi / Gr;
             int dup = -1;
@@ -949,7 +1022,8 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, 
             JSTSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(omp_gram_kernel<1024>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
             hipLaunchKernelGGL(omp_gram_kernel<1024>, dim3(batch), dim3(1024), lds, ctx->stream, size_d, m, Gr, G2, c0, cw,
-                               GA, strideA ? (long long)Gr * Gr : 0, GB, strideB ? (long long)G2 * G2 : 0, xh, io);
+                               GA, strideA ? (long long)Gr * Gr : 0, GB, strideB ? (long long)G2 * G2 : 0, xh, io, N, (int)nm,
+                               y, Af, strideA, Bf, strideB);
             JSTSP_HIP(hipGetLastError());
             JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(x_hat), xh, batch * g, memspace));
             JSTSP_TRY(stage_out(ctx, index_out, io, (size_t)batch * m, memspace));

@@ -21,7 +21,7 @@ __all__ = [
     "vec", "unvec", "svt", "soft_threshold_complex",
     "proposed_algorithm_literal", "proposed_algorithm",
     "proposed_algorithm_angles_literal", "proposed_algorithm_angles",
-    "omp_literal", "omp", "sparse_admm_literal", "sparse_admm",
+    "omp_literal", "omp_literal_margins", "omp", "sparse_admm_literal", "sparse_admm",
     "mc_svt", "mc_admm_literal", "mc_admm", "spectral_norm", "nmse_capped",
     "mmv_omp", "tssr", "rate",
 ]
@@ -273,6 +273,19 @@ def omp_literal(A, v, m, snr=None):
     Returns ``x_hat`` (size_d,), ``indexSet`` (1-based ints, length m), ``v``,
     ``targetMatrix`` (measures x m).
     """
+    return _omp_literal(A, v, m, None)
+
+
+def omp_literal_margins(A, v, m, snr=None):
+    """``omp_literal`` plus the margin of every selection (OMP.m:17): per iteration the float64 relative gap
+    ``(c1 - c2) / c1`` between the largest and the second-largest ``|A' r|`` (0 for a tie, also when every
+    correlation is 0; 1 for a single atom).  Returns ``(x_hat, indexSet, v, targetMatrix, gaps)``."""
+    gaps = []
+    out = _omp_literal(A, v, m, gaps)
+    return out + (np.array(gaps, dtype=np.float64),)
+
+
+def _omp_literal(A, v, m, gaps):
     A = np.asarray(A, dtype=np.complex128)
     v = np.asarray(v, dtype=np.complex128).reshape(-1)
     measures, size_d = A.shape                           # :9
@@ -284,6 +297,9 @@ def omp_literal(A, v, m, snr=None):
     while t <= m:                                        # :16
         corr = np.abs(A.conj().T @ r)                    # :17
         idx = int(np.argmax(corr))                       # first index on ties, like MATLAB max
+        if gaps is not None:
+            c2, c1 = np.partition(corr, -2)[-2:] if size_d > 1 else (0.0, corr[0])
+            gaps.append(float((c1 - c2) / c1) if c1 > 0 else (1.0 if size_d == 1 else 0.0))
         index_set.append(idx + 1)
         target = np.concatenate([target, A[:, idx:idx + 1]], axis=1)   # :18
         x = np.linalg.pinv(target) @ v                   # :19

@@ -60,7 +60,7 @@ def test_omp_reselected_atom_and_batch():
 
 def test_omp_kron_coefficient_domain_equals_measurement_domain_and_oracle():
     """jstsp_omp_kron_c32 runs OMP in the coefficient domain (factor Grams + Cholesky, one kernel for all
-    iterations; the measurement-space variant is in the experiments build only since round 6).  Index sets and x against the
+    iterations) for m <= 96, and the measurement-space Gram-Schmidt above (tests/test_gpu_omp_paths.py).  Index sets and x against the
     literal OMP.m on kron(B.', A), per-trial and shared dictionaries, and a re-selected atom (identity dictionary: pinv splits
     the coefficient)."""
     import jstsp19_amd as J
@@ -88,8 +88,8 @@ def test_omp_kron_coefficient_domain_equals_measurement_domain_and_oracle():
                                            # measurement vector too long for it (the global-memory form)
                                            (1536, 700, 20), (300, 512, 30), (2100, 300, 8)])
 def test_omp_one_problem_sixteen_wave_step_equals_the_batched_four_wave_step_and_oracle(meas, size_d, m):
-    """ONE problem (the reference's own case) takes the 1024-thread step kernel, a batch above 64 the 256-thread one (omp.hip:
-    classical Gram-Schmidt twice with wave-parallel inner products): the same problem through both and through the float64 oracle -
+    """ONE problem (the reference's own case) takes a 1024-thread step kernel (omp.hip: classical Gram-Schmidt twice with
+    wave-parallel inner products), a batch above 64 the 256-thread one (modified Gram-Schmidt, applied twice): the same problem through both and through the float64 oracle -
     index sets equal (integer work), coefficients and the selected columns to fp32."""
     import jstsp19_amd as J
     from oracle import solvers as O
@@ -486,7 +486,7 @@ def test_sparse_admm_rectangular_fused_epilogues_and_oracle():
 @pytest.mark.parametrize("meas,size_d,m,batch", [(1024, 1024, 24, 1), (1536, 700, 20, 3), (300, 512, 30, 5)])
 def test_omp_register_step_against_the_literal_oracle(meas, size_d, m, batch):
     """Few problems: the Gram-Schmidt step keeps the candidate atom and the residual in registers and the first basis columns in
-    LDS (omp_step_reg_kernel; the global-memory step is in the experiments build only since round 6): the atoms of the literal
+    LDS (omp_step_reg_kernel; above 2048 measurements the global-memory omp_step_kernel<1024>): the atoms of the literal
     OMP.m in the same order, coefficients to fp32 accuracy."""
     import jstsp19_amd as J
     from oracle import solvers as O
