@@ -9,7 +9,7 @@ S, Y, convergence_error) at BASELINE.json configs[1]:
 (jstsp19_amd.system_model, per-trial pilots => per-trial B) and resident in HBM before the
 timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,6 +19,10 @@ all-reduce of the NMSE sum (plus the timing MAX).  Rank 0 prints ONE JSON line.
 
 --dump-outputs DIR writes what the last timed step returned, so that two builds can be compared output for output on the
 same inputs (they depend on the arguments only: the generator is keyed by seed and global trial id).
+
+A plain run does what the headline needs and no more: inputs, priming call, warm-up, timed steps, the dump, the mean NMSE,
+the line.  --full adds the measurement legs after the timed steps (end_to_end, strict_fp32_mfma, roofline, cpu_baseline,
+parity, host_path, configs4); they never touch the timed region, so `value` and `ms_per_step` mean the same in both.
 """
 from __future__ import annotations
 
@@ -56,11 +60,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="Monte-Carlo trials per GPU per step")
     ap.add_argument("--snr-db", type=float, default=5.0)
     ap.add_argument("--no-ce", action="store_true", help="skip convergence_error (2-output call)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run the measurement legs too: end_to_end, strict_fp32_mfma, roofline, cpu_baseline, "
+                         "parity, host_path, configs4 (the --no-* / --cpu-* / --parity-trials options below select among them)")
     ap.add_argument("--cpu-trials", type=int, default=-1,
-                    help="trials timed on the host baseline (rank 0, N=1); -1 = three per thread (at most the batch), 0 = none")
+                    help="--full: trials timed on the host baseline (rank 0, N=1); -1 = three per thread (at most the batch), 0 = none")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="OpenMP threads of the host baseline (0 = min(physical cores, the cgroup's CPU quota))")
+                    help="--full: OpenMP threads of the host baseline (0 = min(physical cores, the cgroup's CPU quota))")
     ap.add_argument("--shared-pilots", action="store_true", help="one pilot set for all trials (B shared, stride 0)")
     ap.add_argument("--small", action="store_true", help="reference-native shape (plumbing check)")
     ap.add_argument("--sweep", action="store_true",
@@ -70,8 +77,8 @@ def parse():
     ap.add_argument("--sweep-trials", type=int, default=500, help="realisations per SNR point in --sweep mode")
     ap.add_argument("--no-host-path", action="store_true", help="skip the JSTSP_HOST (PCIe-inclusive) measurement")
     ap.add_argument("--parity-trials", type=int, default=0,
-                    help="besides the bench batch (always checked against the committed float64 fixture), this many trials of the "
-                         "configs[3] sweep (10 SNR points, up to 2560) against the same fixture: about 3.5 s per 100")
+                    help="--full: besides the bench batch (always checked against the committed float64 fixture), this many trials "
+                         "of the configs[3] sweep (10 SNR points, up to 2560) against the same fixture: about 3.5 s per 100")
     ap.add_argument("--no-strict-fp32", action="store_true", help="skip the informational JSTSP_H2=0 (strict complex-fp32 MFMA) rate")
     ap.add_argument("--no-configs4", action="store_true",
                     help="skip the informational BASELINE configs[4] leg (proposed_algorithm_angles at N=64 M=65536 G2=4096, 32 trials, one call)")
@@ -83,6 +90,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be >= 1")
+    if not a.full and (a.parity_trials > 0 or a.cpu_trials > 0 or a.cpu_threads > 0):
+        ap.error("--parity-trials, --cpu-trials and --cpu-threads size legs that only --full runs")
     return a
 
 
@@ -219,6 +228,20 @@ def configs4_leg(device, batch=32):
     del o, B, S
     torch.cuda.empty_cache()
     return out
+
+
+def headline_line(a, world, dt, workload, want_ce, mean_nmse, dumped):
+    """The line's headline fields, the same in a plain and a --full run (which adds its legs to them)."""
+    return {
+        "metric": "channel-estimates/sec (batched MC) at Nt=Nr=64,K=64; NMSE vs ref",
+        "value": round(a.batch * world * a.steps / dt, 3), "unit": "channel-estimates/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "c32 (storage and results fp32 complex; big contractions as split-f16 MFMA with fp32 accumulation, fp32-equivalent)", "data": "synthetic",
+        "config": {"workload": workload, "trials_per_gpu_per_step": a.batch, "Imax": IMAX,
+                   "outputs": "S,Y,convergence_error" if want_ce else "S,Y", "snr_db": a.snr_db,
+                   "pilots": "shared (one B)" if a.shared_pilots else "per-trial (B per trial)", "parallelism": "trials sharded, dp%d" % world},
+        "mean_nmse": mean_nmse, "full": a.full, "dump_outputs": dumped,
+    }
 
 
 def emit(line, dist, rank):
@@ -382,6 +405,10 @@ def main():
                     "dtype": "stub", "data": "stub", "config": {"workload": workload, "trials_per_gpu_per_step": a.batch},
                     "mean_nmse": mean_nmse, "trial_ids_rank0": [ids[0], ids[-1]], "dump_outputs": dumped}
         emit(line, dist, rank)
+        return
+
+    if not a.full:
+        emit(headline_line(a, world, dt, workload, want_ce, mean_nmse, dumped) if rank == 0 else None, dist, rank)
         return
 
     import jstsp19_amd as J
@@ -735,19 +762,8 @@ def main():
             extra["configs4"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0:
-        total = a.batch * world * a.steps
-        line = {
-            "metric": "channel-estimates/sec (batched MC) at Nt=Nr=64,K=64; NMSE vs ref",
-            "value": round(total / dt, 3), "unit": "channel-estimates/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "c32 (storage and results fp32 complex; big contractions as split-f16 MFMA with fp32 accumulation, fp32-equivalent)", "data": "synthetic",
-            "config": {"workload": workload, "trials_per_gpu_per_step": a.batch, "Imax": IMAX,
-                       "outputs": "S,Y,convergence_error" if want_ce else "S,Y", "snr_db": a.snr_db,
-                       "pilots": "shared (one B)" if a.shared_pilots else "per-trial (B per trial)", "parallelism": "trials sharded, dp%d" % world},
-            "mean_nmse": mean_nmse, "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "host_path": host,
-            "dump_outputs": dumped,
-        }
-        line.update(extra)
+        line = headline_line(a, world, dt, workload, want_ce, mean_nmse, dumped)
+        line.update(roofline=roofline, cpu_baseline=cpu, parity=parity, host_path=host, **extra)
     emit(line if rank == 0 else None, dist, rank)
 
 

@@ -25,6 +25,12 @@ def test_more_gpus_than_the_node_has_is_refused_loudly():
     assert "--gpus %d" % n in r.stderr
 
 
+def test_options_of_the_full_legs_need_full():
+    for opt in (["--parity-trials", "64"], ["--cpu-trials", "4"], ["--cpu-threads", "8"]):
+        r = _run(opt)
+        assert r.returncode == 2 and "only --full runs" in r.stderr and "n_gpus" not in r.stdout, (opt, r.stderr[-500:])
+
+
 def test_world_size_must_match_gpus():
     r = _run(["--gpus", "2"], {"WORLD_SIZE": "4", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "n_gpus" not in r.stdout and "WORLD_SIZE=4" in r.stderr

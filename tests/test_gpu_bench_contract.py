@@ -1,4 +1,4 @@
-"""bench.py prints ONE JSON line with the driver's contract fields (plus roofline / cpu_baseline / parity), and
+"""bench.py prints ONE JSON line with the driver's contract fields (plus, with --full, roofline / cpu_baseline / parity), and
 __graft_entry__.smoke() runs — both on the reference-native shape so the test stays short."""
 import json
 import os
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_line_small_shape():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "2", "--warmup", "1",
-                        "--batch", "8", "--cpu-trials", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--batch", "8", "--cpu-trials", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -32,6 +32,23 @@ def test_bench_json_line_small_shape():
     assert j["parity"]["max_abs_dNMSE"] < 1e-6
 
 
+def test_bench_plain_run_prints_the_headline_only():
+    """Without --full the line holds the headline fields and none of the measurement legs; `value` is still the timed steps'."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "2", "--warmup", "1", "--batch", "8"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "mean_nmse", "dump_outputs"):
+        assert k in j, k
+    for k in ("roofline", "cpu_baseline", "parity", "host_path", "end_to_end", "strict_fp32_mfma", "configs4"):
+        assert k not in j, k
+    assert j["full"] is False and j["steps"] == 2 and j["warmup"] == 1 and j["data"] == "synthetic" and 0 < j["mean_nmse"] < 1
+    assert j["value"] > 0 and abs(j["value"] - 8 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-3
+
+
 def test_graft_entry_smoke():
     sys.path.insert(0, ROOT)
     import __graft_entry__ as g
@@ -39,10 +56,10 @@ def test_graft_entry_smoke():
 
 
 def test_bench_host_path_and_sweep_mode_small_shape():
-    """The line carries the drop-in (JSTSP_HOST) rate next to the device-resident value, and `--sweep` (BASELINE configs[3]
+    """A --full line carries the drop-in (JSTSP_HOST) rate next to the device-resident value, and `--sweep` (BASELINE configs[3]
     at the reference-native shape here) prints one line with the per-point mean NMSE of both solvers."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "1", "--warmup", "0",
-                        "--batch", "8", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--batch", "8", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     hp = j["host_path"]
@@ -124,7 +141,7 @@ def test_bench_two_ranks_real_library_on_one_gpu_over_gloo():
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
 
-    head = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-path"]
+    head = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-path", "--full"]
     two = run(2, head + ["--batch", "8"])
     one = run(1, head + ["--batch", "16"])
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["data"] == "synthetic" and one["n_gpus"] == 1
