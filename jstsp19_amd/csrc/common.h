@@ -210,7 +210,8 @@ struct jstsp_ctx {
     // and the convergence-error norms concurrently with the MFMA-bound GEMMs of the main stream
     // conditioning record of the last call that (pseudo-)inverted something (pinv.hip / hinv.hip), device memory:
     // float bits of [0] the smallest sigma_min/sigma_max met by the float64 pinv kernel, [1] the largest Newton-Schulz
-    // residual max|I - G X|, [2] the smallest lambda_min/lambda_max of an eigen-inverted factor Gram
+    // residual ||I - G X||_F / sqrt(n), [2] the smallest lambda_min/lambda_max of an inverted factor Gram (eigen route: 0 when a
+    // component was dropped; Newton-Schulz: 1 / (lambda_max(G) lambda_max(X)), 0 when the residual exceeds its rounding floor)
     uint32_t *diag = nullptr;
     // [0] warm-started lambda_max values of the last ADMM solve that a periodic cold verification contradicted (eig2.hip:
     // lanczos_lmax_kernel; jstsp_last_lanczos_mismatches), device memory

@@ -423,12 +423,12 @@ int diag_check_host(jstsp_ctx *ctx, const char *what)
 {
     double rc = 1.0, res = 0.0, gr = 1.0;
     JSTSP_TRY(diag_read(ctx, &rc, &res, &gr));
+    // (res is reported, not checked here: a Newton-Schulz inverse whose residual exceeds its rounding floor records ratio 0)
+    (void)res;
     JSTSP_REQUIRE(gr >= 1e-6, JSTSP_E_ILLCOND,
-                  "%s: a factor Gram has lambda_min/lambda_max = %.3g < 1e-6: its fp32 inverse (factors too large for "
-                  "the float64 pinv kernel) would carry no correct digit", what, gr);
-    JSTSP_REQUIRE(res < 1e-2, JSTSP_E_ILLCOND,
-                  "%s: the Newton-Schulz inverse of a factor Gram of order > 128 did not converge (max|I - G X| = %.3g): "
-                  "the factor is rank-deficient or too ill-conditioned for fp32", what, res);
+                  "%s: a factor Gram has lambda_min/lambda_max = %.3g < 1e-6 (0: an eigenvalue at or below n*eps_fp32*lambda_max, "
+                  "or a Newton-Schulz residual above its rounding floor): its fp32 inverse (factors too large for the float64 "
+                  "pinv kernel) would carry no correct digit", what, gr);
     return 0;
 }
 

@@ -3,7 +3,7 @@ and sparse_admm.  Index selections must be bit-exact (integer work); coefficient
 import numpy as np
 import pytest
 
-from conftest import load_golden, rel_err
+from conftest import load_golden, rel_err, check_below
 
 pytestmark = pytest.mark.gpu
 
@@ -328,7 +328,7 @@ def test_ls_baseline_matches_pinv():
     S = J.ls_estimate(Y, A, B)
     for t in range(b):
         ref = np.linalg.pinv(A) @ Y[t] @ np.linalg.pinv(B[t])
-        assert rel_err(S[t], ref) < 2e-3
+        check_below("ls.ns150.S", rel_err(S[t], ref), 2.5e-5)    # (measured 4.9e-6)
 
 
 def test_pinv_matches_numpy_float64_including_rank_deficient_and_ill_conditioned():
@@ -396,7 +396,7 @@ def test_ls_gram_route_reports_ill_conditioning_instead_of_garbage():
     bad = (U * np.logspace(0, -4, G2)) @ Vh.conj().T           # cond(B B^H) = 1e8
     Y = r(N, M)
     S = J.ls_estimate(Y, A, good)
-    assert rel_err(S, np.linalg.pinv(A) @ Y @ np.linalg.pinv(good)) < 2e-3
+    check_below("ls.eig100.S", rel_err(S, np.linalg.pinv(A) @ Y @ np.linalg.pinv(good)), 4e-5)   # (measured 7.6e-6)
     with pytest.raises(J.JstspError, match="-6"):
         J.ls_estimate(Y, A, bad)
 

@@ -9,33 +9,11 @@ import pytest
 
 import jstsp19_amd
 from jstsp19_amd import _lib
-from conftest import rel_err
+from conftest import rel_err, check_below, ce_rel
+from capi_calls import _f, _unf, _p, _dp, _proposed  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 HOST, DEVICE = 0, 1
-
-
-def _f(a):                       # column-major bytes of a (batch, R, C) / (R, C) array: trial index slowest
-    a = np.asarray(a)
-    if a.ndim == 3:
-        return np.ascontiguousarray(np.transpose(a, (0, 2, 1)))
-    return np.ascontiguousarray(a.T)
-
-
-def _unf(buf, shape):            # inverse of _f
-    if len(shape) == 3:
-        b, R, Cc = shape
-        return np.transpose(buf.reshape(b, Cc, R), (0, 2, 1))
-    R, Cc = shape
-    return buf.reshape(Cc, R).T
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _problem(rng, batch, N, M, Gr, G2, dtype):
@@ -53,23 +31,6 @@ def _problem(rng, batch, N, M, Gr, G2, dtype):
     return A, B, Om, subY
 
 
-def _proposed(lib, ctx, suffix, A, B, Om, subY, Imax, tY, tS, rho, type_, indx=None, want_ce=True):
-    batch, N, M = subY.shape
-    Gr, G2 = A.shape[1], B.shape[1]
-    cdt, rdt = (np.complex128, np.float64) if suffix == "c64" else (np.complex64, np.float32)
-    a, b, om, sy = _f(A.astype(cdt)), _f(B.astype(cdt)), _f(Om.astype(rdt)), _f(subY.astype(cdt))
-    S = np.empty(batch * Gr * G2, cdt)
-    Y = np.empty(batch * N * M, cdt)
-    ce = np.empty(batch * 3 * Imax, np.float64) if want_ce else None
-    ty, ts, rh = (np.full(batch, v, np.float64) for v in (tY, tS, rho))
-    ix = np.ascontiguousarray(indx, np.int32) if indx is not None else None
-    fn = getattr(lib, "jstsp_proposed_algorithm_" + suffix)
-    _lib.check(fn(ctx.handle, N, M, Gr, G2, batch, _p(sy), _p(om), _p(a), 0, _p(b), G2 * M, Imax, _dp(ty), _dp(ts), _dp(rh),
-                  type_, _p(ix), _p(S), _p(Y), _p(ce), HOST), "proposed_" + suffix)
-    return (_unf(S, (batch, Gr, G2)), _unf(Y, (batch, N, M)),
-            np.transpose(ce.reshape(batch, 3, Imax), (0, 2, 1)) if want_ce else None)
-
-
 @pytest.mark.parametrize("type_", [0, 1])
 def test_proposed_algorithm_c64(type_):
     from oracle import solvers as O
@@ -81,7 +42,9 @@ def test_proposed_algorithm_c64(type_):
     assert S.dtype == np.complex128 and ce.dtype == np.float64
     for t in range(batch):
         So, Yo, ceo = O.proposed_algorithm(subY[t], Om[t], A, B[t], Imax, 0.02, 0.01, 0.4, "approximate" if type_ == 0 else "std")
-        assert rel_err(S[t], So) < 3e-4 and rel_err(Y[t], Yo) < 3e-4
+        check_below("c64.%d.S" % type_, rel_err(S[t], So), 2e-5)                 # (measured 3.0e-6)
+        check_below("c64.%d.Y" % type_, rel_err(Y[t], Yo), 2e-5)
+        check_below("c64.%d.ce12" % type_, ce_rel(ce[t][1:, :2], ceo[1:, :2]), 1e-4)  # (measured 1.4e-5)
         np.testing.assert_allclose(ce[t][1:], ceo[1:], rtol=3e-3)
     # float-representable inputs: identical to the _c32 entry point, bit for bit
     A, B, Om, subY = _problem(rng, batch, N, M, Gr, G2, np.complex64)

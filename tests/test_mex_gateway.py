@@ -13,6 +13,8 @@ import sys
 import numpy as np
 import pytest
 
+from conftest import check_below
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DOUBLE, INT32, CHAR, CELL = 6, 12, 4, 1
 
@@ -166,7 +168,7 @@ def test_gateway_proposed_algorithm_outputs_and_batch(mex):
         np.testing.assert_allclose(ce[1:, :, t], ref[t][2][1:], rtol=2e-3)
     # 'std' (anything but 'approximate', proposed_algorithm.m:45-54) needs full column rank: N >= Gr, M >= G2 holds here
     (Sstd,) = call(mex, 1, "proposed_algorithm", subY[:, :, 1], Om[:, :, 1], A, B, 10, tY[1], tS, rho, "std")
-    assert rel(Sstd, O.proposed_algorithm(subY[:, :, 1], Om[:, :, 1], A, B, 10, tY[1], tS, rho, "std")[0]) < 5e-4
+    check_below("mex.std.S", rel(Sstd, O.proposed_algorithm(subY[:, :, 1], Om[:, :, 1], A, B, 10, tY[1], tS, rho, "std")[0]), 1e-6)   # (measured 1.5e-7)
     # proposed_algorithm_angles.m:1 - indx_S as MATLAB doubles, per-problem dictionaries B (3-D)
     idx = np.stack([np.argsort(-np.abs(S0[:, :, t]).reshape(-1, order="F"), kind="stable") + 1.0 for t in range(3)], axis=1)
     B3 = np.stack([B, 1.1 * B, 0.9 * B], axis=2)
