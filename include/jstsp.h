@@ -433,7 +433,9 @@ typedef struct jstsp_model {
                                beamformer = JSTSP_BF_DFT (:10), Mr = round(subSamplingRatio*Nr) (:5), Mr_e = Nr, T_prop = T
                                and rho_scale = sqrt(0.75) this call IS that function + the driver's lines :50-58) */
 } jstsp_model;
-enum { JSTSP_BF_ZC = 0, JSTSP_BF_DFT = 1 };
+/* createBeamformer.m kinds.  JSTSP_BF_QUANTIZED ('quantized', N_q = 6, :25-31) and JSTSP_BF_QUANTIZED4 ('quantized_4',
+ * N_q = 4, :18-24) are for jstsp_beamformer_* and jstsp_ase_trials_c32; jstsp_build_trials_c32 accepts only ZC and DFT. */
+enum { JSTSP_BF_ZC = 0, JSTSP_BF_DFT = 1, JSTSP_BF_QUANTIZED = 2, JSTSP_BF_QUANTIZED4 = 3 };
 enum { JSTSP_RHO_MIN6 = 0, JSTSP_RHO_MAX = 1 };
 enum { JSTSP_PILOTS_QAM4 = 0, JSTSP_PILOTS_GAUSS = 1 };
 
@@ -462,6 +464,57 @@ typedef struct jstsp_trials {
 
 int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx,
                            long long trial0, int batch, const jstsp_trials *out, int memspace);
+
+/* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
+ * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
+ * JSTSP_BF_QUANTIZED ('quantized') and JSTSP_BF_QUANTIZED4 ('quantized_4'): W (N x N, column-major, same memspace).  The
+ * phase of every entry is reduced in integers before sincospi; the quantized kinds keep the reference's construction, each of
+ * the 2^Nq phase indices repeated ceil(N/2^Nq) times in a row (at N = 64 'quantized' is the unitary DFT; at N = 128 its
+ * columns come in identical pairs; at N = 32 it is not orthogonal).  Asserted (tests/test_gpu_capacity.py), N in
+ * {1, 7, 32, 64, 100, 128, 256}: |W - W_64| sqrt(N) < 1e-6 for the _c32 form (measured 1.9e-7) and < 4e-14 N for the _c64
+ * form (measured 8.3e-15 N: the float64 transcription's own error on its unreduced phases); both memspaces give the same bits. */
+int jstsp_beamformer_c32(jstsp_ctx *ctx, int N, int kind, jstsp_c32 *W, int memspace);
+int jstsp_beamformer_c64(jstsp_ctx *ctx, int N, int kind, jstsp_c64 *W, int memspace);
+
+/* ase[t] = real(log2(det(eye(Mr) + scale * W_c' * (Y_t Y_t') * W_c)))   plot_capacity.m:47,52,57,64, plot_ee.m:48-65
+ * with W_c = W(:, cols(:, t)) (cols: Mr x batch, 1-based, same memspace) or W(:, 1:Mr) when cols is NULL (hbf.m:23).
+ * Y: Nr x T x batch; W: Nr x Ncols, shared by the batch; ase: batch doubles (same memspace).  The scale of the drivers is
+ * 1/(square_noise_variance * Nt).  P = W_c' Y is accumulated in fp64 from the operands, the Gram is taken on the smaller side
+ * (n = min(Mr, T), Sylvester) and factorised by an fp64 Cholesky; n > 64 returns JSTSP_E_UNSUPPORTED.  A column index outside
+ * 1..Ncols gives NaN for its own trial (nothing is read through it); non-finite input gives NaN.  The _c64 form reads double
+ * operands and computes the same way.  Asserted (tests/test_gpu_capacity.py): relative error against float64 on the same operand
+ * values <= 1e-13 (_c32) / 1e-14 (_c64) (measured 2.3e-15 / 2.3e-16) for Mr < T, Mr > T, Mr = 1, Mr = Ncols, T = 1, n = 64 and
+ * duplicated columns, in both memspaces; Y = 0 gives 0 exactly; cols = NULL gives the bits of cols = 1..Mr; prefixes of one
+ * codebook give a non-decreasing ASE; an Inf or NaN in Y gives NaN for its own trial only (both forms). */
+int jstsp_ase_c32(jstsp_ctx *ctx, int Nr, int T, int Ncols, int Mr, int batch, const jstsp_c32 *Y, const jstsp_c32 *W,
+                  const int32_t *cols, double scale, double *ase, int memspace);
+int jstsp_ase_c64(jstsp_ctx *ctx, int Nr, int T, int Ncols, int Mr, int batch, const jstsp_c64 *Y, const jstsp_c64 *W,
+                  const int32_t *cols, double scale, double *ase, int memspace);
+
+/* One combiner design of jstsp_ase_trials_c32: the codebook createBeamformer(Nr, kind) and
+ *   pool = 0: its first n_cols columns (hbf.m:23; plot_capacity.m:45-57: DBF = ('ZC', Nr), HBF-PS = ('quantized', Mr),
+ *             HBF-ZC = ('ZC', Mr));
+ *   pool > 0: n_cols columns drawn per trial from the first pool, ind = randperm(pool), ind(1:n_cols) (plot_capacity.m:61-64:
+ *             proposed = ('quantized', Mr, Mr_e)). */
+typedef struct { int kind; int n_cols; int pool; } jstsp_ase_design;
+
+/* plot_capacity.m:35-64 / plot_ee.m:36-65 for trials [trial0, trial0 + batch) of sweep point sweep_idx: the ASE of every design
+ * on one realisation.  The channel H and the pilot symbols of trial t are exactly those jstsp_build_trials_c32 returns for
+ * trial t of the same (model, seed, sweep_idx) (same Philox streams); Y = [H_1 .. H_L] Psi is noise-free (the drivers call
+ * hbf / proposed_hbf with N = zeros) and T = model->T_prop; scale = 1/(noise_var * Nt).  Fields read: Nt, Nr, L, T_prop,
+ * clusters, rays, shared_pilots, noise_var, pilots.  The codebook columns are generated from their phase indices on the device
+ * (never read from memory).  The column subsets of the pool > 0 designs: the n_cols smallest of pool Philox keys (stream 7,
+ * element (design index << 32) + i).  ase: n_designs x batch (ase[d + n_designs*t]); cols (optional, NULL = not wanted): per trial
+ * the 1-based subsets of the pool > 0 designs one after the other, in design order (sum of their n_cols) x batch.  Both in
+ * memspace.  1 <= n_designs <= 8; min(n_cols, T_prop) <= 64.  No _c64 form: no complex array crosses this boundary.
+ * Asserted: relative error <= 2e-12 per trial (measured 3.7e-13) against float64 ASE of jstsp_build_trials_c32's H and pilot
+ * symbols with the returned columns (three panel shapes, four Mr values, all four designs); a trial's values and columns do
+ * not depend on the batch it is computed in, nor on the memspace; the pilot options (shared_pilots, JSTSP_PILOTS_GAUSS) follow
+ * jstsp_build_trials_c32; the subsets are uniform (per-index frequency n_cols/pool within 5 sigma); panel-1
+ * means at 2000 trials lie within 4 standard errors of a numpy run of the reference's own samplers. */
+int jstsp_ase_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, const jstsp_ase_design *designs, int n_designs,
+                         uint64_t seed, int sweep_idx, long long trial0, int batch, double *ase, int32_t *cols,
+                         int memspace);
 
 /* ---- the reference's own element type at the boundary ------------------------------------------
  * Same functions, same argument meaning, arrays as MATLAB holds them: interleaved complex DOUBLE, and the 0/1 masks as

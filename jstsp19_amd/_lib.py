@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libjstsp_mi355x.so")
 
 HOST, DEVICE = 0, 1
 TYPE_APPROXIMATE, TYPE_STD = 0, 1
-BF_ZC, BF_DFT = 0, 1
+BF_ZC, BF_DFT, BF_QUANTIZED, BF_QUANTIZED4 = 0, 1, 2, 3
 RHO_MIN6, RHO_MAX = 0, 1
 PILOTS_QAM4, PILOTS_GAUSS = 0, 1
 
@@ -34,6 +34,11 @@ class Trials(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("subY", "Omega", "A", "B", "Zbar", "H", "indx_S")] + \
                [(n, c_dp) for n in ("tau_Y", "tau_Z", "rho")] + \
                [(n, c_void_p) for n in ("Y_hbf", "A_hbf", "B_hbf", "gains", "u_r", "u_t", "noise", "qam_idx", "pilot_sym")]
+
+
+class AseDesign(C.Structure):
+    """jstsp_ase_design (include/jstsp.h): codebook kind, columns, pool (0 = the first n_cols columns)."""
+    _fields_ = [("kind", c_int), ("n_cols", c_int), ("pool", c_int)]
 
 
 # name -> (restype, argtypes); mirrors include/jstsp.h one to one
@@ -90,13 +95,18 @@ SIGNATURES = {
     "jstsp_nmse_spectral_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "jstsp_build_trials_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, C.POINTER(Trials),
                                        c_int]),
+    "jstsp_beamformer_c32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
+    "jstsp_ase_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p,
+                              c_int]),
+    "jstsp_ase_trials_c32": (c_int, [c_void_p, C.POINTER(Model), C.POINTER(AseDesign), c_int, C.c_uint64, c_int, c_ll, c_int,
+                                     c_void_p, c_void_p, c_int]),
     "jstsp_set_profiling": (c_int, [c_void_p, c_int]),
     "jstsp_get_profile": (c_int, [c_void_p, C.c_char_p, c_ip, c_dp]),
 }
 
 
 for _n in ("correlate", "synthesize", "proposed_algorithm", "svt", "omp", "sparse_admm", "mc_svt", "mc_admm", "vamp", "ls", "pinv",
-           "mmv_omp", "vamp_kron", "nmse_spectral", "rate"):
+           "mmv_omp", "vamp_kron", "nmse_spectral", "rate", "beamformer", "ase"):
     # the double-complex forms take the same argument lists (pointers are void* here)
     SIGNATURES["jstsp_%s_c64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 

@@ -13,99 +13,12 @@
 // Random numbers: Philox4x32-10, key = mix(seed, sweep index, global trial index), counter =
 // (element index, stream id) — a trial's inputs do not depend on the batch it is drawn in or
 // on how trials are sharded over GPUs.
-#include "solver_common.h"
+#include "inputgen.h"
 #include <hipcub/hipcub.hpp>
 
 using namespace jstsp;
 
 namespace {
-
-enum { ST_GAIN = 0, ST_UR = 1, ST_UT = 2, ST_NOISE = 3, ST_QAM = 4, ST_OMEGA = 5, ST_PILOT = 6 };
-
-__host__ __device__ inline uint64_t mix_key(uint64_t seed, uint64_t sweep, uint64_t trial)
-{
-    uint64_t x = seed * 0x9E3779B97F4A7C15ull + sweep * 0xBF58476D1CE4E5B9ull + trial * 0x94D049BB133111EBull;
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-__device__ __forceinline__ uint4 philox(uint64_t elem, uint32_t stream, uint64_t key64)
-{
-    uint32_t c0 = (uint32_t)elem, c1 = (uint32_t)(elem >> 32), c2 = stream, c3 = 0u;
-    uint32_t k0 = (uint32_t)key64, k1 = (uint32_t)(key64 >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
-__device__ __forceinline__ float u01(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
-// two independent N(0,1) from two words (Box-Muller)
-__device__ __forceinline__ float2 normal2(uint32_t w0, uint32_t w1)
-{
-    const float r = sqrtf(-2.0f * logf(u01(w0)));
-    float s, c;
-    sincospif(2.0f * u01(w1), &s, &c);
-    return make_float2(r * c, r * s);
-}
-
-struct Model {
-    int Nt, Nr, L, Tp, Mr, Mr_e, Gr, Gt, clusters, rays, Np, NtL, G2;
-};
-
-// ---- gains / angle draws (wideband_mmwave_channel.m:19-22; only tap 1's angles are used, :24) ----
-__global__ void draw_small_kernel(Model m, uint64_t seed, uint64_t sweep, long long trial0, float2 *gains,
-                                  float *u_r, float *u_t)
-{
-    const int t = blockIdx.x;
-    const uint64_t key = mix_key(seed, sweep, (uint64_t)(trial0 + t));
-    for (int i = threadIdx.x; i < m.L * m.Np; i += blockDim.x) {
-        const uint4 w = philox((uint64_t)i, ST_GAIN, key);
-        const float2 g = normal2(w.x, w.y);
-        gains[(size_t)t * m.L * m.Np + i] = make_float2(g.x * 0.70710678f, g.y * 0.70710678f);     // :19
-    }
-    for (int i = threadIdx.x; i < m.Np; i += blockDim.x) {
-        u_r[(size_t)t * m.Np + i] = u01(philox((uint64_t)i, ST_UR, key).x);                          // :20
-        u_t[(size_t)t * m.Np + i] = u01(philox((uint64_t)i, ST_UT, key).x);                          // :22
-    }
-}
-
-// noise = randn + 1j*randn (plot_errorVSsnr.m:60, unscaled) and the 4-QAM symbol indices (qam4mod.m:8)
-// gauss != 0: Gaussian pilot draws randn + 1j*randn into psym instead (wideband_hybBF_comm_system_training.m:20, before its 1/sqrt(2))
-__global__ __launch_bounds__(256) void draw_noise_qam_kernel(Model m, uint64_t seed, uint64_t sweep, long long trial0,
-                                                             float2 *noise, uint8_t *qam, int shared_pilots, int gauss,
-                                                             float2 *psym)
-{
-    const int t = blockIdx.y;
-    const uint64_t key = mix_key(seed, sweep, (uint64_t)(trial0 + t));
-    const uint64_t qkey = shared_pilots ? mix_key(seed, sweep, ~0ull) : key;     // one pilot set per sweep point
-    const long long nn = (long long)m.Nr * m.Tp, nq = (long long)m.Nt * m.Tp;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nn; i += stride) {
-        const uint4 w = philox((uint64_t)i, ST_NOISE, key);
-        noise[(size_t)t * nn + i] = normal2(w.x, w.y);
-    }
-    const float a = 0.70710678f;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += stride) {
-        if (gauss) {
-            const uint4 w = philox((uint64_t)i, ST_PILOT, qkey);
-            psym[(size_t)t * nq + i] = normal2(w.x, w.y);
-            qam[(size_t)t * nq + i] = 0;
-        } else {
-            const uint8_t q = (uint8_t)(philox((uint64_t)i, ST_QAM, qkey).x & 3u);
-            qam[(size_t)t * nq + i] = q;
-            // alphabet order of qam4mod.m:7: (1+j), (-1+j), (1-j), (-1-j), all / sqrt(2)
-            psym[(size_t)t * nq + i] = make_float2((q & 1) ? -a : a, (q & 2) ? -a : a);
-        }
-    }
-}
 
 // Omega(:, j): ones on the Mr rows with the smallest of Mr_e uniform keys (= randperm(Mr_e)(1:Mr), proposed_hbf.m:37-40)
 __global__ __launch_bounds__(256) void omega_kernel(Model m, uint64_t seed, uint64_t sweep, long long trial0,
@@ -144,51 +57,6 @@ __global__ void dict_kernel(int rows, int cols, int kind, float2 *D)
     }
     const float sc = rsqrtf((float)rows);
     D[i] = make_float2(c * sc, s * sc);
-}
-
-// ---- channel: Hmat[t] = [H_1 ... H_L]  (Nr x Nt*L), H_l = 1/sqrt(Np) sum_p w_p g[l,p] a_r(p) a_t(p)^H
-//      with tap 1's steering vectors for every l (:24) and w_p = clusters - cluster(p) (:29)
-__global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gains, const float *u_r,
-                                                      const float *u_t, float2 *Hmat)
-{
-    extern __shared__ float2 sh[];
-    float2 *ar = sh, *at = sh + (size_t)m.Nr * m.Np, *cf = at + (size_t)m.Nt * m.Np;
-    const int t = blockIdx.y;
-    const double beta = 1.0 / (1.0 - exp(-sqrt(2.0) * M_PI / 50.0));
-    const double e0 = exp(-sqrt(2.0) / 50.0 * M_PI);
-    for (int i = threadIdx.x; i < (m.Nr + m.Nt) * m.Np; i += 256) {
-        const bool rx = i < m.Nr * m.Np;
-        const int ii = rx ? i : i - m.Nr * m.Np;
-        const int dim = rx ? m.Nr : m.Nt;
-        const int n = ii % dim, p = ii / dim;
-        const double u = rx ? u_r[(size_t)t * m.Np + p] : u_t[(size_t)t * m.Np + p];
-        const double phi = beta * (e0 - cosh(u));                      // :56-62
-        double s, c;
-        sincos(-M_PI * sin(-phi) * (double)n, &s, &c);                 // :42-52
-        (rx ? ar : at)[ii] = make_float2((float)c, (float)s);
-    }
-    const float isq = rsqrtf((float)m.Np);
-    for (int i = threadIdx.x; i < m.L * m.Np; i += 256) {
-        const int p = i % m.Np;
-        const float w = (float)(m.clusters - p / m.rays) * isq;
-        const float2 g = gains[(size_t)t * m.L * m.Np + i];
-        cf[i] = make_float2(g.x * w, g.y * w);
-    }
-    __syncthreads();
-    const long long n_el = (long long)m.Nr * m.NtL;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n_el; e += (long long)gridDim.x * 256) {
-        const int r = (int)(e % m.Nr);
-        const int sl = (int)(e / m.Nr);
-        const int s = sl % m.Nt, l = sl / m.Nt;
-        float hx = 0.f, hy = 0.f;
-        for (int p = 0; p < m.Np; ++p) {
-            const float2 a = ar[p * m.Nr + r], b = at[p * m.Nt + s], c = cf[l * m.Np + p];
-            const float qx = a.x * b.x + a.y * b.y, qy = a.y * b.x - a.x * b.y;     // a * conj(b)
-            hx += c.x * qx - c.y * qy;
-            hy += c.x * qy + c.y * qx;
-        }
-        Hmat[(size_t)t * n_el + e] = make_float2(hx, hy);
-    }
 }
 
 // ---- pilots: Psi[t] (Nt*L x Tp), row (s + Nt*l), column j = toeplitz(s_s)(l, j): s(|j-l|), conjugated below the diagonal
@@ -284,7 +152,6 @@ __global__ void offsets_kernel(int batch, long long nz, int *off)
     for (int i = threadIdx.x; i <= batch; i += blockDim.x) off[i] = (int)(i * nz);
 }
 
-inline int grid_for(long long n, int cap = 4096) { return (int)std::min<long long>((n + 255) / 256, cap); }
 
 template <class T> T *out_or_tmp(jstsp_ctx *ctx, T *user, size_t n, int memspace)
 {

@@ -14,10 +14,11 @@ from __future__ import annotations
 
 import torch
 
-from .system_model import SweepParams, TrainingParams, build_trials, build_trials_training
+from .system_model import SweepParams, TrainingParams, ase_trials, build_trials, build_trials_training
 
 __all__ = ["partition", "run_sweep", "run_points", "sweep_points", "run_approx_sweep", "driver", "run_driver",
-           "admmiters_points", "run_convergence_curves", "zy_points", "run_zy"]
+           "admmiters_points", "run_convergence_curves", "zy_points", "run_zy", "capacity_points", "capacity_designs",
+           "power_model", "run_capacity"]
 
 
 def partition(n_items, world, rank):
@@ -485,3 +486,50 @@ def run_zy(points=None, n_trials=1, *, Imax=50, batch=32, seed=20190913, device=
         return torch.stack([torch.as_tensor(ez).double().cpu(), torch.as_tensor(ey).double().cpu()], dim=1)
 
     return _generic_sharded(points, n_trials, 2, work, batch=batch, seed=seed, device=device, dist=dist, builder=builder)
+
+
+# (Nr, Mr_e) of the three panels of plot_capacity.m (:8-19, :92-103, :175-186); plot_ee.m (:1-12) is panel 2's shape
+CAPACITY_PANELS = {1: (32, 32), 2: (64, 32), 3: (128, 64)}
+CAPACITY_DESIGNS = ("DBF", "HBF-PS", "HBF-ZC", "proposed")
+
+
+def capacity_points(panel):
+    """The 11 Mr points ``1:3:32`` of one panel of plot_capacity.m (panel 3: ``1:3:floor(Mr_e/2)``, the same points):
+    Nt = 16, L = 4, T = 5, 2 clusters x 3 rays, Gr = Nr, sigma^2 = 10^(-15/10); the frame is T itself."""
+    Nr, Mr_e = CAPACITY_PANELS[panel]
+    return [SweepParams(Nt=16, Nr=Nr, L=4, T=5, Mr=Mr, Mr_e=Mr_e, snr_db=15.0, T_prop=5) for Mr in range(1, 33, 3)]
+
+
+def capacity_designs(p):
+    """The four combiners of plot_capacity.m at point ``p``: DBF ('ZC', all Nr columns, :45-47), HBF-PS ('quantized', first
+    Mr, :50-52), HBF-ZC ('ZC', first Mr, :55-57), proposed ('quantized', Mr of the first Mr_e drawn per realisation, :61-64)."""
+    return [("ZC", p.Nr, 0), ("quantized", p.Mr, 0), ("ZC", p.Mr, 0), ("quantized", p.Mr, p.Mr_e)]
+
+
+def power_model(Nr, Mr, Mr_e, *, Psw=0.005, Pps=0.015, Plna=0.02, Pps_zc=0.06, Pcirc=0.0):
+    """plot_ee.m:69-77 — power of (DBF, HBF-PS, HBF-ZC, proposed); EE = mean ASE / power (:84-87)."""
+    return [Pcirc + Nr * Nr * Plna + Nr * (Nr + 1) * Pps_zc,
+            Pcirc + Mr * Nr * Plna + Nr * (Mr + 1) * Pps,
+            Pcirc + Mr * Nr * Plna + Nr * (Mr + 1) * Pps_zc,
+            Pcirc + Mr_e * Nr * Plna + Mr_e * Psw + Nr * (Mr_e + 1) * Pps]
+
+
+def run_capacity(points, n_trials, *, batch=4096, seed=20190913, sweep0=0, device=None, dist=None):
+    """plot_capacity.m:32-75 / plot_ee.m:33-88 on the HIP path: per point the mean ASE of the four designs of
+    ``capacity_designs`` over ``n_trials`` fresh realisations (point i is sweep index ``sweep0 + i``), sharded over the
+    ranks of ``dist`` with one all-reduce of the sums.  Returns float64 numpy (mean, standard error), each
+    (len(points), 4)."""
+    import numpy as np
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+
+    def build(p, trials, seed_, pt, device_, _):
+        return ase_trials(p, capacity_designs(p), trials.start, len(trials), seed=seed_, sweep_idx=sweep0 + pt, device=device_)
+
+    def work(a, p):
+        return torch.cat([a, a * a], dim=1)
+
+    m = _generic_sharded(points, n_trials, 8, work, batch=batch, seed=seed, device=device, dist=dist, builder=build).numpy()
+    mean = m[:, :4]
+    var = np.maximum(m[:, 4:] - mean * mean, 0.0) * (n_trials / max(n_trials - 1, 1))
+    return mean, np.sqrt(var / n_trials)

@@ -28,7 +28,7 @@ from ._lib import DEVICE, HOST, JstspError, check
 
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
            "sparse_admm", "vamp", "vamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
-           "empty_colmajor"]
+           "empty_colmajor", "beamformer", "ase"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -599,3 +599,87 @@ def cawgn_estim_out(y, phat, pvar, wvar, *, ctx=None):
     check(c._lib.jstsp_cawgn_estim_out_f64(c.handle, yy.size, yy.ctypes.data, pp.ctypes.data, float(pvar), float(wvar), zh.ctypes.data,
                                            C.byref(zv), HOST), "jstsp_cawgn_estim_out_f64")
     return zh.reshape(np.shape(y)), float(zv.value)
+
+
+# ----------------------------------------------------------------------------- capacity / energy efficiency
+BEAMFORMER_KINDS = {"ZC": _lib.BF_ZC, "fft": _lib.BF_DFT, "ps": _lib.BF_DFT, "quantized": _lib.BF_QUANTIZED,
+                    "quantized_4": _lib.BF_QUANTIZED4}
+
+
+def _bf_kind(kind):
+    if kind not in BEAMFORMER_KINDS:
+        raise ValueError("beamformer kind must be one of %s, got %r" % (sorted(BEAMFORMER_KINDS), kind))
+    return BEAMFORMER_KINDS[kind]
+
+
+def beamformer(N, kind, *, dtype=np.complex64, device=None, ctx=None):
+    """createBeamformer.m:1-35 — ``createBeamformer(N, kind)`` for 'ZC', 'fft', 'ps', 'quantized', 'quantized_4' (N x N).
+    numpy (host path) by default; ``device``: a column-major torch tensor on that GPU.  ``dtype=np.complex128`` takes
+    ``jstsp_beamformer_c64`` (phases evaluated in float64)."""
+    k = _bf_kind(kind)
+    f64 = np.dtype(dtype) == np.complex128
+    N = int(N)
+    if device is not None:
+        import torch
+        dev = torch.device(device)
+        c = ctx or _lib.default_context(dev.index or 0)
+        c.use_torch_stream()
+        W = empty_colmajor(1, N, N, torch.complex128 if f64 else torch.complex64, dev)[0]
+        ptr, mem = W.data_ptr(), DEVICE
+    else:
+        c = ctx or _lib.default_context(0)
+        buf = np.empty((N, N), dtype=np.complex128 if f64 else np.complex64)       # [column][row]
+        ptr, mem = buf.ctypes.data, HOST
+    fn, name = (c._lib.jstsp_beamformer_c64, "jstsp_beamformer_c64") if f64 else (c._lib.jstsp_beamformer_c32, "jstsp_beamformer_c32")
+    check(fn(c.handle, N, k, ptr, mem), name)
+    return W if device is not None else buf.T
+
+
+def ase(Y, W, scale, Mr=None, cols=None, *, ctx=None):
+    """plot_capacity.m:47,52,57,64 — ``real(log2(det(eye(Mr) + scale * W_c'*(Y*Y')*W_c)))`` per problem, with
+    ``W_c = W(:, cols)`` (1-based, per problem) or ``W(:, 1:Mr)`` (hbf.m:23).  ``Y``: (Nr, T) or (batch, Nr, T); ``W``: (Nr, Ncols),
+    shared; ``cols``: (Mr,) or (batch, Mr) integers.  complex128 ``Y`` and ``W`` take ``jstsp_ase_c64``.  Returns float64
+    (batch,) (a scalar for 2-D ``Y``); a bad column index gives NaN for its problem."""
+    f64 = _is_c128(Y) and _is_c128(W)
+    cdt = np.complex128 if f64 else np.complex64
+    a_Y, a_W = _Arg(Y, cdt, "Y"), _Arg(W, cdt, "W")
+    if a_W.batched:
+        raise ValueError("W is shared by the batch: pass one (Nr, Ncols) matrix")
+    if a_W.R != a_Y.R:
+        raise ValueError("Y and W must have the same number of rows")
+    c, mem, dev = _ctx_for([a_Y, a_W], ctx)
+    if mem == DEVICE and a_W.device != dev:
+        raise ValueError("Y and W must live on the same GPU")
+    batch = a_Y.batch
+    cptr, keep = None, None
+    if cols is not None:
+        # cols lives where Y and W live: the library reads it in the call's memspace
+        if mem == DEVICE:
+            import torch
+            if not (_is_torch(cols) and cols.is_cuda and cols.device == dev and cols.dtype == torch.int32):
+                raise ValueError("cols: with device arrays pass an int32 CUDA tensor on the device of Y (%s)" % dev)
+            keep = cols.reshape(-1, cols.shape[-1]).contiguous()
+        else:
+            if _is_torch(cols):
+                raise ValueError("cols: with host (numpy) arrays pass a numpy integer array, not a torch tensor")
+            keep = np.ascontiguousarray(np.asarray(cols, dtype=np.int32).reshape(-1, np.shape(cols)[-1]))
+        if keep.shape[0] == 1 and batch > 1:
+            keep = keep.expand(batch, -1).contiguous() if _is_torch(keep) else np.ascontiguousarray(np.repeat(keep, batch, 0))
+        if keep.shape[0] != batch:
+            raise ValueError("cols must have one row per problem (%d), got %d" % (batch, keep.shape[0]))
+        if Mr is not None and int(Mr) != keep.shape[1]:
+            raise ValueError("Mr disagrees with cols")
+        Mr = keep.shape[1]
+        cptr = keep.data_ptr() if _is_torch(keep) else keep.ctypes.data
+    elif Mr is None:
+        Mr = a_W.C
+    if mem == DEVICE:
+        import torch
+        out = torch.empty(batch, dtype=torch.float64, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty(batch, dtype=np.float64)
+        optr = out.ctypes.data
+    fn, name = (c._lib.jstsp_ase_c64, "jstsp_ase_c64") if f64 else (c._lib.jstsp_ase_c32, "jstsp_ase_c32")
+    check(fn(c.handle, a_Y.R, a_Y.C, a_W.C, int(Mr), batch, a_Y.ptr, a_W.ptr, cptr, float(scale), optr, mem), name)
+    return out if a_Y.batched else out[0]

@@ -21,7 +21,7 @@ import math
 
 import torch
 
-__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training"]
+__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training", "ase_trials"]
 
 
 class SweepParams:
@@ -172,3 +172,37 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
     _lib.check(rc, "jstsp_build_trials_c32")
     out.update({k: torch.from_numpy(v) for k, v in hyp.items()})
     return out
+
+
+def ase_trials(p: SweepParams, designs, trial0, batch, *, seed=20190913, sweep_idx=0, want_cols=False, device=None, ctx=None,
+               shared_pilots=False, pilots="qam4"):
+    """plot_capacity.m:35-64 / plot_ee.m:36-65 for trials [trial0, trial0 + batch) on the HIP path
+    (``jstsp_ase_trials_c32``, csrc/capacity.hip): the achievable spectral efficiency of every combiner design on one
+    realisation, ``real(log2(det(eye(Mr) + 1/(noise_var*Nt) W_c'*(Y*Y')*W_c)))`` with the noise-free ``Y`` of the frame
+    ``p.T_prop``.  Trial t has the channel and pilots ``build_trials(p, ...)`` returns for t with the same seed, sweep index,
+    ``shared_pilots`` and ``pilots`` (the drivers: fresh 4-QAM pilots per realisation, the defaults of both).
+
+    ``designs``: (kind, n_cols, pool) per design, kind as ``solvers.beamformer``; pool = 0: the first n_cols columns
+    (hbf.m:23), pool > 0: n_cols columns drawn per trial from the first pool (plot_capacity.m:63-64).
+    Returns the float64 (batch, len(designs)) ASE on the device; with ``want_cols`` also the int32 (batch, sum of n_cols of
+    the pool > 0 designs) 1-based subsets, design after design."""
+    import ctypes as C
+    from . import _lib
+    from .solvers import _bf_kind
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    c = ctx if ctx is not None else _lib.default_context(device.index or 0)
+    c.use_torch_stream()
+    model = _lib.Model(p.Nt, p.Nr, p.L, p.T_prop, p.Mr, p.Mr_e, p.Gr, p.Gt, p.clusters, p.rays, 0, 1 if shared_pilots else 0,
+                       p.noise_var, _lib.BF_ZC, _lib.RHO_MIN6, 1.0,
+                       _lib.PILOTS_GAUSS if pilots == "gauss" else _lib.PILOTS_QAM4)
+    ds = (_lib.AseDesign * len(designs))(*[_lib.AseDesign(_bf_kind(k), int(n), int(pool)) for k, n, pool in designs])
+    n_sel = sum(int(n) for _, n, pool in designs if int(pool) > 0)
+    out = torch.empty((batch, len(designs)), dtype=torch.float64, device=device)
+    cols = torch.empty((batch, max(n_sel, 1)), dtype=torch.int32, device=device) if want_cols else None
+    rc = c._lib.jstsp_ase_trials_c32(c.handle, C.byref(model), ds, len(designs), C.c_uint64(seed), int(sweep_idx),
+                                     int(trial0), int(batch), out.data_ptr(), cols.data_ptr() if want_cols else None,
+                                     _lib.DEVICE)
+    _lib.check(rc, "jstsp_ase_trials_c32")
+    return (out, cols[:, :n_sel]) if want_cols else out
