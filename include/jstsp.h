@@ -516,6 +516,37 @@ int jstsp_ase_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, const jstsp_a
                          uint64_t seed, int sweep_idx, long long trial0, int batch, double *ase, int32_t *cols,
                          int memspace);
 
+/* ---- singular values, and the spectrum sweep of plot_rankR.m (csrc/svdvals.hip) ---------------------------------------------
+ * sv(:, t) = svd(Y_t): the min(rows, cols) singular values of each matrix, descending, as doubles in the memspace of Y
+ * (sv[k + min(rows, cols)*t]).  Y: rows x cols x batch, column-major.  Computed by a one-sided (Hestenes) Jacobi iteration in
+ * float64 on the columns of Y itself (of Y^H when rows < cols), one workgroup per matrix with the matrix in LDS - NOT through
+ * a Gram matrix, which squares the condition number and returns a zero singular value near sqrt(eps) sigma_1: the values that
+ * decide a numerical rank are accurate to eps sigma_1 here.  No singular vectors.  The operand is scaled by a power of two
+ * first, so any finite input is safe; the sweeps stop when one rotates nothing (|c_p^H c_q| <= sqrt(m) eps |c_p| |c_q| for
+ * every pair; columns that have fallen to eps |Y|_F / sqrt(n) are zero singular values and are left alone) or after 30.  Shapes: min(rows, cols) <= 64 and rows * cols <= 8192 (128 KiB of complex double), else
+ * JSTSP_E_UNSUPPORTED - there is no fall-back.  An Inf or NaN entry gives NaN for all values of its own matrix only.  The _c64
+ * form reads double operands and computes the same way.  Asserted (tests/test_gpu_singular_values.py) against
+ * numpy.linalg.svd in float64 on the same operand values: max_k |sv_k - ref_k| / ref_1 <= 9e-14 for 32x50, 64x50, 128x50,
+ * 50x128, 64x64, 128x64, 1x7, 7x1, 5x5, rank 6, sigma graded over 12 decades, repeated sigma (measured 1.8e-14); the zero
+ * matrix gives exact zeros; both memspaces give the same bits; sv(Y) = sv(Y^H) = sv(Y Q) for a permutation Q within that bound;
+ * sv_1^2 agrees with jstsp_lambda_max_sequence_c32 on Y Y^H within that entry's 2e-5. */
+int jstsp_singular_values_c32(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c32 *Y, double *sv, int memspace);
+int jstsp_singular_values_c64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *Y, double *sv, int memspace);
+
+/* plot_rankR.m:24-50 for trials [trial0, trial0 + batch) of sweep point sweep_idx: the first n_keep <= min(Nr, T_prop) singular
+ * values of the noise-free Y = [H_1 .. H_L] Psi (Nr x T_prop; proposed_hbf.m:15-20 with N = zeros), sv[k + n_keep*t] in
+ * memspace.  The channel H and the pilot symbols of trial t are exactly those jstsp_build_trials_c32 returns for trial t of
+ * the same (model, seed, sweep_idx) (same Philox streams and kernels, csrc/inputgen.h); Y is formed in fp64 in LDS from those
+ * fp32 operands; no noise and no Omega is drawn.  Fields read: Nt, Nr, L, T_prop, clusters, rays, shared_pilots, pilots.
+ * Shapes as jstsp_singular_values_c32 on Nr x T_prop.  No _c64 form: no complex array crosses this boundary.
+ * Asserted: max_k |sv_k - ref_k| / ref_1 <= 5e-14 (measured 9.7e-15) against the float64 SVD of Y rebuilt from
+ * jstsp_build_trials_c32's H and pilot symbols, for the six panels of the figure at L = 1, 4, 8; a trial's values do not depend
+ * on the batch it is computed in, nor on the memspace; the pilot options follow jstsp_build_trials_c32; over 256 trials per
+ * point sv_{r+1} / sv_1, r = min(Np, L Nt, Nr, T), stays within 10 x the largest value of the float64 reference (H is fp32, so
+ * the tail is of order 6e-8 sqrt(Nr Nt L), not zero). */
+int jstsp_rank_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx, long long trial0, int batch,
+                          int n_keep, double *sv, int memspace);
+
 /* ---- the reference's own element type at the boundary ------------------------------------------
  * Same functions, same argument meaning, arrays as MATLAB holds them: interleaved complex DOUBLE, and the 0/1 masks as
  * double (proposed_hbf.m:36-41 builds Omega with zeros()).  Inputs are narrowed and outputs widened on the device;

@@ -226,21 +226,7 @@ __global__ __launch_bounds__(256) void ase_sweep_kernel(Model m, Designs ds, uin
     double2 *G = reinterpret_cast<double2 *>(sel + r4);
     const float2 *H = Hmat + (size_t)t * m.Nr * m.NtL;
     const float2 *sym = psym + (size_t)t * m.Nt * m.Tp;
-    for (int e = tid; e < m.Nr * m.Tp; e += blockDim.x) {
-        const int r = e % m.Nr, j = e / m.Nr;
-        double yr = 0.0, yi = 0.0;
-        for (int l = 0; l < m.L; ++l) {
-            const int d = j - l;                                  // Psi_bar_l(s, j) = toeplitz(s_s)(l, j): s(|j-l|), conj below
-            for (int s = 0; s < m.Nt; ++s) {
-                const float2 h = H[r + (size_t)m.Nr * (s + m.Nt * l)];
-                const float2 v = sym[s * m.Tp + (d < 0 ? -d : d)];
-                const double px = (double)(v.x * pscale), py = (double)((d < 0 ? -v.y : v.y) * pscale);   // pilots_kernel's values
-                yr += (double)h.x * px - (double)h.y * py;
-                yi += (double)h.x * py + (double)h.y * px;
-            }
-        }
-        Y[e] = make_double2(yr, yi);
-    }
+    for (int e = tid; e < m.Nr * m.Tp; e += blockDim.x) Y[e] = received_entry(m, H, sym, pscale, e % m.Nr, e / m.Nr);
     const uint64_t key = mix_key(seed, sweep, (uint64_t)(trial0 + t));
     for (int di = 0; di < ds.n; ++di) {
         const Design dz = ds.d[di];
@@ -397,37 +383,24 @@ int jstsp_ase_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, const jstsp_ase_
         lds_g = std::max(lds_g, ase_lds_bytes(d.n_cols, m.Tp));
     }
     const size_t r4 = (size_t)((m.Nr + 3) & ~3);
-    const size_t lds_ch = ((size_t)(m.Nr + m.Nt) * m.Np + (size_t)m.L * m.Np) * sizeof(float2);
+    const size_t lds_ch = channel_lds_bytes(m);
     const size_t lds = (size_t)m.Nr * m.Tp * sizeof(double2) + (size_t)std::max(2 * m.Nr, 64) * sizeof(float2) + 2 * r4 * 4 + lds_g;
     JSTSP_REQUIRE(lds_ch <= 150 * 1024 && lds <= 150 * 1024, JSTSP_E_UNSUPPORTED, "ase_trials: Nr x T_prop too large for the LDS");
 
     const size_t b = (size_t)batch;
-    const size_t nH = (size_t)m.Nr * m.NtL, nQ = (size_t)m.Nt * m.Tp;
-    size_t need = 0;
-    auto acc = [&](size_t bytes) { need += rnd256(bytes); };
-    acc(b * m.L * m.Np * 8); acc(b * m.Np * 4); acc(b * m.Np * 4); acc(b * nQ); acc(b * nQ * 8); acc(b * nH * 8); acc(b * n_designs * 8); acc(b * (n_sel + 1) * 4);
-    JSTSP_TRY(ctx->arena.reserve(need + 4096));
+    JSTSP_TRY(ctx->arena.reserve(operands_bytes(m, b) + rnd256(b * n_designs * 8) + rnd256(b * (n_sel + 1) * 4) + 4096));
     ctx->arena.reset();
     Arena &ar = ctx->arena;
-    float2 *gains = ar.get<float2>(b * m.L * m.Np), *psym = ar.get<float2>(b * nQ), *Hmat = ar.get<float2>(b * nH);
-    float *u_r = ar.get<float>(b * m.Np), *u_t = ar.get<float>(b * m.Np);
-    uint8_t *qam = ar.get<uint8_t>(b * nQ);
-    double *o = memspace == JSTSP_DEVICE ? ase : ar.get<double>(b * n_designs);
-    int32_t *c = cols && n_sel ? (memspace == JSTSP_DEVICE ? cols : ar.get<int32_t>(b * n_sel)) : nullptr;
-    JSTSP_REQUIRE(gains && psym && Hmat && u_r && u_t && qam && o && (c || !(cols && n_sel)), JSTSP_E_NOMEM,
-                  "ase_trials: workspace exhausted");
-    hipStream_t st = ctx->stream;
-    const uint64_t sw = (uint64_t)sweep_idx;
-    const int gauss = mp->pilots == JSTSP_PILOTS_GAUSS;
     // the draws and the channel of jstsp_build_trials_c32 (csrc/inputgen.hip) for the same (seed, sweep_idx, trial); Y is
     // noise-free (the drivers pass N = zeros), so the noise block is not drawn
-    draw_small_kernel<<<batch, 64, 0, st>>>(m, seed, sw, trial0, gains, u_r, u_t);
-    draw_noise_qam_kernel<<<dim3(grid_for((long long)nQ, 1024), batch), 256, 0, st>>>(
-        m, seed, sw, trial0, nullptr, qam, mp->shared_pilots, gauss, psym);
-    channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, Hmat);
-    JSTSP_HIP(hipGetLastError());
+    Operands op;
+    JSTSP_TRY(draw_operands(ctx, m, mp, seed, (uint64_t)sweep_idx, trial0, batch, &op));
+    double *o = memspace == JSTSP_DEVICE ? ase : ar.get<double>(b * n_designs);
+    int32_t *c = cols && n_sel ? (memspace == JSTSP_DEVICE ? cols : ar.get<int32_t>(b * n_sel)) : nullptr;
+    JSTSP_REQUIRE(o && (c || !(cols && n_sel)), JSTSP_E_NOMEM, "ase_trials: workspace exhausted");
+    hipStream_t st = ctx->stream;
     JSTSP_HIP(hipFuncSetAttribute((const void *)ase_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ase_sweep_kernel<<<batch, 256, lds, st>>>(m, ds, seed, sw, trial0, Hmat, psym, gauss ? 0.70710678f : 1.f,
+    ase_sweep_kernel<<<batch, 256, lds, st>>>(m, ds, seed, (uint64_t)sweep_idx, trial0, op.Hmat, op.psym, op.pscale,
                                               1.0 / (mp->noise_var * m.Nt), n_sel, o, c);
     JSTSP_HIP(hipGetLastError());
     if (memspace == JSTSP_HOST) {

@@ -1,5 +1,6 @@
 // Philox streams, the per-trial draws and the channel of the device-side trial construction (csrc/inputgen.hip), shared
-// with the capacity sweep (csrc/capacity.hip) so that both see the same channel and pilots for the same (seed, sweep, trial).
+// with the capacity sweep (csrc/capacity.hip) and the rank sweep (csrc/svdvals.hip) so that all of them see the same channel
+// and pilots for the same (seed, sweep, trial).
 #pragma once
 #include "solver_common.h"
 
@@ -139,5 +140,57 @@ __global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gai
 }
 
 inline int grid_for(long long n, int cap = 4096) { return (int)std::min<long long>((n + 255) / 256, cap); }
+
+// ---- the noise-free receive signal of the sweeps that have no solver on their path (hbf.m:12-18, proposed_hbf.m:15-20, N = 0)
+// Entry (r, j) of Y = sum_l H_l Psi_bar_l in fp64 from one trial's H (Nr x Nt*L) and pilot symbols (Nt x Tp, unscaled draws):
+// Psi_bar_l(s, j) = toeplitz(s_s)(l, j) = s_s(|j - l|), conjugated below the diagonal; pscale: pilots_kernel's fp32 scaling.
+__device__ __forceinline__ double2 received_entry(const Model &m, const float2 *H, const float2 *sym, float pscale, int r, int j)
+{
+    double yr = 0.0, yi = 0.0;
+    for (int l = 0; l < m.L; ++l) {
+        const int d = j - l;
+        for (int s = 0; s < m.Nt; ++s) {
+            const float2 h = H[r + (size_t)m.Nr * (s + m.Nt * l)];
+            const float2 v = sym[s * m.Tp + (d < 0 ? -d : d)];
+            const double px = (double)(v.x * pscale), py = (double)((d < 0 ? -v.y : v.y) * pscale);   // pilots_kernel's values
+            yr += (double)h.x * px - (double)h.y * py;
+            yi += (double)h.x * py + (double)h.y * px;
+        }
+    }
+    return make_double2(yr, yi);
+}
+
+// The channel and pilot symbols of jstsp_build_trials_c32's trials [trial0, trial0 + batch) of (seed, sweep) in the context's
+// arena, which the caller has reserved (operands_bytes) and reset: the same three kernels on the same Philox streams, without
+// the noise block.  Hmat: Nr x Nt*L per trial; psym: Nt x Tp per trial, to be scaled by *pscale.
+struct Operands { float2 *Hmat, *psym; float pscale; };
+
+inline size_t operands_bytes(const Model &m, size_t b)
+{
+    const size_t nQ = (size_t)m.Nt * m.Tp;
+    return jstsp::rnd256(b * m.L * m.Np * 8) + 2 * jstsp::rnd256(b * m.Np * 4) + jstsp::rnd256(b * nQ) + jstsp::rnd256(b * nQ * 8) +
+           jstsp::rnd256(b * m.Nr * m.NtL * 8);
+}
+inline size_t channel_lds_bytes(const Model &m) { return ((size_t)(m.Nr + m.Nt) * m.Np + (size_t)m.L * m.Np) * sizeof(float2); }
+
+inline int draw_operands(jstsp_ctx *ctx, const Model &m, const jstsp_model *mp, uint64_t seed, uint64_t sweep, long long trial0,
+                         int batch, Operands *out)
+{
+    const size_t b = (size_t)batch, nH = (size_t)m.Nr * m.NtL, nQ = (size_t)m.Nt * m.Tp;
+    jstsp::Arena &ar = ctx->arena;
+    float2 *gains = ar.get<float2>(b * m.L * m.Np), *psym = ar.get<float2>(b * nQ), *Hmat = ar.get<float2>(b * nH);
+    float *u_r = ar.get<float>(b * m.Np), *u_t = ar.get<float>(b * m.Np);
+    uint8_t *qam = ar.get<uint8_t>(b * nQ);
+    JSTSP_REQUIRE(gains && psym && Hmat && u_r && u_t && qam, JSTSP_E_NOMEM, "trial operands: workspace exhausted");
+    hipStream_t st = ctx->stream;
+    const int gauss = mp->pilots == JSTSP_PILOTS_GAUSS;
+    draw_small_kernel<<<batch, 64, 0, st>>>(m, seed, sweep, trial0, gains, u_r, u_t);
+    draw_noise_qam_kernel<<<dim3(grid_for((long long)nQ, 1024), batch), 256, 0, st>>>(
+        m, seed, sweep, trial0, nullptr, qam, mp->shared_pilots, gauss, psym);
+    channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, channel_lds_bytes(m), st>>>(m, gains, u_r, u_t, Hmat);
+    JSTSP_HIP(hipGetLastError());
+    *out = Operands{Hmat, psym, gauss ? 0.70710678f : 1.f};
+    return 0;
+}
 
 }  // namespace

@@ -14,11 +14,11 @@ from __future__ import annotations
 
 import torch
 
-from .system_model import SweepParams, TrainingParams, ase_trials, build_trials, build_trials_training
+from .system_model import SweepParams, TrainingParams, ase_trials, build_trials, build_trials_training, rank_trials
 
 __all__ = ["partition", "run_sweep", "run_points", "sweep_points", "run_approx_sweep", "driver", "run_driver",
            "admmiters_points", "run_convergence_curves", "zy_points", "run_zy", "capacity_points", "capacity_designs",
-           "power_model", "run_capacity"]
+           "power_model", "run_capacity", "rank_points", "run_rank"]
 
 
 def partition(n_items, world, rank):
@@ -533,3 +533,38 @@ def run_capacity(points, n_trials, *, batch=4096, seed=20190913, sweep0=0, devic
     mean = m[:, :4]
     var = np.maximum(m[:, 4:] - mean * mean, 0.0) * (n_trials / max(n_trials - 1, 1))
     return mean, np.sqrt(var / n_trials)
+
+
+# (Nr, clusters, rays) of the six panels of plot_rankR.m (:9-19, :70-80, :128-138, :189-199, :251-261, :313-323)
+RANK_PANELS = {1: (32, 2, 3), 2: (64, 2, 3), 3: (128, 2, 3), 4: (32, 3, 12), 5: (64, 3, 12), 6: (128, 3, 12)}
+
+
+def rank_points(panel):
+    """The three points ``L = 1, 4, 8`` of one panel of plot_rankR.m: Nt = 4, Mr_e = 32, Mr = 4, Gr = Nr, 4-QAM pilots; the
+    frame is T = 50 itself (the script passes T to proposed_hbf).  ``min(Nr, Mr_e) = 32`` values are kept per curve."""
+    Nr, clusters, rays = RANK_PANELS[panel]
+    return [SweepParams(Nt=4, Nr=Nr, L=L, T=50, Mr=4, Mr_e=32, clusters=clusters, rays=rays, T_prop=50) for L in (1, 4, 8)]
+
+
+def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, sweep0=0, device=None, dist=None):
+    """plot_rankR.m:24-50 on the HIP path: per point the mean over ``n_trials`` realisations of the first ``n_keep``
+    singular values (default ``min(Nr, Mr_e, T_prop)`` of the first point) of the noise-free receive signal (point i is
+    sweep index ``sweep0 + i``), sharded over the ranks of ``dist`` with one all-reduce of the sums.
+
+    The reference plots ONE realisation per curve: its ``mean(eig_dist, 3)`` (:52) acts on a 2-D array and does nothing.  So
+    ``n_trials`` defaults to 1; larger values give the averaged curve, which the script's author presumably meant.
+
+    Returns float64 numpy ``(spectrum, marker)``: (len(points), n_keep) mean singular values, and per point the rank bound
+    ``min(Np, L*Nt)`` whose successor index the script marks with a vertical line (:61-62)."""
+    import numpy as np
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if n_keep is None:
+        n_keep = min(points[0].Nr, points[0].Mr_e, points[0].T_prop)
+
+    def build(p, trials, seed_, pt, device_, _):
+        return rank_trials(p, trials.start, len(trials), seed=seed_, sweep_idx=sweep0 + pt, n_keep=n_keep, device=device_)
+
+    mean = _generic_sharded(points, n_trials, n_keep, lambda sv, p: sv, batch=batch, seed=seed, device=device, dist=dist,
+                            builder=build).numpy()
+    return mean, np.array([min(p.clusters * p.rays, p.L * p.Nt) for p in points])

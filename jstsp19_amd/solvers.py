@@ -28,7 +28,7 @@ from ._lib import DEVICE, HOST, JstspError, check
 
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
            "sparse_admm", "vamp", "vamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
-           "empty_colmajor", "beamformer", "ase"]
+           "empty_colmajor", "beamformer", "ase", "singular_values"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -71,7 +71,7 @@ class _Arg:
                 raise ValueError("%s: expected dtype %s, got %s" % (name, want, x.dtype))
             x3 = x if x.ndim == 3 else x.unsqueeze(0)
             b, R, Cc = x3.shape
-            ok = x3.stride(1) == 1 and (x3.stride(2) == R or Cc == 1) and (x3.stride(0) == R * Cc or b == 1)
+            ok = (x3.stride(1) == 1 or R == 1) and (x3.stride(2) == R or Cc == 1) and (x3.stride(0) == R * Cc or b == 1)
             if not ok:
                 raise ValueError("%s: device tensors must be column-major per problem "
                                  "(use jstsp19_amd.colmajor); strides %s" % (name, x3.stride()))
@@ -682,4 +682,28 @@ def ase(Y, W, scale, Mr=None, cols=None, *, ctx=None):
         optr = out.ctypes.data
     fn, name = (c._lib.jstsp_ase_c64, "jstsp_ase_c64") if f64 else (c._lib.jstsp_ase_c32, "jstsp_ase_c32")
     check(fn(c.handle, a_Y.R, a_Y.C, a_W.C, int(Mr), batch, a_Y.ptr, a_W.ptr, cptr, float(scale), optr, mem), name)
+    return out if a_Y.batched else out[0]
+
+
+def singular_values(Y, *, ctx=None):
+    """``svd(Y)`` without the vectors (plot_rankR.m:49) — the singular values of ``Y``: (rows, cols) or (batch, rows, cols),
+    numpy or a column-major torch CUDA tensor, complex64 (``jstsp_singular_values_c32``) or complex128 (``_c64``).  float64
+    one-sided Jacobi on the matrix itself, not on a Gram matrix, so values down to ``eps * sigma_1`` are resolved (what a
+    numerical rank is read from).  Returns float64 (batch, min(rows, cols)) (one row less for 2-D ``Y``), descending, where
+    ``Y`` lives; min(rows, cols) <= 64 and rows * cols <= 8192, else ``JstspError`` (code -3); a non-finite entry gives NaN for
+    its own matrix."""
+    f64 = _is_c128(Y)
+    a_Y = _Arg(Y, np.complex128 if f64 else np.complex64, "Y")
+    c, mem, dev = _ctx_for([a_Y], ctx)
+    n = min(a_Y.R, a_Y.C)
+    if mem == DEVICE:
+        import torch
+        out = torch.empty((a_Y.batch, n), dtype=torch.float64, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty((a_Y.batch, n), dtype=np.float64)
+        optr = out.ctypes.data
+    fn, name = (c._lib.jstsp_singular_values_c64, "jstsp_singular_values_c64") if f64 else \
+        (c._lib.jstsp_singular_values_c32, "jstsp_singular_values_c32")
+    check(fn(c.handle, a_Y.R, a_Y.C, a_Y.batch, a_Y.ptr, optr, mem), name)
     return out if a_Y.batched else out[0]

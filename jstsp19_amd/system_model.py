@@ -21,7 +21,7 @@ import math
 
 import torch
 
-__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training", "ase_trials"]
+__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training", "ase_trials", "rank_trials"]
 
 
 class SweepParams:
@@ -206,3 +206,29 @@ def ase_trials(p: SweepParams, designs, trial0, batch, *, seed=20190913, sweep_i
                                      _lib.DEVICE)
     _lib.check(rc, "jstsp_ase_trials_c32")
     return (out, cols[:, :n_sel]) if want_cols else out
+
+
+def rank_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, n_keep=None, device=None, ctx=None,
+                shared_pilots=False, pilots="qam4"):
+    """plot_rankR.m:24-50 for trials [trial0, trial0 + batch) on the HIP path (``jstsp_rank_trials_c32``, csrc/svdvals.hip):
+    the first ``n_keep`` singular values (default ``min(Nr, Mr_e, T_prop)``; the script keeps ``min(Nr, Mr_e)``) of the
+    noise-free ``Y = sum_l H_l Psi_bar_l`` (Nr x ``p.T_prop``) of one realisation, by float64 one-sided Jacobi on ``Y`` itself.
+    Trial t has the channel and pilots ``build_trials(p, ...)`` returns for t with the same seed, sweep index,
+    ``shared_pilots`` and ``pilots``.  Returns float64 (batch, n_keep) on the device, descending per trial."""
+    import ctypes as C
+    from . import _lib
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    c = ctx if ctx is not None else _lib.default_context(device.index or 0)
+    c.use_torch_stream()
+    if n_keep is None:
+        n_keep = min(p.Nr, p.Mr_e, p.T_prop)
+    model = _lib.Model(p.Nt, p.Nr, p.L, p.T_prop, p.Mr, p.Mr_e, p.Gr, p.Gt, p.clusters, p.rays, 0, 1 if shared_pilots else 0,
+                       p.noise_var, _lib.BF_ZC, _lib.RHO_MIN6, 1.0,
+                       _lib.PILOTS_GAUSS if pilots == "gauss" else _lib.PILOTS_QAM4)
+    out = torch.empty((batch, int(n_keep)), dtype=torch.float64, device=device)
+    rc = c._lib.jstsp_rank_trials_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0), int(batch),
+                                      int(n_keep), out.data_ptr(), _lib.DEVICE)
+    _lib.check(rc, "jstsp_rank_trials_c32")
+    return out
