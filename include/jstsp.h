@@ -327,6 +327,50 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
                        long long strideB, const jstsp_c32 *y, int m,
                        jstsp_c32 *x_hat, int32_t *index_out, int memspace);
 
+/* CoSaMP — the seventh estimator of the timing figure:  s_cosamp = CoSaMP(Phi, y, numOfnz)   plot_time_comparisions.m:96
+ * The 3-argument function the driver calls is not vendored, so this is the published algorithm (Needell & Tropp, "CoSaMP:
+ * Iterative signal recovery from incomplete and inaccurate samples", Algorithm 1); MATLAB parity is unpinned.
+ * One problem: dictionary Phi (measures x size_d), data u, sparsity K, iters >= 1, tol >= 0.
+ *     a = 0;  kept = {};  v = u
+ *     for it = 1 .. iters
+ *         c     = Phi' * v
+ *         Omega = the min(2K, size_d) indices of largest |c|^2        (equal values: the smaller index first)
+ *         T     = sort(Omega U kept)                                  (|T| <= 3K)
+ *         b     = argmin_b || Phi(:,T) b - u ||_2
+ *         kept  = the K positions of T with largest |b|^2             (equal values: the smaller index first)
+ *         a     = 0;  a(kept) = b(kept)                               (pruned, not re-solved)
+ *         v     = u - Phi a
+ *         if ||v||_2 <= tol * ||u||_2: stop this problem              (tol = 0: never)
+ * `kept` is the index set that was kept, whether or not a kept coefficient is exactly zero.  u = 0 returns a = 0 after zero
+ * iterations (resid_out 0, support_out all 0).  JSTSP_E_ARG unless 1 <= K, 2K <= size_d and 3K <= measures (the least
+ * squares is then never under-determined), iters >= 1 and tol >= 0.
+ * Arithmetic: the whole iteration - c, the least squares, |.|^2, the norms and every selection, prune and stop decision -
+ * is float64 on the device for BOTH element types (products of two fp32 values are exact in float64, so a _c32 call is a
+ * float64 evaluation on exactly its inputs; the _c64 entries do not narrow).  x_hat is rounded once to fp32 for _c32.
+ * Form (csrc/cosamp.hip): coefficient domain.  c0 = Phi' u and G = Phi' Phi are formed once; c = c0 - G a; b solves the
+ * gathered normal equations G(T,T) b = c0(T) by Cholesky with one step of refinement; ||v||^2 = ||u||^2 - 2 Re(a' c0) + a' G a
+ * (so a relative residual below about 1e-7 is reported as rounding leaves it, possibly 0).  The dense entry forms G
+ * (size_d <= 4096); the Kronecker entry never does: an entry of G is one entry of Af' Af times one of conj(Bf Bf').
+ * JSTSP_E_UNSUPPORTED: K > 256, size_d > 65536, a dense size_d > 4096, a float64 workspace above 24 GiB.
+ * Rank: when a Cholesky pivot of G(T,T) is at or below 1e-12 times its largest diagonal entry (Phi(:,T) numerically rank
+ * deficient, for instance a repeated column: both copies tie and enter T together), that problem stops, keeps the iterate
+ * it had before this iteration and reports status 1; the other problems are unaffected and the call returns JSTSP_OK.
+ * A, u as in jstsp_omp_c32.  x_hat: size_d x batch.  support_out: K x batch int32, 1-based, ascending.  iters_out: int32
+ * per problem, iterations completed.  resid_out: double per problem, ||v|| / ||u|| at return.  status_out: int32 per
+ * problem, 0 or 1.  The last four may each be NULL.  One launch per step for the whole batch; no flag is read back per
+ * iteration; a repeated call is bit-identical and a problem's result does not depend on the batch around it. */
+int jstsp_cosamp_c32(jstsp_ctx *ctx, int measures, int size_d, int batch,
+                     const jstsp_c32 *A, long long strideA, const jstsp_c32 *u, int K, int iters, double tol,
+                     jstsp_c32 *x_hat, int32_t *support_out, int32_t *iters_out, double *resid_out,
+                     int32_t *status_out, int memspace);
+/* CoSaMP on Phi = kron(Bf.', Af) given by its factors, conventions of jstsp_omp_kron_c32 (atoms indexed g + Gr*h).  The
+ * driver's dictionary is of this kind: Phi = kron((B*B').', A), y = vec(Y*B')  (plot_time_comparisions.m:74-75). */
+int jstsp_cosamp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                          const jstsp_c32 *Af, long long strideA, const jstsp_c32 *Bf, long long strideB,
+                          const jstsp_c32 *y, int K, int iters, double tol,
+                          jstsp_c32 *x_hat, int32_t *support_out, int32_t *iters_out, double *resid_out,
+                          int32_t *status_out, int memspace);
+
 /* Joint (MMV) OMP — the drivers' "OMP with MMV" baseline and the second stage of their TSSR recipe
  *   spx.pursuit.joint.OrthogonalMatchingPursuit(A, K).solve(Y)  ->  .Z      plot_errorVSsnr.m:116-117, :158-162
  * sparse-plex is not vendored and not version-pinned (README.md:9): this is the published simultaneous OMP
@@ -613,6 +657,16 @@ int jstsp_vamp_kron_c64(jstsp_ctx *ctx, int Na, int Gr, int G2, int batch, const
                         double sigma, double L, int nit, jstsp_c64 *X_out, int memspace);
 int jstsp_nmse_spectral_c64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S,
                             const jstsp_c64 *Zbar, double *nmse, int memspace);
+/* CoSaMP (plot_time_comparisions.m:96) on doubles: like the two VAMP entries these do not narrow (see jstsp_cosamp_c32) */
+int jstsp_cosamp_c64(jstsp_ctx *ctx, int measures, int size_d, int batch,
+                     const jstsp_c64 *A, long long strideA, const jstsp_c64 *u, int K, int iters, double tol,
+                     jstsp_c64 *x_hat, int32_t *support_out, int32_t *iters_out, double *resid_out,
+                     int32_t *status_out, int memspace);
+int jstsp_cosamp_kron_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                          const jstsp_c64 *Af, long long strideA, const jstsp_c64 *Bf, long long strideB,
+                          const jstsp_c64 *y, int K, int iters, double tol,
+                          jstsp_c64 *x_hat, int32_t *support_out, int32_t *iters_out, double *resid_out,
+                          int32_t *status_out, int memspace);
 int jstsp_rate_c64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar,
                    double noise_var, double *rate, int memspace);
 

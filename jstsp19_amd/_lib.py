@@ -76,6 +76,10 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_int]),
     "jstsp_omp_kron_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_ll,
                                    c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "jstsp_cosamp_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_int, c_int, C.c_double, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "jstsp_cosamp_kron_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p,
+                                      c_int, c_int, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "jstsp_mmv_omp_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p, c_int]),
     "jstsp_rate_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, C.c_double, c_void_p, c_int]),
@@ -108,7 +112,7 @@ SIGNATURES = {
 
 
 for _n in ("correlate", "synthesize", "proposed_algorithm", "svt", "omp", "sparse_admm", "mc_svt", "mc_admm", "vamp", "ls", "pinv",
-           "mmv_omp", "vamp_kron", "nmse_spectral", "rate", "beamformer", "ase", "singular_values"):
+           "mmv_omp", "vamp_kron", "nmse_spectral", "rate", "beamformer", "ase", "singular_values", "cosamp", "cosamp_kron"):
     # the double-complex forms take the same argument lists (pointers are void* here)
     SIGNATURES["jstsp_%s_c64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 

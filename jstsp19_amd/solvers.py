@@ -27,7 +27,7 @@ from . import _lib
 from ._lib import DEVICE, HOST, JstspError, check
 
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
-           "sparse_admm", "vamp", "vamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
+           "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
            "empty_colmajor", "beamformer", "ase", "singular_values"]
 
 
@@ -521,6 +521,66 @@ def omp_kron(Af, Bf, y, m, *, ctx=None):
                                     a_B.ptr, _shared_stride(a_B, G2 * M, batch, "Bf"), a_y.ptr, int(m), px, pi, mem),
           "jstsp_omp_kron_c32")
     return fx(single)[..., 0], fi(single)[..., 0]
+
+
+def _cosamp_call(kron, mats, y, K, iters, tol, ctx):
+    f64 = all(_is_c128(m) for m in mats) and _is_c128(y)
+    cdt = np.complex128 if f64 else np.complex64
+    a_m = [_Arg(m, cdt, n) for m, n in zip(mats, ("Af", "Bf") if kron else ("Phi",))]
+    tor = _is_torch(y)
+    single = y.ndim == 1
+    y3 = (y.reshape(1, -1, 1) if single else y.reshape(y.shape[0], -1, 1))
+    if tor:
+        y3 = colmajor(y3)
+    a_y = _Arg(y3, cdt, "y")
+    batch, K = a_y.batch, int(K)
+    if kron:
+        N, Gr, G2, M = a_m[0].R, a_m[0].C, a_m[1].R, a_m[1].C
+        meas, size_d = N * M, Gr * G2
+    else:
+        meas, size_d = a_m[0].R, a_m[0].C
+    if a_y.R != meas:
+        raise ValueError("length(y) must equal the number of rows of the dictionary (%d)" % meas)
+    c, mem, dev = _ctx_for(a_m + [a_y], ctx)
+    px, fx = _out(mem == DEVICE, batch, size_d, 1, cdt, dev)
+    ps, fs = _out(mem == DEVICE, batch, max(K, 1), 1, np.int32, dev)
+    pi, fi = _out(mem == DEVICE, batch, 1, 1, np.int32, dev)
+    pr, fr = _out(mem == DEVICE, batch, 1, 1, np.float64, dev)
+    pt, ft = _out(mem == DEVICE, batch, 1, 1, np.int32, dev)
+    name = "jstsp_cosamp%s_%s" % ("_kron" if kron else "", "c64" if f64 else "c32")
+    fn = getattr(c._lib, name)
+    if kron:
+        rc = fn(c.handle, N, M, Gr, G2, batch, a_m[0].ptr, _shared_stride(a_m[0], N * Gr, batch, "Af"), a_m[1].ptr,
+                _shared_stride(a_m[1], G2 * M, batch, "Bf"), a_y.ptr, K, int(iters), float(tol), px, ps, pi, pr, pt, mem)
+    else:
+        rc = fn(c.handle, meas, size_d, batch, a_m[0].ptr, _shared_stride(a_m[0], meas * size_d, batch, "Phi"), a_y.ptr, K,
+                int(iters), float(tol), px, ps, pi, pr, pt, mem)
+    check(rc, name)
+    return fx(single)[..., 0], {"support": fs(single)[..., 0], "iters": fi(single)[..., 0, 0], "resid": fr(single)[..., 0, 0],
+                                "status": ft(single)[..., 0, 0]}
+
+
+def cosamp(Phi, y, K, *, iters=12, tol=1e-6, info=False, ctx=None):
+    """``x = CoSaMP(Phi, y, K)`` (plot_time_comparisions.m:96): the published algorithm (Needell & Tropp, Algorithm 1) as
+    include/jstsp.h states it, float64 on the device whatever the input type.
+
+    ``Phi``: (measures, size_d) or (batch, measures, size_d); ``y``: (measures,) or (batch, measures).  complex128 inputs
+    take ``jstsp_cosamp_c64`` (float64 in and out), complex64 inputs ``jstsp_cosamp_c32`` (x rounded once to fp32).
+    ``iters`` = 12 and ``tol`` = 1e-6 (stop when ||y - Phi x|| <= tol ||y||) are this library's choice: the driver passes
+    neither.  ``iters`` is a definition, not a convergence guarantee: on the driver's own problem (512 x 512, K = 100) the
+    float64 iteration does not settle (relative residual between 0.17 and 0.21 over 12 iterations).
+    ``info=True`` also returns a dict: ``support`` (K, 1-based, ascending), ``iters``, ``resid``, ``status`` (1: the least
+    squares met a rank-deficient Phi(:,T) and the problem kept its previous iterate)."""
+    x, rec = _cosamp_call(False, [Phi], y, K, iters, tol, ctx)
+    return (x, rec) if info else x
+
+
+def cosamp_kron(Af, Bf, y, K, *, iters=12, tol=1e-6, info=False, ctx=None):
+    """``cosamp`` on the Kronecker dictionary ``kron(Bf.', Af)`` given by its factors (never formed), conventions of
+    ``omp_kron``: ``y`` (N*M,) or (batch, N*M) in column-major vec order, atoms indexed g + Gr*h.  The driver's dictionary is
+    ``Af = A``, ``Bf = B*B'``, ``y = vec(Y*B')`` (plot_time_comparisions.m:74-75)."""
+    x, rec = _cosamp_call(True, [Af, Bf], y, K, iters, tol, ctx)
+    return (x, rec) if info else x
 
 
 def _is_c128(x):

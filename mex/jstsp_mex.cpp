@@ -217,6 +217,32 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         }
         if (nlhs >= 3) plhs[2] = mxDuplicateArray(in[1]);
         if (T) plhs[3] = T;
+    } else if (!strcmp(fn, "CoSaMP")) {
+        // [x, support, iters, resid, status] = CoSaMP(Phi, y, K [, iters, tol])     plot_time_comparisions.m:96 (three inputs, one output)
+        check_nargs(fn, nrhs, 3, 5, nlhs, 5);
+        const Dims da = dims_of(in[0]), dv = dims_of(in[1]);
+        const int meas = da.r, size_d = da.c, batch = dv.c * dv.b;        // y: measures x 1 (x batch columns)
+        if (dv.r != meas) mexErrMsgIdAndTxt("jstsp:shape", "CoSaMP: size(y,1) must equal size(Phi,1)");
+        const int K = (int)mxGetScalar(in[2]);
+        const int iters = nrhs > 4 ? (int)mxGetScalar(in[3]) : 12;        // the library's defaults (include/jstsp.h): the driver passes neither
+        const double tol = nrhs > 5 ? mxGetScalar(in[4]) : 1e-6;
+        if (K < 1 || 2 * (long long)K > size_d || 3 * (long long)K > meas)
+            mexErrMsgIdAndTxt("jstsp:args", "CoSaMP: K must satisfy 1 <= K, 2K <= size(Phi,2) and 3K <= size(Phi,1)");
+        if (iters < 1 || !(tol >= 0)) mexErrMsgIdAndTxt("jstsp:args", "CoSaMP: iters must be >= 1 and tol >= 0");
+        const jstsp_c64 *A = cplx(in[0], fn, "Phi"), *v = cplx(in[1], fn, "y");
+        const long long sA = da.b == 1 ? 0 : dict_stride(da, batch, fn, "Phi");
+        ensure_ctx();
+        plhs[0] = new_complex(size_d, batch, 1);
+        const mwSize ds[2] = {(mwSize)K, (mwSize)batch}, d1[2] = {1, (mwSize)batch};
+        mxArray *sup = mxCreateNumericArray(2, ds, mxINT32_CLASS, mxREAL), *it = mxCreateNumericArray(2, d1, mxINT32_CLASS, mxREAL);
+        mxArray *st = mxCreateNumericArray(2, d1, mxINT32_CLASS, mxREAL), *rs = new_real(1, batch, 1);
+        const int rc = jstsp_cosamp_c64(g_ctx, meas, size_d, batch, A, sA, v, K, iters, tol, c64(plhs[0]), (int32_t *)mxGetData(sup),
+                                        (int32_t *)mxGetData(it), mxGetDoubles(rs), (int32_t *)mxGetData(st), JSTSP_HOST);
+        if (rc) fail("jstsp_cosamp_c64", rc);
+        if (nlhs >= 2) plhs[1] = sup;
+        if (nlhs >= 3) plhs[2] = it;
+        if (nlhs >= 4) plhs[3] = rs;
+        if (nlhs >= 5) plhs[4] = st;
     } else if (!strcmp(fn, "sparse_admm")) {
         // [S, convergence_error] = sparse_admm(Htrue, OH, Dr, Dt, Imax)     benchmark_algorithms/sparse_admm.m:1
         check_nargs(fn, nrhs, 5, 5, nlhs, 2);
