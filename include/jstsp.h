@@ -670,6 +670,50 @@ int jstsp_cosamp_kron_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batc
 int jstsp_rate_c64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar,
                    double noise_var, double *rate, int memspace);
 
+/* ---- proposed_algorithm in float64 -----------------------------------------------------------------
+ * proposed_algorithm.m:1-73 / proposed_algorithm_angles.m:1-85 ('approximate') evaluated in FLOAT64 on the device
+ * (csrc/proposed64.hip, csrc/zgemm64.hip): storage, products, reductions, eigen-decompositions, thresholds and every scalar
+ * (1/rho, rho/(rho+1), 1/(Omega+2 rho), tau/rho, alpha) are doubles; nothing is narrowed anywhere - unlike
+ * jstsp_proposed_algorithm_c64, which takes the same arrays and narrows them to the fp32 solver.  This is the library's reference
+ * path: what MATLAB would have returned to more than six digits, and the float64 side of a parity fixture at device speed
+ * (tools/float64_reference.py).  Arguments, layouts, NULL-able outputs (Y_out, ce_out, indx_S), both memspaces and the error
+ * conventions are those of jstsp_proposed_algorithm_c64 / jstsp_svt_c64 / jstsp_correlate_c64 / jstsp_synthesize_c64.
+ *  - products: a batched complex float64 GEMM on v_mfma_f64_16x16x4_f64, four real accumulations per complex product (no
+ *    3-multiplication form), split along k in a fixed order for the small Grams; no atomics - a repeated call returns the same
+ *    bits and a trial's result does not depend on the batch around it.
+ *  - svt: Y = U diag(max(0, 1 - tau/sigma)) U^H Z through the Hermitian eigen-decomposition of the Gram on the smaller side,
+ *    n = min(N, M), sigma = sqrt(lambda).  Guard (that of the float64 host port the committed fixtures were solved with): a
+ *    non-positive eigenvalue is a singular value at rounding level and is dropped; the output is all zeros exactly when NO
+ *    eigenvalue is positive (the zero argument of iteration 1, svt.m:8-12).
+ *  - n <= 64: two-sided cyclic Jacobi in LDS, convergence decided on the device (a sweep that rotates nothing, at most 30): no
+ *    device-to-host read inside the iteration loop.  64 < n <= 512: the global-memory Jacobi of csrc/vamp64.hip, which reads one
+ *    norm per sweep on the host - such a call synchronises the context's stream in every iteration.  n > 512:
+ *    JSTSP_E_UNSUPPORTED.  Every call synchronises the stream once at entry (the per-trial scalars are staged from the caller's
+ *    host arrays) and a JSTSP_HOST call at exit.
+ *  - convergence_error(i, 1:2) from lambda_max of the n x n Grams of V1, V2, X (the same Jacobi); skipped when ce_out is NULL.
+ *  - type: JSTSP_TYPE_APPROXIMATE only; JSTSP_TYPE_STD returns JSTSP_E_UNSUPPORTED (use jstsp_proposed_algorithm_c64).
+ *  - workspace: about 72 MiB per trial at BASELINE configs[1] with per-trial B; above 24 GiB the call returns
+ *    JSTSP_E_UNSUPPORTED with the largest batch that fits in the message (the Python wrappers chunk the batch).
+ * Asserted (tests/test_gpu_f64_gemm.py, test_gpu_f64_proposed.py, test_gpu_f64_fullsize.py): the two kernel-level entries
+ * entrywise within 8 (k1 + k2 + 8) 2^-53 (|A| |S| |B|) of numpy complex128; S and Y within 1e-10 of max|ref|, convergence_error
+ * within 1e-8, NMSE within 1e-11 of oracle/solvers.py and the committed goldens; |dNMSE| <= 1e-9 per trial against the float64
+ * host port at BASELINE configs[1] (measured values: DESIGN.md section 6). */
+int jstsp_correlate_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                        const jstsp_c64 *K, const jstsp_c64 *A, long long strideA,
+                        const jstsp_c64 *B, long long strideB, jstsp_c64 *out, int memspace);      /* A' K B' */
+int jstsp_synthesize_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                         const jstsp_c64 *S, const jstsp_c64 *A, long long strideA,
+                         const jstsp_c64 *B, long long strideB, jstsp_c64 *out, int memspace);     /* A S B */
+int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                                 const jstsp_c64 *subY, const double *Omega,
+                                 const jstsp_c64 *A, long long strideA,
+                                 const jstsp_c64 *B, long long strideB,
+                                 int Imax, const double *tau_Y, const double *tau_S,
+                                 const double *rho, int type, const int32_t *indx_S,
+                                 jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, int memspace);
+int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y,
+                  const double *tau, jstsp_c64 *X, int memspace);
+
 /* Per-kernel timing of the last proposed_algorithm call made with profiling enabled:
  * jstsp_set_profiling(ctx, 1) brackets every launch of the dominant kernel with HIP
  * events on the context's stream; jstsp_get_profile() returns launches and total ms. */

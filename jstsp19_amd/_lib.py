@@ -117,6 +117,11 @@ for _n in ("correlate", "synthesize", "proposed_algorithm", "svt", "omp", "spars
     SIGNATURES["jstsp_%s_c64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 
 
+for _n in ("correlate", "synthesize", "proposed_algorithm", "svt"):
+    # the float64 solver (csrc/proposed64.hip, csrc/zgemm64.hip): argument lists of the _c64 namesakes
+    SIGNATURES["jstsp_%s_f64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
+
+
 class JstspError(RuntimeError):
     """A failed C-ABI call; ``code`` is its status (< 0: JSTSP_E_*, > 0: hipError_t), None when raised on the Python side."""
 

@@ -17,6 +17,7 @@
 // The structure is that of vamp.hip: the LMMSE stage in complex arithmetic on the Kronecker factors, Phi = kron(Gb.', Af) never formed
 // (a dense dictionary is the case G2 = 1, Gb = 1); both branches M <= N (:402-406) and M > N (:407-411).
 #include "vamp_kernels.h"
+#include "zgemm64.h"
 #include <algorithm>
 #include <vector>
 
@@ -355,6 +356,14 @@ const double2 *stage64(Scratch &sc, const jstsp_c64 *src, size_t n, int memspace
 }
 
 }  // namespace
+
+// the Jacobi above for callers outside this file (proposed64.hip, orders above what its in-LDS kernel holds)
+int eig64_global(hipStream_t st, int n, int nmat, const double2 *G, long long sG, double2 *U, double *lam)
+{
+    Scratch sc(st);
+    return eig64(st, sc, n, nmat, G, sG, U, lam);
+}
+
 }  // namespace jstsp
 
 using namespace jstsp;

@@ -28,7 +28,8 @@ from ._lib import DEVICE, HOST, JstspError, check
 
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
            "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
-           "empty_colmajor", "beamformer", "ase", "singular_values"]
+           "empty_colmajor", "beamformer", "ase", "singular_values",
+           "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -64,7 +65,8 @@ class _Arg:
             raise ValueError("%s must be 2-D or 3-D (batch first), got shape %s" % (name, tuple(x.shape)))
         if self.torch:
             import torch
-            want = {np.complex64: torch.complex64, np.complex128: torch.complex128, np.float32: torch.float32, np.int32: torch.int32}[np_dtype]
+            want = {np.complex64: torch.complex64, np.complex128: torch.complex128, np.float32: torch.float32, np.float64: torch.float64,
+                    np.int32: torch.int32}[np_dtype]
             if not x.is_cuda:
                 raise ValueError("%s: torch tensors must live on the GPU (numpy arrays use the host path)" % name)
             if x.dtype != want:
@@ -767,3 +769,119 @@ def singular_values(Y, *, ctx=None):
         (c._lib.jstsp_singular_values_c32, "jstsp_singular_values_c32")
     check(fn(c.handle, a_Y.R, a_Y.C, a_Y.batch, a_Y.ptr, optr, mem), name)
     return out if a_Y.batched else out[0]
+
+
+# ----------------------------------------------------------------------------- float64 solver
+_F64_CHUNK_BYTES = 20 << 30        # the library refuses a float64 workspace above 24 GiB (include/jstsp.h): stay under it
+
+
+def _wide(x, real=False):
+    """complex64 / float32 (or any real / complex numpy dtype) -> complex128 / float64, exactly; layout kept."""
+    if x is None:
+        return None
+    if _is_torch(x):
+        import torch
+        return x.to(torch.float64 if real else torch.complex128)
+    return np.asarray(x, dtype=np.float64 if real else np.complex128)
+
+
+def _off(ptr, elems, size):
+    return None if ptr is None else ptr + int(elems) * size
+
+
+def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None,
+                           want_ce=True, ctx=None):
+    """:func:`proposed_algorithm` evaluated in float64 on the device (include/jstsp.h: jstsp_proposed_algorithm_f64) -
+    nothing is narrowed.  Same arguments; complex64 / float32 inputs are widened exactly, the outputs are complex128
+    (numpy in -> numpy out, torch CUDA tensors in -> torch CUDA tensors out).  ``'approximate'`` only.  A batch whose
+    float64 workspace would exceed the library's limit is solved in chunks."""
+    a_sub = _Arg(_wide(subY), np.complex128, "subY")
+    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
+    a_A = _Arg(_wide(A), np.complex128, "A")
+    a_B = _Arg(_wide(B), np.complex128, "B")
+    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
+    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
+    Gr, G2 = a_A.C, a_B.R
+    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
+        raise ValueError("Omega must have the shape of subY")
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+    if type not in ("approximate", "std"):
+        raise ValueError("type must be 'approximate' or 'std'")
+    if indx_S is not None:
+        if _is_torch(indx_S):
+            import torch
+            ix2 = indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous()
+        else:
+            ix2 = np.asarray(indx_S).reshape(batch, Gr * G2, 1).astype(np.int32)
+        a_ix = _Arg(ix2, np.int32, "indx_S")
+    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
+    sA = _shared_stride(a_A, N * Gr, batch, "A")
+    sB = _shared_stride(a_B, G2 * M, batch, "B")
+    tY, _ = _scalars(tau_Y, batch, "tau_Y")
+    tS, _ = _scalars(tau_S, batch, "tau_S")
+    rh, _ = _scalars(rho, batch, "rho")
+    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
+    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
+    pce, fce = _out(mem == DEVICE, batch, int(Imax), 3, np.float64, dev) if want_ce else (None, None)
+    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
+    # bytes of float64 state per trial (csrc/proposed64.hip): the N x M and Gr x G2 arrays, the staged copies of a host call
+    n = min(N, M)
+    per = 16 * (8 * N * M + 5 * Gr * G2 + Gr * M + N * G2 + 20 * n * n + (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0))
+    if mem == HOST:
+        per += 16 * (2 * N * M + Gr * G2 + (G2 * M if sB else 0) + (N * Gr if sA else 0)) + 8 * N * M
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    dp = C.POINTER(C.c_double)
+    for t0 in range(0, batch, step):
+        nb = min(step, batch - t0)
+        rc = c._lib.jstsp_proposed_algorithm_f64(
+            c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
+            _off(a_B.ptr, t0 * sB, 16), sB, int(Imax), tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp),
+            tcode, _off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * int(Imax), 8), mem)
+        check(rc, "jstsp_proposed_algorithm_f64")
+    sq = not a_sub.batched
+    return fS(sq), fY(sq), (fce(sq) if want_ce else None)
+
+
+def proposed_algorithm_angles_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type="approximate",
+                                  greedy_nnz=None, *, want_ce=True, ctx=None):
+    """:func:`proposed_algorithm_angles` in float64 on the device (see :func:`proposed_algorithm_f64`)."""
+    return proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type, indx_S=indx_S, want_ce=want_ce, ctx=ctx)
+
+
+def svt_f64(Y, tau, *, ctx=None):
+    """benchmark_algorithms/svt.m:1 in float64 on the device (jstsp_svt_f64); complex128 out."""
+    a_Y = _Arg(_wide(Y), np.complex128, "Y")
+    c, mem, dev = _ctx_for([a_Y], ctx)
+    t, pt = _scalars(tau, a_Y.batch, "tau")
+    p, f = _out(mem == DEVICE, a_Y.batch, a_Y.R, a_Y.C, np.complex128, dev)
+    check(c._lib.jstsp_svt_f64(c.handle, a_Y.R, a_Y.C, a_Y.batch, a_Y.ptr, pt, p, mem), "jstsp_svt_f64")
+    return f(not a_Y.batched)
+
+
+def correlate_f64(K, A, B, *, ctx=None):
+    """``A' * K * B'`` (Gr x G2) in float64 on the f64 matrix pipe (jstsp_correlate_f64); complex128 out."""
+    a_K, a_A, a_B = _Arg(_wide(K), np.complex128, "K"), _Arg(_wide(A), np.complex128, "A"), _Arg(_wide(B), np.complex128, "B")
+    batch, N, M, Gr, G2 = a_K.batch, a_K.R, a_K.C, a_A.C, a_B.R
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("shape mismatch")
+    c, mem, dev = _ctx_for([a_K, a_A, a_B], ctx)
+    p, f = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
+    check(c._lib.jstsp_correlate_f64(c.handle, N, M, Gr, G2, batch, a_K.ptr, a_A.ptr,
+                                     _shared_stride(a_A, N * Gr, batch, "A"), a_B.ptr,
+                                     _shared_stride(a_B, G2 * M, batch, "B"), p, mem), "jstsp_correlate_f64")
+    return f(not a_K.batched)
+
+
+def synthesize_f64(S, A, B, *, ctx=None):
+    """``A * S * B`` (N x M) in float64 on the f64 matrix pipe (jstsp_synthesize_f64); complex128 out."""
+    a_S, a_A, a_B = _Arg(_wide(S), np.complex128, "S"), _Arg(_wide(A), np.complex128, "A"), _Arg(_wide(B), np.complex128, "B")
+    batch, Gr, G2, N, M = a_S.batch, a_S.R, a_S.C, a_A.R, a_B.C
+    if a_A.C != Gr or a_B.R != G2:
+        raise ValueError("shape mismatch")
+    c, mem, dev = _ctx_for([a_S, a_A, a_B], ctx)
+    p, f = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
+    check(c._lib.jstsp_synthesize_f64(c.handle, N, M, Gr, G2, batch, a_S.ptr, a_A.ptr,
+                                      _shared_stride(a_A, N * Gr, batch, "A"), a_B.ptr,
+                                      _shared_stride(a_B, G2 * M, batch, "B"), p, mem), "jstsp_synthesize_f64")
+    return f(not a_S.batched)

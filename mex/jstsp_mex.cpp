@@ -131,7 +131,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     if (mxGetString(prhs[0], fn, sizeof(fn))) mexErrMsgIdAndTxt("jstsp:args", "function name too long");
     const mxArray *const *in = prhs + 1;         // in[0] is the reference function's first argument
 
-    if (!strcmp(fn, "proposed_algorithm")) {
+    const bool f64 = !strcmp(fn, "proposed_algorithm_f64");     // the same argument list, solved in float64 (jstsp_proposed_algorithm_f64)
+    if (f64 || !strcmp(fn, "proposed_algorithm")) {
         // [S, Y, convergence_error] = proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type)
         //   basic_system_functions/proposed_algorithm.m:1; a 10th argument indx_S makes it proposed_algorithm_angles.m:1
         check_nargs(fn, nrhs, 9, 10, nlhs, 3);
@@ -165,10 +166,10 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         plhs[0] = new_complex(Gr, G2, batch);
         mxArray *Y = nlhs >= 2 ? new_complex(N, M, batch) : nullptr;
         mxArray *ce = nlhs >= 3 ? new_real(Imax, 3, batch) : nullptr;          // spectral norms only if requested
-        const int rc = jstsp_proposed_algorithm_c64(g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, Imax, tY, tS, rho, tcode,
-                                                    idx, c64(plhs[0]), Y ? c64(Y) : nullptr, ce ? mxGetDoubles(ce) : nullptr,
-                                                    JSTSP_HOST);
-        if (rc) fail("jstsp_proposed_algorithm_c64", rc);
+        const int rc = (f64 ? jstsp_proposed_algorithm_f64 : jstsp_proposed_algorithm_c64)(
+            g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, Imax, tY, tS, rho, tcode, idx, c64(plhs[0]), Y ? c64(Y) : nullptr,
+            ce ? mxGetDoubles(ce) : nullptr, JSTSP_HOST);
+        if (rc) fail(f64 ? "jstsp_proposed_algorithm_f64" : "jstsp_proposed_algorithm_c64", rc);
         if (Y) plhs[1] = Y;
         if (ce) plhs[2] = ce;
     } else if (!strcmp(fn, "svt")) {
