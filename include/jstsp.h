@@ -714,6 +714,37 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
 int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y,
                   const double *tau, jstsp_c64 *X, int memspace);
 
+/* ---- pinv and the least-squares estimate in float64 ------------------------------------------------
+ * MATLAB's SVD-based pinv (pinv.m) and S_ls = pinv(A)*Y*pinv(B) (plot_errorVSsnr.m:83) computed and returned in FLOAT64
+ * (csrc/pinv64.hip), for factors of any driver size - unlike jstsp_pinv_c64 / jstsp_ls_c64, which store complex fp32 and
+ * leave a factor that does not fit one workgroup's LDS to the fp32 Gram inverse (JSTSP_E_ILLCOND on the drivers' B_hbf).
+ *  - route: one-sided (Hestenes) Jacobi on the columns of W = A (rows >= cols) or A^H in global memory, the rotations
+ *    accumulated in V:  W V = U Sigma,  pinv(W) = V Sigma^-2 (W V)^H, assembled by the f64-MFMA GEMM.  No Gram matrix is formed:
+ *    the error grows like cond * 2^-53, not like its square.
+ *  - drop rule (pinv.m's default tolerance): sigma_k is kept iff sigma_k > max(rows, cols) * eps(sigma_max),
+ *    eps(x) = 2^(floor(log2 x) - 52).
+ *  - P: cols x rows x batch, column-major complex double.  rcond_out: NULL or double[batch], the smallest KEPT sigma over
+ *    sigma_max (0 for the zero matrix); rank_out: NULL or int32[batch], the number of kept singular values.  Both live in
+ *    the call's memspace, like A and P.  jstsp_ls_f64: arguments as jstsp_ls_c64 (a stride is 0 - the factor is shared and
+ *    inverted ONCE for the call - or the size of one factor); rcond_out: NULL or double[2] in the call's memspace, the
+ *    smallest rcond over the A factors and over the B factors of the call.
+ *  - limits: min(rows, cols) <= 512 and max(rows, cols) <= 8192 per matrix / factor, batch <= 65535; otherwise, or when the
+ *    float64 workspace would exceed 24 GiB, JSTSP_E_UNSUPPORTED (the message names the largest batch that fits).
+ *  - an ill-conditioned or rank-deficient matrix is NOT an error: both entries return JSTSP_OK and the caller reads
+ *    rcond_out / rank_out (there is no JSTSP_E_ILLCOND on this path, and jstsp_last_conditioning is not touched).  A NaN or
+ *    Inf in a matrix gives NaN for that matrix's P, rcond NaN and rank 0, and leaves its batch mates alone.
+ *  - every sum is formed in a fixed order and there are no atomics: a repeated call returns the same bits, and a matrix's
+ *    result does not depend on the batch around it.
+ *  - both memspaces.  Like jstsp_vamp_c64 these calls synchronise the context's stream, also with JSTSP_DEVICE: whether a
+ *    matrix of the call is still rotating is read on the host once per sweep.
+ * Asserted (tests/test_gpu_pinv64.py): ||P - P_exact||_2 / ||P_exact||_2 <= 8 max(d_numpy, cond 2^-53) for cond up to 1e10
+ * on shapes from 7 x 13 to 512 x 4096, full rank and rank-deficient (measured values: DESIGN.md section 9d). */
+int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A,
+                   jstsp_c64 *P, double *rcond_out, int32_t *rank_out, int memspace);
+int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *Y,
+                 const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB,
+                 jstsp_c64 *S_out, double *rcond_out, int memspace);
+
 /* Per-kernel timing of the last proposed_algorithm call made with profiling enabled:
  * jstsp_set_profiling(ctx, 1) brackets every launch of the dominant kernel with HIP
  * events on the context's stream; jstsp_get_profile() returns launches and total ms. */

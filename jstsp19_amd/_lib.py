@@ -121,6 +121,11 @@ for _n in ("correlate", "synthesize", "proposed_algorithm", "svt"):
     # the float64 solver (csrc/proposed64.hip, csrc/zgemm64.hip): argument lists of the _c64 namesakes
     SIGNATURES["jstsp_%s_f64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 
+# pinv and least squares in float64 (csrc/pinv64.hip): the _c64 argument lists plus the rcond / rank outputs
+SIGNATURES["jstsp_pinv_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int])
+SIGNATURES["jstsp_ls_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
+                                      c_void_p, c_void_p, c_int])
+
 
 class JstspError(RuntimeError):
     """A failed C-ABI call; ``code`` is its status (< 0: JSTSP_E_*, > 0: hipError_t), None when raised on the Python side."""

@@ -1,0 +1,475 @@
+// jstsp_pinv_f64 / jstsp_ls_f64 - MATLAB's SVD-based `pinv` and the least-squares estimate pinv(A)*Y*pinv(B)
+// (plot_errorVSsnr.m:83) computed AND returned in float64, for dictionary factors of any driver size:
+// min(rows, cols) <= 512, max(rows, cols) <= 8192.  Nothing is narrowed and no Gram matrix is formed, so the error grows
+// like cond * eps64 (the Gram routes of hinv.hip square the condition number).
+//
+// Route: one-sided (Hestenes) Jacobi directly on the columns of W in GLOBAL memory, W = A when
+// rows >= cols and W = A^H otherwise (pinv(A) = pinv(A^H)^H); W is m x n, m >= n.  A round-robin round has n/2 disjoint
+// column pairs; one kernel launch per round, one wave (m <= 512) or one workgroup (m > 512) per pair, the three inner
+// products a = |w_p|^2, b = |w_q|^2, g = w_p^H w_q by wave reductions in a fixed order, consecutive lanes on consecutive
+// 16-byte elements of a column.  The same plane rotation is applied to the columns of V (n x n, starts as I), so that
+//     W V = U Sigma (columns orthogonal)   =>   pinv(W) = V Sigma^-2 (W V)^H,
+// which the f64-MFMA GEMM (zgemm64.hip) assembles.  As in svdvals.hip the operand is first scaled by a power of two to
+// max |entry| in [1/2, 1) (exact), and a column whose norm has fallen to eps |W|_F / sqrt(n) is left alone.  The sweeps of
+// a matrix end when one of them met no pair with |g| > sqrt(m) eps sqrt(a b) (its own flag: a matrix's result does not depend
+// on the batch around it); whether any matrix of the call is still rotating is read on the host once per sweep, so a call
+// synchronises the context's stream.  Drop rule (pinv.m): sigma_k is kept iff sigma_k > max(rows, cols) * eps(sigma_max),
+// eps(x) = 2^(floor(log2 x) - 52) - one place, p64_sigma_kernel.  No atomics anywhere: a repeated call returns the same bits.
+#include "zgemm64.h"
+#include <algorithm>
+
+namespace jstsp {
+
+namespace {
+
+constexpr int PV_MAX_ORDER = 512;        // min(rows, cols): the float64 family's largest order (proposed64.hip: P64_MAX_ORDER)
+constexpr int PV_MAX_LONG = 8192;        // max(rows, cols)
+constexpr int PV_SWEEPS = 40;            // cap (the tested inputs stop after 6 to 12)
+constexpr int PV_WAVE_ROWS = 512;        // columns up to this length: one wave per pair; longer: one workgroup per pair
+constexpr size_t PV_WS_LIMIT = (size_t)24 << 30;
+constexpr double PV_EPS = 2.220446049250313e-16;
+
+struct PvMeta {
+    double sc;          // the power of two the operand was multiplied by
+    double fro2;        // squared Frobenius norm of the scaled operand
+    int bad;            // a non-finite entry: the matrix is not decomposed, its outputs are NaN
+    int done;           // a whole sweep met no significant pair
+    int rot;            // the running sweep met one
+    int pad;
+};
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+// One workgroup per matrix: W = sc * A (rows >= cols) or sc * A^H, V = I, meta.  Sums in a fixed order.
+__global__ __launch_bounds__(1024) void p64_prep_kernel(int rows, int cols, const double2 *A, long long sA, double2 *W, double2 *V, PvMeta *meta)
+{
+    __shared__ double red[16];
+    __shared__ int sbad;
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const bool tr = rows < cols;
+    const int m = tr ? cols : rows, n = tr ? rows : cols;
+    const long long cnt = (long long)rows * cols;
+    const double2 *a = A + (long long)t * sA;
+    double2 *Wt = W + (long long)t * m * n, *Vt = V + (long long)t * n * n;
+    if (tid == 0) sbad = 0;
+    __syncthreads();
+    double amax = 0.0;
+    int bad = 0;
+    for (long long e = tid; e < cnt; e += 1024) {
+        const double2 v = a[e];
+        bad |= !isfinite(v.x) || !isfinite(v.y);
+        amax = fmax(amax, fmax(fabs(v.x), fabs(v.y)));
+    }
+    amax = wave_max(amax);
+    if (lane == 0) red[w] = amax;
+    if (bad) sbad = 1;                                            // (every writer stores the same value)
+    __syncthreads();
+    bad = sbad;
+    amax = 0.0;
+    for (int i = 0; i < 16; ++i) amax = fmax(amax, red[i]);
+    int ex = 0;
+    if (!bad && amax > 0.0) frexp(amax, &ex);
+    ex = max(-1000, min(1000, ex));
+    const double sc = ldexp(1.0, -ex);
+    double f2 = 0.0;
+    for (long long e = tid; e < cnt; e += 1024) {
+        const double2 v = a[e];
+        const double x = v.x * sc, y = v.y * sc;
+        f2 += x * x + y * y;
+        if (!tr) Wt[e] = make_double2(x, y);
+        else {
+            const long long i = e % rows, j = e / rows;           // a(i, j) -> w(j, i) = conj
+            Wt[j + (long long)m * i] = make_double2(x, -y);
+        }
+    }
+    for (long long e = tid; e < (long long)n * n; e += 1024) Vt[e] = make_double2(e % n == e / n ? 1.0 : 0.0, 0.0);
+    f2 = wave_sum(f2);
+    __syncthreads();                                              // every wave has read the maxima
+    if (lane == 0) red[w] = f2;
+    __syncthreads();
+    if (tid == 0) {
+        f2 = 0.0;
+        for (int i = 0; i < 16; ++i) f2 += red[i];
+        PvMeta mt;
+        mt.sc = sc; mt.fro2 = f2; mt.bad = bad; mt.done = 0; mt.rot = 0; mt.pad = 0;
+        meta[t] = mt;
+    }
+}
+
+// One round of the round-robin schedule: pair k of round r rotates columns (p, q) of W and of V.  TPP threads per pair:
+// 64 (four pairs per workgroup, no barrier) or 256 (one pair per workgroup, the four waves' partial sums added in wave order).
+template <int TPP>
+__global__ __launch_bounds__(256) void p64_round_kernel(int m, int n, int r, double2 *W, double2 *V, PvMeta *meta)
+{
+    __shared__ double red[16];
+    const int t = blockIdx.y;
+    PvMeta *mt = meta + t;
+    if (mt->bad || mt->done) return;
+    const int ne = n + (n & 1), half = ne / 2, ring = ne - 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int k = TPP == 64 ? (int)blockIdx.x * 4 + w : (int)blockIdx.x;
+    const int g0 = TPP == 64 ? lane : (int)threadIdx.x;
+    if (k >= half) return;                                        // (TPP == 256: the grid has exactly `half` workgroups)
+    const int u = k == 0 ? ring : (r + k) % ring, v = k == 0 ? r : (r + ring - k) % ring;
+    const int p = min(u, v), q = max(u, v);
+    if (q >= n) return;                                           // the idle slot of an odd n (uniform over the pair's threads)
+    double2 *cp = W + ((long long)t * n + p) * m, *cq = W + ((long long)t * n + q) * m;
+    double a = 0.0, b = 0.0, gr = 0.0, gi = 0.0;
+    for (int i = g0; i < m; i += TPP) {
+        const double2 x = cp[i], y = cq[i];
+        a += x.x * x.x + x.y * x.y;
+        b += y.x * y.x + y.y * y.y;
+        gr += x.x * y.x + x.y * y.y;                              // conj(x) y
+        gi += x.x * y.y - x.y * y.x;
+    }
+    a = wave_sum(a); b = wave_sum(b); gr = wave_sum(gr); gi = wave_sum(gi);
+    if (TPP == 256) {
+        if (lane == 0) { red[w] = a; red[4 + w] = b; red[8 + w] = gr; red[12 + w] = gi; }
+        __syncthreads();
+        a = ((red[0] + red[1]) + red[2]) + red[3];
+        b = ((red[4] + red[5]) + red[6]) + red[7];
+        gr = ((red[8] + red[9]) + red[10]) + red[11];
+        gi = ((red[12] + red[13]) + red[14]) + red[15];
+    }
+    const double floor2 = mt->fro2 * PV_EPS * PV_EPS / (double)n;
+    const double g = hypot(gr, gi), ab = sqrt(a) * sqrt(b);
+    // a column at rounding level stays as it is; a pair that is orthogonal to the last bit needs nothing
+    if (a <= floor2 || b <= floor2 || !(g > 0.25 * PV_EPS * ab)) return;
+    if (g > sqrt((double)m) * PV_EPS * ab && g0 == 0) mt->rot = 1;        // (every writer stores the same value)
+    const double z = (b - a) / (2.0 * g);
+    const double tt = copysign(1.0, z) / (fabs(z) + hypot(1.0, z));
+    const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
+    const double wr = gr / g, wi = gi / g;
+    for (int i = g0; i < m; i += TPP) {
+        const double2 x = cp[i], y = cq[i];
+        const double yr = y.x * wr + y.y * wi, yi = y.y * wr - y.x * wi;  // y conj(w)
+        cp[i] = make_double2(c * x.x - s * yr, c * x.y - s * yi);
+        cq[i] = make_double2(s * x.x + c * yr, s * x.y + c * yi);
+    }
+    double2 *vp = V + ((long long)t * n + p) * n, *vq = V + ((long long)t * n + q) * n;
+    for (int i = g0; i < n; i += TPP) {
+        const double2 x = vp[i], y = vq[i];
+        const double yr = y.x * wr + y.y * wi, yi = y.y * wr - y.x * wi;
+        vp[i] = make_double2(c * x.x - s * yr, c * x.y - s * yi);
+        vq[i] = make_double2(s * x.x + c * yr, s * x.y + c * yi);
+    }
+}
+
+// After a sweep: a matrix whose sweep met no significant pair is finished; *any = 1 while one matrix is not.
+__global__ __launch_bounds__(256) void p64_sweep_end_kernel(int batch, PvMeta *meta, int *any)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= batch) return;
+    PvMeta *mt = meta + t;
+    if (mt->bad || mt->done) return;
+    if (mt->rot) { mt->rot = 0; *any = 1; }                       // (every writer stores the same value)
+    else mt->done = 1;
+}
+
+// One workgroup per matrix: sigma_k = |column k of W V|, the drop rule, rcond, rank, and Vs = V diag(sc / sigma_k^2) with
+// zeros for the dropped components.  LDS: n doubles.
+__global__ __launch_bounds__(256) void p64_sigma_kernel(int rows, int cols, const double2 *W, const double2 *V, double2 *Vs, const PvMeta *meta,
+                                                        double *rcond, int32_t *rank)
+{
+    __shared__ double sig2[PV_MAX_ORDER];
+    __shared__ double stol;
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int m = max(rows, cols), n = min(rows, cols);
+    const PvMeta mt = meta[t];
+    const double2 *Wt = W + (long long)t * m * n, *Vt = V + (long long)t * n * n;
+    double2 *Vst = Vs + (long long)t * n * n;
+    if (mt.bad) {
+        if (tid == 0) {
+            if (rcond) rcond[t] = __builtin_nan("");
+            if (rank) rank[t] = 0;
+        }
+        return;
+    }
+    for (int k = w; k < n; k += 4) {
+        const double2 *c = Wt + (long long)k * m;
+        double a = 0.0;
+        for (int i = lane; i < m; i += 64) a += c[i].x * c[i].x + c[i].y * c[i].y;
+        a = wave_sum(a);
+        if (lane == 0) sig2[k] = a;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double smax2 = 0.0;
+        for (int k = 0; k < n; ++k) smax2 = fmax(smax2, sig2[k]);
+        const double smax = sqrt(smax2);
+        // pinv.m: tol = max(size(A)) * eps(norm(A));  eps(x) = 2^(floor(log2 x) - 52)
+        const double tol = smax > 0.0 ? (double)m * ldexp(1.0, ilogb(smax) - 52) : 0.0;
+        double smin = smax;
+        int kept = 0;
+        for (int k = 0; k < n; ++k) {
+            const double s = sqrt(sig2[k]);
+            if (s > tol) { ++kept; smin = fmin(smin, s); }
+        }
+        stol = tol;
+        if (rcond) rcond[t] = kept ? smin / smax : 0.0;
+        if (rank) rank[t] = kept;
+    }
+    __syncthreads();
+    const double tol = stol;
+    for (int e = tid; e < n * n; e += 256) {
+        const int k = e / n;
+        const double s2 = sig2[k];
+        const double f = sqrt(s2) > tol ? mt.sc / s2 : 0.0;
+        const double2 v = Vt[e];
+        Vst[e] = make_double2(v.x * f, v.y * f);
+    }
+}
+
+// NaN for the matrices that held a non-finite entry
+__global__ __launch_bounds__(256) void p64_nan_kernel(long long cnt, double2 *P, long long sP, const PvMeta *meta)
+{
+    const int t = blockIdx.y;
+    if (!meta[t].bad) return;
+    const double q = __builtin_nan("");
+    double2 *Pt = P + (long long)t * sP;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (long long)gridDim.x * 256) Pt[e] = make_double2(q, q);
+}
+
+// out[0] = the smallest of v[0 .. cnt), NaN when one of them is NaN
+__global__ void p64_min_kernel(int cnt, const double *v, double *out)
+{
+    double r = v[0];
+    for (int i = 1; i < cnt; ++i) r = (r != r || v[i] != v[i]) ? __builtin_nan("") : fmin(r, v[i]);
+    *out = r;
+}
+
+struct Slab64 {
+    hipStream_t st;
+    char *base = nullptr;
+    size_t cap = 0, off = 0;
+    explicit Slab64(hipStream_t s) : st(s) {}
+    ~Slab64() { if (base) (void)hipFreeAsync(base, st); }
+    static size_t rnd(size_t b) { return (b + 255) & ~(size_t)255; }
+    int reserve(size_t bytes, const char *nm)
+    {
+        const hipError_t e = hipMallocAsync((void **)&base, std::max<size_t>(bytes, 256), st);
+        if (e != hipSuccess) { base = nullptr; set_error("%s: hipMallocAsync(%zu) failed: %s", nm, bytes, hipGetErrorString(e)); return JSTSP_E_NOMEM; }
+        cap = bytes;
+        return 0;
+    }
+    template <class T> T *get(size_t n)
+    {
+        const size_t b = rnd(n * sizeof(T));
+        if (off + b > cap) return nullptr;
+        T *p = reinterpret_cast<T *>(base + off);
+        off += b;
+        return p;
+    }
+};
+
+bool pv_shape_ok(int rows, int cols) { return std::min(rows, cols) <= PV_MAX_ORDER && std::max(rows, cols) <= PV_MAX_LONG; }
+
+size_t pv_gemm_ws(int rows, int cols, int count)
+{
+    const int m = std::max(rows, cols), n = std::min(rows, cols);
+    return std::max<size_t>(1, rows >= cols ? zgemm64_ws_elems(n, m, n, count) : zgemm64_ws_elems(m, n, n, count));
+}
+
+// workspace of pinv64_run for `count` matrices (its allocations in the same order)
+size_t pinv64_bytes(int rows, int cols, int count)
+{
+    const size_t m = std::max(rows, cols), n = std::min(rows, cols), z2 = sizeof(double2);
+    return Slab64::rnd(m * n * count * z2) + 2 * Slab64::rnd(n * n * count * z2) + Slab64::rnd(count * sizeof(PvMeta)) + Slab64::rnd(sizeof(int)) +
+           Slab64::rnd(pv_gemm_ws(rows, cols, count) * z2);
+}
+
+// P[t] (cols x rows, contiguous) = pinv(A[t]) (rows x cols, sA elements apart), t < count; rcond / rank: nullptr or device [count].
+// Synchronises the stream once per sweep.
+int pinv64_run(hipStream_t st, Slab64 &s, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond, int32_t *rank,
+               const char *nm)
+{
+    const int m = std::max(rows, cols), n = std::min(rows, cols);
+    const size_t mn = (size_t)m * n, nn = (size_t)n * n;
+    double2 *W = s.get<double2>(mn * count), *V = s.get<double2>(nn * count), *Vs = s.get<double2>(nn * count);
+    PvMeta *meta = s.get<PvMeta>(count);
+    int *any = s.get<int>(1);
+    double2 *ws = s.get<double2>(pv_gemm_ws(rows, cols, count));
+    JSTSP_REQUIRE(W && V && Vs && meta && any && ws, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
+    hipLaunchKernelGGL(p64_prep_kernel, dim3(count), dim3(1024), 0, st, rows, cols, A, sA, W, V, meta);
+    JSTSP_HIP(hipGetLastError());
+    const int ne = n + (n & 1), half = ne / 2, ring = ne - 1;
+    for (int sweep = 0; sweep < PV_SWEEPS && n > 1; ++sweep) {
+        for (int r = 0; r < ring; ++r) {
+            if (m <= PV_WAVE_ROWS) hipLaunchKernelGGL(p64_round_kernel<64>, dim3((half + 3) / 4, count), dim3(256), 0, st, m, n, r, W, V, meta);
+            else hipLaunchKernelGGL(p64_round_kernel<256>, dim3(half, count), dim3(256), 0, st, m, n, r, W, V, meta);
+        }
+        JSTSP_HIP(hipGetLastError());
+        JSTSP_HIP(hipMemsetAsync(any, 0, sizeof(int), st));
+        hipLaunchKernelGGL(p64_sweep_end_kernel, dim3((count + 255) / 256), dim3(256), 0, st, count, meta, any);
+        int h_any = 0;
+        JSTSP_HIP(hipMemcpyAsync(&h_any, any, sizeof(int), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+        if (!h_any) break;
+    }
+    hipLaunchKernelGGL(p64_sigma_kernel, dim3(count), dim3(256), 0, st, rows, cols, W, V, Vs, meta, rcond, rank);
+    JSTSP_HIP(hipGetLastError());
+    const long long smn = (long long)mn, snn = (long long)nn;
+    if (rows >= cols) JSTSP_TRY(zgemm64(st, 'N', 'C', n, m, n, count, Mat64{Vs, snn, n}, Mat64{W, smn, m}, P, smn, n, ws));     // V f (W V)^H
+    else JSTSP_TRY(zgemm64(st, 'N', 'C', m, n, n, count, Mat64{W, smn, m}, Mat64{Vs, snn, n}, P, smn, m, ws));               // its adjoint
+    hipLaunchKernelGGL(p64_nan_kernel, dim3((unsigned)std::min<size_t>((mn + 255) / 256, 1024), count), dim3(256), 0, st, (long long)mn, P, smn, meta);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+int largest_fit(size_t (*bytes)(const int *, int), const int *shape, int batch)
+{
+    int fit = batch;
+    while (fit > 1 && bytes(shape, fit) > PV_WS_LIMIT) fit = fit > 64 ? fit - fit / 16 : fit - 1;
+    return fit;
+}
+
+size_t pinv_call_bytes(const int *sh, int batch)
+{
+    const size_t e = (size_t)sh[0] * sh[1] * batch;
+    size_t b = pinv64_bytes(sh[0], sh[1], batch);
+    if (sh[2]) b += 2 * Slab64::rnd(e * sizeof(double2)) + Slab64::rnd(batch * sizeof(double)) + Slab64::rnd(batch * sizeof(int32_t));
+    return b;
+}
+
+// sh: N, M, Gr, G2, host, strideA != 0, strideB != 0
+size_t ls_call_bytes(const int *sh, int batch)
+{
+    const size_t N = sh[0], M = sh[1], Gr = sh[2], G2 = sh[3], z2 = sizeof(double2);
+    const int nA = sh[5] ? batch : 1, nB = sh[6] ? batch : 1;
+    size_t b = pinv64_bytes(sh[0], sh[2], nA) + pinv64_bytes(sh[3], sh[1], nB);
+    b += Slab64::rnd(N * Gr * nA * z2) + Slab64::rnd(G2 * M * nB * z2);                       // pinv(A), pinv(B)
+    b += Slab64::rnd(Gr * M * batch * z2);                                                    // pinv(A) Y
+    b += Slab64::rnd(std::max<size_t>(1, std::max(zgemm64_ws_elems(sh[2], sh[1], sh[0], batch), zgemm64_ws_elems(sh[2], sh[3], sh[1], batch))) * z2);
+    b += Slab64::rnd(nA * sizeof(double)) + Slab64::rnd(nB * sizeof(double)) + Slab64::rnd(2 * sizeof(double));
+    if (sh[4]) b += Slab64::rnd(N * M * batch * z2) + Slab64::rnd(N * Gr * nA * z2) + Slab64::rnd(G2 * M * nB * z2) + Slab64::rnd(Gr * G2 * batch * z2);
+    return b;
+}
+
+}  // namespace
+}  // namespace jstsp
+
+using namespace jstsp;
+
+extern "C" {
+
+int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A_, jstsp_c64 *P_, double *rcond_out, int32_t *rank_out, int memspace)
+{
+    const char *nm = "pinv (float64)";
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(rows > 0 && cols > 0 && batch > 0, JSTSP_E_SHAPE, "%s: bad shape", nm);
+    JSTSP_REQUIRE(A_ && P_, JSTSP_E_NULL, "%s: NULL argument", nm);
+    JSTSP_REQUIRE(pv_shape_ok(rows, cols) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "%s: %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d and batch <= 65535", nm, rows, cols, batch, PV_MAX_ORDER,
+                  PV_MAX_LONG);
+    const bool host = memspace == JSTSP_HOST;
+    const int sh[3] = {rows, cols, host ? 1 : 0};
+    const size_t need = pinv_call_bytes(sh, batch);
+    if (need > PV_WS_LIMIT) {
+        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nm,
+                  (double)need / (double)((size_t)1 << 30), largest_fit(pinv_call_bytes, sh, batch));
+        return JSTSP_E_UNSUPPORTED;
+    }
+    hipStream_t st = ctx->stream;
+    Slab64 s(st);
+    JSTSP_TRY(s.reserve(need, nm));
+    const size_t e = (size_t)rows * cols * batch;
+    const double2 *A = reinterpret_cast<const double2 *>(A_);
+    double2 *P = reinterpret_cast<double2 *>(P_);
+    double *rc = rcond_out;
+    int32_t *rk = rank_out;
+    if (host) {
+        double2 *a = s.get<double2>(e);
+        P = s.get<double2>(e);
+        rc = s.get<double>(batch);
+        rk = s.get<int32_t>(batch);
+        JSTSP_REQUIRE(a && P && rc && rk, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
+        JSTSP_HIP(hipMemcpyAsync(a, A_, e * sizeof(double2), hipMemcpyHostToDevice, st));
+        A = a;
+    }
+    JSTSP_TRY(pinv64_run(st, s, rows, cols, batch, A, (long long)rows * cols, P, rc, rk, nm));
+    if (host) {
+        JSTSP_HIP(hipMemcpyAsync(P_, P, e * sizeof(double2), hipMemcpyDeviceToHost, st));
+        if (rcond_out) JSTSP_HIP(hipMemcpyAsync(rcond_out, rc, batch * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (rank_out) JSTSP_HIP(hipMemcpyAsync(rank_out, rk, batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *Y_, const jstsp_c64 *A_, long long strideA,
+                 const jstsp_c64 *B_, long long strideB, jstsp_c64 *S_out, double *rcond_out, int memspace)
+{
+    const char *nm = "ls (float64)";
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nm);
+    JSTSP_REQUIRE(Y_ && A_ && B_ && S_out, JSTSP_E_NULL, "%s: NULL argument", nm);
+    JSTSP_REQUIRE((strideA == 0 || strideA == (long long)N * Gr) && (strideB == 0 || strideB == (long long)G2 * M), JSTSP_E_ARG,
+                  "%s: a factor stride is 0 (shared) or the size of one factor", nm);
+    JSTSP_REQUIRE(pv_shape_ok(N, Gr) && pv_shape_ok(G2, M) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "%s: A %d x %d, B %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d per factor and batch <= 65535", nm, N, Gr, G2, M,
+                  batch, PV_MAX_ORDER, PV_MAX_LONG);
+    const bool host = memspace == JSTSP_HOST;
+    const int sh[7] = {N, M, Gr, G2, host ? 1 : 0, strideA ? 1 : 0, strideB ? 1 : 0};
+    const size_t need = ls_call_bytes(sh, batch);
+    if (need > PV_WS_LIMIT) {
+        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nm,
+                  (double)need / (double)((size_t)1 << 30), largest_fit(ls_call_bytes, sh, batch));
+        return JSTSP_E_UNSUPPORTED;
+    }
+    hipStream_t st = ctx->stream;
+    Slab64 s(st);
+    JSTSP_TRY(s.reserve(need, nm));
+    const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
+    const size_t eY = (size_t)N * M * batch, eA = (size_t)N * Gr * nA, eB = (size_t)G2 * M * nB, eS = (size_t)Gr * G2 * batch;
+    const double2 *Y = reinterpret_cast<const double2 *>(Y_), *A = reinterpret_cast<const double2 *>(A_), *B = reinterpret_cast<const double2 *>(B_);
+    double2 *S = reinterpret_cast<double2 *>(S_out);
+    double *rc2 = rcond_out;
+    if (host) {
+        double2 *y = s.get<double2>(eY), *a = s.get<double2>(eA), *b = s.get<double2>(eB);
+        S = s.get<double2>(eS);
+        JSTSP_REQUIRE(y && a && b && S, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
+        JSTSP_HIP(hipMemcpyAsync(y, Y_, eY * sizeof(double2), hipMemcpyHostToDevice, st));
+        JSTSP_HIP(hipMemcpyAsync(a, A_, eA * sizeof(double2), hipMemcpyHostToDevice, st));
+        JSTSP_HIP(hipMemcpyAsync(b, B_, eB * sizeof(double2), hipMemcpyHostToDevice, st));
+        Y = y; A = a; B = b;
+    }
+    double2 *PA = s.get<double2>(eA), *PB = s.get<double2>(eB), *T = s.get<double2>((size_t)Gr * M * batch);
+    double2 *ws = s.get<double2>(std::max<size_t>(1, std::max(zgemm64_ws_elems(Gr, M, N, batch), zgemm64_ws_elems(Gr, G2, M, batch))));
+    double *rcA = s.get<double>(nA), *rcB = s.get<double>(nB), *rcd = s.get<double>(2);
+    JSTSP_REQUIRE(PA && PB && T && ws && rcA && rcB && rcd, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
+    // a shared factor is inverted once for the call
+    JSTSP_TRY(pinv64_run(st, s, N, Gr, nA, A, (long long)N * Gr, PA, rcA, nullptr, nm));
+    JSTSP_TRY(pinv64_run(st, s, G2, M, nB, B, (long long)G2 * M, PB, rcB, nullptr, nm));
+    JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, Mat64{PA, strideA ? (long long)Gr * N : 0, Gr}, Mat64{Y, (long long)N * M, N}, T, (long long)Gr * M, Gr,
+                      ws));
+    JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Mat64{PB, strideB ? (long long)M * G2 : 0, M}, S, (long long)Gr * G2,
+                      Gr, ws));
+    if (rcond_out) {
+        if (host) rc2 = rcd;
+        hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nA, rcA, rc2);
+        hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nB, rcB, rc2 + 1);
+        JSTSP_HIP(hipGetLastError());
+        if (host) JSTSP_HIP(hipMemcpyAsync(rcond_out, rcd, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (host) JSTSP_HIP(hipMemcpyAsync(S_out, S, eS * sizeof(double2), hipMemcpyDeviceToHost, st));
+    JSTSP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // extern "C"

@@ -127,7 +127,7 @@ def _times(A, S, P):
     return J.synthesize(S, _eye(S.shape[-2], S) if A is None else A, P)
 
 
-def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_max_order=128):
+def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_max_order=128, ls_precision="f32"):
     """LS, VAMP and MMV-OMP baselines of plot_errorVSsnr.m:73-121 on the conventional-HBF measurement; with
     ``tssr = (Imax, rho)`` also the commented TSSR recipe (:151,158-162) on the proposed scheme's measurement.
     Every product goes through the library (correlate / synthesize entry points), nothing through torch matmuls.
@@ -135,14 +135,23 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
     LS of a factor too large for the float64 pinv kernel takes the fp32 Gram-inverse route, whose accuracy is
     ``6e-8 * cond(B B')``; the library records the conditioning on the device (``jstsp_last_conditioning``).  Where that
     record says the digits are not there (``lambda_min/lambda_max < 1e-6``, or 0: a truncated or unconverged inverse) the LS
-    column - and the MMV-OMP column when it had to be built from that LS estimate - is NaN instead of a wrong number."""
+    column - and the MMV-OMP column when it had to be built from that LS estimate - is NaN instead of a wrong number.
+
+    ``ls_precision="f64"`` (opt-in; the default "f32" is the behaviour above, unchanged): ``pinv(B)``, ``S_ls`` and
+    ``Y*pinv(B)`` come from the float64 entries (``jstsp_pinv_f64`` / ``jstsp_ls_f64``: SVD-based, no Gram matrix, any
+    factor up to 512 x 8192), the LS column is scored in float64 (``_score_f64``), and the LS and MMV-OMP columns are
+    numbers where the default gives NaN.  The joint OMP itself stays the fp32 kernel (its input is narrowed)."""
     from . import _lib
     from . import solvers as J
+    if ls_precision not in ("f32", "f64"):
+        raise ValueError("ls_precision must be 'f32' or 'f64'")
     zb = J.colmajor(inp["Zbar"].to(torch.complex64))
     ctx = _lib.default_context(inp["Y_hbf"].device.index or 0)
     nan = lambda: torch.full((inp["Y_hbf"].shape[0],), float("nan"), dtype=torch.float64)
     Bh = inp["B_hbf"]
     G2 = Bh.shape[1]
+    if ls_precision == "f64":
+        return _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order)
     try:
         PB = J.pinv(Bh)                                                                  # pinv(B)  :83, :117
     except J.JstspError as e:
@@ -178,6 +187,54 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
             out["tssr"] = _score(St, zb, metric, noise_var)
             out["svt"] = _score(Ssvt, zb, metric, noise_var)                             # :152-153
         except J.JstspError as e:
+            if e.code != _lib.E_UNSUPPORTED:
+                raise
+    return out
+
+
+def _score_f64(S, zb, metric, noise_var):
+    """``_score`` for a float64 estimate: the same two formulas (plot_errorVSsnr.m:138-141, plot_rateVSframelength.m:81)
+    evaluated in float64 on the host - the library's scoring kernels store fp32, which would put back the rounding that the
+    float64 least squares removes.  ``S``, ``zb``: (batch, R, C) tensors; returns a float64 tensor (batch,)."""
+    import numpy as np
+    Sh, zh = S.detach().cpu().numpy().astype(np.complex128), zb.detach().cpu().numpy().astype(np.complex128)
+    out = np.empty(Sh.shape[0], dtype=np.float64)
+    for t in range(Sh.shape[0]):
+        e = (np.linalg.norm(Sh[t] - zh[t], 2) / np.linalg.norm(zh[t], 2)) ** 2
+        if metric == "nmse":
+            out[t] = min(1.0, e) if e == e else e
+        else:
+            nr = zh.shape[1]
+            out[t] = np.log2(np.real(np.linalg.det(np.eye(nr) + zh[t] @ zh[t].conj().T / nr / (noise_var + e))))
+    return torch.from_numpy(out)
+
+
+def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order):
+    """``_hip_baselines`` with the least-squares pieces in float64 (``ls_precision="f64"``)."""
+    from . import solvers as J
+    zb = J.colmajor(inp["Zbar"].to(torch.complex64))
+    Bh, Ah, Yh = inp["B_hbf"], inp["A_hbf"], inp["Y_hbf"]
+    G2 = Bh.shape[1]
+    wide = lambda x: x.to(torch.complex128)
+    PB = J.pinv_f64(wide(Bh))                                                            # pinv(B)  :83, :117
+    S_ls = J.ls_estimate_f64(wide(Yh), wide(Ah), wide(Bh))                               # :83
+    out = {"ls": _score_f64(S_ls, inp["Zbar"], metric, noise_var)}
+    if G2 <= vamp_max_order and Ah.shape[0] <= 128:
+        Gb = _times_h(Bh, Bh)                                                            # (B*B')  :79
+        Ym = _times_h(Yh, Bh)                                                            # Y_hbf*B' :80
+        out["vamp"] = _score(J.vamp_kron(Ym, Ah, Gb, 1.0, numOfnz), zb, metric, noise_var)   # :100
+    eye = J.colmajor(torch.eye(Yh.shape[-2], dtype=torch.complex128, device=Yh.device))
+    Ypb = J.synthesize_f64(wide(Yh), eye, PB).to(torch.complex64)                        # Y_hbf_nr*pinv(B)  :117
+    Z, _, _ = J.mmv_omp(Ah, Ypb, numOfnz)                                                # :116-117
+    out["omp_mmv"] = _score(Z, zb, metric, noise_var)
+    if tssr is not None:
+        try:
+            St, _, Ssvt = J.tssr(inp["subY"], inp["Omega"], inp["A"], inp["B"], tssr[0], inp["tau_Y"].numpy(), tssr[1],
+                                 2 * numOfnz)                                            # :151,:160-161
+            out["tssr"] = _score(St, zb, metric, noise_var)
+            out["svt"] = _score(Ssvt, zb, metric, noise_var)                             # :152-153
+        except J.JstspError as e:
+            from . import _lib
             if e.code != _lib.E_UNSUPPORTED:
                 raise
     return out
@@ -243,7 +300,7 @@ def _merge_cap(p, batch, with_hbf):
 
 def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=None, solve_fn=None, dist=None,
                baselines=False, numOfnz=100, builder=None, metric="nmse", tssr=None, merge=True, vamp_max_order=128,
-               samples=None):
+               samples=None, ls_precision="f32"):
     """Mean capped NMSE per sweep point; columns (proposed_algorithm, proposed_algorithm_angles[, LS, VAMP, MMV-OMP
     [, TSSR]]).  ``metric="rate"``: the rate of plot_rateVSframelength.m:81 instead of the NMSE (HIP solvers only).
     ``tssr=(Imax_svt, rho_svt)`` adds the commented recipes of plot_errorVSsnr.m:151-162 as columns six and seven: TSSR
@@ -259,8 +316,12 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
     the library builder's statistically, not sample by sample).
     ``samples``: a list that receives, per sweep point, a float64 tensor (trials of THIS rank, ncol) of the per-trial values
     before averaging (what plot_errorVSsnr.m:138-141 computes per realisation) - for distributional checks.
+    ``ls_precision="f64"``: the LS column, and the ``Y*pinv(B)`` in front of the MMV-OMP column, from the float64
+    least-squares entries (see ``_hip_baselines``); the default "f32" leaves every column as it was.
     Returns a float64 tensor (len(points), ncol) identical on every rank.
     """
+    if ls_precision not in ("f32", "f64"):
+        raise ValueError("ls_precision must be 'f32' or 'f64'")
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     if device is None:
@@ -304,7 +365,7 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
         e, ea = solve_fn(inp, Imax) if custom else solve_fn(inp, Imax, p.noise_var)
         cols = [torch.as_tensor(e).double().cpu(), torch.as_tensor(ea).double().cpu()]
         if baselines:
-            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order)
+            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order, ls_precision)
             for key in ("ls", "vamp", "omp_mmv", "tssr", "svt")[:ncol - 2]:
                 cols.append(b[key].double().cpu() if key in b else torch.full((total,), float("nan"), dtype=torch.float64))
         o = 0

@@ -29,7 +29,8 @@ from ._lib import DEVICE, HOST, JstspError, check
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
            "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
            "empty_colmajor", "beamformer", "ase", "singular_values",
-           "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64"]
+           "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
+           "pinv_f64", "ls_estimate_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -885,3 +886,50 @@ def synthesize_f64(S, A, B, *, ctx=None):
                                       _shared_stride(a_A, N * Gr, batch, "A"), a_B.ptr,
                                       _shared_stride(a_B, G2 * M, batch, "B"), p, mem), "jstsp_synthesize_f64")
     return f(not a_S.batched)
+
+
+def _vec_out(kind_torch, n, np_dtype, device=None):
+    """A length-n output vector where the call's arrays live: (ptr, array)."""
+    if kind_torch:
+        import torch
+        buf = torch.empty(n, dtype={np.float64: torch.float64, np.int32: torch.int32}[np_dtype], device=device)
+        return buf.data_ptr(), buf
+    buf = np.empty(n, dtype=np_dtype)
+    return buf.ctypes.data, buf
+
+
+def pinv_f64(A, *, info=False, ctx=None):
+    """MATLAB's ``pinv(A)`` computed and returned in float64 on the device (include/jstsp.h: jstsp_pinv_f64): one-sided Jacobi
+    SVD of the matrix itself - no Gram matrix - with ``pinv.m``'s drop rule ``sigma <= max(size(A)) * eps(sigma_max)``.
+    ``A``: (rows, cols) or (batch, rows, cols), numpy or a column-major torch CUDA tensor; complex64 / real inputs are widened
+    exactly; complex128 out, where ``A`` lives.  min(rows, cols) <= 512 and max(rows, cols) <= 8192, else ``JstspError``
+    (code -3).  An ill-conditioned or rank-deficient matrix is not an error: ``info=True`` also returns ``rcond`` (float64,
+    the smallest kept singular value over the largest) and ``rank`` (int32), one entry per matrix.  A non-finite entry gives
+    NaN for its own matrix."""
+    a_A = _Arg(_wide(A), np.complex128, "A")
+    c, mem, dev = _ctx_for([a_A], ctx)
+    p, f = _out(mem == DEVICE, a_A.batch, a_A.C, a_A.R, np.complex128, dev)
+    prc, rc = _vec_out(mem == DEVICE, a_A.batch, np.float64, dev) if info else (None, None)
+    prk, rk = _vec_out(mem == DEVICE, a_A.batch, np.int32, dev) if info else (None, None)
+    check(c._lib.jstsp_pinv_f64(c.handle, a_A.R, a_A.C, a_A.batch, a_A.ptr, p, prc, prk, mem), "jstsp_pinv_f64")
+    P = f(not a_A.batched)
+    if not info:
+        return P
+    return (P, rc, rk) if a_A.batched else (P, rc[0], rk[0])
+
+
+def ls_estimate_f64(Y, A, B, *, info=False, ctx=None):
+    """``pinv(A)*Y*pinv(B)`` (plot_errorVSsnr.m:83) in float64 on the device (jstsp_ls_f64): :func:`pinv_f64` of every
+    factor - a 2-D ``A`` / ``B`` is shared by the batch and inverted once - and two products on the f64 matrix pipe.
+    complex128 out; ``info=True`` also returns ``rcond``: float64 (2,), the smallest over the ``A`` and over the ``B`` factors."""
+    a_Y, a_A, a_B = _Arg(_wide(Y), np.complex128, "Y"), _Arg(_wide(A), np.complex128, "A"), _Arg(_wide(B), np.complex128, "B")
+    batch, N, M, Gr, G2 = a_Y.batch, a_Y.R, a_Y.C, a_A.C, a_B.R
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("shape mismatch")
+    c, mem, dev = _ctx_for([a_Y, a_A, a_B], ctx)
+    p, f = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
+    prc, rc = _vec_out(mem == DEVICE, 2, np.float64, dev) if info else (None, None)
+    check(c._lib.jstsp_ls_f64(c.handle, N, M, Gr, G2, batch, a_Y.ptr, a_A.ptr, _shared_stride(a_A, N * Gr, batch, "A"),
+                              a_B.ptr, _shared_stride(a_B, G2 * M, batch, "B"), p, prc, mem), "jstsp_ls_f64")
+    S = f(not a_Y.batched)
+    return (S, rc) if info else S

@@ -348,6 +348,34 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         plhs[0] = new_complex(d.c, d.r, d.b);
         const int rc = jstsp_pinv_c64(g_ctx, d.r, d.c, d.b, A, c64(plhs[0]), JSTSP_HOST);
         if (rc) fail("jstsp_pinv_c64", rc);
+    } else if (!strcmp(fn, "pinv_f64")) {
+        // [P, rcond, rank] = pinv_f64(A): MATLAB's pinv in float64 for factors up to 512 x 8192 (jstsp_pinv_f64); pages = batch
+        check_nargs(fn, nrhs, 1, 1, nlhs, 3);
+        const Dims d = dims_of(in[0]);
+        const jstsp_c64 *A = cplx(in[0], fn, "A");
+        ensure_ctx();
+        plhs[0] = new_complex(d.c, d.r, d.b);
+        mxArray *rc = nlhs >= 2 ? mxCreateDoubleMatrix(d.b, 1, mxREAL) : nullptr;
+        const mwSize dk[2] = {(mwSize)d.b, 1};
+        mxArray *rk = nlhs >= 3 ? mxCreateNumericArray(2, dk, mxINT32_CLASS, mxREAL) : nullptr;
+        const int rcode = jstsp_pinv_f64(g_ctx, d.r, d.c, d.b, A, c64(plhs[0]), rc ? mxGetDoubles(rc) : nullptr,
+                                         rk ? (int32_t *)mxGetData(rk) : nullptr, JSTSP_HOST);
+        if (rcode) fail("jstsp_pinv_f64", rcode);
+        if (rc) plhs[1] = rc;
+        if (rk) plhs[2] = rk;
+    } else if (!strcmp(fn, "ls_f64")) {
+        // [S_ls, rcond] = ls_f64(Y, A, B): pinv(A)*Y*pinv(B) in float64 (jstsp_ls_f64); rcond = [over the A factors; over the B factors]
+        check_nargs(fn, nrhs, 3, 3, nlhs, 2);
+        const Dims dy = dims_of(in[0]), da = dims_of(in[1]), db = dims_of(in[2]);
+        if (da.r != dy.r || db.c != dy.c) mexErrMsgIdAndTxt("jstsp:shape", "ls_f64: inconsistent dimensions");
+        const jstsp_c64 *Y = cplx(in[0], fn, "Y"), *A = cplx(in[1], fn, "A"), *B = cplx(in[2], fn, "B");
+        const long long sA = dict_stride(da, dy.b, fn, "A"), sB = dict_stride(db, dy.b, fn, "B");
+        ensure_ctx();
+        plhs[0] = new_complex(da.c, db.r, dy.b);
+        mxArray *rc = nlhs >= 2 ? mxCreateDoubleMatrix(2, 1, mxREAL) : nullptr;
+        const int rcode = jstsp_ls_f64(g_ctx, dy.r, dy.c, da.c, db.r, dy.b, Y, A, sA, B, sB, c64(plhs[0]), rc ? mxGetDoubles(rc) : nullptr, JSTSP_HOST);
+        if (rcode) fail("jstsp_ls_f64", rcode);
+        if (rc) plhs[1] = rc;
     } else if (!strcmp(fn, "nmse") || !strcmp(fn, "rate")) {
         // nmse(S, Zbar): min(1, norm(S-Zbar)^2/norm(Zbar)^2)  plot_errorVSsnr.m:138-141 (one value per page)
         // rate(S, Zbar, noise_var): log2(real(det(eye(Nr) + 1/Nr*Zbar*Zbar'/(noise_var + nmse))))  plot_rateVSframelength.m:81

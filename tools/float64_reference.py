@@ -5,7 +5,8 @@ Same trials as parity_tail.py (BASELINE configs[1] shape N=64, M=4096, Gr=64, G2
 configs[3] sweep x `--trials` realisations, `--bench-trials` of the bench workload at 5 dB, `--angles-trials` of
 proposed_algorithm_angles), same options for seed, SNR points, trials and groups, and the same `fixture.npz` layout
 (`<group>/snr_db`, `sweep_idx`, `trial`, `fingerprint`, `nmse_port`, `ce_port`, `seed`), so that
-tests/golden/make_fullsize_port_fixture.py reads its output unchanged.  The host port needs 5-6 core-seconds per trial; this
+tests/golden/make_fullsize_port_fixture.py reads its output unchanged.  `--ls` adds the LS column in float64 per trial
+(`S_ls`, `nmse_ls`: `pinv(A_hbf)*Y_hbf*pinv(B_hbf)` by jstsp_ls_f64).  The host port needs 5-6 core-seconds per trial; this
 needs milliseconds.  It does not replace parity_tail.py (which measures the fp32 path against the host port) and the committed
 fixtures are not regenerated from it.
 
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--seed", type=int, default=20190913)
     ap.add_argument("--chunk", type=int, default=64)
     ap.add_argument("--no-ce", action="store_true", help="skip convergence_error (ce_port is then absent from the fixture)")
+    ap.add_argument("--ls", action="store_true", help="also the float64 least-squares estimate pinv(A_hbf)*Y_hbf*pinv(B_hbf) per trial "
+                    "(jstsp_ls_f64): S_ls (complex128, Gr x G2 per trial) and nmse_ls in the fixture")
     ap.add_argument("--host-port", type=int, default=0, help="also solve this many trials with oracle/cpu_port.cpp and compare")
     ap.add_argument("--threads", type=int, default=16, help="threads of the host port")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "build", "f64_reference"),
@@ -83,7 +86,7 @@ def main():
     groups, secs, trials, host = {}, [], 0, None
     for n, (tag, solver, snr, sidx, t0, cnt) in enumerate(work):
         p = SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=snr)
-        inp = build_trials(p, t0, cnt, seed=a.seed, sweep_idx=sidx, device=dev)
+        inp = build_trials(p, t0, cnt, seed=a.seed, sweep_idx=sidx, device=dev, with_hbf=a.ls)
         idx = inp["indx_S"] if solver == "angles" else None
         if n == 0:                                  # warm-up: allocations, code objects, clocks
             solve({k: (v[:2] if k != "A" or v.ndim == 3 else v) for k, v in inp.items()}, None if idx is None else idx[:2])
@@ -100,6 +103,11 @@ def main():
                "seed": np.full(cnt, a.seed, dtype=np.int64), "nmse_port": nm}
         if not a.no_ce:
             rec["ce_port"] = ce.cpu().numpy().astype(np.float64)
+        if a.ls:                                    # plot_errorVSsnr.m:83 on the conventional-HBF measurement, nothing narrowed
+            wide = lambda x: x.to(torch.complex128)
+            Sl = J.ls_estimate_f64(wide(inp["Y_hbf"]), wide(inp["A_hbf"]), wide(inp["B_hbf"])).cpu().numpy()
+            rec["S_ls"] = np.ascontiguousarray(Sl)
+            rec["nmse_ls"] = np.array([O.nmse_capped(Sl[t], zb[t]) for t in range(cnt)])
         for k, v in rec.items():
             g.setdefault(k, []).append(v)
         if n == 0 and a.host_port > 0:

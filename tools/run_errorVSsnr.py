@@ -15,6 +15,7 @@ ap.add_argument("--builder", default="hip", choices=["hip"], help="(the torch te
 ap.add_argument("--rate", action="store_true", help="rate metric of plot_rateVSframelength.m instead of the NMSE")
 ap.add_argument("--tssr", action="store_true", help="add the TSSR recipe (mc_svt with rho = 0.1, then joint OMP)")
 ap.add_argument("--vamp-large", action="store_true", help="VAMP column also where L*Gt > 128 (one order-L*Gt eigen-decomposition per trial)")
+ap.add_argument("--ls-f64", action="store_true", help="LS and Y*pinv(B) from the float64 entries (jstsp_pinv_f64 / jstsp_ls_f64): numbers where the fp32 Gram route gives NaN")
 ap.add_argument("--config3", action="store_true", help="BASELINE configs[3]: Nt=Nr=64, Nrf=8, K=64, L=8, 10 SNR points")
 ap.add_argument("--dist", action="store_true",
                 help="one rank per GPU (start with python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 "
@@ -37,7 +38,8 @@ if a.config3:
     snrs = list(range(-15, 15, 3))                              # 10 points
 t0 = time.perf_counter()
 out = run_sweep(base, snrs, a.trials, Imax=100, batch=a.batch, baselines=True, numOfnz=100, builder=a.builder, vamp_max_order=8192 if a.vamp_large else 128,
-                metric="rate" if a.rate else "nmse", tssr=(100, 0.1) if a.tssr else None, dist=dist)
+                metric="rate" if a.rate else "nmse", tssr=(100, 0.1) if a.tssr else None, dist=dist,
+                ls_precision="f64" if a.ls_f64 else "f32")
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 if dist is not None:
