@@ -377,7 +377,25 @@ int jstsp_cosamp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batc
  * (one support for all columns; atom = argmax_g ||A(:,g)' * R||_p, p = pnorm in {2, 1}; least squares on the support),
  * stopping after K atoms, when all min(N, Gr) independent atoms are in, or when ||R||_F <= 1e-6 ||Y||_F.
  * A: N x Gr (strideA 0 = shared); Y: N x S x batch; Z_out: Gr x S x batch; index_out: NULL or K x batch int32
- * (1-based atoms in selection order, 0 beyond the count); count_out: NULL or batch int32 (atoms selected). */
+ * (1-based atoms in selection order, 0 beyond the count); count_out: NULL or batch int32 (atoms selected).
+ * Contract (tests/test_gpu_mmv_omp_paths.py, against the float64 oracle on the same complex64 values):
+ *   Stop rules, tested in this order per atom: (1) min(K, N, Gr) atoms are in; (2) the chosen atom a is dependent on the
+ *   support: ||a - Q Q' a||^2 <= 1e-10 ||a||^2 after two Gram-Schmidt passes (float64 sums), or a = 0 - it is NOT added, the
+ *   count stays; (3) after an atom is added, ||R||_F^2 <= 1e-12 ||Y||_F^2 (float64 sums) - the atom counts.  Y = 0 returns
+ *   support [1], count 1, Z = 0.  A residual within rounding of rule (3) (a noiseless Y = A Z0: fp32 leaves 1e-7..1e-8 ||Y||)
+ *   may take the device one atom further than float64; the first atoms and Z agree.
+ *   Ties: the lowest index wins.  Every atom's score is the same arithmetic in the same order, so equal columns and columns
+ *   differing by a factor -1 or +-1i score bit-equal and tie exactly.  A selection whose float64 relative gap to the runner-up
+ *   is >= 1e-3 is the float64 selection; Z is then within 1e-4 of the float64 Z relative to max|Z| when
+ *   cond(A(:,support)) <= 100 (measured: profiles/mmv_measured_tolerances.json, mmv_paths.*.Z).
+ *   Scale: each problem is solved on Y * 2^-e with e the exponent of its largest finite component, and Z is scaled back.
+ *   Both scalings are exact unless a value underflows (a component of Y more than 2^125 times smaller than the largest, or
+ *   an entry of Z below the normal fp32 range): supports and counts do not depend on the scale of Y over the whole fp32
+ *   range, and Z of Y * 2^k is Z of Y times 2^k bit for bit (tested: Y * 2^+-70, 2^+-100, asserted on the bits); atoms
+ *   with norms within 2^+-40 of 1 are supported (tested: A * 2^+-40, same support, Z within 1e-6 of the rescaled Z),
+ *   beyond that the fp32 row scores ||A(:,g)' R||^2 may overflow or vanish.  A NaN or Inf in a problem's Y (tested: NaN,
+ *   +Inf, -Inf) ends that problem with a count in [0, K] and status 0; other problems of the batch are not affected.  A repeated call is bit-identical and a problem's
+ *   result does not depend on the batch around it or on the memspace. */
 int jstsp_mmv_omp_c32(jstsp_ctx *ctx, int N, int Gr, int S, int batch, const jstsp_c32 *A, long long strideA,
                       const jstsp_c32 *Y, int K, int pnorm, jstsp_c32 *Z_out, int32_t *index_out,
                       int32_t *count_out, int memspace);

@@ -11,6 +11,9 @@
 // stopping early when every atom is in the support, when the new atom is numerically dependent on the chosen ones,
 // or when ||R||_F <= 1e-6 ||Y||_F (with the drivers' numOfnz = 100 >= 32 atoms of a square A the result is the LS
 // estimate pinv(A)*Y, which is what errorVSsnr_angles.fig shows: the LS and MMV-OMP curves coincide).
+// The row scores are fp32 sums of |c|^2: each problem is solved on Y * 2^-e (e = exponent of its largest component; the
+// scaling, undone on Z, is exact unless a component underflows: one more than 2^125 times smaller than the largest rounds
+// in the denormal range), so the selections do not depend on the scale of Y (include/jstsp.h states the contract).
 //
 // One workgroup per problem; the least squares is carried incrementally by modified Gram-Schmidt of the selected atoms
 // (float64 dot products), R is updated in place, Z comes from one back-substitution per column at the end.  The
@@ -18,6 +21,7 @@
 // not a hot kernel.
 #include "solver_common.h"
 #include <algorithm>
+#include <cfloat>
 #include <cstring>
 
 namespace jstsp {
@@ -57,18 +61,38 @@ __global__ __launch_bounds__(256) void mmv_omp_kernel(int N, int Gr, int S, int 
         __syncthreads();
         return red[0] + red[1] + red[2] + red[3];
     };
+    auto block_max = [&](float v) {                               // through part[]: free until the first scores
+        for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+        __syncthreads();
+        if (lane == 0) part[wave] = v;
+        __syncthreads();
+        return fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+    };
 
+    // ||Y||_F^2 and the largest finite component of Y: the problem is solved on Y * 2^-ey (largest component in [0.5, 1)),
+    // exact unless a component underflows (it is then below the rounding of every sum it enters), so that the fp32 row
+    // scores |c|^2 neither overflow nor vanish whatever the scale of Y
     double y2 = 0.0;
+    float ymax = 0.f;
     for (int e = tid; e < N * S; e += 256) {
         const float2 v = y[e];
-        R[e] = v;
         y2 += (double)v.x * v.x + (double)v.y * v.y;
+        const float ax = fabsf(v.x), ay = fabsf(v.y);
+        if (ax <= FLT_MAX) ymax = fmaxf(ymax, ax);               // (not NaN, not Inf)
+        if (ay <= FLT_MAX) ymax = fmaxf(ymax, ay);
+    }
+    ymax = block_max(ymax);
+    int ey = 0;
+    if (ymax > 0.f) (void)frexpf(ymax, &ey);
+    for (int e = tid; e < N * S; e += 256) {
+        const float2 v = y[e];
+        R[e] = make_float2(ldexpf(v.x, -ey), ldexpf(v.y, -ey));
     }
     for (int e = tid; e < Gr * S; e += 256) z[e] = make_float2(0.f, 0.f);
     for (int e = tid; e < K * K; e += 256) Rt[e] = make_float2(0.f, 0.f);
     for (int g = tid; g < Gr; g += 256) taken[g] = 0;
     for (int k = tid; k < K; k += 256) io[k] = 0;
-    y2 = block_sum(y2);
+    y2 = ldexp(block_sum(y2), -2 * ey);                           // of the scaled Y (exact)
     const int kmax = min(K, min(N, Gr));
     int k = 0;
     // deterministic split of the (atom, column) correlations: thread -> atom g = tid % gp, column group tid / gp
@@ -200,6 +224,13 @@ __global__ __launch_bounds__(256) void mmv_omp_kernel(int N, int Gr, int S, int 
             z[(io[r] - 1) + (long long)Gr * s] = make_float2(acc.x / d, acc.y / d);
         }
     }
+    // ---- back to the scale of Y (each thread rescales the column it solved)
+    if (ey != 0)
+        for (int s = tid; s < S; s += 256)
+            for (int r = 0; r < nsel; ++r) {
+                float2 &v = z[(io[r] - 1) + (long long)Gr * s];
+                v = make_float2(ldexpf(v.x, ey), ldexpf(v.y, ey));
+            }
 }
 
 }  // namespace

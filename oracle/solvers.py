@@ -23,7 +23,7 @@ __all__ = [
     "proposed_algorithm_angles_literal", "proposed_algorithm_angles",
     "omp_literal", "omp_literal_margins", "omp", "sparse_admm_literal", "sparse_admm",
     "mc_svt", "mc_admm_literal", "mc_admm", "spectral_norm", "nmse_capped",
-    "mmv_omp", "tssr", "rate",
+    "mmv_omp", "mmv_omp_margins", "tssr", "rate",
 ]
 
 
@@ -500,6 +500,18 @@ def mmv_omp(A, Y, K, norm="l2"):
     for all columns, atom = argmax_g ||A(:,g)'*R||_p (first index on ties), least squares on the support; stops after
     K atoms, when min(N, Gr) atoms are in, when the new atom depends on the support, or when
     ||R||_F <= 1e-6 ||Y||_F.  Returns (Z (Gr x S), support (1-based, selection order))."""
+    return _mmv_omp(A, Y, K, norm, None)
+
+
+def mmv_omp_margins(A, Y, K, norm="l2"):
+    """``mmv_omp`` plus the margin of every selection that was made: per appended atom the float64 relative gap
+    ``(s1 - s2) / s1`` between the largest and the second-largest row score among the atoms not yet in the support
+    (0 for a tie, also when every score is 0; 1 when a single candidate is left).  Returns ``(Z, support, gaps)``."""
+    gaps = []
+    return _mmv_omp(A, Y, K, norm, gaps) + (np.array(gaps, dtype=np.float64),)
+
+
+def _mmv_omp(A, Y, K, norm, gaps):
     A = np.asarray(A, dtype=np.complex128)
     Y = np.asarray(Y, dtype=np.complex128)
     N, Gr = A.shape
@@ -516,6 +528,10 @@ def mmv_omp(A, Y, K, norm="l2"):
         sub = A[:, support + [g]]
         if np.linalg.matrix_rank(sub, tol=1e-5 * np.linalg.norm(A[:, g])) < sub.shape[1]:
             break
+        if gaps is not None:
+            free = np.delete(score, support)
+            s2, s1 = np.partition(free, -2)[-2:] if len(free) > 1 else (0.0, free[0])
+            gaps.append(float((s1 - s2) / s1) if s1 > 0 else (1.0 if len(free) == 1 else 0.0))
         support.append(g)
         coef = np.linalg.lstsq(sub, Y, rcond=None)[0]
         R = Y - sub @ coef
