@@ -87,7 +87,9 @@ size_t jstsp_workspace_bytes(const jstsp_ctx *ctx);
  *   JSTSP_H2=0            strict complex-fp32 MFMA (v_mfma_f32_32x32x2_f32) for every contraction; default 1: contractions of
  *                         at least 2^22 complex MACs per problem run as split-f16 MFMA with fp32 accumulation (fp32-equivalent,
  *                         see "Accuracy" below); 2: split-f16 whatever the size
- *   JSTSP_FUSED=0         proposed_algorithm: three kernels per iteration instead of the one-pass kernel (csrc/fused.hip)
+ *   JSTSP_FUSED=0|2       proposed_algorithm: 0 three kernels per iteration instead of the one-pass kernel (csrc/fused.hip); 2 the
+ *                         one-pass kernel, but between two passes Res = A^H Tc - R v and P1 = G_A Res as two launches (default 1:
+ *                         one launch that keeps the tile of Res on chip, csrc/gradstep.hip; same bits - the A/B and test handle)
  *   JSTSP_FUSED_PARTS=n   column ranges per problem in that pass (default: 4, 2 or 1 by divisibility of M / 32)
  *   JSTSP_FUSED_KBACK=b   headroom bits of the operand scale the pass predicts (default 4; a negative value is the test hook
  *                         that forces the per-trial re-solve, jstsp_last_fused_fallbacks)

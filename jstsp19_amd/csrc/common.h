@@ -61,9 +61,10 @@ struct DeviceScope {
 // sees one consistent setting from its first launch to its last.
 struct Tuning {
     int h2 = 1;             // JSTSP_H2: 0 strict complex-fp32 MFMA everywhere, 1 split-f16 MFMA for big contractions, 2 always
-    int fused = 1;          // JSTSP_FUSED: 0 three-kernel ADMM iteration instead of the fused pass
+    int fused = 1;          // JSTSP_FUSED: 0 three-kernel ADMM iteration instead of the fused pass; 2 the pass, gradient step unfused (grad_fused = 0)
     int fused_parts = 0;    // JSTSP_FUSED_PARTS: column ranges per problem in the pass (0: chosen from M)
     int fused_kback = 4;    // JSTSP_FUSED_KBACK: headroom bits of the predicted k scale (test hook: negative forces the re-solve)
+    int grad_fused = 1;     // (no variable of its own: JSTSP_FUSED=2 clears it) 0 the gradient step between two passes as its separate launches (gradstep.hip; same bits)
     int toeplitz = 2;       // JSTSP_TOEPLITZ: 0 dictionary taken as unstructured, 1 compact image only, 2 + window kernel (block 64)
     int overlap = -1;       // JSTSP_OVERLAP: side streams between the kernels of an iteration (-1: on with the fused pass)
     int lanczos = 1;        // JSTSP_LANCZOS: 0 Householder + Sturm instead of Lanczos for the convergence_error norms

@@ -604,10 +604,19 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             // `R*v` of :47; the recurrence alone drifts in fp32)
             const bool refreshed = refresh_at(it);
             if (refreshed) JSTSP_TRY(apply_R(w.V, w.RV, true));
+            // behind a pass (gradstep.hip; JSTSP_FUSED=2: the separate launches): Res and P1 = G_A Res from ONE launch - the 64 x 64 tile of Res is the
+            // whole k range of the second product for its columns and stays in LDS; same MFMA chains, same bits
+            if (svt_split && tn.grad_fused != 0 && w.h2g && grad_fused_shape(N, Gr, G2)) {
+                uint32_t *pm = w.pmax + (size_t)(apply_no++ & 1) * batch;
+                JSTSP_TRY(launch_grad_res_p1(ctx, A, strideA, w.Tc, w.RV, w.Res, w.GA, strideA ? (long long)Gr * Gr : 0, w.P1, pm,
+                                             G2, batch));
+                JSTSP_TRY(second_factor(w.RRes, pm, false));                        //    (:48)
+            } else {
             GemmDesc dres = make_gemm('C', 'N', Gr, G2, N, batch, Am, Mat{w.Tc, sng, N}, w.Res, sg, Gr, 1.f, w.RV, sg, Gr, -1.f);
             JSTSP_TRY(launch_cgemm(ctx, dres, GEMM_MISC));
             //    R*res for alpha = res'*res / (res'*R*res)                                (:48)
             JSTSP_TRY(apply_R(w.Res, w.RRes, false));
+            }
             if (svt_split) {
                 JSTSP_HIP(hipEventRecord(ev_q1, sm));
                 JSTSP_HIP(hipStreamWaitEvent(s1, ev_q1, 0));

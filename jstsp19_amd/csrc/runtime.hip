@@ -27,6 +27,7 @@ void load_tuning()
     t.fused = env_int("JSTSP_FUSED", t.fused);
     t.fused_parts = env_int("JSTSP_FUSED_PARTS", t.fused_parts);
     t.fused_kback = env_int("JSTSP_FUSED_KBACK", t.fused_kback);
+    t.grad_fused = t.fused == 2 ? 0 : 1;
     t.toeplitz = env_int("JSTSP_TOEPLITZ", t.toeplitz);
     t.overlap = env_int("JSTSP_OVERLAP", t.overlap);
     t.lanczos = env_int("JSTSP_LANCZOS", t.lanczos);

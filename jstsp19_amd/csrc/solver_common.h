@@ -216,4 +216,10 @@ int launch_fused_pass(jstsp_ctx *ctx, const FusedDesc &d);
 int fused_reduce(jstsp_ctx *ctx, const FusedWS &f, int G2, int M, int batch, float2 *Tc);
 int fused_pack_wq(jstsp_ctx *ctx, const FusedWS &f, const float2 *Q, int batch);      // from the raw Q of svt_prepare
 
+// ---- fused launches of the gradient step between two passes (gradstep.hip; JSTSP_FUSED=2 runs the separate launches) -----------------------------
+bool grad_fused_shape(int N, int Gr, int G2);
+// Res = A^H Tc - R v and P1 = G_A Res (+ max|P1| into pmax[t]) in one launch: the bits of the two cgemm launches it replaces
+int launch_grad_res_p1(jstsp_ctx *ctx, const float2 *A, long long sAt, const float2 *Tc, const float2 *RV, float2 *Res,
+                       const float2 *GA, long long sGAt, float2 *P1, uint32_t *pmax, int G2, int batch);
+
 }  // namespace jstsp

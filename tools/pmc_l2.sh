@@ -14,7 +14,7 @@ pass() {
     f=$(find $d -name "*counter_collection.csv" | head -1)
     if [ -z "$f" ]; then echo "pass $name: no counter csv" >> $out; tail -5 $R/gpurun_out/${tag}_pmc_l2_$name.err >> $out; return; fi
     echo "# pass $name: $*" >> $out
-    for k in fused_pass hgram3 hgram_kernel cgemm_kernel reduce_parts hgemm_kernel step_v lanczos jacobi2 pack_as; do python3 $R/tools/pmc_summary.py $f $k >> $out; done
+    for k in fused_pass hgram3 hgram_kernel cgemm_kernel grad_res_p1 reduce_parts hgemm_kernel step_v lanczos jacobi2 pack_as; do python3 $R/tools/pmc_summary.py $f $k >> $out; done
 }
 ARGS="$*"
 pass l2 TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_REQ_sum
