@@ -89,7 +89,9 @@ size_t jstsp_workspace_bytes(const jstsp_ctx *ctx);
  *                         see "Accuracy" below); 2: split-f16 whatever the size
  *   JSTSP_FUSED=0|2       proposed_algorithm: 0 three kernels per iteration instead of the one-pass kernel (csrc/fused.hip); 2 the
  *                         one-pass kernel, but between two passes Res = A^H Tc - R v and P1 = G_A Res as two launches (default 1:
- *                         one launch that keeps the tile of Res on chip, csrc/gradstep.hip; same bits - the A/B and test handle)
+ *                         one launch that keeps the tile of Res on chip, csrc/gradstep.hip; same bits - the A/B and test handle),
+ *                         the recomputation of R v inline as three launches (default: early on a side stream, first factor in one
+ *                         launch) and a memset of the pass's operand maxima (default: zeroed by the step kernel)
  *   JSTSP_FUSED_PARTS=n   column ranges per problem in that pass (default: 4, 2 or 1 by divisibility of M / 32)
  *   JSTSP_FUSED_KBACK=b   headroom bits of the operand scale the pass predicts (default 4; a negative value is the test hook
  *                         that forces the per-trial re-solve, jstsp_last_fused_fallbacks)

@@ -184,7 +184,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void step_v_kernel(int g, const float2 *Res, const float2 *RRes,
                                                     float2 *V, float2 *S, const int32_t *rank,
                                                     int cnt, const TrialParams *prm, double *ce3,
-                                                    int Imax, int it, float2 *RV)
+                                                    int Imax, int it, float2 *RV, uint32_t *zero8)
 {
     __shared__ double sh[NT / 64];
     const int t = blockIdx.x;
@@ -247,6 +247,8 @@ __global__ __launch_bounds__(NT) void step_v_kernel(int g, const float2 *Res, co
             S[base + i] = sv;
         }
     }
+    // the operand maxima the coming pass accumulates for this problem: eight words at a pitch of one per problem (proposed.hip)
+    if (zero8 && threadIdx.x < 8) zero8[(size_t)threadIdx.x * gridDim.x + t] = 0u;
     if (ce3 && threadIdx.x == 0) {
         // |v - v_prev|^2 = |alpha|^2 |res|^2 ; 0-divide at i = 1 gives Inf (NaN if res = 0) as in :51
         const double a2 = (double)ax * ax + (double)ay * ay;
@@ -332,19 +334,19 @@ int launch_update_c(jstsp_ctx *ctx, long long nm, int batch, const float2 *X, co
 }
 int launch_step_v(jstsp_ctx *ctx, int g, int batch, const float2 *Res, const float2 *RRes, float2 *V,
                   float2 *S, const int32_t *rank, int cnt, const TrialParams *prm, double *ce3,
-                  int Imax, int it, float2 *RV, int waves8)
+                  int Imax, int it, float2 *RV, int waves8, uint32_t *zero8)
 {
     // waves8 (the caller runs an eigen-decomposition beside this kernel): eight waves per problem - a workgroup that fits on a
     // CU beside a resident Jacobi, 16 waves x 106 registers do not; alone, the 16-wave form is 25 % faster
     if (g >= 8192 && waves8)
         hipLaunchKernelGGL(step_v_kernel<512>, dim3(batch), dim3(512), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV);
+                           cnt, prm, ce3, Imax, it, RV, zero8);
     else if (g >= 8192)
         hipLaunchKernelGGL(step_v_kernel<1024>, dim3(batch), dim3(1024), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV);
+                           cnt, prm, ce3, Imax, it, RV, zero8);
     else
         hipLaunchKernelGGL(step_v_kernel<256>, dim3(batch), dim3(256), 0, ctx->stream, g, Res, RRes, V, S, rank,
-                           cnt, prm, ce3, Imax, it, RV);
+                           cnt, prm, ce3, Imax, it, RV, zero8);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

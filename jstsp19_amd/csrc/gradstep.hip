@@ -143,6 +143,83 @@ __global__ __launch_bounds__(256) void grad_res_p1_kernel(const float2 *A, long 
     if (lane == 0) atomicMax(&pmax[t], __float_as_uint(tmax));
 }
 
+// grad_refresh_p1_kernel: the first factor of the recomputation of R v, P1 = G_A,hi V + (G_A,lo V), per (trial, 64 columns of G2)
+// in ONE workgroup instead of two launches of cgemm_kernel<64, ...> (P1 = G_A,lo V, then P1 = G_A,hi V + 1 * P1) between which
+// P1 made an HBM round trip and V was read twice.  The 64 x 64 tile of V is the whole k range of both products: it is staged in
+// LDS once, as the Res tile above is; the G_A fragments come from L2.  The two chains run one after the other from zero
+// accumulators, each k = 0..63 in pairs in the order of the cgemm loop; the lo product, already an fp32 accumulator, is the beta
+// term of the hi one: the cgemm epilogue forms 1 * acc + 1 * P1, which is the one rounding of acc + lo.  max|P1| is not formed
+// (the fp64-master second factor of the recomputation takes no scale).  Footprint of grad_res_p1_kernel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void grad_refresh_p1_kernel(const float2 *V, const float2 *GA, const float2 *GAlo, long long sGAt,
+                                                              float2 *P1, int G2, int batch)
+{
+    __shared__ float2 smem[64 * GLD];           // V tile: b(k, j) at [k][j]
+    const int tiles = G2 / 64;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int t = (slot / tiles) * 8 + xcd;
+    if (t >= batch) return;
+    const int n0 = (slot % tiles) * 64;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wi = wave & 1, wj = wave >> 1, l31 = lane & 31, lhi = lane >> 5;
+    const long long cbase = (long long)t * 64 * G2 + 64ll * n0;                 // column n0 of this trial's 64 x G2 arrays
+    const int gi = wi * 32 + l31;
+    // a(i, k) = G[i + 64 k], lane: k = 2 kp + lhi; the first fragments of the lo factor are requested before the tile is staged
+    const float2 *Gl = GAlo + (long long)t * sGAt + gi + 64 * lhi, *Gh = GA + (long long)t * sGAt + gi + 64 * lhi;
+    float2 ga[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) ga[q] = Gl[128 * q];
+    {
+        // the tile is contiguous: element e = tid + 256 p is b(k = e % 64, j = e / 64)
+        const float2 *Vp = V + cbase;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float2 rv[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) rv[p] = Vp[tid + 256 * (8 * h + p)];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) smem[(tid & 63) * GLD + (tid >> 6) + 4 * (8 * h + p)] = rv[p];
+        }
+    }
+    __syncthreads();
+
+    const float2 *rs = smem + wj * 32 + l31 + lhi * GLD;
+    f32x16 are, aim, lre, lim;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { are[r] = 0.f; aim[r] = 0.f; lre[r] = 0.f; lim[r] = 0.f; }
+    // eight chunks of eight k pairs: 0..3 G_A,lo V, 4..7 G_A,hi V; the fragments of the next chunk are requested before the
+    // MFMAs of this one (the last chunk requests its own again: no branch in the loop)
+#pragma unroll 1
+    for (int c = 0; c < 8; ++c) {
+        const int cn = min(c + 1, 7);
+        const float2 *Gn = ((cn < 4) ? Gl : Gh) + 1024 * (cn & 3);
+        float2 gn[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) gn[q] = Gn[128 * q];
+        if (c == 4) {                           // the lo product is complete: the hi chain starts from zero
+            lre = are; lim = aim;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { are[r] = 0.f; aim[r] = 0.f; }
+        }
+        const float2 *rc = rs + 16 * GLD * (c & 3);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float2 av = ga[q], bv = rc[2 * q * GLD];
+            are = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, av.x, are, 0, 0, 0);
+            aim = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, av.y, aim, 0, 0, 0);
+            are = __builtin_amdgcn_mfma_f32_32x32x2f32(-bv.y, av.y, are, 0, 0, 0);
+            aim = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, av.x, aim, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ga[q] = gn[q];
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int j = wj * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        P1[cbase + gi + 64ll * j] = make_float2(are[r] + lre[r], aim[r] + lim[r]);
+    }
+}
+
 }  // namespace
 
 bool grad_fused_shape(int N, int Gr, int G2) { return N == 64 && Gr == 64 && G2 >= 64 && G2 % 64 == 0; }
@@ -155,6 +232,17 @@ int launch_grad_res_p1(jstsp_ctx *ctx, const float2 *A, long long sAt, const flo
     JSTSP_REQUIRE(grid < (1ll << 31), JSTSP_E_UNSUPPORTED, "gradient step: grid too large");
     hipLaunchKernelGGL(grad_res_p1_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, A, sAt, Tc, RV, Res, GA, sGAt, P1,
                        pmax, G2, batch);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_grad_refresh_p1(jstsp_ctx *ctx, const float2 *V, const float2 *GA, const float2 *GAlo, long long sGAt, float2 *P1, int G2,
+                           int batch)
+{
+    JSTSP_REQUIRE(G2 >= 64 && G2 % 64 == 0 && batch > 0 && GA && GAlo, JSTSP_E_ARG, "gradient step: fused first factor of R v at G2 = %d", G2);
+    const long long grid = (long long)((batch + 7) / 8) * 8 * (G2 / 64);
+    JSTSP_REQUIRE(grid < (1ll << 31), JSTSP_E_UNSUPPORTED, "gradient step: grid too large");
+    hipLaunchKernelGGL(grad_refresh_p1_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, V, GA, GAlo, sGAt, P1, G2, batch);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

@@ -388,7 +388,11 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     //       V2 after update_c, then lambda_max of all three.
     // Buffer hazards are closed by events: update_x(i+1) waits for s1 (needs Q) and for s2's Gram of
     // [X | V1] (reads what update_x overwrites); update_c(i+1) waits for s2's Gram of V2.
-    // The per-iteration memset of the operand maxima is double-buffered by iteration parity for the same reason.
+    // The per-iteration zeroing of the operand maxima is double-buffered by iteration parity for the same reason.
+    // Behind a fused pass s2 also carries the recomputation of R v (every 4th iteration): it reads only v, G_A and G_B, and v is
+    // final when step_v of the iteration before ends, so it is issued there (ev_v) and runs beside the latency-bound tail of that
+    // window and the head of the pass, not in the HBM-saturated head of its own window; the main stream waits for it (ev_rv) in
+    // front of the first reader of R v.  JSTSP_FUSED=2 keeps it inline on the main stream, as three launches.
     // Default: everything on the context's stream (same kernels, same arithmetic, identical
     // results).  JSTSP_OVERLAP=1 enables the side streams: measured +3 % channel-estimates/s at
     // BASELINE configs[1], but co-running kernels stretch each other (the K B^H launch goes from
@@ -458,7 +462,20 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     // runs with eight waves.  The alternatives that were measured and lost (Gram of V2 one window late with double-buffered
     // norm partials, the whole side chain behind the step's head, other gate positions, stream priorities) are gone from
     // the code; their numbers are in DESIGN.md.
-    hipEvent_t ev_q1 = ctx->ev[7];
+    hipEvent_t ev_q1 = ctx->ev[7], ev_v = ctx->ev[8], ev_rv = ctx->ev[9];
+    // The recomputation of R v, P1 = (G_A,hi + G_A,lo) V then R v = P1 G_B with fp64 masters:
+    //  * its first factor as ONE launch (gradstep.hip) wherever the fused gradient step is on, same bits as the two launches;
+    //  * issued EARLY on s2 for an iteration behind a pass: after step_v of the iteration before (which then does not carry R v
+    //    forward: the recomputation overwrites all of it).  Hazards, all closed by ev_v / ev_rv: R v is written after step_v(it - 1),
+    //    the last main-stream kernel of that iteration that touches it, and before its first reader of iteration it (the Res
+    //    product); V is not written again before step_v(it), behind ev_rv; the product's scratch is w.P1, which the main stream does
+    //    not touch between the G_B apply of it - 1 (before step_v) and the Res / P1 launch of it (behind ev_rv).  s2 is idle at that
+    //    point (its Gram of V2 and lambda_max ended early in the window); its next Gram of V2, after the pass, queues behind it.
+    //    Iteration 0 (V = 0) and every path without a pass or without side streams recompute inline.  The two-output call
+    //    (no convergence_error: no split window, no work on s2) is left inline as well: not measured there.
+    const bool rv_fused1 = fusedp && tn.grad_fused != 0 && grad_fused_shape(N, Gr, G2);
+    const bool rv_early_ok = rv_fused1 && zfly && w.h2g && overlap;
+    bool rv_early = false;                      // R v of this iteration is being recomputed on s2 (issued by the previous iteration)
     // convergence_error(:,1:2): lambda_max of three Grams per trial and iteration, each warm-started from its own Ritz vector
     // of the previous iteration (eig2.hip); the record starts empty
     if (want_ce) JSTSP_TRY(lanczos_warm_reset(ctx, w.gn));
@@ -475,6 +492,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             if (!passed) JSTSP_HIP(hipMemsetAsync(w.kmax, 0, 8 * (size_t)batch * sizeof(uint32_t), sm));
         } else if (w.h2g) JSTSP_HIP(hipMemsetAsync(w.pmax, 0, 2 * (size_t)batch * sizeof(uint32_t), sm));
         int apply_no = 0;
+        bool next_zeroed = false;                   // step_v has zeroed the next iteration's operand maxima
         // -- sub 1: Y = svt(X - V1/rho, tau_Y/rho) = Z - Q Z                                 (:35)
         if (it > 0) JSTSP_HIP(hipStreamWaitEvent(sm, ev_svt, 0));
         if (it > 0 && want_ce) JSTSP_HIP(hipStreamWaitEvent(sm, ev_gxv, 0));
@@ -592,6 +610,10 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         };
         auto apply_R = [&](const float2 *Xin, float2 *out, bool exact) -> int {
             uint32_t *pm = w.pmax ? w.pmax + (size_t)(apply_no++ & 1) * batch : nullptr;      // two applies per iteration, one slot each
+            if (exact && rv_fused1) {       // P1 = G_A,hi X + (G_A,lo X) in one launch; no maximum (unused by the exact second factor)
+                JSTSP_TRY(launch_grad_refresh_p1(ctx, Xin, w.GA, GAlo, strideA ? (long long)Gr * Gr : 0, w.P1, G2, batch));
+                return second_factor(out, pm, exact);
+            }
             if (exact) JSTSP_TRY(gemm(ctx, 'N', 'N', Gr, G2, Gr, batch, GAl, Mat{Xin, sg, Gr}, w.P1, sg, Gr));      // P1 = G_A,lo X
             GemmDesc dp = make_gemm('N', 'N', Gr, G2, Gr, batch, GAm, Mat{Xin, sg, Gr}, w.P1, sg, Gr, 1.f, exact ? w.P1 : nullptr, sg,
                                     Gr, exact ? 1.f : 0.f);
@@ -603,7 +625,10 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             // R v: recomputed from v every `rv_refresh` iterations, carried by R v += alpha R res in between (both are
             // `R*v` of :47; the recurrence alone drifts in fp32)
             const bool refreshed = refresh_at(it);
-            if (refreshed) JSTSP_TRY(apply_R(w.V, w.RV, true));
+            if (refreshed && rv_early) {
+                JSTSP_HIP(hipStreamWaitEvent(sm, ev_rv, 0));       // recomputed on s2 since step_v of the previous iteration
+                rv_early = false;
+            } else if (refreshed) JSTSP_TRY(apply_R(w.V, w.RV, true));
             // behind a pass (gradstep.hip; JSTSP_FUSED=2: the separate launches): Res and P1 = G_A Res from ONE launch - the 64 x 64 tile of Res is the
             // whole k range of the second product for its columns and stays in LDS; same MFMA chains, same bits
             if (svt_split && tn.grad_fused != 0 && w.h2g && grad_fused_shape(N, Gr, G2)) {
@@ -623,8 +648,26 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                 JSTSP_TRY(issue_s1(2));
             }
             //    v += alpha res; ce(i,3); s = soft(v) (.* Omega_S)                            (:49-56, angles :36,:68)
+            // (when the next iteration recomputes R v early, R v += alpha R res would be overwritten: not formed)
+            const bool early_next = rv_early_ok && it + 1 < Imax && refresh_at(it + 1);
+            // The pass at the end of this iteration accumulates the operand maxima of iteration it + 1 (k, X, V1, next Z) in block
+            // (it + 1) & 1: step_v zeroes it (JSTSP_FUSED=2: a memset in front of the pass).  Every reader of that block from
+            // iteration it - 1 is behind an event the main stream has waited for by now: the three-Gram pass and svt_prepare
+            // (ev_gxv, ev_svt at the top of this iteration), the Gram of V2 (ev_gv2, here; it ended about 1 ms ago).
+            uint32_t *const nx_zero = (fusedp && tn.grad_fused != 0 && it + 1 < Imax) ? kmax0 + (size_t)((it + 1) & 1) * 8 * (size_t)batch : nullptr;
+            if (nx_zero && it > 0 && want_ce) JSTSP_HIP(hipStreamWaitEvent(sm, ev_gv2, 0));
+            next_zeroed = nx_zero != nullptr;
             JSTSP_TRY(launch_step_v(ctx, (int)g, batch, w.Res, w.RRes, w.V, w.S, w.rank, (int)cnt_ll, w.prm, w.ce,
-                                    Imax, it, w.RV, svt_split));
+                                    Imax, it, early_next ? nullptr : w.RV, svt_split, nx_zero));
+            if (early_next) {
+                JSTSP_HIP(hipEventRecord(ev_v, sm));
+                JSTSP_HIP(hipStreamWaitEvent(s2, ev_v, 0));
+                StreamScope sc(ctx, s2);
+                JSTSP_TRY(launch_grad_refresh_p1(ctx, w.V, w.GA, GAlo, strideA ? (long long)Gr * Gr : 0, w.P1, G2, batch));
+                JSTSP_TRY(second_factor(w.RV, nullptr, true));
+                JSTSP_HIP(hipEventRecord(ev_rv, s2));
+                rv_early = true;
+            }
         } else {
             //    v = U\(L\k) = pinv(A) K pinv(B)   [ = G_A^-1 (A^H Tc) G_B^-1 on the Gram route: GA / GB hold the inverses ]  (:53)
             float2 *left = PB ? w.V : w.P1;        // result of the A side; the B side (if any) finishes into V
@@ -653,7 +696,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         if (fusedp && it + 1 < Imax) {
             // the pass writes the operand maxima of iteration it + 1 (k, X, V1, next Z): zero that block now
             uint32_t *nx = kmax0 + (size_t)((it + 1) & 1) * 8 * (size_t)batch;
-            JSTSP_HIP(hipMemsetAsync(nx, 0, 8 * (size_t)batch * sizeof(uint32_t), sm));
+            if (!next_zeroed) JSTSP_HIP(hipMemsetAsync(nx, 0, 8 * (size_t)batch * sizeof(uint32_t), sm));
             JSTSP_TRY(fused_pack_as(ctx, fw, w.W, sng, G2, M, batch, w.wmax));
             JSTSP_HIP(hipStreamWaitEvent(sm, ev_svt, 0));          // Y of the next iteration (side stream s1)
             FusedDesc fd{fw.Bf, strideB ? fw.sBf : 0, w.Bc.bmax, strideB ? 1 : 0, fw.ASp, fw.sAS, w.wmax, w.kmax,

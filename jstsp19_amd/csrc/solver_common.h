@@ -221,5 +221,9 @@ bool grad_fused_shape(int N, int Gr, int G2);
 // Res = A^H Tc - R v and P1 = G_A Res (+ max|P1| into pmax[t]) in one launch: the bits of the two cgemm launches it replaces
 int launch_grad_res_p1(jstsp_ctx *ctx, const float2 *A, long long sAt, const float2 *Tc, const float2 *RV, float2 *Res,
                        const float2 *GA, long long sGAt, float2 *P1, uint32_t *pmax, int G2, int batch);
+// first factor of the recomputation of R v, P1 = G_A,hi V + (G_A,lo V), in one launch: the bits of the two cgemm launches it
+// replaces (P1 = G_A,lo V; P1 = G_A,hi V + P1); no maximum is formed
+int launch_grad_refresh_p1(jstsp_ctx *ctx, const float2 *V, const float2 *GA, const float2 *GAlo, long long sGAt, float2 *P1, int G2,
+                           int batch);
 
 }  // namespace jstsp
