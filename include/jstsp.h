@@ -709,8 +709,11 @@ int jstsp_rate_c64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, 
  *    eigenvalue is positive (the zero argument of iteration 1, svt.m:8-12).
  *  - n <= 64: two-sided cyclic Jacobi in LDS, convergence decided on the device (a sweep that rotates nothing, at most 30): no
  *    device-to-host read inside the iteration loop.  64 < n <= 512: the global-memory Jacobi of csrc/vamp64.hip, which reads one
- *    norm per sweep on the host - such a call synchronises the context's stream in every iteration.  n > 512:
- *    JSTSP_E_UNSUPPORTED.  Every call synchronises the stream once at entry (the per-trial scalars are staged from the caller's
+ *    norm per sweep on the host - such a call synchronises the context's stream in every iteration.  That Jacobi sweeps ALL
+ *    matrices of the call while any of them is above its stop criterion: for 64 < n a trial of jstsp_svt_f64 /
+ *    jstsp_proposed_algorithm_f64 may get sweeps it would not get alone, so its last bits can depend on the batch around it
+ *    (within the bounds asserted below; for n <= 64 they do not).  jstsp_mc_svt_f64 / jstsp_mc_admm_f64 ask the same Jacobi to
+ *    leave a converged matrix alone and are batch-independent at every order.  n > 512: JSTSP_E_UNSUPPORTED.  Every call synchronises the stream once at entry (the per-trial scalars are staged from the caller's
  *    host arrays) and a JSTSP_HOST call at exit.
  *  - convergence_error(i, 1:2) from lambda_max of the n x n Grams of V1, V2, X (the same Jacobi); skipped when ce_out is NULL.
  *  - type: JSTSP_TYPE_APPROXIMATE only; JSTSP_TYPE_STD returns JSTSP_E_UNSUPPORTED (use jstsp_proposed_algorithm_c64).
@@ -766,6 +769,49 @@ int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c6
 int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *Y,
                  const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB,
                  jstsp_c64 *S_out, double *rcond_out, int memspace);
+
+/* ---- joint OMP and matrix completion in float64 -----------------------------------------------------
+ * The "OMP with MMV" column (plot_errorVSsnr.m:116-117) and the TSSR / "SVT-based" recipe (:151-162) evaluated in FLOAT64 on the
+ * device - unlike jstsp_mmv_omp_c64 / jstsp_mc_svt_c64 / jstsp_mc_admm_c64, which narrow the same arrays to the fp32 kernels.
+ * jstsp_mmv_omp_f64 (csrc/mmv_omp64.hip): the algorithm, shapes, strideA, NULL-able index_out / count_out, both memspaces and the
+ * Gr <= 4096 limit of jstsp_mmv_omp_c32; every stored value and every sum is a double (residual, basis, triangular factor,
+ * coefficients, row scores, dot products, back-substitution, Z).  Contract (tests/test_gpu_mmv_omp64.py, against
+ * oracle/solvers.py mmv_omp on the same values):
+ *   Stop rules, in this order per atom, with the constants of the fp32 entry: (1) min(K, N, Gr) atoms are in; (2) the chosen atom
+ *   is dependent on the support, ||a - Q Q' a||^2 <= 1e-10 ||a||^2 after two Gram-Schmidt passes, or a = 0 - not added;
+ *   (3) ||R||_F^2 <= 1e-12 ||Y||_F^2 after an atom is added - it counts.  Y = 0 returns support [1], count 1, Z = 0.
+ *   Selections: a selection whose float64 relative gap to the runner-up is >= 1e-9, or exactly 0, is the oracle's; Z is then within
+ *   1e-12 of the oracle's relative to max|Z| when cond(A(:,support)) <= 100.
+ *   Ties: the lowest index wins.  A correlation is carried in four real fma chains joined at the end and |c|^2 is a sum of two
+ *   rounded squares, so columns equal to column j, to -column j or to +-1i column j score bit-equal.
+ *   Scale: each problem is solved on Y * 2^-e, e the exponent of its largest finite component (frexp / ldexp, exact unless a
+ *   component more than 2^1021 times smaller underflows), ||Y||_F^2 is summed on the scaled values: supports and counts do not
+ *   depend on the scale of Y, and Z of Y * 2^k is Z of Y times 2^k bit for bit (tested: k = +-100, +-400).
+ *   A NaN or Inf in a problem's Y ends that problem with a count in [0, K] and status 0; its batch mates are not affected.
+ *   No atomics, every sum in a fixed order: a repeated call returns the same bits, and a problem's result does not depend on the
+ *   batch around it or on the memspace.
+ * jstsp_mc_svt_f64 / jstsp_mc_admm_f64 (csrc/mc64.hip): mc_svt.m:1-12 and mc_admm.m:1-34 with the dense solve written as
+ * b ./ (Omega + rho).  Arguments as the _c64 entries, Omega a double array; tau, rho: host double[batch]; ce_out: NULL (Htrue may
+ * then be NULL too) or Imax x batch double, sigma_max(X - Htrue)^2 / sigma_max(Htrue)^2, not capped.  The svt is the one of
+ * jstsp_svt_f64 (csrc/svt64.h), with its guard - non-positive eigenvalues dropped, all zeros exactly when none is positive - and
+ * its limits: min(Mr, Mt) <= 512, batch <= 65535, a workspace above 24 GiB is JSTSP_E_UNSUPPORTED.  The eigen-decomposition runs
+ * to convergence in every iteration (no warm start, no early stop, no environment switch).  Imax = 0 returns zeros.  Both calls
+ * synchronise the context's stream at entry (the scalars are staged) and at exit, in both memspaces; for 64 < min(Mr, Mt) also
+ * once per Jacobi sweep.  Deterministic, and a trial's bits do not depend on the batch around it, also for 64 < min(Mr, Mt): the
+ * global-memory Jacobi is told to leave a matrix alone from the sweep on at whose start it meets the stop criterion itself
+ * (jstsp_svt_f64 and jstsp_proposed_algorithm_f64 keep the behaviour they had: see their block above).
+ * Asserted (tests/test_gpu_mc64.py, test_gpu_tssr64.py): X within 1e-10 of max|X_ref| and convergence_error within 1e-8 of
+ * oracle/solvers.py mc_svt / mc_admm; the TSSR chain within 1e-10 (Y_svt) and 1e-9 (S_tssr, S_svt) of oracle/solvers.py tssr
+ * (measured on MI355X: Z 3.7e-15, mc_svt X 1.1e-14, mc_admm X 1.6e-13 and ce 7.2e-13, the TSSR chain 1.2e-14; DESIGN.md section 9e,
+ * profiles/tssr64_measured_tolerances.json). */
+int jstsp_mmv_omp_f64(jstsp_ctx *ctx, int N, int Gr, int S, int batch, const jstsp_c64 *A, long long strideA,
+                      const jstsp_c64 *Y, int K, int pnorm, jstsp_c64 *Z_out, int32_t *index_out,
+                      int32_t *count_out, int memspace);
+int jstsp_mc_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *OH, const double *Omega,
+                     int Imax, const double *tau, const double *rho, jstsp_c64 *X_out, int memspace);
+int jstsp_mc_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Htrue, const jstsp_c64 *OH,
+                      const double *Omega, int Imax, const double *tau, const double *rho,
+                      jstsp_c64 *X_out, double *ce_out, int memspace);
 
 /* Per-kernel timing of the last proposed_algorithm call made with profiling enabled:
  * jstsp_set_profiling(ctx, 1) brackets every launch of the dominant kernel with HIP

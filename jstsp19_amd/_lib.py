@@ -126,6 +126,11 @@ SIGNATURES["jstsp_pinv_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p,
 SIGNATURES["jstsp_ls_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
                                       c_void_p, c_void_p, c_int])
 
+for _n in ("mmv_omp", "mc_svt", "mc_admm"):
+    # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes
+    # (pointers are void* here, so the two are one list)
+    SIGNATURES["jstsp_%s_f64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
+
 
 class JstspError(RuntimeError):
     """A failed C-ABI call; ``code`` is its status (< 0: JSTSP_E_*, > 0: hipError_t), None when raised on the Python side."""

@@ -1,0 +1,218 @@
+// jstsp_mc_svt_f64 / jstsp_mc_admm_f64 - benchmark_algorithms/mc_svt.m:1-12 and mc_admm.m:1-34 evaluated in FLOAT64 on the device:
+// the first stage of the drivers' TSSR recipe (plot_errorVSsnr.m:151-162) and its ADMM sibling, to the digits MATLAB carries.
+//   mc_svt   Y = 0;  repeat Imax times:  X = svt(Y, tau/rho);  Y = Y + rho (OH - Omega .* X)                          (:5-9)
+//   mc_admm  X = Y = Z = 0;  repeat:  X = svt(Y - Z/rho, tau/rho);  Y = (OH + Z + rho X) ./ (Omega + rho);            (:22-25)
+//                                     Z = Z + rho (X - Y);  ce(i) = sigma_max(X - Htrue)^2 / sigma_max(Htrue)^2       (:26-28)
+// (the reference's dense solve A \ b has A = diag(vec(Omega)) + rho I: an entrywise division).  The svt is Svt64 of svt64.h - the
+// one jstsp_svt_f64 and jstsp_proposed_algorithm_f64 use: Gram on the smaller side, in-LDS Jacobi for n <= 64, the global-memory
+// Jacobi of vamp64.hip for 64 < n <= 512, non-positive eigenvalues dropped - and runs to convergence in every iteration: no warm
+// start, no early stop, no environment switch.  sigma_max^2 is lambda_max of the same Gram (Svt64::lambda_max).  The two updates
+// are element-wise kernels; every reduction lives in the products and the Jacobi, which sum in a fixed order inside one trial: a
+// repeated call returns the same bits and a trial's result does not depend on the batch around it (for 64 < n the global Jacobi is
+// told to leave a converged matrix alone while its batch mates are still swept: Svt64::freeze).
+#include "svt64.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace jstsp {
+namespace {
+
+struct McPar {          // per-trial scalars: rho and the threshold tau / rho, both formed in float64
+    double rho, thr;
+};
+
+inline dim3 mc_grid(long long per, int batch) { return dim3((unsigned)std::max<long long>(1, std::min<long long>((per + 255) / 256, 2048)), batch); }
+
+// mc_svt.m:9   Y = Y + rho (OH - Omega .* X)
+__global__ __launch_bounds__(256) void mc_svt_update64_kernel(long long nm, const McPar *par, double2 *Y, const double2 *OH, const double *Omega,
+                                                              const double2 *X)
+{
+    const long long o = (long long)blockIdx.y * nm;
+    const double rho = par[blockIdx.y].rho;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nm; e += (long long)gridDim.x * 256) {
+        const double om = Omega[o + e];
+        const double2 x = X[o + e], oh = OH[o + e];
+        double2 y = Y[o + e];
+        y.x += rho * (oh.x - om * x.x);
+        y.y += rho * (oh.y - om * x.y);
+        Y[o + e] = y;
+    }
+}
+
+// mc_admm.m:24-26   Y = (OH + Z + rho X) ./ (Omega + rho);  Z = Z + rho (X - Y);  Zn = Y - Z/rho (the next svt argument, :22)
+__global__ __launch_bounds__(256) void mc_admm_update64_kernel(long long nm, const McPar *par, double2 *Y, double2 *Z, const double2 *OH,
+                                                               const double *Omega, const double2 *X, double2 *Zn)
+{
+    const long long o = (long long)blockIdx.y * nm;
+    const double rho = par[blockIdx.y].rho;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nm; e += (long long)gridDim.x * 256) {
+        const double den = Omega[o + e] + rho;
+        const double2 x = X[o + e], oh = OH[o + e];
+        double2 z = Z[o + e];
+        const double2 y = make_double2((oh.x + z.x + rho * x.x) / den, (oh.y + z.y + rho * x.y) / den);
+        z.x += rho * (x.x - y.x);
+        z.y += rho * (x.y - y.y);
+        Y[o + e] = y;
+        Z[o + e] = z;
+        Zn[o + e] = make_double2(y.x - z.x / rho, y.y - z.y / rho);
+    }
+}
+
+__global__ __launch_bounds__(256) void mc_diff64_kernel(long long n, const double2 *X, const double2 *H, double2 *D)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const double2 x = X[e], h = H[e];
+        D[e] = make_double2(x.x - h.x, x.y - h.y);
+    }
+}
+
+// ce(it, t) = num[t] / den[t] (IEEE: x / 0 = Inf, 0 / 0 = NaN, as the reference); ce laid out Imax per trial
+__global__ __launch_bounds__(256) void mc_ratio64_kernel(int batch, int Imax, int it, const double *num, const double *den, double *ce)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < batch) ce[(long long)t * Imax + it] = num[t] / den[t];
+}
+
+int mc64_check(jstsp_ctx *ctx, const char *nm, int Mr, int Mt, int batch, int Imax, int memspace)
+{
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_REQUIRE(Mr > 0 && Mt > 0 && batch > 0 && Imax >= 0, JSTSP_E_SHAPE, "%s: bad shape", nm);
+    JSTSP_REQUIRE(std::min(Mr, Mt) <= P64_MAX_ORDER && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "%s: min(Mr, Mt) = %d, batch = %d: the float64 eigen-decomposition is limited to order %d (batch 65535)", nm, std::min(Mr, Mt), batch,
+                  P64_MAX_ORDER);
+    return 0;
+}
+
+// rho and tau / rho of every trial on the device (synchronises: the staging vector is this function's own)
+int mc64_params(hipStream_t st, int batch, const double *tau, const double *rho, McPar *par)
+{
+    std::vector<McPar> hp(batch);
+    for (int t = 0; t < batch; ++t) hp[t] = McPar{rho[t], tau[t] / rho[t]};
+    JSTSP_HIP(hipMemcpyAsync(par, hp.data(), batch * sizeof(McPar), hipMemcpyHostToDevice, st));
+    JSTSP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // namespace
+}  // namespace jstsp
+
+using namespace jstsp;
+
+extern "C" {
+
+int jstsp_mc_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *OH_, const double *Omega_, int Imax, const double *tau,
+                     const double *rho, jstsp_c64 *X_out, int memspace)
+{
+    const char *nmf = "mc_svt (float64)";
+    JSTSP_TRY(mc64_check(ctx, nmf, Mr, Mt, batch, Imax, memspace));
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(OH_ && Omega_ && tau && rho && X_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    const bool host = memspace == JSTSP_HOST;
+    const size_t nm1 = (size_t)Mr * Mt, nm = nm1 * batch, z2 = sizeof(double2);
+    const size_t need = Svt64::bytes(Mr, Mt, batch) + Slab::rnd(batch * sizeof(McPar)) + Slab::rnd(nm * z2) +
+                        (host ? 2 * Slab::rnd(nm * z2) + Slab::rnd(nm * sizeof(double)) : 0);
+    JSTSP_REQUIRE(need <= P64_WS_LIMIT, JSTSP_E_UNSUPPORTED, "%s: the float64 workspace would be %.1f GiB (limit 24)", nmf,
+                  (double)need / (double)((size_t)1 << 30));
+    hipStream_t st = ctx->stream;
+    Slab s(st);
+    JSTSP_TRY(s.reserve(need, nmf));
+    McPar *par = s.get<McPar>(batch);
+    JSTSP_TRY(mc64_params(st, batch, tau, rho, par));
+    const double2 *OH = reinterpret_cast<const double2 *>(OH_);
+    const double *Omega = Omega_;
+    double2 *X = reinterpret_cast<double2 *>(X_out);
+    if (host) {
+        double2 *oh = s.get<double2>(nm);
+        double *om = s.get<double>(nm);
+        X = s.get<double2>(nm);
+        JSTSP_HIP(hipMemcpyAsync(oh, OH_, nm * z2, hipMemcpyHostToDevice, st));
+        JSTSP_HIP(hipMemcpyAsync(om, Omega_, nm * sizeof(double), hipMemcpyHostToDevice, st));
+        OH = oh; Omega = om;
+    }
+    double2 *Y = s.get<double2>(nm);
+    Svt64 sv;
+    sv.init(s, Mr, Mt, batch);
+    sv.freeze = true;                       // a trial's bits do not depend on the batch around it, also for 64 < n
+    JSTSP_REQUIRE(Y != nullptr && sv.lam != nullptr, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
+    JSTSP_HIP(hipMemsetAsync(Y, 0, nm * z2, st));                                                      // mc_svt.m:5
+    JSTSP_HIP(hipMemsetAsync(X, 0, nm * z2, st));
+    const dim3 g = mc_grid((long long)nm1, batch);
+    for (int it = 0; it < Imax; ++it) {                                                                // :7
+        JSTSP_TRY(sv.apply(st, Y, &par->thr, (long long)(sizeof(McPar) / sizeof(double)), X));        // :8
+        hipLaunchKernelGGL(mc_svt_update64_kernel, g, dim3(256), 0, st, (long long)nm1, par, Y, OH, Omega, X);     // :9
+        JSTSP_HIP(hipGetLastError());
+    }
+    if (host) JSTSP_HIP(hipMemcpyAsync(X_out, X, nm * z2, hipMemcpyDeviceToHost, st));
+    JSTSP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int jstsp_mc_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Htrue_, const jstsp_c64 *OH_, const double *Omega_, int Imax,
+                      const double *tau, const double *rho, jstsp_c64 *X_out, double *ce_out, int memspace)
+{
+    const char *nmf = "mc_admm (float64)";
+    JSTSP_TRY(mc64_check(ctx, nmf, Mr, Mt, batch, Imax, memspace));
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(OH_ && Omega_ && tau && rho && X_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE(!ce_out || Htrue_, JSTSP_E_NULL, "%s: convergence_error needs Htrue", nmf);
+    const bool host = memspace == JSTSP_HOST, want_ce = ce_out != nullptr;
+    const size_t nm1 = (size_t)Mr * Mt, nm = nm1 * batch, z2 = sizeof(double2), nce = (size_t)batch * std::max(Imax, 1);
+    size_t need = Svt64::bytes(Mr, Mt, batch) + Slab::rnd(batch * sizeof(McPar)) + 3 * Slab::rnd(nm * z2);
+    if (want_ce) need += Slab::rnd(nm * z2) + 2 * Slab::rnd(batch * sizeof(double));
+    if (host) need += 2 * Slab::rnd(nm * z2) + Slab::rnd(nm * sizeof(double)) + (want_ce ? Slab::rnd(nm * z2) + Slab::rnd(nce * sizeof(double)) : 0);
+    JSTSP_REQUIRE(need <= P64_WS_LIMIT, JSTSP_E_UNSUPPORTED, "%s: the float64 workspace would be %.1f GiB (limit 24)", nmf,
+                  (double)need / (double)((size_t)1 << 30));
+    hipStream_t st = ctx->stream;
+    Slab s(st);
+    JSTSP_TRY(s.reserve(need, nmf));
+    McPar *par = s.get<McPar>(batch);
+    JSTSP_TRY(mc64_params(st, batch, tau, rho, par));
+    const double2 *OH = reinterpret_cast<const double2 *>(OH_), *Htrue = reinterpret_cast<const double2 *>(Htrue_);
+    const double *Omega = Omega_;
+    double2 *X = reinterpret_cast<double2 *>(X_out);
+    double *ce = ce_out;
+    if (host) {
+        double2 *oh = s.get<double2>(nm);
+        double *om = s.get<double>(nm);
+        X = s.get<double2>(nm);
+        JSTSP_HIP(hipMemcpyAsync(oh, OH_, nm * z2, hipMemcpyHostToDevice, st));
+        JSTSP_HIP(hipMemcpyAsync(om, Omega_, nm * sizeof(double), hipMemcpyHostToDevice, st));
+        OH = oh; Omega = om;
+        if (want_ce) {
+            double2 *h = s.get<double2>(nm);
+            ce = s.get<double>(nce);
+            JSTSP_HIP(hipMemcpyAsync(h, Htrue_, nm * z2, hipMemcpyHostToDevice, st));
+            Htrue = h;
+        }
+    }
+    double2 *Y = s.get<double2>(nm), *Z = s.get<double2>(nm), *Zn = s.get<double2>(nm);
+    double2 *D = want_ce ? s.get<double2>(nm) : nullptr;
+    double *num = want_ce ? s.get<double>(batch) : nullptr, *den = want_ce ? s.get<double>(batch) : nullptr;
+    Svt64 sv;
+    sv.init(s, Mr, Mt, batch);
+    sv.freeze = true;                       // a trial's bits do not depend on the batch around it, also for 64 < n
+    JSTSP_REQUIRE(Zn != nullptr && sv.lam != nullptr && (!want_ce || den != nullptr), JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
+    for (double2 *p : {X, Y, Z, Zn}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * z2, st));                    // mc_admm.m:6-8
+    if (want_ce) JSTSP_TRY(sv.lambda_max(st, Htrue, den));
+    const dim3 g = mc_grid((long long)nm1, batch);
+    for (int it = 0; it < Imax; ++it) {                                                                // :20
+        JSTSP_TRY(sv.apply(st, Zn, &par->thr, (long long)(sizeof(McPar) / sizeof(double)), X));       // :22
+        hipLaunchKernelGGL(mc_admm_update64_kernel, g, dim3(256), 0, st, (long long)nm1, par, Y, Z, OH, Omega, X, Zn);     // :24-26
+        if (want_ce) {                                                                                 // :28
+            hipLaunchKernelGGL(mc_diff64_kernel, dim3((unsigned)std::min<size_t>((nm + 255) / 256, 4096)), dim3(256), 0, st, (long long)nm, X, Htrue, D);
+            JSTSP_TRY(sv.lambda_max(st, D, num));
+            hipLaunchKernelGGL(mc_ratio64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, num, den, ce);
+        }
+        JSTSP_HIP(hipGetLastError());
+    }
+    if (host) {
+        JSTSP_HIP(hipMemcpyAsync(X_out, X, nm * z2, hipMemcpyDeviceToHost, st));
+        if (want_ce && Imax > 0) JSTSP_HIP(hipMemcpyAsync(ce_out, ce, (size_t)batch * Imax * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    JSTSP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+}  // extern "C"

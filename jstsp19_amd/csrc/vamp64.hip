@@ -88,8 +88,10 @@ __device__ __forceinline__ void pair_of(int n, int r, int s, int &p, int &q)
     p = min(a, b); q = max(a, b);
 }
 
-// rotation of pair s of round r: J = [c, s; -conj(s), c] (c real) with J^H [hpp, hpq; conj(hpq), hqq] J diagonal
-__global__ __launch_bounds__(256) void jacobi64_rot_kernel(int n, int r, const double2 *H, double2 *rot)
+// rotation of pair s of round r: J = [c, s; -conj(s), c] (c real) with J^H [hpp, hpq; conj(hpq), hqq] J diagonal.
+// off != NULL (the sums of jacobi64_off_kernel at the start of this sweep): a matrix that meets the stop criterion on its own is
+// not rotated any more - its result is then the one it has when it is decomposed alone, whatever else the batch holds.
+__global__ __launch_bounds__(256) void jacobi64_rot_kernel(int n, int r, const double2 *H, double2 *rot, const double *off)
 {
     const int t = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     if (s >= n / 2) return;
@@ -100,7 +102,8 @@ __global__ __launch_bounds__(256) void jacobi64_rot_kernel(int n, int r, const d
     const double2 hpq = h[p + (long long)n * q];
     const double a = hypot(hpq.x, hpq.y);
     double c = 1.0; double2 sn = make_double2(0.0, 0.0);
-    if (a > 0.0 && a > 1e-300 * (fabs(hpp) + fabs(hqq))) {
+    const bool settled = off != nullptr && !(off[2 * t] > 1e-28 * off[2 * t + 1]);
+    if (!settled && a > 0.0 && a > 1e-300 * (fabs(hpp) + fabs(hqq))) {
         // real symmetric rotation for [hpp, a; a, hqq] after the phase e = hpq / |hpq| is pulled out
         const double tau = (hqq - hpp) / (2.0 * a);
         const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
@@ -219,7 +222,7 @@ struct Scratch {            // stream-ordered temporaries of one call
 };
 
 // Hermitian eigen-decomposition of nmat matrices of order n0 (G: column-major, ld = n0, stride sG): U (n0 x n0 each), lam (n0 each)
-int eig64(hipStream_t st, Scratch &sc, int n0, int nmat, const double2 *G, long long sG, double2 *U, double *lam)
+int eig64(hipStream_t st, Scratch &sc, int n0, int nmat, const double2 *G, long long sG, double2 *U, double *lam, bool freeze = false)
 {
     if (n0 == 1) {          // (the Kronecker factor of a dense dictionary, Gb = 1: U = 1, lambda = the entry)
         hipLaunchKernelGGL(eig64_order1_kernel, dim3((nmat + 255) / 256), dim3(256), 0, st, nmat, G, sG, U, lam);
@@ -241,7 +244,7 @@ int eig64(hipStream_t st, Scratch &sc, int n0, int nmat, const double2 *G, long 
         for (int t = 0; t < nmat; ++t) done = done && !(hoff[2 * t] > 1e-28 * hoff[2 * t + 1]);      // off-norm <= 1e-14 of the whole (rounding leaves ~ n eps)
         if (done) break;
         for (int r = 0; r < n - 1; ++r) {
-            hipLaunchKernelGGL(jacobi64_rot_kernel, dim3((h2 + 255) / 256, nmat), dim3(256), 0, st, n, r, H, rot);
+            hipLaunchKernelGGL(jacobi64_rot_kernel, dim3((h2 + 255) / 256, nmat), dim3(256), 0, st, n, r, H, rot, freeze ? off : (const double *)nullptr);
             hipLaunchKernelGGL(jacobi64_apply_kernel, dim3((h2 + 15) / 16, (h2 + 15) / 16, nmat), dim3(256), 0, st, n, r, H, V, rot, nmat);
         }
     }
@@ -358,10 +361,10 @@ const double2 *stage64(Scratch &sc, const jstsp_c64 *src, size_t n, int memspace
 }  // namespace
 
 // the Jacobi above for callers outside this file (proposed64.hip, orders above what its in-LDS kernel holds)
-int eig64_global(hipStream_t st, int n, int nmat, const double2 *G, long long sG, double2 *U, double *lam)
+int eig64_global(hipStream_t st, int n, int nmat, const double2 *G, long long sG, double2 *U, double *lam, bool freeze)
 {
     Scratch sc(st);
-    return eig64(st, sc, n, nmat, G, sG, U, lam);
+    return eig64(st, sc, n, nmat, G, sG, U, lam, freeze);
 }
 
 }  // namespace jstsp

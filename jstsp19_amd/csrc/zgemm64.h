@@ -19,7 +19,9 @@ int zgemm64_splits(int m, int n, int k);
 size_t zgemm64_ws_elems(int m, int n, int k, int batch);
 
 // vamp64.hip's global-memory two-sided Jacobi (any order; reads one norm per sweep on the host, so it synchronises the stream):
-// U (n x n each) and lam (n each) of nmat Hermitian matrices G (column-major, leading dimension n, sG elements apart)
-int eig64_global(hipStream_t st, int n, int nmat, const double2 *G, long long sG, double2 *U, double *lam);
+// U (n x n each) and lam (n each) of nmat Hermitian matrices G (column-major, leading dimension n, sG elements apart).
+// The sweeps go on while ANY matrix of the call is above the stop criterion; freeze = true leaves a matrix alone from the sweep
+// on at whose start it meets the criterion itself, so that its bits do not depend on the matrices around it.
+int eig64_global(hipStream_t st, int n, int nmat, const double2 *G, long long sG, double2 *U, double *lam, bool freeze = false);
 
 }  // namespace jstsp

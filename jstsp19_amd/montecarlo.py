@@ -127,7 +127,8 @@ def _times(A, S, P):
     return J.synthesize(S, _eye(S.shape[-2], S) if A is None else A, P)
 
 
-def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_max_order=128, ls_precision="f32"):
+def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_max_order=128, ls_precision="f32",
+                   mmv_precision="f32"):
     """LS, VAMP and MMV-OMP baselines of plot_errorVSsnr.m:73-121 on the conventional-HBF measurement; with
     ``tssr = (Imax, rho)`` also the commented TSSR recipe (:151,158-162) on the proposed scheme's measurement.
     Every product goes through the library (correlate / synthesize entry points), nothing through torch matmuls.
@@ -140,18 +141,23 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
     ``ls_precision="f64"`` (opt-in; the default "f32" is the behaviour above, unchanged): ``pinv(B)``, ``S_ls`` and
     ``Y*pinv(B)`` come from the float64 entries (``jstsp_pinv_f64`` / ``jstsp_ls_f64``: SVD-based, no Gram matrix, any
     factor up to 512 x 8192), the LS column is scored in float64 (``_score_f64``), and the LS and MMV-OMP columns are
-    numbers where the default gives NaN.  The joint OMP itself stays the fp32 kernel (its input is narrowed)."""
+    numbers where the default gives NaN.  With ``mmv_precision="f32"`` the joint OMP itself stays the fp32 kernel (its input is
+    narrowed).
+
+    ``mmv_precision="f64"`` (opt-in, independent of ``ls_precision``): the MMV-OMP column is
+    ``mmv_omp_f64(A_hbf, Y_hbf*pinv_f64(B_hbf), numOfnz)`` and the TSSR / SVT-based columns come from ``tssr_f64`` - float64
+    matrix completion, pinv, products and joint OMP (``jstsp_mc_svt_f64``, ``jstsp_mmv_omp_f64``), at every driver size -
+    and all three are scored in float64 (``_score_f64``).  The default "f32" leaves every column as it was."""
     from . import _lib
     from . import solvers as J
-    if ls_precision not in ("f32", "f64"):
-        raise ValueError("ls_precision must be 'f32' or 'f64'")
+    _check_precisions(ls_precision, mmv_precision)
     zb = J.colmajor(inp["Zbar"].to(torch.complex64))
     ctx = _lib.default_context(inp["Y_hbf"].device.index or 0)
     nan = lambda: torch.full((inp["Y_hbf"].shape[0],), float("nan"), dtype=torch.float64)
     Bh = inp["B_hbf"]
     G2 = Bh.shape[1]
     if ls_precision == "f64":
-        return _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order)
+        return _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision)
     try:
         PB = J.pinv(Bh)                                                                  # pinv(B)  :83, :117
     except J.JstspError as e:
@@ -168,6 +174,9 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
         Gb = _times_h(Bh, Bh)                                                            # (B*B')  :79
         Ym = _times_h(inp["Y_hbf"], Bh)                                                  # Y_hbf*B' :80
         out["vamp"] = _score(J.vamp_kron(Ym, inp["A_hbf"], Gb, 1.0, numOfnz), zb, metric, noise_var)   # :100
+    if mmv_precision == "f64":
+        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr))
+        return out
     Ypb = None
     if PB is not None:
         Ypb = _times(None, inp["Y_hbf"], PB)                                             # Y_hbf_nr*pinv(B)  :117
@@ -209,7 +218,33 @@ def _score_f64(S, zb, metric, noise_var):
     return torch.from_numpy(out)
 
 
-def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order):
+def _check_precisions(ls_precision, mmv_precision):
+    if ls_precision not in ("f32", "f64"):
+        raise ValueError("ls_precision must be 'f32' or 'f64'")
+    if mmv_precision not in ("f32", "f64"):
+        raise ValueError("mmv_precision must be 'f32' or 'f64'")
+
+
+def _mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB=None):
+    """The MMV-OMP column and, with ``tssr = (Imax, rho)``, the TSSR and SVT-based columns in float64
+    (``mmv_precision="f64"``); ``PB``: ``pinv_f64(B_hbf)`` where the caller has it."""
+    from . import solvers as J
+    wide = lambda x: x.to(torch.complex128)
+    Bh, Ah, Yh = inp["B_hbf"], inp["A_hbf"], inp["Y_hbf"]
+    if PB is None:
+        PB = J.pinv_f64(wide(Bh))                                                        # pinv(B)  :117
+    eye = J.colmajor(torch.eye(Yh.shape[-2], dtype=torch.complex128, device=Yh.device))
+    Z, _, _ = J.mmv_omp_f64(wide(Ah), J.synthesize_f64(wide(Yh), eye, PB), numOfnz)      # :116-117
+    out = {"omp_mmv": _score_f64(Z, inp["Zbar"], metric, noise_var)}
+    if tssr is not None:
+        St, _, Ssvt = J.tssr_f64(inp["subY"], inp["Omega"], inp["A"], inp["B"], tssr[0], inp["tau_Y"].numpy(), tssr[1],
+                                 2 * numOfnz)                                            # :151,:160-161
+        out["tssr"] = _score_f64(St, inp["Zbar"], metric, noise_var)
+        out["svt"] = _score_f64(Ssvt, inp["Zbar"], metric, noise_var)                    # :152-153
+    return out
+
+
+def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision="f32"):
     """``_hip_baselines`` with the least-squares pieces in float64 (``ls_precision="f64"``)."""
     from . import solvers as J
     zb = J.colmajor(inp["Zbar"].to(torch.complex64))
@@ -223,6 +258,9 @@ def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order):
         Gb = _times_h(Bh, Bh)                                                            # (B*B')  :79
         Ym = _times_h(Yh, Bh)                                                            # Y_hbf*B' :80
         out["vamp"] = _score(J.vamp_kron(Ym, Ah, Gb, 1.0, numOfnz), zb, metric, noise_var)   # :100
+    if mmv_precision == "f64":
+        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB))
+        return out
     eye = J.colmajor(torch.eye(Yh.shape[-2], dtype=torch.complex128, device=Yh.device))
     Ypb = J.synthesize_f64(wide(Yh), eye, PB).to(torch.complex64)                        # Y_hbf_nr*pinv(B)  :117
     Z, _, _ = J.mmv_omp(Ah, Ypb, numOfnz)                                                # :116-117
@@ -300,7 +338,7 @@ def _merge_cap(p, batch, with_hbf):
 
 def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=None, solve_fn=None, dist=None,
                baselines=False, numOfnz=100, builder=None, metric="nmse", tssr=None, merge=True, vamp_max_order=128,
-               samples=None, ls_precision="f32"):
+               samples=None, ls_precision="f32", mmv_precision="f32"):
     """Mean capped NMSE per sweep point; columns (proposed_algorithm, proposed_algorithm_angles[, LS, VAMP, MMV-OMP
     [, TSSR]]).  ``metric="rate"``: the rate of plot_rateVSframelength.m:81 instead of the NMSE (HIP solvers only).
     ``tssr=(Imax_svt, rho_svt)`` adds the commented recipes of plot_errorVSsnr.m:151-162 as columns six and seven: TSSR
@@ -318,10 +356,11 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
     before averaging (what plot_errorVSsnr.m:138-141 computes per realisation) - for distributional checks.
     ``ls_precision="f64"``: the LS column, and the ``Y*pinv(B)`` in front of the MMV-OMP column, from the float64
     least-squares entries (see ``_hip_baselines``); the default "f32" leaves every column as it was.
+    ``mmv_precision="f64"``: the MMV-OMP, TSSR and SVT-based columns from the float64 entries (``mmv_omp_f64``, ``tssr_f64``),
+    scored in float64 - numbers also where the fp32 chain refuses the size of ``B``; the default "f32" changes nothing.
     Returns a float64 tensor (len(points), ncol) identical on every rank.
     """
-    if ls_precision not in ("f32", "f64"):
-        raise ValueError("ls_precision must be 'f32' or 'f64'")
+    _check_precisions(ls_precision, mmv_precision)
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     if device is None:
@@ -365,7 +404,7 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
         e, ea = solve_fn(inp, Imax) if custom else solve_fn(inp, Imax, p.noise_var)
         cols = [torch.as_tensor(e).double().cpu(), torch.as_tensor(ea).double().cpu()]
         if baselines:
-            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order, ls_precision)
+            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order, ls_precision, mmv_precision)
             for key in ("ls", "vamp", "omp_mmv", "tssr", "svt")[:ncol - 2]:
                 cols.append(b[key].double().cpu() if key in b else torch.full((total,), float("nan"), dtype=torch.float64))
         o = 0

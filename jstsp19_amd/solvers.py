@@ -30,7 +30,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
            "empty_colmajor", "beamformer", "ase", "singular_values",
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
-           "pinv_f64", "ls_estimate_f64"]
+           "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -933,3 +933,73 @@ def ls_estimate_f64(Y, A, B, *, info=False, ctx=None):
                               a_B.ptr, _shared_stride(a_B, G2 * M, batch, "B"), p, prc, mem), "jstsp_ls_f64")
     S = f(not a_Y.batched)
     return (S, rc) if info else S
+
+
+def mmv_omp_f64(A, Y, K, *, norm="l2", ctx=None):
+    """:func:`mmv_omp` in float64 on the device (include/jstsp.h: jstsp_mmv_omp_f64): residual, basis, scores, least squares
+    and ``Z`` are doubles, nothing is narrowed.  complex64 inputs are widened exactly; ``Z`` is complex128, where the inputs
+    live.  Returns (Z (Gr, S), support (1-based atoms in selection order, 0 beyond the count), count)."""
+    a_A, a_Y = _Arg(_wide(A), np.complex128, "A"), _Arg(_wide(Y), np.complex128, "Y")
+    batch, N, S, Gr = a_Y.batch, a_Y.R, a_Y.C, a_A.C
+    if a_A.R != N:
+        raise ValueError("size(A,1) must equal size(Y,1)")
+    if norm not in ("l2", "l1"):
+        raise ValueError("norm must be 'l2' or 'l1'")
+    c, mem, dev = _ctx_for([a_A, a_Y], ctx)
+    pz, fz = _out(mem == DEVICE, batch, Gr, S, np.complex128, dev)
+    pi, fi = _out(mem == DEVICE, batch, int(K), 1, np.int32, dev)
+    pc, fc = _out(mem == DEVICE, batch, 1, 1, np.int32, dev)
+    check(c._lib.jstsp_mmv_omp_f64(c.handle, N, Gr, S, batch, a_A.ptr, _shared_stride(a_A, N * Gr, batch, "A"), a_Y.ptr,
+                                   int(K), 1 if norm == "l1" else 2, pz, pi, pc, mem), "jstsp_mmv_omp_f64")
+    sq = not a_Y.batched
+    return fz(sq), fi(sq)[..., 0], fc(sq)[..., 0, 0]
+
+
+def mc_svt_f64(OH, Omega, Imax, tau, rho, *, ctx=None):
+    """benchmark_algorithms/mc_svt.m:1 in float64 on the device (jstsp_mc_svt_f64); complex128 out."""
+    a_O, a_om = _Arg(_wide(OH), np.complex128, "OH"), _Arg(_wide(Omega, real=True), np.float64, "Omega")
+    if (a_om.batch, a_om.R, a_om.C) != (a_O.batch, a_O.R, a_O.C):
+        raise ValueError("Omega must have the shape of OH")
+    c, mem, dev = _ctx_for([a_O, a_om], ctx)
+    t, pt = _scalars(tau, a_O.batch, "tau")
+    r, pr = _scalars(rho, a_O.batch, "rho")
+    p, f = _out(mem == DEVICE, a_O.batch, a_O.R, a_O.C, np.complex128, dev)
+    check(c._lib.jstsp_mc_svt_f64(c.handle, a_O.R, a_O.C, a_O.batch, a_O.ptr, a_om.ptr, int(Imax), pt, pr, p, mem),
+          "jstsp_mc_svt_f64")
+    return f(not a_O.batched)
+
+
+def mc_admm_f64(Htrue, OH, Omega, Imax, tau, rho, *, want_ce=True, ctx=None):
+    """benchmark_algorithms/mc_admm.m:1 in float64 on the device (jstsp_mc_admm_f64) - returns (X complex128,
+    convergence_error (batch, Imax) float64, ``None`` with ``want_ce=False``: ``Htrue`` may then be ``None``)."""
+    a_H = _Arg(_wide(Htrue) if want_ce else None, np.complex128, "Htrue", allow_none=not want_ce)
+    a_O, a_om = _Arg(_wide(OH), np.complex128, "OH"), _Arg(_wide(Omega, real=True), np.float64, "Omega")
+    if (a_om.batch, a_om.R, a_om.C) != (a_O.batch, a_O.R, a_O.C) or (want_ce and (a_H.batch, a_H.R, a_H.C) != (a_O.batch, a_O.R, a_O.C)):
+        raise ValueError("Omega and Htrue must have the shape of OH")
+    c, mem, dev = _ctx_for([a_H, a_O, a_om], ctx)
+    t, pt = _scalars(tau, a_O.batch, "tau")
+    r, pr = _scalars(rho, a_O.batch, "rho")
+    p, f = _out(mem == DEVICE, a_O.batch, a_O.R, a_O.C, np.complex128, dev)
+    pce, fce = _out(mem == DEVICE, a_O.batch, int(Imax), 1, np.float64, dev) if want_ce else (None, None)
+    check(c._lib.jstsp_mc_admm_f64(c.handle, a_O.R, a_O.C, a_O.batch, a_H.ptr, a_O.ptr, a_om.ptr, int(Imax), pt, pr, p, pce,
+                                   mem), "jstsp_mc_admm_f64")
+    sq = not a_O.batched
+    return f(sq), (fce(sq)[..., 0] if want_ce else None)
+
+
+def tssr_f64(Y_prop, Omega, A, B, Imax, tau, rho, K, *, norm="l2", ctx=None):
+    """:func:`tssr` in float64 on the device, at every driver size (``pinv_f64`` has no in-LDS limit): returns
+    (S_tssr, Y_svt, S_svt) as complex128 with ``Y_svt = mc_svt_f64(...)``, ``S_svt = pinv(A)*Y_svt*pinv(B)`` from
+    ``ls_estimate_f64`` and ``S_tssr`` the float64 joint OMP of ``Y_svt*pinv_f64(B)`` on ``A``."""
+    Y_svt = mc_svt_f64(Y_prop, Omega, Imax, tau, rho, ctx=ctx)
+    PB = pinv_f64(B, ctx=ctx)
+    n = Y_svt.shape[-2]
+    if _is_torch(Y_svt):
+        import torch
+        eye = colmajor(torch.eye(n, dtype=torch.complex128, device=Y_svt.device))
+    else:
+        eye = np.eye(n, dtype=np.complex128)
+    T = synthesize_f64(Y_svt, eye, PB, ctx=ctx)               # Y_svt*pinv(B)  (:160)
+    S_svt = ls_estimate_f64(Y_svt, A, B, ctx=ctx)             # pinv(A)*Y_svt*pinv(B)  (:151)
+    Z, _, _ = mmv_omp_f64(A, T, K, norm=norm, ctx=ctx)
+    return Z, Y_svt, S_svt

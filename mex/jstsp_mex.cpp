@@ -376,6 +376,63 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const int rcode = jstsp_ls_f64(g_ctx, dy.r, dy.c, da.c, db.r, dy.b, Y, A, sA, B, sB, c64(plhs[0]), rc ? mxGetDoubles(rc) : nullptr, JSTSP_HOST);
         if (rcode) fail("jstsp_ls_f64", rcode);
         if (rc) plhs[1] = rc;
+    } else if (!strcmp(fn, "mmv_omp_f64")) {
+        // [Z, support, count] = mmv_omp_f64(A, K, Y [, pnorm]): joint OMP in float64 (jstsp_mmv_omp_f64); pages of Y = batch, A shared (one
+        // page) or one per page; pnorm 2 (default) or 1; support: K x batch int32 (1-based, 0 beyond the count), count: batch x 1 int32
+        check_nargs(fn, nrhs, 3, 4, nlhs, 3);
+        const Dims da = dims_of(in[0]), dy = dims_of(in[2]);
+        const int K = (int)mxGetScalar(in[1]), pnorm = nrhs - 1 >= 4 ? (int)mxGetScalar(in[3]) : 2;
+        if (dy.r != da.r) mexErrMsgIdAndTxt("jstsp:shape", "mmv_omp_f64: size(Y,1) must equal size(A,1)");
+        if (K < 1) mexErrMsgIdAndTxt("jstsp:args", "mmv_omp_f64: K must be >= 1");
+        if (pnorm != 1 && pnorm != 2) mexErrMsgIdAndTxt("jstsp:args", "mmv_omp_f64: pnorm must be 1 or 2");
+        const jstsp_c64 *A = cplx(in[0], fn, "A"), *Y = cplx(in[2], fn, "Y");
+        const long long sA = dict_stride(da, dy.b, fn, "A");
+        ensure_ctx();
+        plhs[0] = new_complex(da.c, dy.c, dy.b);
+        const mwSize di[2] = {(mwSize)K, (mwSize)dy.b}, dc[2] = {(mwSize)dy.b, 1};
+        mxArray *ix = nlhs >= 2 ? mxCreateNumericArray(2, di, mxINT32_CLASS, mxREAL) : nullptr;
+        mxArray *cn = nlhs >= 3 ? mxCreateNumericArray(2, dc, mxINT32_CLASS, mxREAL) : nullptr;
+        const int rc = jstsp_mmv_omp_f64(g_ctx, da.r, da.c, dy.c, dy.b, A, sA, Y, K, pnorm, c64(plhs[0]), ix ? (int32_t *)mxGetData(ix) : nullptr,
+                                         cn ? (int32_t *)mxGetData(cn) : nullptr, JSTSP_HOST);
+        if (rc) fail("jstsp_mmv_omp_f64", rc);
+        if (ix) plhs[1] = ix;
+        if (cn) plhs[2] = cn;
+    } else if (!strcmp(fn, "mc_svt_f64")) {
+        // X = mc_svt_f64(OH, Omega, Imax, tau, rho): mc_svt.m:1 in float64 (jstsp_mc_svt_f64); pages = batch
+        check_nargs(fn, nrhs, 5, 5, nlhs, 1);
+        const Dims d = dims_of(in[0]), dom = dims_of(in[1]);
+        if (dom.r != d.r || dom.c != d.c || dom.b != d.b) mexErrMsgIdAndTxt("jstsp:shape", "mc_svt_f64: Omega must have the shape of OH");
+        const jstsp_c64 *OH = cplx(in[0], fn, "OH");
+        const double *Om = real_of(in[1], fn, "Omega");
+        const int Imax = (int)mxGetScalar(in[2]);
+        if (Imax < 0) mexErrMsgIdAndTxt("jstsp:args", "mc_svt_f64: Imax must be >= 0");
+        const double *tau = scalars(in[3], d.b, fn, "tau"), *rho = scalars(in[4], d.b, fn, "rho");
+        ensure_ctx();
+        plhs[0] = new_complex(d.r, d.c, d.b);
+        const int rc = jstsp_mc_svt_f64(g_ctx, d.r, d.c, d.b, OH, Om, Imax, tau, rho, c64(plhs[0]), JSTSP_HOST);
+        if (rc) fail("jstsp_mc_svt_f64", rc);
+    } else if (!strcmp(fn, "mc_admm_f64")) {
+        // [X, convergence_error] = mc_admm_f64(Htrue, OH, Omega, Imax, tau, rho): mc_admm.m:1 in float64 (jstsp_mc_admm_f64); pages = batch;
+        // with one output the error curve is not computed and Htrue may be []
+        check_nargs(fn, nrhs, 6, 6, nlhs, 2);
+        const Dims d = dims_of(in[1]), dom = dims_of(in[2]);
+        const bool want_ce = nlhs >= 2;
+        if (dom.r != d.r || dom.c != d.c || dom.b != d.b) mexErrMsgIdAndTxt("jstsp:shape", "mc_admm_f64: Omega must have the shape of OH");
+        if (want_ce || !mxIsEmpty(in[0])) {
+            const Dims dh = dims_of(in[0]);
+            if (dh.r != d.r || dh.c != d.c || dh.b != d.b) mexErrMsgIdAndTxt("jstsp:shape", "mc_admm_f64: Htrue must have the shape of OH");
+        }
+        const jstsp_c64 *H = want_ce ? cplx(in[0], fn, "Htrue") : nullptr, *OH = cplx(in[1], fn, "OH");
+        const double *Om = real_of(in[2], fn, "Omega");
+        const int Imax = (int)mxGetScalar(in[3]);
+        if (Imax < 1) mexErrMsgIdAndTxt("jstsp:args", "mc_admm_f64: Imax must be >= 1");
+        const double *tau = scalars(in[4], d.b, fn, "tau"), *rho = scalars(in[5], d.b, fn, "rho");
+        ensure_ctx();
+        plhs[0] = new_complex(d.r, d.c, d.b);
+        mxArray *ce = want_ce ? new_real(Imax, 1, d.b) : nullptr;
+        const int rc = jstsp_mc_admm_f64(g_ctx, d.r, d.c, d.b, H, OH, Om, Imax, tau, rho, c64(plhs[0]), ce ? mxGetDoubles(ce) : nullptr, JSTSP_HOST);
+        if (rc) fail("jstsp_mc_admm_f64", rc);
+        if (ce) plhs[1] = ce;
     } else if (!strcmp(fn, "nmse") || !strcmp(fn, "rate")) {
         // nmse(S, Zbar): min(1, norm(S-Zbar)^2/norm(Zbar)^2)  plot_errorVSsnr.m:138-141 (one value per page)
         // rate(S, Zbar, noise_var): log2(real(det(eye(Nr) + 1/Nr*Zbar*Zbar'/(noise_var + nmse))))  plot_rateVSframelength.m:81

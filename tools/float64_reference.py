@@ -6,7 +6,8 @@ configs[3] sweep x `--trials` realisations, `--bench-trials` of the bench worklo
 proposed_algorithm_angles), same options for seed, SNR points, trials and groups, and the same `fixture.npz` layout
 (`<group>/snr_db`, `sweep_idx`, `trial`, `fingerprint`, `nmse_port`, `ce_port`, `seed`), so that
 tests/golden/make_fullsize_port_fixture.py reads its output unchanged.  `--ls` adds the LS column in float64 per trial
-(`S_ls`, `nmse_ls`: `pinv(A_hbf)*Y_hbf*pinv(B_hbf)` by jstsp_ls_f64).  The host port needs 5-6 core-seconds per trial; this
+(`S_ls`, `nmse_ls`: `pinv(A_hbf)*Y_hbf*pinv(B_hbf)` by jstsp_ls_f64), `--tssr IMAX,RHO` the TSSR and SVT-based columns
+(`S_tssr`, `S_svt`, `nmse_tssr`, `nmse_svt` by tssr_f64: jstsp_mc_svt_f64, jstsp_pinv_f64, jstsp_mmv_omp_f64).  The host port needs 5-6 core-seconds per trial; this
 needs milliseconds.  It does not replace parity_tail.py (which measures the fp32 path against the host port) and the committed
 fixtures are not regenerated from it.
 
@@ -52,6 +53,8 @@ def main():
     ap.add_argument("--no-ce", action="store_true", help="skip convergence_error (ce_port is then absent from the fixture)")
     ap.add_argument("--ls", action="store_true", help="also the float64 least-squares estimate pinv(A_hbf)*Y_hbf*pinv(B_hbf) per trial "
                     "(jstsp_ls_f64): S_ls (complex128, Gr x G2 per trial) and nmse_ls in the fixture")
+    ap.add_argument("--tssr", type=str, default="", metavar="IMAX,RHO", help="also the float64 TSSR recipe of plot_errorVSsnr.m:151-162 per trial "
+                    "(tssr_f64 with K = 200): S_tssr, S_svt (complex128, Gr x G2 per trial), nmse_tssr and nmse_svt in the fixture")
     ap.add_argument("--host-port", type=int, default=0, help="also solve this many trials with oracle/cpu_port.cpp and compare")
     ap.add_argument("--threads", type=int, default=16, help="threads of the host port")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "build", "f64_reference"),
@@ -108,6 +111,12 @@ def main():
             Sl = J.ls_estimate_f64(wide(inp["Y_hbf"]), wide(inp["A_hbf"]), wide(inp["B_hbf"])).cpu().numpy()
             rec["S_ls"] = np.ascontiguousarray(Sl)
             rec["nmse_ls"] = np.array([O.nmse_capped(Sl[t], zb[t]) for t in range(cnt)])
+        if a.tssr:                                  # plot_errorVSsnr.m:151-162 on the proposed scheme's measurement, nothing narrowed
+            ti, tr = a.tssr.split(",")
+            St, _, Sv = J.tssr_f64(inp["subY"], inp["Omega"], inp["A"], inp["B"], int(ti), inp["tau_Y"].numpy(), float(tr), 200)
+            for nm_, Sx in (("tssr", St.cpu().numpy()), ("svt", Sv.cpu().numpy())):
+                rec["S_" + nm_] = np.ascontiguousarray(Sx)
+                rec["nmse_" + nm_] = np.array([O.nmse_capped(Sx[t], zb[t]) for t in range(cnt)])
         for k, v in rec.items():
             g.setdefault(k, []).append(v)
         if n == 0 and a.host_port > 0:

@@ -13,6 +13,7 @@ ap.add_argument("name")
 ap.add_argument("--trials", type=int, default=None, help="default: the driver's own maxMCRealizations")
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--ls-f64", action="store_true", help="LS and Y*pinv(B) of the baseline columns from the float64 entries (jstsp_pinv_f64 / jstsp_ls_f64)")
+ap.add_argument("--mmv-f64", action="store_true", help="MMV-OMP, TSSR and SVT-based baseline columns from the float64 entries (jstsp_mmv_omp_f64 / jstsp_mc_svt_f64)")
 a = ap.parse_args()
 t0 = time.perf_counter()
 if a.name == "errorVSadmmiters":
@@ -34,7 +35,8 @@ elif a.name == "errorVSzy":
 else:
     d = mc.driver(a.name)
     n = a.trials or d["n_trials"]
-    out = mc.run_driver(a.name, n, batch=min(a.batch, n), ls_precision="f64" if a.ls_f64 else "f32")
+    out = mc.run_driver(a.name, n, batch=min(a.batch, n), ls_precision="f64" if a.ls_f64 else "f32",
+                        mmv_precision="f64" if a.mmv_f64 else "f32")
     torch.cuda.synchronize()
     print("%s (%s), %d trials/point, %.1f s" % (a.name, d["metric"], n, time.perf_counter() - t0))
     print("%-8s proposed  +angles   LS        VAMP      MMV-OMP" % d["axis"])
