@@ -813,6 +813,56 @@ int jstsp_mc_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64
                       const double *Omega, int Imax, const double *tau, const double *rho,
                       jstsp_c64 *X_out, double *ce_out, int memspace);
 
+/* ---- OMP (dense and Kronecker) and sparse_admm in float64 -------------------------------------------
+ * OMP.m:1-32 and sparse_admm.m:1-36 evaluated in FLOAT64 on the device - unlike jstsp_omp_c64 / jstsp_sparse_admm_c64, which narrow
+ * the same arrays to the fp32 kernels.  Arguments, layouts, NULL-able outputs (target_out; ce_out, with which Htrue may be NULL), both
+ * memspaces and the error codes are those of jstsp_omp_c64 / jstsp_omp_kron_c32 / jstsp_sparse_admm_c64; every stored value and every
+ * sum is a double.  No atomics and every sum in a fixed order: a repeated call returns the same bits, and a problem's result does not
+ * depend on its batch mates, on whether a dictionary is shared (stride 0) or on the memspace.  The device reference for the fp32
+ * selection contract of jstsp_omp_c32, and the float64 OMP column of tools/run_time_comparison.py --omp-f64.
+ * jstsp_omp_f64 / jstsp_omp_kron_f64 (csrc/omp64.hip): exactly m iterations, chosen atoms are not excluded, x = pinv(targetMatrix) v.
+ *   Measurement space: an orthonormal basis of the distinct selected atoms (two passes of classical Gram-Schmidt per atom), the
+ *   triangular factor, one back-substitution at the end; launches per iteration for the whole batch, nothing read back on the host.
+ *   Correlation: dense - one wave per atom, four real fma chains joined at the end; Kronecker - Af^H R Bf^H by two f64-MFMA products
+ *   (what jstsp_correlate_f64 computes), Phi is never formed.
+ *   Selection: the score is |c|^2 as a sum of two rounded squares; the first index among equal scores, a NaN never wins.  Columns
+ *   equal to column j, to -column j or to +-1i column j score bit-equal (dense), and so do the atoms built on equal or negated rows
+ *   of Bf (Kronecker).  A selection whose float64 relative gap to the runner-up is >= 1e-9, or exactly 0, is the one of
+ *   oracle/solvers.py omp_literal on the same values; x_hat is then within 1e-12 of it relative to max|x_hat|.
+ *   Re-selection: an index already in the index set leaves span and residual unchanged; its coefficient is split equally over its
+ *   copies and x_hat keeps the last one (OMP.m:29-32), as jstsp_omp_c32 does.  A new index whose atom lies in the span of the chosen
+ *   ones (||a - Q Q' a||^2 <= 1e-20 ||a||^2, or a = 0) adds nothing and keeps the coefficient 0.  v = 0 gives all ones, x_hat = 0.
+ *   target_out: the selected columns, bit-equal to A's.
+ *   Scale: each problem is solved on v * 2^-e, e the exponent of the largest finite component of v (frexp / ldexp), and x_hat is
+ *   scaled back by 2^e: index sets do not depend on the scale of v, and x_hat of v * 2^k is x_hat * 2^k bit for bit (tested: k =
+ *   +-70, +-100, +-400).  A NaN or Inf in a problem's v ends that problem with status 0 and arbitrary indices in [1, size_d]; its
+ *   batch mates are not affected.
+ *   Limits (JSTSP_E_UNSUPPORTED): m <= 1024; measures (N M) <= 65536; size_d (Gr G2) <= 1048576; batch <= 65535; a float64
+ *   workspace (about 16 measures m bytes per problem) above 24 GiB - the message names the largest batch that fits.  As in the fp32
+ *   entries m is not limited by measures or size_d.  JSTSP_DEVICE calls are asynchronous on the context's stream.
+ * jstsp_sparse_admm_f64 (csrc/sparse_admm64.hip): the structured form of jstsp_sparse_admm_c32 - factor Grams by the f64-MFMA GEMM,
+ *   their eigen-decompositions once per call by the float64 Jacobi (in LDS up to order 64, in global memory above), A'OH once, per
+ *   iteration one element-wise kernel (V = R + Z/rho, soft threshold, RHS), four products around the divide by lr lt^T - rho, and
+ *   Z += rho (R - S).  rho = 0.01 and tau_s = 1e-4 in double.  ce_out: Imax x batch, sigma_max(Dr S Dt^H - Htrue)^2 /
+ *   sigma_max(Htrue)^2, not capped.  Gr == Mr and Gt == Mt (JSTSP_E_SHAPE otherwise); max(Mr, Mt) <= 512 and batch <= 65535, else
+ *   JSTSP_E_UNSUPPORTED; Imax = 0 returns zeros.  A denominator lr lt - rho that is exactly 0 gives what IEEE gives (the reference's
+ *   singular B \), not an error.  A non-finite eigenvalue of a factor Gram - a NaN or Inf in Dr / Dt - returns JSTSP_E_ILLCOND before
+ *   the first iteration.  The call synchronises the context's stream (the eigenvalues are checked on the host; with ce_out and
+ *   64 < min(Mr, Mt) also once per Jacobi sweep), in both memspaces.
+ * Asserted (tests/test_gpu_omp64.py, test_gpu_sparse_admm64.py): every index set equal to the oracle's on the engineered rows of
+ * tests/omp_problems.py and tests/omp64_problems.py, x_hat within 1e-12 of max|x_ref|; S within 1e-10 of max|S_ref| and
+ * convergence_error within 1e-8 of oracle/solvers.py sparse_admm (measured values: DESIGN.md section 9f,
+ * profiles/omp64_measured_tolerances.json). */
+int jstsp_omp_f64(jstsp_ctx *ctx, int measures, int size_d, int batch,
+                  const jstsp_c64 *A, long long strideA, const jstsp_c64 *v, int m,
+                  jstsp_c64 *x_hat, int32_t *index_out, jstsp_c64 *target_out, int memspace);
+int jstsp_omp_kron_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                       const jstsp_c64 *Af, long long strideA, const jstsp_c64 *Bf, long long strideB,
+                       const jstsp_c64 *y, int m, jstsp_c64 *x_hat, int32_t *index_out, int memspace);
+int jstsp_sparse_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int Gt, int batch,
+                          const jstsp_c64 *Htrue, const jstsp_c64 *OH, const jstsp_c64 *Dr,
+                          const jstsp_c64 *Dt, int Imax, jstsp_c64 *S_out, double *ce_out, int memspace);
+
 /* Per-kernel timing of the last proposed_algorithm call made with profiling enabled:
  * jstsp_set_profiling(ctx, 1) brackets every launch of the dominant kernel with HIP
  * events on the context's stream; jstsp_get_profile() returns launches and total ms. */

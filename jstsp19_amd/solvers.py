@@ -30,7 +30,8 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
            "empty_colmajor", "beamformer", "ase", "singular_values",
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
-           "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64"]
+           "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
+           "OMP_f64", "omp_kron_f64", "sparse_admm_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1003,3 +1004,94 @@ def tssr_f64(Y_prop, Omega, A, B, Imax, tau, rho, K, *, norm="l2", ctx=None):
     S_svt = ls_estimate_f64(Y_svt, A, B, ctx=ctx)             # pinv(A)*Y_svt*pinv(B)  (:151)
     Z, _, _ = mmv_omp_f64(A, T, K, norm=norm, ctx=ctx)
     return Z, Y_svt, S_svt
+
+
+def _vec3(v):
+    """a vector (n,) or a batch of vectors (batch, n) as (batch, n, 1), column-major for torch: (array, single)."""
+    single = v.ndim == 1
+    v3 = v.reshape(1, -1, 1) if single else v.reshape(v.shape[0], -1, 1)
+    return (colmajor(v3) if _is_torch(v) else v3), single
+
+
+def OMP_f64(A, v, m, snr=None, *, want_target=True, ctx=None):
+    """:func:`OMP` in float64 on the device (include/jstsp.h: jstsp_omp_f64): residual, basis, correlations, scores and the
+    least squares are doubles, nothing is narrowed.  Same arguments; complex64 inputs are widened exactly, ``x_hat`` and
+    ``targetMatrix`` are complex128, where the inputs live.  A batch whose float64 workspace would exceed the library's limit
+    is solved in chunks.  Returns (x_hat, indexSet, v, targetMatrix)."""
+    a_A = _Arg(_wide(A), np.complex128, "A")
+    v3, single = _vec3(_wide(v))
+    a_v = _Arg(v3, np.complex128, "v")
+    batch, meas, size_d, m = a_v.batch, a_A.R, a_A.C, int(m)
+    if a_v.R != meas:
+        raise ValueError("length(v) must equal size(A,1)")
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    sA = _shared_stride(a_A, meas * size_d, batch, "A")
+    c, mem, dev = _ctx_for([a_A, a_v], ctx)
+    px, fx = _out(mem == DEVICE, batch, size_d, 1, np.complex128, dev)
+    pi, fi = _out(mem == DEVICE, batch, m, 1, np.int32, dev)
+    pt, ft = _out(mem == DEVICE, batch, meas, m, np.complex128, dev) if want_target else (None, None)
+    # bytes of float64 state per problem (csrc/omp64.hip): residual, basis, triangular factor, correlations, staged copies
+    per = 16 * (2 * meas + meas * m + m * m + m + 2 * size_d + (meas * size_d if sA else 0) + (meas * m if want_target else 0)) + 16 * m
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    for t0 in range(0, batch, step):
+        nb = min(step, batch - t0)
+        check(c._lib.jstsp_omp_f64(c.handle, meas, size_d, nb, _off(a_A.ptr, t0 * sA, 16), sA, _off(a_v.ptr, t0 * meas, 16), m,
+                                   _off(px, t0 * size_d, 16), _off(pi, t0 * m, 4), _off(pt, t0 * meas * m, 16), mem), "jstsp_omp_f64")
+    return fx(single)[..., 0], fi(single)[..., 0], v, (ft(single) if want_target else None)
+
+
+def omp_kron_f64(Af, Bf, y, m, *, ctx=None):
+    """:func:`omp_kron` in float64 on the device (jstsp_omp_kron_f64): OMP.m on ``kron(Bf.', Af)`` given by its factors, the
+    correlation ``Af' R Bf'`` on the f64 matrix pipe; complex128 out.  Returns (x_hat (Gr*G2), indexSet (1-based))."""
+    a_A, a_B = _Arg(_wide(Af), np.complex128, "Af"), _Arg(_wide(Bf), np.complex128, "Bf")
+    y3, single = _vec3(_wide(y))
+    a_y = _Arg(y3, np.complex128, "y")
+    batch, N, Gr, G2, M, m = a_y.batch, a_A.R, a_A.C, a_B.R, a_B.C, int(m)
+    if a_y.R != N * M:
+        raise ValueError("length(y) must be N*M")
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    sA, sB = _shared_stride(a_A, N * Gr, batch, "Af"), _shared_stride(a_B, G2 * M, batch, "Bf")
+    c, mem, dev = _ctx_for([a_A, a_B, a_y], ctx)
+    px, fx = _out(mem == DEVICE, batch, Gr * G2, 1, np.complex128, dev)
+    pi, fi = _out(mem == DEVICE, batch, m, 1, np.int32, dev)
+    per = 16 * (2 * N * M + N * M * m + m * m + m + 2 * Gr * G2 + 17 * Gr * M + sA + sB) + 16 * m
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    for t0 in range(0, batch, step):
+        nb = min(step, batch - t0)
+        check(c._lib.jstsp_omp_kron_f64(c.handle, N, M, Gr, G2, nb, _off(a_A.ptr, t0 * sA, 16), sA, _off(a_B.ptr, t0 * sB, 16), sB,
+                                        _off(a_y.ptr, t0 * N * M, 16), m, _off(px, t0 * Gr * G2, 16), _off(pi, t0 * m, 4), mem),
+              "jstsp_omp_kron_f64")
+    return fx(single)[..., 0], fi(single)[..., 0]
+
+
+def sparse_admm_f64(Htrue, OH, Dr, Dt, Imax, *, want_ce=True, ctx=None):
+    """:func:`sparse_admm` in float64 on the device (jstsp_sparse_admm_f64) - returns (S complex128, convergence_error
+    (batch, Imax) float64, ``None`` with ``want_ce=False``: ``Htrue`` may then be ``None``).  ``Dr`` and ``Dt`` are square
+    (the reference adds R to Z) and shared by the batch; a NaN or Inf in them raises ``JstspError`` (code -6)."""
+    a_H = _Arg(_wide(Htrue) if want_ce else None, np.complex128, "Htrue", allow_none=not want_ce)
+    a_O = _Arg(_wide(OH), np.complex128, "OH")
+    a_Dr, a_Dt = _Arg(_wide(Dr), np.complex128, "Dr"), _Arg(_wide(Dt), np.complex128, "Dt")
+    if a_Dr.batched or a_Dt.batched:
+        raise ValueError("Dr and Dt are shared by the batch (2-D)")
+    batch, Mr, Mt, Imax = a_O.batch, a_O.R, a_O.C, int(Imax)
+    if (a_Dr.R, a_Dr.C) != (Mr, Mr) or (a_Dt.R, a_Dt.C) != (Mt, Mt):
+        raise ValueError("Dr must be size(OH,1) x size(OH,1) and Dt size(OH,2) x size(OH,2) (sparse_admm.m:21 adds R to Z)")
+    if want_ce and (a_H.batch, a_H.R, a_H.C) != (batch, Mr, Mt):
+        raise ValueError("Htrue must have the shape of OH")
+    if Imax < 0:
+        raise ValueError("Imax must not be negative")
+    c, mem, dev = _ctx_for([a_H, a_O, a_Dr, a_Dt], ctx)
+    p, f = _out(mem == DEVICE, batch, Mr, Mt, np.complex128, dev)
+    pce, fce = _out(mem == DEVICE, batch, Imax, 1, np.float64, dev) if want_ce else (None, None)
+    n = min(Mr, Mt)
+    per = 16 * (10 * Mr * Mt + (6 * n * n + 16 * Mr * Mt if want_ce else 0)) + 8 * Imax
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    for t0 in range(0, batch, step):
+        nb = min(step, batch - t0)
+        check(c._lib.jstsp_sparse_admm_f64(c.handle, Mr, Mt, a_Dr.C, a_Dt.C, nb, _off(a_H.ptr, t0 * Mr * Mt, 16), _off(a_O.ptr, t0 * Mr * Mt, 16),
+                                           a_Dr.ptr, a_Dt.ptr, Imax, _off(p, t0 * Mr * Mt, 16), _off(pce, t0 * Imax, 8), mem),
+              "jstsp_sparse_admm_f64")
+    sq = not a_O.batched
+    return f(sq), (fce(sq)[..., 0] if want_ce else None)

@@ -193,14 +193,16 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         plhs[0] = new_complex(da.c, db.r, dy.b);
         const int rc = jstsp_ls_c64(g_ctx, dy.r, dy.c, da.c, db.r, dy.b, Y, A, sA, B, sB, c64(plhs[0]), JSTSP_HOST);
         if (rc) fail("jstsp_ls_c64", rc);
-    } else if (!strcmp(fn, "OMP")) {
+    } else if (!strcmp(fn, "OMP") || !strcmp(fn, "omp_f64")) {
         // [x_hat, indexSet, v, targetMatrix] = OMP(A, v, m, snr)     benchmark_algorithms/OMP.m:1 (snr is unused there too)
+        // 'omp_f64': the same call evaluated in float64 on the device (jstsp_omp_f64) instead of narrowed to the fp32 kernels
+        const bool f64 = fn[0] == 'o';
         check_nargs(fn, nrhs, 3, 4, nlhs, 4);
         const Dims da = dims_of(in[0]), dv = dims_of(in[1]);
         const int meas = da.r, size_d = da.c, batch = dv.c * dv.b;        // v: measures x 1 (x batch columns)
-        if (dv.r != meas) mexErrMsgIdAndTxt("jstsp:shape", "OMP: size(v,1) must equal size(A,1)");
+        if (dv.r != meas) mexErrMsgIdAndTxt("jstsp:shape", "%s: size(v,1) must equal size(A,1)", fn);
         const int m = (int)mxGetScalar(in[2]);
-        if (m < 1) mexErrMsgIdAndTxt("jstsp:args", "OMP: m must be >= 1");
+        if (m < 1) mexErrMsgIdAndTxt("jstsp:args", "%s: m must be >= 1", fn);
         const jstsp_c64 *A = cplx(in[0], fn, "A"), *v = cplx(in[1], fn, "v");
         const long long sA = da.b == 1 ? 0 : dict_stride(da, batch, fn, "A");
         ensure_ctx();
@@ -208,9 +210,9 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const mwSize di[2] = {(mwSize)m, (mwSize)batch};
         mxArray *ix = mxCreateNumericArray(2, di, mxINT32_CLASS, mxREAL);
         mxArray *T = nlhs >= 4 ? new_complex(meas, m, batch) : nullptr;
-        const int rc = jstsp_omp_c64(g_ctx, meas, size_d, batch, A, sA, v, m, c64(plhs[0]), (int32_t *)mxGetData(ix),
-                                     T ? c64(T) : nullptr, JSTSP_HOST);
-        if (rc) fail("jstsp_omp_c64", rc);
+        const int rc = (f64 ? jstsp_omp_f64 : jstsp_omp_c64)(g_ctx, meas, size_d, batch, A, sA, v, m, c64(plhs[0]), (int32_t *)mxGetData(ix),
+                                                             T ? c64(T) : nullptr, JSTSP_HOST);
+        if (rc) fail(f64 ? "jstsp_omp_f64" : "jstsp_omp_c64", rc);
         if (nlhs >= 2) {                                                  // indexSet: 1 x m cell (OMP.m:9,22), first problem
             plhs[1] = mxCreateCellMatrix(1, m);
             const int32_t *pi = (const int32_t *)mxGetData(ix);
@@ -244,22 +246,24 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs >= 3) plhs[2] = it;
         if (nlhs >= 4) plhs[3] = rs;
         if (nlhs >= 5) plhs[4] = st;
-    } else if (!strcmp(fn, "sparse_admm")) {
+    } else if (!strcmp(fn, "sparse_admm") || !strcmp(fn, "sparse_admm_f64")) {
         // [S, convergence_error] = sparse_admm(Htrue, OH, Dr, Dt, Imax)     benchmark_algorithms/sparse_admm.m:1
+        // 'sparse_admm_f64': the same call evaluated in float64 on the device (jstsp_sparse_admm_f64)
+        const bool f64 = fn[11] != 0;
         check_nargs(fn, nrhs, 5, 5, nlhs, 2);
         const Dims d = dims_of(in[1]), dh = dims_of(in[0]), dr = dims_of(in[2]), dt = dims_of(in[3]);
         if (dh.r != d.r || dh.c != d.c || dh.b != d.b || dr.r != d.r || dt.r != d.c)
-            mexErrMsgIdAndTxt("jstsp:shape", "sparse_admm: inconsistent dimensions");
+            mexErrMsgIdAndTxt("jstsp:shape", "%s: inconsistent dimensions", fn);
         const int Imax = (int)mxGetScalar(in[4]);
-        if (Imax < 1) mexErrMsgIdAndTxt("jstsp:args", "sparse_admm: Imax must be >= 1");
+        if (Imax < 1) mexErrMsgIdAndTxt("jstsp:args", "%s: Imax must be >= 1", fn);
         const jstsp_c64 *H = cplx(in[0], fn, "Htrue"), *OH = cplx(in[1], fn, "OH"), *Dr = cplx(in[2], fn, "Dr"),
                         *Dt = cplx(in[3], fn, "Dt");
         ensure_ctx();
         plhs[0] = new_complex(d.r, d.c, d.b);
         mxArray *ce = new_real(Imax, 1, d.b);
-        const int rc = jstsp_sparse_admm_c64(g_ctx, d.r, d.c, dr.c, dt.c, d.b, H, OH, Dr, Dt, Imax, c64(plhs[0]), mxGetDoubles(ce),
-                                             JSTSP_HOST);
-        if (rc) fail("jstsp_sparse_admm_c64", rc);
+        const int rc = (f64 ? jstsp_sparse_admm_f64 : jstsp_sparse_admm_c64)(g_ctx, d.r, d.c, dr.c, dt.c, d.b, H, OH, Dr, Dt, Imax, c64(plhs[0]),
+                                                                             mxGetDoubles(ce), JSTSP_HOST);
+        if (rc) fail(f64 ? "jstsp_sparse_admm_f64" : "jstsp_sparse_admm_c64", rc);
         if (nlhs >= 2) plhs[1] = ce;
     } else if (!strcmp(fn, "mc_svt")) {
         // X = mc_svt(OH, Omega, Imax, tau, rho)     benchmark_algorithms/mc_svt.m:1

@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--trials", type=int, default=64)
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--seed", type=int, default=20190913)
+ap.add_argument("--omp-f64", action="store_true", help="OMP column from the float64 entry (jstsp_omp_kron_f64) instead of the fp32 kernels")
 a = ap.parse_args()
 p = SweepParams(Nt=4, Nr=32, L=4, T=35, Mr=4, snr_db=5.0)          # :8-24
 K, Imax = 100, 100                                                    # :20, :25
@@ -41,7 +42,10 @@ for rep in range(2):                                                  # the firs
         y = Ym.transpose(1, 2).reshape(b, -1).contiguous()            # vec
         tY, tZ, rho = inp["tau_Y"].numpy(), inp["tau_Z"].numpy(), inp["rho"].numpy()
         timed("ls", lambda: J.ls_estimate(Y, A, B))                   # :79
-        timed("omp", lambda: J.omp_kron(A, Gb, y, K))                 # :83-85
+        if a.omp_f64:
+            timed("omp", lambda: J.omp_kron_f64(A, Gb, y, K))         # :83-85 in float64
+        else:
+            timed("omp", lambda: J.omp_kron(A, Gb, y, K))             # :83-85
         timed("vamp", lambda: J.vamp_kron(Ym, A, Gb, 1.0, K))         # :91
         timed("cosamp", lambda: J.cosamp_kron(A, Gb, y, K))           # :96
         timed("omp_mmv", lambda: J.mmv_omp(A, mc._times(None, Y, J.pinv(B)), K))   # :101-102
@@ -53,5 +57,5 @@ for rep in range(2):                                                  # the firs
     if rep == 0:
         tot = {k: 0.0 for k in tot}
         done = 0
-print(json.dumps({"driver": "plot_time_comparisions", "trials": done, "batch": a.batch,
+print(json.dumps({"driver": "plot_time_comparisions", "trials": done, "batch": a.batch, **({"omp_precision": "f64"} if a.omp_f64 else {}),
                   "seconds_per_trial": {k: v / done for k, v in tot.items()}}))
