@@ -17,6 +17,7 @@
 // the host reads no flag back.  Every sum has a fixed order (the only atomics count histogram bins), so a call repeated is
 // bit-identical, and a problem's result does not depend on the batch it is in.
 #include "solver_common.h"
+#include "ws64.h"
 
 namespace jstsp {
 namespace {
@@ -25,7 +26,6 @@ constexpr int CS_KMAX = 256;          // 3K <= 768 rows: one thread per row of T
 constexpr int CS_DMAX = 65536;        // atoms: the selection's membership bitmap is 8 KiB of LDS
 constexpr double CS_PIVOT = 1e-12;    // rank rule: a Cholesky pivot at or below this times the largest diagonal entry of G(T,T)
 
-__device__ __forceinline__ double2 zmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ double2 zmulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a conj(b)
 __device__ __forceinline__ double2 zsub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ double2 zscale(double2 a, double s) { return make_double2(a.x * s, a.y * s); }

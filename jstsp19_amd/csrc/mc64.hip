@@ -59,21 +59,6 @@ __global__ __launch_bounds__(256) void mc_admm_update64_kernel(long long nm, con
     }
 }
 
-__global__ __launch_bounds__(256) void mc_diff64_kernel(long long n, const double2 *X, const double2 *H, double2 *D)
-{
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const double2 x = X[e], h = H[e];
-        D[e] = make_double2(x.x - h.x, x.y - h.y);
-    }
-}
-
-// ce(it, t) = num[t] / den[t] (IEEE: x / 0 = Inf, 0 / 0 = NaN, as the reference); ce laid out Imax per trial
-__global__ __launch_bounds__(256) void mc_ratio64_kernel(int batch, int Imax, int it, const double *num, const double *den, double *ce)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < batch) ce[(long long)t * Imax + it] = num[t] / den[t];
-}
-
 int mc64_check(jstsp_ctx *ctx, const char *nm, int Mr, int Mt, int batch, int Imax, int memspace)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
@@ -85,14 +70,12 @@ int mc64_check(jstsp_ctx *ctx, const char *nm, int Mr, int Mt, int batch, int Im
     return 0;
 }
 
-// rho and tau / rho of every trial on the device (synchronises: the staging vector is this function's own)
-int mc64_params(hipStream_t st, int batch, const double *tau, const double *rho, McPar *par)
+// rho and tau / rho of every trial
+std::vector<McPar> mc64_params(int batch, const double *tau, const double *rho)
 {
     std::vector<McPar> hp(batch);
     for (int t = 0; t < batch; ++t) hp[t] = McPar{rho[t], tau[t] / rho[t]};
-    JSTSP_HIP(hipMemcpyAsync(par, hp.data(), batch * sizeof(McPar), hipMemcpyHostToDevice, st));
-    JSTSP_HIP(hipStreamSynchronize(st));
-    return 0;
+    return hp;
 }
 
 }  // namespace
@@ -111,31 +94,25 @@ int jstsp_mc_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 
     JSTSP_REQUIRE(OH_ && Omega_ && tau && rho && X_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
     const bool host = memspace == JSTSP_HOST;
     const size_t nm1 = (size_t)Mr * Mt, nm = nm1 * batch, z2 = sizeof(double2);
-    const size_t need = Svt64::bytes(Mr, Mt, batch) + Slab::rnd(batch * sizeof(McPar)) + Slab::rnd(nm * z2) +
-                        (host ? 2 * Slab::rnd(nm * z2) + Slab::rnd(nm * sizeof(double)) : 0);
-    JSTSP_REQUIRE(need <= P64_WS_LIMIT, JSTSP_E_UNSUPPORTED, "%s: the float64 workspace would be %.1f GiB (limit 24)", nmf,
-                  (double)need / (double)((size_t)1 << 30));
     hipStream_t st = ctx->stream;
-    Slab s(st);
-    JSTSP_TRY(s.reserve(need, nmf));
-    McPar *par = s.get<McPar>(batch);
-    JSTSP_TRY(mc64_params(st, batch, tau, rho, par));
-    const double2 *OH = reinterpret_cast<const double2 *>(OH_);
-    const double *Omega = Omega_;
-    double2 *X = reinterpret_cast<double2 *>(X_out);
-    if (host) {
-        double2 *oh = s.get<double2>(nm);
-        double *om = s.get<double>(nm);
-        X = s.get<double2>(nm);
-        JSTSP_HIP(hipMemcpyAsync(oh, OH_, nm * z2, hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(om, Omega_, nm * sizeof(double), hipMemcpyHostToDevice, st));
-        OH = oh; Omega = om;
-    }
-    double2 *Y = s.get<double2>(nm);
+    const std::vector<McPar> hp = mc64_params(batch, tau, rho);
+    const McPar *par;
+    const double2 *OH;
+    const double *Omega;
+    double2 *X, *Y;
     Svt64 sv;
-    sv.init(s, Mr, Mt, batch);
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
+        const size_t e = nm1 * b;
+        par = w.in(hp.data(), b, true);
+        OH = w.in(reinterpret_cast<const double2 *>(OH_), e, host);
+        Omega = w.in(Omega_, e, host);
+        X = w.out(reinterpret_cast<double2 *>(X_out), e, host);
+        Y = w.get<double2>(e);
+        sv.layout(w, Mr, Mt, b);
+    }));
+    JSTSP_HIP(hipStreamSynchronize(st));    // (hp is this call's own: copied before it goes out of scope on any path)
     sv.freeze = true;                       // a trial's bits do not depend on the batch around it, also for 64 < n
-    JSTSP_REQUIRE(Y != nullptr && sv.lam != nullptr, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
     JSTSP_HIP(hipMemsetAsync(Y, 0, nm * z2, st));                                                      // mc_svt.m:5
     JSTSP_HIP(hipMemsetAsync(X, 0, nm * z2, st));
     const dim3 g = mc_grid((long long)nm1, batch);
@@ -144,7 +121,7 @@ int jstsp_mc_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 
         hipLaunchKernelGGL(mc_svt_update64_kernel, g, dim3(256), 0, st, (long long)nm1, par, Y, OH, Omega, X);     // :9
         JSTSP_HIP(hipGetLastError());
     }
-    if (host) JSTSP_HIP(hipMemcpyAsync(X_out, X, nm * z2, hipMemcpyDeviceToHost, st));
+    if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(X_out), X, nm));
     JSTSP_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -158,42 +135,32 @@ int jstsp_mc_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64
     JSTSP_REQUIRE(OH_ && Omega_ && tau && rho && X_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
     JSTSP_REQUIRE(!ce_out || Htrue_, JSTSP_E_NULL, "%s: convergence_error needs Htrue", nmf);
     const bool host = memspace == JSTSP_HOST, want_ce = ce_out != nullptr;
-    const size_t nm1 = (size_t)Mr * Mt, nm = nm1 * batch, z2 = sizeof(double2), nce = (size_t)batch * std::max(Imax, 1);
-    size_t need = Svt64::bytes(Mr, Mt, batch) + Slab::rnd(batch * sizeof(McPar)) + 3 * Slab::rnd(nm * z2);
-    if (want_ce) need += Slab::rnd(nm * z2) + 2 * Slab::rnd(batch * sizeof(double));
-    if (host) need += 2 * Slab::rnd(nm * z2) + Slab::rnd(nm * sizeof(double)) + (want_ce ? Slab::rnd(nm * z2) + Slab::rnd(nce * sizeof(double)) : 0);
-    JSTSP_REQUIRE(need <= P64_WS_LIMIT, JSTSP_E_UNSUPPORTED, "%s: the float64 workspace would be %.1f GiB (limit 24)", nmf,
-                  (double)need / (double)((size_t)1 << 30));
+    const size_t nm1 = (size_t)Mr * Mt, nm = nm1 * batch, z2 = sizeof(double2);
     hipStream_t st = ctx->stream;
-    Slab s(st);
-    JSTSP_TRY(s.reserve(need, nmf));
-    McPar *par = s.get<McPar>(batch);
-    JSTSP_TRY(mc64_params(st, batch, tau, rho, par));
-    const double2 *OH = reinterpret_cast<const double2 *>(OH_), *Htrue = reinterpret_cast<const double2 *>(Htrue_);
-    const double *Omega = Omega_;
-    double2 *X = reinterpret_cast<double2 *>(X_out);
-    double *ce = ce_out;
-    if (host) {
-        double2 *oh = s.get<double2>(nm);
-        double *om = s.get<double>(nm);
-        X = s.get<double2>(nm);
-        JSTSP_HIP(hipMemcpyAsync(oh, OH_, nm * z2, hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(om, Omega_, nm * sizeof(double), hipMemcpyHostToDevice, st));
-        OH = oh; Omega = om;
-        if (want_ce) {
-            double2 *h = s.get<double2>(nm);
-            ce = s.get<double>(nce);
-            JSTSP_HIP(hipMemcpyAsync(h, Htrue_, nm * z2, hipMemcpyHostToDevice, st));
-            Htrue = h;
-        }
-    }
-    double2 *Y = s.get<double2>(nm), *Z = s.get<double2>(nm), *Zn = s.get<double2>(nm);
-    double2 *D = want_ce ? s.get<double2>(nm) : nullptr;
-    double *num = want_ce ? s.get<double>(batch) : nullptr, *den = want_ce ? s.get<double>(batch) : nullptr;
+    const std::vector<McPar> hp = mc64_params(batch, tau, rho);
+    const McPar *par;
+    const double2 *OH, *Htrue = nullptr;
+    const double *Omega;
+    double2 *X, *Y, *Z, *Zn, *D = nullptr;
+    double *ce = nullptr, *num = nullptr, *den = nullptr;
     Svt64 sv;
-    sv.init(s, Mr, Mt, batch);
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
+        const size_t e = nm1 * b;
+        par = w.in(hp.data(), b, true);
+        OH = w.in(reinterpret_cast<const double2 *>(OH_), e, host);
+        Omega = w.in(Omega_, e, host);
+        X = w.out(reinterpret_cast<double2 *>(X_out), e, host);
+        Y = w.get<double2>(e); Z = w.get<double2>(e); Zn = w.get<double2>(e);
+        if (want_ce) {
+            Htrue = w.in(reinterpret_cast<const double2 *>(Htrue_), e, host);
+            ce = w.out(ce_out, (size_t)b * std::max(Imax, 1), host);
+            D = w.get<double2>(e); num = w.get<double>(b); den = w.get<double>(b);
+        }
+        sv.layout(w, Mr, Mt, b);
+    }));
+    JSTSP_HIP(hipStreamSynchronize(st));    // (hp is this call's own: copied before it goes out of scope on any path)
     sv.freeze = true;                       // a trial's bits do not depend on the batch around it, also for 64 < n
-    JSTSP_REQUIRE(Zn != nullptr && sv.lam != nullptr && (!want_ce || den != nullptr), JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
     for (double2 *p : {X, Y, Z, Zn}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * z2, st));                    // mc_admm.m:6-8
     if (want_ce) JSTSP_TRY(sv.lambda_max(st, Htrue, den));
     const dim3 g = mc_grid((long long)nm1, batch);
@@ -201,15 +168,15 @@ int jstsp_mc_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64
         JSTSP_TRY(sv.apply(st, Zn, &par->thr, (long long)(sizeof(McPar) / sizeof(double)), X));       // :22
         hipLaunchKernelGGL(mc_admm_update64_kernel, g, dim3(256), 0, st, (long long)nm1, par, Y, Z, OH, Omega, X, Zn);     // :24-26
         if (want_ce) {                                                                                 // :28
-            hipLaunchKernelGGL(mc_diff64_kernel, dim3((unsigned)std::min<size_t>((nm + 255) / 256, 4096)), dim3(256), 0, st, (long long)nm, X, Htrue, D);
+            hipLaunchKernelGGL(diff64_kernel, dim3((unsigned)std::min<size_t>((nm + 255) / 256, 4096)), dim3(256), 0, st, (long long)nm, X, Htrue, D);
             JSTSP_TRY(sv.lambda_max(st, D, num));
-            hipLaunchKernelGGL(mc_ratio64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, num, den, ce);
+            hipLaunchKernelGGL(ratio64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, num, den, ce);
         }
         JSTSP_HIP(hipGetLastError());
     }
     if (host) {
-        JSTSP_HIP(hipMemcpyAsync(X_out, X, nm * z2, hipMemcpyDeviceToHost, st));
-        if (want_ce && Imax > 0) JSTSP_HIP(hipMemcpyAsync(ce_out, ce, (size_t)batch * Imax * sizeof(double), hipMemcpyDeviceToHost, st));
+        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(X_out), X, nm));
+        if (want_ce && Imax > 0) JSTSP_TRY(s.copy_back(ce_out, ce, (size_t)batch * Imax));
     }
     JSTSP_HIP(hipStreamSynchronize(st));
     return 0;

@@ -14,6 +14,7 @@
 // Every sum is formed in a fixed order by a fixed thread: no atomics, a repeated call returns the same bits, and a problem's
 // result does not depend on its batch mates or on the memspace.
 #include "solver_common.h"
+#include "ws64.h"
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
@@ -21,32 +22,6 @@
 namespace jstsp {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum64(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// x^2 + y^2 from two rounded squares and one sum (symmetric in x and y whatever the compiler would like to contract)
-__device__ __forceinline__ double abs2_sym(double x, double y)
-{
-#pragma clang fp contract(off)
-    const double a = x * x, b = y * y;
-    return a + b;
-}
-
-// conj(u)^T v over n entries from p with stride st: (sum ux vx, sum uy vy, sum ux vy, sum uy vx) continued in acc
-struct Dot4 {
-    double xx, yy, xy, yx;
-};
-__device__ __forceinline__ void dot4_step(Dot4 &d, double2 u, double2 v)
-{
-    d.xx = fma(u.x, v.x, d.xx);
-    d.yy = fma(u.y, v.y, d.yy);
-    d.xy = fma(u.x, v.y, d.xy);
-    d.yx = fma(u.y, v.x, d.yx);
-}
 
 // workspace per problem (global): R N x S | Q N x K | Rt K x K | T K x S | D K
 __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, int K, int pnorm, const double2 *A, long long strideA,

@@ -19,7 +19,8 @@
 // do not depend on the scale of v and x_hat of v 2^k is x_hat 2^k on the bits.  No atomics, every sum in a fixed order by a fixed
 // thread: a repeated call returns the same bits and a problem's result does not depend on its batch mates, on whether the
 // dictionary is shared, or on the memspace.
-#include "svt64.h"
+#include "ws64.h"
+#include "zgemm64.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -42,32 +43,6 @@ struct Omp64 {
     int *nu;           // [batch]              basis vectors so far
     int *ex;           // [batch]              e: the problem is solved on v 2^-e
 };
-
-__device__ __forceinline__ double wave_sum64(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// x^2 + y^2 from two rounded squares and one sum (symmetric in x and y whatever the compiler would like to contract)
-__device__ __forceinline__ double abs2_sym(double x, double y)
-{
-#pragma clang fp contract(off)
-    const double a = x * x, b = y * y;
-    return a + b;
-}
-
-// conj(u)^T v: (sum ux vx, sum uy vy, sum ux vy, sum uy vx), c = (xx + yy, xy - yx)
-struct Dot4 {
-    double xx, yy, xy, yx;
-};
-__device__ __forceinline__ void dot4_step(Dot4 &d, double2 u, double2 v)
-{
-    d.xx = fma(u.x, v.x, d.xx);
-    d.yy = fma(u.y, v.y, d.yy);
-    d.xy = fma(u.x, v.y, d.xy);
-    d.yx = fma(u.y, v.x, d.yx);
-}
 
 // the sum of a complex value over the 256 threads: xor tree per wave, then the four waves in order (three barriers; sh: 8 doubles)
 __device__ __forceinline__ double2 block_sum2(double2 v, double *sh)
@@ -296,68 +271,36 @@ struct Omp64Shape {
     bool host, want_target;
 };
 
-size_t dict_elems(long long stride, size_t one, int batch) { return stride ? (size_t)stride * (batch - 1) + one : one; }
-
 size_t omp64_zws(const Omp64Shape &p, int batch)
 {
     return p.kron ? std::max<size_t>(1, std::max(zgemm64_ws_elems(p.Gr, p.M, p.N, batch), zgemm64_ws_elems(p.Gr, p.G2, p.M, batch))) : 0;
 }
 
-size_t omp64_bytes(const Omp64Shape &p, int batch)
-{
-    const size_t b = (size_t)batch, z2 = sizeof(double2), m = (size_t)p.m, meas = (size_t)p.meas, sd = (size_t)p.size_d;
-    size_t need = Slab::rnd(b * meas * z2) + Slab::rnd(b * meas * m * z2) + Slab::rnd(b * m * m * z2) + Slab::rnd(b * m * z2) +
-                  Slab::rnd(b * sd * z2) + 3 * Slab::rnd(b * m * sizeof(int)) + 2 * Slab::rnd(b * sizeof(int));
-    if (p.kron) need += Slab::rnd(b * p.Gr * p.M * z2) + Slab::rnd(omp64_zws(p, batch) * z2);
-    if (p.host) {
-        need += Slab::rnd(dict_elems(p.strideA, (size_t)p.N * p.Gr, batch) * z2) + Slab::rnd(b * meas * z2) + Slab::rnd(b * sd * z2) +
-                Slab::rnd(b * m * sizeof(int32_t));
-        if (p.kron) need += Slab::rnd(dict_elems(p.strideB, (size_t)p.G2 * p.M, batch) * z2);
-        if (p.want_target) need += Slab::rnd(b * meas * m * z2);
-    }
-    return need;
-}
-
 int omp64_run(jstsp_ctx *ctx, const char *nmf, const Omp64Shape &p, int batch, const jstsp_c64 *A_, const jstsp_c64 *B_, const jstsp_c64 *v_,
               jstsp_c64 *x_hat, int32_t *index_out, jstsp_c64 *target_out)
 {
-    const size_t need = omp64_bytes(p, batch);
-    if (need > P64_WS_LIMIT) {
-        int fit = batch;
-        while (fit > 1 && omp64_bytes(p, fit) > P64_WS_LIMIT) fit = fit > 64 ? fit - fit / 16 : fit - 1;
-        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nmf,
-                  (double)need / (double)((size_t)1 << 30), fit);
-        return JSTSP_E_UNSUPPORTED;
-    }
     hipStream_t st = ctx->stream;
-    Slab sl(st);
-    JSTSP_TRY(sl.reserve(need, nmf));
     const size_t b = (size_t)batch, z2 = sizeof(double2), m = (size_t)p.m, meas = (size_t)p.meas, sd = (size_t)p.size_d;
-    const double2 *A = reinterpret_cast<const double2 *>(A_), *B = reinterpret_cast<const double2 *>(B_), *v = reinterpret_cast<const double2 *>(v_);
-    double2 *xh = reinterpret_cast<double2 *>(x_hat), *to = reinterpret_cast<double2 *>(target_out);
-    int32_t *io = index_out;
-    if (p.host) {
-        const size_t szA = dict_elems(p.strideA, (size_t)p.N * p.Gr, batch), szB = p.kron ? dict_elems(p.strideB, (size_t)p.G2 * p.M, batch) : 0;
-        double2 *a = sl.get<double2>(szA), *vv = sl.get<double2>(b * meas), *bb = p.kron ? sl.get<double2>(szB) : nullptr;
-        xh = sl.get<double2>(b * sd);
-        io = sl.get<int32_t>(b * m);
-        to = p.want_target ? sl.get<double2>(b * meas * m) : nullptr;
-        JSTSP_REQUIRE(a && vv && xh && io && (!p.kron || bb) && (!p.want_target || to), JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
-        JSTSP_HIP(hipMemcpyAsync(a, A_, szA * z2, hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(vv, v_, b * meas * z2, hipMemcpyHostToDevice, st));
-        if (p.kron) JSTSP_HIP(hipMemcpyAsync(bb, B_, szB * z2, hipMemcpyHostToDevice, st));
-        A = a; B = bb; v = vv;
-    }
+    const double2 *A, *B = nullptr, *v;
+    double2 *xh, *to = nullptr, *corr, *T = nullptr, *zws = nullptr;
+    int32_t *io;
     Omp64 s;
-    s.r = sl.get<double2>(b * meas); s.Q = sl.get<double2>(b * meas * m); s.Rm = sl.get<double2>(b * m * m); s.z = sl.get<double2>(b * m);
-    double2 *corr = sl.get<double2>(b * sd);
-    s.uniq = sl.get<int>(b * m); s.mult = sl.get<int>(b * m); s.sel = sl.get<int>(b * m);
-    s.nu = sl.get<int>(b); s.ex = sl.get<int>(b);
-    double2 *T = p.kron ? sl.get<double2>(b * p.Gr * p.M) : nullptr, *zws = p.kron ? sl.get<double2>(omp64_zws(p, batch)) : nullptr;
-    JSTSP_REQUIRE(s.r && s.Q && s.Rm && s.z && corr && s.uniq && s.mult && s.sel && s.nu && s.ex && (!p.kron || (T && zws)), JSTSP_E_NOMEM,
-                  "%s: workspace accounting error", nmf);
+    Slab sl(st);
+    JSTSP_TRY(ws64_open(sl, nmf, batch, [&](Slab &w, int nb) {
+        const size_t n = (size_t)nb;
+        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(p.strideA, (size_t)p.N * p.Gr, nb), p.host);
+        v = w.in(reinterpret_cast<const double2 *>(v_), n * meas, p.host);
+        if (p.kron) B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(p.strideB, (size_t)p.G2 * p.M, nb), p.host);
+        xh = w.out(reinterpret_cast<double2 *>(x_hat), n * sd, p.host);
+        io = w.out(index_out, n * m, p.host);
+        if (p.want_target) to = w.out(reinterpret_cast<double2 *>(target_out), n * meas * m, p.host);
+        s.r = w.get<double2>(n * meas); s.Q = w.get<double2>(n * meas * m); s.Rm = w.get<double2>(n * m * m); s.z = w.get<double2>(n * m);
+        corr = w.get<double2>(n * sd);
+        s.uniq = w.get<int>(n * m); s.mult = w.get<int>(n * m); s.sel = w.get<int>(n * m);
+        s.nu = w.get<int>(n); s.ex = w.get<int>(n);
+        if (p.kron) { T = w.get<double2>(n * p.Gr * p.M); zws = w.get<double2>(omp64_zws(p, nb)); }
+    }));
     hipLaunchKernelGGL(omp64_init_kernel, dim3(batch), dim3(256), 0, st, p.meas, v, s);
-    const double2 *Bk = p.kron ? B : nullptr;
     for (int it = 0; it < p.m; ++it) {                                                                 // OMP.m:16
         if (p.kron) {
             // Phi' r = vec(Af^H R Bf^H), R = reshape(r, N, M): what jstsp_correlate_f64 computes
@@ -367,15 +310,15 @@ int omp64_run(jstsp_ctx *ctx, const char *nmf, const Omp64Shape &p, int batch, c
                               (long long)sd, p.Gr, zws));
         } else
             hipLaunchKernelGGL(omp64_corr_kernel, dim3((p.size_d + 3) / 4, batch), dim3(256), 0, st, p.meas, p.size_d, A, p.strideA, s.r, corr);
-        hipLaunchKernelGGL(omp64_step_kernel, dim3(batch), dim3(256), 0, st, p.meas, p.size_d, p.m, it, corr, A, p.strideA, Bk, p.strideB, p.N,
+        hipLaunchKernelGGL(omp64_step_kernel, dim3(batch), dim3(256), 0, st, p.meas, p.size_d, p.m, it, corr, A, p.strideA, B, p.strideB, p.N,
                            p.Gr, p.G2, s);
     }
     hipLaunchKernelGGL(omp64_finish_kernel, dim3(batch), dim3(256), m * z2, st, p.meas, p.size_d, p.m, A, p.strideA, s, xh, io, to);
     JSTSP_HIP(hipGetLastError());
     if (p.host) {
-        JSTSP_HIP(hipMemcpyAsync(x_hat, xh, b * sd * z2, hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipMemcpyAsync(index_out, io, b * m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (p.want_target) JSTSP_HIP(hipMemcpyAsync(target_out, to, b * meas * m * z2, hipMemcpyDeviceToHost, st));
+        JSTSP_TRY(sl.copy_back(reinterpret_cast<double2 *>(x_hat), xh, b * sd));
+        JSTSP_TRY(sl.copy_back(index_out, io, b * m));
+        if (p.want_target) JSTSP_TRY(sl.copy_back(reinterpret_cast<double2 *>(target_out), to, b * meas * m));
         JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;

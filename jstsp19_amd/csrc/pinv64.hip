@@ -15,7 +15,9 @@
 // on the batch around it); whether any matrix of the call is still rotating is read on the host once per sweep, so a call
 // synchronises the context's stream.  Drop rule (pinv.m): sigma_k is kept iff sigma_k > max(rows, cols) * eps(sigma_max),
 // eps(x) = 2^(floor(log2 x) - 52) - one place, p64_sigma_kernel.  No atomics anywhere: a repeated call returns the same bits.
+#include "ws64.h"
 #include "zgemm64.h"
+
 #include <algorithm>
 
 namespace jstsp {
@@ -26,7 +28,6 @@ constexpr int PV_MAX_ORDER = 512;        // min(rows, cols): the float64 family'
 constexpr int PV_MAX_LONG = 8192;        // max(rows, cols)
 constexpr int PV_SWEEPS = 40;            // cap (the tested inputs stop after 6 to 12)
 constexpr int PV_WAVE_ROWS = 512;        // columns up to this length: one wave per pair; longer: one workgroup per pair
-constexpr size_t PV_WS_LIMIT = (size_t)24 << 30;
 constexpr double PV_EPS = 2.220446049250313e-16;
 
 struct PvMeta {
@@ -250,30 +251,6 @@ __global__ void p64_min_kernel(int cnt, const double *v, double *out)
     *out = r;
 }
 
-struct Slab64 {
-    hipStream_t st;
-    char *base = nullptr;
-    size_t cap = 0, off = 0;
-    explicit Slab64(hipStream_t s) : st(s) {}
-    ~Slab64() { if (base) (void)hipFreeAsync(base, st); }
-    static size_t rnd(size_t b) { return (b + 255) & ~(size_t)255; }
-    int reserve(size_t bytes, const char *nm)
-    {
-        const hipError_t e = hipMallocAsync((void **)&base, std::max<size_t>(bytes, 256), st);
-        if (e != hipSuccess) { base = nullptr; set_error("%s: hipMallocAsync(%zu) failed: %s", nm, bytes, hipGetErrorString(e)); return JSTSP_E_NOMEM; }
-        cap = bytes;
-        return 0;
-    }
-    template <class T> T *get(size_t n)
-    {
-        const size_t b = rnd(n * sizeof(T));
-        if (off + b > cap) return nullptr;
-        T *p = reinterpret_cast<T *>(base + off);
-        off += b;
-        return p;
-    }
-};
-
 bool pv_shape_ok(int rows, int cols) { return std::min(rows, cols) <= PV_MAX_ORDER && std::max(rows, cols) <= PV_MAX_LONG; }
 
 size_t pv_gemm_ws(int rows, int cols, int count)
@@ -282,26 +259,31 @@ size_t pv_gemm_ws(int rows, int cols, int count)
     return std::max<size_t>(1, rows >= cols ? zgemm64_ws_elems(n, m, n, count) : zgemm64_ws_elems(m, n, n, count));
 }
 
-// workspace of pinv64_run for `count` matrices (its allocations in the same order)
-size_t pinv64_bytes(int rows, int cols, int count)
-{
-    const size_t m = std::max(rows, cols), n = std::min(rows, cols), z2 = sizeof(double2);
-    return Slab64::rnd(m * n * count * z2) + 2 * Slab64::rnd(n * n * count * z2) + Slab64::rnd(count * sizeof(PvMeta)) + Slab64::rnd(sizeof(int)) +
-           Slab64::rnd(pv_gemm_ws(rows, cols, count) * z2);
-}
+// the arrays of pinv64_run for `count` matrices (rows x cols)
+struct Pinv64 {
+    double2 *W, *V, *Vs, *ws;
+    PvMeta *meta;
+    int *any;
+    void layout(Slab &s, int rows, int cols, int count)
+    {
+        const size_t m = std::max(rows, cols), n = std::min(rows, cols);
+        W = s.get<double2>(m * n * count); V = s.get<double2>(n * n * count); Vs = s.get<double2>(n * n * count);
+        meta = s.get<PvMeta>(count);
+        any = s.get<int>(1);
+        ws = s.get<double2>(pv_gemm_ws(rows, cols, count));
+    }
+};
 
 // P[t] (cols x rows, contiguous) = pinv(A[t]) (rows x cols, sA elements apart), t < count; rcond / rank: nullptr or device [count].
 // Synchronises the stream once per sweep.
-int pinv64_run(hipStream_t st, Slab64 &s, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond, int32_t *rank,
-               const char *nm)
+int pinv64_run(hipStream_t st, const Pinv64 &w, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond,
+               int32_t *rank)
 {
     const int m = std::max(rows, cols), n = std::min(rows, cols);
     const size_t mn = (size_t)m * n, nn = (size_t)n * n;
-    double2 *W = s.get<double2>(mn * count), *V = s.get<double2>(nn * count), *Vs = s.get<double2>(nn * count);
-    PvMeta *meta = s.get<PvMeta>(count);
-    int *any = s.get<int>(1);
-    double2 *ws = s.get<double2>(pv_gemm_ws(rows, cols, count));
-    JSTSP_REQUIRE(W && V && Vs && meta && any && ws, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
+    double2 *W = w.W, *V = w.V, *Vs = w.Vs, *ws = w.ws;
+    PvMeta *meta = w.meta;
+    int *any = w.any;
     hipLaunchKernelGGL(p64_prep_kernel, dim3(count), dim3(1024), 0, st, rows, cols, A, sA, W, V, meta);
     JSTSP_HIP(hipGetLastError());
     const int ne = n + (n & 1), half = ne / 2, ring = ne - 1;
@@ -328,35 +310,6 @@ int pinv64_run(hipStream_t st, Slab64 &s, int rows, int cols, int count, const d
     return 0;
 }
 
-int largest_fit(size_t (*bytes)(const int *, int), const int *shape, int batch)
-{
-    int fit = batch;
-    while (fit > 1 && bytes(shape, fit) > PV_WS_LIMIT) fit = fit > 64 ? fit - fit / 16 : fit - 1;
-    return fit;
-}
-
-size_t pinv_call_bytes(const int *sh, int batch)
-{
-    const size_t e = (size_t)sh[0] * sh[1] * batch;
-    size_t b = pinv64_bytes(sh[0], sh[1], batch);
-    if (sh[2]) b += 2 * Slab64::rnd(e * sizeof(double2)) + Slab64::rnd(batch * sizeof(double)) + Slab64::rnd(batch * sizeof(int32_t));
-    return b;
-}
-
-// sh: N, M, Gr, G2, host, strideA != 0, strideB != 0
-size_t ls_call_bytes(const int *sh, int batch)
-{
-    const size_t N = sh[0], M = sh[1], Gr = sh[2], G2 = sh[3], z2 = sizeof(double2);
-    const int nA = sh[5] ? batch : 1, nB = sh[6] ? batch : 1;
-    size_t b = pinv64_bytes(sh[0], sh[2], nA) + pinv64_bytes(sh[3], sh[1], nB);
-    b += Slab64::rnd(N * Gr * nA * z2) + Slab64::rnd(G2 * M * nB * z2);                       // pinv(A), pinv(B)
-    b += Slab64::rnd(Gr * M * batch * z2);                                                    // pinv(A) Y
-    b += Slab64::rnd(std::max<size_t>(1, std::max(zgemm64_ws_elems(sh[2], sh[1], sh[0], batch), zgemm64_ws_elems(sh[2], sh[3], sh[1], batch))) * z2);
-    b += Slab64::rnd(nA * sizeof(double)) + Slab64::rnd(nB * sizeof(double)) + Slab64::rnd(2 * sizeof(double));
-    if (sh[4]) b += Slab64::rnd(N * M * batch * z2) + Slab64::rnd(N * Gr * nA * z2) + Slab64::rnd(G2 * M * nB * z2) + Slab64::rnd(Gr * G2 * batch * z2);
-    return b;
-}
-
 }  // namespace
 }  // namespace jstsp
 
@@ -376,35 +329,26 @@ int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c6
                   "%s: %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d and batch <= 65535", nm, rows, cols, batch, PV_MAX_ORDER,
                   PV_MAX_LONG);
     const bool host = memspace == JSTSP_HOST;
-    const int sh[3] = {rows, cols, host ? 1 : 0};
-    const size_t need = pinv_call_bytes(sh, batch);
-    if (need > PV_WS_LIMIT) {
-        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nm,
-                  (double)need / (double)((size_t)1 << 30), largest_fit(pinv_call_bytes, sh, batch));
-        return JSTSP_E_UNSUPPORTED;
-    }
     hipStream_t st = ctx->stream;
-    Slab64 s(st);
-    JSTSP_TRY(s.reserve(need, nm));
-    const size_t e = (size_t)rows * cols * batch;
-    const double2 *A = reinterpret_cast<const double2 *>(A_);
-    double2 *P = reinterpret_cast<double2 *>(P_);
-    double *rc = rcond_out;
-    int32_t *rk = rank_out;
+    const double2 *A;
+    double2 *P;
+    double *rc;
+    int32_t *rk;
+    Pinv64 pv;
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nm, batch, [&](Slab &w, int b) {
+        const size_t e = (size_t)rows * cols * b;
+        A = w.in(reinterpret_cast<const double2 *>(A_), e, host);
+        P = w.out(reinterpret_cast<double2 *>(P_), e, host);
+        rc = w.out(rcond_out, b, host);
+        rk = w.out(rank_out, b, host);
+        pv.layout(w, rows, cols, b);
+    }));
+    JSTSP_TRY(pinv64_run(st, pv, rows, cols, batch, A, (long long)rows * cols, P, rc, rk));
     if (host) {
-        double2 *a = s.get<double2>(e);
-        P = s.get<double2>(e);
-        rc = s.get<double>(batch);
-        rk = s.get<int32_t>(batch);
-        JSTSP_REQUIRE(a && P && rc && rk, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
-        JSTSP_HIP(hipMemcpyAsync(a, A_, e * sizeof(double2), hipMemcpyHostToDevice, st));
-        A = a;
-    }
-    JSTSP_TRY(pinv64_run(st, s, rows, cols, batch, A, (long long)rows * cols, P, rc, rk, nm));
-    if (host) {
-        JSTSP_HIP(hipMemcpyAsync(P_, P, e * sizeof(double2), hipMemcpyDeviceToHost, st));
-        if (rcond_out) JSTSP_HIP(hipMemcpyAsync(rcond_out, rc, batch * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (rank_out) JSTSP_HIP(hipMemcpyAsync(rank_out, rk, batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(P_), P, (size_t)rows * cols * batch));
+        if (rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rc, batch));
+        if (rank_out) JSTSP_TRY(s.copy_back(rank_out, rk, batch));
         JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;
@@ -425,37 +369,30 @@ int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
                   "%s: A %d x %d, B %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d per factor and batch <= 65535", nm, N, Gr, G2, M,
                   batch, PV_MAX_ORDER, PV_MAX_LONG);
     const bool host = memspace == JSTSP_HOST;
-    const int sh[7] = {N, M, Gr, G2, host ? 1 : 0, strideA ? 1 : 0, strideB ? 1 : 0};
-    const size_t need = ls_call_bytes(sh, batch);
-    if (need > PV_WS_LIMIT) {
-        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nm,
-                  (double)need / (double)((size_t)1 << 30), largest_fit(ls_call_bytes, sh, batch));
-        return JSTSP_E_UNSUPPORTED;
-    }
     hipStream_t st = ctx->stream;
-    Slab64 s(st);
-    JSTSP_TRY(s.reserve(need, nm));
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    const size_t eY = (size_t)N * M * batch, eA = (size_t)N * Gr * nA, eB = (size_t)G2 * M * nB, eS = (size_t)Gr * G2 * batch;
-    const double2 *Y = reinterpret_cast<const double2 *>(Y_), *A = reinterpret_cast<const double2 *>(A_), *B = reinterpret_cast<const double2 *>(B_);
-    double2 *S = reinterpret_cast<double2 *>(S_out);
+    const double2 *Y, *A, *B;
+    double2 *S, *PA, *PB, *T, *ws;
+    double *rcA, *rcB, *rcd;
+    Pinv64 pvA, pvB;
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nm, batch, [&](Slab &w, int b) {
+        const int bA = strideA ? b : 1, bB = strideB ? b : 1;
+        const size_t eA = (size_t)N * Gr * bA, eB = (size_t)G2 * M * bB;
+        Y = w.in(reinterpret_cast<const double2 *>(Y_), (size_t)N * M * b, host);
+        A = w.in(reinterpret_cast<const double2 *>(A_), eA, host);
+        B = w.in(reinterpret_cast<const double2 *>(B_), eB, host);
+        S = w.out(reinterpret_cast<double2 *>(S_out), (size_t)Gr * G2 * b, host);
+        PA = w.get<double2>(eA); PB = w.get<double2>(eB); T = w.get<double2>((size_t)Gr * M * b);
+        ws = w.get<double2>(std::max<size_t>(1, std::max(zgemm64_ws_elems(Gr, M, N, b), zgemm64_ws_elems(Gr, G2, M, b))));
+        rcA = w.get<double>(bA); rcB = w.get<double>(bB); rcd = w.get<double>(2);
+        pvA.layout(w, N, Gr, bA);
+        pvB.layout(w, G2, M, bB);
+    }));
     double *rc2 = rcond_out;
-    if (host) {
-        double2 *y = s.get<double2>(eY), *a = s.get<double2>(eA), *b = s.get<double2>(eB);
-        S = s.get<double2>(eS);
-        JSTSP_REQUIRE(y && a && b && S, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
-        JSTSP_HIP(hipMemcpyAsync(y, Y_, eY * sizeof(double2), hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(a, A_, eA * sizeof(double2), hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(b, B_, eB * sizeof(double2), hipMemcpyHostToDevice, st));
-        Y = y; A = a; B = b;
-    }
-    double2 *PA = s.get<double2>(eA), *PB = s.get<double2>(eB), *T = s.get<double2>((size_t)Gr * M * batch);
-    double2 *ws = s.get<double2>(std::max<size_t>(1, std::max(zgemm64_ws_elems(Gr, M, N, batch), zgemm64_ws_elems(Gr, G2, M, batch))));
-    double *rcA = s.get<double>(nA), *rcB = s.get<double>(nB), *rcd = s.get<double>(2);
-    JSTSP_REQUIRE(PA && PB && T && ws && rcA && rcB && rcd, JSTSP_E_NOMEM, "%s: workspace accounting error", nm);
     // a shared factor is inverted once for the call
-    JSTSP_TRY(pinv64_run(st, s, N, Gr, nA, A, (long long)N * Gr, PA, rcA, nullptr, nm));
-    JSTSP_TRY(pinv64_run(st, s, G2, M, nB, B, (long long)G2 * M, PB, rcB, nullptr, nm));
+    JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, A, (long long)N * Gr, PA, rcA, nullptr));
+    JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, B, (long long)G2 * M, PB, rcB, nullptr));
     JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, Mat64{PA, strideA ? (long long)Gr * N : 0, Gr}, Mat64{Y, (long long)N * M, N}, T, (long long)Gr * M, Gr,
                       ws));
     JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Mat64{PB, strideB ? (long long)M * G2 : 0, M}, S, (long long)Gr * G2,
@@ -465,9 +402,9 @@ int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
         hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nA, rcA, rc2);
         hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nB, rcB, rc2 + 1);
         JSTSP_HIP(hipGetLastError());
-        if (host) JSTSP_HIP(hipMemcpyAsync(rcond_out, rcd, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (host) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
     }
-    if (host) JSTSP_HIP(hipMemcpyAsync(S_out, S, eS * sizeof(double2), hipMemcpyDeviceToHost, st));
+    if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), S, (size_t)Gr * G2 * batch));
     JSTSP_HIP(hipStreamSynchronize(st));
     return 0;
 }

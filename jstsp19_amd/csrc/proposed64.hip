@@ -164,30 +164,6 @@ size_t solver_ws_elems(int N, int M, int Gr, int G2, int batch, int nA, int nB)
     return std::max<size_t>(1, e);
 }
 
-// bytes of the solver's workspace for `batch` trials (the allocations of proposed64_run in the same order)
-size_t proposed64_bytes(int N, int M, int Gr, int G2, int batch, bool host, long long strideA, long long strideB, bool angles, bool want_ce, int Imax)
-{
-    auto r = [](size_t n, size_t sz) { return Slab::rnd(n * sz); };
-    const size_t nm = (size_t)N * M * batch, g = (size_t)Gr * G2 * batch, z2 = sizeof(double2);
-    const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    size_t b = r(batch, sizeof(Par64));
-    if (host) {
-        b += r(nm, z2) + r(nm, sizeof(double)) + r((strideA ? (size_t)strideA * (batch - 1) : 0) + (size_t)N * Gr, z2) +
-             r((strideB ? (size_t)strideB * (batch - 1) : 0) + (size_t)G2 * M, z2);
-        if (angles) b += r(g, sizeof(int32_t));
-        b += r(g, z2) + r(nm, z2) + r((size_t)3 * Imax * batch, sizeof(double));
-    }
-    b += 8 * r(nm, z2);                                                     // X V1 V2 C Xs Y Z K
-    b += 5 * r(g, z2);                                                      // V S Res RRes T2
-    b += r((size_t)Gr * M * batch, z2) + r((size_t)N * G2 * batch, z2);     // T W
-    b += r((size_t)Gr * Gr * nA, z2) + r((size_t)G2 * G2 * nB, z2);         // G_A G_B
-    b += r(solver_ws_elems(N, M, Gr, G2, batch, nA, nB), z2);
-    if (angles) b += r(g, sizeof(int32_t));
-    b += 4 * r(batch, sizeof(double));
-    (void)want_ce;
-    return b + Svt64::bytes(N, M, batch);
-}
-
 }  // namespace
 }  // namespace jstsp
 
@@ -206,31 +182,23 @@ int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y_
                   "svt (float64): min(Mr, Mt) = %d, batch = %d: the float64 eigen-decomposition is limited to order %d (batch 65535)", std::min(Mr, Mt), batch,
                   P64_MAX_ORDER);
     hipStream_t st = ctx->stream;
+    const bool host = memspace == JSTSP_HOST;
     const size_t nm = (size_t)Mr * Mt * batch;
-    const size_t need = Svt64::bytes(Mr, Mt, batch) + Slab::rnd(batch * sizeof(double)) + (memspace == JSTSP_HOST ? 2 * Slab::rnd(nm * sizeof(double2)) : 0);
-    JSTSP_REQUIRE(need <= P64_WS_LIMIT, JSTSP_E_UNSUPPORTED, "svt (float64): the float64 workspace would be %.1f GiB (limit 24)",
-                  (double)need / (double)((size_t)1 << 30));
-    Slab s(st);
-    JSTSP_TRY(s.reserve(need, "svt (float64)"));
-    double *thr = s.get<double>(batch);
-    JSTSP_HIP(hipMemcpyAsync(thr, tau, batch * sizeof(double), hipMemcpyHostToDevice, st));
-    const double2 *Y = reinterpret_cast<const double2 *>(Y_);
-    double2 *X = reinterpret_cast<double2 *>(X_);
-    if (memspace == JSTSP_HOST) {
-        double2 *y = s.get<double2>(nm);
-        X = s.get<double2>(nm);
-        JSTSP_HIP(hipMemcpyAsync(y, Y_, nm * sizeof(double2), hipMemcpyHostToDevice, st));
-        Y = y;
-    }
+    const double *thr;
+    const double2 *Y;
+    double2 *X;
     Svt64 sv;
-    sv.init(s, Mr, Mt, batch);
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, "svt (float64)", batch, [&](Slab &w, int b) {
+        const size_t e = (size_t)Mr * Mt * b;
+        thr = w.in(tau, b, true);
+        Y = w.in(reinterpret_cast<const double2 *>(Y_), e, host);
+        X = w.out(reinterpret_cast<double2 *>(X_), e, host);
+        sv.layout(w, Mr, Mt, b);
+    }));
     JSTSP_TRY(sv.apply(st, Y, thr, 1, X));
-    if (memspace == JSTSP_HOST) {
-        JSTSP_HIP(hipMemcpyAsync(X_, X, nm * sizeof(double2), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-    } else {
-        JSTSP_HIP(hipStreamSynchronize(st));        // (tau was read from the caller's host array by the copy above)
-    }
+    if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(X_), X, nm));
+    JSTSP_HIP(hipStreamSynchronize(st));            // (also for a device call: tau was read from the caller's host array)
     return 0;
 }
 
@@ -253,60 +221,43 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31) && (long long)N * M < (1ll << 31) && batch <= 65535, JSTSP_E_UNSUPPORTED,
                   "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
     const bool host = memspace == JSTSP_HOST, angles = indx_S_ != nullptr, want_ce = ce_out != nullptr;
-    const size_t need = proposed64_bytes(N, M, Gr, G2, batch, host, strideA, strideB, angles, want_ce, Imax);
-    if (need > P64_WS_LIMIT) {
-        int fit = batch;
-        while (fit > 1 && proposed64_bytes(N, M, Gr, G2, fit, host, strideA ? strideA : 0, strideB ? strideB : 0, angles, want_ce, Imax) > P64_WS_LIMIT)
-            fit = fit > 64 ? fit - fit / 16 : fit - 1;
-        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nmf,
-                  (double)need / (double)((size_t)1 << 30), fit);
-        return JSTSP_E_UNSUPPORTED;
-    }
     hipStream_t st = ctx->stream;
-    Slab s(st);
-    JSTSP_TRY(s.reserve(need, nmf));
     const size_t nm1 = (size_t)N * M, g1 = (size_t)Gr * G2, nm = nm1 * batch, g = g1 * batch;
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-
     std::vector<Par64> hp(batch);
     for (int t = 0; t < batch; ++t) hp[t] = Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]};
-    Par64 *par = s.get<Par64>(batch);
-    JSTSP_HIP(hipMemcpyAsync(par, hp.data(), batch * sizeof(Par64), hipMemcpyHostToDevice, st));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (hp is this call's own: copied before it goes out of scope on any path)
 
-    const double2 *subY = reinterpret_cast<const double2 *>(subY_), *A = reinterpret_cast<const double2 *>(A_), *B = reinterpret_cast<const double2 *>(B_);
-    const double *Omega = Omega_;
-    const int32_t *indx = indx_S_;
-    double2 *Sd = reinterpret_cast<double2 *>(S_out), *Yd = reinterpret_cast<double2 *>(Y_out);
-    double *ced = ce_out;
-    if (host) {
-        const size_t szA = (strideA ? (size_t)strideA * (batch - 1) : 0) + (size_t)N * Gr, szB = (strideB ? (size_t)strideB * (batch - 1) : 0) + (size_t)G2 * M;
-        double2 *y = s.get<double2>(nm);
-        double *om = s.get<double>(nm);
-        double2 *a = s.get<double2>(szA), *b = s.get<double2>(szB);
-        JSTSP_HIP(hipMemcpyAsync(y, subY_, nm * sizeof(double2), hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(om, Omega_, nm * sizeof(double), hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(a, A_, szA * sizeof(double2), hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(b, B_, szB * sizeof(double2), hipMemcpyHostToDevice, st));
-        subY = y; Omega = om; A = a; B = b;
-        if (angles) {
-            int32_t *ix = s.get<int32_t>(g);
-            JSTSP_HIP(hipMemcpyAsync(ix, indx_S_, g * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            indx = ix;
-        }
-        Sd = s.get<double2>(g); Yd = s.get<double2>(nm); ced = s.get<double>((size_t)3 * Imax * batch);
-    }
-    double2 *X = s.get<double2>(nm), *V1 = s.get<double2>(nm), *V2 = s.get<double2>(nm), *Cm = s.get<double2>(nm), *Xs = s.get<double2>(nm),
-            *Y = s.get<double2>(nm), *Z = s.get<double2>(nm), *K = s.get<double2>(nm);
-    double2 *V = s.get<double2>(g), *S = s.get<double2>(g), *Res = s.get<double2>(g), *RRes = s.get<double2>(g), *T2 = s.get<double2>(g);
-    double2 *T = s.get<double2>((size_t)Gr * M * batch), *W = s.get<double2>((size_t)N * G2 * batch);
-    double2 *GA = s.get<double2>((size_t)Gr * Gr * nA), *GB = s.get<double2>((size_t)G2 * G2 * nB);
-    double2 *gws = s.get<double2>(solver_ws_elems(N, M, Gr, G2, batch, nA, nB));
-    int32_t *rank = angles ? s.get<int32_t>(g) : nullptr;
-    double *lx = s.get<double>(batch), *l1 = s.get<double>(batch), *l2 = s.get<double>(batch), *ce3 = s.get<double>(batch);
+    const Par64 *par;
+    const double2 *subY, *A, *B;
+    const double *Omega;
+    const int32_t *indx = nullptr;
+    double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *V, *S, *Res, *RRes, *T2, *T, *W, *GA, *GB, *gws;
+    double *ced, *lx, *l1, *l2, *ce3;
+    int32_t *rank = nullptr;
     Svt64 sv;
-    sv.init(s, N, M, batch);
-    JSTSP_REQUIRE(sv.lam != nullptr && ce3 != nullptr, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
+        const size_t enm = nm1 * b, eg = g1 * b;
+        const int bA = strideA ? b : 1, bB = strideB ? b : 1;
+        par = w.in(hp.data(), b, true);
+        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
+        Omega = w.in(Omega_, enm, host);
+        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
+        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
+        if (angles) indx = w.in(indx_S_, eg, host);
+        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
+        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
+        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
+        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
+        for (double2 **p : {&V, &S, &Res, &RRes, &T2}) *p = w.get<double2>(eg);
+        T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
+        GA = w.get<double2>((size_t)Gr * Gr * bA); GB = w.get<double2>((size_t)G2 * G2 * bB);
+        gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
+        if (angles) rank = w.get<int32_t>(eg);
+        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
+        sv.layout(w, N, M, b);
+    }));
+    JSTSP_HIP(hipStreamSynchronize(st));            // (hp is this call's own: copied before it goes out of scope on any path)
 
     for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * sizeof(double2), st));
     JSTSP_HIP(hipMemsetAsync(V, 0, g * sizeof(double2), st));
@@ -346,9 +297,9 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     JSTSP_HIP(hipMemcpyAsync(Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
     if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, st));
     if (host) {
-        JSTSP_HIP(hipMemcpyAsync(S_out, Sd, g * sizeof(double2), hipMemcpyDeviceToHost, st));
-        if (Y_out) JSTSP_HIP(hipMemcpyAsync(Y_out, Yd, nm * sizeof(double2), hipMemcpyDeviceToHost, st));
-        if (want_ce) JSTSP_HIP(hipMemcpyAsync(ce_out, ced, (size_t)3 * Imax * batch * sizeof(double), hipMemcpyDeviceToHost, st));
+        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g));
+        if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
+        if (want_ce) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
         JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;

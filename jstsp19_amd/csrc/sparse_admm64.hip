@@ -67,51 +67,10 @@ __global__ __launch_bounds__(256) void sadmm64_dual_kernel(long long n, const do
     }
 }
 
-__global__ __launch_bounds__(256) void sadmm64_diff_kernel(long long n, const double2 *X, const double2 *H, double2 *D)
-{
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-        const double2 x = X[e], h = H[e];
-        D[e] = make_double2(x.x - h.x, x.y - h.y);
-    }
-}
-
-// ce(it, t) = num[t] / den[t] (IEEE: x / 0 = Inf, 0 / 0 = NaN, as the reference); Imax entries per trial
-__global__ __launch_bounds__(256) void sadmm64_ratio_kernel(int batch, int Imax, int it, const double *num, const double *den, double *ce)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < batch) ce[(long long)t * Imax + it] = num[t] / den[t];
-}
-
-// U, lam of ONE Hermitian matrix G of order n
-int sadmm64_eig(hipStream_t st, int n, const double2 *G, double2 *U, double *lam)
-{
-    if (n <= P64_LDS_ORDER) {
-        const size_t sh = jacobi_lds_bytes(n, true);
-        JSTSP_HIP(hipFuncSetAttribute((const void *)jacobi64_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(jacobi64_lds_kernel<true>, dim3(1), dim3(256), sh, st, n, G, (long long)n * n, U, lam);
-        JSTSP_HIP(hipGetLastError());
-        return 0;
-    }
-    return eig64_global(st, n, 1, G, (long long)n * n, U, lam, true);
-}
-
 size_t sadmm64_zws(int Mr, int Mt, int batch)
 {
     return std::max<size_t>(1, std::max(std::max(zgemm64_ws_elems(Mr, Mr, Mr, 1), zgemm64_ws_elems(Mt, Mt, Mt, 1)),
                                         std::max(zgemm64_ws_elems(Mr, Mt, Mr, batch), zgemm64_ws_elems(Mr, Mt, Mt, batch))));
-}
-
-size_t sadmm64_bytes(int Mr, int Mt, int batch, int Imax, bool host, bool want_ce)
-{
-    const size_t z2 = sizeof(double2), nm = (size_t)Mr * Mt * batch, nce = (size_t)batch * std::max(Imax, 1);
-    size_t need = 6 * Slab::rnd(nm * z2) + 2 * Slab::rnd((size_t)Mr * Mr * z2) + 2 * Slab::rnd((size_t)Mt * Mt * z2) + Slab::rnd(Mr * sizeof(double)) +
-                  Slab::rnd(Mt * sizeof(double)) + Slab::rnd(sadmm64_zws(Mr, Mt, batch) * z2);
-    if (want_ce) need += Slab::rnd(nm * z2) + 2 * Slab::rnd(batch * sizeof(double)) + Svt64::bytes(Mr, Mt, batch);
-    if (host) {
-        need += 2 * Slab::rnd(nm * z2) + Slab::rnd((size_t)Mr * Mr * z2) + Slab::rnd((size_t)Mt * Mt * z2);        // OH, S_out, Dr, Dt
-        if (want_ce) need += Slab::rnd(nm * z2) + Slab::rnd(nce * sizeof(double));
-    }
-    return need;
 }
 
 }  // namespace
@@ -136,63 +95,40 @@ extern "C" int jstsp_sparse_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
                   std::max(Mr, Mt), batch, SADMM64_MAX_ORDER);
     JSTSP_ENTER(ctx);
     const bool host = memspace == JSTSP_HOST, want_ce = ce_out != nullptr;
-    const size_t need = sadmm64_bytes(Mr, Mt, batch, Imax, host, want_ce);
-    if (need > P64_WS_LIMIT) {
-        int fit = batch;
-        while (fit > 1 && sadmm64_bytes(Mr, Mt, fit, Imax, host, want_ce) > P64_WS_LIMIT) fit = fit > 64 ? fit - fit / 16 : fit - 1;
-        set_error("%s: the float64 workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", nmf,
-                  (double)need / (double)((size_t)1 << 30), fit);
-        return JSTSP_E_UNSUPPORTED;
-    }
     hipStream_t st = ctx->stream;
-    Slab s(st);
-    JSTSP_TRY(s.reserve(need, nmf));
-    const size_t z2 = sizeof(double2), nm1 = (size_t)Mr * Mt, nm = nm1 * batch, nce = (size_t)batch * std::max(Imax, 1);
+    const size_t z2 = sizeof(double2), nm1 = (size_t)Mr * Mt, nm = nm1 * batch;
     const double rho = 0.01, tau_s = 0.0001, thr = tau_s / rho;                                          // :12-13
-    const double2 *OH = reinterpret_cast<const double2 *>(OH_), *Dr = reinterpret_cast<const double2 *>(Dr_),
-                  *Dt = reinterpret_cast<const double2 *>(Dt_), *Htrue = reinterpret_cast<const double2 *>(Htrue_);
-    double2 *Sdev = reinterpret_cast<double2 *>(S_out);
-    double *ce = ce_out;
-    if (host) {
-        double2 *oh = s.get<double2>(nm), *dr = s.get<double2>((size_t)Mr * Mr), *dt = s.get<double2>((size_t)Mt * Mt);
-        Sdev = s.get<double2>(nm);
-        JSTSP_REQUIRE(oh && dr && dt && Sdev, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
-        JSTSP_HIP(hipMemcpyAsync(oh, OH_, nm * z2, hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(dr, Dr_, (size_t)Mr * Mr * z2, hipMemcpyHostToDevice, st));
-        JSTSP_HIP(hipMemcpyAsync(dt, Dt_, (size_t)Mt * Mt * z2, hipMemcpyHostToDevice, st));
-        OH = oh; Dr = dr; Dt = dt;
-        if (want_ce) {
-            double2 *h = s.get<double2>(nm);
-            ce = s.get<double>(nce);
-            JSTSP_REQUIRE(h && ce, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
-            JSTSP_HIP(hipMemcpyAsync(h, Htrue_, nm * z2, hipMemcpyHostToDevice, st));
-            Htrue = h;
-        }
-    }
-    double2 *R = s.get<double2>(nm), *Z = s.get<double2>(nm), *RHS = s.get<double2>(nm), *P = s.get<double2>(nm), *T = s.get<double2>(nm),
-            *AhOH = s.get<double2>(nm);
-    double2 *Gg = s.get<double2>((size_t)Mr * Mr), *Ur = s.get<double2>((size_t)Mr * Mr), *Gc = s.get<double2>((size_t)Mt * Mt),
-            *Uc = s.get<double2>((size_t)Mt * Mt);
-    double *lr = s.get<double>(Mr), *lt = s.get<double>(Mt);
-    double2 *zws = s.get<double2>(sadmm64_zws(Mr, Mt, batch));
-    JSTSP_REQUIRE(R && Z && RHS && P && T && AhOH && Gg && Ur && Gc && Uc && lr && lt && zws, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
-    double2 *Dd = nullptr;
-    double *num = nullptr, *den = nullptr;
+    const double2 *OH, *Dr, *Dt, *Htrue = nullptr;
+    double2 *Sdev, *R, *Z, *RHS, *P, *T, *AhOH, *Gg, *Ur, *Gc, *Uc, *zws, *Dd = nullptr;
+    double *ce = nullptr, *lr, *lt, *num = nullptr, *den = nullptr;
     Svt64 sv;
-    if (want_ce) {
-        Dd = s.get<double2>(nm); num = s.get<double>(batch); den = s.get<double>(batch);
-        sv.init(s, Mr, Mt, batch);
-        sv.freeze = true;                   // a trial's bits do not depend on the batch around it, also for 64 < min(Mr, Mt)
-        JSTSP_REQUIRE(Dd && num && den && sv.lam, JSTSP_E_NOMEM, "%s: workspace accounting error", nmf);
-    }
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
+        const size_t e = nm1 * b, rr = (size_t)Mr * Mr, tt = (size_t)Mt * Mt;
+        OH = w.in(reinterpret_cast<const double2 *>(OH_), e, host);
+        Dr = w.in(reinterpret_cast<const double2 *>(Dr_), rr, host);
+        Dt = w.in(reinterpret_cast<const double2 *>(Dt_), tt, host);
+        Sdev = w.out(reinterpret_cast<double2 *>(S_out), e, host);
+        for (double2 **p : {&R, &Z, &RHS, &P, &T, &AhOH}) *p = w.get<double2>(e);
+        Gg = w.get<double2>(rr); Ur = w.get<double2>(rr); Gc = w.get<double2>(tt); Uc = w.get<double2>(tt);
+        lr = w.get<double>(Mr); lt = w.get<double>(Mt);
+        zws = w.get<double2>(sadmm64_zws(Mr, Mt, b));
+        if (want_ce) {
+            Htrue = w.in(reinterpret_cast<const double2 *>(Htrue_), e, host);
+            ce = w.out(ce_out, (size_t)b * std::max(Imax, 1), host);
+            Dd = w.get<double2>(e); num = w.get<double>(b); den = w.get<double>(b);
+            sv.layout(w, Mr, Mt, b);
+        }
+    }));
+    sv.freeze = true;                       // a trial's bits do not depend on the batch around it, also for 64 < min(Mr, Mt)
     const long long snm = (long long)nm1, tot = (long long)nm;
     const Mat64 Drm{Dr, 0, Mr}, Dtm{Dt, 0, Mt}, Urm{Ur, 0, Mr}, Ucm{Uc, 0, Mt};
 
     // ---- setup: the factor Grams and their eigen-decompositions, shared by the batch
     JSTSP_TRY(zgemm64(st, 'C', 'N', Mr, Mr, Mr, 1, Drm, Drm, Gg, 0, Mr, zws));                           // Dr^H Dr
     JSTSP_TRY(zgemm64(st, 'C', 'N', Mt, Mt, Mt, 1, Dtm, Dtm, Gc, 0, Mt, zws));                           // Dt^H Dt = conj(Gt_)
-    JSTSP_TRY(sadmm64_eig(st, Mr, Gg, Ur, lr));
-    JSTSP_TRY(sadmm64_eig(st, Mt, Gc, Uc, lt));
+    JSTSP_TRY(eig64(st, Mr, 1, Gg, Ur, lr, true));
+    JSTSP_TRY(eig64(st, Mt, 1, Gc, Uc, lt, true));
     {
         std::vector<double> hl((size_t)Mr + Mt);
         JSTSP_HIP(hipMemcpyAsync(hl.data(), lr, Mr * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -213,9 +149,9 @@ extern "C" int jstsp_sparse_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
         if (want_ce) {                                                                                   // :32
             JSTSP_TRY(zgemm64(st, 'N', 'N', Mr, Mt, Mr, batch, Drm, Mat64{Sdev, snm, Mr}, P, snm, Mr, zws));
             JSTSP_TRY(zgemm64(st, 'N', 'C', Mr, Mt, Mt, batch, Mat64{P, snm, Mr}, Dtm, T, snm, Mr, zws));
-            hipLaunchKernelGGL(sadmm64_diff_kernel, sa_grid(tot), dim3(256), 0, st, tot, T, Htrue, Dd);
+            hipLaunchKernelGGL(diff64_kernel, sa_grid(tot), dim3(256), 0, st, tot, T, Htrue, Dd);
             JSTSP_TRY(sv.lambda_max(st, Dd, num));
-            hipLaunchKernelGGL(sadmm64_ratio_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, num, den, ce);
+            hipLaunchKernelGGL(ratio64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, num, den, ce);
         }
         // (the last iteration's R and Z feed nothing that is returned: S and convergence_error are complete before them)
         if (it + 1 < Imax) {
@@ -230,8 +166,8 @@ extern "C" int jstsp_sparse_admm_f64(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
         JSTSP_HIP(hipGetLastError());
     }
     if (host) {
-        JSTSP_HIP(hipMemcpyAsync(S_out, Sdev, nm * z2, hipMemcpyDeviceToHost, st));
-        if (want_ce && Imax > 0) JSTSP_HIP(hipMemcpyAsync(ce_out, ce, (size_t)batch * Imax * sizeof(double), hipMemcpyDeviceToHost, st));
+        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sdev, nm));
+        if (want_ce && Imax > 0) JSTSP_TRY(s.copy_back(ce_out, ce, (size_t)batch * Imax));
     }
     JSTSP_HIP(hipStreamSynchronize(st));
     return 0;

@@ -1,11 +1,9 @@
-// The float64 singular-value threshold shared by proposed64.hip and mc64.hip (internal): the per-call workspace slab, the in-LDS
-// two-sided Jacobi for Gram orders n <= 64 and the steps Y = svt(Z, thr), lambda_max(Z Z^H) built on it and on zgemm64.hip.
+// The float64 singular-value threshold shared by proposed64.hip, mc64.hip and sparse_admm64.hip (internal): the in-LDS two-sided
+// Jacobi for Gram orders n <= 64 and the steps Y = svt(Z, thr), lambda_max(Z Z^H) built on it and on zgemm64.hip.
 // Everything sits in an anonymous namespace: each file that includes this compiles kernels of its own (no relocatable device code).
 #pragma once
+#include "ws64.h"
 #include "zgemm64.h"
-#include "solver_common.h"
-
-#include <algorithm>
 
 namespace jstsp {
 namespace {
@@ -13,10 +11,6 @@ namespace {
 constexpr int P64_LDS_ORDER = 64;        // largest Gram order of the in-LDS Jacobi
 constexpr int P64_MAX_ORDER = 512;       // largest Gram order at all
 constexpr int P64_SWEEPS = 30;
-constexpr size_t P64_WS_LIMIT = (size_t)24 << 30;
-
-__device__ __forceinline__ double2 zmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 zconj(double2 a) { return make_double2(a.x, -a.y); }
 
 // ---- two-sided cyclic Jacobi in LDS ------------------------------------------------------------------------------------------
 // round r of the circle ordering of n players (n even): slot s meets slot n - 1 - s, player 0 fixed, the others rotate by r
@@ -153,50 +147,49 @@ __global__ __launch_bounds__(256) void svt_scale64_kernel(int n, const double *t
     }
 }
 
-// ---- workspace: one stream-ordered slab, bump allocation ----------------------------------------------------------------------
-struct Slab {
-    hipStream_t st;
-    char *base = nullptr;
-    size_t cap = 0, off = 0;
-    explicit Slab(hipStream_t s) : st(s) {}
-    ~Slab() { if (base) (void)hipFreeAsync(base, st); }
-    static size_t rnd(size_t b) { return (b + 255) & ~(size_t)255; }
-    int reserve(size_t bytes, const char *nm)
-    {
-        const hipError_t e = hipMallocAsync((void **)&base, std::max<size_t>(bytes, 256), st);
-        if (e != hipSuccess) { base = nullptr; set_error("%s: hipMallocAsync(%zu) failed: %s", nm, bytes, hipGetErrorString(e)); return JSTSP_E_NOMEM; }
-        cap = bytes;
+// D = X - H, n elements
+__global__ __launch_bounds__(256) void diff64_kernel(long long n, const double2 *X, const double2 *H, double2 *D)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const double2 x = X[e], h = H[e];
+        D[e] = make_double2(x.x - h.x, x.y - h.y);
+    }
+}
+
+// ce(it, t) = num[t] / den[t] (IEEE: x / 0 = Inf, 0 / 0 = NaN, as the reference); ce laid out Imax per trial
+__global__ __launch_bounds__(256) void ratio64_kernel(int batch, int Imax, int it, const double *num, const double *den, double *ce)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < batch) ce[(long long)t * Imax + it] = num[t] / den[t];
+}
+
+// U, lam of nmat Hermitian matrices G of order n, n * n elements apart (n <= 64: in LDS, asynchronous; above: vamp64.hip's
+// Jacobi, which synchronises; freeze: zgemm64.h, eig64_global)
+int eig64(hipStream_t st, int n, int nmat, const double2 *G, double2 *U, double *lam, bool freeze)
+{
+    if (n <= P64_LDS_ORDER) {
+        const size_t sh = jacobi_lds_bytes(n, true);
+        JSTSP_HIP(hipFuncSetAttribute((const void *)jacobi64_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        hipLaunchKernelGGL(jacobi64_lds_kernel<true>, dim3(nmat), dim3(256), sh, st, n, G, (long long)n * n, U, lam);
+        JSTSP_HIP(hipGetLastError());
         return 0;
     }
-    template <class T> T *get(size_t n)
-    {
-        const size_t b = rnd(n * sizeof(T));
-        if (off + b > cap) return nullptr;          // (every caller reserves what it sums with the same rnd(): cannot happen)
-        T *p = reinterpret_cast<T *>(base + off);
-        off += b;
-        return p;
-    }
-};
+    return eig64_global(st, n, nmat, G, (long long)n * n, U, lam, freeze);
+}
 
-// svt of `batch` matrices Z (N x M) with thresholds thr[t * thr_stride]: the arrays it needs and the steps
+// svt of `batch` matrices Z (N x M) with thresholds thr[t * thr_stride]: the arrays it needs (layout) and the steps
 struct Svt64 {
     int N, M, n, batch;
     bool left;              // n = N: G = Z Z^H, Y = Q Z; otherwise G = Z^H Z, Y = Z Q
     bool freeze = false;    // n > 64: a matrix that has converged is not swept on with its batch mates (zgemm64.h: eig64_global)
     double2 *G, *U, *Uf, *Q, *ws;
     double *lam;
-    static size_t bytes(int N, int M, int batch)
-    {
-        const size_t n = std::min(N, M), nn = n * n * batch;
-        return 4 * Slab::rnd(nn * sizeof(double2)) + Slab::rnd(std::max<size_t>(1, ws_elems(N, M, batch)) * sizeof(double2)) +
-               Slab::rnd(n * batch * sizeof(double));
-    }
     static size_t ws_elems(int N, int M, int batch)
     {
         const int n = std::min(N, M), k = std::max(N, M);
         return std::max(std::max(zgemm64_ws_elems(n, n, k, batch), zgemm64_ws_elems(n, n, n, batch)), zgemm64_ws_elems(N, M, n, batch));
     }
-    void init(Slab &s, int N_, int M_, int batch_)
+    void layout(Slab &s, int N_, int M_, int batch_)
     {
         N = N_; M = M_; batch = batch_; n = std::min(N, M); left = N <= M;
         const size_t nn = (size_t)n * n * batch;
@@ -209,18 +202,6 @@ struct Svt64 {
         const Mat64 z{Z, (long long)N * M, N};
         return left ? zgemm64(st, 'N', 'C', n, n, M, batch, z, z, Gout, (long long)n * n, n, ws)
                     : zgemm64(st, 'C', 'N', n, n, N, batch, z, z, Gout, (long long)n * n, n, ws);
-    }
-    // U, lam of G (n <= 64: in LDS, asynchronous; above: vamp64.hip's Jacobi, synchronises)
-    int eig(hipStream_t st) const
-    {
-        if (n <= P64_LDS_ORDER) {
-            const size_t sh = jacobi_lds_bytes(n, true);
-            JSTSP_HIP(hipFuncSetAttribute((const void *)jacobi64_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-            hipLaunchKernelGGL(jacobi64_lds_kernel<true>, dim3(batch), dim3(256), sh, st, n, G, (long long)n * n, U, lam);
-            JSTSP_HIP(hipGetLastError());
-            return 0;
-        }
-        return eig64_global(st, n, batch, G, (long long)n * n, U, lam, freeze);
     }
     // lmax[t] = lambda_max of the Gram of Z[t]
     int lambda_max(hipStream_t st, const double2 *Z, double *lmax) const
@@ -242,7 +223,7 @@ struct Svt64 {
     {
         const long long snn = (long long)n * n, snm = (long long)N * M;
         JSTSP_TRY(gram(st, Z, G));
-        JSTSP_TRY(eig(st));
+        JSTSP_TRY(eig64(st, n, batch, G, U, lam, freeze));
         hipLaunchKernelGGL(svt_scale64_kernel, dim3((unsigned)std::min((n * n + 255) / 256, 64), batch), dim3(256), 0, st, n, thr, thr_stride, lam, U, Uf);
         JSTSP_HIP(hipGetLastError());
         JSTSP_TRY(zgemm64(st, 'N', 'C', n, n, n, batch, Mat64{Uf, snn, n}, Mat64{U, snn, n}, Q, snn, n, ws));

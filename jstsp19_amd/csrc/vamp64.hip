@@ -17,6 +17,7 @@
 // The structure is that of vamp.hip: the LMMSE stage in complex arithmetic on the Kronecker factors, Phi = kron(Gb.', Af) never formed
 // (a dense dictionary is the case G2 = 1, Gb = 1); both branches M <= N (:402-406) and M > N (:407-411).
 #include "vamp_kernels.h"
+#include "ws64.h"
 #include "zgemm64.h"
 #include <algorithm>
 #include <vector>
@@ -28,8 +29,6 @@ struct MatD {
     const double2 *p; long long st; int ld;
 };
 
-__device__ __forceinline__ double2 zmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 zconj(double2 a) { return make_double2(a.x, -a.y); }
 __device__ __forceinline__ double2 zadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 
 // C[t] (m x n) = op(A[t]) op(B[t]) + beta D[t]; opX: 0 = as stored, 1 = conjugate transpose; column-major
