@@ -717,6 +717,7 @@ int jstsp_rate_c64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, 
  *    host arrays) and a JSTSP_HOST call at exit.
  *  - convergence_error(i, 1:2) from lambda_max of the n x n Grams of V1, V2, X (the same Jacobi); skipped when ce_out is NULL.
  *  - type: JSTSP_TYPE_APPROXIMATE only; JSTSP_TYPE_STD returns JSTSP_E_UNSUPPORTED (use jstsp_proposed_algorithm_c64).
+ *    Alg. 1 ('std') in float64 is an entry of its own, jstsp_proposed_std_f64 below, which takes the least-squares factors.
  *  - workspace: about 72 MiB per trial at BASELINE configs[1] with per-trial B; above 24 GiB the call returns
  *    JSTSP_E_UNSUPPORTED with the largest batch that fits in the message (the Python wrappers chunk the batch).
  * Asserted (tests/test_gpu_f64_gemm.py, test_gpu_f64_proposed.py, test_gpu_f64_fullsize.py): the two kernel-level entries
@@ -769,6 +770,40 @@ int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c6
 int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *Y,
                  const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB,
                  jstsp_c64 *S_out, double *rcond_out, int memspace);
+
+/* ---- proposed_algorithm 'std' (Alg. 1) in float64 -----------------------------------------------------
+ * The 'std' branch of proposed_algorithm.m / proposed_algorithm_angles.m (:29, :53; angles :29, :64) evaluated in FLOAT64 on the
+ * device (csrc/proposed64.hip): the iteration of jstsp_proposed_algorithm_f64 - same kernels, same svt guard, same doubles
+ * everywhere - with the gradient step on V replaced by the least-squares solve v = U\(L\k), which for K2 = kron(B.', A) of full
+ * column rank is V = pinv(A) K pinv(B): two f64-MFMA products per iteration.  G_A, G_B, the carried V, Res and RRes are not
+ * allocated; convergence_error(:, 3) stays 0 (proposed_algorithm.m:6).  Arguments, layouts, NULL-able outputs (Y_out, ce_out,
+ * indx_S) and both memspaces as jstsp_proposed_algorithm_f64, plus:
+ *  - PA, PB: NULL, or pinv(A) (Gr x N) and pinv(B) (M x G2), column-major, in the call's memspace, shared exactly as A / B are
+ *    (strideA == 0: one PA; otherwise one per trial, Gr N elements apart; likewise PB).  A NULL factor is computed by the
+ *    call with the routine of jstsp_pinv_f64 (a shared factor is inverted once); a given one is used as it is, so a caller
+ *    that solves several times on the same dictionaries (plot_errorVSsnr_approx.m: Imax 10 / 30 / 50) inverts them once.
+ *    Passing the output of jstsp_pinv_f64 returns the bits of the NULL call.
+ *  - rcond_out: NULL or double[2] in the call's memspace, as jstsp_ls_f64: the smallest rcond over the A factors and over the
+ *    B factors the call computed; NaN for a side whose factor was given.
+ *  - rank rule: N >= Gr and M >= G2, else JSTSP_E_UNSUPPORTED (the rule of jstsp_proposed_algorithm_c32 'std').  A computed
+ *    factor of which jstsp_pinv_f64's drop rule keeps fewer singular values than it has columns (A) / rows (B), or that holds
+ *    a NaN or Inf, returns JSTSP_E_ILLCOND before the first iteration; the message names the factor and the trial.
+ *  - limits: min(N, M) <= 512, fewer than 2^31 entries per trial, batch <= 65535, and for a factor the call inverts those of
+ *    jstsp_pinv_f64 (min(rows, cols) <= 512, max(rows, cols) <= 8192); otherwise, or above 24 GiB of workspace,
+ *    JSTSP_E_UNSUPPORTED (the message names the largest batch that fits).
+ *  - no atomics in any sum: a repeated call returns the same bits; for min(N, M) <= 64 a trial's bits do not depend on the
+ *    batch around it (above, the note on the global Jacobi of jstsp_proposed_algorithm_f64 applies).  A call that computes a
+ *    factor synchronises the context's stream (jstsp_pinv_f64).
+ * Asserted (tests/test_gpu_std64.py): S and Y within 1e-10 of max|ref|, convergence_error within 1e-8 of oracle/solvers.py
+ * proposed_algorithm(..., 'std') (measured values: DESIGN.md section 9h). */
+int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                           const jstsp_c64 *subY, const double *Omega,
+                           const jstsp_c64 *A, long long strideA,
+                           const jstsp_c64 *B, long long strideB,
+                           const jstsp_c64 *PA, const jstsp_c64 *PB,
+                           int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                           const int32_t *indx_S,
+                           jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace);
 
 /* ---- joint OMP and matrix completion in float64 -----------------------------------------------------
  * The "OMP with MMV" column (plot_errorVSsnr.m:116-117) and the TSSR / "SVT-based" recipe (:151-162) evaluated in FLOAT64 on the

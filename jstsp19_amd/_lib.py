@@ -126,6 +126,11 @@ SIGNATURES["jstsp_pinv_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p,
 SIGNATURES["jstsp_ls_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
                                       c_void_p, c_void_p, c_int])
 
+# Alg. 1 ('std') in float64 (csrc/proposed64.hip): the jstsp_proposed_algorithm_f64 list with PA, PB for `type` and rcond_out
+SIGNATURES["jstsp_proposed_std_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
+                                                c_void_p, c_ll, c_void_p, c_void_p, c_int, c_dp, c_dp, c_dp, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_int])
+
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes
     # (pointers are void* here, so the two are one list)

@@ -15,8 +15,7 @@
 // on the batch around it); whether any matrix of the call is still rotating is read on the host once per sweep, so a call
 // synchronises the context's stream.  Drop rule (pinv.m): sigma_k is kept iff sigma_k > max(rows, cols) * eps(sigma_max),
 // eps(x) = 2^(floor(log2 x) - 52) - one place, p64_sigma_kernel.  No atomics anywhere: a repeated call returns the same bits.
-#include "ws64.h"
-#include "zgemm64.h"
+#include "pinv64.h"
 
 #include <algorithm>
 
@@ -24,20 +23,9 @@ namespace jstsp {
 
 namespace {
 
-constexpr int PV_MAX_ORDER = 512;        // min(rows, cols): the float64 family's largest order (proposed64.hip: P64_MAX_ORDER)
-constexpr int PV_MAX_LONG = 8192;        // max(rows, cols)
 constexpr int PV_SWEEPS = 40;            // cap (the tested inputs stop after 6 to 12)
 constexpr int PV_WAVE_ROWS = 512;        // columns up to this length: one wave per pair; longer: one workgroup per pair
 constexpr double PV_EPS = 2.220446049250313e-16;
-
-struct PvMeta {
-    double sc;          // the power of two the operand was multiplied by
-    double fro2;        // squared Frobenius norm of the scaled operand
-    int bad;            // a non-finite entry: the matrix is not decomposed, its outputs are NaN
-    int done;           // a whole sweep met no significant pair
-    int rot;            // the running sweep met one
-    int pad;
-};
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -251,32 +239,20 @@ __global__ void p64_min_kernel(int cnt, const double *v, double *out)
     *out = r;
 }
 
-bool pv_shape_ok(int rows, int cols) { return std::min(rows, cols) <= PV_MAX_ORDER && std::max(rows, cols) <= PV_MAX_LONG; }
+}  // namespace
 
-size_t pv_gemm_ws(int rows, int cols, int count)
+// ---- what the float64 entry points that invert a factor share (pinv64.h) -------------------------------------------------------
+bool pinv64_shape_ok(int rows, int cols) { return std::min(rows, cols) <= PV_MAX_ORDER && std::max(rows, cols) <= PV_MAX_LONG; }
+
+size_t pinv64_gemm_ws(int rows, int cols, int count)
 {
     const int m = std::max(rows, cols), n = std::min(rows, cols);
     return std::max<size_t>(1, rows >= cols ? zgemm64_ws_elems(n, m, n, count) : zgemm64_ws_elems(m, n, n, count));
 }
 
-// the arrays of pinv64_run for `count` matrices (rows x cols)
-struct Pinv64 {
-    double2 *W, *V, *Vs, *ws;
-    PvMeta *meta;
-    int *any;
-    void layout(Slab &s, int rows, int cols, int count)
-    {
-        const size_t m = std::max(rows, cols), n = std::min(rows, cols);
-        W = s.get<double2>(m * n * count); V = s.get<double2>(n * n * count); Vs = s.get<double2>(n * n * count);
-        meta = s.get<PvMeta>(count);
-        any = s.get<int>(1);
-        ws = s.get<double2>(pv_gemm_ws(rows, cols, count));
-    }
-};
-
 // P[t] (cols x rows, contiguous) = pinv(A[t]) (rows x cols, sA elements apart), t < count; rcond / rank: nullptr or device [count].
 // Synchronises the stream once per sweep.
-int pinv64_run(hipStream_t st, const Pinv64 &w, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond,
+int pinv64_run(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond,
                int32_t *rank)
 {
     const int m = std::max(rows, cols), n = std::min(rows, cols);
@@ -310,7 +286,14 @@ int pinv64_run(hipStream_t st, const Pinv64 &w, int rows, int cols, int count, c
     return 0;
 }
 
-}  // namespace
+// out[0] = the smallest of v[0 .. cnt) on the device, NaN when one of them is NaN
+int pinv64_min(hipStream_t st, int cnt, const double *v, double *out)
+{
+    hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, cnt, v, out);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace jstsp
 
 using namespace jstsp;
@@ -325,7 +308,7 @@ int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c6
     JSTSP_ENTER(ctx);
     JSTSP_REQUIRE(rows > 0 && cols > 0 && batch > 0, JSTSP_E_SHAPE, "%s: bad shape", nm);
     JSTSP_REQUIRE(A_ && P_, JSTSP_E_NULL, "%s: NULL argument", nm);
-    JSTSP_REQUIRE(pv_shape_ok(rows, cols) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+    JSTSP_REQUIRE(pinv64_shape_ok(rows, cols) && batch <= 65535, JSTSP_E_UNSUPPORTED,
                   "%s: %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d and batch <= 65535", nm, rows, cols, batch, PV_MAX_ORDER,
                   PV_MAX_LONG);
     const bool host = memspace == JSTSP_HOST;
@@ -365,7 +348,7 @@ int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
     JSTSP_REQUIRE(Y_ && A_ && B_ && S_out, JSTSP_E_NULL, "%s: NULL argument", nm);
     JSTSP_REQUIRE((strideA == 0 || strideA == (long long)N * Gr) && (strideB == 0 || strideB == (long long)G2 * M), JSTSP_E_ARG,
                   "%s: a factor stride is 0 (shared) or the size of one factor", nm);
-    JSTSP_REQUIRE(pv_shape_ok(N, Gr) && pv_shape_ok(G2, M) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+    JSTSP_REQUIRE(pinv64_shape_ok(N, Gr) && pinv64_shape_ok(G2, M) && batch <= 65535, JSTSP_E_UNSUPPORTED,
                   "%s: A %d x %d, B %d x %d, batch %d: need min(rows, cols) <= %d, max(rows, cols) <= %d per factor and batch <= 65535", nm, N, Gr, G2, M,
                   batch, PV_MAX_ORDER, PV_MAX_LONG);
     const bool host = memspace == JSTSP_HOST;
@@ -399,9 +382,8 @@ int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
                       Gr, ws));
     if (rcond_out) {
         if (host) rc2 = rcd;
-        hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nA, rcA, rc2);
-        hipLaunchKernelGGL(p64_min_kernel, dim3(1), dim3(1), 0, st, nB, rcB, rc2 + 1);
-        JSTSP_HIP(hipGetLastError());
+        JSTSP_TRY(pinv64_min(st, nA, rcA, rc2));
+        JSTSP_TRY(pinv64_min(st, nB, rcB, rc2 + 1));
         if (host) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
     }
     if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), S, (size_t)Gr * G2 * batch));

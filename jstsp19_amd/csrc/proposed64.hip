@@ -17,6 +17,15 @@
 // device when a sweep rotates nothing (at most 30 sweeps) - nothing is read back inside the iteration loop.  For 64 < n <= 512 the
 // global-memory Jacobi of vamp64.hip, which reads one norm per sweep on the host: such a call synchronises the stream.
 // Every reduction is a fixed-order sum inside one workgroup per trial: a trial's bits depend neither on the batch nor on the run.
+//
+// jstsp_proposed_std_f64 - Alg. 1, the 'std' branch of the same two files (:29, :53; angles :29, :64) in float64: the gradient step
+// on V is replaced by the least-squares solve v = U\(L\k), which for a K2 = kron(B.', A) of full column rank is
+//                  V = pinv(A) K pinv(B)                                                                                (:53)
+// two products of the shapes of A^H K and T B^H.  The factors come from the Hestenes route of pinv64.hip (pinv64.h), once per
+// call - once for the batch when a factor is shared - or from the caller, who may hand them from one call to the next.  The
+// rest of the iteration is the list above, kernel for kernel; G_A, G_B, the carried V, Res and RRes do not exist and
+// convergence_error(:, 3) stays 0 (:6).
+#include "pinv64.h"
 #include "svt64.h"
 
 #include <algorithm>
@@ -143,6 +152,25 @@ __global__ __launch_bounds__(256) void step_v64_kernel(int g, const Par64 *par, 
     }
     dv = wg_sum(dv, sh);
     if (threadIdx.x == 0 && ce3) ce3[t] = dv / nv;              // Inf at i = 1 (V_prev = 0), NaN for 0 / 0 as the reference
+}
+
+// 'std': S = soft(V, tau_S/rho) (.* the cumulative mask of _angles), V = pinv(A) K pinv(B)                               (:56, angles :68)
+__global__ __launch_bounds__(256) void soft_mask64_kernel(long long g, const Par64 *par, const double2 *V, double2 *S, const int32_t *rank, int cnt)
+{
+    const long long o = (long long)blockIdx.y * g;
+    const double ts = par[blockIdx.y].tS;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < g; e += (long long)gridDim.x * 256) {
+        const double2 v = V[o + e];
+        const double mr = fmax(fabs(v.x) - ts, 0.0), mi = fmax(fabs(v.y) - ts, 0.0);
+        double2 s = make_double2(v.x > 0.0 ? mr : (v.x < 0.0 ? -mr : 0.0), v.y > 0.0 ? mi : (v.y < 0.0 ? -mi : 0.0));      // sign(0) = 0
+        if (rank && !(rank[o + e] < cnt)) s = make_double2(0.0, 0.0);
+        S[o + e] = s;
+    }
+}
+
+__global__ void fill64_kernel(int n, double *p, double v)
+{
+    if ((int)threadIdx.x < n) p[threadIdx.x] = v;
 }
 
 // ce(i, 1) = lambda_max(V1) / lambda_max(X), ce(i, 2) = lambda_max(V2) / lambda_max(X); ce laid out Imax x 3 per trial
@@ -300,6 +328,150 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
         JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g));
         if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
         if (want_ce) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
+        JSTSP_HIP(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                           const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_,
+                           const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                           const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace)
+{
+    const char *nmf = "proposed_algorithm 'std' (float64)";
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
+    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE((strideA == 0 || strideA >= (long long)N * Gr) && (strideB == 0 || strideB >= (long long)G2 * M), JSTSP_E_SHAPE,
+                  "%s: a factor stride is 0 (shared) or at least the size of one factor", nmf);
+    JSTSP_REQUIRE(N >= Gr && M >= G2, JSTSP_E_UNSUPPORTED,
+                  "%s: K2 = kron(B.', A) must have full column rank (N >= Gr, M >= G2); the under-determined U\\(L\\k) of the reference "
+                  "returns a basic, not least-squares, solution", nmf);
+    JSTSP_REQUIRE(std::min(N, M) <= P64_MAX_ORDER, JSTSP_E_UNSUPPORTED, "%s: min(N, M) = %d: the float64 eigen-decomposition is limited to order %d", nmf,
+                  std::min(N, M), P64_MAX_ORDER);
+    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31) && (long long)N * M < (1ll << 31) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
+    JSTSP_REQUIRE((PA_ || pinv64_shape_ok(N, Gr)) && (PB_ || pinv64_shape_ok(G2, M)), JSTSP_E_UNSUPPORTED,
+                  "%s: A %d x %d, B %d x %d: a factor the call inverts needs min(rows, cols) <= %d and max(rows, cols) <= %d", nmf, N, Gr, G2, M,
+                  PV_MAX_ORDER, PV_MAX_LONG);
+    const bool host = memspace == JSTSP_HOST, angles = indx_S_ != nullptr, want_ce = ce_out != nullptr;
+    hipStream_t st = ctx->stream;
+    const size_t nm1 = (size_t)N * M, g1 = (size_t)Gr * G2, nm = nm1 * batch, g = g1 * batch;
+    const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
+    std::vector<Par64> hp(batch);
+    for (int t = 0; t < batch; ++t) hp[t] = Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]};
+
+    const Par64 *par;
+    const double2 *subY, *A, *B, *PA, *PB;
+    const double *Omega;
+    const int32_t *indx = nullptr;
+    double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *V, *T, *W, *gws, *PAc = nullptr, *PBc = nullptr;
+    double *ced, *lx, *l1, *l2, *ce3, *rcA = nullptr, *rcB = nullptr, *rcd;
+    int32_t *rank = nullptr, *rkA = nullptr, *rkB = nullptr;
+    Pinv64 pvA, pvB;
+    Svt64 sv;
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
+        const size_t enm = nm1 * b, eg = g1 * b;
+        const int bA = strideA ? b : 1, bB = strideB ? b : 1;
+        par = w.in(hp.data(), b, true);
+        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
+        Omega = w.in(Omega_, enm, host);
+        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
+        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
+        if (PA_) PA = w.in(reinterpret_cast<const double2 *>(PA_), (size_t)Gr * N * bA, host);
+        else {
+            PA = PAc = w.get<double2>((size_t)Gr * N * bA); rcA = w.get<double>(bA); rkA = w.get<int32_t>(bA);
+            pvA.layout(w, N, Gr, bA);
+        }
+        if (PB_) PB = w.in(reinterpret_cast<const double2 *>(PB_), (size_t)M * G2 * bB, host);
+        else {
+            PB = PBc = w.get<double2>((size_t)M * G2 * bB); rcB = w.get<double>(bB); rkB = w.get<int32_t>(bB);
+            pvB.layout(w, G2, M, bB);
+        }
+        if (angles) indx = w.in(indx_S_, eg, host);
+        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
+        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
+        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
+        rcd = w.out(rcond_out, 2, host);
+        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
+        V = w.get<double2>(eg);
+        T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
+        const int shp[4][3] = {{Gr, M, N}, {Gr, G2, M}, {N, G2, Gr}, {N, M, G2}};
+        size_t e = 1;
+        for (const auto &q : shp) e = std::max(e, zgemm64_ws_elems(q[0], q[1], q[2], b));
+        gws = w.get<double2>(e);
+        if (angles) rank = w.get<int32_t>(eg);
+        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
+        sv.layout(w, N, M, b);
+    }));
+    JSTSP_HIP(hipStreamSynchronize(st));            // (hp is this call's own: copied before it goes out of scope on any path)
+
+    // the factors: a shared one is inverted once for the call; one that is not of full column rank ends the call
+    if (PAc) JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, A, strideA, PAc, rcA, rkA));
+    if (PBc) JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, B, strideB, PBc, rcB, rkB));
+    for (int f = 0; f < 2; ++f) {
+        const int cnt = f ? nB : nA, full = f ? G2 : Gr;
+        const double *rc = f ? rcB : rcA;
+        const int32_t *rk = f ? rkB : rkA;
+        if (!rk) continue;
+        std::vector<int32_t> hk(cnt);
+        std::vector<double> hr(cnt);
+        JSTSP_HIP(hipMemcpyAsync(hk.data(), rk, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipMemcpyAsync(hr.data(), rc, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+        for (int t = 0; t < cnt; ++t) {
+            JSTSP_REQUIRE(hr[t] == hr[t], JSTSP_E_ILLCOND, "%s: factor %s of trial %d%s holds a NaN or Inf", nmf, f ? "B" : "A", t,
+                          cnt == 1 && batch > 1 ? " (shared by the batch)" : "");
+            JSTSP_REQUIRE(hk[t] >= full, JSTSP_E_ILLCOND,
+                          "%s: factor %s of trial %d%s has rank %d < %d (rcond of the kept part %.3g): K2 = kron(B.', A) is not of full column rank", nmf,
+                          f ? "B" : "A", t, cnt == 1 && batch > 1 ? " (shared by the batch)" : "", (int)hk[t], full, hr[t]);
+        }
+    }
+    if (rcond_out) {
+        if (rcA) JSTSP_TRY(pinv64_min(st, nA, rcA, rcd));
+        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd, __builtin_nan(""));
+        if (rcB) JSTSP_TRY(pinv64_min(st, nB, rcB, rcd + 1));
+        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd + 1, __builtin_nan(""));
+        JSTSP_HIP(hipGetLastError());
+    }
+
+    for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * sizeof(double2), st));
+    JSTSP_HIP(hipMemsetAsync(ce3, 0, batch * sizeof(double), st));                                     // convergence_error(:, 3) = 0 (:6)
+    if (angles) {
+        hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
+        hipLaunchKernelGGL(rank64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (int)g1, indx, rank);
+    }
+    const long long sNM = (long long)nm1, sG = (long long)g1;
+    const Mat64 Am{A, strideA, N}, Bm{B, strideB, G2}, PAm{PA, strideA ? (long long)Gr * N : 0, Gr}, PBm{PB, strideB ? (long long)M * G2 : 0, M};
+    const dim3 gnm = egrid((long long)nm1, batch);
+    for (int it = 0; it < Imax; ++it) {
+        const int cnt = (int)std::min<long long>(10 + 5ll * (it + 1), (long long)g1);                  // angles :36
+        hipLaunchKernelGGL(form_z64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, V1, Z);
+        JSTSP_TRY(sv.apply(st, Z, &par->tY, (long long)(sizeof(Par64) / sizeof(double)), Y));          // :35
+        hipLaunchKernelGGL(update_x64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
+        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, PAm, Mat64{K, sNM, N}, T, (long long)Gr * M, Gr, gws));       // pinv(A) K
+        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, PBm, V, sG, Gr, gws));      // ... pinv(B)   (:53)
+        hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, par, V, Sd, rank, cnt);
+        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am, Mat64{Sd, sG, Gr}, W, (long long)N * G2, N, gws));       // A S
+        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm, Xs, sNM, N, gws));        // ... B
+        hipLaunchKernelGGL(update_c64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, Xs, Y, Cm, V1, V2);
+        if (want_ce) {
+            JSTSP_TRY(sv.lambda_max(st, X, lx));
+            JSTSP_TRY(sv.lambda_max(st, V1, l1));
+            JSTSP_TRY(sv.lambda_max(st, V2, l2));
+            hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
+        }
+        JSTSP_HIP(hipGetLastError());
+    }
+    if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, st));
+    if (host) {
+        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g));
+        if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
+        if (want_ce) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
+        if (rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
         JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;

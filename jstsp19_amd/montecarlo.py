@@ -442,8 +442,61 @@ def _hip_alg12(inp, Imax):
     return out
 
 
+def _hip_alg12_f64(inp, Imax_list):
+    """``_hip_alg12`` in float64 for every Imax of the list on ONE batch of trials: ``pinv_f64(A)`` and ``pinv_f64(B)`` are
+    computed once and serve the least-squares step of every Alg. 1 solve (``proposed_algorithm_std_f64(..., PA=, PB=)``) and
+    the scoring product ``pinv(A)*Y*pinv(B)`` of both columns (on the f64 matrix pipe: ``correlate_f64`` with the adjoints of
+    the factors).  Alg. 2 is ``proposed_algorithm_f64``; the columns are scored by ``_score_f64``.  Returns one
+    ``(e_std, e_approx)`` per Imax."""
+    from . import solvers as J
+    wide = lambda x: J.colmajor(x.to(torch.complex128))
+    subY, A, B, zb = wide(inp["subY"]), wide(inp["A"]), wide(inp["B"]), wide(inp["Zbar"])
+    Om = J.colmajor(inp["Omega"].to(torch.float64))
+    prm = (inp["tau_X"].numpy(), inp["tau_S"].numpy(), inp["rho"].numpy())
+    PA, PB = J.pinv_f64(A), J.pinv_f64(B)
+    PAh, PBh = J.colmajor(PA.mH), J.colmajor(PB.mH)
+    out = []
+    for Imax in Imax_list:
+        _, Y1, _ = J.proposed_algorithm_std_f64(subY, Om, A, B, int(Imax), *prm, PA=PA, PB=PB, want_ce=False)     # :60
+        _, Y2, _ = J.proposed_algorithm_f64(subY, Om, A, B, int(Imax), *prm, "approximate", want_ce=False)        # :67
+        out.append(tuple(_score_f64(J.correlate_f64(Y, PAh, PBh), zb, "nmse", 0.0) for Y in (Y1, Y2)))           # :61-65, :68-72
+    return out
+
+
+def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed, device, dist, builder):
+    """``run_approx_sweep(precision="f64")``: the (SNR, trial) pairs are sharded over ranks; a batch of trials is built once and
+    solved for every Imax (its Philox key is the sweep index of the point (SNR, Imax_list[0]) of the default sweep, so that
+    column sees the realisations the fp32 sweep sees)."""
+    rank = dist.get_rank() if dist is not None else 0
+    world = dist.get_world_size() if dist is not None else 1
+    nI = len(Imax_list)
+    lo, hi = partition(len(snr_db_list) * n_trials, world, rank)
+    acc = torch.zeros((len(snr_db_list), nI, 3), dtype=torch.float64)
+    item = lo
+    while item < hi:
+        si = item // n_trials
+        t0 = item % n_trials
+        t1 = min(n_trials, t0 + batch, t0 + (hi - item))
+        p = TrainingParams(base.Nt, base.Nr, base.L, base.T, base.ratio, base.clusters, base.rays, float(snr_db_list[si]))
+        if builder == "hip":
+            inp = build_trials_training(p, t0, t1 - t0, seed=seed, sweep_idx=si * nI, device=device)
+        else:
+            inp = builder(p, range(t0, t1), seed, si * nI, device, False)
+        for ii, (e1, e2) in enumerate(_hip_alg12_f64(inp, Imax_list)):
+            acc[si, ii, 0] += float(e1.sum())
+            acc[si, ii, 1] += float(e2.sum())
+            acc[si, ii, 2] += t1 - t0
+        item += t1 - t0
+    if dist is not None:
+        buf = acc.to(device) if dist.get_backend() == "nccl" else acc
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        acc = buf.cpu()
+    mean = torch.clamp(acc[..., :2] / acc[..., 2:3], max=1.0)                              # :76-77
+    return mean.transpose(0, 1).contiguous()
+
+
 def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, batch=64, seed=20190913, device=None,
-                     solve_fn=None, dist=None, builder=None):
+                     solve_fn=None, dist=None, builder=None, precision="f32"):
     """The Alg.1-vs-Alg.2 sweep of plot_errorVSsnr_approx.m:34-85: for each SNR and each Imax, ``n_trials`` fresh
     realisations of wideband_hybBF_comm_system_training, both solver variants, capped NMSE of
     ``pinv(A)*Y*pinv(B)``, mean then ``min(., 1)`` (:76-77).
@@ -453,12 +506,24 @@ def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, 
     defaults to the HIP path; the (sweep point, trial) pairs are sharded over ranks as in ``run_points``.
     ``builder``: None / "hip" - the inputs from the library's own kernels (``jstsp_build_trials_c32`` with the training model
     fields) - or a callable hook as in ``run_points``.
+    ``precision="f64"`` (opt-in; the default "f32" is the behaviour above, unchanged): both columns evaluated and scored in
+    float64 - Alg. 1 by ``proposed_algorithm_std_f64``, Alg. 2 by ``proposed_algorithm_f64``, ``_score_f64``.  The reference
+    draws fresh realisations for every (SNR, Imax) point; here a batch of trials is built once per SNR and solved for every
+    Imax of the list, so that ``pinv_f64(A)`` and ``pinv_f64(B)`` are computed once per batch (``_hip_alg12_f64``).  No
+    ``solve_fn`` hook.
     """
+    if precision not in ("f32", "f64"):
+        raise ValueError("precision must be 'f32' or 'f64'")
+    if precision == "f64" and solve_fn is not None:
+        raise ValueError("precision='f64' solves with the library's float64 entries: no solve_fn")
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     builder = _resolve_builder(builder, device)
+    if precision == "f64":
+        return _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, batch=batch, seed=seed, device=device, dist=dist,
+                                     builder=builder)
     if solve_fn is None:
         solve_fn = _hip_alg12
     pts = [(si, ii) for si in range(len(snr_db_list)) for ii in range(len(Imax_list))]    # loop order of :34-38

@@ -31,7 +31,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "empty_colmajor", "beamformer", "ase", "singular_values",
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
-           "OMP_f64", "omp_kron_f64", "sparse_admm_f64"]
+           "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -849,6 +849,84 @@ def proposed_algorithm_angles_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S,
                                   greedy_nnz=None, *, want_ce=True, ctx=None):
     """:func:`proposed_algorithm_angles` in float64 on the device (see :func:`proposed_algorithm_f64`)."""
     return proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type, indx_S=indx_S, want_ce=want_ce, ctx=ctx)
+
+
+def proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, indx_S=None, PA=None, PB=None, want_ce=True,
+                               info=False, ctx=None):
+    """Alg. 1 - ``proposed_algorithm(..., 'std')`` - evaluated in float64 on the device (include/jstsp.h:
+    jstsp_proposed_std_f64): the least-squares step ``v = U\\(L\\k)`` as ``pinv(A) K pinv(B)``, which needs ``K2`` of full column
+    rank (``N >= Gr``, ``M >= G2``; a rank-deficient factor raises ``JstspError`` with code -6).  Arguments and outputs as
+    :func:`proposed_algorithm_f64`.  ``PA`` / ``PB``: ``None``, or ``pinv(A)`` / ``pinv(B)`` - e.g. from :func:`pinv_f64`, which
+    gives the bits of the ``None`` call - batched exactly as ``A`` / ``B`` are; a caller that solves several times on the same
+    dictionaries inverts them once.  ``info=True`` also returns ``rcond``: float64 (2,), the smallest over the ``A`` and over the
+    ``B`` factors the call inverted, NaN for a side that was given (the smallest over the chunks when the batch is chunked)."""
+    a_sub = _Arg(_wide(subY), np.complex128, "subY")
+    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
+    a_A = _Arg(_wide(A), np.complex128, "A")
+    a_B = _Arg(_wide(B), np.complex128, "B")
+    a_PA = _Arg(_wide(PA), np.complex128, "PA", allow_none=True)
+    a_PB = _Arg(_wide(PB), np.complex128, "PB", allow_none=True)
+    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
+    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
+    Gr, G2 = a_A.C, a_B.R
+    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
+        raise ValueError("Omega must have the shape of subY")
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+    for a_P, a_F, nmP in ((a_PA, a_A, "PA"), (a_PB, a_B, "PB")):
+        if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
+            raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
+    if indx_S is not None:
+        if _is_torch(indx_S):
+            import torch
+            ix2 = indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous()
+        else:
+            ix2 = np.asarray(indx_S).reshape(batch, Gr * G2, 1).astype(np.int32)
+        a_ix = _Arg(ix2, np.int32, "indx_S")
+    sA = _shared_stride(a_A, N * Gr, batch, "A")
+    sB = _shared_stride(a_B, G2 * M, batch, "B")
+    tY, _ = _scalars(tau_Y, batch, "tau_Y")
+    tS, _ = _scalars(tau_S, batch, "tau_S")
+    rh, _ = _scalars(rho, batch, "rho")
+    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_PA, a_PB, a_ix], ctx)
+    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
+    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
+    pce, fce = _out(mem == DEVICE, batch, int(Imax), 3, np.float64, dev) if want_ce else (None, None)
+    # bytes of float64 state per trial (csrc/proposed64.hip): the N x M arrays, V, the products, the svt, the Hestenes arrays of a
+    # per-trial factor, the staged copies of a host call
+    n = min(N, M)
+    per = 16 * (8 * N * M + 2 * Gr * G2 + Gr * M + N * G2 + 20 * n * n)
+    per += 16 * ((2 * N * Gr + 3 * Gr * Gr if sA and a_PA.ptr is None else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and a_PB.ptr is None else 0))
+    if mem == HOST:
+        per += 16 * (2 * N * M + Gr * G2 + 2 * (G2 * M if sB else 0) + 2 * (N * Gr if sA else 0)) + 8 * N * M
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    dp = C.POINTER(C.c_double)
+    rcs = []
+    for t0 in range(0, batch, step):
+        nb = min(step, batch - t0)
+        prc, rc1 = _vec_out(mem == DEVICE, 2, np.float64, dev) if info else (None, None)
+        rc = c._lib.jstsp_proposed_std_f64(
+            c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
+            _off(a_B.ptr, t0 * sB, 16), sB, _off(a_PA.ptr, t0 * (Gr * N if sA else 0), 16), _off(a_PB.ptr, t0 * (M * G2 if sB else 0), 16),
+            int(Imax), tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp),
+            _off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * int(Imax), 8), prc, mem)
+        check(rc, "jstsp_proposed_std_f64")
+        rcs.append(rc1)
+    sq = not a_sub.batched
+    out = (fS(sq), fY(sq), (fce(sq) if want_ce else None))
+    if not info:
+        return out
+    rcond = rcs[0]
+    for r in rcs[1:]:          # (min propagates NaN in numpy and in torch)
+        rcond = np.minimum(rcond, r) if mem == HOST else rcond.minimum(r)
+    return out + (rcond,)
+
+
+def proposed_algorithm_angles_std_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, greedy_nnz=None, *, PA=None, PB=None,
+                                      want_ce=True, info=False, ctx=None):
+    """``proposed_algorithm_angles(..., 'std')`` in float64 on the device (see :func:`proposed_algorithm_std_f64`)."""
+    return proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S=indx_S, PA=PA, PB=PB, want_ce=want_ce,
+                                      info=info, ctx=ctx)
 
 
 def svt_f64(Y, tau, *, ctx=None):

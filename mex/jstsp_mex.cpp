@@ -172,6 +172,57 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (rc) fail(f64 ? "jstsp_proposed_algorithm_f64" : "jstsp_proposed_algorithm_c64", rc);
         if (Y) plhs[1] = Y;
         if (ce) plhs[2] = ce;
+    } else if (!strcmp(fn, "proposed_algorithm_std_f64")) {
+        // [S, Y, convergence_error, rcond] = proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, 'std', indx_S, PA, PB)
+        //   Alg. 1 in float64 (jstsp_proposed_std_f64): the reference's argument list, then optional (or []) indx_S, pinv(A), pinv(B)
+        check_nargs(fn, nrhs, 9, 12, nlhs, 4);
+        const Dims dy = dims_of(in[0]), dom = dims_of(in[1]), da = dims_of(in[2]), db = dims_of(in[3]);
+        const int N = dy.r, M = dy.c, batch = dy.b, Gr = da.c, G2 = db.r;
+        if (dom.r != N || dom.c != M || dom.b != batch || da.r != N || db.c != M)
+            mexErrMsgIdAndTxt("jstsp:shape", "%s: inconsistent dimensions", fn);
+        const jstsp_c64 *subY = cplx(in[0], fn, "subY"), *A = cplx(in[2], fn, "A"), *B = cplx(in[3], fn, "B");
+        const double *Om = real_of(in[1], fn, "Omega");
+        const long long sA = dict_stride(da, batch, fn, "A"), sB = dict_stride(db, batch, fn, "B");
+        const int Imax = (int)mxGetScalar(in[4]);
+        if (Imax < 1) mexErrMsgIdAndTxt("jstsp:args", "%s: Imax must be >= 1", fn);
+        const double *tY = scalars(in[5], batch, fn, "tau_Y"), *tS = scalars(in[6], batch, fn, "tau_S"),
+                     *rho = scalars(in[7], batch, fn, "rho");
+        char type[32] = "";
+        if (!mxIsChar(in[8]) || mxGetString(in[8], type, sizeof(type)) || strcmp(type, "std"))
+            mexErrMsgIdAndTxt("jstsp:args", "%s: type must be 'std' ('approximate' in float64 is proposed_algorithm_f64)", fn);
+        const int32_t *idx = nullptr;
+        if (nrhs - 1 >= 10 && !mxIsEmpty(in[9])) {            // 1-based linear indices, doubles in MATLAB
+            const size_t n = mxGetNumberOfElements(in[9]);
+            if (n != (size_t)Gr * G2 * batch) mexErrMsgIdAndTxt("jstsp:shape", "%s: numel(indx_S) must be Gr*G2 per problem", fn);
+            const double *pi = real_of(in[9], fn, "indx_S");
+            const mwSize d1[2] = {(mwSize)n, 1};
+            mxArray *t = mxCreateNumericArray(2, d1, mxINT32_CLASS, mxREAL);
+            int32_t *q = (int32_t *)mxGetData(t);
+            for (size_t i = 0; i < n; ++i) q[i] = (int32_t)pi[i];
+            idx = q;
+        }
+        const jstsp_c64 *PA = nullptr, *PB = nullptr;
+        if (nrhs - 1 >= 11 && !mxIsEmpty(in[10])) {           // pinv(A): Gr x N, paged as A is
+            const Dims dp = dims_of(in[10]);
+            if (dp.r != Gr || dp.c != N || dp.b != da.b) mexErrMsgIdAndTxt("jstsp:shape", "%s: PA must have the size of pinv(A), paged as A is", fn);
+            PA = cplx(in[10], fn, "PA");
+        }
+        if (nrhs - 1 >= 12 && !mxIsEmpty(in[11])) {           // pinv(B): M x G2, paged as B is
+            const Dims dp = dims_of(in[11]);
+            if (dp.r != M || dp.c != G2 || dp.b != db.b) mexErrMsgIdAndTxt("jstsp:shape", "%s: PB must have the size of pinv(B), paged as B is", fn);
+            PB = cplx(in[11], fn, "PB");
+        }
+        ensure_ctx();
+        plhs[0] = new_complex(Gr, G2, batch);
+        mxArray *Y = nlhs >= 2 ? new_complex(N, M, batch) : nullptr;
+        mxArray *ce = nlhs >= 3 ? new_real(Imax, 3, batch) : nullptr;
+        mxArray *rcnd = nlhs >= 4 ? new_real(1, 2, 1) : nullptr;
+        const int rc = jstsp_proposed_std_f64(g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, PA, PB, Imax, tY, tS, rho, idx, c64(plhs[0]),
+                                              Y ? c64(Y) : nullptr, ce ? mxGetDoubles(ce) : nullptr, rcnd ? mxGetDoubles(rcnd) : nullptr, JSTSP_HOST);
+        if (rc) fail("jstsp_proposed_std_f64", rc);
+        if (Y) plhs[1] = Y;
+        if (ce) plhs[2] = ce;
+        if (rcnd) plhs[3] = rcnd;
     } else if (!strcmp(fn, "svt")) {
         // X = svt(Y, tau)     benchmark_algorithms/svt.m:1
         check_nargs(fn, nrhs, 2, 2, nlhs, 1);

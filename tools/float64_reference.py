@@ -7,7 +7,9 @@ proposed_algorithm_angles), same options for seed, SNR points, trials and groups
 (`<group>/snr_db`, `sweep_idx`, `trial`, `fingerprint`, `nmse_port`, `ce_port`, `seed`), so that
 tests/golden/make_fullsize_port_fixture.py reads its output unchanged.  `--ls` adds the LS column in float64 per trial
 (`S_ls`, `nmse_ls`: `pinv(A_hbf)*Y_hbf*pinv(B_hbf)` by jstsp_ls_f64), `--tssr IMAX,RHO` the TSSR and SVT-based columns
-(`S_tssr`, `S_svt`, `nmse_tssr`, `nmse_svt` by tssr_f64: jstsp_mc_svt_f64, jstsp_pinv_f64, jstsp_mmv_omp_f64).  The host port needs 5-6 core-seconds per trial; this
+(`S_tssr`, `S_svt`, `nmse_tssr`, `nmse_svt` by tssr_f64: jstsp_mc_svt_f64, jstsp_pinv_f64, jstsp_mmv_omp_f64), `--std IMAX`
+Alg. 1 (`S_std`, `nmse_std`: proposed_algorithm 'std' in float64 by jstsp_proposed_std_f64, on the trial's own indx_S in the
+_angles groups).  The host port needs 5-6 core-seconds per trial; this
 needs milliseconds.  It does not replace parity_tail.py (which measures the fp32 path against the host port) and the committed
 fixtures are not regenerated from it.
 
@@ -55,6 +57,8 @@ def main():
                     "(jstsp_ls_f64): S_ls (complex128, Gr x G2 per trial) and nmse_ls in the fixture")
     ap.add_argument("--tssr", type=str, default="", metavar="IMAX,RHO", help="also the float64 TSSR recipe of plot_errorVSsnr.m:151-162 per trial "
                     "(tssr_f64 with K = 200): S_tssr, S_svt (complex128, Gr x G2 per trial), nmse_tssr and nmse_svt in the fixture")
+    ap.add_argument("--std", type=int, default=0, metavar="IMAX", help="also Alg. 1 ('std') in float64 per trial at this Imax "
+                    "(proposed_algorithm_std_f64): S_std (complex128, Gr x G2 per trial) and nmse_std in the fixture")
     ap.add_argument("--host-port", type=int, default=0, help="also solve this many trials with oracle/cpu_port.cpp and compare")
     ap.add_argument("--threads", type=int, default=16, help="threads of the host port")
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "build", "f64_reference"),
@@ -117,6 +121,11 @@ def main():
             for nm_, Sx in (("tssr", St.cpu().numpy()), ("svt", Sv.cpu().numpy())):
                 rec["S_" + nm_] = np.ascontiguousarray(Sx)
                 rec["nmse_" + nm_] = np.array([O.nmse_capped(Sx[t], zb[t]) for t in range(cnt)])
+        if a.std:                                   # proposed_algorithm.m:29,53 on the same trial, nothing narrowed
+            hyp = [inp[k].numpy() for k in ("tau_Y", "tau_Z", "rho")]
+            Ss = J.proposed_algorithm_std_f64(inp["subY"], inp["Omega"], inp["A"], inp["B"], a.std, *hyp, indx_S=idx, want_ce=False)[0].cpu().numpy()
+            rec["S_std"] = np.ascontiguousarray(Ss)
+            rec["nmse_std"] = np.array([O.nmse_capped(Ss[t], zb[t]) for t in range(cnt)])
         for k, v in rec.items():
             g.setdefault(k, []).append(v)
         if n == 0 and a.host_port > 0:
