@@ -9,7 +9,8 @@
 //    +-1i c of column j on the bits; |c|^2 is then formed with contraction off (x*x + y*y, a commutative sum of two rounded
 //    squares), so that the swap cannot turn fma(x, x, y*y) into fma(y, y, x*x): such columns tie exactly and the lowest index wins.
 //  - the new atom is orthogonalised by two passes of classical Gram-Schmidt: the k dot products of a pass are independent, one
-//    per wave at a time, instead of 2 k block-wide reductions in sequence.
+//    per wave at a time, instead of 2 k block-wide reductions in sequence (cgs2_append of ws64.h, shared with omp64.hip, as are
+//    the block sum and the exponent of the scaling).
 //  - ||Y||_F^2 is summed on the scaled Y, so that after the exact scaling by 2^-e nothing depends on the scale of Y.
 // Every sum is formed in a fixed order by a fixed thread: no atomics, a repeated call returns the same bits, and a problem's
 // result does not depend on its batch mates or on the memspace.
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, in
     double *red = score + Gr;                                     // [8]
     int *taken = reinterpret_cast<int *>(red + 8);                // [Gr]
     __shared__ int s_best, s_stop;
-    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = blockIdx.x, tid = threadIdx.x;
     const double2 *a = A + (long long)t * strideA;
     const double2 *y = Y + (long long)t * N * S;
     double2 *R = Rws + (long long)t * N * S, *Q = Qws + (long long)t * N * K, *Rt = Rtws + (long long)t * K * K,
@@ -43,32 +44,8 @@ __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, in
     int32_t *io = index_out + (long long)t * K;
     const long long NS = (long long)N * S;
 
-    auto block_sum = [&](double v) {
-        v = wave_sum64(v);
-        __syncthreads();
-        if (lane == 0) red[wave] = v;
-        __syncthreads();
-        return (red[0] + red[1]) + (red[2] + red[3]);
-    };
-    auto block_max = [&](double v) {
-        for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-        __syncthreads();
-        if (lane == 0) red[4 + wave] = v;
-        __syncthreads();
-        return fmax(fmax(red[4], red[5]), fmax(red[6], red[7]));
-    };
-
     // the problem is solved on Y * 2^-ey (largest finite component in [0.5, 1)): exact unless a component underflows
-    double ymax = 0.0;
-    for (long long e = tid; e < NS; e += 256) {
-        const double2 v = y[e];
-        const double ax = fabs(v.x), ay = fabs(v.y);
-        if (ax <= DBL_MAX) ymax = fmax(ymax, ax);                 // (not NaN, not Inf)
-        if (ay <= DBL_MAX) ymax = fmax(ymax, ay);
-    }
-    ymax = block_max(ymax);
-    int ey = 0;
-    if (ymax > 0.0) (void)frexp(ymax, &ey);
+    const int ey = finite_max_exponent(y, NS, red + 4);
     double y2 = 0.0;
     for (long long e = tid; e < NS; e += 256) {
         const double2 v = y[e];
@@ -81,7 +58,7 @@ __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, in
     for (long long e = tid; e < (long long)K * K; e += 256) Rt[e] = make_double2(0.0, 0.0);
     for (int g = tid; g < Gr; g += 256) taken[g] = 0;
     for (int k = tid; k < K; k += 256) io[k] = 0;
-    y2 = block_sum(y2);
+    y2 = block_sum64(y2, red);
     const int kmax = min(K, min(N, Gr));
     int k = 0;
     // deterministic split of the (atom, column) correlations: thread -> atom g = tid % gp, column group tid / gp
@@ -131,39 +108,8 @@ __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, in
             n0 = fma(v.x, v.x, n0);
             n0 = fma(v.y, v.y, n0);
         }
-        n0 = block_sum(n0);                                        // (its barriers publish q)
-        for (int pass = 0; pass < 2 && k > 0; ++pass) {
-            for (int j = wave; j < k; j += 4) {                    // d_j = q_j^H q, one wave per j
-                const double2 *qj = Q + (long long)N * j;
-                Dot4 d = {0.0, 0.0, 0.0, 0.0};
-                for (int i = lane; i < N; i += 64) dot4_step(d, qj[i], q[i]);
-                const double dx = wave_sum64(d.xx + d.yy), dy = wave_sum64(d.xy - d.yx);
-                if (lane == 0) {
-                    D[j] = make_double2(dx, dy);
-                    double2 r = Rt[j + (long long)K * k];
-                    r.x += dx; r.y += dy;
-                    Rt[j + (long long)K * k] = r;
-                }
-            }
-            __syncthreads();
-            for (int i = tid; i < N; i += 256) {                   // q -= sum_j q_j d_j, j ascending
-                double2 v = q[i];
-                for (int j = 0; j < k; ++j) {
-                    const double2 u = Q[(long long)N * j + i], d = D[j];
-                    v.x -= d.x * u.x - d.y * u.y;
-                    v.y -= d.x * u.y + d.y * u.x;
-                }
-                q[i] = v;
-            }
-            __syncthreads();
-        }
-        double n1 = 0.0;
-        for (int i = tid; i < N; i += 256) {
-            const double2 v = q[i];
-            n1 = fma(v.x, v.x, n1);
-            n1 = fma(v.y, v.y, n1);
-        }
-        n1 = block_sum(n1);
+        n0 = block_sum64(n0, red);                                 // (its barriers publish q)
+        const double n1 = cgs2_append(q, Q, N, k, Rt + (long long)K * k, D, red);
         if (!(n1 > 1e-10 * n0) || !(n0 > 0.0)) break;             // atom numerically inside the span of the support
         const double nrm = sqrt(n1), inv = 1.0 / nrm;
         for (int i = tid; i < N; i += 256) { double2 v = q[i]; v.x *= inv; v.y *= inv; q[i] = v; }
@@ -187,7 +133,7 @@ __global__ __launch_bounds__(256) void mmv_omp64_kernel(int N, int Gr, int S, in
                 r2 = fma(v.y, v.y, r2);
             }
         }
-        r2 = block_sum(r2);
+        r2 = block_sum64(r2, red);
         if (tid == 0) s_stop = (r2 <= 1e-12 * y2);
         __syncthreads();
         if (s_stop) { ++k; break; }

@@ -4,8 +4,8 @@
 //     repeat m times:  idx = argmax |Phi' r| (first index on ties; chosen atoms are NOT excluded, OMP.m:18)
 //                      targetMatrix = [targetMatrix, Phi(:, idx)];  x = pinv(targetMatrix) v;  r = v - targetMatrix x
 // The least squares is carried in measurement space, the structure of mmv_omp64.hip with S = 1: an orthonormal basis Q of the
-// selected atoms (two passes of classical Gram-Schmidt per new atom), the triangular factor, z = Q^H v, one back-substitution at
-// the end.  An index that is already in the index set leaves span and residual alone and raises the atom's multiplicity: pinv
+// selected atoms (two passes of classical Gram-Schmidt per new atom: cgs2_append of ws64.h, the code mmv_omp64.hip runs), the
+// triangular factor, z = Q^H v, one back-substitution at the end.  An index that is already in the index set leaves span and residual alone and raises the atom's multiplicity: pinv
 // splits the coefficient equally over the copies and the scatter of OMP.m:29-32 leaves the last copy in x_hat.  A NEW index whose
 // atom lies in the span already (||a - Q Q' a||^2 <= 1e-20 ||a||^2 after the two passes, or a = 0) adds nothing either and keeps
 // the coefficient 0, as in omp.hip.
@@ -44,18 +44,6 @@ struct Omp64 {
     int *ex;           // [batch]              e: the problem is solved on v 2^-e
 };
 
-// the sum of a complex value over the 256 threads: xor tree per wave, then the four waves in order (three barriers; sh: 8 doubles)
-__device__ __forceinline__ double2 block_sum2(double2 v, double *sh)
-{
-    v.x = wave_sum64(v.x); v.y = wave_sum64(v.y);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sh[2 * (threadIdx.x >> 6)] = v.x; sh[2 * (threadIdx.x >> 6) + 1] = v.y; }
-    __syncthreads();
-    const double2 out = make_double2((sh[0] + sh[2]) + (sh[4] + sh[6]), (sh[1] + sh[3]) + (sh[5] + sh[7]));
-    __syncthreads();
-    return out;
-}
-
 // r = v 2^-e, e the exponent of the largest finite component (exact unless a component underflows); nu = 0
 __global__ __launch_bounds__(256) void omp64_init_kernel(int meas, const double2 *V, Omp64 s)
 {
@@ -63,18 +51,7 @@ __global__ __launch_bounds__(256) void omp64_init_kernel(int meas, const double2
     const int t = blockIdx.x, tid = threadIdx.x;
     const double2 *v = V + (long long)t * meas;
     double2 *r = s.r + (long long)t * meas;
-    double vmax = 0.0;
-    for (int e = tid; e < meas; e += 256) {
-        const double ax = fabs(v[e].x), ay = fabs(v[e].y);
-        if (ax <= DBL_MAX) vmax = fmax(vmax, ax);                 // (not NaN, not Inf)
-        if (ay <= DBL_MAX) vmax = fmax(vmax, ay);
-    }
-    for (int o = 32; o > 0; o >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, o));
-    if ((tid & 63) == 0) red[tid >> 6] = vmax;
-    __syncthreads();
-    vmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    int ev = 0;
-    if (vmax > 0.0) (void)frexp(vmax, &ev);
+    const int ev = finite_max_exponent(v, meas, red);
     for (int e = tid; e < meas; e += 256) r[e] = make_double2(ldexp(v[e].x, -ev), ldexp(v[e].y, -ev));
     if (tid == 0) { s.nu[t] = 0; s.ex[t] = ev; }
 }
@@ -105,7 +82,7 @@ __global__ __launch_bounds__(256) void omp64_step_kernel(int meas, int size_d, i
                                                          long long strideA, const double2 *Bf, long long strideB, int N, int Gr, int G2,
                                                          Omp64 s)
 {
-    __shared__ double sh[8];
+    __shared__ double sh[4];
     __shared__ double sbv[4];
     __shared__ int sbi[4];
     __shared__ int s_idx, s_dup;
@@ -166,38 +143,8 @@ __global__ __launch_bounds__(256) void omp64_step_kernel(int meas, int size_d, i
         }
     }
     for (int j = tid; j < m; j += 256) Rc[j] = make_double2(0.0, 0.0);
-    n0 = block_sum2(make_double2(n0, 0.0), sh).x;                  // (its barriers publish q and Rc)
-    // ---- two passes of classical Gram-Schmidt: the u dot products of a pass are independent, one wave per basis vector
-    for (int pass = 0; pass < 2 && u > 0; ++pass) {
-        for (int j = wave; j < u; j += 4) {
-            const double2 *qj = Q + (long long)meas * j;
-            Dot4 d = {0.0, 0.0, 0.0, 0.0};
-            for (int e = lane; e < meas; e += 64) dot4_step(d, qj[e], q[e]);
-            const double dx = wave_sum64(d.xx + d.yy), dy = wave_sum64(d.xy - d.yx);
-            if (lane == 0) {
-                D[j] = make_double2(dx, dy);
-                Rc[j] = make_double2(Rc[j].x + dx, Rc[j].y + dy);
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < meas; e += 256) {                    // q -= sum_j q_j d_j, j ascending
-            double2 v = q[e];
-            for (int j = 0; j < u; ++j) {
-                const double2 w = Q[(long long)meas * j + e], d = D[j];
-                v.x -= d.x * w.x - d.y * w.y;
-                v.y -= d.x * w.y + d.y * w.x;
-            }
-            q[e] = v;
-        }
-        __syncthreads();
-    }
-    double n1 = 0.0;
-    for (int e = tid; e < meas; e += 256) {
-        const double2 v = q[e];
-        n1 = fma(v.x, v.x, n1);
-        n1 = fma(v.y, v.y, n1);
-    }
-    n1 = block_sum2(make_double2(n1, 0.0), sh).x;
+    n0 = block_sum64(n0, sh);                                      // (its barriers publish q and Rc)
+    const double n1 = cgs2_append(q, Q, meas, u, Rc, D, sh);       // two passes of classical Gram-Schmidt, then ||q||^2
     if (!(n1 > 1e-20 * n0) || !(n0 > 0.0)) return;                // inside the span of the chosen atoms (or NaN): adds nothing
     const double nrm = sqrt(n1), inv = 1.0 / nrm;
     // ---- q_u = w / |w|;  z_u = q_u^H r (r is orthogonal to the old basis);  r -= z_u q_u
@@ -208,7 +155,9 @@ __global__ __launch_bounds__(256) void omp64_step_kernel(int meas, int size_d, i
         q[e] = v;
         dot4_step(d, v, r[e]);
     }
-    const double2 zu = block_sum2(make_double2(d.xx + d.yy, d.xy - d.yx), sh);
+    double2 zu;
+    zu.x = block_sum64(d.xx + d.yy, sh);
+    zu.y = block_sum64(d.xy - d.yx, sh);
     for (int e = tid; e < meas; e += 256) {
         const double2 w = q[e];
         double2 v = r[e];

@@ -24,7 +24,8 @@
 // two products of the shapes of A^H K and T B^H.  The factors come from the Hestenes route of pinv64.hip (pinv64.h), once per
 // call - once for the batch when a factor is shared - or from the caller, who may hand them from one call to the next.  The
 // rest of the iteration is the list above, kernel for kernel; G_A, G_B, the carried V, Res and RRes do not exist and
-// convergence_error(:, 3) stays 0 (:6).
+// convergence_error(:, 3) stays 0 (:6).  The two entries share one host frame, Admm64 below: parameters, the shared layout, the
+// zeroing, head (Z, svt, X, K) and tail (A S B, C, V1, V2, convergence_error); each writes its own S-step between the two.
 #include "pinv64.h"
 #include "svt64.h"
 
@@ -192,6 +193,113 @@ size_t solver_ws_elems(int N, int M, int Gr, int G2, int batch, int nA, int nB)
     return std::max<size_t>(1, e);
 }
 
+// What Alg. 2 ('approximate') and Alg. 1 ('std') share - everything of the iteration but the S-step.  An entry fills in the call,
+// states its own arrays after layout() inside the same ws64_open() lambda (gws among them: it knows its products), and writes its
+// S-step inline between head() and tail().
+struct Admm64 {
+    int N, M, Gr, G2, batch, Imax;                  // the call
+    long long strideA, strideB;
+    const jstsp_c64 *subY_; const double *Omega_; const jstsp_c64 *A_, *B_; const int32_t *indx_;
+    jstsp_c64 *S_out, *Y_out; double *ce_out;
+    bool host;
+    std::vector<Par64> hp;                          // the arrays: parameters, shared inputs, outputs, state of the iteration
+    const Par64 *par; const double2 *subY, *A, *B; const double *Omega; const int32_t *indx = nullptr;
+    double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *T, *W, *gws = nullptr;
+    double *ced, *lx, *l1, *l2, *ce3;
+    int32_t *rank = nullptr;
+    Svt64 sv;
+
+    bool angles() const { return indx_ != nullptr; }
+    bool want_ce() const { return ce_out != nullptr; }
+    size_t nm1() const { return (size_t)N * M; }
+    size_t g1() const { return (size_t)Gr * G2; }
+    Mat64 Am() const { return Mat64{A, strideA, N}; }
+    Mat64 Bm() const { return Mat64{B, strideB, G2}; }
+    dim3 gnm() const { return egrid((long long)nm1(), batch); }
+    int mask_count(int it) const { return (int)std::min<long long>(10 + 5ll * (it + 1), (long long)g1()); }     // angles :36
+
+    void make_par(const double *tau_Y, const double *tau_S, const double *rho)
+    {
+        for (int t = 0; t < batch; ++t) hp.push_back(Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]});
+    }
+    void layout(Slab &w, int b)
+    {
+        const size_t enm = nm1() * b, eg = g1() * b;
+        par = w.in(hp.data(), b, true);
+        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
+        Omega = w.in(Omega_, enm, host);
+        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
+        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
+        if (angles()) indx = w.in(indx_, eg, host);
+        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
+        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
+        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
+        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
+        T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
+        if (angles()) rank = w.get<int32_t>(eg);
+        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
+        sv.layout(w, N, M, b);
+    }
+    // X = V1 = V2 = C = Xs = 0; the rank of every entry in indx_S (_angles)
+    int begin(hipStream_t st)
+    {
+        const size_t g = g1() * batch;
+        for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm1() * batch * sizeof(double2), st));
+        if (angles()) {
+            hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
+            hipLaunchKernelGGL(rank64_kernel, egrid((long long)g1(), batch), dim3(256), 0, st, (int)g1(), indx, rank);
+        }
+        return 0;
+    }
+    // Z, Y = svt(Z), X; leaves K = X - V2/rho - C for the S-step                                                           (:35-43)
+    int head(hipStream_t st)
+    {
+        hipLaunchKernelGGL(form_z64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, X, V1, Z);
+        JSTSP_TRY(sv.apply(st, Z, &par->tY, (long long)(sizeof(Par64) / sizeof(double)), Y));          // :35
+        hipLaunchKernelGGL(update_x64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
+        return 0;
+    }
+    // Xs = A S B, C, V1, V2 and row `it` of convergence_error (its third column is what ce3 holds)                          (:58-69)
+    int tail(hipStream_t st, const double2 *S, int it)
+    {
+        const long long sNM = (long long)nm1(), sG = (long long)g1();
+        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am(), Mat64{S, sG, Gr}, W, (long long)N * G2, N, gws));      // A S
+        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm(), Xs, sNM, N, gws));      // ... B
+        hipLaunchKernelGGL(update_c64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, X, Xs, Y, Cm, V1, V2);
+        if (want_ce()) {
+            JSTSP_TRY(sv.lambda_max(st, X, lx));
+            JSTSP_TRY(sv.lambda_max(st, V1, l1));
+            JSTSP_TRY(sv.lambda_max(st, V2, l2));
+            hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
+        }
+        JSTSP_HIP(hipGetLastError());
+        return 0;
+    }
+    // Y to the caller; for a host call S (in Sd by now), Y and convergence_error go back and the stream is synchronised
+    int deliver(const Slab &s)
+    {
+        const size_t nm = nm1() * batch;
+        if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, s.st));
+        if (host) {
+            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g1() * batch));
+            if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
+            if (want_ce()) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
+            JSTSP_HIP(hipStreamSynchronize(s.st));
+        }
+        return 0;
+    }
+};
+
+// the limits the two entries share
+int admm64_limits(const char *nmf, int N, int M, int Gr, int G2, int batch)
+{
+    JSTSP_REQUIRE(std::min(N, M) <= P64_MAX_ORDER, JSTSP_E_UNSUPPORTED, "%s: min(N, M) = %d: the float64 eigen-decomposition is limited to order %d", nmf,
+                  std::min(N, M), P64_MAX_ORDER);
+    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31) && (long long)N * M < (1ll << 31) && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
+    return 0;
+}
+
 }  // namespace
 }  // namespace jstsp
 
@@ -244,93 +352,46 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
     JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
                   "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use jstsp_proposed_algorithm_c64", nmf);
-    JSTSP_REQUIRE(std::min(N, M) <= P64_MAX_ORDER, JSTSP_E_UNSUPPORTED, "%s: min(N, M) = %d: the float64 eigen-decomposition is limited to order %d", nmf,
-                  std::min(N, M), P64_MAX_ORDER);
-    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31) && (long long)N * M < (1ll << 31) && batch <= 65535, JSTSP_E_UNSUPPORTED,
-                  "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
-    const bool host = memspace == JSTSP_HOST, angles = indx_S_ != nullptr, want_ce = ce_out != nullptr;
+    JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
+    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
+    f.make_par(tau_Y, tau_S, rho);
     hipStream_t st = ctx->stream;
-    const size_t nm1 = (size_t)N * M, g1 = (size_t)Gr * G2, nm = nm1 * batch, g = g1 * batch;
+    const size_t g1 = f.g1(), g = g1 * batch;
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    std::vector<Par64> hp(batch);
-    for (int t = 0; t < batch; ++t) hp[t] = Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]};
 
-    const Par64 *par;
-    const double2 *subY, *A, *B;
-    const double *Omega;
-    const int32_t *indx = nullptr;
-    double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *V, *S, *Res, *RRes, *T2, *T, *W, *GA, *GB, *gws;
-    double *ced, *lx, *l1, *l2, *ce3;
-    int32_t *rank = nullptr;
-    Svt64 sv;
+    double2 *V, *S, *Res, *RRes, *T2, *GA, *GB;
     Slab s(st);
     JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
-        const size_t enm = nm1 * b, eg = g1 * b;
         const int bA = strideA ? b : 1, bB = strideB ? b : 1;
-        par = w.in(hp.data(), b, true);
-        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
-        Omega = w.in(Omega_, enm, host);
-        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
-        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
-        if (angles) indx = w.in(indx_S_, eg, host);
-        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
-        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
-        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
-        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
-        for (double2 **p : {&V, &S, &Res, &RRes, &T2}) *p = w.get<double2>(eg);
-        T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
+        f.layout(w, b);
+        for (double2 **p : {&V, &S, &Res, &RRes, &T2}) *p = w.get<double2>(g1 * b);
         GA = w.get<double2>((size_t)Gr * Gr * bA); GB = w.get<double2>((size_t)G2 * G2 * bB);
-        gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
-        if (angles) rank = w.get<int32_t>(eg);
-        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
-        sv.layout(w, N, M, b);
+        f.gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
     }));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (hp is this call's own: copied before it goes out of scope on any path)
+    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
 
-    for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * sizeof(double2), st));
     JSTSP_HIP(hipMemsetAsync(V, 0, g * sizeof(double2), st));
-    if (angles) {
-        hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
-        hipLaunchKernelGGL(rank64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (int)g1, indx, rank);
-    }
-    const long long sNM = (long long)nm1, sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
-    const Mat64 Am{A, strideA, N}, Bm{B, strideB, G2}, GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
+    JSTSP_TRY(f.begin(st));
+    const long long sNM = (long long)f.nm1(), sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
+    const Mat64 Am = f.Am(), Bm = f.Bm(), GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
+    double2 *T = f.T, *gws = f.gws;
     JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr, gws));          // G_A = A^H A
     JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, Bm, Bm, GB, (long long)G2 * G2, G2, gws));          // G_B = B B^H
-    const dim3 gnm = egrid((long long)nm1, batch);
     for (int it = 0; it < Imax; ++it) {
-        const int cnt = (int)std::min<long long>(10 + 5ll * (it + 1), (long long)g1);                  // angles :36
-        hipLaunchKernelGGL(form_z64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, V1, Z);
-        JSTSP_TRY(sv.apply(st, Z, &par->tY, (long long)(sizeof(Par64) / sizeof(double)), Y));          // :35
-        hipLaunchKernelGGL(update_x64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
-        JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, M, N, batch, Am, Mat64{K, sNM, N}, T, (long long)Gr * M, Gr, gws));        // A^H K
+        JSTSP_TRY(f.head(st));
+        JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, M, N, batch, Am, Mat64{f.K, sNM, N}, T, (long long)Gr * M, Gr, gws));      // A^H K
         JSTSP_TRY(zgemm64(st, 'N', 'C', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Bm, Res, sG, Gr, gws));     // ... B^H
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{V, sG, Gr}, T2, sG, Gr, gws));                   // G_A V
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
         hipLaunchKernelGGL(sub64_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, Res, RRes);
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{Res, sG, Gr}, T2, sG, Gr, gws));                 // G_A Res
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
-        hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, par, Res, RRes, V, S, rank, cnt, want_ce ? ce3 : nullptr);
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am, Mat64{S, sG, Gr}, W, (long long)N * G2, N, gws));        // A S
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm, Xs, sNM, N, gws));        // ... B
-        hipLaunchKernelGGL(update_c64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, Xs, Y, Cm, V1, V2);
-        if (want_ce) {
-            JSTSP_TRY(sv.lambda_max(st, X, lx));
-            JSTSP_TRY(sv.lambda_max(st, V1, l1));
-            JSTSP_TRY(sv.lambda_max(st, V2, l2));
-            hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
-        }
-        JSTSP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S, f.rank, f.mask_count(it),
+                           f.want_ce() ? f.ce3 : nullptr);
+        JSTSP_TRY(f.tail(st, S, it));
     }
-    JSTSP_HIP(hipMemcpyAsync(Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
-    if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, st));
-    if (host) {
-        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g));
-        if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
-        if (want_ce) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
-        JSTSP_HIP(hipStreamSynchronize(st));
-    }
-    return 0;
+    JSTSP_HIP(hipMemcpyAsync(f.Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
+    return f.deliver(s);
 }
 
 int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
@@ -349,38 +410,26 @@ int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int bat
     JSTSP_REQUIRE(N >= Gr && M >= G2, JSTSP_E_UNSUPPORTED,
                   "%s: K2 = kron(B.', A) must have full column rank (N >= Gr, M >= G2); the under-determined U\\(L\\k) of the reference "
                   "returns a basic, not least-squares, solution", nmf);
-    JSTSP_REQUIRE(std::min(N, M) <= P64_MAX_ORDER, JSTSP_E_UNSUPPORTED, "%s: min(N, M) = %d: the float64 eigen-decomposition is limited to order %d", nmf,
-                  std::min(N, M), P64_MAX_ORDER);
-    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31) && (long long)N * M < (1ll << 31) && batch <= 65535, JSTSP_E_UNSUPPORTED,
-                  "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
+    JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
     JSTSP_REQUIRE((PA_ || pinv64_shape_ok(N, Gr)) && (PB_ || pinv64_shape_ok(G2, M)), JSTSP_E_UNSUPPORTED,
                   "%s: A %d x %d, B %d x %d: a factor the call inverts needs min(rows, cols) <= %d and max(rows, cols) <= %d", nmf, N, Gr, G2, M,
                   PV_MAX_ORDER, PV_MAX_LONG);
-    const bool host = memspace == JSTSP_HOST, angles = indx_S_ != nullptr, want_ce = ce_out != nullptr;
+    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
+    f.make_par(tau_Y, tau_S, rho);
+    const bool host = f.host;
     hipStream_t st = ctx->stream;
-    const size_t nm1 = (size_t)N * M, g1 = (size_t)Gr * G2, nm = nm1 * batch, g = g1 * batch;
+    const size_t g1 = f.g1();
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    std::vector<Par64> hp(batch);
-    for (int t = 0; t < batch; ++t) hp[t] = Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]};
 
-    const Par64 *par;
-    const double2 *subY, *A, *B, *PA, *PB;
-    const double *Omega;
-    const int32_t *indx = nullptr;
-    double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *V, *T, *W, *gws, *PAc = nullptr, *PBc = nullptr;
-    double *ced, *lx, *l1, *l2, *ce3, *rcA = nullptr, *rcB = nullptr, *rcd;
-    int32_t *rank = nullptr, *rkA = nullptr, *rkB = nullptr;
+    const double2 *PA, *PB;
+    double2 *V, *PAc = nullptr, *PBc = nullptr;
+    double *rcA = nullptr, *rcB = nullptr, *rcd;
+    int32_t *rkA = nullptr, *rkB = nullptr;
     Pinv64 pvA, pvB;
-    Svt64 sv;
     Slab s(st);
     JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
-        const size_t enm = nm1 * b, eg = g1 * b;
         const int bA = strideA ? b : 1, bB = strideB ? b : 1;
-        par = w.in(hp.data(), b, true);
-        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
-        Omega = w.in(Omega_, enm, host);
-        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
-        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
+        f.layout(w, b);
         if (PA_) PA = w.in(reinterpret_cast<const double2 *>(PA_), (size_t)Gr * N * bA, host);
         else {
             PA = PAc = w.get<double2>((size_t)Gr * N * bA); rcA = w.get<double>(bA); rkA = w.get<int32_t>(bA);
@@ -391,27 +440,18 @@ int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int bat
             PB = PBc = w.get<double2>((size_t)M * G2 * bB); rcB = w.get<double>(bB); rkB = w.get<int32_t>(bB);
             pvB.layout(w, G2, M, bB);
         }
-        if (angles) indx = w.in(indx_S_, eg, host);
-        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
-        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
-        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
         rcd = w.out(rcond_out, 2, host);
-        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
-        V = w.get<double2>(eg);
-        T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
+        V = w.get<double2>(g1 * b);
         const int shp[4][3] = {{Gr, M, N}, {Gr, G2, M}, {N, G2, Gr}, {N, M, G2}};
         size_t e = 1;
         for (const auto &q : shp) e = std::max(e, zgemm64_ws_elems(q[0], q[1], q[2], b));
-        gws = w.get<double2>(e);
-        if (angles) rank = w.get<int32_t>(eg);
-        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
-        sv.layout(w, N, M, b);
+        f.gws = w.get<double2>(e);
     }));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (hp is this call's own: copied before it goes out of scope on any path)
+    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
 
     // the factors: a shared one is inverted once for the call; one that is not of full column rank ends the call
-    if (PAc) JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, A, strideA, PAc, rcA, rkA));
-    if (PBc) JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, B, strideB, PBc, rcB, rkB));
+    if (PAc) JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, f.A, strideA, PAc, rcA, rkA));
+    if (PBc) JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, f.B, strideB, PBc, rcB, rkB));
     for (int f = 0; f < 2; ++f) {
         const int cnt = f ? nB : nA, full = f ? G2 : Gr;
         const double *rc = f ? rcB : rcA;
@@ -438,43 +478,20 @@ int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int bat
         JSTSP_HIP(hipGetLastError());
     }
 
-    for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm * sizeof(double2), st));
-    JSTSP_HIP(hipMemsetAsync(ce3, 0, batch * sizeof(double), st));                                     // convergence_error(:, 3) = 0 (:6)
-    if (angles) {
-        hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
-        hipLaunchKernelGGL(rank64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (int)g1, indx, rank);
-    }
-    const long long sNM = (long long)nm1, sG = (long long)g1;
-    const Mat64 Am{A, strideA, N}, Bm{B, strideB, G2}, PAm{PA, strideA ? (long long)Gr * N : 0, Gr}, PBm{PB, strideB ? (long long)M * G2 : 0, M};
-    const dim3 gnm = egrid((long long)nm1, batch);
+    JSTSP_HIP(hipMemsetAsync(f.ce3, 0, batch * sizeof(double), st));                                   // convergence_error(:, 3) = 0 (:6)
+    JSTSP_TRY(f.begin(st));
+    const long long sNM = (long long)f.nm1(), sG = (long long)g1;
+    const Mat64 PAm{PA, strideA ? (long long)Gr * N : 0, Gr}, PBm{PB, strideB ? (long long)M * G2 : 0, M};
     for (int it = 0; it < Imax; ++it) {
-        const int cnt = (int)std::min<long long>(10 + 5ll * (it + 1), (long long)g1);                  // angles :36
-        hipLaunchKernelGGL(form_z64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, V1, Z);
-        JSTSP_TRY(sv.apply(st, Z, &par->tY, (long long)(sizeof(Par64) / sizeof(double)), Y));          // :35
-        hipLaunchKernelGGL(update_x64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, PAm, Mat64{K, sNM, N}, T, (long long)Gr * M, Gr, gws));       // pinv(A) K
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, PBm, V, sG, Gr, gws));      // ... pinv(B)   (:53)
-        hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, par, V, Sd, rank, cnt);
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am, Mat64{Sd, sG, Gr}, W, (long long)N * G2, N, gws));       // A S
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm, Xs, sNM, N, gws));        // ... B
-        hipLaunchKernelGGL(update_c64_kernel, gnm, dim3(256), 0, st, (long long)nm1, par, X, Xs, Y, Cm, V1, V2);
-        if (want_ce) {
-            JSTSP_TRY(sv.lambda_max(st, X, lx));
-            JSTSP_TRY(sv.lambda_max(st, V1, l1));
-            JSTSP_TRY(sv.lambda_max(st, V2, l2));
-            hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
-        }
-        JSTSP_HIP(hipGetLastError());
+        JSTSP_TRY(f.head(st));
+        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, PAm, Mat64{f.K, sNM, N}, f.T, (long long)Gr * M, Gr, f.gws));     // pinv(A) K
+        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{f.T, (long long)Gr * M, Gr}, PBm, V, sG, Gr, f.gws));      // ... pinv(B)   (:53)
+        hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, f.par, V, f.Sd, f.rank,
+                           f.mask_count(it));
+        JSTSP_TRY(f.tail(st, f.Sd, it));
     }
-    if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, st));
-    if (host) {
-        JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g));
-        if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
-        if (want_ce) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
-        if (rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
-        JSTSP_HIP(hipStreamSynchronize(st));
-    }
-    return 0;
+    if (host && rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
+    return f.deliver(s);
 }
 
 }  // extern "C"

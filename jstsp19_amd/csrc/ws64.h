@@ -6,6 +6,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <cfloat>
 
 namespace jstsp {
 namespace {
@@ -40,6 +41,79 @@ __device__ __forceinline__ void dot4_step(Dot4 &d, double2 u, double2 v)
     d.yy = fma(u.y, v.y, d.yy);
     d.xy = fma(u.x, v.y, d.xy);
     d.yx = fma(u.y, v.x, d.yx);
+}
+
+// ---- the tie-safe append of omp64.hip and mmv_omp64.hip (workgroups of 256 threads, every thread calls).  The order of every fma
+// and sum below is a contract: exact ties between columns equal up to a factor -1 or +-1i, and the scale invariance, depend on it.
+
+// the sum of v over the workgroup: xor tree per wave, then the four waves in order (sh: 4 doubles; one barrier before the
+// write, which also publishes what the workgroup stored before the call, and one after)
+__device__ __forceinline__ double block_sum64(double v, double *sh)
+{
+    v = wave_sum64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// e of frexp for the largest finite |component| of v[0 .. n) (0 when there is none or it is 0): v 2^-e has it in [0.5, 1), and
+// the scaling is exact unless a component underflows (sh: 4 doubles, barriers as block_sum64)
+__device__ __forceinline__ int finite_max_exponent(const double2 *v, long long n, double *sh)
+{
+    double vmax = 0.0;
+    for (long long e = threadIdx.x; e < n; e += 256) {
+        const double ax = fabs(v[e].x), ay = fabs(v[e].y);
+        if (ax <= DBL_MAX) vmax = fmax(vmax, ax);                 // (not NaN, not Inf)
+        if (ay <= DBL_MAX) vmax = fmax(vmax, ay);
+    }
+    for (int o = 32; o > 0; o >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = vmax;
+    __syncthreads();
+    vmax = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+    int ev = 0;
+    if (vmax > 0.0) (void)frexp(vmax, &ev);
+    return ev;
+}
+
+// q (len entries, already published by a barrier) is orthogonalised against the k orthonormal columns of Q (len x k) by two passes
+// of classical Gram-Schmidt: the k dot products d_j = q_j^H q of a pass are independent, one wave per j; D[j] = d_j (k entries,
+// LDS or global) and Rcol[j] += d_j, the column of the triangular factor; then q -= sum_j q_j d_j with j ascending.  Returns
+// ||q||^2 after the passes, summed per thread in one fma chain over tid, tid + 256, ... and then over the workgroup.
+__device__ __forceinline__ double cgs2_append(double2 *q, const double2 *Q, int len, int k, double2 *Rcol, double2 *D, double *sh)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int pass = 0; pass < 2 && k > 0; ++pass) {
+        for (int j = wave; j < k; j += 4) {
+            const double2 *qj = Q + (long long)len * j;
+            Dot4 d = {0.0, 0.0, 0.0, 0.0};
+            for (int e = lane; e < len; e += 64) dot4_step(d, qj[e], q[e]);
+            const double dx = wave_sum64(d.xx + d.yy), dy = wave_sum64(d.xy - d.yx);
+            if (lane == 0) {
+                D[j] = make_double2(dx, dy);
+                Rcol[j] = make_double2(Rcol[j].x + dx, Rcol[j].y + dy);
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < len; e += 256) {
+            double2 v = q[e];
+            for (int j = 0; j < k; ++j) {
+                const double2 w = Q[(long long)len * j + e], d = D[j];
+                v.x -= d.x * w.x - d.y * w.y;
+                v.y -= d.x * w.y + d.y * w.x;
+            }
+            q[e] = v;
+        }
+        __syncthreads();
+    }
+    double n1 = 0.0;
+    for (int e = tid; e < len; e += 256) {
+        const double2 v = q[e];
+        n1 = fma(v.x, v.x, n1);
+        n1 = fma(v.y, v.y, n1);
+    }
+    return block_sum64(n1, sh);
 }
 
 // ---- workspace: one stream-ordered slab, bump allocation -----------------------------------------------------------------------

@@ -137,6 +137,18 @@ def _shared_stride(arg, rows_cols, batch, name):
 
 
 # ----------------------------------------------------------------------------- proposed_algorithm
+def _indx_arg(indx_S, batch, n):
+    """indx_S (1-based linear indices, (n,) or (batch, n)) as a (batch, n, 1) int32 argument; ``None`` stays absent."""
+    if indx_S is None:
+        return _Arg(None, np.int32, "indx_S", allow_none=True)
+    if _is_torch(indx_S):
+        import torch
+        ix2 = indx_S.reshape(batch, n, 1).to(torch.int32).contiguous()
+    else:
+        ix2 = np.asarray(indx_S).reshape(batch, n, 1).astype(np.int32)
+    return _Arg(ix2, np.int32, "indx_S")
+
+
 def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None,
                        want_ce=True, ctx=None):
     """basic_system_functions/proposed_algorithm.m:1 — returns (S, Y, convergence_error).
@@ -148,20 +160,13 @@ def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approxi
     a_om = _Arg(Omega, np.float32, "Omega")
     a_A = _Arg(A, np.complex64, "A")
     a_B = _Arg(B, np.complex64, "B")
-    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
     batch, N, M = a_sub.batch, a_sub.R, a_sub.C
     Gr, G2 = a_A.C, a_B.R
     if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
         raise ValueError("Omega must have the shape of subY")
     if a_A.R != N or a_B.C != M:
         raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
-    if indx_S is not None:
-        if _is_torch(indx_S):
-            import torch
-            ix2 = indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous()
-        else:
-            ix2 = np.asarray(indx_S).reshape(batch, Gr * G2, 1).astype(np.int32)
-        a_ix = _Arg(ix2, np.int32, "indx_S")
+    a_ix = _indx_arg(indx_S, batch, Gr * G2)
     c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
     sA = _shared_stride(a_A, N * Gr, batch, "A")
     sB = _shared_stride(a_B, G2 * M, batch, "B")
@@ -791,6 +796,13 @@ def _off(ptr, elems, size):
     return None if ptr is None else ptr + int(elems) * size
 
 
+def _f64_chunks(batch, per):
+    """(t0, nb) of the calls that solve a batch whose float64 state is ``per`` bytes a problem, each under the limit."""
+    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
+    for t0 in range(0, batch, step):
+        yield t0, min(step, batch - t0)
+
+
 def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None,
                            want_ce=True, ctx=None):
     """:func:`proposed_algorithm` evaluated in float64 on the device (include/jstsp.h: jstsp_proposed_algorithm_f64) -
@@ -801,7 +813,6 @@ def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="app
     a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
     a_A = _Arg(_wide(A), np.complex128, "A")
     a_B = _Arg(_wide(B), np.complex128, "B")
-    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
     batch, N, M = a_sub.batch, a_sub.R, a_sub.C
     Gr, G2 = a_A.C, a_B.R
     if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
@@ -810,13 +821,7 @@ def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="app
         raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
     if type not in ("approximate", "std"):
         raise ValueError("type must be 'approximate' or 'std'")
-    if indx_S is not None:
-        if _is_torch(indx_S):
-            import torch
-            ix2 = indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous()
-        else:
-            ix2 = np.asarray(indx_S).reshape(batch, Gr * G2, 1).astype(np.int32)
-        a_ix = _Arg(ix2, np.int32, "indx_S")
+    a_ix = _indx_arg(indx_S, batch, Gr * G2)
     c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
     sA = _shared_stride(a_A, N * Gr, batch, "A")
     sB = _shared_stride(a_B, G2 * M, batch, "B")
@@ -832,10 +837,8 @@ def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="app
     per = 16 * (8 * N * M + 5 * Gr * G2 + Gr * M + N * G2 + 20 * n * n + (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0))
     if mem == HOST:
         per += 16 * (2 * N * M + Gr * G2 + (G2 * M if sB else 0) + (N * Gr if sA else 0)) + 8 * N * M
-    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
     dp = C.POINTER(C.c_double)
-    for t0 in range(0, batch, step):
-        nb = min(step, batch - t0)
+    for t0, nb in _f64_chunks(batch, per):
         rc = c._lib.jstsp_proposed_algorithm_f64(
             c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
             _off(a_B.ptr, t0 * sB, 16), sB, int(Imax), tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp),
@@ -866,7 +869,6 @@ def proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, in
     a_B = _Arg(_wide(B), np.complex128, "B")
     a_PA = _Arg(_wide(PA), np.complex128, "PA", allow_none=True)
     a_PB = _Arg(_wide(PB), np.complex128, "PB", allow_none=True)
-    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
     batch, N, M = a_sub.batch, a_sub.R, a_sub.C
     Gr, G2 = a_A.C, a_B.R
     if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
@@ -876,13 +878,7 @@ def proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, in
     for a_P, a_F, nmP in ((a_PA, a_A, "PA"), (a_PB, a_B, "PB")):
         if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
             raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
-    if indx_S is not None:
-        if _is_torch(indx_S):
-            import torch
-            ix2 = indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous()
-        else:
-            ix2 = np.asarray(indx_S).reshape(batch, Gr * G2, 1).astype(np.int32)
-        a_ix = _Arg(ix2, np.int32, "indx_S")
+    a_ix = _indx_arg(indx_S, batch, Gr * G2)
     sA = _shared_stride(a_A, N * Gr, batch, "A")
     sB = _shared_stride(a_B, G2 * M, batch, "B")
     tY, _ = _scalars(tau_Y, batch, "tau_Y")
@@ -899,11 +895,9 @@ def proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, in
     per += 16 * ((2 * N * Gr + 3 * Gr * Gr if sA and a_PA.ptr is None else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and a_PB.ptr is None else 0))
     if mem == HOST:
         per += 16 * (2 * N * M + Gr * G2 + 2 * (G2 * M if sB else 0) + 2 * (N * Gr if sA else 0)) + 8 * N * M
-    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
     dp = C.POINTER(C.c_double)
     rcs = []
-    for t0 in range(0, batch, step):
-        nb = min(step, batch - t0)
+    for t0, nb in _f64_chunks(batch, per):
         prc, rc1 = _vec_out(mem == DEVICE, 2, np.float64, dev) if info else (None, None)
         rc = c._lib.jstsp_proposed_std_f64(
             c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
@@ -1111,9 +1105,7 @@ def OMP_f64(A, v, m, snr=None, *, want_target=True, ctx=None):
     pt, ft = _out(mem == DEVICE, batch, meas, m, np.complex128, dev) if want_target else (None, None)
     # bytes of float64 state per problem (csrc/omp64.hip): residual, basis, triangular factor, correlations, staged copies
     per = 16 * (2 * meas + meas * m + m * m + m + 2 * size_d + (meas * size_d if sA else 0) + (meas * m if want_target else 0)) + 16 * m
-    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
-    for t0 in range(0, batch, step):
-        nb = min(step, batch - t0)
+    for t0, nb in _f64_chunks(batch, per):
         check(c._lib.jstsp_omp_f64(c.handle, meas, size_d, nb, _off(a_A.ptr, t0 * sA, 16), sA, _off(a_v.ptr, t0 * meas, 16), m,
                                    _off(px, t0 * size_d, 16), _off(pi, t0 * m, 4), _off(pt, t0 * meas * m, 16), mem), "jstsp_omp_f64")
     return fx(single)[..., 0], fi(single)[..., 0], v, (ft(single) if want_target else None)
@@ -1135,9 +1127,7 @@ def omp_kron_f64(Af, Bf, y, m, *, ctx=None):
     px, fx = _out(mem == DEVICE, batch, Gr * G2, 1, np.complex128, dev)
     pi, fi = _out(mem == DEVICE, batch, m, 1, np.int32, dev)
     per = 16 * (2 * N * M + N * M * m + m * m + m + 2 * Gr * G2 + 17 * Gr * M + sA + sB) + 16 * m
-    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
-    for t0 in range(0, batch, step):
-        nb = min(step, batch - t0)
+    for t0, nb in _f64_chunks(batch, per):
         check(c._lib.jstsp_omp_kron_f64(c.handle, N, M, Gr, G2, nb, _off(a_A.ptr, t0 * sA, 16), sA, _off(a_B.ptr, t0 * sB, 16), sB,
                                         _off(a_y.ptr, t0 * N * M, 16), m, _off(px, t0 * Gr * G2, 16), _off(pi, t0 * m, 4), mem),
               "jstsp_omp_kron_f64")
@@ -1165,9 +1155,7 @@ def sparse_admm_f64(Htrue, OH, Dr, Dt, Imax, *, want_ce=True, ctx=None):
     pce, fce = _out(mem == DEVICE, batch, Imax, 1, np.float64, dev) if want_ce else (None, None)
     n = min(Mr, Mt)
     per = 16 * (10 * Mr * Mt + (6 * n * n + 16 * Mr * Mt if want_ce else 0)) + 8 * Imax
-    step = max(1, min(batch, _F64_CHUNK_BYTES // max(per, 1), 65535))
-    for t0 in range(0, batch, step):
-        nb = min(step, batch - t0)
+    for t0, nb in _f64_chunks(batch, per):
         check(c._lib.jstsp_sparse_admm_f64(c.handle, Mr, Mt, a_Dr.C, a_Dt.C, nb, _off(a_H.ptr, t0 * Mr * Mt, 16), _off(a_O.ptr, t0 * Mr * Mt, 16),
                                            a_Dr.ptr, a_Dt.ptr, Imax, _off(p, t0 * Mr * Mt, 16), _off(pce, t0 * Imax, 8), mem),
               "jstsp_sparse_admm_f64")
