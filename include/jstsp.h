@@ -115,7 +115,8 @@ size_t jstsp_workspace_bytes(const jstsp_ctx *ctx);
  *                         0 never, 1 always - then every returned value is the cold one; jstsp_last_lanczos_mismatches)
  *   JSTSP_EIG128=0        general Jacobi kernel (basis in HBM) for Gram orders 65..128
  *   JSTSP_BJ_MASK=0       block Jacobi (orders above 128) without streams restricted to a subset of the compute units
- * (JSTSP_DEVICE=<id> is read by the MEX gateway, not by the library.) */
+ * (JSTSP_DEVICE=<id> is read by the MEX gateway, not by the library.)
+ * jstsp_build_trials_from_channel_c32 adds no variable: the form of the channel and its normalisation are arguments. */
 
 /* ---- kernel-level entry points (the north-star correlation / synthesis) ------------ */
 
@@ -481,7 +482,7 @@ typedef struct jstsp_model {
     int T_prop;             /* training length of the proposed scheme (T*Nt)         :23                     */
     int Mr, Mr_e;           /* RF chains sampled per slot / extended                 :15-16                  */
     int Gr, Gt;             /* dictionary sizes                                      :13-14                  */
-    int clusters, rays;     /* total_num_of_clusters, total_num_of_rays              :18-19                  */
+    int clusters, rays;     /* total_num_of_clusters, total_num_of_rays              :18-19 (ignored for a supplied channel) */
     int T_hbf;              /* training length of the conventional HBF baseline (0 = not wanted) :22         */
     int shared_pilots;      /* 0: new pilots every trial (plot_errorVSsnr.m:63-67); 1: one pilot set per sweep point */
     double noise_var;       /* 10^(-snr_db/10)                                       :49                     */
@@ -530,6 +531,39 @@ typedef struct jstsp_trials {
 
 int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx,
                            long long trial0, int batch, const jstsp_trials *out, int memspace);
+
+/* The same construction from a channel the caller supplies - NYUSIM or ray-tracing output, a measured channel - instead of the
+ * drawn one: the first lines of plot_errorVSsnr_nyuwireless.m (:60-69), which loads Hf{l}, one matrix per delay tap, and cuts and
+ * scales it.  Everything downstream of H is the code of jstsp_build_trials_c32 (csrc/inputgen.hip: one body, two entry points).
+ *  - Hsrc: column-major taps as MATLAB stores H(:,:,l): tap l starts at Hsrc + l*ld_rows*ld_cols, its entry (r, s) is at
+ *    r + ld_rows*s; ld_rows >= Nr, ld_cols >= Nt, the leading Nr x Nt block is used (Hfl(1:Nr, 1:Nt), :63-64).  strideH = 0: one
+ *    channel for every trial (what the driver does); otherwise trial t of the call reads Hsrc + t*strideH, strideH >=
+ *    L*ld_rows*ld_cols.  Same memspace as the outputs.
+ *  - normalize, per tap, with s = norm(H_l), the largest singular value: JSTSP_CHAN_ASIS H_l as given (the stored bits are the
+ *    input bits); JSTSP_CHAN_REFERENCE H_l / s^2 - lines :65-66 AS WRITTEN, rho = 1/norm(H(:,:,l))^2; H(:,:,l) = rho*H(:,:,l), which
+ *    leaves a tap of spectral norm 1/s, not 1: the quirk is kept; JSTSP_CHAN_UNIT H_l / s.  Each entry is scaled in float64 and
+ *    rounded once to fp32.
+ *  - sigma_max: L x batch doubles (L when strideH = 0), HOST memory in either memspace like tau_Y; receives s in every mode;
+ *    NULL = not wanted.  s is sqrt(lambda_max) of the float64 Hermitian Gram on the smaller side (order min(Nr, Nt) <= 64, in
+ *    LDS, the Jacobi of the float64 solvers), of the tap scaled exactly by a power of two so that taps of size 2^+-40 lose
+ *    nothing; a value does not depend on the batch it is computed in.
+ *  - model: clusters and rays are ignored (may be 0); every other field means what it means above.
+ *  - out: gains, u_r and u_t must be NULL (JSTSP_E_ARG: nothing was drawn); H returns the cut and scaled channel in the builder's
+ *    layout.  Noise, pilot symbols and Omega come from the same Philox streams: for equal model, seed, sweep and trial both entry
+ *    points return the same noise, qam_idx, pilot_sym and Omega bits.
+ *  - JSTSP_E_SHAPE: ld_rows < Nr, ld_cols < Nt, a non-zero stride that is too short; JSTSP_E_ARG: bad normalize; JSTSP_E_NULL:
+ *    Hsrc NULL; JSTSP_E_ILLCOND: a NaN or Inf in a used block, or s == 0 under _REFERENCE / _UNIT - the message names the tap and
+ *    the trial, and no output has been written (entries outside the used block are never read); JSTSP_E_UNSUPPORTED:
+ *    min(Nr, Nt) > 64 when s is needed (JSTSP_CHAN_ASIS without sigma_max has no such limit).
+ *  - The call waits for its stream once before it builds (s and the flag word come to the host in one copy), in either memspace.
+ *  Asserted (tests/test_gpu_measured_channel.py): the drawn path's H passed back JSTSP_CHAN_ASIS returns every array of the drawn
+ *  call on the bits; against the float64 oracle on the cut and scaled channel the tolerances of jstsp_build_trials_c32; sigma_max
+ *  within 1e-12 relative of numpy's norm(H_l, 2). */
+enum { JSTSP_CHAN_ASIS = 0, JSTSP_CHAN_REFERENCE = 1, JSTSP_CHAN_UNIT = 2 };
+int jstsp_build_trials_from_channel_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx,
+                                        long long trial0, int batch,
+                                        const jstsp_c32 *Hsrc, int ld_rows, int ld_cols, long long strideH, int normalize,
+                                        const jstsp_trials *out, double *sigma_max, int memspace);
 
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),

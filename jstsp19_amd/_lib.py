@@ -16,6 +16,7 @@ TYPE_APPROXIMATE, TYPE_STD = 0, 1
 BF_ZC, BF_DFT, BF_QUANTIZED, BF_QUANTIZED4 = 0, 1, 2, 3
 RHO_MIN6, RHO_MAX = 0, 1
 PILOTS_QAM4, PILOTS_GAUSS = 0, 1
+CHAN_ASIS, CHAN_REFERENCE, CHAN_UNIT = 0, 1, 2
 
 c_void_p, c_int, c_ll, c_dp, c_ip = C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_int)
 
@@ -99,6 +100,8 @@ SIGNATURES = {
     "jstsp_nmse_spectral_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     "jstsp_build_trials_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, C.POINTER(Trials),
                                        c_int]),
+    "jstsp_build_trials_from_channel_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, c_void_p, c_int,
+                                                    c_int, c_ll, c_int, C.POINTER(Trials), c_dp, c_int]),
     "jstsp_beamformer_c32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "jstsp_ase_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p,
                               c_int]),

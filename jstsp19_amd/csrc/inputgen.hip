@@ -9,12 +9,16 @@
 //   plot_errorVSsnr.m:127-130       -> hyper_kernel (tau_Y, tau_Z, rho from the 6th largest eigenvalue of Y'Y)
 //   plot_errorVSsnr.m:132-136       -> A = W_e' Dr, B_l = Dt' Psi_l                   (GEMMs)
 //   plot_errorVSsnr.m:143           -> indx_S: stable descending sort of |vec(Zbar)| (64-bit keys, segmented radix sort)
+//   plot_errorVSsnr_nyuwireless.m:62-68 -> a channel the caller supplies instead of the drawn one (jstsp_build_trials_from_channel_c32):
+//                                      given_channel_sigma_kernel (norm(H_l), the non-finite / zero flag), given_channel_pack_kernel
 //
 // Random numbers: Philox4x32-10, key = mix(seed, sweep index, global trial index), counter =
 // (element index, stream id) — a trial's inputs do not depend on the batch it is drawn in or
 // on how trials are sharded over GPUs.
 #include "inputgen.h"
+#include "svt64.h"
 #include <hipcub/hipcub.hpp>
+#include <cstring>
 
 using namespace jstsp;
 
@@ -153,16 +157,131 @@ __global__ void offsets_kernel(int batch, long long nz, int *off)
 }
 
 
+// ---- a supplied channel (plot_errorVSsnr_nyuwireless.m:62-68) ---------------------------------------------------------------------
+// Tap l of channel ch: X = Hsrc + ch * chanStride + l * tapStride, entry (r, s) at r + ldr * s, the leading Nr x Nt block used (:63-64).
+// One workgroup per (channel, tap), blockIdx.x = l + L * ch.  s = norm(X) (:65, the largest singular value) from the Hermitian Gram
+// of the smaller side in float64: X is first scaled by 2^-e, e the frexp exponent of its largest finite |component| (exact, as
+// finite_max_exponent of ws64.h does for OMP), every Gram entry is one fma chain over the long side in index order (a result does
+// not depend on the batch it is computed in; G(j, i) = conj(G(i, j)) on the bits), lambda_max by the in-LDS Jacobi of svt64.h and
+// s = 2^e sqrt(lambda_max).  A NaN / Inf in the block, or (zero_is_bad) an all-zero block, lowers *flag to 4 * blockIdx.x + 1 / + 2:
+// the smallest index wins, so the word is the same from run to run.  want_s = 0: the check only (no LDS, any order).
+__global__ __launch_bounds__(256) void given_channel_sigma_kernel(int Nr, int Nt, int L, const float2 *Hsrc, int ldr, long long tapStride,
+                                                                  long long chanStride, int want_s, int zero_is_bad, double *sig,
+                                                                  unsigned long long *flag)
+{
+    extern __shared__ double2 gsm[];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, l = blockIdx.x % L, ch = blockIdx.x / L;
+    const float2 *X = Hsrc + (long long)ch * chanStride + (long long)l * tapStride;
+    double vmax = 0.0;
+    int bad = 0;
+    for (int e = tid; e < Nr * Nt; e += 256) {
+        const float2 v = X[(e % Nr) + (long long)ldr * (e / Nr)];
+        const double ax = fabs((double)v.x), ay = fabs((double)v.y);
+        if (ax <= DBL_MAX) vmax = fmax(vmax, ax); else bad = 1;            // (not NaN, not Inf)
+        if (ay <= DBL_MAX) vmax = fmax(vmax, ay); else bad = 1;
+    }
+    bad = __syncthreads_or(bad);
+    for (int o = 32; o > 0; o >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, o));
+    if ((tid & 63) == 0) red[tid >> 6] = vmax;
+    __syncthreads();
+    vmax = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    if (bad || vmax == 0.0) {                                              // (the same for the whole workgroup)
+        if (tid == 0) {
+            if (bad || zero_is_bad) atomicMin(flag, 4ull * blockIdx.x + (bad ? 1ull : 2ull));
+            sig[blockIdx.x] = bad ? nan("") : 0.0;
+        }
+        return;
+    }
+    if (!want_s) return;
+    int ev = 0;
+    (void)frexp(vmax, &ev);
+    const double sc = ldexp(1.0, -ev);              // fp32 exponents: 2^-ev is a normal double and x * sc is exact
+    const bool right = Nt <= Nr;                    // G = X^H X of order Nt; otherwise X X^H of order Nr
+    const int n0 = right ? Nt : Nr, k = right ? Nr : Nt, n = (n0 + 1) & ~1, h2 = n / 2;
+    double2 *H = gsm, *rs = H + (size_t)n * n;
+    double *rc = reinterpret_cast<double *>(rs + h2);
+    double dm = 0.0;
+    for (int e = tid; e < n * n; e += 256) {
+        const int i = e % n, j = e / n;
+        double2 g = make_double2(0.0, 0.0);
+        if (i < n0 && j < n0) {
+            Dot4 d = {0.0, 0.0, 0.0, 0.0};
+            for (int q = 0; q < k; ++q) {
+                const float2 a = right ? X[q + (long long)ldr * i] : X[i + (long long)ldr * q];
+                const float2 b = right ? X[q + (long long)ldr * j] : X[j + (long long)ldr * q];
+                const double2 u = make_double2((double)a.x * sc, (double)a.y * sc), v = make_double2((double)b.x * sc, (double)b.y * sc);
+                if (right) dot4_step(d, u, v);      // sum_q conj(X(q, i)) X(q, j)
+                else dot4_step(d, v, u);            // sum_q X(i, q) conj(X(j, q))
+            }
+            g = make_double2(d.xx + d.yy, d.xy - d.yx);
+        }
+        if (i == j) { g.y = 0.0; dm = fmax(dm, fabs(g.x)); }
+        H[e] = g;
+    }
+    for (int o = 32; o > 0; o >>= 1) dm = fmax(dm, __shfl_xor(dm, o));
+    __syncthreads();                                // (red has been read by every thread)
+    if ((tid & 63) == 0) red[tid >> 6] = dm;
+    __syncthreads();
+    const double EPS = 1.1102230246251565e-16;
+    const double floor_abs = EPS * EPS * fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    jacobi64_lds_sweeps<false>(n, H, nullptr, rs, rc, floor_abs);
+    if (tid == 0) {
+        double mx = H[0].x;
+        for (int i = 1; i < n0; ++i) mx = fmax(mx, H[i + n * i].x);
+        sig[blockIdx.x] = ldexp(sqrt(fmax(mx, 0.0)), ev);
+    }
+}
+
+// Hmat[t] = [H_1 ... H_L] (Nr x Nt*L, the layout of channel_kernel) from the supplied taps: each entry scaled in float64 by 1, 1/s^2
+// (plot_errorVSsnr_nyuwireless.m:65-66 as written: rho = 1/norm(H_l)^2, which leaves a tap of norm 1/s) or 1/s and rounded once
+// to fp32; JSTSP_CHAN_ASIS stores the input bits.  chanStride = 0: one channel, scaled once per entry and written to every trial slot.
+__global__ __launch_bounds__(256) void given_channel_pack_kernel(int Nr, int Nt, int L, int batch, const float2 *Hsrc, int ldr,
+                                                                 long long tapStride, long long chanStride, int normalize,
+                                                                 const double *sig, float2 *Hmat)
+{
+    const long long n_el = (long long)Nr * Nt * L;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n_el; e += (long long)gridDim.x * 256) {
+        const int r = (int)(e % Nr);
+        const int sl = (int)(e / Nr);
+        const int s = sl % Nt, l = sl / Nt;
+        const long long src = (long long)l * tapStride + r + (long long)ldr * s;
+        float2 v = make_float2(0.f, 0.f);
+        for (int t = blockIdx.y; t < batch; t += gridDim.y) {
+            if (chanStride != 0 || t == (int)blockIdx.y) {
+                v = Hsrc[(long long)t * chanStride + src];
+                if (normalize != JSTSP_CHAN_ASIS) {
+                    const double sg = sig[(chanStride != 0 ? (long long)t * L : 0) + l];
+                    const double d = normalize == JSTSP_CHAN_REFERENCE ? sg * sg : sg;
+                    v = make_float2((float)((double)v.x / d), (float)((double)v.y / d));
+                }
+            }
+            Hmat[(size_t)t * n_el + e] = v;
+        }
+    }
+}
+
+
 template <class T> T *out_or_tmp(jstsp_ctx *ctx, T *user, size_t n, int memspace)
 {
     if (user && memspace == JSTSP_DEVICE) return user;
     return ctx->arena.get<T>(n);
 }
 
-}  // namespace
+// the channel of jstsp_build_trials_from_channel_c32 (the arguments of that call)
+struct GivenChannel {
+    const float2 *H;
+    int ld_rows, ld_cols;
+    long long stride;
+    int normalize;
+    double *sigma_max;
+};
 
-extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
-                                      long long trial0, int batch, const jstsp_trials *out, int memspace)
+// The body of both builders.  given == NULL: the channel of wideband_mmwave_channel.m from the Philox draws (jstsp_build_trials_c32);
+// otherwise the caller's taps, cut and scaled (plot_errorVSsnr_nyuwireless.m:62-68) - draw_small_kernel and channel_kernel are then
+// not launched, and everything after Hmat is the same code.
+int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx, long long trial0, int batch,
+                      const GivenChannel *given, const jstsp_trials *out, int memspace)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "build_trials: NULL context");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "build_trials: bad memspace");
@@ -171,6 +290,7 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
     Model m;
     m.Nt = mp->Nt; m.Nr = mp->Nr; m.L = mp->L; m.Tp = mp->T_prop; m.Mr = mp->Mr; m.Mr_e = mp->Mr_e;
     m.Gr = mp->Gr; m.Gt = mp->Gt; m.clusters = mp->clusters; m.rays = mp->rays;
+    if (given) m.clusters = m.rays = 1;             // (ignored: nothing is drawn for the channel)
     JSTSP_REQUIRE(m.Nt > 0 && m.Nr > 0 && m.L > 0 && m.Tp > 0 && m.Gr > 0 && m.Gt > 0 && m.clusters > 0 && m.rays > 0 &&
                       batch > 0 && trial0 >= 0 && sweep_idx >= 0,
                   JSTSP_E_SHAPE, "build_trials: bad model dimensions");
@@ -188,10 +308,35 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
     const int N = m.Mr_e, M = m.Tp, nG = std::min(N, M), Th = mp->T_hbf;
     const bool want_hyp = out->tau_Y || out->tau_Z || out->rho;
     JSTSP_REQUIRE(!want_hyp || nG <= 128, JSTSP_E_UNSUPPORTED, "build_trials: rho needs min(Mr_e, T_prop) <= 128");
-    const size_t lds_ch = ((size_t)(m.Nr + m.Nt) * m.Np + (size_t)m.L * m.Np) * sizeof(float2);
+    const size_t lds_ch = given ? 0 : ((size_t)(m.Nr + m.Nt) * m.Np + (size_t)m.L * m.Np) * sizeof(float2);
     JSTSP_REQUIRE(lds_ch <= 150 * 1024 && (size_t)m.Mr_e * 4 <= 64 * 1024, JSTSP_E_UNSUPPORTED,
                   "build_trials: steering tables exceed the LDS");
     const bool want_hbf = Th > 0 && (out->Y_hbf || out->A_hbf || out->B_hbf);
+    // ---- a supplied channel: its form -----------------------------------------------------------------------------------------
+    const bool shared_ch = given && given->stride == 0;
+    const long long tap_stride = given ? (long long)given->ld_rows * given->ld_cols : 0;
+    const size_t n_sig = given ? (size_t)m.L * (shared_ch ? 1 : (size_t)batch) : 0;
+    bool need_s = false;
+    if (given) {
+        JSTSP_REQUIRE(!out->gains && !out->u_r && !out->u_t, JSTSP_E_ARG,
+                      "build_trials_from_channel: gains, u_r and u_t must be NULL - nothing is drawn for a supplied channel");
+        JSTSP_REQUIRE(given->normalize == JSTSP_CHAN_ASIS || given->normalize == JSTSP_CHAN_REFERENCE ||
+                          given->normalize == JSTSP_CHAN_UNIT,
+                      JSTSP_E_ARG, "build_trials_from_channel: normalize must be JSTSP_CHAN_ASIS, _REFERENCE or _UNIT (got %d)",
+                      given->normalize);
+        JSTSP_REQUIRE(given->H, JSTSP_E_NULL, "build_trials_from_channel: Hsrc is NULL");
+        JSTSP_REQUIRE(given->ld_rows >= m.Nr && given->ld_cols >= m.Nt, JSTSP_E_SHAPE,
+                      "build_trials_from_channel: the source taps are %d x %d, smaller than Nr x Nt = %d x %d", given->ld_rows,
+                      given->ld_cols, m.Nr, m.Nt);
+        JSTSP_REQUIRE(given->stride == 0 || given->stride >= (long long)m.L * tap_stride, JSTSP_E_SHAPE,
+                      "build_trials_from_channel: strideH = %lld is shorter than one channel, L * ld_rows * ld_cols = %lld",
+                      given->stride, (long long)m.L * tap_stride);
+        need_s = given->normalize != JSTSP_CHAN_ASIS || given->sigma_max;
+        JSTSP_REQUIRE(!need_s || std::min(m.Nr, m.Nt) <= P64_LDS_ORDER, JSTSP_E_UNSUPPORTED,
+                      "build_trials_from_channel: the spectral norm of a tap needs min(Nr, Nt) <= %d (got %d); JSTSP_CHAN_ASIS without "
+                      "sigma_max has no such limit", P64_LDS_ORDER, std::min(m.Nr, m.Nt));
+    }
+    const size_t nHsrc = given ? (shared_ch ? 0 : (size_t)(batch - 1) * (size_t)given->stride) + (size_t)m.L * (size_t)tap_stride : 0;
 
     const size_t b = (size_t)batch;
     const size_t nH = (size_t)m.Nr * m.NtL, nPsi = (size_t)m.NtL * m.Tp, nR = (size_t)m.Nr * m.Tp, nY = (size_t)N * M,
@@ -213,11 +358,45 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
     need += GramWS::bytes(N, M, batch, true);
     if (out->indx_S) { acc(b * nZ * 8); acc(b * nZ * 8); acc(sort_tmp); acc((b + 1) * 8); acc(b * nZ * 4); }
     if (want_hbf) { acc(b * (size_t)m.Nr * Th * 8); acc((size_t)m.Nr * m.Gr * 8); acc(b * (size_t)m.G2 * Th * 8); }
+    if (given) { acc((n_sig + 1) * 8); if (memspace == JSTSP_HOST) acc(nHsrc * 8); }
     JSTSP_TRY(ctx->arena.reserve(need + 4096));
     ctx->arena.reset();
     Arena &ar = ctx->arena;
-    float2 *gains = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->gains), b * m.L * m.Np, memspace);
-    float *u_r = out_or_tmp(ctx, out->u_r, b * m.Np, memspace), *u_t = out_or_tmp(ctx, out->u_t, b * m.Np, memspace);
+    hipStream_t st = ctx->stream;
+    // ---- a supplied channel: norm(H_l) and the refusals, decided before any output is written ----------------------------------
+    const float2 *Hsrc = nullptr;
+    double *sig = nullptr;
+    if (given) {
+        sig = ar.get<double>(n_sig + 1);            // s per (channel, tap), then the flag word of the call
+        JSTSP_REQUIRE(sig, JSTSP_E_NOMEM, "build_trials_from_channel: workspace exhausted");
+        JSTSP_TRY(stage_in(ctx, given->H, nHsrc, memspace, &Hsrc));
+        unsigned long long *flag = reinterpret_cast<unsigned long long *>(sig + n_sig);
+        JSTSP_HIP(hipMemsetAsync(flag, 0xFF, sizeof(*flag), st));
+        const size_t sh = need_s ? jacobi_lds_bytes(std::min(m.Nr, m.Nt), false) : 0;
+        if (sh > 48 * 1024)
+            JSTSP_HIP(hipFuncSetAttribute((const void *)given_channel_sigma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        given_channel_sigma_kernel<<<(unsigned)n_sig, 256, sh, st>>>(m.Nr, m.Nt, m.L, Hsrc, given->ld_rows, tap_stride, given->stride,
+                                                                     need_s ? 1 : 0, given->normalize != JSTSP_CHAN_ASIS ? 1 : 0, sig,
+                                                                     flag);
+        JSTSP_HIP(hipGetLastError());
+        std::vector<double> h(n_sig + 1);
+        JSTSP_HIP(hipMemcpyAsync(h.data(), sig, (n_sig + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+        unsigned long long w;
+        memcpy(&w, &h[n_sig], sizeof(w));
+        if (w != ~0ull) {
+            const long long idx = (long long)(w / 4);
+            const int tap = (int)(idx % m.L);
+            const char *what = (w & 3) == 1 ? "has a NaN or Inf in its Nr x Nt block" : "is all zero, so 1/norm(H_l) does not exist";
+            if (shared_ch) set_error("build_trials_from_channel: tap %d of the shared channel %s", tap, what);
+            else set_error("build_trials_from_channel: tap %d of trial %lld %s", tap, trial0 + idx / m.L, what);
+            return JSTSP_E_ILLCOND;
+        }
+        if (given->sigma_max) std::copy(h.begin(), h.begin() + n_sig, given->sigma_max);
+    }
+    float2 *gains = given ? nullptr : out_or_tmp(ctx, reinterpret_cast<float2 *>(out->gains), b * m.L * m.Np, memspace);
+    float *u_r = given ? nullptr : out_or_tmp(ctx, out->u_r, b * m.Np, memspace),
+          *u_t = given ? nullptr : out_or_tmp(ctx, out->u_t, b * m.Np, memspace);
     float2 *noise = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->noise), b * nR, memspace);
     uint8_t *qam = out_or_tmp(ctx, out->qam_idx, b * nQ, memspace);
     float2 *psym = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->pilot_sym), b * nQ, memspace);
@@ -233,14 +412,13 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
     float2 *T1 = ar.get<float2>(b * (size_t)m.Gr * m.NtL);
     double *hyp = ar.get<double>(b * 3);
     float *lam = ar.get<float>(b * nG);
-    JSTSP_REQUIRE(gains && u_r && u_t && noise && qam && psym && Dr && Dt && W && Hmat && Psi && R && WR && subY && Omega &&
+    JSTSP_REQUIRE((given || (gains && u_r && u_t)) && noise && qam && psym && Dr && Dt && W && Hmat && Psi && R && WR && subY && Omega &&
                       A && (B || !out->B) && Zbar && T1 && hyp && lam,
                   JSTSP_E_NOMEM, "build_trials: workspace exhausted");
-    hipStream_t st = ctx->stream;
     const uint64_t sw = (uint64_t)sweep_idx;
 
     // ---- draws ------------------------------------------------------------------------------
-    draw_small_kernel<<<batch, 64, 0, st>>>(m, seed, sw, trial0, gains, u_r, u_t);
+    if (!given) draw_small_kernel<<<batch, 64, 0, st>>>(m, seed, sw, trial0, gains, u_r, u_t);
     draw_noise_qam_kernel<<<dim3(grid_for((long long)std::max(nR, nQ), 1024), batch), 256, 0, st>>>(m, seed, sw, trial0,
                                                                                                       noise, qam, mp->shared_pilots, gauss, psym);
     omega_kernel<<<dim3(m.Tp, batch), 256, (size_t)m.Mr_e * 4, st>>>(m, seed, sw, trial0, Omega);
@@ -250,7 +428,11 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
     // createBeamformer.m: 'ZC' (:15-16, plot_errorVSsnr.m:124) or 'fft' / 'ps' (:5,:12-13 - the same unitary DFT matrix)
     dict_kernel<<<grid_for((long long)m.Nr * m.Nr), 256, 0, st>>>(m.Nr, m.Nr, mp->beamformer == JSTSP_BF_ZC ? 1 : 0, W);
     // ---- channel, pilots ------------------------------------------------------------------------
-    channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, Hmat);
+    if (!given)
+        channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, Hmat);
+    else
+        given_channel_pack_kernel<<<dim3(grid_for((long long)nH, 64), shared_ch ? std::min(batch, 16) : batch), 256, 0, st>>>(
+            m.Nr, m.Nt, m.L, batch, Hsrc, given->ld_rows, tap_stride, given->stride, given->normalize, sig, Hmat);
     pilots_kernel<<<dim3(grid_for((long long)nPsi, 1024), batch), 256, 0, st>>>(m, psym, gauss ? 0.70710678f : 1.f, Psi);
     JSTSP_HIP(hipGetLastError());
     // R = [H_1..H_L] Psi + sqrt(var/2) noise                                     proposed_hbf.m:19-22
@@ -351,4 +533,21 @@ extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uin
         JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
+                                      long long trial0, int batch, const jstsp_trials *out, int memspace)
+{
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, out, memspace);
+}
+
+extern "C" int jstsp_build_trials_from_channel_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
+                                                   long long trial0, int batch, const jstsp_c32 *Hsrc, int ld_rows, int ld_cols,
+                                                   long long strideH, int normalize, const jstsp_trials *out, double *sigma_max,
+                                                   int memspace)
+{
+    const GivenChannel g{reinterpret_cast<const float2 *>(Hsrc), ld_rows, ld_cols, strideH, normalize, sigma_max};
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, &g, out, memspace);
 }

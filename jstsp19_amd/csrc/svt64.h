@@ -21,32 +21,14 @@ __device__ __forceinline__ void pair_of(int n, int r, int s, int &p, int &q)
     p = min(a, b); q = max(a, b);
 }
 
-// G (n0 x n0 Hermitian, leading dimension n0) = U diag(lam) U^H.  VECS: U and all lam are written; otherwise lam[t] = lambda_max.
-// LDS: H (n x n), [U (n x n)], n / 2 rotations (c, s), n even >= n0 (an odd order gets a decoupled zero row and column).
-// A pair is rotated when |h_pq| > eps sqrt(|h_pp h_qq|) and |h_pq| > eps^2 dmax, dmax the largest diagonal entry of G (entries below
-// the second level are rounding residue of a rank-deficient G: rotating them moves no eigenvalue by more than eps^2 dmax).
+// The sweeps themselves, on H (n x n, n even) already in LDS [and U = I]: every thread of the workgroup of 256 calls; rs, rc: room
+// for the n / 2 rotations; floor_abs = eps^2 dmax.  On return the diagonal of H holds the eigenvalues (a barrier has passed).
+// Shared by jacobi64_lds_kernel below and by the kernels that build their Gram in LDS themselves (inputgen.hip: sigma_max of a tap).
 template <bool VECS>
-__global__ __launch_bounds__(256) void jacobi64_lds_kernel(int n0, const double2 *G, long long sG, double2 *Uout, double *lam)
+__device__ __forceinline__ void jacobi64_lds_sweeps(int n, double2 *H, double2 *U, double2 *rs, double *rc, double floor_abs)
 {
-    extern __shared__ double2 sm[];
-    const int n = (n0 + 1) & ~1, h2 = n / 2, t = blockIdx.x, tid = threadIdx.x;
-    double2 *H = sm, *U = sm + (size_t)n * n, *rs = U + (VECS ? (size_t)n * n : 0);
-    double *rc = reinterpret_cast<double *>(rs + h2), *red = rc + h2;
+    const int h2 = n / 2, tid = threadIdx.x;
     const double EPS = 1.1102230246251565e-16;
-    const double2 *g = G + (long long)t * sG;
-    double dm = 0.0;
-    for (int e = tid; e < n * n; e += 256) {
-        const int i = e % n, j = e / n;
-        double2 x = make_double2(0.0, 0.0);
-        if (i < n0 && j < n0) x = g[i + (long long)n0 * j];
-        if (i == j) { x.y = 0.0; dm = fmax(dm, fabs(x.x)); }
-        H[e] = x;
-        if (VECS) U[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
-    }
-    for (int o = 32; o > 0; o >>= 1) dm = fmax(dm, __shfl_xor(dm, o));
-    if ((tid & 63) == 0) red[tid >> 6] = dm;
-    __syncthreads();
-    const double floor_abs = EPS * EPS * fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
     for (int sweep = 0; sweep < P64_SWEEPS; ++sweep) {
         int rotated = 0;
         for (int r = 0; r < n - 1; ++r) {
@@ -108,6 +90,35 @@ __global__ __launch_bounds__(256) void jacobi64_lds_kernel(int n0, const double2
         }
         if (!__syncthreads_or(rotated)) break;
     }
+}
+
+// G (n0 x n0 Hermitian, leading dimension n0) = U diag(lam) U^H.  VECS: U and all lam are written; otherwise lam[t] = lambda_max.
+// LDS: H (n x n), [U (n x n)], n / 2 rotations (c, s), n even >= n0 (an odd order gets a decoupled zero row and column).
+// A pair is rotated when |h_pq| > eps sqrt(|h_pp h_qq|) and |h_pq| > eps^2 dmax, dmax the largest diagonal entry of G (entries below
+// the second level are rounding residue of a rank-deficient G: rotating them moves no eigenvalue by more than eps^2 dmax).
+template <bool VECS>
+__global__ __launch_bounds__(256) void jacobi64_lds_kernel(int n0, const double2 *G, long long sG, double2 *Uout, double *lam)
+{
+    extern __shared__ double2 sm[];
+    const int n = (n0 + 1) & ~1, h2 = n / 2, t = blockIdx.x, tid = threadIdx.x;
+    double2 *H = sm, *U = sm + (size_t)n * n, *rs = U + (VECS ? (size_t)n * n : 0);
+    double *rc = reinterpret_cast<double *>(rs + h2), *red = rc + h2;
+    const double EPS = 1.1102230246251565e-16;
+    const double2 *g = G + (long long)t * sG;
+    double dm = 0.0;
+    for (int e = tid; e < n * n; e += 256) {
+        const int i = e % n, j = e / n;
+        double2 x = make_double2(0.0, 0.0);
+        if (i < n0 && j < n0) x = g[i + (long long)n0 * j];
+        if (i == j) { x.y = 0.0; dm = fmax(dm, fabs(x.x)); }
+        H[e] = x;
+        if (VECS) U[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
+    }
+    for (int o = 32; o > 0; o >>= 1) dm = fmax(dm, __shfl_xor(dm, o));
+    if ((tid & 63) == 0) red[tid >> 6] = dm;
+    __syncthreads();
+    const double floor_abs = EPS * EPS * fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    jacobi64_lds_sweeps<VECS>(n, H, U, rs, rc, floor_abs);
     if (VECS) {
         for (int e = tid; e < n0 * n0; e += 256) Uout[(long long)t * n0 * n0 + e] = U[(e % n0) + n * (e / n0)];
         for (int i = tid; i < n0; i += 256) lam[(long long)t * n0 + i] = H[i + n * i].x;

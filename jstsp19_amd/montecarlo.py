@@ -18,7 +18,7 @@ from .system_model import SweepParams, TrainingParams, ase_trials, build_trials,
 
 __all__ = ["partition", "run_sweep", "run_points", "sweep_points", "run_approx_sweep", "driver", "run_driver",
            "admmiters_points", "run_convergence_curves", "zy_points", "run_zy", "capacity_points", "capacity_designs",
-           "power_model", "run_capacity", "rank_points", "run_rank"]
+           "power_model", "run_capacity", "rank_points", "run_rank", "load_channel"]
 
 
 def partition(n_items, world, rank):
@@ -43,17 +43,22 @@ def driver(name):
     metric=d["metric"], baselines=True)``.  Each driver's construction quirks are kept: beamformer kind, the
     min/max eigenvalue in rho, the (L, T) and (Nt, T) pairs that move together.
 
-    ================== ======================================= =====================================================
-    name               sweep axis                              cite
-    ================== ======================================= =====================================================
-    errorVSsnr         snr_db = -15:3:15                       plot_errorVSsnr.m:8-25,124-130
-    errorVSdelays      L = 2,4,6,8,10 with T = 5,10,...,25     plot_errorVSdelays.m:7-21,43-46,122,128
-    errorVSframelength T = 5,15,25,35 (Nt = 8, 'fft')          plot_errorVSframelength.m:7-22,44-46,123,129
-    errorVSnrf         Mr = 4,8,12,16 (T = 5)                  plot_errorVSnrf.m:7-22,44-46,122,128
-    errorVSnt          Nt = 4,6,8,12,16 with T = 35,..,35,25   plot_errorVSnt.m:7-22,44-48,123,129
-    errorVSpaths       rays = 1,3,6,9,12                       plot_errorVSpaths.m:7-23,45,122,128
-    rateVSframelength  T = 5,10,15 (Nt = 8, 'fft'), rate       plot_rateVSframelength.m:7-22,44-46,116,122
-    ================== ======================================= =====================================================
+    ====================== ======================================= =====================================================
+    name                   sweep axis                              cite
+    ====================== ======================================= =====================================================
+    errorVSsnr             snr_db = -15:3:15                       plot_errorVSsnr.m:8-25,124-130
+    errorVSdelays          L = 2,4,6,8,10 with T = 5,10,...,25     plot_errorVSdelays.m:7-21,43-46,122,128
+    errorVSframelength     T = 5,15,25,35 (Nt = 8, 'fft')          plot_errorVSframelength.m:7-22,44-46,123,129
+    errorVSnrf             Mr = 4,8,12,16 (T = 5)                  plot_errorVSnrf.m:7-22,44-46,122,128
+    errorVSnt              Nt = 4,6,8,12,16 with T = 35,..,35,25   plot_errorVSnt.m:7-22,44-48,123,129
+    errorVSpaths           rays = 1,3,6,9,12                       plot_errorVSpaths.m:7-23,45,122,128
+    rateVSframelength      T = 5,10,15 (Nt = 8, 'fft'), rate       plot_rateVSframelength.m:7-22,44-46,116,122
+    errorVSsnr_nyuwireless snr_db = -15:3:15, a SUPPLIED channel   plot_errorVSsnr_nyuwireless.m:9-26,60-69,135-141
+    ====================== ======================================= =====================================================
+
+    ``errorVSsnr_nyuwireless`` draws no channel: it loads one (``Hf{l}``, one matrix per delay tap) from a file the reference
+    does not ship.  Its dict carries ``needs_channel=True``; pass any channel as ``run_driver(name, channel=H)`` (``load_channel``
+    reads one from a file).
     """
     snr = lambda db: dict(snr_db=float(db))
     if name == "errorVSsnr":
@@ -86,6 +91,10 @@ def driver(name):
         base = SweepParams(Nt=8, Nr=32, L=4, T=5, Mr=4, beamformer="fft", **snr(15))
         axis, values, pts = "T", [5, 10, 15], None
         cfg = dict(Imax=100, numOfnz=50, n_trials=1, metric="rate")
+    elif name == "errorVSsnr_nyuwireless":
+        base = SweepParams(Nt=4, Nr=32, L=4, T=25, Mr=4, Mr_e=32)
+        axis, values, pts = "snr_db", list(range(-15, 16, 3)), None
+        cfg = dict(Imax=100, numOfnz=250, n_trials=50, metric="nmse", needs_channel=True)
     else:
         raise ValueError("unknown driver %r" % (name,))
     cfg.update(points=pts if pts is not None else sweep_points(base, axis, values), axis=axis, values=values)
@@ -96,9 +105,58 @@ def run_driver(name, n_trials=None, **kw):
     """``run_points`` on the preset of ``driver(name)`` (all seven columns' worth of baselines unless overridden);
     ``n_trials`` defaults to the driver's own maxMCRealizations."""
     d = driver(name)
+    if d.get("needs_channel") and kw.get("channel") is None:
+        raise ValueError("driver %r draws no channel: pass one as run_driver(%r, channel=H) with H of shape (Nr_src, Nt_src, L) "
+                         "(load_channel(path) reads .npy / .npz / .mat; tools/run_driver.py takes --channel FILE)" % (name, name))
     kw.setdefault("baselines", True)
     return run_points(d["points"], d["n_trials"] if n_trials is None else n_trials, Imax=d["Imax"], numOfnz=d["numOfnz"],
                       metric=d["metric"], **kw)
+
+
+def load_channel(path):
+    """A channel for ``build_trials(..., channel=)`` from a file: ``.npy``, or ``.npz`` with key ``Hf`` or ``H``, holding an
+    array ``(Nr_src, Nt_src, L)``; or a ``.mat`` file with the cell array ``Hf`` of the reference's own file (``Hf{l}``, one
+    matrix per delay tap, plot_errorVSsnr_nyuwireless.m:6,63) or a 3-D array ``Hf`` / ``H``, through ``scipy.io.loadmat``
+    (scipy is imported only then).  Returns a complex numpy array ``(Nr_src, Nt_src, L)``."""
+    import numpy as np
+    ext = str(path).lower().rsplit(".", 1)[-1]
+    if ext == "npy":
+        H = np.load(path, allow_pickle=False)
+    elif ext == "npz":
+        with np.load(path, allow_pickle=False) as z:
+            keys = [k for k in ("Hf", "H") if k in z.files]
+            if not keys:
+                raise ValueError("%s holds %s, neither 'Hf' nor 'H'" % (path, sorted(z.files)))
+            H = z[keys[0]]
+    elif ext == "mat":
+        with open(path, "rb") as f:
+            head = f.read(128)
+        if head[:8] == b"\x89HDF\r\n\x1a\n" or b"MATLAB 7.3" in head:
+            raise ValueError("%s is a MATLAB v7.3 (HDF5) file, which scipy.io.loadmat does not read: save it again with "
+                             "save(..., '-v7'), or convert it to .npy" % (path,))
+        try:
+            from scipy.io import loadmat
+        except ImportError as e:
+            raise ImportError("reading %s needs scipy (scipy.io.loadmat), which is not installed: convert the channel to "
+                              ".npy, an array (Nr_src, Nt_src, L)" % (path,)) from e
+        m = loadmat(path)
+        keys = [k for k in ("Hf", "H") if k in m]
+        if not keys:
+            raise ValueError("%s holds %s, neither 'Hf' nor 'H'" % (path, sorted(k for k in m if not k.startswith("__"))))
+        H = m[keys[0]]
+        if H.dtype == object:                                   # the cell array Hf{l}
+            taps = [np.asarray(t) for t in H.reshape(-1)]
+            if len({t.shape for t in taps}) != 1 or taps[0].ndim != 2:
+                raise ValueError("the cells of %s in %s are not matrices of one size" % (keys[0], path))
+            H = np.stack(taps, axis=2)
+    else:
+        raise ValueError("channel file %s: expected .npy, .npz or .mat" % (path,))
+    H = np.asarray(H)
+    if H.ndim == 2:
+        H = H[:, :, None]
+    if H.ndim != 3:
+        raise ValueError("the channel in %s has shape %r, expected (Nr_src, Nt_src, L)" % (path, H.shape))
+    return H.astype(np.complex128 if H.dtype != np.complex64 else np.complex64, copy=False)
 
 
 def _score(S, zb, metric, noise_var):
@@ -338,7 +396,7 @@ def _merge_cap(p, batch, with_hbf):
 
 def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=None, solve_fn=None, dist=None,
                baselines=False, numOfnz=100, builder=None, metric="nmse", tssr=None, merge=True, vamp_max_order=128,
-               samples=None, ls_precision="f32", mmv_precision="f32"):
+               samples=None, ls_precision="f32", mmv_precision="f32", channel=None, channel_normalize="reference"):
     """Mean capped NMSE per sweep point; columns (proposed_algorithm, proposed_algorithm_angles[, LS, VAMP, MMV-OMP
     [, TSSR]]).  ``metric="rate"``: the rate of plot_rateVSframelength.m:81 instead of the NMSE (HIP solvers only).
     ``tssr=(Imax_svt, rho_svt)`` adds the commented recipes of plot_errorVSsnr.m:151-162 as columns six and seven: TSSR
@@ -358,9 +416,17 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
     least-squares entries (see ``_hip_baselines``); the default "f32" leaves every column as it was.
     ``mmv_precision="f64"``: the MMV-OMP, TSSR and SVT-based columns from the float64 entries (``mmv_omp_f64``, ``tssr_f64``),
     scored in float64 - numbers also where the fp32 chain refuses the size of ``B``; the default "f32" changes nothing.
+    ``channel``, ``channel_normalize``: handed to ``build_trials`` - a supplied channel instead of the drawn one, shared
+    ``(Nr_src, Nt_src, L)`` or one per trial ``(n_trials, Nr_src, Nt_src, L)`` (the same n_trials channels at every sweep
+    point); library builder only.
     Returns a float64 tensor (len(points), ncol) identical on every rank.
     """
     _check_precisions(ls_precision, mmv_precision)
+    if channel is not None:
+        if builder is not None and builder != "hip":
+            raise ValueError("channel= goes to the library's builder; a callable builder makes its own channel")
+        if len(channel.shape) == 4 and channel.shape[0] != n_trials:
+            raise ValueError("a per-trial channel needs n_trials = %d channels, not %d" % (n_trials, channel.shape[0]))
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     if device is None:
@@ -392,7 +458,12 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
                            or total + (t1 - t0) > _merge_cap(p, batch, baselines)):
                 break
             if builder == "hip":
-                inps.append(build_trials(p, t0, t1 - t0, seed=seed, sweep_idx=pt, device=device, with_hbf=baselines))
+                if channel is None:
+                    inps.append(build_trials(p, t0, t1 - t0, seed=seed, sweep_idx=pt, device=device, with_hbf=baselines))
+                else:
+                    inps.append(build_trials(p, t0, t1 - t0, seed=seed, sweep_idx=pt, device=device, with_hbf=baselines,
+                                             channel=channel if len(channel.shape) == 3 else channel[t0:t1],
+                                             channel_normalize=channel_normalize))
             else:
                 inps.append(builder(p, range(t0, t1), seed, pt, device, baselines))
             chunks.append((pt, t1 - t0))

@@ -116,8 +116,54 @@ def build_trials_training(p: TrainingParams, trial0, batch, *, seed=20190913, sw
     return o
 
 
+_CHANNEL_NORMALIZE = {"asis": 0, "reference": 1, "unit": 2}         # JSTSP_CHAN_* (include/jstsp.h)
+
+
+def _check_channel(p, batch, channel, channel_normalize):
+    """Shape and dtype of a supplied channel, on the Python side (nothing of the library is touched): returns
+    (per_trial, Nr_src, Nt_src)."""
+    if channel_normalize not in _CHANNEL_NORMALIZE:
+        raise ValueError("channel_normalize must be 'asis', 'reference' or 'unit', not %r" % (channel_normalize,))
+    if not hasattr(channel, "shape") or not hasattr(channel, "dtype"):
+        raise TypeError("channel must be a numpy or torch complex array, not %s" % type(channel).__name__)
+    cplx = channel.is_complex() if torch.is_tensor(channel) else channel.dtype.kind == "c"
+    if not cplx:
+        raise TypeError("channel must be complex (complex64, or complex128 which is narrowed once), not %s" % (channel.dtype,))
+    shape = tuple(channel.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError("channel must be (Nr_src, Nt_src, L) or (batch, Nr_src, Nt_src, L), not %r" % (shape,))
+    if len(shape) == 4 and shape[0] != batch:
+        raise ValueError("a per-trial channel needs one channel per trial of the call: %d, not %d" % (batch, shape[0]))
+    nr, nt, L = shape[-3:]
+    if L != p.L:
+        raise ValueError("channel has %d delay taps, the model has L = %d" % (L, p.L))
+    if nr < p.Nr or nt < p.Nt:
+        raise ValueError("the source taps are %d x %d, smaller than Nr x Nt = %d x %d" % (nr, nt, p.Nr, p.Nt))
+    return len(shape) == 4, nr, nt
+
+
+def _channel_on_device(channel, device):
+    """The supplied channel as a complex64 tensor on ``device`` whose taps are column-major, as MATLAB stores H(:,:,l):
+    strides (1, Nr_src, Nr_src*Nt_src), trial index slowest.  complex128 is narrowed once, on the host side; a tensor that
+    already is complex64, on the device and in that layout is returned as it is."""
+    x = channel if torch.is_tensor(channel) else None
+    if x is None:
+        import numpy as np
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(channel).astype(np.complex64, copy=False)))
+    elif x.dtype != torch.complex64:
+        x = x.to(torch.complex64)
+    nr, nt, L = x.shape[-3:]
+    want = (1, nr, nr * nt) if x.ndim == 3 else (nr * nt * L, 1, nr, nr * nt)
+    if x.device == device and tuple(x.stride()) == want:
+        return x
+    x = x.to(device)
+    perm = (2, 1, 0) if x.ndim == 3 else (0, 3, 2, 1)
+    return x.permute(*perm).contiguous().permute(*perm)
+
+
 def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, device=None, with_hbf=False,
-                 want_draws=False, want_H=False, shared_pilots=False, ctx=None, pilots="qam4"):
+                 want_draws=False, want_H=False, shared_pilots=False, ctx=None, pilots="qam4", channel=None,
+                 channel_normalize="reference"):
     """plot_errorVSsnr.m:57-136 for trials [trial0, trial0 + batch) on the HIP path
     (``jstsp_build_trials_c32``, csrc/inputgen.hip): draws, channel, pilots, measurement, A, B,
     hyper-parameters and indx_S are produced by the library's own kernels — nothing but the output
@@ -126,11 +172,22 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
     ``shared_pilots``: one pilot set for the whole sweep point (``B`` identical for every trial: pass ``B[0]``).
     ``want_draws`` adds the raw draws (gains, u_r, u_t, noise, qam_idx) for checking against a CPU
     restatement.  The Philox streams are keyed by (seed, sweep_idx, global trial index).
+
+    ``channel``: a numpy or torch complex array that replaces the drawn channel (``jstsp_build_trials_from_channel_c32``, the
+    first lines of plot_errorVSsnr_nyuwireless.m:60-69) - ``(Nr_src, Nt_src, L)`` with ``channel[:, :, l]`` as tap l, one
+    channel for every trial, or ``(batch, Nr_src, Nt_src, L)``, one per trial; ``Nr_src >= p.Nr``, ``Nt_src >= p.Nt`` (the
+    leading block is used, :63-64), ``L == p.L``.  ``channel_normalize`` per tap, with s = norm(H_l): "asis", "reference"
+    (H_l / s^2, :65-66 as written - a tap of norm 1/s) or "unit" (H_l / s).  The result has the same keys plus ``sigma_max``,
+    float64 ``(L,)`` or ``(batch, L)`` (left out where "asis" meets min(Nr, Nt) > 64, the one case the library needs no s
+    for and cannot compute it); ``want_draws`` then adds noise, qam_idx and pilot_sym only - nothing else was drawn.  Noise,
+    pilots and Omega are those of the drawn call with the same seed, sweep index and trial.
     """
     import ctypes as C
     import numpy as np
     from . import _lib
     from .solvers import empty_colmajor
+    if channel is not None:
+        per_trial, nr_src, nt_src = _check_channel(p, batch, channel, channel_normalize)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -154,10 +211,11 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
         out["Y_hbf"] = empty_colmajor(batch, p.Nr, Th, c64, device)
         out["A_hbf"] = empty_colmajor(1, p.Nr, Gr, c64, device)[0]
         out["B_hbf"] = empty_colmajor(batch, G2, Th, c64, device)
-    if want_draws:
+    if want_draws and channel is None:
         out["gains"] = torch.empty((batch, p.L, Np), dtype=c64, device=device)
         out["u_r"] = torch.empty((batch, Np), dtype=f32, device=device)
         out["u_t"] = torch.empty((batch, Np), dtype=f32, device=device)
+    if want_draws:
         out["noise"] = empty_colmajor(batch, p.Nr, p.T_prop, c64, device)
         out["qam_idx"] = torch.empty((batch, p.Nt, p.T_prop), dtype=torch.uint8, device=device)
         out["pilot_sym"] = torch.empty((batch, p.Nt, p.T_prop), dtype=c64, device=device)
@@ -167,9 +225,23 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
         setattr(tr, k, v.data_ptr())
     for k, v in hyp.items():
         setattr(tr, k, v.ctypes.data_as(C.POINTER(C.c_double)))
-    rc = c._lib.jstsp_build_trials_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0),
-                                       int(batch), C.byref(tr), _lib.DEVICE)
-    _lib.check(rc, "jstsp_build_trials_c32")
+    if channel is None:
+        rc = c._lib.jstsp_build_trials_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0),
+                                           int(batch), C.byref(tr), _lib.DEVICE)
+        _lib.check(rc, "jstsp_build_trials_c32")
+    else:
+        src = _channel_on_device(channel, device)
+        mode = _CHANNEL_NORMALIZE[channel_normalize]
+        sig = None
+        if mode != _lib.CHAN_ASIS or min(p.Nr, p.Nt) <= 64:
+            sig = np.empty((batch, p.L) if per_trial else (p.L,), dtype=np.float64)
+        rc = c._lib.jstsp_build_trials_from_channel_c32(
+            c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0), int(batch), src.data_ptr(), nr_src, nt_src,
+            nr_src * nt_src * p.L if per_trial else 0, mode, C.byref(tr),
+            sig.ctypes.data_as(C.POINTER(C.c_double)) if sig is not None else None, _lib.DEVICE)
+        _lib.check(rc, "jstsp_build_trials_from_channel_c32")
+        if sig is not None:
+            out["sigma_max"] = torch.from_numpy(sig)
     out.update({k: torch.from_numpy(v) for k, v in hyp.items()})
     return out
 

@@ -2,7 +2,7 @@
 """Any of the reference's sweep drivers at its own parameters on the HIP path:
   errorVSsnr | errorVSdelays | errorVSframelength | errorVSnrf | errorVSnt | errorVSpaths | rateVSframelength
   (columns proposed, proposed+angles, LS, VAMP, MMV-OMP), errorVSadmmiters (mean convergence curves, four panels),
-  errorVSzy (Z vs Y estimate)."""
+  errorVSzy (Z vs Y estimate), errorVSsnr_nyuwireless (the same five columns on a channel you supply: --channel FILE)."""
 import argparse, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +14,11 @@ ap.add_argument("--trials", type=int, default=None, help="default: the driver's 
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--ls-f64", action="store_true", help="LS and Y*pinv(B) of the baseline columns from the float64 entries (jstsp_pinv_f64 / jstsp_ls_f64)")
 ap.add_argument("--mmv-f64", action="store_true", help="MMV-OMP, TSSR and SVT-based baseline columns from the float64 entries (jstsp_mmv_omp_f64 / jstsp_mc_svt_f64)")
+ap.add_argument("--channel", default=None, metavar="FILE",
+                help=".npy, .npz (key Hf or H) or .mat (cell array Hf) with an array (Nr_src, Nt_src, L): the channel instead of the "
+                     "drawn one (errorVSsnr_nyuwireless needs it)")
+ap.add_argument("--channel-normalize", default="reference", choices=["asis", "reference", "unit"],
+                help="per tap, s = norm(H_l): as given, H_l/s^2 (plot_errorVSsnr_nyuwireless.m:65-66 as written) or H_l/s")
 a = ap.parse_args()
 t0 = time.perf_counter()
 if a.name == "errorVSadmmiters":
@@ -34,9 +39,12 @@ elif a.name == "errorVSzy":
     print("capped NMSE, %d realisations, %.1f s:  Z %.6f   Y %.6f" % (n, time.perf_counter() - t0, out[0, 0], out[0, 1]))
 else:
     d = mc.driver(a.name)
+    if d.get("needs_channel") and not a.channel:
+        ap.error("%s draws no channel: give one with --channel FILE (.npy, .npz or .mat: an array (Nr_src, Nt_src, L))" % a.name)
     n = a.trials or d["n_trials"]
+    kw = dict(channel=mc.load_channel(a.channel), channel_normalize=a.channel_normalize) if a.channel else {}
     out = mc.run_driver(a.name, n, batch=min(a.batch, n), ls_precision="f64" if a.ls_f64 else "f32",
-                        mmv_precision="f64" if a.mmv_f64 else "f32")
+                        mmv_precision="f64" if a.mmv_f64 else "f32", **kw)
     torch.cuda.synchronize()
     print("%s (%s), %d trials/point, %.1f s" % (a.name, d["metric"], n, time.perf_counter() - t0))
     print("%-8s proposed  +angles   LS        VAMP      MMV-OMP" % d["axis"])
