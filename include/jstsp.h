@@ -647,6 +647,43 @@ int jstsp_singular_values_c64(jstsp_ctx *ctx, int rows, int cols, int batch, con
 int jstsp_rank_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx, long long trial0, int batch,
                           int n_keep, double *sv, int memspace);
 
+/* ---- singular values at every driver size, and the spectrum sweep on any channel (csrc/svdvals.hip) -------
+ * jstsp_spectrum_c32 / _c64: sv[k + n_keep*t], k < n_keep <= min(rows, cols): the leading singular values of Y_t, descending,
+ * as doubles in the memspace of Y; every other convention as jstsp_singular_values_*.  With m = max(rows, cols) and
+ * n = min(rows, cols), three routes, none through a Gram matrix:
+ *   - a shape jstsp_singular_values_* accepts: that kernel, and its bits;
+ *   - n <= 64, m <= 65536: a float64 tall-skinny QR in front of the same Jacobi.  After a pass that finds the largest component, one workgroup
+ *     per matrix walks the oriented operand once in chunks of 128 (n <= 48) or 64 rows and reduces each stack [R; chunk] to a new n x n
+ *     triangle by Householder reflections in LDS; sv(R) = sv(Y), and R goes to the Jacobi kernel's own code.  The operand is
+ *     scaled by a power of two on load (largest component into [1/2, 1)) and the values scaled back: both exact;
+ *   - 64 < n <= 512, m <= 8192: the one-sided Jacobi of jstsp_pinv_f64 on the operand in global memory, without the inverse.
+ *     Like that entry it waits for the context's stream once per sweep, and takes batch <= 65535.
+ * JSTSP_E_UNSUPPORTED: n > 512, m > 65536, n > 64 with m > 8192, or a workspace (the staged copy of a JSTSP_HOST operand, the
+ * float64 arrays of the third route) above 24 GiB - the message names the largest batch that fits.  A non-finite entry gives NaN
+ * for its own matrix only; the zero matrix gives exact zeros; a repeated call returns the same bits (no atomics, every sum in a
+ * fixed order); a matrix's values depend neither on the batch around it nor on the memspace; sv(Y 2^k) = sv(Y) 2^k on the bits.
+ * Asserted (tests/test_gpu_spectrum.py) against numpy.linalg.svd in float64 on the same operand values, max_k |sv_k - ref_k| / ref_1:
+ * <= 1.1e-13 on the QR route (measured 2.2e-14) and <= 3.6e-13 on the third (measured 7.2e-14), under the 1e-10 fixed beforehand
+ * that no Gram route can meet, on random operands, rank 6, sigma graded over 12 decades and repeated sigma
+ * (profiles/spectrum_measured_tolerances.json).  Unpivoted QR promises this ABSOLUTE bound only: a value far below sigma_1 is not relatively accurate. */
+int jstsp_spectrum_c32(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c32 *Y, int n_keep, double *sv, int memspace);
+int jstsp_spectrum_c64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *Y, int n_keep, double *sv, int memspace);
+
+/* jstsp_rank_trials_c32 at any of those shapes of Nr x T_prop, on the drawn channel or on a supplied one.
+ *   Hsrc == NULL: the drawn channel; on a shape jstsp_rank_trials_c32 accepts, that entry's bits (ld_rows, ld_cols, strideH,
+ *   normalize and sigma_max are ignored).
+ *   Hsrc != NULL: trial t's channel is cut from Hsrc and scaled; ld_rows, ld_cols, strideH, normalize and sigma_max mean what they
+ *   mean in jstsp_build_trials_from_channel_c32 (one implementation, csrc/inputgen.h), error codes included: JSTSP_E_ILLCOND for a
+ *   NaN or Inf in a used block, and then nothing is written.  clusters and rays are ignored.  The pilots come from the same Philox
+ *   streams, so Y is the noise-free receive signal of the trial that entry builds for the same arguments.
+ * On the QR route each entry of Y is formed once, in fp64 from the fp32 operands, as its chunk is loaded; on the third route Y is
+ * written to the workspace first.  The call waits for its stream once when a channel is supplied.  Asserted: <= 5.5e-14 (measured
+ * 1.1e-14) against the float64 SVD of Y rebuilt from the builder's H and pilot symbols at 64 x 160, 32 x 300 and 128 x 100, drawn
+ * and supplied channels; a trial's values depend neither on the batch nor on the memspace; sigma_max has the builder's bits. */
+int jstsp_spectrum_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx, long long trial0, int batch,
+                              const jstsp_c32 *Hsrc, int ld_rows, int ld_cols, long long strideH, int normalize,
+                              int n_keep, double *sv, double *sigma_max, int memspace);
+
 /* ---- the reference's own element type at the boundary ------------------------------------------
  * Same functions, same argument meaning, arrays as MATLAB holds them: interleaved complex DOUBLE, and the 0/1 masks as
  * double (proposed_hbf.m:36-41 builds Omega with zeros()).  Inputs are narrowed and outputs widened on the device;

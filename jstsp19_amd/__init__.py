@@ -8,7 +8,7 @@ There is no CPU fallback: without the built library / without a GPU the calls ra
 from ._lib import Context, JstspError, default_context, load, LIB_PATH, HOST, DEVICE  # noqa: F401
 from .solvers import (OMP, sparse_sca_estim, cawgn_estim_out, gradient_head, ls_estimate, colmajor, correlate, empty_colmajor, mc_admm, mc_svt, nmse_spectral, lambda_max_sequence,  # noqa: F401
                       omp_kron, pinv, mmv_omp, tssr, rate, proposed_algorithm, proposed_algorithm_begin, proposed_algorithm_angles, sparse_admm, svt, synthesize, vamp,
-                      vamp_kron, beamformer, ase, singular_values, cosamp, cosamp_kron,
+                      vamp_kron, beamformer, ase, singular_values, spectrum, cosamp, cosamp_kron,
                       proposed_algorithm_f64, proposed_algorithm_angles_f64, svt_f64, correlate_f64, synthesize_f64,
                       pinv_f64, ls_estimate_f64, mmv_omp_f64, mc_svt_f64, mc_admm_f64, tssr_f64,
                       OMP_f64, omp_kron_f64, sparse_admm_f64, proposed_algorithm_std_f64, proposed_algorithm_angles_std_f64)

@@ -109,13 +109,16 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int]),
     "jstsp_singular_values_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     "jstsp_rank_trials_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, c_int, c_void_p, c_int]),
+    "jstsp_spectrum_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int]),
+    "jstsp_spectrum_trials_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, c_void_p, c_int, c_int, c_ll,
+                                          c_int, c_int, c_void_p, c_dp, c_int]),
     "jstsp_set_profiling": (c_int, [c_void_p, c_int]),
     "jstsp_get_profile": (c_int, [c_void_p, C.c_char_p, c_ip, c_dp]),
 }
 
 
 for _n in ("correlate", "synthesize", "proposed_algorithm", "svt", "omp", "sparse_admm", "mc_svt", "mc_admm", "vamp", "ls", "pinv",
-           "mmv_omp", "vamp_kron", "nmse_spectral", "rate", "beamformer", "ase", "singular_values", "cosamp", "cosamp_kron"):
+           "mmv_omp", "vamp_kron", "nmse_spectral", "rate", "beamformer", "ase", "singular_values", "spectrum", "cosamp", "cosamp_kron"):
     # the double-complex forms take the same argument lists (pointers are void* here)
     SIGNATURES["jstsp_%s_c64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 

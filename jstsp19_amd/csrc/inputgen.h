@@ -194,3 +194,25 @@ inline int draw_operands(jstsp_ctx *ctx, const Model &m, const jstsp_model *mp, 
 }
 
 }  // namespace
+
+namespace jstsp {
+
+// a supplied channel: the arguments of jstsp_build_trials_from_channel_c32 that describe it
+struct GivenChannel {
+    const float2 *H;
+    int ld_rows, ld_cols;
+    long long stride;
+    int normalize;
+    double *sigma_max;
+};
+
+// The cut and scale of a supplied channel for trials [trial0, trial0 + batch) (csrc/inputgen.hip), ONE implementation for the trial
+// builder and the spectrum sweep: checks the form of g (the error codes of jstsp_build_trials_from_channel_c32), reserves the
+// context's arena for caller_bytes plus its own arrays and resets it, computes norm(H_l) per tap, returns JSTSP_E_ILLCOND before
+// anything is written when a used block holds a NaN or Inf (or is zero where 1/s is needed), copies s to g.sigma_max, and writes
+// Hmat[t] = [H_1 .. H_L] (Nr x Nt*L, the layout of channel_kernel) to Hmat_user (device) or, when that is NULL, to an array of
+// the arena.  *Hmat_out: where it is.  Waits for the stream once.
+int given_channel_hmat(jstsp_ctx *ctx, int Nr, int Nt, int L, long long trial0, int batch, const GivenChannel &g, int memspace,
+                       size_t caller_bytes, float2 *Hmat_user, float2 **Hmat_out);
+
+}  // namespace jstsp

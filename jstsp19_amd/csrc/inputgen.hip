@@ -268,15 +268,6 @@ template <class T> T *out_or_tmp(jstsp_ctx *ctx, T *user, size_t n, int memspace
     return ctx->arena.get<T>(n);
 }
 
-// the channel of jstsp_build_trials_from_channel_c32 (the arguments of that call)
-struct GivenChannel {
-    const float2 *H;
-    int ld_rows, ld_cols;
-    long long stride;
-    int normalize;
-    double *sigma_max;
-};
-
 // The body of both builders.  given == NULL: the channel of wideband_mmwave_channel.m from the Philox draws (jstsp_build_trials_c32);
 // otherwise the caller's taps, cut and scaled (plot_errorVSsnr_nyuwireless.m:62-68) - draw_small_kernel and channel_kernel are then
 // not launched, and everything after Hmat is the same code.
@@ -312,31 +303,9 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     JSTSP_REQUIRE(lds_ch <= 150 * 1024 && (size_t)m.Mr_e * 4 <= 64 * 1024, JSTSP_E_UNSUPPORTED,
                   "build_trials: steering tables exceed the LDS");
     const bool want_hbf = Th > 0 && (out->Y_hbf || out->A_hbf || out->B_hbf);
-    // ---- a supplied channel: its form -----------------------------------------------------------------------------------------
-    const bool shared_ch = given && given->stride == 0;
-    const long long tap_stride = given ? (long long)given->ld_rows * given->ld_cols : 0;
-    const size_t n_sig = given ? (size_t)m.L * (shared_ch ? 1 : (size_t)batch) : 0;
-    bool need_s = false;
-    if (given) {
+    if (given)
         JSTSP_REQUIRE(!out->gains && !out->u_r && !out->u_t, JSTSP_E_ARG,
                       "build_trials_from_channel: gains, u_r and u_t must be NULL - nothing is drawn for a supplied channel");
-        JSTSP_REQUIRE(given->normalize == JSTSP_CHAN_ASIS || given->normalize == JSTSP_CHAN_REFERENCE ||
-                          given->normalize == JSTSP_CHAN_UNIT,
-                      JSTSP_E_ARG, "build_trials_from_channel: normalize must be JSTSP_CHAN_ASIS, _REFERENCE or _UNIT (got %d)",
-                      given->normalize);
-        JSTSP_REQUIRE(given->H, JSTSP_E_NULL, "build_trials_from_channel: Hsrc is NULL");
-        JSTSP_REQUIRE(given->ld_rows >= m.Nr && given->ld_cols >= m.Nt, JSTSP_E_SHAPE,
-                      "build_trials_from_channel: the source taps are %d x %d, smaller than Nr x Nt = %d x %d", given->ld_rows,
-                      given->ld_cols, m.Nr, m.Nt);
-        JSTSP_REQUIRE(given->stride == 0 || given->stride >= (long long)m.L * tap_stride, JSTSP_E_SHAPE,
-                      "build_trials_from_channel: strideH = %lld is shorter than one channel, L * ld_rows * ld_cols = %lld",
-                      given->stride, (long long)m.L * tap_stride);
-        need_s = given->normalize != JSTSP_CHAN_ASIS || given->sigma_max;
-        JSTSP_REQUIRE(!need_s || std::min(m.Nr, m.Nt) <= P64_LDS_ORDER, JSTSP_E_UNSUPPORTED,
-                      "build_trials_from_channel: the spectral norm of a tap needs min(Nr, Nt) <= %d (got %d); JSTSP_CHAN_ASIS without "
-                      "sigma_max has no such limit", P64_LDS_ORDER, std::min(m.Nr, m.Nt));
-    }
-    const size_t nHsrc = given ? (shared_ch ? 0 : (size_t)(batch - 1) * (size_t)given->stride) + (size_t)m.L * (size_t)tap_stride : 0;
 
     const size_t b = (size_t)batch;
     const size_t nH = (size_t)m.Nr * m.NtL, nPsi = (size_t)m.NtL * m.Tp, nR = (size_t)m.Nr * m.Tp, nY = (size_t)N * M,
@@ -358,42 +327,18 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     need += GramWS::bytes(N, M, batch, true);
     if (out->indx_S) { acc(b * nZ * 8); acc(b * nZ * 8); acc(sort_tmp); acc((b + 1) * 8); acc(b * nZ * 4); }
     if (want_hbf) { acc(b * (size_t)m.Nr * Th * 8); acc((size_t)m.Nr * m.Gr * 8); acc(b * (size_t)m.G2 * Th * 8); }
-    if (given) { acc((n_sig + 1) * 8); if (memspace == JSTSP_HOST) acc(nHsrc * 8); }
-    JSTSP_TRY(ctx->arena.reserve(need + 4096));
-    ctx->arena.reset();
+    // a supplied channel: given_channel_hmat checks its form, reserves the workspace with its own share on top, and decides the
+    // refusals before any output is written
+    float2 *Hgiven = nullptr;
+    if (given) {
+        JSTSP_TRY(given_channel_hmat(ctx, m.Nr, m.Nt, m.L, trial0, batch, *given, memspace, need + 4096,
+                                     memspace == JSTSP_DEVICE ? reinterpret_cast<float2 *>(out->H) : nullptr, &Hgiven));
+    } else {
+        JSTSP_TRY(ctx->arena.reserve(need + 4096));
+        ctx->arena.reset();
+    }
     Arena &ar = ctx->arena;
     hipStream_t st = ctx->stream;
-    // ---- a supplied channel: norm(H_l) and the refusals, decided before any output is written ----------------------------------
-    const float2 *Hsrc = nullptr;
-    double *sig = nullptr;
-    if (given) {
-        sig = ar.get<double>(n_sig + 1);            // s per (channel, tap), then the flag word of the call
-        JSTSP_REQUIRE(sig, JSTSP_E_NOMEM, "build_trials_from_channel: workspace exhausted");
-        JSTSP_TRY(stage_in(ctx, given->H, nHsrc, memspace, &Hsrc));
-        unsigned long long *flag = reinterpret_cast<unsigned long long *>(sig + n_sig);
-        JSTSP_HIP(hipMemsetAsync(flag, 0xFF, sizeof(*flag), st));
-        const size_t sh = need_s ? jacobi_lds_bytes(std::min(m.Nr, m.Nt), false) : 0;
-        if (sh > 48 * 1024)
-            JSTSP_HIP(hipFuncSetAttribute((const void *)given_channel_sigma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        given_channel_sigma_kernel<<<(unsigned)n_sig, 256, sh, st>>>(m.Nr, m.Nt, m.L, Hsrc, given->ld_rows, tap_stride, given->stride,
-                                                                     need_s ? 1 : 0, given->normalize != JSTSP_CHAN_ASIS ? 1 : 0, sig,
-                                                                     flag);
-        JSTSP_HIP(hipGetLastError());
-        std::vector<double> h(n_sig + 1);
-        JSTSP_HIP(hipMemcpyAsync(h.data(), sig, (n_sig + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-        unsigned long long w;
-        memcpy(&w, &h[n_sig], sizeof(w));
-        if (w != ~0ull) {
-            const long long idx = (long long)(w / 4);
-            const int tap = (int)(idx % m.L);
-            const char *what = (w & 3) == 1 ? "has a NaN or Inf in its Nr x Nt block" : "is all zero, so 1/norm(H_l) does not exist";
-            if (shared_ch) set_error("build_trials_from_channel: tap %d of the shared channel %s", tap, what);
-            else set_error("build_trials_from_channel: tap %d of trial %lld %s", tap, trial0 + idx / m.L, what);
-            return JSTSP_E_ILLCOND;
-        }
-        if (given->sigma_max) std::copy(h.begin(), h.begin() + n_sig, given->sigma_max);
-    }
     float2 *gains = given ? nullptr : out_or_tmp(ctx, reinterpret_cast<float2 *>(out->gains), b * m.L * m.Np, memspace);
     float *u_r = given ? nullptr : out_or_tmp(ctx, out->u_r, b * m.Np, memspace),
           *u_t = given ? nullptr : out_or_tmp(ctx, out->u_t, b * m.Np, memspace);
@@ -402,7 +347,7 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     float2 *psym = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->pilot_sym), b * nQ, memspace);
     float2 *Dr = ar.get<float2>((size_t)m.Nr * m.Gr), *Dt = ar.get<float2>((size_t)m.Nt * m.Gt),
            *W = ar.get<float2>((size_t)m.Nr * m.Nr);
-    float2 *Hmat = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->H), b * nH, memspace);
+    float2 *Hmat = given ? Hgiven : out_or_tmp(ctx, reinterpret_cast<float2 *>(out->H), b * nH, memspace);
     float2 *Psi = ar.get<float2>(b * nPsi), *R = ar.get<float2>(b * nR), *WR = ar.get<float2>(b * nY);
     float2 *subY = out_or_tmp(ctx, reinterpret_cast<float2 *>(out->subY), b * nY, memspace);
     float *Omega = out_or_tmp(ctx, out->Omega, b * nY, memspace);
@@ -428,11 +373,8 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     // createBeamformer.m: 'ZC' (:15-16, plot_errorVSsnr.m:124) or 'fft' / 'ps' (:5,:12-13 - the same unitary DFT matrix)
     dict_kernel<<<grid_for((long long)m.Nr * m.Nr), 256, 0, st>>>(m.Nr, m.Nr, mp->beamformer == JSTSP_BF_ZC ? 1 : 0, W);
     // ---- channel, pilots ------------------------------------------------------------------------
-    if (!given)
+    if (!given)                                 // (a supplied channel is in Hmat already)
         channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, Hmat);
-    else
-        given_channel_pack_kernel<<<dim3(grid_for((long long)nH, 64), shared_ch ? std::min(batch, 16) : batch), 256, 0, st>>>(
-            m.Nr, m.Nt, m.L, batch, Hsrc, given->ld_rows, tap_stride, given->stride, given->normalize, sig, Hmat);
     pilots_kernel<<<dim3(grid_for((long long)nPsi, 1024), batch), 256, 0, st>>>(m, psym, gauss ? 0.70710678f : 1.f, Psi);
     JSTSP_HIP(hipGetLastError());
     // R = [H_1..H_L] Psi + sqrt(var/2) noise                                     proposed_hbf.m:19-22
@@ -536,6 +478,67 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
 }
 
 }  // namespace
+
+// The cut and scale of a supplied channel (plot_errorVSsnr_nyuwireless.m:62-68) for every entry point that takes one
+// (inputgen.h): the form of the arguments, norm(H_l) per tap, the refusals, then Hmat.
+int jstsp::given_channel_hmat(jstsp_ctx *ctx, int Nr, int Nt, int L, long long trial0, int batch, const GivenChannel &g, int memspace,
+                              size_t caller_bytes, float2 *Hmat_user, float2 **Hmat_out)
+{
+    JSTSP_REQUIRE(g.normalize == JSTSP_CHAN_ASIS || g.normalize == JSTSP_CHAN_REFERENCE || g.normalize == JSTSP_CHAN_UNIT, JSTSP_E_ARG,
+                  "build_trials_from_channel: normalize must be JSTSP_CHAN_ASIS, _REFERENCE or _UNIT (got %d)", g.normalize);
+    JSTSP_REQUIRE(g.H, JSTSP_E_NULL, "build_trials_from_channel: Hsrc is NULL");
+    JSTSP_REQUIRE(g.ld_rows >= Nr && g.ld_cols >= Nt, JSTSP_E_SHAPE,
+                  "build_trials_from_channel: the source taps are %d x %d, smaller than Nr x Nt = %d x %d", g.ld_rows, g.ld_cols, Nr, Nt);
+    const bool shared_ch = g.stride == 0;
+    const long long tap_stride = (long long)g.ld_rows * g.ld_cols;
+    JSTSP_REQUIRE(g.stride == 0 || g.stride >= (long long)L * tap_stride, JSTSP_E_SHAPE,
+                  "build_trials_from_channel: strideH = %lld is shorter than one channel, L * ld_rows * ld_cols = %lld", g.stride,
+                  (long long)L * tap_stride);
+    const bool need_s = g.normalize != JSTSP_CHAN_ASIS || g.sigma_max;
+    JSTSP_REQUIRE(!need_s || std::min(Nr, Nt) <= P64_LDS_ORDER, JSTSP_E_UNSUPPORTED,
+                  "build_trials_from_channel: the spectral norm of a tap needs min(Nr, Nt) <= %d (got %d); JSTSP_CHAN_ASIS without "
+                  "sigma_max has no such limit", P64_LDS_ORDER, std::min(Nr, Nt));
+    const size_t n_sig = (size_t)L * (shared_ch ? 1 : (size_t)batch);
+    const size_t nHsrc = (shared_ch ? 0 : (size_t)(batch - 1) * (size_t)g.stride) + (size_t)L * (size_t)tap_stride;
+    const size_t nH = (size_t)Nr * Nt * L;
+    JSTSP_TRY(ctx->arena.reserve(caller_bytes + rnd256((n_sig + 1) * 8) + (memspace == JSTSP_HOST ? rnd256(nHsrc * 8) : 0) +
+                                 (Hmat_user ? 0 : rnd256((size_t)batch * nH * 8))));
+    ctx->arena.reset();
+    hipStream_t st = ctx->stream;
+    double *sig = ctx->arena.get<double>(n_sig + 1);            // s per (channel, tap), then the flag word of the call
+    JSTSP_REQUIRE(sig, JSTSP_E_NOMEM, "build_trials_from_channel: workspace exhausted");
+    const float2 *Hsrc = nullptr;
+    JSTSP_TRY(stage_in(ctx, g.H, nHsrc, memspace, &Hsrc));
+    unsigned long long *flag = reinterpret_cast<unsigned long long *>(sig + n_sig);
+    JSTSP_HIP(hipMemsetAsync(flag, 0xFF, sizeof(*flag), st));
+    const size_t sh = need_s ? jacobi_lds_bytes(std::min(Nr, Nt), false) : 0;
+    if (sh > 48 * 1024)
+        JSTSP_HIP(hipFuncSetAttribute((const void *)given_channel_sigma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    given_channel_sigma_kernel<<<(unsigned)n_sig, 256, sh, st>>>(Nr, Nt, L, Hsrc, g.ld_rows, tap_stride, g.stride, need_s ? 1 : 0,
+                                                                 g.normalize != JSTSP_CHAN_ASIS ? 1 : 0, sig, flag);
+    JSTSP_HIP(hipGetLastError());
+    std::vector<double> h(n_sig + 1);
+    JSTSP_HIP(hipMemcpyAsync(h.data(), sig, (n_sig + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    JSTSP_HIP(hipStreamSynchronize(st));
+    unsigned long long w;
+    memcpy(&w, &h[n_sig], sizeof(w));
+    if (w != ~0ull) {
+        const long long idx = (long long)(w / 4);
+        const int tap = (int)(idx % L);
+        const char *what = (w & 3) == 1 ? "has a NaN or Inf in its Nr x Nt block" : "is all zero, so 1/norm(H_l) does not exist";
+        if (shared_ch) set_error("build_trials_from_channel: tap %d of the shared channel %s", tap, what);
+        else set_error("build_trials_from_channel: tap %d of trial %lld %s", tap, trial0 + idx / L, what);
+        return JSTSP_E_ILLCOND;
+    }
+    if (g.sigma_max) std::copy(h.begin(), h.begin() + n_sig, g.sigma_max);
+    float2 *Hmat = Hmat_user ? Hmat_user : ctx->arena.get<float2>((size_t)batch * nH);
+    JSTSP_REQUIRE(Hmat, JSTSP_E_NOMEM, "build_trials_from_channel: workspace exhausted");
+    given_channel_pack_kernel<<<dim3(grid_for((long long)nH, 64), shared_ch ? std::min(batch, 16) : batch), 256, 0, st>>>(
+        Nr, Nt, L, batch, Hsrc, g.ld_rows, tap_stride, g.stride, g.normalize, sig, Hmat);
+    JSTSP_HIP(hipGetLastError());
+    *Hmat_out = Hmat;
+    return 0;
+}
 
 extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
                                       long long trial0, int batch, const jstsp_trials *out, int memspace)

@@ -35,6 +35,9 @@ size_t pinv64_gemm_ws(int rows, int cols, int count);
 // depend on the matrices around it.  Synchronises the stream once per sweep.
 int pinv64_run(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA, double2 *P, double *rcond,
                int32_t *rank);
+// sv[k + n_keep t] (device) = the k-th largest singular value of A[t], k < n_keep: the same one-sided Jacobi without the inverse
+// (jstsp_spectrum_*, svdvals.hip).  Uses w.W, w.V, w.meta and w.any only.  Synchronises the stream once per sweep.
+int pinv64_values(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA, int n_keep, double *sv);
 // out[0] = the smallest of v[0 .. cnt) (device arrays), NaN when one of them is NaN
 int pinv64_min(hipStream_t st, int cnt, const double *v, double *out);
 

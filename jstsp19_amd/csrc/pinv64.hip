@@ -239,7 +239,64 @@ __global__ void p64_min_kernel(int cnt, const double *v, double *out)
     *out = r;
 }
 
+
+// One workgroup per matrix: the first n_keep column norms of the rotated W in descending order, scaled back, to sv[k + n_keep t]
+// (the singular values alone, spectrum_values below); NaN for a matrix with a non-finite entry.  Equal norms keep column order.
+__global__ __launch_bounds__(256) void p64_values_kernel(int m, int n, const double2 *W, const PvMeta *meta, int n_keep, double *sv)
+{
+    __shared__ double sig[PV_MAX_ORDER];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const PvMeta mt = meta[t];
+    double *out = sv + (long long)n_keep * t;
+    if (mt.bad) {
+        for (int k = tid; k < n_keep; k += 256) out[k] = __builtin_nan("");
+        return;
+    }
+    const double2 *Wt = W + (long long)t * m * n;
+    for (int k = w; k < n; k += 4) {
+        const double2 *c = Wt + (long long)k * m;
+        double a = 0.0;
+        for (int i = lane; i < m; i += 64) a += c[i].x * c[i].x + c[i].y * c[i].y;
+        a = wave_sum(a);
+        if (lane == 0) sig[k] = sqrt(a);
+    }
+    __syncthreads();
+    const double unscale = 1.0 / mt.sc;                           // (a power of two: exact)
+    for (int i = tid; i < n; i += 256) {
+        const double v = sig[i];
+        int rank = 0;
+        for (int k = 0; k < n; ++k) rank += (sig[k] > v) || (sig[k] == v && k < i);
+        if (rank < n_keep) out[rank] = v * unscale;
+    }
+}
+
 }  // namespace
+
+// The prescale and the sweeps of `count` matrices: what pinv64_run and pinv64_values share.  Synchronises the stream once per sweep.
+static int p64_decompose(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA)
+{
+    const int m = std::max(rows, cols), n = std::min(rows, cols);
+    double2 *W = w.W, *V = w.V;
+    PvMeta *meta = w.meta;
+    int *any = w.any;
+    hipLaunchKernelGGL(p64_prep_kernel, dim3(count), dim3(1024), 0, st, rows, cols, A, sA, W, V, meta);
+    JSTSP_HIP(hipGetLastError());
+    const int ne = n + (n & 1), half = ne / 2, ring = ne - 1;
+    for (int sweep = 0; sweep < PV_SWEEPS && n > 1; ++sweep) {
+        for (int r = 0; r < ring; ++r) {
+            if (m <= PV_WAVE_ROWS) hipLaunchKernelGGL(p64_round_kernel<64>, dim3((half + 3) / 4, count), dim3(256), 0, st, m, n, r, W, V, meta);
+            else hipLaunchKernelGGL(p64_round_kernel<256>, dim3(half, count), dim3(256), 0, st, m, n, r, W, V, meta);
+        }
+        JSTSP_HIP(hipGetLastError());
+        JSTSP_HIP(hipMemsetAsync(any, 0, sizeof(int), st));
+        hipLaunchKernelGGL(p64_sweep_end_kernel, dim3((count + 255) / 256), dim3(256), 0, st, count, meta, any);
+        int h_any = 0;
+        JSTSP_HIP(hipMemcpyAsync(&h_any, any, sizeof(int), hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+        if (!h_any) break;
+    }
+    return 0;
+}
 
 // ---- what the float64 entry points that invert a factor share (pinv64.h) -------------------------------------------------------
 bool pinv64_shape_ok(int rows, int cols) { return std::min(rows, cols) <= PV_MAX_ORDER && std::max(rows, cols) <= PV_MAX_LONG; }
@@ -259,29 +316,24 @@ int pinv64_run(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int co
     const size_t mn = (size_t)m * n, nn = (size_t)n * n;
     double2 *W = w.W, *V = w.V, *Vs = w.Vs, *ws = w.ws;
     PvMeta *meta = w.meta;
-    int *any = w.any;
-    hipLaunchKernelGGL(p64_prep_kernel, dim3(count), dim3(1024), 0, st, rows, cols, A, sA, W, V, meta);
-    JSTSP_HIP(hipGetLastError());
-    const int ne = n + (n & 1), half = ne / 2, ring = ne - 1;
-    for (int sweep = 0; sweep < PV_SWEEPS && n > 1; ++sweep) {
-        for (int r = 0; r < ring; ++r) {
-            if (m <= PV_WAVE_ROWS) hipLaunchKernelGGL(p64_round_kernel<64>, dim3((half + 3) / 4, count), dim3(256), 0, st, m, n, r, W, V, meta);
-            else hipLaunchKernelGGL(p64_round_kernel<256>, dim3(half, count), dim3(256), 0, st, m, n, r, W, V, meta);
-        }
-        JSTSP_HIP(hipGetLastError());
-        JSTSP_HIP(hipMemsetAsync(any, 0, sizeof(int), st));
-        hipLaunchKernelGGL(p64_sweep_end_kernel, dim3((count + 255) / 256), dim3(256), 0, st, count, meta, any);
-        int h_any = 0;
-        JSTSP_HIP(hipMemcpyAsync(&h_any, any, sizeof(int), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-        if (!h_any) break;
-    }
+    JSTSP_TRY(p64_decompose(st, w, rows, cols, count, A, sA));
     hipLaunchKernelGGL(p64_sigma_kernel, dim3(count), dim3(256), 0, st, rows, cols, W, V, Vs, meta, rcond, rank);
     JSTSP_HIP(hipGetLastError());
     const long long smn = (long long)mn, snn = (long long)nn;
     if (rows >= cols) JSTSP_TRY(zgemm64(st, 'N', 'C', n, m, n, count, Mat64{Vs, snn, n}, Mat64{W, smn, m}, P, smn, n, ws));     // V f (W V)^H
     else JSTSP_TRY(zgemm64(st, 'N', 'C', m, n, n, count, Mat64{W, smn, m}, Mat64{Vs, snn, n}, P, smn, m, ws));               // its adjoint
     hipLaunchKernelGGL(p64_nan_kernel, dim3((unsigned)std::min<size_t>((mn + 255) / 256, 1024), count), dim3(256), 0, st, (long long)mn, P, smn, meta);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+// sv[k + n_keep t] = the k-th largest singular value of A[t], k < n_keep <= min(rows, cols) (device): the same prescale, rounds
+// and per-matrix stop as pinv64_run, then the sorted column norms.  V is rotated along and discarded (the round kernel is the
+// one jstsp_pinv_f64 runs, unchanged); w.Vs and w.ws are not used.  Synchronises the stream once per sweep.
+int pinv64_values(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA, int n_keep, double *sv)
+{
+    JSTSP_TRY(p64_decompose(st, w, rows, cols, count, A, sA));
+    hipLaunchKernelGGL(p64_values_kernel, dim3(count), dim3(256), 0, st, std::max(rows, cols), std::min(rows, cols), w.W, w.meta, n_keep, sv);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

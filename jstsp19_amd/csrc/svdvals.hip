@@ -17,7 +17,20 @@
 // sweeps.  The singular values are the final column norms, sorted; no singular vector is formed.  The operand is scaled by a
 // power of two to max |entry| in [1/2, 1) first (exact), so no squared norm overflows or underflows; a non-finite entry
 // gives NaN for that matrix.  Columns that have shrunk to eps |Y|_F / sqrt(n) are not rotated any further (jacobi_sweeps).
+//
+// Beyond the LDS limit (jstsp_spectrum_c32 / _c64 / jstsp_spectrum_trials_c32) - still no Gram:
+//   n <= 64, m <= 65536: tsqr_values_kernel.  One workgroup per matrix walks the oriented operand once (after the scale pre-pass), in chunks of 128 (n <= 48)
+//     or 64 rows, and reduces each stack [R; chunk] to a new n x n triangle R by Householder reflections in LDS (a reflector of
+//     column j touches row j of R and the chunk only, so R stays triangular); Householder, not Gram-Schmidt, because the operands
+//     of interest have rank 4..24 of 32..64 and a column in the span of the earlier ones must not be normalised.  The chunks are
+//     walked in order, so the result does not depend on the batch; the next chunk is fetched into registers while the current one
+//     is reduced.  R then goes to singular_values_block above, unchanged: sv(R) = sv(Y).  A pre-pass finds the largest component
+//     and the loader multiplies by the power of two that brings it into [1/2, 1) (the trial loader: by a power of two from the
+//     bound 2 L Nt max|H| max|pilot|, its entries being sums), undone at the end; both exact.
+//   64 < n <= 512, m <= 8192: the global-memory one-sided Jacobi of pinv64.hip without the inverse (pinv64_values), which
+//     synchronises the stream once per sweep.
 #include "inputgen.h"
+#include "pinv64.h"
 
 using namespace jstsp;
 
@@ -199,6 +212,224 @@ __global__ __launch_bounds__(64 * SV_WAVES) void rank_sweep_kernel(Model mdl, co
     singular_values_block(lds, m, n, n_keep, sv + (size_t)n_keep * t);
 }
 
+
+// ---- beyond the LDS limit, n <= 64: tall-skinny QR in front of the Jacobi -------------------------------------------------------
+constexpr int TQ_THREADS = 512;
+constexpr int TQ_NMAX = SV_NMAX;    // the triangle goes to singular_values_block
+constexpr int TQ_MMAX = 65536;
+constexpr int TQ_PRE = 12;          // chunk entries a thread fetches ahead: 128 * 48 / 512
+
+__host__ __device__ inline int tq_chunk(int n) { return n <= 48 ? 128 : 64; }             // rows per chunk: R and the chunk within 144 KiB
+inline size_t tq_lds_bytes(int n) { return ((size_t)n * n + (size_t)tq_chunk(n) * n) * sizeof(double2); }
+inline bool tq_fits(int rows, int cols) { return std::min(rows, cols) <= TQ_NMAX && std::max(rows, cols) <= TQ_MMAX; }
+
+// the largest of v over the workgroup and whether any thread saw a non-finite entry (red: 8 doubles of LDS)
+__device__ __forceinline__ bool block_max_or_bad(double &amax, int bad, double *red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+    if (__syncthreads_or(bad)) return true;
+    amax = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) amax = fmax(amax, red[i]);
+    return false;
+}
+
+// Loaders of tsqr_values_kernel: bind(t) selects matrix t; scan() is the pre-pass - true when an entry is not finite, else *ex is
+// the exponent whose power of two the entries are divided by; at(r, c, sc) is entry (r, c) of the rows x cols operand times sc.
+template <class T> struct MatrixLoader {
+    const T *Y;
+    int rows, cols;
+    __device__ void bind(int t) { Y += (size_t)rows * cols * t; }
+    __device__ bool scan(double *red, int *ex) const
+    {
+        double amax = 0.0;
+        int bad = 0;
+        for (int e = threadIdx.x; e < rows * cols; e += blockDim.x) {
+            const double2 v = ld2(Y[e]);
+            bad |= !isfinite(v.x) || !isfinite(v.y);
+            amax = fmax(amax, fmax(fabs(v.x), fabs(v.y)));
+        }
+        if (block_max_or_bad(amax, bad, red)) return true;
+        int e2 = 0;
+        if (amax > 0.0) frexp(amax, &e2);
+        *ex = max(-1000, min(1000, e2));
+        return false;
+    }
+    __device__ __forceinline__ double2 at(int r, int c, double sc) const
+    {
+        const double2 v = ld2(Y[r + (size_t)rows * c]);
+        return make_double2(v.x * sc, v.y * sc);
+    }
+};
+
+// the noise-free receive signal of a trial, entry by entry (received_entry, inputgen.h): each entry is formed once
+struct TrialLoader {
+    Model mdl;
+    const float2 *H, *sym;
+    float pscale;
+    int rows, cols;
+    __device__ void bind(int t) { H += (size_t)t * mdl.Nr * mdl.NtL; sym += (size_t)t * mdl.Nt * mdl.Tp; }
+    __device__ bool scan(double *red, int *ex) const
+    {
+        double hmax = 0.0, smax = 0.0;
+        int bad = 0;
+        for (int e = threadIdx.x; e < mdl.Nr * mdl.NtL; e += blockDim.x) {
+            const float2 v = H[e];
+            bad |= !isfinite(v.x) || !isfinite(v.y);
+            hmax = fmax(hmax, (double)fmaxf(fabsf(v.x), fabsf(v.y)));
+        }
+        for (int e = threadIdx.x; e < mdl.Nt * mdl.Tp; e += blockDim.x) {
+            const float2 v = sym[e];
+            bad |= !isfinite(v.x) || !isfinite(v.y);
+            smax = fmax(smax, (double)fmaxf(fabsf(v.x * pscale), fabsf(v.y * pscale)));
+        }
+        if (block_max_or_bad(hmax, bad, red)) return true;
+        __syncthreads();                                           // every wave has read the maxima of H
+        if (block_max_or_bad(smax, 0, red)) return true;
+        const double bound = 2.0 * (double)mdl.NtL * hmax * smax;  // |re|, |im| of an entry: a sum of 2 L Nt products
+        int e2 = 0;
+        if (bound > 0.0) frexp(bound, &e2);
+        *ex = e2;
+        return false;
+    }
+    __device__ __forceinline__ double2 at(int r, int c, double sc) const
+    {
+        const double2 v = received_entry(mdl, H, sym, pscale, r, c);
+        return make_double2(v.x * sc, v.y * sc);
+    }
+};
+
+// [R; chunk] -> R: column j's reflector P = I - u u^H / (|x| (|x| + |alpha|)), x = (alpha; y) with alpha = R(j, j) and y the chunk's
+// column j, u = x - beta e_1, beta = -(alpha / |alpha|) |x| (no cancellation in u_1), applied to the columns k > j, one wave
+// per column.  Every wave forms the reflector itself from the same numbers in the same order, so none waits for another; one
+// barrier per column.  R: n x n, ld n; Ck: the chunk, cc rows, ld C.  A column whose chunk part is zero is left as it is.
+__device__ void tq_reduce(double2 *R, double2 *Ck, int n, int C, int cc)
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    for (int j = 0; j < n; ++j) {
+        const double2 *y = Ck + (size_t)C * j;
+        double s2 = 0.0;
+        for (int i = lane; i < cc; i += 64) s2 += y[i].x * y[i].x + y[i].y * y[i].y;
+        s2 = wave_sum(s2);
+        if (!(s2 > 0.0)) continue;                                 // (the same bits in every wave)
+        const double2 alpha = R[j + (size_t)n * j];
+        const double aa = hypot(alpha.x, alpha.y), nx = sqrt(aa * aa + s2);
+        const double px = aa > 0.0 ? alpha.x / aa : 1.0, py = aa > 0.0 ? alpha.y / aa : 0.0;
+        const double u0x = px * (aa + nx), u0y = py * (aa + nx), inv = 1.0 / (nx * (nx + aa));
+        for (int k = j + 1 + w; k < n; k += nw) {
+            double2 *a = Ck + (size_t)C * k;
+            double dr = 0.0, di = 0.0;
+            for (int i = lane; i < cc; i += 64) {
+                const double2 yy = y[i], v = a[i];
+                dr += yy.x * v.x + yy.y * v.y;                     // conj(y) a
+                di += yy.x * v.y - yy.y * v.x;
+            }
+            dr = wave_sum(dr); di = wave_sum(di);
+            const double2 rjk = R[j + (size_t)n * k];
+            dr += u0x * rjk.x + u0y * rjk.y;                       // conj(u_1) R(j, k)
+            di += u0x * rjk.y - u0y * rjk.x;
+            const double fr = dr * inv, fi = di * inv;
+            if (lane == 0) R[j + (size_t)n * k] = make_double2(rjk.x - (u0x * fr - u0y * fi), rjk.y - (u0x * fi + u0y * fr));
+            for (int i = lane; i < cc; i += 64) {
+                const double2 yy = y[i], v = a[i];
+                a[i] = make_double2(v.x - (yy.x * fr - yy.y * fi), v.y - (yy.x * fi + yy.y * fr));
+            }
+        }
+        __syncthreads();
+        if (tid == 0) R[j + (size_t)n * j] = make_double2(-px * nx, -py * nx);
+    }
+}
+
+template <class L> __global__ __launch_bounds__(TQ_THREADS) void tsqr_values_kernel(L ld, int n_keep, double *sv)
+{
+    extern __shared__ double2 lds[];
+    const int t = blockIdx.x, tid = threadIdx.x;
+    ld.bind(t);
+    const bool tall = ld.rows >= ld.cols;
+    const int m = tall ? ld.rows : ld.cols, n = tall ? ld.cols : ld.rows, C = tq_chunk(n);
+    double2 *R = lds, *Ck = lds + (size_t)n * n;
+    double *scr = reinterpret_cast<double *>(Ck);
+    double *out = sv + (size_t)n_keep * t;
+    int ex = 0;
+    if (ld.scan(scr, &ex)) {
+        for (int i = tid; i < n_keep; i += TQ_THREADS) out[i] = __builtin_nan("");
+        return;
+    }
+    const double sc = ldexp(1.0, -ex);
+    for (int e = tid; e < n * n; e += TQ_THREADS) R[e] = make_double2(0.0, 0.0);
+    // chunk entry e of rows [i0, i0 + cc): consecutive threads on consecutive addresses of the operand - down a column of a tall
+    // one, along the contiguous rows x cc block of a wide one (whose adjoint is what is reduced)
+    double2 pre[TQ_PRE];
+    auto fetch = [&](int i0) {
+        const int cc = min(C, m - i0);
+#pragma unroll
+        for (int q = 0; q < TQ_PRE; ++q) {
+            const int e = tid + q * TQ_THREADS;
+            if (e < cc * n) {
+                if (tall) pre[q] = ld.at(i0 + e % cc, e / cc, sc);
+                else {
+                    const double2 v = ld.at(e % n, i0 + e / n, sc);
+                    pre[q] = make_double2(v.x, -v.y);
+                }
+            }
+        }
+    };
+    fetch(0);
+    for (int i0 = 0; i0 < m; i0 += C) {
+        const int cc = min(C, m - i0);
+        __syncthreads();                                           // the chunk before this one is reduced (first: the scan's scratch is read)
+#pragma unroll
+        for (int q = 0; q < TQ_PRE; ++q) {
+            const int e = tid + q * TQ_THREADS;
+            if (e < cc * n) Ck[tall ? e % cc + C * (e / cc) : e / n + C * (e % n)] = pre[q];
+        }
+        __syncthreads();
+        if (i0 + C < m) fetch(i0 + C);
+        tq_reduce(R, Ck, n, C, cc);
+    }
+    // nrm and red of singular_values_block lie behind R, in the chunk's place; the values go through LDS to be scaled back
+    double *vals = scr + n + SV_RED;
+    singular_values_block(R, n, n, n_keep, vals);
+    __syncthreads();
+    const double back = ldexp(1.0, ex);
+    for (int i = tid; i < n_keep; i += TQ_THREADS) out[i] = vals[i] * back;
+}
+
+template <class L> int tsqr_launch(hipStream_t st, const L &ld, int n, int batch, int n_keep, double *sv)
+{
+    const size_t sh = tq_lds_bytes(n) < 1024 ? 1024 : tq_lds_bytes(n);
+    JSTSP_HIP(hipFuncSetAttribute((const void *)tsqr_values_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+    tsqr_values_kernel<L><<<batch, TQ_THREADS, sh, st>>>(ld, n_keep, sv);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- 64 < n <= 512: the operand as complex double for pinv64_values ---------------------------------------------------------------
+__global__ __launch_bounds__(256) void widen_kernel(long long cnt, const float2 *src, double2 *dst)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (long long)gridDim.x * 256) dst[e] = ld2(src[e]);
+}
+
+__global__ __launch_bounds__(256) void received_kernel(Model mdl, const float2 *Hmat, const float2 *psym, float pscale, double2 *Y)
+{
+    const int t = blockIdx.y;
+    const float2 *H = Hmat + (size_t)t * mdl.Nr * mdl.NtL, *sym = psym + (size_t)t * mdl.Nt * mdl.Tp;
+    const long long cnt = (long long)mdl.Nr * mdl.Tp;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (long long)gridDim.x * 256)
+        Y[(size_t)t * cnt + e] = received_entry(mdl, H, sym, pscale, (int)(e % mdl.Nr), (int)(e / mdl.Nr));
+}
+
+// sv[k + n_keep t] = full[k + n t], k < n_keep
+__global__ __launch_bounds__(256) void leading_kernel(int n, int n_keep, long long cnt, const double *full, double *sv)
+{
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < cnt) sv[e] = full[e % n_keep + (long long)n * (e / n_keep)];
+}
+
+inline bool spectrum_shape_ok(int rows, int cols) { return sv_fits(rows, cols) || tq_fits(rows, cols) || pinv64_shape_ok(rows, cols); }
+#define SPECTRUM_LIMITS "min(rows, cols) <= 512, max(rows, cols) <= 65536, and max(rows, cols) <= 8192 when min(rows, cols) > 64"
+
 template <class T>
 int singular_values_impl(jstsp_ctx *ctx, int rows, int cols, int batch, const T *Y, double *sv, int memspace, const char *what)
 {
@@ -226,6 +457,89 @@ int singular_values_impl(jstsp_ctx *ctx, int rows, int cols, int batch, const T 
     if (memspace == JSTSP_HOST) {
         JSTSP_TRY(stage_out(ctx, sv, o, nS, memspace));
         JSTSP_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
+
+
+template <class T>
+int spectrum_impl(jstsp_ctx *ctx, int rows, int cols, int batch, const T *Y, int n_keep, double *sv, int memspace, const char *what)
+{
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: NULL context", what);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace", what);
+    JSTSP_REQUIRE(Y && sv, JSTSP_E_NULL, "%s: NULL argument", what);
+    JSTSP_REQUIRE(rows > 0 && cols > 0 && batch > 0, JSTSP_E_SHAPE, "%s: bad shape", what);
+    const int m = std::max(rows, cols), n = std::min(rows, cols);
+    JSTSP_REQUIRE(n_keep >= 1 && n_keep <= n, JSTSP_E_SHAPE, "%s: need 1 <= n_keep <= min(rows, cols)", what);
+    JSTSP_REQUIRE(spectrum_shape_ok(rows, cols), JSTSP_E_UNSUPPORTED, "%s: %d x %d: need " SPECTRUM_LIMITS, what, rows, cols);
+    const bool host = memspace == JSTSP_HOST;
+    const size_t nY = (size_t)rows * cols * batch, nS = (size_t)n_keep * batch;
+    if (sv_fits(rows, cols)) {                                     // the LDS kernel and its bits
+        if (n_keep == n) return singular_values_impl(ctx, rows, cols, batch, Y, sv, memspace, what);
+        JSTSP_ENTER(ctx);
+        hipStream_t st = ctx->stream;
+        const T *y;
+        double *full, *o;
+        Slab s(st);
+        JSTSP_TRY(ws64_open(s, what, batch, [&](Slab &w, int b) {
+            y = w.in(Y, (size_t)rows * cols * b, host);
+            full = w.get<double>((size_t)n * b);
+            o = w.out(sv, (size_t)n_keep * b, host);
+        }));
+        const size_t sh = sv_lds_bytes(m, n);
+        JSTSP_HIP(hipFuncSetAttribute((const void *)svdvals_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        svdvals_kernel<T><<<batch, sv_threads(n), sh, st>>>(rows, cols, y, full);
+        leading_kernel<<<(unsigned)((nS + 255) / 256), 256, 0, st>>>(n, n_keep, (long long)nS, full, o);
+        JSTSP_HIP(hipGetLastError());
+        if (host) {
+            JSTSP_TRY(s.copy_back(sv, o, nS));
+            JSTSP_HIP(hipStreamSynchronize(st));
+        }
+        return 0;
+    }
+    JSTSP_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    Slab s(st);
+    if (tq_fits(rows, cols)) {
+        const T *y;
+        double *o;
+        JSTSP_TRY(ws64_open(s, what, batch, [&](Slab &w, int b) {
+            y = w.in(Y, (size_t)rows * cols * b, host);
+            o = w.out(sv, (size_t)n_keep * b, host);
+        }));
+        JSTSP_TRY(tsqr_launch(st, MatrixLoader<T>{y, rows, cols}, n, batch, n_keep, o));
+        if (host) {
+            JSTSP_TRY(s.copy_back(sv, o, nS));
+            JSTSP_HIP(hipStreamSynchronize(st));
+        }
+        return 0;
+    }
+    JSTSP_REQUIRE(batch <= 65535, JSTSP_E_UNSUPPORTED, "%s: %d x %d, batch %d: orders above 64 need batch <= 65535", what, rows, cols, batch);
+    constexpr bool narrow = sizeof(T) == sizeof(float2);
+    const T *y;
+    double2 *y64 = nullptr;
+    double *o;
+    Pinv64Arrays pv{};
+    JSTSP_TRY(ws64_open(s, what, batch, [&](Slab &w, int b) {
+        y = w.in(Y, (size_t)rows * cols * b, host);
+        if (narrow) y64 = w.get<double2>((size_t)rows * cols * b);
+        o = w.out(sv, (size_t)n_keep * b, host);
+        pv.W = w.get<double2>((size_t)m * n * b); pv.V = w.get<double2>((size_t)n * n * b);
+        pv.meta = w.get<PvMeta>(b);
+        pv.any = w.get<int>(1);
+    }));
+    const double2 *a;
+    if constexpr (narrow) {
+        widen_kernel<<<grid_for((long long)nY), 256, 0, st>>>((long long)nY, y, y64);
+        JSTSP_HIP(hipGetLastError());
+        a = y64;
+    } else {
+        a = y;
+    }
+    JSTSP_TRY(pinv64_values(st, pv, rows, cols, batch, a, (long long)rows * cols, n_keep, o));
+    if (host) {
+        JSTSP_TRY(s.copy_back(sv, o, nS));
+        JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;
 }
@@ -277,6 +591,106 @@ int jstsp_rank_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, 
     if (memspace == JSTSP_HOST) {
         JSTSP_TRY(stage_out(ctx, sv, o, nS, memspace));
         JSTSP_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return 0;
+}
+
+int jstsp_spectrum_c32(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c32 *Y, int n_keep, double *sv, int memspace)
+{
+    return spectrum_impl(ctx, rows, cols, batch, reinterpret_cast<const float2 *>(Y), n_keep, sv, memspace, "spectrum_c32");
+}
+
+int jstsp_spectrum_c64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *Y, int n_keep, double *sv, int memspace)
+{
+    return spectrum_impl(ctx, rows, cols, batch, reinterpret_cast<const double2 *>(Y), n_keep, sv, memspace, "spectrum_c64");
+}
+
+int jstsp_spectrum_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx, long long trial0, int batch,
+                              const jstsp_c32 *Hsrc, int ld_rows, int ld_cols, long long strideH, int normalize, int n_keep, double *sv,
+                              double *sigma_max, int memspace)
+{
+    const char *what = "spectrum_trials";
+    if (!Hsrc && ctx && mp && sv && (memspace == JSTSP_HOST || memspace == JSTSP_DEVICE) && mp->T_prop > 0 && mp->Nr > 0 &&
+        sv_fits(mp->Nr, mp->T_prop))
+        return jstsp_rank_trials_c32(ctx, mp, seed, sweep_idx, trial0, batch, n_keep, sv, memspace);   // the LDS kernel and its bits
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: NULL context", what);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace", what);
+    JSTSP_REQUIRE(mp && sv, JSTSP_E_NULL, "%s: NULL argument", what);
+    JSTSP_ENTER(ctx);
+    const bool given = Hsrc != nullptr;
+    Model m{};
+    m.Nt = mp->Nt; m.Nr = mp->Nr; m.L = mp->L; m.Tp = mp->T_prop; m.clusters = mp->clusters; m.rays = mp->rays;
+    if (given) m.clusters = m.rays = 1;             // (ignored: nothing is drawn for the channel)
+    JSTSP_REQUIRE(m.Nt > 0 && m.Nr > 0 && m.L > 0 && m.Tp > 0 && m.clusters > 0 && m.rays > 0 && batch > 0 && trial0 >= 0 &&
+                      sweep_idx >= 0,
+                  JSTSP_E_SHAPE, "%s: bad model dimensions", what);
+    JSTSP_REQUIRE(m.L <= m.Tp, JSTSP_E_SHAPE, "%s: L > T_prop", what);
+    JSTSP_REQUIRE(mp->pilots == JSTSP_PILOTS_QAM4 || mp->pilots == JSTSP_PILOTS_GAUSS, JSTSP_E_ARG, "%s: bad pilots kind", what);
+    const int rows = m.Nr, cols = m.Tp, n = std::min(rows, cols), mm = std::max(rows, cols);
+    JSTSP_REQUIRE(n_keep >= 1 && n_keep <= n, JSTSP_E_SHAPE, "%s: need 1 <= n_keep <= min(Nr, T_prop)", what);
+    m.Np = m.clusters * m.rays; m.NtL = m.Nt * m.L;
+    JSTSP_REQUIRE(spectrum_shape_ok(rows, cols), JSTSP_E_UNSUPPORTED, "%s: Nr x T_prop = %d x %d: need " SPECTRUM_LIMITS, what, rows, cols);
+    JSTSP_REQUIRE(given || channel_lds_bytes(m) <= 150 * 1024, JSTSP_E_UNSUPPORTED, "%s: steering tables exceed the LDS", what);
+    const bool lds = sv_fits(rows, cols), qr = !lds && tq_fits(rows, cols);
+    JSTSP_REQUIRE(lds || qr || batch <= 65535, JSTSP_E_UNSUPPORTED, "%s: orders above 64 need batch <= 65535", what);
+    const bool host = memspace == JSTSP_HOST;
+    const size_t b = (size_t)batch, nS = (size_t)n_keep * b, nQ = (size_t)m.Nt * m.Tp, nR = (size_t)rows * cols;
+    // ---- workspace: the float64 family's limit, with the largest batch that fits -------------------------------------------------
+    auto bytes = [&](size_t bb) {
+        size_t need = operands_bytes(m, bb) + rnd256((size_t)n_keep * bb * 8) + 4096;
+        if (!lds && !qr) need += rnd256(bb * nR * 16) + rnd256(bb * mm * n * 16) + rnd256(bb * n * n * 16) + rnd256(bb * sizeof(PvMeta)) + 256;
+        return need;
+    };
+    if (bytes(b) > WS64_LIMIT) {
+        int fit = batch;
+        while (fit > 1 && bytes((size_t)fit) > WS64_LIMIT) fit = fit > 64 ? fit - fit / 16 : fit - 1;
+        set_error("%s: the workspace would be %.1f GiB (limit 24); the largest batch that fits is about %d", what,
+                  (double)bytes(b) / (double)((size_t)1 << 30), fit);
+        return JSTSP_E_UNSUPPORTED;
+    }
+    // ---- channel and pilots ------------------------------------------------------------------------------------------------------
+    hipStream_t st = ctx->stream;
+    Operands op;
+    if (given) {
+        const GivenChannel g{reinterpret_cast<const float2 *>(Hsrc), ld_rows, ld_cols, strideH, normalize, sigma_max};
+        float2 *Hmat = nullptr;
+        JSTSP_TRY(given_channel_hmat(ctx, m.Nr, m.Nt, m.L, trial0, batch, g, memspace, bytes(b), nullptr, &Hmat));
+        float2 *psym = ctx->arena.get<float2>(b * nQ);
+        uint8_t *qam = ctx->arena.get<uint8_t>(b * nQ);
+        JSTSP_REQUIRE(psym && qam, JSTSP_E_NOMEM, "%s: workspace exhausted", what);
+        const int gauss = mp->pilots == JSTSP_PILOTS_GAUSS;
+        draw_noise_qam_kernel<<<dim3(grid_for((long long)nQ, 1024), batch), 256, 0, st>>>(m, seed, (uint64_t)sweep_idx, trial0, nullptr, qam,
+                                                                                          mp->shared_pilots, gauss, psym);
+        JSTSP_HIP(hipGetLastError());
+        op = Operands{Hmat, psym, gauss ? 0.70710678f : 1.f};
+    } else {
+        JSTSP_TRY(ctx->arena.reserve(bytes(b)));
+        ctx->arena.reset();
+        JSTSP_TRY(draw_operands(ctx, m, mp, seed, (uint64_t)sweep_idx, trial0, batch, &op));
+    }
+    double *o = host ? ctx->arena.get<double>(nS) : sv;
+    JSTSP_REQUIRE(o, JSTSP_E_NOMEM, "%s: workspace exhausted", what);
+    if (lds) {
+        const size_t sh = sv_lds_bytes(mm, n);
+        JSTSP_HIP(hipFuncSetAttribute((const void *)rank_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        rank_sweep_kernel<<<batch, sv_threads(n), sh, st>>>(m, op.Hmat, op.psym, op.pscale, n_keep, o);
+        JSTSP_HIP(hipGetLastError());
+    } else if (qr) {
+        JSTSP_TRY(tsqr_launch(st, TrialLoader{m, op.Hmat, op.psym, op.pscale, rows, cols}, n, batch, n_keep, o));
+    } else {
+        Pinv64Arrays pv{};
+        double2 *Y = ctx->arena.get<double2>(b * nR);
+        pv.W = ctx->arena.get<double2>(b * mm * n); pv.V = ctx->arena.get<double2>(b * n * n);
+        pv.meta = ctx->arena.get<PvMeta>(b);
+        pv.any = ctx->arena.get<int>(1);
+        JSTSP_REQUIRE(Y && pv.W && pv.V && pv.meta && pv.any, JSTSP_E_NOMEM, "%s: workspace exhausted", what);
+        received_kernel<<<dim3(grid_for((long long)nR, 64), batch), 256, 0, st>>>(m, op.Hmat, op.psym, op.pscale, Y);
+        JSTSP_HIP(hipGetLastError());
+        JSTSP_TRY(pinv64_values(st, pv, rows, cols, batch, Y, (long long)nR, n_keep, o));
+    }
+    if (host) {
+        JSTSP_TRY(stage_out(ctx, sv, o, nS, memspace));
+        JSTSP_HIP(hipStreamSynchronize(st));
     }
     return 0;
 }

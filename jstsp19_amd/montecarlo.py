@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import torch
 
-from .system_model import SweepParams, TrainingParams, ase_trials, build_trials, build_trials_training, rank_trials
+from .system_model import SweepParams, TrainingParams, ase_trials, build_trials, build_trials_training, rank_trials, spectrum_trials
 
 __all__ = ["partition", "run_sweep", "run_points", "sweep_points", "run_approx_sweep", "driver", "run_driver",
            "admmiters_points", "run_convergence_curves", "zy_points", "run_zy", "capacity_points", "capacity_designs",
@@ -782,7 +782,8 @@ def rank_points(panel):
     return [SweepParams(Nt=4, Nr=Nr, L=L, T=50, Mr=4, Mr_e=32, clusters=clusters, rays=rays, T_prop=50) for L in (1, 4, 8)]
 
 
-def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, sweep0=0, device=None, dist=None):
+def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, sweep0=0, device=None, dist=None, channel=None,
+             channel_normalize="reference"):
     """plot_rankR.m:24-50 on the HIP path: per point the mean over ``n_trials`` realisations of the first ``n_keep``
     singular values (default ``min(Nr, Mr_e, T_prop)`` of the first point) of the noise-free receive signal (point i is
     sweep index ``sweep0 + i``), sharded over the ranks of ``dist`` with one all-reduce of the sums.
@@ -790,17 +791,29 @@ def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, swee
     The reference plots ONE realisation per curve: its ``mean(eig_dist, 3)`` (:52) acts on a 2-D array and does nothing.  So
     ``n_trials`` defaults to 1; larger values give the averaged curve, which the script's author presumably meant.
 
+    Any shape ``spectrum_trials`` takes (at the figure's shapes: the kernel and the bits of ``rank_trials``).  ``channel``,
+    ``channel_normalize``: a supplied channel instead of the drawn one, as ``run_points(..., channel=H)`` takes it - shared
+    ``(Nr_src, Nt_src, L)`` or one per trial ``(n_trials, Nr_src, Nt_src, L)``, every point with that L; the marker is then
+    ``L*Nt``, the only bound known without the channel's own rank.
+
     Returns float64 numpy ``(spectrum, marker)``: (len(points), n_keep) mean singular values, and per point the rank bound
     ``min(Np, L*Nt)`` whose successor index the script marks with a vertical line (:61-62)."""
     import numpy as np
+    if channel is not None:                     # refused here, before anything touches a device
+        from .system_model import _check_channel
+        per_trial = len(getattr(channel, "shape", ())) == 4
+        for p in points:
+            _check_channel(p, n_trials if per_trial else 1, channel, channel_normalize)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     if n_keep is None:
         n_keep = min(points[0].Nr, points[0].Mr_e, points[0].T_prop)
 
     def build(p, trials, seed_, pt, device_, _):
-        return rank_trials(p, trials.start, len(trials), seed=seed_, sweep_idx=sweep0 + pt, n_keep=n_keep, device=device_)
+        ch = channel if channel is None or len(channel.shape) == 3 else channel[trials.start:trials.stop]
+        return spectrum_trials(p, trials.start, len(trials), seed=seed_, sweep_idx=sweep0 + pt, n_keep=n_keep, device=device_,
+                               channel=ch, channel_normalize=channel_normalize)
 
     mean = _generic_sharded(points, n_trials, n_keep, lambda sv, p: sv, batch=batch, seed=seed, device=device, dist=dist,
                             builder=build).numpy()
-    return mean, np.array([min(p.clusters * p.rays, p.L * p.Nt) for p in points])
+    return mean, np.array([min(p.clusters * p.rays, p.L * p.Nt) if channel is None else p.L * p.Nt for p in points])

@@ -28,7 +28,7 @@ from ._lib import DEVICE, HOST, JstspError, check
 
 __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "mc_admm", "OMP", "omp_kron",
            "sparse_admm", "vamp", "vamp_kron", "cosamp", "cosamp_kron", "sparse_sca_estim", "cawgn_estim_out", "ls_estimate", "pinv", "mmv_omp", "tssr", "rate", "correlate", "synthesize", "gradient_head", "nmse_spectral", "colmajor",
-           "empty_colmajor", "beamformer", "ase", "singular_values",
+           "empty_colmajor", "beamformer", "ase", "singular_values", "spectrum",
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64"]
@@ -775,6 +775,40 @@ def singular_values(Y, *, ctx=None):
     fn, name = (c._lib.jstsp_singular_values_c64, "jstsp_singular_values_c64") if f64 else \
         (c._lib.jstsp_singular_values_c32, "jstsp_singular_values_c32")
     check(fn(c.handle, a_Y.R, a_Y.C, a_Y.batch, a_Y.ptr, optr, mem), name)
+    return out if a_Y.batched else out[0]
+
+
+def spectrum(Y, n_keep=None, *, ctx=None):
+    """The leading ``n_keep`` (default: all ``min(rows, cols)``) singular values of ``Y`` at every driver size
+    (``jstsp_spectrum_c32`` / ``_c64``, csrc/svdvals.hip): the arguments and the result of :func:`singular_values`, without its
+    shape limit.  Shapes that function accepts return its bits; ``min(rows, cols) <= 64`` with ``max(rows, cols) <= 65536`` goes
+    through a float64 Householder tall-skinny QR in front of the same Jacobi; orders 65..512 with ``max(rows, cols) <= 8192``
+    through the global-memory one-sided Jacobi of :func:`pinv_f64`.  No Gram matrix on any route.  Anything larger raises
+    ``JstspError`` (code -3).  A batch whose workspace would exceed the library's 24 GiB limit is computed in chunks."""
+    f64 = _is_c128(Y)
+    a_Y = _Arg(Y, np.complex128 if f64 else np.complex64, "Y")
+    c, mem, dev = _ctx_for([a_Y], ctx)
+    m, n = max(a_Y.R, a_Y.C), min(a_Y.R, a_Y.C)
+    keep = n if n_keep is None else int(n_keep)
+    if not 1 <= keep <= n:
+        raise ValueError("n_keep must lie in 1..min(rows, cols) = %d, got %d" % (n, keep))
+    batch = a_Y.batch
+    if mem == DEVICE:
+        import torch
+        out = torch.empty((batch, keep), dtype=torch.float64, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty((batch, keep), dtype=np.float64)
+        optr = out.ctypes.data
+    fn, name = (c._lib.jstsp_spectrum_c64, "jstsp_spectrum_c64") if f64 else (c._lib.jstsp_spectrum_c32, "jstsp_spectrum_c32")
+    esz = 16 if f64 else 8
+    # bytes of workspace per matrix (csrc/svdvals.hip): the staged copy of a host operand; above order 64 the float64 operand,
+    # its rotated copy and V
+    per = (a_Y.R * a_Y.C * esz if mem == HOST else 0) + 8 * (keep + n)
+    if n > 64:
+        per += 16 * (m * n + n * n) + (0 if f64 else 16 * m * n)
+    for t0, nb in _f64_chunks(batch, per):
+        check(fn(c.handle, a_Y.R, a_Y.C, nb, _off(a_Y.ptr, t0 * a_Y.R * a_Y.C, esz), keep, _off(optr, t0 * keep, 8), mem), name)
     return out if a_Y.batched else out[0]
 
 

@@ -21,7 +21,7 @@ import math
 
 import torch
 
-__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training", "ase_trials", "rank_trials"]
+__all__ = ["SweepParams", "TrainingParams", "build_trials", "build_trials_training", "ase_trials", "rank_trials", "spectrum_trials"]
 
 
 class SweepParams:
@@ -304,3 +304,47 @@ def rank_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, n_
                                       int(n_keep), out.data_ptr(), _lib.DEVICE)
     _lib.check(rc, "jstsp_rank_trials_c32")
     return out
+
+
+def spectrum_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, n_keep=None, channel=None,
+                    channel_normalize="reference", device=None, ctx=None, shared_pilots=False, pilots="qam4", want_sigma=False):
+    """:func:`rank_trials` at every driver size and on any channel (``jstsp_spectrum_trials_c32``, csrc/svdvals.hip): the first
+    ``n_keep`` singular values of the noise-free ``Y`` (Nr x ``p.T_prop``) of trials [trial0, trial0 + batch), for
+    ``min(Nr, T_prop) <= 64`` with ``max(Nr, T_prop) <= 65536`` (float64 Householder tall-skinny QR in front of the Jacobi) or
+    ``min <= 512`` with ``max <= 8192`` (the global-memory Jacobi); on the shapes ``rank_trials`` accepts, its bits.
+
+    ``channel``, ``channel_normalize``: as in :func:`build_trials` - trial t then has the channel and pilots
+    ``build_trials(p, ..., channel=channel)`` returns for t, and ``p.clusters`` / ``p.rays`` are not used.  ``want_sigma`` (with a
+    channel) returns ``(sv, sigma_max)``, the float64 norm(H_l) per tap as ``build_trials`` reports it.
+    Returns float64 (batch, n_keep) on the device, descending per trial."""
+    import ctypes as C
+    import numpy as np
+    from . import _lib
+    if channel is not None:
+        per_trial, nr_src, nt_src = _check_channel(p, batch, channel, channel_normalize)
+    elif want_sigma:
+        raise ValueError("want_sigma needs a supplied channel")
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    c = ctx if ctx is not None else _lib.default_context(device.index or 0)
+    c.use_torch_stream()
+    if n_keep is None:
+        n_keep = min(p.Nr, p.Mr_e, p.T_prop)
+    model = _lib.Model(p.Nt, p.Nr, p.L, p.T_prop, p.Mr, p.Mr_e, p.Gr, p.Gt, p.clusters, p.rays, 0, 1 if shared_pilots else 0,
+                       p.noise_var, _lib.BF_ZC, _lib.RHO_MIN6, 1.0,
+                       _lib.PILOTS_GAUSS if pilots == "gauss" else _lib.PILOTS_QAM4)
+    out = torch.empty((batch, int(n_keep)), dtype=torch.float64, device=device)
+    src, sig, ld, stride, mode = None, None, (0, 0), 0, 0
+    if channel is not None:
+        src = _channel_on_device(channel, device)
+        mode = _CHANNEL_NORMALIZE[channel_normalize]
+        ld, stride = (nr_src, nt_src), nr_src * nt_src * p.L if per_trial else 0
+        if want_sigma:
+            sig = np.empty((batch, p.L) if per_trial else (p.L,), dtype=np.float64)
+    rc = c._lib.jstsp_spectrum_trials_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0), int(batch),
+                                          src.data_ptr() if src is not None else None, ld[0], ld[1], stride, mode, int(n_keep),
+                                          out.data_ptr(), sig.ctypes.data_as(C.POINTER(C.c_double)) if sig is not None else None,
+                                          _lib.DEVICE)
+    _lib.check(rc, "jstsp_spectrum_trials_c32")
+    return (out, torch.from_numpy(sig)) if want_sigma else out
