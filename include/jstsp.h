@@ -621,7 +621,7 @@ int jstsp_ase_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, const jstsp_a
  * (sv[k + min(rows, cols)*t]).  Y: rows x cols x batch, column-major.  Computed by a one-sided (Hestenes) Jacobi iteration in
  * float64 on the columns of Y itself (of Y^H when rows < cols), one workgroup per matrix with the matrix in LDS - NOT through
  * a Gram matrix, which squares the condition number and returns a zero singular value near sqrt(eps) sigma_1: the values that
- * decide a numerical rank are accurate to eps sigma_1 here.  No singular vectors.  The operand is scaled by a power of two
+ * decide a numerical rank are accurate to eps sigma_1 here.  No singular vectors (jstsp_svd_f64 returns them).  The operand is scaled by a power of two
  * first, so any finite input is safe; the sweeps stop when one rotates nothing (|c_p^H c_q| <= sqrt(m) eps |c_p| |c_q| for
  * every pair; columns that have fallen to eps |Y|_F / sqrt(n) are zero singular values and are left alone) or after 30.  Shapes: min(rows, cols) <= 64 and rows * cols <= 8192 (128 KiB of complex double), else
  * JSTSP_E_UNSUPPORTED - there is no fall-back.  An Inf or NaN entry gives NaN for all values of its own matrix only.  The _c64
@@ -841,6 +841,55 @@ int jstsp_pinv_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c6
 int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *Y,
                  const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB,
                  jstsp_c64 *S_out, double *rcond_out, int memspace);
+
+/* ---- [U,S,V] = svd(A,'econ') and the best rank-R approximation in float64 (csrc/svd64.hip) -----------------
+ * jstsp_svd_f64: the leading n_keep <= n = min(rows, cols) singular triplets of each matrix of A (rows x cols x batch,
+ * column-major), A_t = U diag(sv) V^H when n_keep = n (plot_rankR.m:49, vamp.m:32).  One-sided (Hestenes) Jacobi in float64 on the
+ * columns of A itself (of A^H when rows < cols) with the rotations accumulated - no Gram matrix.
+ *  - outputs, all in the call's memspace and column-major: U rows x n_keep x batch, sv n_keep x batch descending (sv[k + n_keep*t]),
+ *    V cols x n_keep x batch - V, not V^H, as MATLAB returns it.  U, V, rank_out (int32[batch]) and conv_out (int32[batch]) may
+ *    each be NULL = not wanted; sv may not.  Equal singular values keep column order.
+ *  - rank_out[t]: the number of singular values the drop rule of jstsp_pinv_f64 keeps, sigma_k > max(rows, cols) * eps(sigma_max)
+ *    (one implementation).  The short-side factor - V when rows >= cols, else U - is the accumulated rotations and always a
+ *    full set of orthonormal columns.  The long-side factor is column / norm and has ZERO columns for k >= rank: one-sided Jacobi
+ *    leaves those columns at rounding level and does not orthogonalise them, so there is nothing to normalise.  sv still carries
+ *    the computed values for those k.
+ *  - conv_out[t]: 1 when a sweep rotated nothing, 0 when the sweep cap (30 on the first route, 40 on the second) ended the iteration
+ *    - the value-only entries above stop silently at the cap; a caller who uses vectors needs to know.
+ *  - two routes, chosen by the shape alone.  n <= 64 and (m + n) n complex doubles (m = max(rows, cols)) plus scratch within
+ *    160 KiB of LDS - 64 x 64, 32 x 140, 128 x 50: one workgroup per matrix, ONE launch, no host read; the kernel of
+ *    jstsp_singular_values_* with V carried under each column and the factors written in its epilogue; sv has that entry's bits on
+ *    the shapes it takes.  Everything else up to 512 x 8192: the global-memory Jacobi of jstsp_pinv_f64, unchanged, and a kernel
+ *    that sorts and writes the factors; like that entry it waits for the context's stream once per sweep (also with JSTSP_DEVICE) and
+ *    takes batch <= 65535; sv has the bits of jstsp_spectrum_c64 for n > 64.
+ *  - conventions of jstsp_spectrum_c64 and jstsp_pinv_f64: the operand is scaled by a power of two on load and the values scaled
+ *    back, both exact, so svd(A 2^k) returns U, V on the bits and sv 2^k on the bits; a NaN or Inf entry gives NaN in U, sv, V,
+ *    rank 0 and conv 0 for its own matrix only; the zero matrix gives sv = 0, rank 0, a zero long-side factor and the identity's
+ *    leading columns in the short-side factor; no atomics, every sum in a fixed order: a repeated call returns the same bits, and
+ *    a matrix's result depends neither on the batch around it nor on the memspace.
+ *  - errors: JSTSP_E_SHAPE for a non-positive size; JSTSP_E_ARG for n_keep outside 1..n; JSTSP_E_NULL when A or sv is NULL;
+ *    JSTSP_E_UNSUPPORTED for n > 512, max(rows, cols) > 8192, batch > 65535 on the second route, or a workspace above 24 GiB (the
+ *    message names the largest batch that fits).
+ *  - not done: a long side above 8192 (the QR route of jstsp_spectrum_* keeps no Q, and U Sigma = A V loses the orthogonality of
+ *    the columns of small sigma); a _c32 form (the Python wrapper widens its input); jstsp_pinv_f64 and jstsp_svt_f64 keep their
+ *    own kernels and bits; no environment switch selects a route.
+ * jstsp_lowrank_f64: X_t = sum_{k < min(R, rank_t)} sigma_k u_k v_k^H, rows x cols x batch, the best rank-R approximation in the
+ * spectral and Frobenius norms, formed as (U_R Sigma_R) V_R^H on the f64 matrix pipe from the factors of the same decomposition.
+ * 1 <= R <= n (JSTSP_E_ARG otherwise).  tail_out: NULL or double[batch], sigma_{R+1} (0 when R >= n) = ||A - X||_2 (Eckart-Young).
+ * Limits, non-finite handling (X and tail NaN for that matrix only) and batch independence as above.
+ * Asserted (tests/test_gpu_svd64.py) with s1 = sigma_1 of numpy.linalg.svd, on 64x64, 32x140, 140x32, 128x50, 7x13, 13x7, 33x3, 5x5,
+ * 1x7, 7x1 (first route) and 96x300, 200x97, 66x520, 520x66, 40x600 (second), random, rank 6, sigma graded over 12 decades and
+ * repeated sigma: max_k |sv_k - ref_k| / s1 <= 9e-14 (first route) / 3.6e-13 (second); ||A - U diag(sv) V^H||_2 / s1,
+ * max |Q^H Q - I| over the kept columns of the long-side factor and over all columns of the short-side factor each within 4 x the
+ * worst value of a numpy restatement of the algorithm over the same problem set (tests/svd64_problems.py,
+ * tests/test_svd64_problems.py; measured values: DESIGN.md section 9k, profiles/svd64_measured_tolerances.json); rank_out equal
+ * to the drop rule on numpy's values; conv_out 1 throughout; the rank-6 projector within Wedin's bound; the low-rank residual
+ * against tail_out and numpy; V diag(1/sv) U^H against jstsp_pinv_f64; isolation, memspace, repeat and power-of-two invariance on
+ * the bits. */
+int jstsp_svd_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A, int n_keep,
+                  jstsp_c64 *U, double *sv, jstsp_c64 *V, int32_t *rank_out, int32_t *conv_out, int memspace);
+int jstsp_lowrank_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A, int R,
+                      jstsp_c64 *X, double *tail_out, int memspace);
 
 /* ---- proposed_algorithm 'std' (Alg. 1) in float64 -----------------------------------------------------
  * The 'std' branch of proposed_algorithm.m / proposed_algorithm_angles.m (:29, :53; angles :29, :64) evaluated in FLOAT64 on the

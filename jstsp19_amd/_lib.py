@@ -132,6 +132,10 @@ SIGNATURES["jstsp_pinv_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p,
 SIGNATURES["jstsp_ls_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
                                       c_void_p, c_void_p, c_int])
 
+# [U,S,V] = svd(A,'econ') and the best rank-R approximation in float64 (csrc/svd64.hip)
+SIGNATURES["jstsp_svd_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int])
+SIGNATURES["jstsp_lowrank_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int])
+
 # Alg. 1 ('std') in float64 (csrc/proposed64.hip): the jstsp_proposed_algorithm_f64 list with PA, PB for `type` and rcond_out
 SIGNATURES["jstsp_proposed_std_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
                                                 c_void_p, c_ll, c_void_p, c_void_p, c_int, c_dp, c_dp, c_dp, c_void_p, c_void_p,

@@ -14,7 +14,7 @@
 // a matrix end when one of them met no pair with |g| > sqrt(m) eps sqrt(a b) (its own flag: a matrix's result does not depend
 // on the batch around it); whether any matrix of the call is still rotating is read on the host once per sweep, so a call
 // synchronises the context's stream.  Drop rule (pinv.m): sigma_k is kept iff sigma_k > max(rows, cols) * eps(sigma_max),
-// eps(x) = 2^(floor(log2 x) - 52) - one place, p64_sigma_kernel.  No atomics anywhere: a repeated call returns the same bits.
+// eps(x) = 2^(floor(log2 x) - 52) - one place, pinv64_drop_tol (pinv64.h).  No atomics anywhere: a repeated call returns the same bits.
 #include "pinv64.h"
 
 #include <algorithm>
@@ -198,8 +198,7 @@ __global__ __launch_bounds__(256) void p64_sigma_kernel(int rows, int cols, cons
         double smax2 = 0.0;
         for (int k = 0; k < n; ++k) smax2 = fmax(smax2, sig2[k]);
         const double smax = sqrt(smax2);
-        // pinv.m: tol = max(size(A)) * eps(norm(A));  eps(x) = 2^(floor(log2 x) - 52)
-        const double tol = smax > 0.0 ? (double)m * ldexp(1.0, ilogb(smax) - 52) : 0.0;
+        const double tol = pinv64_drop_tol(m, smax);              // pinv.m: tol = max(size(A)) * eps(norm(A))
         double smin = smax;
         int kept = 0;
         for (int k = 0; k < n; ++k) {
@@ -270,6 +269,77 @@ __global__ __launch_bounds__(256) void p64_values_kernel(int m, int n, const dou
     }
 }
 
+// One workgroup per matrix, after the sweeps: the leading n_keep singular triplets (pinv64_svd, pinv64.h).  The norms are those of
+// p64_values_kernel, summed the same way; column j of W V goes to place[j] in descending order of the norms.
+__global__ __launch_bounds__(256) void p64_vectors_kernel(int rows, int cols, const double2 *W, const double2 *V, const PvMeta *meta, int n_keep,
+                                                          double2 *U, double *sv, double2 *Vout, int32_t *rank, int32_t *conv)
+{
+    __shared__ double sig[PV_MAX_ORDER];
+    __shared__ int place[PV_MAX_ORDER];
+    __shared__ double stol;
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const bool tall = rows >= cols;
+    const int m = tall ? rows : cols, n = tall ? cols : rows;
+    const PvMeta mt = meta[t];
+    double *out = sv + (long long)n_keep * t;
+    double2 *Lt = tall ? U : Vout, *St = tall ? Vout : U;         // long side: m x n_keep; short side: n x n_keep
+    if (Lt) Lt += (long long)t * m * n_keep;
+    if (St) St += (long long)t * n * n_keep;
+    if (mt.bad) {
+        const double q = __builtin_nan("");
+        for (int k = tid; k < n_keep; k += 256) out[k] = q;
+        if (Lt) for (long long e = tid; e < (long long)m * n_keep; e += 256) Lt[e] = make_double2(q, q);
+        if (St) for (long long e = tid; e < (long long)n * n_keep; e += 256) St[e] = make_double2(q, q);
+        if (tid == 0) {
+            if (rank) rank[t] = 0;
+            if (conv) conv[t] = 0;
+        }
+        return;
+    }
+    const double2 *Wt = W + (long long)t * m * n, *Vt = V + (long long)t * n * n;
+    for (int k = w; k < n; k += 4) {
+        const double2 *c = Wt + (long long)k * m;
+        double a = 0.0;
+        for (int i = lane; i < m; i += 64) a += c[i].x * c[i].x + c[i].y * c[i].y;
+        a = wave_sum(a);
+        if (lane == 0) sig[k] = sqrt(a);
+    }
+    __syncthreads();
+    const double unscale = 1.0 / mt.sc;                           // (a power of two: exact)
+    for (int i = tid; i < n; i += 256) {
+        const double v = sig[i];
+        int pl = 0;
+        for (int k = 0; k < n; ++k) pl += (sig[k] > v) || (sig[k] == v && k < i);
+        place[i] = pl;
+        if (pl < n_keep) out[pl] = v * unscale;
+    }
+    if (tid == 0) {
+        double smax = 0.0;
+        for (int k = 0; k < n; ++k) smax = fmax(smax, sig[k]);
+        const double tol = pinv64_drop_tol(m, smax);
+        int kept = 0;
+        for (int k = 0; k < n; ++k) kept += sig[k] > tol;
+        stol = tol;
+        if (rank) rank[t] = kept;
+        if (conv) conv[t] = (mt.done || n == 1) ? 1 : 0;          // (a single column has no pair and no sweep)
+    }
+    __syncthreads();
+    const double tol = stol;
+    if (Lt)
+        for (long long e = tid; e < (long long)m * n; e += 256) {
+            const int j = (int)(e / m), i = (int)(e % m), pl = place[j];
+            if (pl >= n_keep) continue;
+            const double s = sig[j];
+            const double2 x = Wt[e];
+            Lt[i + (long long)m * pl] = s > tol ? make_double2(x.x / s, x.y / s) : make_double2(0.0, 0.0);
+        }
+    if (St)
+        for (int e = tid; e < n * n; e += 256) {
+            const int j = e / n, i = e % n, pl = place[j];
+            if (pl < n_keep) St[i + (long long)n * pl] = Vt[e];
+        }
+}
+
 }  // namespace
 
 // The prescale and the sweeps of `count` matrices: what pinv64_run and pinv64_values share.  Synchronises the stream once per sweep.
@@ -334,6 +404,17 @@ int pinv64_values(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int
 {
     JSTSP_TRY(p64_decompose(st, w, rows, cols, count, A, sA));
     hipLaunchKernelGGL(p64_values_kernel, dim3(count), dim3(256), 0, st, std::max(rows, cols), std::min(rows, cols), w.W, w.meta, n_keep, sv);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+// The leading singular triplets (pinv64.h).  V is the rotated identity of p64_decompose; w.Vs and w.ws are not used.
+// Synchronises the stream once per sweep.
+int pinv64_svd(hipStream_t st, const Pinv64Arrays &w, int rows, int cols, int count, const double2 *A, long long sA, int n_keep, double2 *U,
+               double *sv, double2 *Vout, int32_t *rank, int32_t *conv)
+{
+    JSTSP_TRY(p64_decompose(st, w, rows, cols, count, A, sA));
+    hipLaunchKernelGGL(p64_vectors_kernel, dim3(count), dim3(256), 0, st, rows, cols, w.W, w.V, w.meta, n_keep, U, sv, Vout, rank, conv);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

@@ -31,7 +31,8 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "empty_colmajor", "beamformer", "ase", "singular_values", "spectrum",
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
-           "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64"]
+           "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
+           "svd_f64", "lowrank_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1023,6 +1024,83 @@ def pinv_f64(A, *, info=False, ctx=None):
     if not info:
         return P
     return (P, rc, rk) if a_A.batched else (P, rc[0], rk[0])
+
+
+def _svd_arg(A, keep, what):
+    """The operand of svd_f64 / lowrank_f64 as a complex128 argument, and ``keep`` checked against min(rows, cols) - before any
+    device call."""
+    if getattr(A, "ndim", None) is None:
+        A = np.asarray(A)
+    if A.ndim not in (2, 3):
+        raise ValueError("A must be 2-D or 3-D (batch first), got shape %s" % (tuple(A.shape),))
+    if _is_torch(A) and not A.is_cuda:
+        raise ValueError("A: torch tensors must live on the GPU (numpy arrays use the host path)")
+    n = int(min(A.shape[-2:]))
+    keep = n if keep is None else int(keep)
+    if not 1 <= keep <= n:
+        raise ValueError("%s must lie in 1..min(rows, cols) = %d, got %d" % (what, n, keep))
+    return _Arg(_wide(A), np.complex128, "A"), keep
+
+
+def _svd_per_matrix(a_A, keep, mem):
+    """bytes of workspace per matrix (csrc/svd64.hip): the staged copies of a host call; beyond the LDS limit the rotated operand, V
+    and the meta record"""
+    m, n = max(a_A.R, a_A.C), min(a_A.R, a_A.C)
+    per = 16 * (a_A.R * a_A.C + (a_A.R + a_A.C) * keep) + 8 * keep + 8 if mem == HOST else 0
+    if n > 64 or (m + n) * n * 16 + (n + 16) * 8 + n * 4 > 159 * 1024:
+        per += 16 * (m * n + n * n) + 32
+    return per + 1024
+
+
+def svd_f64(A, n_keep=None, *, info=False, ctx=None):
+    """``[U,S,V] = svd(A,'econ')`` in float64 on the device (include/jstsp.h: jstsp_svd_f64): returns ``(U, s, V)`` with
+    ``A = U @ diag(s) @ V^H`` - ``V``, not ``V^H``, as MATLAB does - or their leading ``n_keep`` columns / values.  ``A``:
+    (rows, cols) or (batch, rows, cols), numpy or a column-major torch CUDA tensor; complex64 / real inputs are widened exactly;
+    ``U`` (.., rows, n_keep) and ``V`` (.., cols, n_keep) complex128, ``s`` (.., n_keep) float64 descending, where ``A`` lives.
+    One-sided Jacobi on the matrix itself, no Gram matrix: one launch with the matrix in LDS for min(rows, cols) <= 64 and
+    shapes such as 64 x 64, 32 x 140, 128 x 50; the global-memory route of :func:`pinv_f64` up to 512 x 8192; anything larger
+    raises ``JstspError`` (code -3).  ``info=True`` also returns ``rank`` (int32, the singular values ``pinv``'s drop rule
+    keeps; the long-side factor has zero columns from there on) and ``converged`` (int32, 0 where the sweep cap ended the
+    iteration), one entry per matrix.  A non-finite entry gives NaN for its own matrix.  A batch whose workspace would exceed
+    the library's 24 GiB limit is computed in chunks."""
+    a_A, keep = _svd_arg(A, n_keep, "n_keep")
+    c, mem, dev = _ctx_for([a_A], ctx)
+    batch, R, Cc = a_A.batch, a_A.R, a_A.C
+    pU, fU = _out(mem == DEVICE, batch, R, keep, np.complex128, dev)
+    pV, fV = _out(mem == DEVICE, batch, Cc, keep, np.complex128, dev)
+    ps, fs = _out(mem == DEVICE, batch, keep, 1, np.float64, dev)
+    prk, rk = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
+    pcv, cv = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
+    for t0, nb in _f64_chunks(batch, _svd_per_matrix(a_A, keep, mem)):
+        check(c._lib.jstsp_svd_f64(c.handle, R, Cc, nb, _off(a_A.ptr, t0 * R * Cc, 16), keep, _off(pU, t0 * R * keep, 16),
+                                   _off(ps, t0 * keep, 8), _off(pV, t0 * Cc * keep, 16), _off(prk, t0, 4), _off(pcv, t0, 4), mem),
+              "jstsp_svd_f64")
+    sq = not a_A.batched
+    sv = fs(False)[:, :, 0]
+    out = (fU(sq), sv[0] if sq else sv, fV(sq))
+    if not info:
+        return out
+    return out + ((rk, cv) if a_A.batched else (rk[0], cv[0]))
+
+
+def lowrank_f64(A, R, *, info=False, ctx=None):
+    """The best rank-``R`` approximation of ``A`` in the spectral and Frobenius norms, ``sum_{k < R} s_k u_k v_k^H`` of
+    :func:`svd_f64`'s factors (jstsp_lowrank_f64), complex128, where ``A`` lives; arguments, limits and chunking as
+    :func:`svd_f64`, ``1 <= R <= min(rows, cols)``.  ``info=True`` also returns ``tail``: float64, ``s_{R+1}`` per matrix (0 for
+    ``R = min(rows, cols)``), which is ``||A - X||_2``."""
+    a_A, rr = _svd_arg(A, R, "R")
+    c, mem, dev = _ctx_for([a_A], ctx)
+    batch, Rw, Cc = a_A.batch, a_A.R, a_A.C
+    pX, fX = _out(mem == DEVICE, batch, Rw, Cc, np.complex128, dev)
+    ptl, tl = _vec_out(mem == DEVICE, batch, np.float64, dev) if info else (None, None)
+    per = _svd_per_matrix(a_A, min(rr + 1, min(Rw, Cc)), HOST) + (16 * Rw * Cc if mem == HOST else 0) + 32 * Rw * Cc
+    for t0, nb in _f64_chunks(batch, per):
+        check(c._lib.jstsp_lowrank_f64(c.handle, Rw, Cc, nb, _off(a_A.ptr, t0 * Rw * Cc, 16), rr, _off(pX, t0 * Rw * Cc, 16),
+                                       _off(ptl, t0, 8), mem), "jstsp_lowrank_f64")
+    X = fX(not a_A.batched)
+    if not info:
+        return X
+    return (X, tl) if a_A.batched else (X, tl[0])
 
 
 def ls_estimate_f64(Y, A, B, *, info=False, ctx=None):
