@@ -870,8 +870,8 @@ int jstsp_ls_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
  *  - errors: JSTSP_E_SHAPE for a non-positive size; JSTSP_E_ARG for n_keep outside 1..n; JSTSP_E_NULL when A or sv is NULL;
  *    JSTSP_E_UNSUPPORTED for n > 512, max(rows, cols) > 8192, batch > 65535 on the second route, or a workspace above 24 GiB (the
  *    message names the largest batch that fits).
- *  - not done: a long side above 8192 (the QR route of jstsp_spectrum_* keeps no Q, and U Sigma = A V loses the orthogonality of
- *    the columns of small sigma); a _c32 form (the Python wrapper widens its input); jstsp_pinv_f64 and jstsp_svt_f64 keep their
+ *  - not done here: a long side above 8192 (jstsp_svd_tall_f64 below takes n <= 64 up to 65536 by a QR route that keeps its
+ *    reflectors; U Sigma = A V would lose the orthogonality of the columns of small sigma); a _c32 form (the Python wrapper widens its input); jstsp_pinv_f64 and jstsp_svt_f64 keep their
  *    own kernels and bits; no environment switch selects a route.
  * jstsp_lowrank_f64: X_t = sum_{k < min(R, rank_t)} sigma_k u_k v_k^H, rows x cols x batch, the best rank-R approximation in the
  * spectral and Frobenius norms, formed as (U_R Sigma_R) V_R^H on the f64 matrix pipe from the factors of the same decomposition.
@@ -890,6 +890,45 @@ int jstsp_svd_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64
                   jstsp_c64 *U, double *sv, jstsp_c64 *V, int32_t *rank_out, int32_t *conv_out, int memspace);
 int jstsp_lowrank_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A, int R,
                       jstsp_c64 *X, double *tail_out, int memspace);
+
+/* ---- the same for a long side up to 65536: the QR route with the reflectors kept (csrc/svd64.hip) ---------------
+ * jstsp_svd_tall_f64 / jstsp_lowrank_tall_f64: arguments, layouts, NULL-able outputs, both memspaces, the error codes and every
+ * convention of jstsp_svd_f64 / jstsp_lowrank_f64 (V, not V^H; sv descending, equal values keep column order; the zero matrix; NaN
+ * for the matrix with a non-finite entry only; no atomics, fixed summation order, a result independent of the batch and of the
+ * memspace; svd(A 2^k) = U, V on the bits and sv 2^k on the bits), for n = min(rows, cols) <= 64 and m = max(rows, cols) <= 65536 in
+ * either orientation (A^H is reduced when rows < cols and the factors swap on the way out).  JSTSP_E_UNSUPPORTED for anything
+ * else, for a workspace above 24 GiB (the message names the largest batch that fits) and, jstsp_lowrank_tall_f64 only, for
+ * batch > 65535.
+ *  - ALWAYS the QR route, whatever the shape - small shapes are legal: (1) forward, one workgroup per matrix: the chunked Householder
+ *    reduction [R; chunk] -> R of jstsp_spectrum_* (same chunk rule - 128 rows for n <= 48, else 64 -, same power-of-two prescale on
+ *    load, the same code) with the reflectors kept: the tails stay where the operand's rows were, in a workspace of the operand's
+ *    size, beside the head and the factor 1 / (|x| (|x| + |alpha|)) of every (chunk, column); then, in the same launch, the in-LDS
+ *    Jacobi of jstsp_svd_f64's first route on the n x n triangle, R = U_R diag(sv) V^H.  (2) backward, one workgroup per matrix:
+ *    the reflectors applied to [U_R(:, :n_keep); 0], last chunk first, one wave per output column; the rows below the top block
+ *    are the long-side factor.  (3) what the back-application leaves in the top block E - zero in exact arithmetic, of size
+ *    eps sigma_1 / sigma_k in column k in floating point - is exactly what the rows below lack, L^H L = I - E^H E; the long-side
+ *    factor is multiplied by I + E^H E / 2, which makes it orthonormal to rounding level also for sigma_k < 1e-8 sigma_1.
+ *    The correction couples the kept columns: the long-side columns of a call with a smaller n_keep agree with the leading ones of
+ *    n_keep = n to rounding level, not on the bits (sv, the short-side factor, rank_out and conv_out do, on the bits).
+ *    The short-side factor is V of the Jacobi, unchanged; sv its values scaled back.  Three launches (one when the long-side
+ *    factor is not asked for), nothing read on the host: a JSTSP_DEVICE call does not wait for the stream.
+ *  - rank_out and the zero columns of the long-side factor follow the drop rule with the long side of A:
+ *    sigma_k > max(rows, cols) * eps(sigma_max).
+ *  - sv has the bits of jstsp_spectrum_c64 wherever that entry reduces the same way (rows * cols > 8192): the same reduction and
+ *    the same rotations.
+ *  - workspace per matrix beside operand and outputs: 16 m n + 24 n ceil(m / chunk) + 16 (n n_keep + n_keep^2) bytes.
+ * Asserted (tests/test_gpu_svd64_tall.py) against numpy.linalg.svd on 5x3, 3x5, 1x7, 7x1, 128x48, 130x48, 129x49, 64x64, 200x64,
+ * 64x200, 8193x2, 2x8193, 9000x33 (random, rank 6, sigma graded over 12 decades, repeated sigma) and one 64x65536 matrix:
+ * max_k |sv_k - ref_k| / s1 <= 1.1e-13; sv within 2.2e-13 s1 of jstsp_spectrum_c64; ||A - U diag(sv) V^H||_2 / s1 and
+ * max |Q^H Q - I| of both factors each within 4 x the worst value of the numpy restatement of the route
+ * (tests/svd64_tall_problems.py, tests/golden/svd64_tall_restatement_worst.json; measured values: DESIGN.md section 9k,
+ * profiles/svd64_tall_measured_tolerances.json); rank_out equal to the drop rule on numpy's values; conv_out 1; the low-rank
+ * residual against tail_out and numpy; U diag(sv) V^H against jstsp_svd_f64's; isolation, memspace, repeat and power-of-two
+ * invariance on the bits. */
+int jstsp_svd_tall_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A, int n_keep,
+                       jstsp_c64 *U, double *sv, jstsp_c64 *V, int32_t *rank_out, int32_t *conv_out, int memspace);
+int jstsp_lowrank_tall_f64(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c64 *A, int R,
+                           jstsp_c64 *X, double *tail_out, int memspace);
 
 /* ---- proposed_algorithm 'std' (Alg. 1) in float64 -----------------------------------------------------
  * The 'std' branch of proposed_algorithm.m / proposed_algorithm_angles.m (:29, :53; angles :29, :64) evaluated in FLOAT64 on the

@@ -135,6 +135,9 @@ SIGNATURES["jstsp_ls_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_in
 # [U,S,V] = svd(A,'econ') and the best rank-R approximation in float64 (csrc/svd64.hip)
 SIGNATURES["jstsp_svd_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int])
 SIGNATURES["jstsp_lowrank_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int])
+# the same for min(rows, cols) <= 64 and a long side up to 65536: the QR route with the reflectors kept
+SIGNATURES["jstsp_svd_tall_f64"] = SIGNATURES["jstsp_svd_f64"]
+SIGNATURES["jstsp_lowrank_tall_f64"] = SIGNATURES["jstsp_lowrank_f64"]
 
 # Alg. 1 ('std') in float64 (csrc/proposed64.hip): the jstsp_proposed_algorithm_f64 list with PA, PB for `type` and rcond_out
 SIGNATURES["jstsp_proposed_std_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,

@@ -32,7 +32,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
-           "svd_f64", "lowrank_f64"]
+           "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1052,6 +1052,46 @@ def _svd_per_matrix(a_A, keep, mem):
     return per + 1024
 
 
+def _svd_call(entry, per_matrix, A, n_keep, info, ctx):
+    """svd_f64 / svd_tall_f64: the outputs where ``A`` lives, the batch in chunks under the 24 GiB limit"""
+    a_A, keep = _svd_arg(A, n_keep, "n_keep")
+    c, mem, dev = _ctx_for([a_A], ctx)
+    batch, R, Cc = a_A.batch, a_A.R, a_A.C
+    pU, fU = _out(mem == DEVICE, batch, R, keep, np.complex128, dev)
+    pV, fV = _out(mem == DEVICE, batch, Cc, keep, np.complex128, dev)
+    ps, fs = _out(mem == DEVICE, batch, keep, 1, np.float64, dev)
+    prk, rk = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
+    pcv, cv = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
+    fn = getattr(c._lib, entry)
+    for t0, nb in _f64_chunks(batch, per_matrix(a_A, keep, mem)):
+        check(fn(c.handle, R, Cc, nb, _off(a_A.ptr, t0 * R * Cc, 16), keep, _off(pU, t0 * R * keep, 16),
+                 _off(ps, t0 * keep, 8), _off(pV, t0 * Cc * keep, 16), _off(prk, t0, 4), _off(pcv, t0, 4), mem),
+              entry)
+    sq = not a_A.batched
+    sv = fs(False)[:, :, 0]
+    out = (fU(sq), sv[0] if sq else sv, fV(sq))
+    if not info:
+        return out
+    return out + ((rk, cv) if a_A.batched else (rk[0], cv[0]))
+
+
+def _lowrank_call(entry, per_matrix, A, R, info, ctx):
+    """lowrank_f64 / lowrank_tall_f64"""
+    a_A, rr = _svd_arg(A, R, "R")
+    c, mem, dev = _ctx_for([a_A], ctx)
+    batch, Rw, Cc = a_A.batch, a_A.R, a_A.C
+    pX, fX = _out(mem == DEVICE, batch, Rw, Cc, np.complex128, dev)
+    ptl, tl = _vec_out(mem == DEVICE, batch, np.float64, dev) if info else (None, None)
+    per = per_matrix(a_A, min(rr + 1, min(Rw, Cc)), HOST) + (16 * Rw * Cc if mem == HOST else 0) + 32 * Rw * Cc
+    fn = getattr(c._lib, entry)
+    for t0, nb in _f64_chunks(batch, per):
+        check(fn(c.handle, Rw, Cc, nb, _off(a_A.ptr, t0 * Rw * Cc, 16), rr, _off(pX, t0 * Rw * Cc, 16), _off(ptl, t0, 8), mem), entry)
+    X = fX(not a_A.batched)
+    if not info:
+        return X
+    return (X, tl) if a_A.batched else (X, tl[0])
+
+
 def svd_f64(A, n_keep=None, *, info=False, ctx=None):
     """``[U,S,V] = svd(A,'econ')`` in float64 on the device (include/jstsp.h: jstsp_svd_f64): returns ``(U, s, V)`` with
     ``A = U @ diag(s) @ V^H`` - ``V``, not ``V^H``, as MATLAB does - or their leading ``n_keep`` columns / values.  ``A``:
@@ -1063,24 +1103,7 @@ def svd_f64(A, n_keep=None, *, info=False, ctx=None):
     keeps; the long-side factor has zero columns from there on) and ``converged`` (int32, 0 where the sweep cap ended the
     iteration), one entry per matrix.  A non-finite entry gives NaN for its own matrix.  A batch whose workspace would exceed
     the library's 24 GiB limit is computed in chunks."""
-    a_A, keep = _svd_arg(A, n_keep, "n_keep")
-    c, mem, dev = _ctx_for([a_A], ctx)
-    batch, R, Cc = a_A.batch, a_A.R, a_A.C
-    pU, fU = _out(mem == DEVICE, batch, R, keep, np.complex128, dev)
-    pV, fV = _out(mem == DEVICE, batch, Cc, keep, np.complex128, dev)
-    ps, fs = _out(mem == DEVICE, batch, keep, 1, np.float64, dev)
-    prk, rk = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
-    pcv, cv = _vec_out(mem == DEVICE, batch, np.int32, dev) if info else (None, None)
-    for t0, nb in _f64_chunks(batch, _svd_per_matrix(a_A, keep, mem)):
-        check(c._lib.jstsp_svd_f64(c.handle, R, Cc, nb, _off(a_A.ptr, t0 * R * Cc, 16), keep, _off(pU, t0 * R * keep, 16),
-                                   _off(ps, t0 * keep, 8), _off(pV, t0 * Cc * keep, 16), _off(prk, t0, 4), _off(pcv, t0, 4), mem),
-              "jstsp_svd_f64")
-    sq = not a_A.batched
-    sv = fs(False)[:, :, 0]
-    out = (fU(sq), sv[0] if sq else sv, fV(sq))
-    if not info:
-        return out
-    return out + ((rk, cv) if a_A.batched else (rk[0], cv[0]))
+    return _svd_call("jstsp_svd_f64", _svd_per_matrix, A, n_keep, info, ctx)
 
 
 def lowrank_f64(A, R, *, info=False, ctx=None):
@@ -1088,19 +1111,32 @@ def lowrank_f64(A, R, *, info=False, ctx=None):
     :func:`svd_f64`'s factors (jstsp_lowrank_f64), complex128, where ``A`` lives; arguments, limits and chunking as
     :func:`svd_f64`, ``1 <= R <= min(rows, cols)``.  ``info=True`` also returns ``tail``: float64, ``s_{R+1}`` per matrix (0 for
     ``R = min(rows, cols)``), which is ``||A - X||_2``."""
-    a_A, rr = _svd_arg(A, R, "R")
-    c, mem, dev = _ctx_for([a_A], ctx)
-    batch, Rw, Cc = a_A.batch, a_A.R, a_A.C
-    pX, fX = _out(mem == DEVICE, batch, Rw, Cc, np.complex128, dev)
-    ptl, tl = _vec_out(mem == DEVICE, batch, np.float64, dev) if info else (None, None)
-    per = _svd_per_matrix(a_A, min(rr + 1, min(Rw, Cc)), HOST) + (16 * Rw * Cc if mem == HOST else 0) + 32 * Rw * Cc
-    for t0, nb in _f64_chunks(batch, per):
-        check(c._lib.jstsp_lowrank_f64(c.handle, Rw, Cc, nb, _off(a_A.ptr, t0 * Rw * Cc, 16), rr, _off(pX, t0 * Rw * Cc, 16),
-                                       _off(ptl, t0, 8), mem), "jstsp_lowrank_f64")
-    X = fX(not a_A.batched)
-    if not info:
-        return X
-    return (X, tl) if a_A.batched else (X, tl[0])
+    return _lowrank_call("jstsp_lowrank_f64", _svd_per_matrix, A, R, info, ctx)
+
+
+def _svd_tall_per_matrix(a_A, keep, mem):
+    """bytes of workspace per matrix on the QR route (csrc/svd64.hip, tall_layout): the staged copies of a host call, the
+    reflector tails (the operand's size), three doubles per chunk and column, the top block, its correction and the flag"""
+    m, n = max(a_A.R, a_A.C), min(a_A.R, a_A.C)
+    chunk = 128 if n <= 48 else 64
+    per = 16 * (a_A.R * a_A.C + (a_A.R + a_A.C) * keep) + 8 * keep + 8 if mem == HOST else 0
+    return per + 16 * m * n + 24 * n * (-(-m // chunk)) + 16 * (n * keep + keep * keep) + 4 + 2048
+
+
+def svd_tall_f64(A, n_keep=None, *, info=False, ctx=None):
+    """:func:`svd_f64` for ``min(rows, cols) <= 64`` and a long side up to 65536 (include/jstsp.h: jstsp_svd_tall_f64): the
+    same arguments, results and conventions.  Always the QR route, whatever the shape: a streaming Householder reduction to the
+    n x n triangle with the reflectors kept, the one-sided Jacobi with vectors on the triangle, the reflectors applied back to
+    its left vectors, and a first-order correction that keeps the long-side factor orthonormal to rounding level.  ``rank``
+    follows ``pinv``'s drop rule with the long side of ``A``.  Anything larger raises ``JstspError`` (code -3); a batch whose
+    workspace (the operand's size again per matrix for the reflectors) would exceed 24 GiB is computed in chunks."""
+    return _svd_call("jstsp_svd_tall_f64", _svd_tall_per_matrix, A, n_keep, info, ctx)
+
+
+def lowrank_tall_f64(A, R, *, info=False, ctx=None):
+    """:func:`lowrank_f64` on the factors of :func:`svd_tall_f64` (jstsp_lowrank_tall_f64): ``min(rows, cols) <= 64``, a long
+    side up to 65536."""
+    return _lowrank_call("jstsp_lowrank_tall_f64", _svd_tall_per_matrix, A, R, info, ctx)
 
 
 def ls_estimate_f64(Y, A, B, *, info=False, ctx=None):

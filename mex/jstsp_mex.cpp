@@ -418,13 +418,15 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (rcode) fail("jstsp_pinv_f64", rcode);
         if (rc) plhs[1] = rc;
         if (rk) plhs[2] = rk;
-    } else if (!strcmp(fn, "svd_f64")) {
+    } else if (!strcmp(fn, "svd_f64") || !strcmp(fn, "svd_tall_f64")) {
         // [U, S, V, rank, converged] = svd_f64(A [, n_keep]): svd(A,'econ') in float64 (jstsp_svd_f64); pages = batch.  S: the n_keep x n_keep
-        // diagonal matrix per page; with at most one output the column of singular values (n_keep x 1 per page) and no vectors are formed
+        // diagonal matrix per page; with at most one output the column of singular values (n_keep x 1 per page) and no vectors are formed.
+        // svd_tall_f64: the same by the QR route, min(size) <= 64 and max(size) <= 65536 (jstsp_svd_tall_f64)
+        const bool qr = !strcmp(fn, "svd_tall_f64");
         check_nargs(fn, nrhs, 1, 2, nlhs, 5);
         const Dims d = dims_of(in[0]);
         const int n = d.r < d.c ? d.r : d.c, keep = nrhs - 1 >= 2 ? (int)mxGetScalar(in[1]) : n;
-        if (keep < 1 || keep > n) mexErrMsgIdAndTxt("jstsp:args", "svd_f64: n_keep must lie in 1..min(size(A,1), size(A,2))");
+        if (keep < 1 || keep > n) mexErrMsgIdAndTxt("jstsp:args", "%s: n_keep must lie in 1..min(size(A,1), size(A,2))", fn);
         const jstsp_c64 *A = cplx(in[0], fn, "A");
         ensure_ctx();
         const bool vectors = nlhs >= 2;
@@ -433,9 +435,11 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const mwSize dk[2] = {(mwSize)d.b, 1};
         mxArray *rk = nlhs >= 4 ? mxCreateNumericArray(2, dk, mxINT32_CLASS, mxREAL) : nullptr;
         mxArray *cv = nlhs >= 5 ? mxCreateNumericArray(2, dk, mxINT32_CLASS, mxREAL) : nullptr;
-        const int rc = jstsp_svd_f64(g_ctx, d.r, d.c, d.b, A, keep, U ? c64(U) : nullptr, mxGetDoubles(sv), V ? c64(V) : nullptr,
-                                     rk ? (int32_t *)mxGetData(rk) : nullptr, cv ? (int32_t *)mxGetData(cv) : nullptr, JSTSP_HOST);
-        if (rc) fail("jstsp_svd_f64", rc);
+        jstsp_c64 *pU = U ? c64(U) : nullptr, *pV = V ? c64(V) : nullptr;
+        int32_t *prk = rk ? (int32_t *)mxGetData(rk) : nullptr, *pcv = cv ? (int32_t *)mxGetData(cv) : nullptr;
+        const int rc = qr ? jstsp_svd_tall_f64(g_ctx, d.r, d.c, d.b, A, keep, pU, mxGetDoubles(sv), pV, prk, pcv, JSTSP_HOST)
+                          : jstsp_svd_f64(g_ctx, d.r, d.c, d.b, A, keep, pU, mxGetDoubles(sv), pV, prk, pcv, JSTSP_HOST);
+        if (rc) fail(qr ? "jstsp_svd_tall_f64" : "jstsp_svd_f64", rc);
         if (!vectors) {
             plhs[0] = sv;
         } else {
@@ -449,18 +453,21 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
             if (rk) plhs[3] = rk;
             if (cv) plhs[4] = cv;
         }
-    } else if (!strcmp(fn, "lowrank_f64")) {
-        // [X, tail] = lowrank_f64(A, R): the best rank-R approximation of every page in float64 (jstsp_lowrank_f64); tail: sigma_{R+1} per page
+    } else if (!strcmp(fn, "lowrank_f64") || !strcmp(fn, "lowrank_tall_f64")) {
+        // [X, tail] = lowrank_f64(A, R): the best rank-R approximation of every page in float64 (jstsp_lowrank_f64); tail: sigma_{R+1} per page.
+        // lowrank_tall_f64: the same by the QR route, min(size) <= 64 and max(size) <= 65536 (jstsp_lowrank_tall_f64)
+        const bool qr = !strcmp(fn, "lowrank_tall_f64");
         check_nargs(fn, nrhs, 2, 2, nlhs, 2);
         const Dims d = dims_of(in[0]);
         const int n = d.r < d.c ? d.r : d.c, R = (int)mxGetScalar(in[1]);
-        if (R < 1 || R > n) mexErrMsgIdAndTxt("jstsp:args", "lowrank_f64: R must lie in 1..min(size(A,1), size(A,2))");
+        if (R < 1 || R > n) mexErrMsgIdAndTxt("jstsp:args", "%s: R must lie in 1..min(size(A,1), size(A,2))", fn);
         const jstsp_c64 *A = cplx(in[0], fn, "A");
         ensure_ctx();
         plhs[0] = new_complex(d.r, d.c, d.b);
         mxArray *tl = nlhs >= 2 ? mxCreateDoubleMatrix(d.b, 1, mxREAL) : nullptr;
-        const int rc = jstsp_lowrank_f64(g_ctx, d.r, d.c, d.b, A, R, c64(plhs[0]), tl ? mxGetDoubles(tl) : nullptr, JSTSP_HOST);
-        if (rc) fail("jstsp_lowrank_f64", rc);
+        const int rc = qr ? jstsp_lowrank_tall_f64(g_ctx, d.r, d.c, d.b, A, R, c64(plhs[0]), tl ? mxGetDoubles(tl) : nullptr, JSTSP_HOST)
+                          : jstsp_lowrank_f64(g_ctx, d.r, d.c, d.b, A, R, c64(plhs[0]), tl ? mxGetDoubles(tl) : nullptr, JSTSP_HOST);
+        if (rc) fail(qr ? "jstsp_lowrank_tall_f64" : "jstsp_lowrank_f64", rc);
         if (tl) plhs[1] = tl;
     } else if (!strcmp(fn, "ls_f64")) {
         // [S_ls, rcond] = ls_f64(Y, A, B): pinv(A)*Y*pinv(B) in float64 (jstsp_ls_f64); rcond = [over the A factors; over the B factors]
