@@ -684,6 +684,31 @@ int jstsp_spectrum_trials_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t
                               const jstsp_c32 *Hsrc, int ld_rows, int ld_cols, long long strideH, int normalize,
                               int n_keep, double *sv, double *sigma_max, int memspace);
 
+/* ---- scoring a float64 estimate on the device (csrc/svdvals.hip) ------------------------------------------
+ * jstsp_nmse_spectral_f64: nmse[t] = min(1, e_t), e_t = (sigma_1(S_t - Zbar_t) / sigma_1(Zbar_t))^2 (plot_errorVSsnr.m:138-141; the
+ * quotient first, then the square).  jstsp_rate_f64: rate[t] = sum_k log2(1 + sigma_k(Zbar_t)^2 / (R (noise_var + e_t))) over all
+ * min(R, C) values of Zbar_t, = log2 det(I + Zbar Zbar^H / (R (noise_var + e))) of plot_rateVSframelength.m:81, with e NOT capped
+ * and R the row count of Zbar in either orientation.  S, Zbar: R x C x batch complex doubles, column-major; the result is
+ * double[batch] in the memspace of the operands.  Unlike jstsp_nmse_spectral_c64 / jstsp_rate_c64, which narrow to the fp32
+ * Gram/Lanczos kernels, nothing is narrowed and no Gram matrix is formed: the singular values come from the three routes of
+ * jstsp_spectrum_c64, at its shapes (else JSTSP_E_UNSUPPORTED, and batch <= 65535 on the third route).  D = S - Zbar is formed in
+ * float64 from the operands - as it is loaded on the first two routes, where the power-of-two scale is found from |D|'s own
+ * largest component and D never reaches memory; into the workspace on the third - so an error 1e-9 of Zbar keeps its digits.
+ *  - errors: JSTSP_E_NULL (ctx, S, Zbar, result), JSTSP_E_SHAPE (a non-positive size), JSTSP_E_ARG (bad memspace; noise_var < 0 or
+ *    NaN); a workspace above 24 GiB is JSTSP_E_UNSUPPORTED and the message names the largest batch that fits.
+ *  - a non-finite entry in S_t or Zbar_t gives NaN for trial t only; S == Zbar gives exactly 0.0 (and the rate of noise_var alone);
+ *    S = 3 Zbar gives e = 4 exactly (NMSE 1.0); Zbar == 0 gives what the quotient gives: NaN for S == 0 (0/0), else e = Inf, NMSE 1.
+ *  - no atomics, every sum in a fixed order: a trial's value depends neither on the batch around it, nor on the memspace, nor on a
+ *    repeated call; the NMSE of (2^k S, 2^k Zbar) has the bits of that of (S, Zbar).
+ * Asserted (tests/test_gpu_score64.py) against numpy.linalg.norm(., 2) and det in float64 on the same operand values, per trial
+ * |x - ref| / |ref|: NMSE <= 3.0e-14 / 7.8e-14 / 7.5e-14 on the three routes (measured 5.9e-15 / 1.5e-14 / 1.5e-14), rate <= 5.3e-14 /
+ * 9.3e-14 / 9.9e-14 (measured 1.0e-14 / 1.9e-14 / 2.0e-14; profiles/score64_measured_tolerances.json), all under the 1e-10 fixed
+ * beforehand, including S = Zbar (1 + 1e-9 eps), where the NMSE is 2e-18 and jstsp_nmse_spectral_c64 returns 1e-16 .. 4e-16. */
+int jstsp_nmse_spectral_f64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar,
+                            double *nmse, int memspace);
+int jstsp_rate_f64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar,
+                   double noise_var, double *rate, int memspace);
+
 /* ---- the reference's own element type at the boundary ------------------------------------------
  * Same functions, same argument meaning, arrays as MATLAB holds them: interleaved complex DOUBLE, and the 0/1 masks as
  * double (proposed_hbf.m:36-41 builds Omega with zeros()).  Inputs are narrowed and outputs widened on the device;

@@ -153,6 +153,10 @@ for _n in ("omp", "omp_kron", "sparse_admm"):
     # OMP (dense and Kronecker) and sparse_admm in float64 (csrc/omp64.hip, csrc/sparse_admm64.hip): the _c32 argument lists
     SIGNATURES["jstsp_%s_f64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
 
+for _n in ("nmse_spectral", "rate"):
+    # scoring a float64 estimate without narrowing (csrc/svdvals.hip): the argument lists of the _c64 namesakes
+    SIGNATURES["jstsp_%s_f64" % _n] = SIGNATURES["jstsp_%s_c32" % _n]
+
 
 class JstspError(RuntimeError):
     """A failed C-ABI call; ``code`` is its status (< 0: JSTSP_E_*, > 0: hipError_t), None when raised on the Python side."""

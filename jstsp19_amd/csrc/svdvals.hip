@@ -334,9 +334,133 @@ int spectrum_impl(jstsp_ctx *ctx, int rows, int cols, int batch, const T *Y, int
     return 0;
 }
 
+// ---- scoring a float64 estimate: spectral NMSE and rate (jstsp_nmse_spectral_f64 / jstsp_rate_f64) --------
+// sigma_1(S - Zbar) and the values of Zbar on the three routes above, then one thread per trial.  D = S - Zbar is formed in
+// float64 from the operands: as it is loaded on the LDS and QR routes (never stored, and the power-of-two scale is found from
+// |D|'s own largest component - D may be 1e-9 of Zbar), into the workspace on the third.
+
+// One workgroup per (trial, operand): operand 0 is D, operand 1 is Zbar; LDS and threads as svdvals_kernel.
+__global__ __launch_bounds__(64 * SV_WAVES) void score_values_kernel(int rows, int cols, const double2 *S, const double2 *Z, int z_keep,
+                                                                     double *svD, double *svZ)
+{
+    extern __shared__ double2 lds[];
+    const int t = blockIdx.x;
+    const bool diff = blockIdx.y == 0, tall = rows >= cols;
+    const int m = tall ? rows : cols, n = tall ? cols : rows;
+    const double2 *St = S + (size_t)rows * cols * t, *Zt = Z + (size_t)rows * cols * t;
+    for (int e = threadIdx.x; e < rows * cols; e += blockDim.x) {
+        double2 v = Zt[e];
+        if (diff) {
+            const double2 s = St[e];
+            v = make_double2(s.x - v.x, s.y - v.y);
+        }
+        if (tall) lds[e] = v;
+        else lds[e / rows + m * (e % rows)] = make_double2(v.x, -v.y);
+    }
+    if (diff) singular_values_block(lds, m, n, 1, svD + t);
+    else singular_values_block(lds, m, n, z_keep, svZ + (size_t)z_keep * t);
+}
+
+__global__ __launch_bounds__(256) void subtract_kernel(long long cnt, const double2 *S, const double2 *Z, double2 *D)
+{
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (long long)gridDim.x * 256)
+        D[e] = make_double2(S[e].x - Z[e].x, S[e].y - Z[e].y);
+}
+
+// One thread per trial.  e = (sigma_1(D) / sigma_1(Zbar))^2, the quotient first (plot_errorVSsnr.m:138-141).  NMSE: min(1, e),
+// NaN stays NaN.  Rate (plot_rateVSframelength.m:81): log2 det(I + Zbar Zbar^H / (R (noise_var + e))) as the sum over the z_keep = n
+// values of Zbar, k ascending, with e not capped.
+__global__ __launch_bounds__(256) void score_finish_kernel(int batch, int z_keep, int rate, double R, double noise_var, const double *svD,
+                                                           const double *svZ, double *out)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= batch) return;
+    const double *z = svZ + (size_t)z_keep * t;
+    const double q = svD[t] / z[0], e = q * q;
+    if (!rate) {
+        out[t] = e > 1.0 ? 1.0 : e;
+        return;
+    }
+    const double den = R * (noise_var + e);
+    double acc = 0.0;
+    for (int k = 0; k < z_keep; ++k) acc += log2(1.0 + z[k] * z[k] / den);
+    out[t] = acc;
+}
+
+int score_impl(jstsp_ctx *ctx, int rows, int cols, int batch, const double2 *S, const double2 *Z, bool rate, double noise_var, double *res,
+               int memspace, const char *what)
+{
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: NULL context", what);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace", what);
+    JSTSP_REQUIRE(S && Z && res, JSTSP_E_NULL, "%s: NULL argument", what);
+    JSTSP_REQUIRE(rows > 0 && cols > 0 && batch > 0, JSTSP_E_SHAPE, "%s: bad shape", what);
+    JSTSP_REQUIRE(!rate || noise_var >= 0.0, JSTSP_E_ARG, "%s: noise_var must be >= 0", what);     // (a NaN fails the comparison)
+    JSTSP_REQUIRE(spectrum_shape_ok(rows, cols), JSTSP_E_UNSUPPORTED, "%s: %d x %d: need " SPECTRUM_LIMITS, what, rows, cols);
+    const int m = std::max(rows, cols), n = std::min(rows, cols), z_keep = rate ? n : 1;
+    const bool host = memspace == JSTSP_HOST, lds = sv_fits(rows, cols), qr = !lds && tq_fits(rows, cols);
+    JSTSP_REQUIRE(lds || qr || batch <= 65535, JSTSP_E_UNSUPPORTED, "%s: %d x %d, batch %d: orders above 64 need batch <= 65535", what, rows,
+                  cols, batch);
+    JSTSP_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t nY = (size_t)rows * cols;
+    const double2 *s, *z;
+    double2 *D = nullptr;
+    double *svD, *svZ, *o;
+    Pinv64Arrays pv{};
+    Slab w(st);
+    JSTSP_TRY(ws64_open(w, what, batch, [&](Slab &a, int b) {
+        s = a.in(S, nY * b, host);
+        z = a.in(Z, nY * b, host);
+        svD = a.get<double>((size_t)b);
+        svZ = a.get<double>((size_t)z_keep * b);
+        o = a.out(res, (size_t)b, host);
+        if (!lds && !qr) {
+            D = a.get<double2>(nY * b);
+            pv.W = a.get<double2>((size_t)m * n * b); pv.V = a.get<double2>((size_t)n * n * b);
+            pv.meta = a.get<PvMeta>(b);
+            pv.any = a.get<int>(1);
+        }
+    }));
+    if (lds) {
+        const size_t sh = sv_lds_bytes(m, n);
+        JSTSP_HIP(hipFuncSetAttribute((const void *)score_values_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+        score_values_kernel<<<dim3(batch, 2), sv_threads(n), sh, st>>>(rows, cols, s, z, z_keep, svD, svZ);
+        JSTSP_HIP(hipGetLastError());
+    } else if (qr) {                                               // tsqr_values_kernel twice: the spectrum entries keep their kernel
+        JSTSP_TRY(tsqr_launch(st, DiffLoader<double2>{s, z, rows, cols}, n, batch, 1, svD));
+        JSTSP_TRY(tsqr_launch(st, MatrixLoader<double2>{z, rows, cols}, n, batch, z_keep, svZ));
+    } else {
+        const long long cnt = (long long)nY * batch;
+        subtract_kernel<<<grid_for(cnt), 256, 0, st>>>(cnt, s, z, D);
+        JSTSP_HIP(hipGetLastError());
+        JSTSP_TRY(pinv64_values(st, pv, rows, cols, batch, D, (long long)nY, 1, svD));
+        JSTSP_TRY(pinv64_values(st, pv, rows, cols, batch, z, (long long)nY, z_keep, svZ));
+    }
+    score_finish_kernel<<<(batch + 255) / 256, 256, 0, st>>>(batch, z_keep, rate ? 1 : 0, (double)rows, noise_var, svD, svZ, o);
+    JSTSP_HIP(hipGetLastError());
+    if (host) {
+        JSTSP_TRY(w.copy_back(res, o, (size_t)batch));
+        JSTSP_HIP(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int jstsp_nmse_spectral_f64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar, double *nmse, int memspace)
+{
+    return score_impl(ctx, R, C, batch, reinterpret_cast<const double2 *>(S), reinterpret_cast<const double2 *>(Zbar), false, 0.0, nmse,
+                      memspace, "nmse_spectral_f64");
+}
+
+int jstsp_rate_f64(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c64 *S, const jstsp_c64 *Zbar, double noise_var, double *rate,
+                   int memspace)
+{
+    return score_impl(ctx, R, C, batch, reinterpret_cast<const double2 *>(S), reinterpret_cast<const double2 *>(Zbar), true, noise_var, rate,
+                      memspace, "rate_f64");
+}
 
 int jstsp_singular_values_c32(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c32 *Y, double *sv, int memspace)
 {

@@ -57,6 +57,36 @@ template <class T> struct MatrixLoader {
     }
 };
 
+// a loader like MatrixLoader: the difference S - Z of two operands, formed in float64 entry by entry as it is loaded and never
+// stored; the scale comes from the largest component of the difference itself, which may be 1e-9 of the operands'
+template <class T> struct DiffLoader {
+    const T *S, *Z;
+    int rows, cols;
+    __device__ void bind(int t) { S += (size_t)rows * cols * t; Z += (size_t)rows * cols * t; }
+    __device__ bool scan(double *red, int *ex) const
+    {
+        double amax = 0.0;
+        int bad = 0;
+        for (int e = threadIdx.x; e < rows * cols; e += blockDim.x) {
+            const double2 s = ld2(S[e]), z = ld2(Z[e]);
+            const double dx = s.x - z.x, dy = s.y - z.y;
+            bad |= !isfinite(dx) || !isfinite(dy);
+            amax = fmax(amax, fmax(fabs(dx), fabs(dy)));
+        }
+        if (block_max_or_bad(amax, bad, red)) return true;
+        int e2 = 0;
+        if (amax > 0.0) frexp(amax, &e2);
+        *ex = max(-1000, min(1000, e2));
+        return false;
+    }
+    __device__ __forceinline__ double2 at(int r, int c, double sc) const
+    {
+        const size_t e = r + (size_t)rows * c;
+        const double2 s = ld2(S[e]), z = ld2(Z[e]);
+        return make_double2((s.x - z.x) * sc, (s.y - z.y) * sc);
+    }
+};
+
 // [R; chunk] -> R: column j's reflector P = I - u u^H / (|x| (|x| + |alpha|)), x = (alpha; y) with alpha = R(j, j) and y the chunk's
 // column j, u = x - beta e_1, beta = -(alpha / |alpha|) |x| (no cancellation in u_1), applied to the columns k > j, one wave
 // per column.  Every wave forms the reflector itself from the same numbers in the same order, so none waits for another; one

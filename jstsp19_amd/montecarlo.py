@@ -186,7 +186,7 @@ def _times(A, S, P):
 
 
 def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_max_order=128, ls_precision="f32",
-                   mmv_precision="f32"):
+                   mmv_precision="f32", score="host"):
     """LS, VAMP and MMV-OMP baselines of plot_errorVSsnr.m:73-121 on the conventional-HBF measurement; with
     ``tssr = (Imax, rho)`` also the commented TSSR recipe (:151,158-162) on the proposed scheme's measurement.
     Every product goes through the library (correlate / synthesize entry points), nothing through torch matmuls.
@@ -205,17 +205,22 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
     ``mmv_precision="f64"`` (opt-in, independent of ``ls_precision``): the MMV-OMP column is
     ``mmv_omp_f64(A_hbf, Y_hbf*pinv_f64(B_hbf), numOfnz)`` and the TSSR / SVT-based columns come from ``tssr_f64`` - float64
     matrix completion, pinv, products and joint OMP (``jstsp_mc_svt_f64``, ``jstsp_mmv_omp_f64``), at every driver size -
-    and all three are scored in float64 (``_score_f64``).  The default "f32" leaves every column as it was."""
+    and all three are scored in float64 (``_score_f64``).  The default "f32" leaves every column as it was.
+
+    ``score="device"`` (opt-in; the default "host" is ``_score_f64``, unchanged): the columns ``_score_f64`` scores are scored
+    by ``nmse_spectral_f64`` / ``rate_f64`` on the device instead (``_score_f64_device``: float64 singular values, no Gram
+    matrix; only one double per trial crosses the bus).  The fp32 columns keep ``_score``."""
     from . import _lib
     from . import solvers as J
     _check_precisions(ls_precision, mmv_precision)
+    _check_score(score)
     zb = J.colmajor(inp["Zbar"].to(torch.complex64))
     ctx = _lib.default_context(inp["Y_hbf"].device.index or 0)
     nan = lambda: torch.full((inp["Y_hbf"].shape[0],), float("nan"), dtype=torch.float64)
     Bh = inp["B_hbf"]
     G2 = Bh.shape[1]
     if ls_precision == "f64":
-        return _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision)
+        return _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision, score)
     try:
         PB = J.pinv(Bh)                                                                  # pinv(B)  :83, :117
     except J.JstspError as e:
@@ -233,7 +238,7 @@ def _hip_baselines(inp, numOfnz, metric="nmse", noise_var=1.0, tssr=None, vamp_m
         Ym = _times_h(inp["Y_hbf"], Bh)                                                  # Y_hbf*B' :80
         out["vamp"] = _score(J.vamp_kron(Ym, inp["A_hbf"], Gb, 1.0, numOfnz), zb, metric, noise_var)   # :100
     if mmv_precision == "f64":
-        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr))
+        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, score=score))
         return out
     Ypb = None
     if PB is not None:
@@ -276,6 +281,26 @@ def _score_f64(S, zb, metric, noise_var):
     return torch.from_numpy(out)
 
 
+def _score_f64_device(S, zb, metric, noise_var):
+    """``_score_f64`` on the device (``score="device"``): the same two formulas by ``nmse_spectral_f64`` / ``rate_f64`` - float64
+    singular values of ``S - Zbar`` and ``Zbar`` themselves, nothing narrowed, no Gram matrix.  ``S``: (batch, R, C) complex128,
+    ``zb`` complex64 or complex128 (widened on the device), CUDA tensors as the solvers and ``build_trials`` leave them.
+    Returns what ``_score_f64`` returns: a float64 CPU tensor (batch,)."""
+    from . import solvers as J
+    S, zb = J.colmajor(S.detach().to(torch.complex128)), J.colmajor(zb.detach())
+    out = J.nmse_spectral_f64(S, zb) if metric == "nmse" else J.rate_f64(S, zb, noise_var)
+    return out.cpu()
+
+
+def _scorer_f64(score):
+    return _score_f64_device if score == "device" else _score_f64
+
+
+def _check_score(score):
+    if score not in ("host", "device"):
+        raise ValueError("score must be 'host' or 'device'")
+
+
 def _check_precisions(ls_precision, mmv_precision):
     if ls_precision not in ("f32", "f64"):
         raise ValueError("ls_precision must be 'f32' or 'f64'")
@@ -283,41 +308,43 @@ def _check_precisions(ls_precision, mmv_precision):
         raise ValueError("mmv_precision must be 'f32' or 'f64'")
 
 
-def _mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB=None):
+def _mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB=None, score="host"):
     """The MMV-OMP column and, with ``tssr = (Imax, rho)``, the TSSR and SVT-based columns in float64
-    (``mmv_precision="f64"``); ``PB``: ``pinv_f64(B_hbf)`` where the caller has it."""
+    (``mmv_precision="f64"``); ``PB``: ``pinv_f64(B_hbf)`` where the caller has it; ``score``: see ``_hip_baselines``."""
     from . import solvers as J
+    score_f64 = _scorer_f64(score)
     wide = lambda x: x.to(torch.complex128)
     Bh, Ah, Yh = inp["B_hbf"], inp["A_hbf"], inp["Y_hbf"]
     if PB is None:
         PB = J.pinv_f64(wide(Bh))                                                        # pinv(B)  :117
     eye = J.colmajor(torch.eye(Yh.shape[-2], dtype=torch.complex128, device=Yh.device))
     Z, _, _ = J.mmv_omp_f64(wide(Ah), J.synthesize_f64(wide(Yh), eye, PB), numOfnz)      # :116-117
-    out = {"omp_mmv": _score_f64(Z, inp["Zbar"], metric, noise_var)}
+    out = {"omp_mmv": score_f64(Z, inp["Zbar"], metric, noise_var)}
     if tssr is not None:
         St, _, Ssvt = J.tssr_f64(inp["subY"], inp["Omega"], inp["A"], inp["B"], tssr[0], inp["tau_Y"].numpy(), tssr[1],
                                  2 * numOfnz)                                            # :151,:160-161
-        out["tssr"] = _score_f64(St, inp["Zbar"], metric, noise_var)
-        out["svt"] = _score_f64(Ssvt, inp["Zbar"], metric, noise_var)                    # :152-153
+        out["tssr"] = score_f64(St, inp["Zbar"], metric, noise_var)
+        out["svt"] = score_f64(Ssvt, inp["Zbar"], metric, noise_var)                    # :152-153
     return out
 
 
-def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision="f32"):
+def _hip_baselines_f64(inp, numOfnz, metric, noise_var, tssr, vamp_max_order, mmv_precision="f32", score="host"):
     """``_hip_baselines`` with the least-squares pieces in float64 (``ls_precision="f64"``)."""
     from . import solvers as J
+    score_f64 = _scorer_f64(score)
     zb = J.colmajor(inp["Zbar"].to(torch.complex64))
     Bh, Ah, Yh = inp["B_hbf"], inp["A_hbf"], inp["Y_hbf"]
     G2 = Bh.shape[1]
     wide = lambda x: x.to(torch.complex128)
     PB = J.pinv_f64(wide(Bh))                                                            # pinv(B)  :83, :117
     S_ls = J.ls_estimate_f64(wide(Yh), wide(Ah), wide(Bh))                               # :83
-    out = {"ls": _score_f64(S_ls, inp["Zbar"], metric, noise_var)}
+    out = {"ls": score_f64(S_ls, inp["Zbar"], metric, noise_var)}
     if G2 <= vamp_max_order and Ah.shape[0] <= 128:
         Gb = _times_h(Bh, Bh)                                                            # (B*B')  :79
         Ym = _times_h(Yh, Bh)                                                            # Y_hbf*B' :80
         out["vamp"] = _score(J.vamp_kron(Ym, Ah, Gb, 1.0, numOfnz), zb, metric, noise_var)   # :100
     if mmv_precision == "f64":
-        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB))
+        out.update(_mmv_columns_f64(inp, numOfnz, metric, noise_var, tssr, PB, score))
         return out
     eye = J.colmajor(torch.eye(Yh.shape[-2], dtype=torch.complex128, device=Yh.device))
     Ypb = J.synthesize_f64(wide(Yh), eye, PB).to(torch.complex64)                        # Y_hbf_nr*pinv(B)  :117
@@ -396,7 +423,7 @@ def _merge_cap(p, batch, with_hbf):
 
 def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=None, solve_fn=None, dist=None,
                baselines=False, numOfnz=100, builder=None, metric="nmse", tssr=None, merge=True, vamp_max_order=128,
-               samples=None, ls_precision="f32", mmv_precision="f32", channel=None, channel_normalize="reference"):
+               samples=None, ls_precision="f32", mmv_precision="f32", channel=None, channel_normalize="reference", score="host"):
     """Mean capped NMSE per sweep point; columns (proposed_algorithm, proposed_algorithm_angles[, LS, VAMP, MMV-OMP
     [, TSSR]]).  ``metric="rate"``: the rate of plot_rateVSframelength.m:81 instead of the NMSE (HIP solvers only).
     ``tssr=(Imax_svt, rho_svt)`` adds the commented recipes of plot_errorVSsnr.m:151-162 as columns six and seven: TSSR
@@ -419,9 +446,12 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
     ``channel``, ``channel_normalize``: handed to ``build_trials`` - a supplied channel instead of the drawn one, shared
     ``(Nr_src, Nt_src, L)`` or one per trial ``(n_trials, Nr_src, Nt_src, L)`` (the same n_trials channels at every sweep
     point); library builder only.
+    ``score="device"``: the float64 columns of the baselines are scored on the device (``nmse_spectral_f64`` / ``rate_f64``)
+    instead of by ``_score_f64`` on the host; the default "host" changes nothing (see ``_hip_baselines``).
     Returns a float64 tensor (len(points), ncol) identical on every rank.
     """
     _check_precisions(ls_precision, mmv_precision)
+    _check_score(score)
     if channel is not None:
         if builder is not None and builder != "hip":
             raise ValueError("channel= goes to the library's builder; a callable builder makes its own channel")
@@ -475,7 +505,7 @@ def run_points(points, n_trials, *, Imax=100, batch=64, seed=20190913, device=No
         e, ea = solve_fn(inp, Imax) if custom else solve_fn(inp, Imax, p.noise_var)
         cols = [torch.as_tensor(e).double().cpu(), torch.as_tensor(ea).double().cpu()]
         if baselines:
-            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order, ls_precision, mmv_precision)
+            b = _hip_baselines(inp, numOfnz, metric, p.noise_var, tssr, vamp_max_order, ls_precision, mmv_precision, score)
             for key in ("ls", "vamp", "omp_mmv", "tssr", "svt")[:ncol - 2]:
                 cols.append(b[key].double().cpu() if key in b else torch.full((total,), float("nan"), dtype=torch.float64))
         o = 0
@@ -513,13 +543,15 @@ def _hip_alg12(inp, Imax):
     return out
 
 
-def _hip_alg12_f64(inp, Imax_list):
+def _hip_alg12_f64(inp, Imax_list, score="host"):
     """``_hip_alg12`` in float64 for every Imax of the list on ONE batch of trials: ``pinv_f64(A)`` and ``pinv_f64(B)`` are
     computed once and serve the least-squares step of every Alg. 1 solve (``proposed_algorithm_std_f64(..., PA=, PB=)``) and
     the scoring product ``pinv(A)*Y*pinv(B)`` of both columns (on the f64 matrix pipe: ``correlate_f64`` with the adjoints of
     the factors).  Alg. 2 is ``proposed_algorithm_f64``; the columns are scored by ``_score_f64``.  Returns one
-    ``(e_std, e_approx)`` per Imax."""
+    ``(e_std, e_approx)`` per Imax.  ``score="device"``: scored by ``nmse_spectral_f64`` on the device instead."""
     from . import solvers as J
+    _check_score(score)
+    score_f64 = _scorer_f64(score)
     wide = lambda x: J.colmajor(x.to(torch.complex128))
     subY, A, B, zb = wide(inp["subY"]), wide(inp["A"]), wide(inp["B"]), wide(inp["Zbar"])
     Om = J.colmajor(inp["Omega"].to(torch.float64))
@@ -530,11 +562,11 @@ def _hip_alg12_f64(inp, Imax_list):
     for Imax in Imax_list:
         _, Y1, _ = J.proposed_algorithm_std_f64(subY, Om, A, B, int(Imax), *prm, PA=PA, PB=PB, want_ce=False)     # :60
         _, Y2, _ = J.proposed_algorithm_f64(subY, Om, A, B, int(Imax), *prm, "approximate", want_ce=False)        # :67
-        out.append(tuple(_score_f64(J.correlate_f64(Y, PAh, PBh), zb, "nmse", 0.0) for Y in (Y1, Y2)))           # :61-65, :68-72
+        out.append(tuple(score_f64(J.correlate_f64(Y, PAh, PBh), zb, "nmse", 0.0) for Y in (Y1, Y2)))           # :61-65, :68-72
     return out
 
 
-def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed, device, dist, builder):
+def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed, device, dist, builder, score="host"):
     """``run_approx_sweep(precision="f64")``: the (SNR, trial) pairs are sharded over ranks; a batch of trials is built once and
     solved for every Imax (its Philox key is the sweep index of the point (SNR, Imax_list[0]) of the default sweep, so that
     column sees the realisations the fp32 sweep sees)."""
@@ -553,7 +585,7 @@ def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed
             inp = build_trials_training(p, t0, t1 - t0, seed=seed, sweep_idx=si * nI, device=device)
         else:
             inp = builder(p, range(t0, t1), seed, si * nI, device, False)
-        for ii, (e1, e2) in enumerate(_hip_alg12_f64(inp, Imax_list)):
+        for ii, (e1, e2) in enumerate(_hip_alg12_f64(inp, Imax_list, score)):
             acc[si, ii, 0] += float(e1.sum())
             acc[si, ii, 1] += float(e2.sum())
             acc[si, ii, 2] += t1 - t0
@@ -567,7 +599,7 @@ def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed
 
 
 def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, batch=64, seed=20190913, device=None,
-                     solve_fn=None, dist=None, builder=None, precision="f32"):
+                     solve_fn=None, dist=None, builder=None, precision="f32", score="host"):
     """The Alg.1-vs-Alg.2 sweep of plot_errorVSsnr_approx.m:34-85: for each SNR and each Imax, ``n_trials`` fresh
     realisations of wideband_hybBF_comm_system_training, both solver variants, capped NMSE of
     ``pinv(A)*Y*pinv(B)``, mean then ``min(., 1)`` (:76-77).
@@ -581,10 +613,12 @@ def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, 
     float64 - Alg. 1 by ``proposed_algorithm_std_f64``, Alg. 2 by ``proposed_algorithm_f64``, ``_score_f64``.  The reference
     draws fresh realisations for every (SNR, Imax) point; here a batch of trials is built once per SNR and solved for every
     Imax of the list, so that ``pinv_f64(A)`` and ``pinv_f64(B)`` are computed once per batch (``_hip_alg12_f64``).  No
-    ``solve_fn`` hook.
+    ``solve_fn`` hook.  ``score="device"`` scores the float64 columns on the device (``nmse_spectral_f64``) instead of by
+    ``_score_f64`` on the host; it changes nothing at ``precision="f32"``.
     """
     if precision not in ("f32", "f64"):
         raise ValueError("precision must be 'f32' or 'f64'")
+    _check_score(score)
     if precision == "f64" and solve_fn is not None:
         raise ValueError("precision='f64' solves with the library's float64 entries: no solve_fn")
     rank = dist.get_rank() if dist is not None else 0
@@ -594,7 +628,7 @@ def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, 
     builder = _resolve_builder(builder, device)
     if precision == "f64":
         return _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, batch=batch, seed=seed, device=device, dist=dist,
-                                     builder=builder)
+                                     builder=builder, score=score)
     if solve_fn is None:
         solve_fn = _hip_alg12
     pts = [(si, ii) for si in range(len(snr_db_list)) for ii in range(len(Imax_list))]    # loop order of :34-38

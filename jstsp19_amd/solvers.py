@@ -32,7 +32,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
-           "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64"]
+           "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1309,3 +1309,50 @@ def sparse_admm_f64(Htrue, OH, Dr, Dt, Imax, *, want_ce=True, ctx=None):
               "jstsp_sparse_admm_f64")
     sq = not a_O.batched
     return f(sq), (fce(sq)[..., 0] if want_ce else None)
+
+
+# ----------------------------------------------------------------------------- scoring a float64 estimate
+def _score_f64_call(entry, S, Zbar, extra, ctx):
+    if _is_torch(Zbar):
+        import torch
+        if Zbar.dtype == torch.complex64:                       # what build_trials returns: widened on the device (exact)
+            Zbar = Zbar.to(torch.complex128)
+    a_S, a_Z = _Arg(S, np.complex128, "S"), _Arg(Zbar, np.complex128, "Zbar")
+    if (a_S.batch, a_S.R, a_S.C) != (a_Z.batch, a_Z.R, a_Z.C):
+        raise ValueError("S and Zbar must have the same shape")
+    c, mem, dev = _ctx_for([a_S, a_Z], ctx)
+    batch, R, Cc = a_S.batch, a_S.R, a_S.C
+    if mem == DEVICE:
+        import torch
+        out = torch.empty(batch, dtype=torch.float64, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty(batch, dtype=np.float64)
+        optr = out.ctypes.data
+    m, n = max(R, Cc), min(R, Cc)
+    # bytes of workspace per trial (csrc/svdvals.hip): the staged copies of host operands, the values; above order 64 the
+    # difference, its rotated copy and V
+    per = (2 * 16 * R * Cc if mem == HOST else 0) + 8 * (n + 2)
+    if n > 64:
+        per += 16 * (R * Cc + m * n + n * n)
+    fn = getattr(c._lib, entry)
+    for t0, nb in _f64_chunks(batch, per):
+        check(fn(c.handle, R, Cc, nb, _off(a_S.ptr, t0 * R * Cc, 16), _off(a_Z.ptr, t0 * R * Cc, 16), *extra, _off(optr, t0, 8), mem), entry)
+    return out if a_S.batched else out[0]
+
+
+def nmse_spectral_f64(S, Zbar, *, ctx=None):
+    """:func:`nmse_spectral` for a float64 estimate, without narrowing (``jstsp_nmse_spectral_f64``, csrc/svdvals.hip):
+    ``min(1, (norm(S-Zbar, 2) / norm(Zbar, 2))^2)`` from float64 singular values of ``S - Zbar`` and ``Zbar`` themselves - no Gram
+    matrix, so an error 1e-9 of ``Zbar`` keeps its digits.  ``S``: (R, C) or (batch, R, C), numpy or a column-major torch CUDA
+    tensor, complex128; ``Zbar`` likewise, and a complex64 CUDA ``Zbar`` (what ``build_trials`` returns) is widened on the
+    device.  Shapes of :func:`spectrum`, else ``JstspError`` (code -3).  Returns float64 (batch,) where ``S`` lives; a non-finite
+    entry gives NaN for its own trial."""
+    return _score_f64_call("jstsp_nmse_spectral_f64", S, Zbar, (), ctx)
+
+
+def rate_f64(S, Zbar, noise_var, *, ctx=None):
+    """:func:`rate` for a float64 estimate, without narrowing (``jstsp_rate_f64``): ``sum_k log2(1 + sigma_k(Zbar)^2 / (R (noise_var +
+    e)))`` = ``log2(real(det(eye(R) + 1/R*Zbar*Zbar'/(noise_var + e))))`` with ``e`` the uncapped spectral-norm NMSE of ``S`` and R
+    the rows of ``Zbar``.  Arguments and result as :func:`nmse_spectral_f64`; ``noise_var`` >= 0."""
+    return _score_f64_call("jstsp_rate_f64", S, Zbar, (float(noise_var),), ctx)

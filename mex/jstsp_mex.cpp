@@ -539,6 +539,21 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         const int rc = jstsp_mc_admm_f64(g_ctx, d.r, d.c, d.b, H, OH, Om, Imax, tau, rho, c64(plhs[0]), ce ? mxGetDoubles(ce) : nullptr, JSTSP_HOST);
         if (rc) fail("jstsp_mc_admm_f64", rc);
         if (ce) plhs[1] = ce;
+    } else if (!strcmp(fn, "nmse_spectral_f64") || !strcmp(fn, "rate_f64")) {
+        // nmse_spectral_f64(S, Zbar), rate_f64(S, Zbar, noise_var): 'nmse' and 'rate' below for a float64 estimate - nothing is narrowed,
+        // float64 singular values of S - Zbar and of Zbar, no Gram matrix (jstsp_nmse_spectral_f64 / jstsp_rate_f64); pages = batch
+        const bool is_rate = fn[0] == 'r';
+        check_nargs(fn, nrhs, is_rate ? 3 : 2, is_rate ? 3 : 2, nlhs, 1);
+        const Dims d = dims_of(in[0]), dz = dims_of(in[1]);
+        if (dz.r != d.r || dz.c != d.c || dz.b != d.b) mexErrMsgIdAndTxt("jstsp:shape", "%s: S and Zbar must have the same size", fn);
+        const double nv = is_rate ? mxGetScalar(in[2]) : 0.0;
+        if (!(nv >= 0.0)) mexErrMsgIdAndTxt("jstsp:args", "%s: noise_var must be >= 0", fn);
+        const jstsp_c64 *S = cplx(in[0], fn, "S"), *Zb = cplx(in[1], fn, "Zbar");
+        ensure_ctx();
+        plhs[0] = mxCreateDoubleMatrix(d.b, 1, mxREAL);
+        const int rc = is_rate ? jstsp_rate_f64(g_ctx, d.r, d.c, d.b, S, Zb, nv, mxGetDoubles(plhs[0]), JSTSP_HOST)
+                               : jstsp_nmse_spectral_f64(g_ctx, d.r, d.c, d.b, S, Zb, mxGetDoubles(plhs[0]), JSTSP_HOST);
+        if (rc) fail(is_rate ? "jstsp_rate_f64" : "jstsp_nmse_spectral_f64", rc);
     } else if (!strcmp(fn, "nmse") || !strcmp(fn, "rate")) {
         // nmse(S, Zbar): min(1, norm(S-Zbar)^2/norm(Zbar)^2)  plot_errorVSsnr.m:138-141 (one value per page)
         // rate(S, Zbar, noise_var): log2(real(det(eye(Nr) + 1/Nr*Zbar*Zbar'/(noise_var + nmse))))  plot_rateVSframelength.m:81

@@ -14,6 +14,7 @@ ap.add_argument("--trials", type=int, default=None, help="default: the driver's 
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--ls-f64", action="store_true", help="LS and Y*pinv(B) of the baseline columns from the float64 entries (jstsp_pinv_f64 / jstsp_ls_f64)")
 ap.add_argument("--mmv-f64", action="store_true", help="MMV-OMP, TSSR and SVT-based baseline columns from the float64 entries (jstsp_mmv_omp_f64 / jstsp_mc_svt_f64)")
+ap.add_argument("--score-device", action="store_true", help="score the float64 columns on the device (jstsp_nmse_spectral_f64 / jstsp_rate_f64) instead of on the host")
 ap.add_argument("--channel", default=None, metavar="FILE",
                 help=".npy, .npz (key Hf or H) or .mat (cell array Hf) with an array (Nr_src, Nt_src, L): the channel instead of the "
                      "drawn one (errorVSsnr_nyuwireless needs it)")
@@ -44,7 +45,7 @@ else:
     n = a.trials or d["n_trials"]
     kw = dict(channel=mc.load_channel(a.channel), channel_normalize=a.channel_normalize) if a.channel else {}
     out = mc.run_driver(a.name, n, batch=min(a.batch, n), ls_precision="f64" if a.ls_f64 else "f32",
-                        mmv_precision="f64" if a.mmv_f64 else "f32", **kw)
+                        mmv_precision="f64" if a.mmv_f64 else "f32", score="device" if a.score_device else "host", **kw)
     torch.cuda.synchronize()
     print("%s (%s), %d trials/point, %.1f s" % (a.name, d["metric"], n, time.perf_counter() - t0))
     print("%-8s proposed  +angles   LS        VAMP      MMV-OMP" % d["axis"])

@@ -17,6 +17,7 @@ ap.add_argument("--tssr", action="store_true", help="add the TSSR recipe (mc_svt
 ap.add_argument("--vamp-large", action="store_true", help="VAMP column also where L*Gt > 128 (one order-L*Gt eigen-decomposition per trial)")
 ap.add_argument("--ls-f64", action="store_true", help="LS and Y*pinv(B) from the float64 entries (jstsp_pinv_f64 / jstsp_ls_f64): numbers where the fp32 Gram route gives NaN")
 ap.add_argument("--mmv-f64", action="store_true", help="MMV-OMP, TSSR and SVT-based columns from the float64 entries (jstsp_mmv_omp_f64 / jstsp_mc_svt_f64), at every size of B")
+ap.add_argument("--score-device", action="store_true", help="score the float64 columns on the device (jstsp_nmse_spectral_f64 / jstsp_rate_f64) instead of on the host")
 ap.add_argument("--config3", action="store_true", help="BASELINE configs[3]: Nt=Nr=64, Nrf=8, K=64, L=8, 10 SNR points")
 ap.add_argument("--dist", action="store_true",
                 help="one rank per GPU (start with python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 "
@@ -40,7 +41,7 @@ if a.config3:
 t0 = time.perf_counter()
 out = run_sweep(base, snrs, a.trials, Imax=100, batch=a.batch, baselines=True, numOfnz=100, builder=a.builder, vamp_max_order=8192 if a.vamp_large else 128,
                 metric="rate" if a.rate else "nmse", tssr=(100, 0.1) if a.tssr else None, dist=dist,
-                ls_precision="f64" if a.ls_f64 else "f32", mmv_precision="f64" if a.mmv_f64 else "f32")
+                ls_precision="f64" if a.ls_f64 else "f32", mmv_precision="f64" if a.mmv_f64 else "f32", score="device" if a.score_device else "host")
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 if dist is not None:
