@@ -460,13 +460,24 @@ int jstsp_cawgn_estim_out_f64(jstsp_ctx *ctx, long long n, const double *y, cons
                               double *zvar, int memspace);
 
 /* nmse[t] = min(1, norm(S - Zbar)^2 / norm(Zbar)^2) with spectral norms
- *   plot_errorVSsnr.m:138-141.   S, Zbar: R x C x batch; nmse: batch doubles (same memspace). */
+ *   plot_errorVSsnr.m:138-141.   S, Zbar: R x C x batch, min(R, C) <= 2048; nmse: batch doubles (same memspace).
+ * Conventions (those of the host formula, of MATLAB and of jstsp_nmse_spectral_f64): S == Zbar gives exactly 0; Zbar == 0 gives NaN
+ * for S == 0 (0/0) and 1 for any other S (x/0 = Inf, capped); a trial with a NaN or Inf entry in S or in Zbar gives NaN and leaves
+ * the other trials of the batch alone.
+ * Input scale: D = S - Zbar and Zbar are each brought to a largest |re|, |im| in [1, 2) by an exact power of two per trial before
+ * the Gram is formed and the scale is undone in double, so the result does not depend on the unit of the operands: any finite
+ * complex64 operands whose difference S - Zbar is finite (the NMSE is the same at 2^-40 and 2^+40 times the operands).
+ * min(R, C) > 128: lambda_max is the Rayleigh quotient, in double, of the leading column of the block Jacobi's basis. */
 int jstsp_nmse_spectral_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S,
                             const jstsp_c32 *Zbar, double *nmse, int memspace);
 
 /* rate[t] = log2(real(det(eye(R) + 1/R * Zbar*Zbar' / (noise_var + norm(Zbar - S)^2/norm(Zbar)^2))))
- *   plot_rateVSframelength.m:81,113,130,135 (spectral norms, NMSE not capped).  S, Zbar: R x C x batch, R <= 128;
- * rate: batch doubles (same memspace). */
+ *   plot_rateVSframelength.m:81,113,130,135 (spectral norms, NMSE not capped).  S, Zbar: R x C x batch, min(R, C) <= 128
+ * (the eigenvalues are those of the Gram of the smaller side; R itself may be larger); rate: batch doubles (same memspace).
+ * Conventions: S == Zbar scores with an NMSE of exactly 0; Zbar == 0 gives NaN for S == 0 (0/0) and 0 for any other S (no signal:
+ * log2 det(I)); a trial with a NaN or Inf entry in S or in Zbar gives NaN and leaves the other trials alone.
+ * Input scale: as jstsp_nmse_spectral_c32 - the eigenvalues are taken of the scaled Zbar (Rayleigh quotients of the Jacobi basis, in
+ * double; a negative one is rounding noise: summed while |lambda c| < 2^-10, clamped to 0 beyond) and brought back in double. */
 int jstsp_rate_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S, const jstsp_c32 *Zbar,
                    double noise_var, double *rate, int memspace);
 

@@ -24,6 +24,120 @@ __global__ void ratio_cap_kernel(int batch, const float *num, const float *den, 
     }
 }
 
+// ---- the two scoring entries (jstsp_nmse_spectral_c32 / jstsp_rate_c32) work on operands scaled per trial by an exact power of two.
+// lmax_kernel squares Gram entries (a fourth power of the input) and guards with absolute constants (1e-30f, +-1e30f): at an input
+// scale of 2^-40 its reflector norm underflows, at 2^+40 its squared off-diagonal overflows, and over an all-zero matrix it returns
+// its floor instead of 0.  D = S - Zbar and Zbar are therefore brought to a largest |re|, |im| in [1, 2) before the Gram (every fp32
+// operation on them is then the same operation on other exponents: results at ordinary magnitudes keep their digits), the scale is
+// undone in double on the two lambda_max, an all-zero operand scores exactly 0, and a trial with a non-finite entry scores NaN
+// without its values ever reaching the eigen-solvers (fminf / fmaxf drop a NaN: the Sturm count then returns a finite number).
+// sigma_max_sq itself is untouched: the ADMM loops that call it once per iteration do not pay for this.
+
+// mx[2 t], mx[2 t + 1] = largest |re|, |im| over D[t] = S[t] - Zbar[t] and over Zbar[t], as the bits of a non-negative float: NaN
+// orders above Inf and Inf above every finite value, so a non-finite entry wins the maximum (mx zeroed beforehand)
+__global__ __launch_bounds__(256) void score_absmax_kernel(long long n, int batch, const float2 *S, const float2 *Zb, uint32_t *mx)
+{
+    const long long stride = (long long)gridDim.x * 256;
+    for (int t = blockIdx.y; t < batch; t += gridDim.y) {
+        const long long base = (long long)t * n;
+        uint32_t md = 0u, mz = 0u;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+            const float2 s = S[base + i], z = Zb[base + i];
+            md = max(md, max(__float_as_uint(s.x - z.x) & 0x7fffffffu, __float_as_uint(s.y - z.y) & 0x7fffffffu));
+            mz = max(mz, max(__float_as_uint(z.x) & 0x7fffffffu, __float_as_uint(z.y) & 0x7fffffffu));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            md = max(md, (uint32_t)__shfl_xor((int)md, o));
+            mz = max(mz, (uint32_t)__shfl_xor((int)mz, o));
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicMax(&mx[2 * t], md);
+            atomicMax(&mx[2 * t + 1], mz);
+        }
+    }
+}
+
+__device__ __forceinline__ bool score_bad(uint32_t m) { return m >= 0x7f800000u; }
+__device__ __forceinline__ int score_exp(uint32_t m) { return (m > 0u && !score_bad(m)) ? ilogbf(__uint_as_float(m)) : 0; }
+
+// D[t] = (S[t] - Zbar[t]) 2^-ed, Zs[t] = Zbar[t] 2^-ez with the exponents of mx; zeros for a trial with a non-finite entry
+__global__ __launch_bounds__(256) void score_scale_kernel(long long n, int batch, const float2 *S, const float2 *Zb, const uint32_t *mx,
+                                                          float2 *D, float2 *Zs)
+{
+    const long long stride = (long long)gridDim.x * 256;
+    for (int t = blockIdx.y; t < batch; t += gridDim.y) {
+        const long long base = (long long)t * n;
+        const uint32_t md = mx[2 * t], mz = mx[2 * t + 1];
+        const bool bad = score_bad(md) || score_bad(mz);
+        const int ed = -score_exp(md), ez = -score_exp(mz);
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+            const float2 s = S[base + i], z = Zb[base + i];
+            D[base + i] = bad ? make_float2(0.f, 0.f) : make_float2(ldexpf(s.x - z.x, ed), ldexpf(s.y - z.y, ed));
+            Zs[base + i] = bad ? make_float2(0.f, 0.f) : make_float2(ldexpf(z.x, ez), ldexpf(z.y, ez));
+        }
+    }
+}
+
+// e = norm(S - Zbar)^2 / norm(Zbar)^2 from the lambda_max of the scaled operands: NaN for a non-finite entry, an all-zero operand
+// counts as exactly 0 (0/0 = NaN and x/0 = Inf, as the host formula and MATLAB give them)
+__device__ __forceinline__ double score_e(int t, const float *num, const float *den, const uint32_t *mx)
+{
+    const uint32_t md = mx[2 * t], mz = mx[2 * t + 1];
+    if (score_bad(md) || score_bad(mz)) return (double)NAN;
+    const double nu = md ? ldexp((double)num[t], 2 * score_exp(md)) : 0.0;
+    const double de = mz ? ldexp((double)den[t], 2 * score_exp(mz)) : 0.0;
+    return nu / de;
+}
+
+// out[t] = Re(u^H G u) / (u^H u) in double for the column u of the basis U[t] whose eigenvalue lam[t][:] is the largest; G = the sum
+// of the Gram partials.  The quotient is exact to the SQUARE of the basis' error, so the last rotations of the block Jacobi - whose
+// number depends on the other matrices of the batch - do not reach its float bits, where the fp32 quotients of eig_large.hip (an
+// fp32 product G U) moved by an ulp between a trial scored alone and in a batch.  n <= 2048; one workgroup per trial.
+__global__ __launch_bounds__(256) void score_top_rayleigh_kernel(int n, const float2 *Gpart, long long sGt, int nsplit, long long sGs,
+                                                                 const float2 *U, const float *lam, float *out)
+{
+    const int t = blockIdx.x, tid = threadIdx.x;
+    __shared__ double ur[2048], ui[2048], red[8];
+    __shared__ int top;
+    if (tid == 0) {
+        int c = 0;
+        for (int i = 1; i < n; ++i) if (lam[(size_t)t * n + i] > lam[(size_t)t * n + c]) c = i;
+        top = c;
+    }
+    __syncthreads();
+    const float2 *u = U + ((size_t)t * n + top) * n;
+    for (int i = tid; i < n; i += 256) { ur[i] = u[i].x; ui[i] = u[i].y; }
+    __syncthreads();
+    double num = 0.0, den = 0.0;
+    const float2 *G = Gpart + (long long)t * sGt;
+    for (long long e = tid; e < (long long)n * n; e += 256) {
+        const int i = (int)(e % n), j = (int)(e / n);
+        double gx = 0.0, gy = 0.0;
+        for (int s = 0; s < nsplit; ++s) {
+            const float2 g = G[(long long)s * sGs + e];
+            gx += g.x; gy += g.y;
+        }
+        num += ur[i] * (gx * ur[j] - gy * ui[j]) + ui[i] * (gx * ui[j] + gy * ur[j]);      // Re(conj(u_i) g_ij u_j)
+    }
+    for (int i = tid; i < n; i += 256) den += ur[i] * ur[i] + ui[i] * ui[i];
+    for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o); den += __shfl_xor(den, o); }
+    if ((tid & 63) == 0) { red[tid >> 6] = num; red[4 + (tid >> 6)] = den; }
+    __syncthreads();
+    if (tid == 0) out[t] = (float)(((red[0] + red[1]) + (red[2] + red[3])) / ((red[4] + red[5]) + (red[6] + red[7])));
+}
+
+// nmse = min(1, e)   (plot_errorVSsnr.m:138-141; NaN stays NaN: `NaN > 1` is false)
+__global__ void score_nmse_kernel(int batch, const float *num, const float *den, const uint32_t *mx, double *out)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < batch) {
+        double e = score_e(t, num, den, mx);
+        if (e > 1.0) e = 1.0;
+        out[t] = e;
+    }
+}
+
 // mc_svt.m:9   Y = Y + rho (OH - Omega .* X)
 __global__ __launch_bounds__(256) void mc_svt_update_kernel(long long nm, float2 *Y, const float2 *OH,
                                                             const float *Omega, const float2 *X,
@@ -65,16 +179,54 @@ __global__ __launch_bounds__(256) void mc_admm_update_kernel(long long nm, float
     }
 }
 
-// rate[t] = sum_i log2(1 + lam_i / (R (noise_var + num/den)))   (plot_rateVSframelength.m:81: log2 det(I + Zbar Zbar'/(R (..))))
-__global__ __launch_bounds__(256) void rate_kernel(int batch, int n, int R, const float *lam, const float *num,
-                                                   const float *den, double noise_var, double *rate)
+// lam[t][c] = Re(u_c^H G u_c) / (u_c^H u_c) in double: G the sum of the Gram partials, u_c column c of the basis jacobi_kernel
+// returned.  The diagonal that kernel ends with has been through sweeps x (n - 1) fp32 rotations, each of which leaves eps |largest
+// entry| in the diagonal entries it touches - of the order of a near-zero eigenvalue itself; a Rayleigh quotient is exact to the
+// SQUARE of the basis' error (1e-12 lambda_max).  n <= 128; grid (n, batch).
+__global__ __launch_bounds__(256) void rate_rayleigh_kernel(int n, const float2 *Gpart, long long sGt, int nsplit, long long sGs,
+                                                            const float2 *U, double *lam)
+{
+    const int c = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    __shared__ double ur[128], ui[128], red[8];
+    const float2 *u = U + ((size_t)t * n + c) * n;
+    for (int i = tid; i < n; i += 256) { ur[i] = u[i].x; ui[i] = u[i].y; }
+    __syncthreads();
+    double num = 0.0, den = 0.0;
+    const float2 *G = Gpart + (long long)t * sGt;
+    for (int e = tid; e < n * n; e += 256) {
+        const int i = e % n, j = e / n;
+        double gx = 0.0, gy = 0.0;
+        for (int s = 0; s < nsplit; ++s) {
+            const float2 g = G[(long long)s * sGs + e];
+            gx += g.x; gy += g.y;
+        }
+        num += ur[i] * (gx * ur[j] - gy * ui[j]) + ui[i] * (gx * ui[j] + gy * ur[j]);      // Re(conj(u_i) g_ij u_j)
+    }
+    for (int i = tid; i < n; i += 256) den += ur[i] * ur[i] + ui[i] * ui[i];
+    for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o); den += __shfl_xor(den, o); }
+    if ((tid & 63) == 0) { red[tid >> 6] = num; red[4 + (tid >> 6)] = den; }
+    __syncthreads();
+    if (tid == 0) lam[(size_t)t * n + c] = ((red[0] + red[1]) + (red[2] + red[3])) / ((red[4] + red[5]) + (red[6] + red[7]));
+}
+
+// rate[t] = sum_i log2(1 + lam_i / (R (noise_var + e)))   (plot_rateVSframelength.m:81: log2 det(I + Zbar Zbar'/(R (..))));
+// lam: the eigenvalues of the Gram of the scaled Zbar (score_scale_kernel, rate_rayleigh_kernel), brought back in double
+__global__ __launch_bounds__(256) void rate_kernel(int batch, int n, int R, const double *lam, const float *num,
+                                                   const float *den, const uint32_t *mx, double noise_var, double *rate)
 {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= batch) return;
-    const double e = (double)num[t] / (double)den[t];
+    const double e = score_e(t, num, den, mx);
     const double c = 1.0 / ((double)R * (noise_var + e));
+    const int ez2 = 2 * score_exp(mx[2 * t + 1]);
     double acc = 0.0;
-    for (int i = 0; i < n; ++i) acc += log2(1.0 + fmax((double)lam[(long long)t * n + i], 0.0) * c);
+    // A negative eigenvalue of a Gram is rounding noise, and the noise of the near-zero eigenvalues has either sign with a sum the
+    // trace pins down: while |lam c| is small the negative terms are kept, so that they cancel the positive noise to first order
+    // (clamping them all to 0 left a bias: 2.6e-5 of the rate at 128 x 600 with a rank-4 Zbar); larger negative terms are clamped.
+    for (int i = 0; i < n; ++i) {
+        const double x = ldexp(lam[(long long)t * n + i], ez2) * c;
+        acc += log2(1.0 + ((x < 0.0 && !(x > -0x1p-10)) ? 0.0 : x));
+    }
     rate[t] = acc;
 }
 
@@ -160,10 +312,38 @@ static dim3 grid2(long long n, int batch)
     return dim3((unsigned)blocks, (unsigned)batch);
 }
 
-static int check_common(jstsp_ctx *ctx, int memspace)
+// D = S - Zbar and a copy of Zbar, each trial scaled by its own power of two (mx: 2 * batch words, see score_absmax_kernel)
+static int score_operands(jstsp_ctx *ctx, long long n, int batch, const float2 *S, const float2 *Zb, uint32_t *mx, float2 *D, float2 *Zs)
 {
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    dim3 g = grid2(n, batch);
+    g.y = (unsigned)std::min(batch, 65535);
+    JSTSP_HIP(hipMemsetAsync(mx, 0, (size_t)2 * batch * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(score_absmax_kernel, g, dim3(256), 0, ctx->stream, n, batch, S, Zb, mx);
+    hipLaunchKernelGGL(score_scale_kernel, g, dim3(256), 0, ctx->stream, n, batch, S, Zb, mx, D, Zs);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+// sigma_max^2 for the scoring entries.  Orders above 128 take the block Jacobi WITH its basis (EIG_VECS) and the Rayleigh quotient of
+// the leading column against the original Gram (score_top_rayleigh_kernel), where the EIG_LMAX mode of sigma_max_sq returns the diagonal of a matrix that went
+// through (blocks - 1) x sweeps two-sided fp32 updates - 3e-6 relative per lambda_max, up to 1.05e-5 on an NMSE near 1 (129 x 140,
+// 300 trials), against the 2e-6 the project asserts there.  U: batch * n * n, lam: batch * n (n = w.n > 128 only).
+static int score_sigma_max_sq(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, float2 *U, float *lam, float *out)
+{
+    if (w.n <= 128) return sigma_max_sq(ctx, w, Z, out);
+    const long long sG = (long long)w.n * w.n;
+    JSTSP_TRY(gram_partials(ctx, w, Z, (long long)w.rows * w.cols));
+    JSTSP_TRY(launch_eig(ctx, EIG_VECS, w.n, w.batch, w.Gpart, sG * w.nsplit, w.nsplit, sG, nullptr, nullptr, U, lam, nullptr));
+    hipLaunchKernelGGL(score_top_rayleigh_kernel, dim3(w.batch), dim3(256), 0, ctx->stream, w.n, w.Gpart, sG * w.nsplit, w.nsplit, sG, U, lam, out);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+
+static int check_common(jstsp_ctx *ctx, int memspace, const char *what = nullptr)
+{
+    const char *pre = what ? what : "", *sep = what ? ": " : "";
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s%sctx is NULL", pre, sep);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s%sbad memspace %d", pre, sep, memspace);
     return 0;
 }
 
@@ -474,33 +654,36 @@ int jstsp_svt_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32 *Y_
 int jstsp_nmse_spectral_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S_,
                             const jstsp_c32 *Zbar_, double *nmse, int memspace)
 {
-    JSTSP_TRY(check_common(ctx, memspace));
+    JSTSP_TRY(check_common(ctx, memspace, "nmse"));
     JSTSP_ENTER(ctx);
     JSTSP_REQUIRE(S_ && Zbar_ && nmse, JSTSP_E_NULL, "nmse: NULL argument");
     JSTSP_REQUIRE(R > 0 && C > 0 && batch > 0, JSTSP_E_SHAPE, "nmse: bad shape");
     JSTSP_REQUIRE(std::min(R, C) <= 2048, JSTSP_E_UNSUPPORTED, "nmse: min(R, C) = %d > 2048", std::min(R, C));
     const size_t n = (size_t)R * C;
-    size_t need = GramWS::bytes(R, C, batch, false) + rnd256(batch * n * sizeof(float2)) +
-                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double));
+    size_t need = GramWS::bytes(R, C, batch, false) + 2 * rnd256(batch * n * sizeof(float2)) +
+                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double)) + rnd256((size_t)2 * batch * sizeof(uint32_t));
+    const int ng = std::min(R, C);
+    const bool big = ng > 128;                  // (block Jacobi with its basis: score_sigma_max_sq)
+    if (big) need += rnd256((size_t)batch * ng * ng * sizeof(float2)) + rnd256((size_t)batch * ng * sizeof(float));
     if (memspace == JSTSP_HOST) need += 2 * rnd256(batch * n * sizeof(float2));
     JSTSP_TRY(ctx->arena.reserve(need));
     ctx->arena.reset();
     const float2 *S, *Zb;
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(S_), batch * n, memspace, &S));
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Zbar_), batch * n, memspace, &Zb));
-    float2 *D = ctx->arena.get<float2>(batch * n);
+    float2 *D = ctx->arena.get<float2>(batch * n), *Zs = ctx->arena.get<float2>(batch * n);
+    uint32_t *mx = ctx->arena.get<uint32_t>((size_t)2 * batch);
     float *num = ctx->arena.get<float>(batch), *den = ctx->arena.get<float>(batch);
     double *o = ctx->arena.get<double>(batch);
-    JSTSP_REQUIRE(D && num && den && o, JSTSP_E_NOMEM, "nmse: workspace exhausted");
+    float2 *U = big ? ctx->arena.get<float2>((size_t)batch * ng * ng) : nullptr;
+    float *lam = big ? ctx->arena.get<float>((size_t)batch * ng) : nullptr;
+    JSTSP_REQUIRE(D && Zs && mx && num && den && o && (!big || (U && lam)), JSTSP_E_NOMEM, "nmse: workspace exhausted");
     GramWS w;
     JSTSP_TRY(w.alloc(ctx->arena, R, C, batch, false));
-    const long long tot = (long long)batch * n;
-    hipLaunchKernelGGL(diff_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0,
-                       ctx->stream, tot, S, Zb, D);
-    JSTSP_TRY(sigma_max_sq(ctx, w, D, num));
-    JSTSP_TRY(sigma_max_sq(ctx, w, Zb, den));
-    hipLaunchKernelGGL(ratio_cap_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx->stream, batch, num, den,
-                       o, 1, 1ll, 0ll);
+    JSTSP_TRY(score_operands(ctx, (long long)n, batch, S, Zb, mx, D, Zs));
+    JSTSP_TRY(score_sigma_max_sq(ctx, w, D, U, lam, num));
+    JSTSP_TRY(score_sigma_max_sq(ctx, w, Zs, U, lam, den));
+    hipLaunchKernelGGL(score_nmse_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx->stream, batch, num, den, mx, o);
     JSTSP_HIP(hipGetLastError());
     JSTSP_TRY(stage_out(ctx, nmse, o, (size_t)batch, memspace));
     if (memspace == JSTSP_HOST) JSTSP_HIP(hipStreamSynchronize(ctx->stream));
@@ -546,16 +729,16 @@ int jstsp_rate_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S_,
     // log2(real(det(eye(Nr) + 1/Nr*Zbar*Zbar'*1/(noise_var + norm(Zbar-S)^2/norm(Zbar)^2))))  (plot_rateVSframelength.m:81)
     // = sum_i log2(1 + lambda_i(Zbar Zbar') / (Nr (noise_var + e))): the eigenvalues of the Gram of the smaller side
     // (det(I + c Z Z') = det(I + c Z' Z)); the NMSE e is NOT capped in that script.
-    JSTSP_TRY(check_common(ctx, memspace));
+    JSTSP_TRY(check_common(ctx, memspace, "rate"));
     JSTSP_ENTER(ctx);
     JSTSP_REQUIRE(S_ && Zbar_ && rate, JSTSP_E_NULL, "rate: NULL argument");
     JSTSP_REQUIRE(R > 0 && C > 0 && batch > 0, JSTSP_E_SHAPE, "rate: bad shape");
     JSTSP_REQUIRE(std::min(R, C) <= 128, JSTSP_E_UNSUPPORTED, "rate: min(R, C) = %d > 128", std::min(R, C));
     const size_t n = (size_t)R * C;
     const int ng = std::min(R, C), ne = (ng + 1) & ~1;
-    size_t need = GramWS::bytes(R, C, batch, false) + rnd256(batch * n * sizeof(float2)) +
-                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double)) +
-                  rnd256((size_t)batch * ng * ng * sizeof(float2)) + rnd256((size_t)batch * ng * sizeof(float)) +
+    size_t need = GramWS::bytes(R, C, batch, false) + 2 * rnd256(batch * n * sizeof(float2)) +
+                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double)) + rnd256((size_t)2 * batch * sizeof(uint32_t)) +
+                  rnd256((size_t)batch * ng * ng * sizeof(float2)) + rnd256((size_t)batch * ng * sizeof(float)) + rnd256((size_t)batch * ng * sizeof(double)) +
                   rnd256((size_t)batch * ne * ne * sizeof(float2));
     if (memspace == JSTSP_HOST) need += 2 * rnd256(batch * n * sizeof(float2));
     JSTSP_TRY(ctx->arena.reserve(need));
@@ -563,24 +746,25 @@ int jstsp_rate_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S_,
     const float2 *S, *Zb;
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(S_), batch * n, memspace, &S));
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Zbar_), batch * n, memspace, &Zb));
-    float2 *D = ctx->arena.get<float2>(batch * n);
+    float2 *D = ctx->arena.get<float2>(batch * n), *Zs = ctx->arena.get<float2>(batch * n);
+    uint32_t *mx = ctx->arena.get<uint32_t>((size_t)2 * batch);
     float *num = ctx->arena.get<float>(batch), *den = ctx->arena.get<float>(batch);
     double *o = ctx->arena.get<double>(batch);
     float2 *U = ctx->arena.get<float2>((size_t)batch * ng * ng);
     float *lam = ctx->arena.get<float>((size_t)batch * ng);
+    double *lamd = ctx->arena.get<double>((size_t)batch * ng);
     float2 *Vg = eig_needs_global_v(ng) ? ctx->arena.get<float2>((size_t)batch * ne * ne) : nullptr;
-    JSTSP_REQUIRE(D && num && den && o && U && lam && (!eig_needs_global_v(ng) || Vg), JSTSP_E_NOMEM, "rate: workspace exhausted");
+    JSTSP_REQUIRE(D && Zs && mx && num && den && o && U && lam && lamd && (!eig_needs_global_v(ng) || Vg), JSTSP_E_NOMEM, "rate: workspace exhausted");
     GramWS w;
     JSTSP_TRY(w.alloc(ctx->arena, R, C, batch, false));
-    const long long tot = (long long)batch * n;
-    hipLaunchKernelGGL(diff_kernel, dim3((unsigned)std::min<long long>((tot + 255) / 256, 4096)), dim3(256), 0,
-                       ctx->stream, tot, S, Zb, D);
+    JSTSP_TRY(score_operands(ctx, (long long)n, batch, S, Zb, mx, D, Zs));
     JSTSP_TRY(sigma_max_sq(ctx, w, D, num));
-    JSTSP_TRY(sigma_max_sq(ctx, w, Zb, den));                     // leaves the Gram partials of Zbar in the workspace
+    JSTSP_TRY(sigma_max_sq(ctx, w, Zs, den));                     // leaves the Gram partials of the scaled Zbar in the workspace
     const long long sG = (long long)w.n * w.n;
     JSTSP_TRY(launch_eig(ctx, EIG_VECS, w.n, batch, w.Gpart, sG * w.nsplit, w.nsplit, sG, nullptr, nullptr, U, lam, Vg));
-    hipLaunchKernelGGL(rate_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx->stream, batch, w.n, R, lam, num, den,
-                       noise_var, o);
+    hipLaunchKernelGGL(rate_rayleigh_kernel, dim3(w.n, batch), dim3(256), 0, ctx->stream, w.n, w.Gpart, sG * w.nsplit, w.nsplit, sG, U, lamd);
+    hipLaunchKernelGGL(rate_kernel, dim3((batch + 255) / 256), dim3(256), 0, ctx->stream, batch, w.n, R, lamd, num, den,
+                       mx, noise_var, o);
     JSTSP_HIP(hipGetLastError());
     JSTSP_TRY(stage_out(ctx, rate, o, (size_t)batch, memspace));
     if (memspace == JSTSP_HOST) JSTSP_HIP(hipStreamSynchronize(ctx->stream));
