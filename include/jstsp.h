@@ -1000,6 +1000,80 @@ int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int bat
                            const int32_t *indx_S,
                            jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace);
 
+/* ---- resuming and warm-starting the float64 ADMM (csrc/proposed64.hip) -------------------------------
+ * The state of the iteration (proposed_algorithm.m:8-12, :27) as an argument: a solve can be split into legs, continued by a
+ * caller who watches convergence_error, or started from the iterate of another problem (the previous frame of a slowly varying
+ * channel).
+ *  - layout: one trial's state is one contiguous block of jstsp_c64, column-major, [X | V1 | V2 | C] (N M each) then [v | S]
+ *    (Gr G2 each); jstsp_admm_state_elems(N, M, Gr, G2) = 4 N M + 2 Gr G2 is its length and the stride between trials (0 for a
+ *    shape that is not positive).  S is stored, not recomputed from v: in _angles the mask depends on the iteration index.
+ *    The state lives in the call's memspace.
+ *  - jstsp_proposed_resume_f64 / jstsp_proposed_std_resume_f64 take the arguments of jstsp_proposed_algorithm_f64 /
+ *    jstsp_proposed_std_f64 and, in front of memspace, it0, state_in, state_out.  The call runs iterations it0 + 1 ... it0 + Imax
+ *    of the reference loop from state_in and, when state_out is not NULL, writes the state after the last of them.
+ *    state_in == NULL: from zero, and it0 must be 0 (JSTSP_E_ARG otherwise) - the bits of the sibling.  it0 < 0, or it0 + Imax
+ *    beyond int: JSTSP_E_ARG.  Limits and error codes are otherwise those of the sibling.
+ *  - ce_out: Imax x 3 x batch, the rows of the iterations THIS call ran.  Row 1, column 3 is |dv|^2 / |v_prev|^2 with the loaded
+ *    v: finite when v != 0, Inf or NaN exactly as proposed_algorithm.m:51 makes it otherwise.  'std' keeps the column 0.
+ *  - _angles: the mask of iteration it of the call has min(10 + 5 (it0 + it), Gr G2) entries (angles :36).
+ *  - Xs = A S B is recomputed from the loaded S by the product the iteration uses.  'std' does not carry v (:53 recomputes it):
+ *    the v of state_in is ignored there, the v of state_out is that of the last iteration.
+ *  - state_out == state_in is allowed: the state is read whole before anything is written.  state_in is not modified otherwise.
+ *  - a non-finite value in one trial's state stays in that trial.
+ *  - The float64 solver carries nothing else between iterations: legs (a, b) return S, Y and the convergence_error rows of one
+ *    call with Imax = a + b, bit for bit, for min(N, M) <= 64; above, the note on the global Jacobi of
+ *    jstsp_proposed_algorithm_f64 applies to a leg as it does to a call (the same batch gives the same bits).
+ *  - A JSTSP_HOST call stages the state with the other arrays: one staged solve.
+ *  - jstsp_proposed_resume_c32: the same for the fp32 solver, jstsp_proposed_algorithm_c32's arguments plus it0, state_in, state_out
+ *    (jstsp_c32, the same layout and stride).  What differs from the float64 entries:
+ *      . the fp32 loop never stores C (after every iteration C == -V2): state_out holds C = -V2, and a state_in with C != -V2 - any
+ *        state that is not an iterate of its own problem - is honoured in the first iteration through D = C + V2 (csrc/resume.hip).
+ *      . not carried: the warm-started Jacobi basis of the svt and the Lanczos Ritz vectors (both start cold, as in a call from
+ *        zero), the phase of the R v refresh (R v is recomputed from the loaded v in the call's first iteration), and the operand
+ *        maxima (taken from the loaded data).  A split fp32 solve is therefore fp32-equivalent to the uninterrupted one, NOT
+ *        bit-identical; state_in == NULL, it0 == 0 runs jstsp_proposed_algorithm_c32's code on one stream-ordered solve.
+ *      . a trial whose k scale overflows in the fused pass is solved again from its state_in at it0 (jstsp_last_fused_fallbacks).
+ *      . a JSTSP_HOST call is ONE staged solve: the two-halves host pipeline of jstsp_proposed_algorithm_c32 is not used.
+ *    jstsp_proposed_resume_c64 is that entry at the reference's element type: every array, the state included, is narrowed to the
+ *    fp32 solver and widened back as jstsp_proposed_algorithm_c64 does (the MEX command 'proposed_algorithm_resume' binds it).
+ *    There is no _begin / _end pair for a resumed call.
+ * Asserted (tests/test_gpu_resume64.py): splits of Imax = 6 against the siblings in bits, with and without indx_S; from an
+ * arbitrary state S and Y within 1e-10 of max|ref| and convergence_error within 1e-8 of tests/resume_ref.py. */
+size_t jstsp_admm_state_elems(int N, int M, int Gr, int G2);
+int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                              const jstsp_c32 *subY, const float *Omega,
+                              const jstsp_c32 *A, long long strideA,
+                              const jstsp_c32 *B, long long strideB,
+                              int Imax, const double *tau_Y, const double *tau_S,
+                              const double *rho, int type, const int32_t *indx_S,
+                              jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out,
+                              int it0, const jstsp_c32 *state_in, jstsp_c32 *state_out, int memspace);
+int jstsp_proposed_resume_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                              const jstsp_c64 *subY, const double *Omega,
+                              const jstsp_c64 *A, long long strideA,
+                              const jstsp_c64 *B, long long strideB,
+                              int Imax, const double *tau_Y, const double *tau_S,
+                              const double *rho, int type, const int32_t *indx_S,
+                              jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                              int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace);
+int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                              const jstsp_c64 *subY, const double *Omega,
+                              const jstsp_c64 *A, long long strideA,
+                              const jstsp_c64 *B, long long strideB,
+                              int Imax, const double *tau_Y, const double *tau_S,
+                              const double *rho, int type, const int32_t *indx_S,
+                              jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                              int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace);
+int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                                  const jstsp_c64 *subY, const double *Omega,
+                                  const jstsp_c64 *A, long long strideA,
+                                  const jstsp_c64 *B, long long strideB,
+                                  const jstsp_c64 *PA, const jstsp_c64 *PB,
+                                  int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                                  const int32_t *indx_S,
+                                  jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out,
+                                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace);
+
 /* ---- joint OMP and matrix completion in float64 -----------------------------------------------------
  * The "OMP with MMV" column (plot_errorVSsnr.m:116-117) and the TSSR / "SVT-based" recipe (:151-162) evaluated in FLOAT64 on the
  * device - unlike jstsp_mmv_omp_c64 / jstsp_mc_svt_c64 / jstsp_mc_admm_c64, which narrow the same arrays to the fp32 kernels.

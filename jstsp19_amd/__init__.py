@@ -12,6 +12,8 @@ from .solvers import (OMP, sparse_sca_estim, cawgn_estim_out, gradient_head, ls_
                       proposed_algorithm_f64, proposed_algorithm_angles_f64, svt_f64, correlate_f64, synthesize_f64,
                       pinv_f64, ls_estimate_f64, mmv_omp_f64, mc_svt_f64, mc_admm_f64, tssr_f64,
                       OMP_f64, omp_kron_f64, sparse_admm_f64, proposed_algorithm_std_f64, proposed_algorithm_angles_std_f64,
-                      svd_f64, lowrank_f64, svd_tall_f64, lowrank_tall_f64, nmse_spectral_f64, rate_f64)
+                      svd_f64, lowrank_f64, svd_tall_f64, lowrank_tall_f64, nmse_spectral_f64, rate_f64,
+                      admm_state_elems, proposed_algorithm_resume_f64, proposed_algorithm_std_resume_f64,
+                      proposed_algorithm_resume, proposed_algorithm_angles_resume)
 
 __version__ = "0.1.0"

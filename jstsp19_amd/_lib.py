@@ -144,6 +144,12 @@ SIGNATURES["jstsp_proposed_std_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c
                                                 c_void_p, c_ll, c_void_p, c_void_p, c_int, c_dp, c_dp, c_dp, c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_int])
 
+# the float64 ADMM resumed from a saved state (csrc/proposed64.hip): the sibling's list with it0, state_in, state_out before memspace
+SIGNATURES["jstsp_admm_state_elems"] = (C.c_size_t, [c_int, c_int, c_int, c_int])
+for _n, _sib in (("jstsp_proposed_resume_f64", "jstsp_proposed_algorithm_f64"), ("jstsp_proposed_std_resume_f64", "jstsp_proposed_std_f64"),
+                 ("jstsp_proposed_resume_c32", "jstsp_proposed_algorithm_c32"), ("jstsp_proposed_resume_c64", "jstsp_proposed_algorithm_c64")):
+    SIGNATURES[_n] = (c_int, SIGNATURES[_sib][1][:-1] + [c_int, c_void_p, c_void_p, c_int])
+
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes
     # (pointers are void* here, so the two are one list)

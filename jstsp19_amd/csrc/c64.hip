@@ -304,6 +304,30 @@ int jstsp_proposed_algorithm_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     return 0;
 }
 
+// jstsp_proposed_resume_c32 at the reference's element type: the state is narrowed and widened with the other arrays (one staged
+// solve in either memspace; state_out may be state_in - the narrowed copy is what the solver reads)
+int jstsp_proposed_resume_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY, const double *Omega,
+                              const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB, int Imax, const double *tau_Y,
+                              const double *tau_S, const double *rho, int type, const int32_t *indx_S, jstsp_c64 *S_out, jstsp_c64 *Y_out,
+                              double *ce_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+{
+    C64_BEGIN(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, "proposed_algorithm resume");
+    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "proposed_algorithm resume: NULL argument");
+    const size_t nm = (size_t)N * M * batch, ne = (4 * (size_t)N * M + 2 * (size_t)Gr * G2) * batch;
+    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch), *b = cv.in_dict(B, (size_t)G2 * M, strideB, batch),
+                    *si = cv.in(state_in, ne);
+    const float *om = cv.in_real(Omega, nm);
+    const int32_t *ix = cv.in_raw(indx_S, (size_t)Gr * G2 * batch);
+    jstsp_c32 *s = cv.out(S_out, (size_t)Gr * G2 * batch), *yo = cv.out(Y_out, nm), *so = cv.out(state_out, ne);
+    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
+    JSTSP_TRY(cv.rc);
+    JSTSP_TRY(jstsp_proposed_resume_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S, rho, type, ix, s, yo, ce,
+                                        it0, si, so, JSTSP_DEVICE));
+    JSTSP_TRY(cv.finish());
+    if (memspace == JSTSP_HOST && type != JSTSP_TYPE_APPROXIMATE) JSTSP_TRY(diag_check_host(ctx, "proposed_algorithm 'std'"));
+    return 0;
+}
+
 int jstsp_svt_c64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y, const double *tau, jstsp_c64 *X,
                   int memspace)
 {

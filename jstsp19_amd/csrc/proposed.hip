@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
+#include <climits>
 
 namespace jstsp {
 
@@ -158,7 +159,8 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                          long long strideB, int Imax, const double *tau_Y,
                          const double *tau_S, const double *rho, int type,
                          const int32_t *indx_S_, jstsp_c32 *S_out, jstsp_c32 *Y_out,
-                         double *ce_out, int memspace, bool allow_fused, std::vector<int> *overflowed, PendingSolve *defer = nullptr)
+                         double *ce_out, int memspace, bool allow_fused, std::vector<int> *overflowed, PendingSolve *defer = nullptr,
+                         int it0 = 0, const jstsp_c32 *state_in = nullptr, jstsp_c32 *state_out = nullptr)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
     JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL,
@@ -216,6 +218,10 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         if (angles) need += rnd256(batch * g * sizeof(int32_t));
         need += rnd256(compact_elems * sizeof(float2));
     }
+    // a resumed call (jstsp_proposed_resume_c32): subY + rho D of its first iteration (resume.hip), the staged state of a host call
+    const size_t ne = 4 * nm + 2 * g;
+    if (state_in) need += rnd256(batch * nm * sizeof(float2));
+    if (memspace == JSTSP_HOST) need += (state_in ? rnd256(batch * ne * sizeof(float2)) : 0) + (state_out ? rnd256(batch * ne * sizeof(float2)) : 0);
     JSTSP_TRY(ctx->arena.reserve(need));
     ctx->arena.reset();
 
@@ -267,6 +273,24 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     if (angles) JSTSP_TRY(launch_rank_from_index(ctx, (int)g, batch, indx_S, w.rank));
 
     const Mat Am{A, strideA, N}, Bm{B, strideB, G2};
+    // a resumed call: the iterate from the caller's state instead of zeros, Xs = A S B from the loaded S.  The loop does not carry
+    // C (C == -V2): where its first X / K update is an epilogue, w.C holds D = C + V2 and subY1 = subY + rho D (resume.hip)
+    const float2 *sin = nullptr, *subY1 = subY;
+    float2 *sout = nullptr;
+    const bool explicit_c = !w.gz.left;             // (the element-wise update of that orientation takes C as an operand)
+    if (state_in) {
+        JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(state_in), batch * ne, memspace, &sin));
+        float2 *sy1 = explicit_c ? nullptr : ctx->arena.get<float2>(batch * nm);
+        JSTSP_REQUIRE(explicit_c || sy1, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (resumed state)");
+        JSTSP_TRY(launch_resume_unpack(ctx, (long long)nm, (long long)g, batch, sin, w.X, w.V1, w.V2, w.C, w.V, w.S, subY, sy1, w.prm, explicit_c));
+        if (!explicit_c) subY1 = sy1;
+        JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, Gr, batch, Am, Mat{w.S, (long long)g, Gr}, w.W, (long long)ng, N));
+        JSTSP_TRY(gemm(ctx, 'N', 'N', N, M, G2, batch, Mat{w.W, (long long)ng, N}, Bm, w.Xs, (long long)nm, N, 1.f, nullptr, 0, 0, 0.f, GEMM_SYNTH));
+    }
+    if (state_out) {
+        sout = memspace == JSTSP_DEVICE ? reinterpret_cast<float2 *>(state_out) : ctx->arena.get<float2>(batch * ne);
+        JSTSP_REQUIRE(sout, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (resumed state)");
+    }
     // JSTSP_TOEPLITZ (fused.hip): 0 - the dictionary is taken as unstructured; 1 - a block-Toeplitz one gets the compact HBM image
     // of the fused pass (bit-identical results); 2 (default) - also the window kernel for block height 64 (fp32-equivalent, not
     // bit-identical)
@@ -505,7 +529,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
             GemmDesc dq = make_gemm('N', 'N', N, M, N, batch, Mat{w.gz.Q, (long long)N * N, N}, Mat{Zc, snm, N}, w.Y, snm, N);
             dq.epi = EPI_UPDATE_X; dq.prm = w.prm;
             dq.e_rw0 = w.V1; dq.e_w1 = w.X; dq.e_w2 = w.ZK;
-            dq.e_r0 = w.V2; dq.e_r2 = w.Xs; dq.e_r3 = subY; dq.e_f0 = w.invD;
+            dq.e_r0 = w.V2; dq.e_r2 = w.Xs; dq.e_r3 = (sin && it == 0) ? subY1 : subY; dq.e_f0 = w.invD;
             dq.e_w3 = (it + 1 < Imax && (!zfly || fusedy)) ? Zn : nullptr;      // (the fused pass reads the stored Z)
             if (zfly && it > 0) { dq.B = w.X; dq.B2 = w.V1; }      // Z = X - V1/rho in the panel loader (it == 0: Z = 0 in Zc)
             dq.epi_store_c = (it + 1 == Imax);          // Y itself is only an output of the last iteration
@@ -514,6 +538,10 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                 if (N <= 64) { dq.amax_x = w.nmax; dq.amax_v1 = w.nmax + batch; dq.amax_z = w.zmax; }
             }
             JSTSP_TRY(launch_cgemm(ctx, dq, GEMM_MISC));
+            if (sin && it == 0) {                       // k = [k with C = -V2] - D, and its maximum again (resume.hip)
+                JSTSP_TRY(launch_resume_fix_k(ctx, (long long)(batch * nm), w.ZK, w.C));
+                if (w.h2) JSTSP_TRY(hgemm_absmax(ctx, w.ZK, snm, snm, batch, w.kmax));
+            }
         } else {
             JSTSP_TRY(svt_apply(ctx, w.gz, Zc, w.Y));
             // -- sub 2 + k of sub 3 + V1 dual update                                        (:38-43,:64)
@@ -592,7 +620,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         } else
         JSTSP_TRY(gemm(ctx, 'N', 'C', N, G2, M, batch, Mat{w.ZK, snm, N}, Bm, w.Tc, sng, N, 1.f, nullptr, 0, 0,
                        0.f, GEMM_CORRELATE));
-        const long long cnt_ll = std::min<long long>(10 + 5ll * (it + 1), (long long)g);
+        const long long cnt_ll = std::min<long long>(10 + 5ll * ((long long)it0 + it + 1), (long long)g);
         // (G_A X) G_B: the G2 x G2 factor is packed once per solve; max|G_A X| comes from the first product's epilogue.
         // exact (R v itself is being formed from v): with the low-order parts of both Grams (see the setup above), the first factor
         // on the f16 pipe with G_A = hi + lo (hsmall.hip), the second as the fp32-MFMA product with fp64 master accumulators against
@@ -684,7 +712,7 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         // -- Xs = A S B                                                                      (:58)
         // (the last iteration of a two-output call on the fused path: Xs only feeds X, V2 and convergence_error, none of which
         //  is returned - S is final, Y was stored by the last pass)
-        if (fusedp && !want_ce && it + 1 == Imax) break;
+        if (fusedp && !want_ce && it + 1 == Imax && !sout) break;       // (a call that returns its state needs the last V2)
         if (w.h2) {
             GemmDesc dw = make_gemm('N', 'N', N, G2, Gr, batch, Am, Mat{w.S, sg, Gr}, w.W, sng, N);
             dw.amax_out = w.wmax;                       // max|A S| for the split-f16 synthesis
@@ -757,6 +785,10 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(S_out), w.S, batch * g, memspace));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Y_out), w.Y, batch * nm, memspace));
     if (want_ce && Imax > 0) JSTSP_TRY(stage_out(ctx, ce_out, w.ce, (size_t)batch * 3 * Imax, memspace));
+    if (sout) {
+        JSTSP_TRY(launch_resume_pack(ctx, (long long)nm, (long long)g, batch, w.X, w.V1, w.V2, explicit_c ? w.C : nullptr, w.V, w.S, sout));
+        if (memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(state_out), sout, batch * ne, memspace));
+    }
     if (fusedp && overflowed) {
         // Trials in which an entry of k left the f16 range of the scale predicted for it (growth beyond 2^(2 + kback) from
         // one iteration to the next): their results are wrong from that pass on.  The caller re-solves exactly those.
@@ -871,6 +903,65 @@ extern "C" int jstsp_proposed_algorithm_c32(jstsp_ctx *ctx, int N, int M, int Gr
                                  Y_out, ce_out, memspace, &fallbacks));
     ctx->fused_fallbacks += fallbacks;
     return 0;
+}
+
+// ---- resumed from a saved state (include/jstsp.h) ---------------------------------------------------------------------------------
+// Iterations it0 + 1 ... it0 + Imax from state_in.  One staged solve in either memspace (no two-halves host pipeline).  A trial
+// whose k scale overflowed in a pass is solved again from ITS state_in at it0 by the three-kernel iteration; state_in is read
+// again for that, so when the caller lets state_out be state_in a copy is taken first.
+extern "C" int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
+                                         const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
+                                         const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
+                                         jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, int it0, const jstsp_c32 *state_in,
+                                         jstsp_c32 *state_out, int memspace)
+{
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0, JSTSP_E_SHAPE, "proposed_algorithm resume: bad shape");
+    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int",
+                  it0, Imax);
+    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", it0);
+    ctx->fused_fallbacks = 0; ctx->last_dict_block = 0;
+    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ne = 4 * nm + 2 * g;
+    // state_out == state_in: the re-solve below needs the state the call started from
+    const jstsp_c32 *sin = state_in;
+    jstsp_c32 *keep_dev = nullptr;
+    std::vector<jstsp_c32> keep_host;
+    if (state_in && state_in == state_out) {
+        if (memspace == JSTSP_HOST) { keep_host.assign(state_in, state_in + (size_t)batch * ne); sin = keep_host.data(); }
+        else {
+            JSTSP_ENTER(ctx);
+            JSTSP_HIP(hipMallocAsync((void **)&keep_dev, (size_t)batch * ne * sizeof(jstsp_c32), ctx->stream));
+            const hipError_t e = hipMemcpyAsync(keep_dev, state_in, (size_t)batch * ne * sizeof(jstsp_c32), hipMemcpyDeviceToDevice, ctx->stream);
+            if (e != hipSuccess) {
+                (void)hipFreeAsync(keep_dev, ctx->stream);
+                set_error("proposed_algorithm resume: copying the state failed: %s", hipGetErrorString(e));
+                return (int)e;
+            }
+            sin = keep_dev;
+        }
+    }
+    std::vector<int> ovf;
+    int rc = proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, S_out, Y_out,
+                           ce_out, memspace, true, &ovf, nullptr, it0, sin, state_out);
+    int fallbacks = 0;
+    for (size_t i = 0; !rc && i < ovf.size();) {
+        size_t j = i + 1;
+        while (j < ovf.size() && ovf[j] == ovf[j - 1] + 1) ++j;
+        const int t0 = ovf[i], cnt = (int)(j - i);
+        rc = proposed_impl(ctx, N, M, Gr, G2, cnt, subY + t0 * nm, Omega + t0 * nm, A + (size_t)t0 * strideA, strideA, B + (size_t)t0 * strideB, strideB,
+                           Imax, tau_Y + t0, tau_S + t0, rho + t0, type, indx_S ? indx_S + t0 * g : nullptr, S_out + t0 * g,
+                           Y_out ? Y_out + t0 * nm : nullptr, ce_out ? ce_out + (size_t)t0 * 3 * Imax : nullptr, memspace, false, nullptr, nullptr, it0,
+                           sin ? sin + t0 * ne : nullptr, state_out ? state_out + t0 * ne : nullptr);
+        fallbacks += cnt;
+        i = j;
+    }
+    if (keep_dev) {
+        JSTSP_ENTER(ctx);
+        (void)hipFreeAsync(keep_dev, ctx->stream);
+    }
+    ctx->fused_fallbacks = fallbacks;
+    return rc;
 }
 
 // ---- the two-phase form for device arrays (include/jstsp.h) ---------------------------------------------------------------------

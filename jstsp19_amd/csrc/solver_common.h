@@ -69,6 +69,14 @@ int svt_prepare(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, const TrialPar
                 bool gram_done = false);   // gram_done: the partials of G are already in the workspace
                 // Z2 (split-f16 Gram path only): the svt argument is Z - prm[t].irho * Z2, never stored
 int svt_apply(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, float2 *Y);
+
+// resume.hip: the state block of a resumed proposed_algorithm call to and from the solver's arrays, and K -= D of its first iteration
+int launch_resume_unpack(jstsp_ctx *ctx, long long nm, long long g, int batch, const float2 *state, float2 *X, float2 *V1, float2 *V2, float2 *Cb,
+                         float2 *V, float2 *S, const float2 *subY, float2 *subY1, const TrialParams *prm, bool explicit_c);
+int launch_resume_fix_k(jstsp_ctx *ctx, long long n, float2 *K, const float2 *D);
+int launch_resume_pack(jstsp_ctx *ctx, long long nm, long long g, int batch, const float2 *X, const float2 *V1, const float2 *V2, const float2 *Cb,
+                       const float2 *V, const float2 *S, float2 *state);
+
 // Gram partials of problems [t0, t0 + count) only (same workspace layout as gram_partials).
 int gram_partials_range(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, long long sZt, int t0, int count,
                         const uint32_t *amax = nullptr, const float2 *Z2 = nullptr,

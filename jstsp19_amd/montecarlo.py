@@ -543,12 +543,16 @@ def _hip_alg12(inp, Imax):
     return out
 
 
-def _hip_alg12_f64(inp, Imax_list, score="host"):
+def _hip_alg12_f64(inp, Imax_list, score="host", resume=False):
     """``_hip_alg12`` in float64 for every Imax of the list on ONE batch of trials: ``pinv_f64(A)`` and ``pinv_f64(B)`` are
     computed once and serve the least-squares step of every Alg. 1 solve (``proposed_algorithm_std_f64(..., PA=, PB=)``) and
     the scoring product ``pinv(A)*Y*pinv(B)`` of both columns (on the f64 matrix pipe: ``correlate_f64`` with the adjoints of
     the factors).  Alg. 2 is ``proposed_algorithm_f64``; the columns are scored by ``_score_f64``.  Returns one
-    ``(e_std, e_approx)`` per Imax.  ``score="device"``: scored by ``nmse_spectral_f64`` on the device instead."""
+    ``(e_std, e_approx)`` per Imax.  ``score="device"``: scored by ``nmse_spectral_f64`` on the device instead.
+    ``resume=True``: one solve per algorithm instead of one per Imax - the list is stepped through in ascending order with the
+    ADMM state carried (``proposed_algorithm_resume_f64`` / ``proposed_algorithm_std_resume_f64``; 10 / 30 / 50 is 10, then
+    20 more, then 20 more: 50 iterations instead of 90).  The float64 solver carries nothing but that state, so the columns
+    are those of ``resume=False`` bit for bit."""
     from . import solvers as J
     _check_score(score)
     score_f64 = _scorer_f64(score)
@@ -558,6 +562,17 @@ def _hip_alg12_f64(inp, Imax_list, score="host"):
     prm = (inp["tau_X"].numpy(), inp["tau_S"].numpy(), inp["rho"].numpy())
     PA, PB = J.pinv_f64(A), J.pinv_f64(B)
     PAh, PBh = J.colmajor(PA.mH), J.colmajor(PB.mH)
+    if resume:
+        out, it0, st1, st2, e = [None] * len(Imax_list), 0, None, None, None
+        for k in sorted(range(len(Imax_list)), key=lambda k: int(Imax_list[k])):
+            more = int(Imax_list[k]) - it0
+            if more > 0:                                    # (an Imax listed twice is scored once)
+                _, Y1, _, st1 = J.proposed_algorithm_std_resume_f64(subY, Om, A, B, more, *prm, PA=PA, PB=PB, want_ce=False, state=st1, it0=it0)
+                _, Y2, _, st2 = J.proposed_algorithm_resume_f64(subY, Om, A, B, more, *prm, want_ce=False, state=st2, it0=it0)
+                e = tuple(score_f64(J.correlate_f64(Y, PAh, PBh), zb, "nmse", 0.0) for Y in (Y1, Y2))
+                it0 += more
+            out[k] = e
+        return out
     out = []
     for Imax in Imax_list:
         _, Y1, _ = J.proposed_algorithm_std_f64(subY, Om, A, B, int(Imax), *prm, PA=PA, PB=PB, want_ce=False)     # :60
@@ -566,7 +581,7 @@ def _hip_alg12_f64(inp, Imax_list, score="host"):
     return out
 
 
-def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed, device, dist, builder, score="host"):
+def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed, device, dist, builder, score="host", resume=False):
     """``run_approx_sweep(precision="f64")``: the (SNR, trial) pairs are sharded over ranks; a batch of trials is built once and
     solved for every Imax (its Philox key is the sweep index of the point (SNR, Imax_list[0]) of the default sweep, so that
     column sees the realisations the fp32 sweep sees)."""
@@ -585,7 +600,7 @@ def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed
             inp = build_trials_training(p, t0, t1 - t0, seed=seed, sweep_idx=si * nI, device=device)
         else:
             inp = builder(p, range(t0, t1), seed, si * nI, device, False)
-        for ii, (e1, e2) in enumerate(_hip_alg12_f64(inp, Imax_list, score)):
+        for ii, (e1, e2) in enumerate(_hip_alg12_f64(inp, Imax_list, score, resume)):
             acc[si, ii, 0] += float(e1.sum())
             acc[si, ii, 1] += float(e2.sum())
             acc[si, ii, 2] += t1 - t0
@@ -599,7 +614,7 @@ def _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, *, batch, seed
 
 
 def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, batch=64, seed=20190913, device=None,
-                     solve_fn=None, dist=None, builder=None, precision="f32", score="host"):
+                     solve_fn=None, dist=None, builder=None, precision="f32", score="host", resume=False):
     """The Alg.1-vs-Alg.2 sweep of plot_errorVSsnr_approx.m:34-85: for each SNR and each Imax, ``n_trials`` fresh
     realisations of wideband_hybBF_comm_system_training, both solver variants, capped NMSE of
     ``pinv(A)*Y*pinv(B)``, mean then ``min(., 1)`` (:76-77).
@@ -615,9 +630,14 @@ def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, 
     Imax of the list, so that ``pinv_f64(A)`` and ``pinv_f64(B)`` are computed once per batch (``_hip_alg12_f64``).  No
     ``solve_fn`` hook.  ``score="device"`` scores the float64 columns on the device (``nmse_spectral_f64``) instead of by
     ``_score_f64`` on the host; it changes nothing at ``precision="f32"``.
+    ``resume=True`` (opt-in, ``precision="f64"`` only): each batch is solved once per algorithm, stepping through the sorted
+    ``Imax_list`` with the ADMM state carried, instead of once per Imax from zero; the result is that of ``resume=False`` bit
+    for bit (``_hip_alg12_f64``).
     """
     if precision not in ("f32", "f64"):
         raise ValueError("precision must be 'f32' or 'f64'")
+    if resume and precision != "f64":
+        raise ValueError("resume=True steps the float64 solvers through Imax_list: it needs precision='f64'")
     _check_score(score)
     if precision == "f64" and solve_fn is not None:
         raise ValueError("precision='f64' solves with the library's float64 entries: no solve_fn")
@@ -628,7 +648,7 @@ def run_approx_sweep(base: TrainingParams, snr_db_list, Imax_list, n_trials, *, 
     builder = _resolve_builder(builder, device)
     if precision == "f64":
         return _run_approx_sweep_f64(base, snr_db_list, Imax_list, n_trials, batch=batch, seed=seed, device=device, dist=dist,
-                                     builder=builder, score=score)
+                                     builder=builder, score=score, resume=resume)
     if solve_fn is None:
         solve_fn = _hip_alg12
     pts = [(si, ii) for si in range(len(snr_db_list)) for ii in range(len(Imax_list))]    # loop order of :34-38

@@ -32,7 +32,9 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "proposed_algorithm_f64", "proposed_algorithm_angles_f64", "svt_f64", "correlate_f64", "synthesize_f64",
            "pinv_f64", "ls_estimate_f64", "mmv_omp_f64", "mc_svt_f64", "mc_admm_f64", "tssr_f64",
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
-           "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64"]
+           "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64",
+           "admm_state_elems", "proposed_algorithm_resume_f64", "proposed_algorithm_std_resume_f64",
+           "proposed_algorithm_resume", "proposed_algorithm_angles_resume"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -187,6 +189,66 @@ def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approxi
     check(rc, "jstsp_proposed_algorithm_c32")
     sq = not a_sub.batched
     return fS(sq), fY(sq), (fce(sq) if want_ce else None)
+
+
+def proposed_algorithm_resume(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None, want_ce=True, ctx=None,
+                              state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm` resumed from a saved state (include/jstsp.h: jstsp_proposed_resume_c32): iterations
+    ``it0 + 1 ... it0 + Imax`` of the reference loop from ``state``.  Returns ``(S, Y, ce, state)``; ``ce`` holds the rows of this
+    call, ``state`` is complex64 ``(batch, admm_state_elems(N, M, Gr, G2))`` (always two-dimensional; ``None`` with
+    ``return_state=False``), a new array of the kind of the inputs.  ``state=None``: from zero (``it0`` must be 0).  A split fp32
+    solve is fp32-equivalent to the uninterrupted one, not bit-identical (the header says what is not carried)."""
+    a_sub = _Arg(subY, np.complex64, "subY")
+    a_om = _Arg(Omega, np.float32, "Omega")
+    a_A = _Arg(A, np.complex64, "A")
+    a_B = _Arg(B, np.complex64, "B")
+    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
+    Gr, G2 = a_A.C, a_B.R
+    Imax, it0 = int(Imax), int(it0)
+    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
+        raise ValueError("Omega must have the shape of subY")
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+    if type not in ("approximate", "std"):
+        raise ValueError("type must be 'approximate' or 'std'")
+    if it0 < 0 or (state is None and it0 != 0):
+        raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
+    ne = 4 * N * M + 2 * Gr * G2
+    p_in, keep_in = _state_arg(state, batch, ne, DEVICE if a_sub.torch else HOST, getattr(a_sub, "device", None), np.complex64)
+    a_ix = _indx_arg(indx_S, batch, Gr * G2)
+    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
+    sA = _shared_stride(a_A, N * Gr, batch, "A")
+    sB = _shared_stride(a_B, G2 * M, batch, "B")
+    tY, ptY = _scalars(tau_Y, batch, "tau_Y")
+    tS, ptS = _scalars(tau_S, batch, "tau_S")
+    rh, prh = _scalars(rho, batch, "rho")
+    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex64, dev)
+    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex64, dev)
+    pce, fce = _out(mem == DEVICE, batch, Imax, 3, np.float64, dev) if want_ce else (None, None)
+    p_out, st_out = None, None
+    if return_state:
+        if mem == DEVICE:
+            import torch
+            st_out = torch.empty((batch, ne), dtype=torch.complex64, device=dev)
+            p_out = st_out.data_ptr()
+        else:
+            st_out = np.empty((batch, ne), dtype=np.complex64)
+            p_out = st_out.ctypes.data
+    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
+    rc = c._lib.jstsp_proposed_resume_c32(c.handle, N, M, Gr, G2, batch, a_sub.ptr, a_om.ptr, a_A.ptr, sA, a_B.ptr, sB, Imax, ptY, ptS, prh,
+                                          tcode, a_ix.ptr, pS, pY, pce, it0, p_in, p_out, mem)
+    check(rc, "jstsp_proposed_resume_c32")
+    del keep_in
+    sq = not a_sub.batched
+    return fS(sq), fY(sq), (fce(sq) if want_ce else None), st_out
+
+
+def proposed_algorithm_angles_resume(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type="approximate", greedy_nnz=None, *,
+                                     want_ce=True, ctx=None, state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm_angles` resumed from a saved state (see :func:`proposed_algorithm_resume`): the mask of the call's
+    iteration ``it`` has ``min(10 + 5 (it0 + it), Gr G2)`` entries."""
+    return proposed_algorithm_resume(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type, indx_S=indx_S, want_ce=want_ce, ctx=ctx, state=state,
+                                     it0=it0, return_state=return_state)
 
 
 class PendingSolve:
@@ -956,6 +1018,122 @@ def proposed_algorithm_angles_std_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, ta
     """``proposed_algorithm_angles(..., 'std')`` in float64 on the device (see :func:`proposed_algorithm_std_f64`)."""
     return proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S=indx_S, PA=PA, PB=PB, want_ce=want_ce,
                                       info=info, ctx=ctx)
+
+
+# ----------------------------------------------------------------------------- float64 solver, resumed from a saved state
+def admm_state_elems(N, M, Gr, G2):
+    """Complex elements of one trial's ADMM state ``[X | V1 | V2 | C | v | S]`` (include/jstsp.h: jstsp_admm_state_elems)."""
+    return 4 * int(N) * int(M) + 2 * int(Gr) * int(G2)
+
+
+def _state_arg(state, batch, elems, mem, dev, np_dtype=np.complex128):
+    """``state`` ((batch, elems), or (elems,) for one problem; of the solver's complex type and of the kind of the other arrays) as
+    (pointer, keep-alive)."""
+    if state is None:
+        return None, None
+    if _is_torch(state) != (mem == DEVICE):
+        raise ValueError("state must be of the kind of the other arrays (numpy on the host path, torch CUDA on the device path)")
+    if tuple(state.shape) not in ((batch, elems), (elems,) if batch == 1 else None):
+        raise ValueError("state must have shape (%d, %d), got %s" % (batch, elems, tuple(state.shape)))
+    if mem == DEVICE:
+        import torch
+        want = torch.complex128 if np_dtype == np.complex128 else torch.complex64
+        if state.dtype != want or state.device != dev:
+            raise ValueError("state: expected a %s tensor on %s" % (want, dev))
+        buf = state.contiguous()
+        return buf.data_ptr(), buf
+    buf = np.ascontiguousarray(state, dtype=np_dtype)
+    return buf.ctypes.data, buf
+
+
+def _resume_f64(std, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, PA, PB, want_ce, ctx, state, it0, return_state):
+    """The resumed forms of :func:`proposed_algorithm_f64` (``std=False``) and :func:`proposed_algorithm_std_f64`."""
+    a_sub = _Arg(_wide(subY), np.complex128, "subY")
+    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
+    a_A = _Arg(_wide(A), np.complex128, "A")
+    a_B = _Arg(_wide(B), np.complex128, "B")
+    a_PA = _Arg(_wide(PA), np.complex128, "PA", allow_none=True)
+    a_PB = _Arg(_wide(PB), np.complex128, "PB", allow_none=True)
+    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
+    Gr, G2 = a_A.C, a_B.R
+    Imax, it0 = int(Imax), int(it0)
+    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
+        raise ValueError("Omega must have the shape of subY")
+    if a_A.R != N or a_B.C != M:
+        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+    for a_P, a_F, nmP in ((a_PA, a_A, "PA"), (a_PB, a_B, "PB")):
+        if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
+            raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
+    if it0 < 0 or (state is None and it0 != 0):
+        raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
+    a_ix = _indx_arg(indx_S, batch, Gr * G2)
+    sA = _shared_stride(a_A, N * Gr, batch, "A")
+    sB = _shared_stride(a_B, G2 * M, batch, "B")
+    tY, _ = _scalars(tau_Y, batch, "tau_Y")
+    tS, _ = _scalars(tau_S, batch, "tau_S")
+    rh, _ = _scalars(rho, batch, "rho")
+    ne = admm_state_elems(N, M, Gr, G2)
+    p_in, keep_in = _state_arg(state, batch, ne, DEVICE if a_sub.torch else HOST, getattr(a_sub, "device", None))
+    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_PA, a_PB, a_ix], ctx)
+    p_out, st_out = None, None
+    if return_state:
+        if mem == DEVICE:
+            import torch
+            st_out = torch.empty((batch, ne), dtype=torch.complex128, device=dev)
+            p_out = st_out.data_ptr()
+        else:
+            st_out = np.empty((batch, ne), dtype=np.complex128)
+            p_out = st_out.ctypes.data
+    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
+    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
+    pce, fce = _out(mem == DEVICE, batch, Imax, 3, np.float64, dev) if want_ce else (None, None)
+    # bytes of float64 state per trial: those of the sibling (whichever is larger) and the staged state blocks of a host call
+    n = min(N, M)
+    per = 16 * (8 * N * M + 5 * Gr * G2 + Gr * M + N * G2 + 20 * n * n + (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0))
+    if std:
+        per += 16 * ((2 * N * Gr + 3 * Gr * Gr if sA and a_PA.ptr is None else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and a_PB.ptr is None else 0))
+    if mem == HOST:
+        per += 16 * (2 * N * M + Gr * G2 + 2 * (G2 * M if sB else 0) + 2 * (N * Gr if sA else 0) + 2 * ne) + 8 * N * M
+    dp = C.POINTER(C.c_double)
+    for t0, nb in _f64_chunks(batch, per):
+        head = (c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
+                _off(a_B.ptr, t0 * sB, 16), sB)
+        prm = (Imax, tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp))
+        outs = (_off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * Imax, 8))
+        tail = (it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16), mem)
+        if std:
+            rc = c._lib.jstsp_proposed_std_resume_f64(*head, _off(a_PA.ptr, t0 * (Gr * N if sA else 0), 16),
+                                                      _off(a_PB.ptr, t0 * (M * G2 if sB else 0), 16), *prm, *outs, None, *tail)
+            check(rc, "jstsp_proposed_std_resume_f64")
+        else:
+            rc = c._lib.jstsp_proposed_resume_f64(*head, *prm, _lib.TYPE_APPROXIMATE, *outs, *tail)
+            check(rc, "jstsp_proposed_resume_f64")
+    del keep_in
+    sq = not a_sub.batched
+    return fS(sq), fY(sq), (fce(sq) if want_ce else None), st_out
+
+
+def proposed_algorithm_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None, want_ce=True, ctx=None,
+                                  state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm_f64` resumed from a saved state (include/jstsp.h: jstsp_proposed_resume_f64): iterations
+    ``it0 + 1 ... it0 + Imax`` of the reference loop from ``state``.  Returns ``(S, Y, ce, state)``: ``ce`` holds the ``Imax`` rows
+    this call ran, ``state`` - complex128 ``(batch, admm_state_elems(N, M, Gr, G2))``, a new array of the kind of the inputs, or
+    ``None`` with ``return_state=False`` - is what a later call takes to go on.  The state is always two-dimensional: for one
+    unbatched problem (``subY`` 2-D, where ``S``, ``Y`` and ``ce`` come back without the batch axis) it is ``(1, elems)``, one row per
+    trial as the C ABI lays it out; as an argument both ``(1, elems)`` and ``(elems,)`` are taken.  ``state=None``: from zero (``it0`` must be 0),
+    the bits of :func:`proposed_algorithm_f64`.  Legs (a, b) return the bits of one solve of ``a + b`` iterations.  The state
+    may come from another problem of the same shape (a warm start); ``it0`` then only sets the mask count of ``indx_S``."""
+    if type != "approximate":
+        raise ValueError("type must be 'approximate' (Alg. 1: proposed_algorithm_std_resume_f64)")
+    return _resume_f64(False, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, None, None, want_ce, ctx, state, it0, return_state)
+
+
+def proposed_algorithm_std_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, indx_S=None, PA=None, PB=None, want_ce=True, ctx=None,
+                                      state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm_std_f64` resumed from a saved state (include/jstsp.h: jstsp_proposed_std_resume_f64); arguments
+    and outputs as :func:`proposed_algorithm_resume_f64`, ``PA`` / ``PB`` as the sibling's.  Alg. 1 recomputes ``v`` in every
+    iteration: the ``v`` of ``state`` is ignored."""
+    return _resume_f64(True, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, PA, PB, want_ce, ctx, state, it0, return_state)
 
 
 def svt_f64(Y, tau, *, ctx=None):

@@ -223,6 +223,66 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (Y) plhs[1] = Y;
         if (ce) plhs[2] = ce;
         if (rcnd) plhs[3] = rcnd;
+    } else if (!strcmp(fn, "proposed_algorithm_resume_f64") || !strcmp(fn, "proposed_algorithm_resume")) {
+        // [S, Y, convergence_error, state] = proposed_algorithm_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type, indx_S, state, it0)
+        //   the float64 ADMM resumed from a saved state (jstsp_proposed_resume_f64; type 'std': jstsp_proposed_std_resume_f64):
+        //   iterations it0 + 1 ... it0 + Imax from `state`, jstsp_admm_state_elems x batch, or [] = from zero (it0 = 0)
+        // 'proposed_algorithm_resume': the same argument list on the fp32 solver (jstsp_proposed_resume_c64, both types)
+        const bool r64 = fn[strlen(fn) - 1] == '4';
+        check_nargs(fn, nrhs, 9, 12, nlhs, 4);
+        const Dims dy = dims_of(in[0]), dom = dims_of(in[1]), da = dims_of(in[2]), db = dims_of(in[3]);
+        const int N = dy.r, M = dy.c, batch = dy.b, Gr = da.c, G2 = db.r;
+        if (dom.r != N || dom.c != M || dom.b != batch || da.r != N || db.c != M)
+            mexErrMsgIdAndTxt("jstsp:shape", "%s: inconsistent dimensions", fn);
+        const jstsp_c64 *subY = cplx(in[0], fn, "subY"), *A = cplx(in[2], fn, "A"), *B = cplx(in[3], fn, "B");
+        const double *Om = real_of(in[1], fn, "Omega");
+        const long long sA = dict_stride(da, batch, fn, "A"), sB = dict_stride(db, batch, fn, "B");
+        const int Imax = (int)mxGetScalar(in[4]);
+        if (Imax < 1) mexErrMsgIdAndTxt("jstsp:args", "%s: Imax must be >= 1", fn);
+        const double *tY = scalars(in[5], batch, fn, "tau_Y"), *tS = scalars(in[6], batch, fn, "tau_S"),
+                     *rho = scalars(in[7], batch, fn, "rho");
+        char type[32] = "";
+        if (!mxIsChar(in[8]) || mxGetString(in[8], type, sizeof(type)) || (strcmp(type, "approximate") && strcmp(type, "std")))
+            mexErrMsgIdAndTxt("jstsp:args", "%s: type must be 'approximate' or 'std'", fn);
+        const bool std1 = !strcmp(type, "std");
+        const int32_t *idx = nullptr;
+        if (nrhs - 1 >= 10 && !mxIsEmpty(in[9])) {            // 1-based linear indices, doubles in MATLAB
+            const size_t n = mxGetNumberOfElements(in[9]);
+            if (n != (size_t)Gr * G2 * batch) mexErrMsgIdAndTxt("jstsp:shape", "%s: numel(indx_S) must be Gr*G2 per problem", fn);
+            const double *pi = real_of(in[9], fn, "indx_S");
+            const mwSize d1[2] = {(mwSize)n, 1};
+            mxArray *t = mxCreateNumericArray(2, d1, mxINT32_CLASS, mxREAL);
+            int32_t *q = (int32_t *)mxGetData(t);
+            for (size_t i = 0; i < n; ++i) q[i] = (int32_t)pi[i];
+            idx = q;
+        }
+        const size_t ne = jstsp_admm_state_elems(N, M, Gr, G2);
+        const jstsp_c64 *st_in = nullptr;
+        if (nrhs - 1 >= 11 && !mxIsEmpty(in[10])) {
+            if (mxGetNumberOfElements(in[10]) != ne * (size_t)batch)
+                mexErrMsgIdAndTxt("jstsp:shape", "%s: state must have 4*N*M + 2*Gr*G2 = %d elements per problem", fn, (int)ne);
+            st_in = cplx(in[10], fn, "state");
+        }
+        const int it0 = nrhs - 1 >= 12 ? (int)mxGetScalar(in[11]) : 0;
+        if (it0 < 0 || (!st_in && it0 != 0)) mexErrMsgIdAndTxt("jstsp:args", "%s: it0 must be >= 0, and 0 without a state", fn);
+        ensure_ctx();
+        plhs[0] = new_complex(Gr, G2, batch);
+        mxArray *Y = nlhs >= 2 ? new_complex(N, M, batch) : nullptr;
+        mxArray *ce = nlhs >= 3 ? new_real(Imax, 3, batch) : nullptr;
+        mxArray *so = nlhs >= 4 ? new_complex((int)ne, batch, 1) : nullptr;
+        const int rc = !r64 ? jstsp_proposed_resume_c64(g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, Imax, tY, tS, rho,
+                                                        std1 ? JSTSP_TYPE_STD : JSTSP_TYPE_APPROXIMATE, idx, c64(plhs[0]), Y ? c64(Y) : nullptr,
+                                                        ce ? mxGetDoubles(ce) : nullptr, it0, st_in, so ? c64(so) : nullptr, JSTSP_HOST)
+                     : std1 ? jstsp_proposed_std_resume_f64(g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, nullptr, nullptr, Imax, tY, tS, rho, idx,
+                                                            c64(plhs[0]), Y ? c64(Y) : nullptr, ce ? mxGetDoubles(ce) : nullptr, nullptr, it0, st_in,
+                                                            so ? c64(so) : nullptr, JSTSP_HOST)
+                            : jstsp_proposed_resume_f64(g_ctx, N, M, Gr, G2, batch, subY, Om, A, sA, B, sB, Imax, tY, tS, rho, JSTSP_TYPE_APPROXIMATE, idx,
+                                                        c64(plhs[0]), Y ? c64(Y) : nullptr, ce ? mxGetDoubles(ce) : nullptr, it0, st_in,
+                                                        so ? c64(so) : nullptr, JSTSP_HOST);
+        if (rc) fail(!r64 ? "jstsp_proposed_resume_c64" : std1 ? "jstsp_proposed_std_resume_f64" : "jstsp_proposed_resume_f64", rc);
+        if (Y) plhs[1] = Y;
+        if (ce) plhs[2] = ce;
+        if (so) plhs[3] = so;
     } else if (!strcmp(fn, "svt")) {
         // X = svt(Y, tau)     benchmark_algorithms/svt.m:1
         check_nargs(fn, nrhs, 2, 2, nlhs, 1);

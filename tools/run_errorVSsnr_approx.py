@@ -13,13 +13,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--trials", type=int, default=50)              # maxMCRealizations, :17
 ap.add_argument("--batch", type=int, default=50)
 ap.add_argument("--f64", action="store_true", help="evaluate and score both algorithms in float64")
+ap.add_argument("--resume", action="store_true", help="with --f64: one solve per algorithm, stepped through the sorted Imax list with the ADMM state carried (same bits)")
 ap.add_argument("--score-device", action="store_true", help="score the float64 columns (--f64) on the device (jstsp_nmse_spectral_f64 / jstsp_rate_f64) instead of on the host")
 a = ap.parse_args()
 base = TrainingParams(Nt=4, Nr=32, L=4, T=70, ratio=0.75)       # :8-19
 snrs = list(range(-15, 16, 5))                                  # :15
 imax = [10, 30, 50]                                             # :19
 t0 = time.perf_counter()
-out = run_approx_sweep(base, snrs, imax, a.trials, batch=a.batch, precision="f64" if a.f64 else "f32", score="device" if a.score_device else "host")
+out = run_approx_sweep(base, snrs, imax, a.trials, batch=a.batch, precision="f64" if a.f64 else "f32", score="device" if a.score_device else "host", resume=a.resume)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print("capped NMSE%s, %d trials/point, %.1f s" % (" (float64)" if a.f64 else "", a.trials, dt))
