@@ -576,6 +576,37 @@ int jstsp_build_trials_from_channel_c32(jstsp_ctx *ctx, const jstsp_model *model
                                         const jstsp_c32 *Hsrc, int ld_rows, int ld_cols, long long strideH, int normalize,
                                         const jstsp_trials *out, double *sigma_max, int memspace);
 
+/* The same construction for frame `frame` of a time-varying channel: trial t is a SEQUENCE of channels and `frame` the position in
+ * it - what a warm start of the ADMM (jstsp_proposed_resume_f64 / _c32) is measured on.  The geometry of a sequence is fixed and
+ * its path gains follow a first-order autoregression; one body with the two builders above (csrc/inputgen.hip).
+ *  - Geometry: u_r, u_t (wideband_mmwave_channel.m:20-24) are those of jstsp_build_trials_c32 for the same (seed, sweep_idx, trial),
+ *    on the bits, at every frame.
+ *  - Gains: let w_k[i] be the gain draw of jstsp_build_trials_c32 (wideband_mmwave_channel.m:19, 1/sqrt(2) (randn + 1j*randn), fp32) at Philox
+ *    element i + (k << 32) of the trial's gain stream, so that w_0 is that call's `gains`.  Then
+ *        g_f = corr^f w_0 + sqrt(1 - corr^2) * sum_{k=1..f} corr^(f-k) w_k,
+ *    the recursion g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f in closed form: every frame has the statistics of a drawn channel
+ *    (:19), and E[g_f conj(g_{f-k})] = corr^k.  Each component is accumulated in float64 in ascending k, one fma per term on the
+ *    widened fp32 draws with the coefficient pow(corr, f-k) (times sqrt(1 - corr^2) for k >= 1) in float64, and rounded once to
+ *    fp32.  A term whose coefficient is exactly zero is skipped: frame 0 returns the bits of w_0 for any corr, corr = 1 returns
+ *    w_0 at every frame, corr = 0 returns w_f.  A frame is a function of (seed, sweep_idx, trial, frame, corr) alone: of no earlier
+ *    call, of no batch and of no sharding.  COST: O(frame) Philox calls per gain, L*Np*batch gains per call.
+ *  - Channel: wideband_mmwave_channel.m:24-38 on (g_f, u_r, u_t), the kernel of jstsp_build_trials_c32 unchanged.
+ *  - Noise (plot_errorVSsnr.m:60), pilot symbols (:63-67) and Omega (proposed_hbf.m:36-40) of frame f are those of
+ *    jstsp_build_trials_c32 with the 64-bit sweep word sweep_idx + ((uint64_t)frame << 32) in the Philox key; with shared_pilots
+ *    the shared key is formed from the same word.  Frame 0 therefore IS jstsp_build_trials_c32: every array, on the bits.
+ *  - Everything after H (R, subY, Zbar, A, B, tau_Y / tau_Z / rho, indx_S, the *_hbf outputs) is the code of jstsp_build_trials_c32.
+ *  - out: gains returns g_f; u_r, u_t, noise, qam_idx, pilot_sym and H as in jstsp_build_trials_c32.
+ *  - JSTSP_E_ARG: corr outside [0, 1] or NaN, frame < 0 or frame > 65535; every other code as jstsp_build_trials_c32.  Nothing is
+ *    written before the arguments are accepted.
+ *  Asserted (tests/test_gpu_tracking.py): frame 0 equals the drawn call on the bits for corr in {0, 0.5, 1}; corr = 1 keeps gains,
+ *  H, Zbar and indx_S of frame 0 while noise, pilots, Omega and subY change; g_f within 2^-23 max|g| of the float64 recursion run
+ *  on the innovations the corr = 0 calls return; the oracle's tolerances of jstsp_build_trials_c32 downstream of (g_f, u_r, u_t);
+ *  a trial's arrays do not depend on the batch it is built in nor on the memspace; |g_f|^2 and the lag correlations corr^k within
+ *  5 sigma over 4096 sequences. */
+int jstsp_build_trials_tracked_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx,
+                                   long long trial0, int batch, int frame, double corr,
+                                   const jstsp_trials *out, int memspace);
+
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
  * JSTSP_BF_QUANTIZED ('quantized') and JSTSP_BF_QUANTIZED4 ('quantized_4'): W (N x N, column-major, same memspace).  The

@@ -206,6 +206,12 @@ struct GivenChannel {
     double *sigma_max;
 };
 
+// a tracked channel: the arguments of jstsp_build_trials_tracked_c32 that place a frame in its sequence
+struct TrackedChannel {
+    int frame;
+    double corr;
+};
+
 // The cut and scale of a supplied channel for trials [trial0, trial0 + batch) (csrc/inputgen.hip), ONE implementation for the trial
 // builder and the spectrum sweep: checks the form of g (the error codes of jstsp_build_trials_from_channel_c32), reserves the
 // context's arena for caller_bytes plus its own arrays and resets it, computes norm(H_l) per tap, returns JSTSP_E_ILLCOND before

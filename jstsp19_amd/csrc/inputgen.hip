@@ -11,6 +11,8 @@
 //   plot_errorVSsnr.m:143           -> indx_S: stable descending sort of |vec(Zbar)| (64-bit keys, segmented radix sort)
 //   plot_errorVSsnr_nyuwireless.m:62-68 -> a channel the caller supplies instead of the drawn one (jstsp_build_trials_from_channel_c32):
 //                                      given_channel_sigma_kernel (norm(H_l), the non-finite / zero flag), given_channel_pack_kernel
+//   wideband_mmwave_channel.m:19-24 over a sequence of frames (jstsp_build_trials_tracked_c32) -> tracked_gain_kernel: fixed angles,
+//                                      gains by a first-order autoregression in closed form; channel_kernel on (g_f, u_r, u_t)
 //
 // Random numbers: Philox4x32-10, key = mix(seed, sweep index, global trial index), counter =
 // (element index, stream id) — a trial's inputs do not depend on the batch it is drawn in or
@@ -43,6 +45,34 @@ __global__ __launch_bounds__(256) void omega_kernel(Model m, uint64_t seed, uint
         }
         Omega[((size_t)t * m.Tp + j) * m.Mr_e + i] = rank < m.Mr ? 1.f : 0.f;
     }
+}
+
+// ---- gains of frame f of a tracked sequence (jstsp_build_trials_tracked_c32): the first-order autoregression
+//      g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f in closed form,
+//        g_f = corr^f w_0 + sqrt(1 - corr^2) sum_{k=1..f} corr^(f-k) w_k,
+//      w_k[i] the draw of draw_small_kernel (wideband_mmwave_channel.m:19) at Philox element i + (k << 32): w_0 is that kernel's
+//      gain.  Accumulated in float64 in ascending k, one fma per term and component on the widened fp32 draws, rounded once to
+//      fp32.  A term whose coefficient is exactly zero is skipped, so frame 0 and corr = 1 give the bits of w_0 and corr = 0
+//      gives w_f.  O(frame) Philox calls per gain; a gain is a function of (seed, sweep, trial, frame, corr) alone.
+//      Grid (ceil(L*Np / 64), batch), one gain per thread.
+__global__ __launch_bounds__(64) void tracked_gain_kernel(Model m, uint64_t seed, uint64_t sweep, long long trial0, int frame,
+                                                          double corr, float2 *gains)
+{
+    const int t = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= m.L * m.Np) return;
+    const uint64_t key = mix_key(seed, sweep, (uint64_t)(trial0 + t));
+    const double s = sqrt(1.0 - corr * corr);
+    double ax = 0.0, ay = 0.0;
+    for (int k = 0; k <= frame; ++k) {
+        const double c = (k == 0 ? 1.0 : s) * pow(corr, (double)(frame - k));
+        if (c == 0.0) continue;
+        const uint4 w = philox((uint64_t)i + ((uint64_t)k << 32), ST_GAIN, key);
+        const float2 g = normal2(w.x, w.y);
+        ax = fma(c, (double)(g.x * 0.70710678f), ax);
+        ay = fma(c, (double)(g.y * 0.70710678f), ay);
+        if (s == 0.0) break;                        // corr = 1: only w_0 has a coefficient
+    }
+    gains[(size_t)t * m.L * m.Np + i] = make_float2((float)ax, (float)ay);
 }
 
 // ---- dictionaries (trial-independent): Dr, Dt (wideband_mmwave_channel.m:9-10), ZC beamformer (createBeamformer.m:15-16)
@@ -268,15 +298,23 @@ template <class T> T *out_or_tmp(jstsp_ctx *ctx, T *user, size_t n, int memspace
     return ctx->arena.get<T>(n);
 }
 
-// The body of both builders.  given == NULL: the channel of wideband_mmwave_channel.m from the Philox draws (jstsp_build_trials_c32);
-// otherwise the caller's taps, cut and scaled (plot_errorVSsnr_nyuwireless.m:62-68) - draw_small_kernel and channel_kernel are then
-// not launched, and everything after Hmat is the same code.
+// The body of the three builders.  given == NULL: the channel of wideband_mmwave_channel.m from the Philox draws
+// (jstsp_build_trials_c32); otherwise the caller's taps, cut and scaled (plot_errorVSsnr_nyuwireless.m:62-68) - draw_small_kernel
+// and channel_kernel are then not launched.  tracked != NULL (with given == NULL): frame tracked->frame of a sequence whose geometry
+// is the drawn one and whose gains follow tracked_gain_kernel; noise, pilots and Omega take the frame into their sweep word.
+// Everything after Hmat is the same code.
 int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx, long long trial0, int batch,
-                      const GivenChannel *given, const jstsp_trials *out, int memspace)
+                      const GivenChannel *given, const TrackedChannel *tracked, const jstsp_trials *out, int memspace)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "build_trials: NULL context");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "build_trials: bad memspace");
     JSTSP_REQUIRE(mp && out, JSTSP_E_NULL, "build_trials: NULL argument");
+    if (tracked) {
+        JSTSP_REQUIRE(tracked->corr >= 0.0 && tracked->corr <= 1.0, JSTSP_E_ARG,                    // (a NaN fails both)
+                      "build_trials_tracked: corr must lie in [0, 1] (got %g)", tracked->corr);
+        JSTSP_REQUIRE(tracked->frame >= 0 && tracked->frame <= 65535, JSTSP_E_ARG,
+                      "build_trials_tracked: frame must lie in [0, 65535] (got %d)", tracked->frame);
+    }
     JSTSP_ENTER(ctx);
     Model m;
     m.Nt = mp->Nt; m.Nr = mp->Nr; m.L = mp->L; m.Tp = mp->T_prop; m.Mr = mp->Mr; m.Mr_e = mp->Mr_e;
@@ -360,13 +398,17 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     JSTSP_REQUIRE((given || (gains && u_r && u_t)) && noise && qam && psym && Dr && Dt && W && Hmat && Psi && R && WR && subY && Omega &&
                       A && (B || !out->B) && Zbar && T1 && hyp && lam,
                   JSTSP_E_NOMEM, "build_trials: workspace exhausted");
-    const uint64_t sw = (uint64_t)sweep_idx;
+    // the sequence (geometry, gain innovations) is keyed by the sweep index; what a frame draws anew by (sweep index, frame)
+    const uint64_t sw = (uint64_t)sweep_idx, swf = sw + ((uint64_t)(tracked ? tracked->frame : 0) << 32);
 
     // ---- draws ------------------------------------------------------------------------------
     if (!given) draw_small_kernel<<<batch, 64, 0, st>>>(m, seed, sw, trial0, gains, u_r, u_t);
-    draw_noise_qam_kernel<<<dim3(grid_for((long long)std::max(nR, nQ), 1024), batch), 256, 0, st>>>(m, seed, sw, trial0,
+    if (tracked)                                // (w_0 of draw_small_kernel is overwritten by g_f; frame 0: by its own bits)
+        tracked_gain_kernel<<<dim3((m.L * m.Np + 63) / 64, batch), 64, 0, st>>>(m, seed, sw, trial0, tracked->frame, tracked->corr,
+                                                                                 gains);
+    draw_noise_qam_kernel<<<dim3(grid_for((long long)std::max(nR, nQ), 1024), batch), 256, 0, st>>>(m, seed, swf, trial0,
                                                                                                       noise, qam, mp->shared_pilots, gauss, psym);
-    omega_kernel<<<dim3(m.Tp, batch), 256, (size_t)m.Mr_e * 4, st>>>(m, seed, sw, trial0, Omega);
+    omega_kernel<<<dim3(m.Tp, batch), 256, (size_t)m.Mr_e * 4, st>>>(m, seed, swf, trial0, Omega);
     // ---- dictionaries -------------------------------------------------------------------------
     dict_kernel<<<grid_for((long long)m.Nr * m.Gr), 256, 0, st>>>(m.Nr, m.Gr, 0, Dr);
     dict_kernel<<<grid_for((long long)m.Nt * m.Gt), 256, 0, st>>>(m.Nt, m.Gt, 0, Dt);
@@ -543,7 +585,15 @@ int jstsp::given_channel_hmat(jstsp_ctx *ctx, int Nr, int Nt, int L, long long t
 extern "C" int jstsp_build_trials_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
                                       long long trial0, int batch, const jstsp_trials *out, int memspace)
 {
-    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, out, memspace);
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, nullptr, out, memspace);
+}
+
+extern "C" int jstsp_build_trials_tracked_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
+                                              long long trial0, int batch, int frame, double corr, const jstsp_trials *out,
+                                              int memspace)
+{
+    const TrackedChannel tr{frame, corr};
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, &tr, out, memspace);
 }
 
 extern "C" int jstsp_build_trials_from_channel_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
@@ -552,5 +602,5 @@ extern "C" int jstsp_build_trials_from_channel_c32(jstsp_ctx *ctx, const jstsp_m
                                                    int memspace)
 {
     const GivenChannel g{reinterpret_cast<const float2 *>(Hsrc), ld_rows, ld_cols, strideH, normalize, sigma_max};
-    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, &g, out, memspace);
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, &g, nullptr, out, memspace);
 }

@@ -18,7 +18,7 @@ from .system_model import SweepParams, TrainingParams, ase_trials, build_trials,
 
 __all__ = ["partition", "run_sweep", "run_points", "sweep_points", "run_approx_sweep", "driver", "run_driver",
            "admmiters_points", "run_convergence_curves", "zy_points", "run_zy", "capacity_points", "capacity_designs",
-           "power_model", "run_capacity", "rank_points", "run_rank", "load_channel"]
+           "power_model", "run_capacity", "rank_points", "run_rank", "load_channel", "run_tracking"]
 
 
 def partition(n_items, world, rank):
@@ -871,3 +871,95 @@ def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, swee
     mean = _generic_sharded(points, n_trials, n_keep, lambda sv, p: sv, batch=batch, seed=seed, device=device, dist=dist,
                             builder=build).numpy()
     return mean, np.array([min(p.clusters * p.rays, p.L * p.Nt) if channel is None else p.L * p.Nt for p in points])
+
+
+TRACKING_MODES = ("cold", "warm", "warm_vs")
+
+
+def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
+                 precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None):
+    """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
+    tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
+    sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
+    ``g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f``, pilots, noise and sampling pattern of the frame's own - so SNR point
+    (``sweep_idx``) and frame vary independently and the result does not depend on ``batch``, the number of sequences built and
+    solved per call.
+
+    Per frame and sequence, at each Imax of ``imax`` (``cold`` also at ``cold_imax``), by ``proposed_algorithm_resume_f64`` and
+    ``nmse_spectral_f64`` (``precision="f64"``) or their fp32 siblings (``"f32"``):
+      cold     from zero
+      warm     from the previous frame's whole state [X | V1 | V2 | C | v | S]; each Imax is a chain of its own
+      warm_vs  from the previous frame's v and S only (X = V1 = V2 = C = 0)
+    States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
+    mode starts from zero, is not scored.  Single process: sequences are not sharded over ranks.
+
+    Returns the dictionary tools/run_tracking.py prints - per (mode, Imax) ``mean_nmse`` over the scored frames, ``sem_over_seqs``,
+    ``median_nmse``, ``mean_nmse_by_frame`` and ``estimates_per_s`` (solver time only, frame 0 left out) - plus
+    ``"channel": "device"``."""
+    import time
+    import numpy as np
+    from . import solvers as J
+    n_seqs, n_frames, batch, corr = int(n_seqs), int(n_frames), int(batch), float(corr)
+    imax = [int(i) for i in imax]
+    if n_seqs < 1 or n_frames < 2 or batch < 1:
+        raise ValueError("run_tracking needs n_seqs >= 1, n_frames >= 2 (frame 0 is not scored) and batch >= 1")
+    if not 0.0 <= corr <= 1.0:
+        raise ValueError("corr must lie in [0, 1], not %r" % (corr,))
+    if precision not in ("f64", "f32"):
+        raise ValueError("precision must be 'f64' or 'f32', not %r" % (precision,))
+    if not modes or any(m not in TRACKING_MODES for m in modes) or not imax or min(imax + [int(cold_imax)]) < 1:
+        raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (TRACKING_MODES,))
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    N, M, Gr, G2 = p.solver_shape
+    nm = N * M
+    f64 = precision == "f64"
+    wide = (lambda x: J.colmajor(x.to(torch.complex128))) if f64 else (lambda x: x)
+    solve = J.proposed_algorithm_resume_f64 if f64 else J.proposed_algorithm_resume
+    score = J.nmse_spectral_f64 if f64 else J.nmse_spectral
+    keys = [("cold", i) for i in sorted(set(imax + [int(cold_imax)])) if "cold" in modes] + \
+           [(m, i) for m in ("warm", "warm_vs") if m in modes for i in imax]
+    err = {k: [] for k in keys}                                     # per chunk: (scored frames, chunk) on the host
+    secs = {k: 0.0 for k in keys}
+    for t0 in range(0, n_seqs, batch):
+        nb = min(batch, n_seqs - t0)
+        state = {}
+        e_dev = {k: [] for k in keys}
+        for f in range(n_frames):
+            inp = build_trials(p, t0, nb, seed=seed, sweep_idx=sweep_idx, device=device, frame=f, corr=corr)
+            args = (wide(inp["subY"]), J.colmajor(inp["Omega"].to(torch.float64)) if f64 else inp["Omega"], wide(inp["A"]),
+                    wide(inp["B"]))
+            prm = (inp["tau_Y"].numpy(), inp["tau_Z"].numpy(), inp["rho"].numpy())
+            zb = wide(inp["Zbar"])
+            for k in keys:
+                mode, n_it = k
+                warm = mode != "cold"
+                st = state.get(k) if warm else None
+                if st is not None and mode == "warm_vs":
+                    st = st.clone()
+                    st[:, :4 * nm] = 0
+                torch.cuda.synchronize(device)
+                c0 = time.perf_counter()
+                S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm)
+                torch.cuda.synchronize(device)
+                dt = time.perf_counter() - c0
+                if warm:
+                    state[k] = out
+                if f:
+                    secs[k] += dt
+                    e_dev[k].append(torch.as_tensor(score(S, zb)).double())
+        for k in keys:
+            err[k].append(torch.stack(e_dev[k]).cpu().numpy())
+
+    def summary(k):
+        e = np.concatenate(err[k], axis=1)                          # (scored frames, seqs)
+        per_seq = e.mean(axis=0)
+        return {"mode": k[0], "Imax": k[1], "mean_nmse": float(e.mean()),
+                "sem_over_seqs": float(per_seq.std(ddof=1) / np.sqrt(len(per_seq))) if len(per_seq) > 1 else None,
+                "median_nmse": float(np.median(e)), "mean_nmse_by_frame": [float(x) for x in e.mean(axis=1)],
+                "estimates_per_s": n_seqs * (n_frames - 1) / secs[k]}
+
+    return {"tool": "run_tracking", "precision": precision, "shape": [N, M, Gr, G2], "frames": n_frames, "seqs": n_seqs, "corr": corr,
+            "clusters": p.clusters, "rays": p.rays, "snr_db": p.snr_db, "seed": seed, "scored_frames": list(range(1, n_frames)),
+            "cold_imax": int(cold_imax), "results": [summary(k) for k in keys], "channel": "device"}

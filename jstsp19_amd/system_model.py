@@ -163,7 +163,7 @@ def _channel_on_device(channel, device):
 
 def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, device=None, with_hbf=False,
                  want_draws=False, want_H=False, shared_pilots=False, ctx=None, pilots="qam4", channel=None,
-                 channel_normalize="reference"):
+                 channel_normalize="reference", frame=0, corr=None):
     """plot_errorVSsnr.m:57-136 for trials [trial0, trial0 + batch) on the HIP path
     (``jstsp_build_trials_c32``, csrc/inputgen.hip): draws, channel, pilots, measurement, A, B,
     hyper-parameters and indx_S are produced by the library's own kernels — nothing but the output
@@ -181,7 +181,17 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
     float64 ``(L,)`` or ``(batch, L)`` (left out where "asis" meets min(Nr, Nt) > 64, the one case the library needs no s
     for and cannot compute it); ``want_draws`` then adds noise, qam_idx and pilot_sym only - nothing else was drawn.  Noise,
     pilots and Omega are those of the drawn call with the same seed, sweep index and trial.
+
+    ``corr``: a float in [0, 1] makes trial t a SEQUENCE of channels and returns its frame ``frame`` (0..65535) by
+    ``jstsp_build_trials_tracked_c32``: the angles of the drawn call at every frame, the path gains
+    ``g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f`` (in closed form: a frame depends on no earlier call), noise, pilots and Omega of
+    the frame's own.  Frame 0 is the drawn call on the bits; ``want_draws`` returns the frame's ``gains``.  ``corr=None`` (the
+    default) is the drawn call and takes no ``frame``; ``corr`` with ``channel=`` is a ``ValueError``.
     """
+    if corr is not None and channel is not None:
+        raise ValueError("corr= (a tracked channel) and channel= (a supplied channel) exclude each other")
+    if corr is None and frame != 0:
+        raise ValueError("frame=%r needs corr=, the correlation of the sequence from one frame to the next" % (frame,))
     import ctypes as C
     import numpy as np
     from . import _lib
@@ -225,7 +235,11 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
         setattr(tr, k, v.data_ptr())
     for k, v in hyp.items():
         setattr(tr, k, v.ctypes.data_as(C.POINTER(C.c_double)))
-    if channel is None:
+    if corr is not None:
+        rc = c._lib.jstsp_build_trials_tracked_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0),
+                                                   int(batch), int(frame), float(corr), C.byref(tr), _lib.DEVICE)
+        _lib.check(rc, "jstsp_build_trials_tracked_c32")
+    elif channel is None:
         rc = c._lib.jstsp_build_trials_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0),
                                            int(batch), C.byref(tr), _lib.DEVICE)
         _lib.check(rc, "jstsp_build_trials_c32")

@@ -4,9 +4,14 @@ frames at BASELINE configs[1]'s shape (or --small: the reference's own driver sh
 wideband_mmwave_channel.m - clusters x rays paths whose Laplacian-distributed angles all delay taps share, cluster c weighted
 (C - c), H_l = A_r diag(g_l w / sqrt(Np)) A_t^H - with the angles fixed over the sequence and the path gains g_l following a
 first-order autoregression with coefficient `--corr` from one frame to the next (g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f,
-w_f ~ CN(0, 1): every frame's channel has the statistics of a drawn one).  It is generated on the host and fed through
-build_trials(..., channel=H, channel_normalize="asis"); every frame has pilots, noise and sampling pattern of its own (the sweep
-index is the frame).
+w_f ~ CN(0, 1): every frame's channel has the statistics of a drawn one).  Every frame has pilots, noise and sampling pattern of
+its own.  Two sources of the channel:
+  default           generated on the host by numpy and fed through build_trials(..., channel=H, channel_normalize="asis"); the
+                    sweep index is the frame
+  --device-channel  built by the library (jstsp_build_trials_tracked_c32 through montecarlo.run_tracking):
+                    Philox draws keyed by (seed, sweep index, sequence) and the frame, the sweep index free for the SNR point;
+                    states, estimates and scores stay on the device.  The two sources see different draws: their results agree
+                    statistically, not number by number.
 
 Per frame and sequence, in float64 (proposed_algorithm_resume_f64, nmse_spectral_f64; the default) or with --precision f32 by the
 fp32 solver (proposed_algorithm_resume, nmse_spectral: its estimates/s are the ones the headline is about), at each Imax of --imax (and --cold-imax):
@@ -38,9 +43,26 @@ ap.add_argument("--seed", type=int, default=20190913)
 ap.add_argument("--precision", choices=("f64", "f32"), default="f64")
 ap.add_argument("--small", action="store_true", help="Nt=4, Nr=32, L=4, T=35, Mr=4 instead of BASELINE configs[1]")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+ap.add_argument("--device-channel", action="store_true", help="frames built by the library (montecarlo.run_tracking)")
+ap.add_argument("--sweep-idx", type=int, default=0, help="--device-channel: the sweep index of the sequences' Philox key")
 a = ap.parse_args()
 
 p = SweepParams(Nt=4, Nr=32, L=4, T=35, Mr=4, snr_db=a.snr_db) if a.small else SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=a.snr_db)
+
+
+def emit(res):
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(res, indent=1) + "\n")
+
+
+if a.device_channel:
+    from jstsp19_amd.montecarlo import run_tracking
+    emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
+                      seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0")))
+    sys.exit(0)
+
 N, M, Gr, G2 = p.solver_shape
 nm, g = N * M, Gr * G2
 dev = torch.device("cuda:0")
@@ -106,8 +128,4 @@ def summary(m, i):
 res = {"tool": "run_tracking", "precision": a.precision, "shape": [N, M, Gr, G2], "frames": a.frames, "seqs": a.seqs, "corr": a.corr,
        "clusters": p.clusters, "rays": p.rays, "snr_db": a.snr_db, "seed": a.seed, "scored_frames": list(range(1, a.frames)),
        "cold_imax": a.cold_imax, "results": [summary(m, i) for m, i in modes if err[(m, i)]]}
-line = json.dumps(res)
-print(line)
-if a.out:
-    with open(a.out, "w") as fh:
-        fh.write(json.dumps(res, indent=1) + "\n")
+emit(res)
