@@ -607,6 +607,58 @@ int jstsp_build_trials_tracked_c32(jstsp_ctx *ctx, const jstsp_model *model, uin
                                    long long trial0, int batch, int frame, double corr,
                                    const jstsp_trials *out, int memspace);
 
+/* jstsp_build_trials_tracked_c32 with one addition: the angle of every path performs a random walk from frame to frame, so the
+ * support of Zbar moves across the dictionary grid - the case a warm start's inherited v, S does not fit.  A fourth channel source
+ * of the one body (csrc/inputgen.hip); jstsp_model and jstsp_trials are unchanged.
+ *  - Model: let phi_0[p] = beta*(e0 - cosh(u[p])) be the angle the drawn call forms from u_r or u_t (wideband_mmwave_channel.m:56-62).
+ *    Then phi_f[p] = phi_0[p] + drift * sum_{k=1..f} z_k[p]: drift is the standard deviation of one frame's increment, in radians;
+ *    the walk is independent per path and per array end (receive, transmit).  No mean reversion.
+ *  - Draws: z_k[p] is the first component of the Box-Muller pair on the Philox word at element p + (k << 32) of the trial's u_r
+ *    (receive) or u_t (transmit) stream - the second counter word is unused by these streams (Np < 2^32); element p at k = 0 stays
+ *    the uniform draw u.  The device of the gains above.
+ *  - Arithmetic: one thread per (path, end) sums the widened fp32 normals in float64 in ascending k and multiplies ONCE by drift
+ *    (the offsets are exactly linear in drift); the channel kernel adds the offset once to phi_0 in float64 and forms the steering
+ *    phase sincos(-pi*sin(-phi_f)*n) in float64 as before.  A frame is a function of (seed, sweep_idx, trial, frame, corr, drift)
+ *    alone: of no earlier call, of no batch and of no sharding.  COST: O(frame) Philox calls per angle, 2*Np*batch angles per call,
+ *    on top of the gains' O(frame).
+ *  - Channel: wideband_mmwave_channel.m:24-38 on (g_f, phi_f).  The drawn, tracked, capacity and spectrum paths launch the
+ *    kernel without the offsets and generate what they generated before.
+ *  - out: u_r, u_t are the drawn call's bits at every frame; gains is g_f of the tracked entry; everything after H is the shared
+ *    body, so indx_S is the frame's own true order.  dphi_r, dphi_t: Np x batch doubles each, in the memspace of the other arrays,
+ *    receive phi_f - phi_0; NULL = not wanted.
+ *  - Identities: drift == 0 at any frame returns every array of jstsp_build_trials_tracked_c32 on the bits; frame 0 at any drift
+ *    returns jstsp_build_trials_c32 on the bits; dphi_* compare equal to zero in both cases.
+ *  - JSTSP_E_ARG: drift < 0, NaN or Inf; corr and frame as jstsp_build_trials_tracked_c32 (the messages keep the prefix
+ *    build_trials_tracked).  Nothing is written before the arguments are accepted.
+ *  Asserted (tests/test_gpu_drift.py): the two identities on all 16 arrays; dphi(drift = s) == s * dphi(drift = 1) exactly, at
+ *  frame 65535 too; keyed by (seed, sweep, sequence, end), not by batch or memspace; H within 2e-6 of the float64 channel on
+ *  (gains, phi_0 + dphi) and the oracle's tolerances downstream; increments of mean 0, variance 1 and no correlation between
+ *  frames, ends, paths and sequences within 5 sigma over 4096 sequences; the refusals. */
+int jstsp_build_trials_tracked_drift_c32(jstsp_ctx *ctx, const jstsp_model *model, uint64_t seed, int sweep_idx,
+                                         long long trial0, int batch, int frame, double corr, double drift,
+                                         const jstsp_trials *out, double *dphi_r, double *dphi_t, int memspace);
+
+/* [~, indx] = sort(abs(vec(S)), 'descend') per trial (plot_errorVSsnr.m:143), for an S that is not the true channel's - the
+ * previous frame's estimate of a tracker - without leaving the device (csrc/support.hip).  S: Gr x G2 x batch, column-major;
+ * indx_S: (Gr*G2) x batch, 1-based, the layout every indx_S argument of the solvers takes.  The _f64 form reads interleaved
+ * (re, im) doubles, the memory of a jstsp_c64 array.
+ *  - Key: |z|^2 = x*x + y*y, in fp32 (_c32) or float64 (_f64).  Equal keys come in ascending index: the exact zeros of a
+ *    soft-thresholded S follow the non-zeros in index order.  A NaN key sorts before everything, +Inf next, as MATLAB's
+ *    descending sort does; NaNs tie with each other whatever their payload.
+ *  - _c32 forms its key with the device function of the trial builder (csrc/support_key.h) and sorts the same 64-bit words
+ *    (key above index) by the same segmented radix sort: support_order(Zbar) of a built trial is its indx_S on the bits.
+ *  - _f64: the keys alone are sorted; an entry's class is the first position of its key in its trial's sorted keys; the words
+ *    (class above index) are sorted.  No step relies on a stable sort.  One route per precision; an order is a function of its own
+ *    trial alone: of no batch and no memspace.  COST: one (_c32) or two (_f64) radix sorts of Gr*G2*batch 64-bit words.
+ *  - Workspace from the context's arena: 16 (_c32) or 24 (_f64) bytes per entry plus the sort's own, per chunk of at most
+ *    2^31 - 1 entries.  Both memspaces.
+ *  - JSTSP_E_SHAPE: a non-positive dimension or Gr*G2 >= 2^31; JSTSP_E_NULL: a NULL array.  Nothing is written then.
+ *  Asserted (tests/test_gpu_support_order.py): equal to the builder's indx_S on Zbar; exact against a stable host argsort of the
+ *  negated key on engineered ties, an all-zero trial, a NaN and an Inf, a 64 x 512 continuous trial and a solver's own sparse S, in
+ *  both precisions; independent of batch and memspace; proposed_algorithm_angles_f64 on it returns the bits of the builder's. */
+int jstsp_support_order_c32(jstsp_ctx *ctx, int Gr, int G2, int batch, const jstsp_c32 *S, int32_t *indx_S, int memspace);
+int jstsp_support_order_f64(jstsp_ctx *ctx, int Gr, int G2, int batch, const double *S, int32_t *indx_S, int memspace);
+
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
  * JSTSP_BF_QUANTIZED ('quantized') and JSTSP_BF_QUANTIZED4 ('quantized_4'): W (N x N, column-major, same memspace).  The

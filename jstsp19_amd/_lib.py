@@ -104,6 +104,10 @@ SIGNATURES = {
                                                     c_int, c_ll, c_int, C.POINTER(Trials), c_dp, c_int]),
     "jstsp_build_trials_tracked_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, c_int, C.c_double,
                                                C.POINTER(Trials), c_int]),
+    "jstsp_build_trials_tracked_drift_c32": (c_int, [c_void_p, C.POINTER(Model), C.c_uint64, c_int, c_ll, c_int, c_int, C.c_double,
+                                                     C.c_double, C.POINTER(Trials), c_void_p, c_void_p, c_int]),
+    "jstsp_support_order_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "jstsp_support_order_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     "jstsp_beamformer_c32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "jstsp_ase_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p,
                               c_int]),

@@ -3,6 +3,7 @@
 // and pilots for the same (seed, sweep, trial).
 #pragma once
 #include "solver_common.h"
+#include "support_key.h"
 
 namespace {
 
@@ -96,8 +97,11 @@ __global__ __launch_bounds__(256) void draw_noise_qam_kernel(Model m, uint64_t s
 
 // ---- channel: Hmat[t] = [H_1 ... H_L]  (Nr x Nt*L), H_l = 1/sqrt(Np) sum_p w_p g[l,p] a_r(p) a_t(p)^H
 //      with tap 1's steering vectors for every l (:24) and w_p = clusters - cluster(p) (:29)
-__global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gains, const float *u_r,
-                                                      const float *u_t, float2 *Hmat)
+//      DRIFT: the angle of path p is phi_0[p] + dphi[p] (jstsp_build_trials_tracked_drift_c32), one float64 addition; without it
+//      the offsets are not read and phi_0 is used as it is formed - the code of the drawn and the tracked channel, unchanged.
+template <bool DRIFT>
+__device__ __forceinline__ void channel_body(const Model &m, const float2 *gains, const float *u_r, const float *u_t,
+                                             const double *dphi_r, const double *dphi_t, float2 *Hmat)
 {
     extern __shared__ float2 sh[];
     float2 *ar = sh, *at = sh + (size_t)m.Nr * m.Np, *cf = at + (size_t)m.Nt * m.Np;
@@ -110,7 +114,8 @@ __global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gai
         const int dim = rx ? m.Nr : m.Nt;
         const int n = ii % dim, p = ii / dim;
         const double u = rx ? u_r[(size_t)t * m.Np + p] : u_t[(size_t)t * m.Np + p];
-        const double phi = beta * (e0 - cosh(u));                      // :56-62
+        double phi = beta * (e0 - cosh(u));                            // :56-62
+        if constexpr (DRIFT) phi = __dadd_rn(phi, (rx ? dphi_r : dphi_t)[(size_t)t * m.Np + p]);
         double s, c;
         sincos(-M_PI * sin(-phi) * (double)n, &s, &c);                 // :42-52
         (rx ? ar : at)[ii] = make_float2((float)c, (float)s);
@@ -137,6 +142,19 @@ __global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gai
         }
         Hmat[(size_t)t * n_el + e] = make_float2(hx, hy);
     }
+}
+
+__global__ __launch_bounds__(256) void channel_kernel(Model m, const float2 *gains, const float *u_r,
+                                                      const float *u_t, float2 *Hmat)
+{
+    channel_body<false>(m, gains, u_r, u_t, nullptr, nullptr, Hmat);
+}
+
+// the same on drifted angles: dphi_r, dphi_t hold phi_f - phi_0 per (trial, path), Np x batch doubles each
+__global__ __launch_bounds__(256) void channel_drift_kernel(Model m, const float2 *gains, const float *u_r, const float *u_t,
+                                                            const double *dphi_r, const double *dphi_t, float2 *Hmat)
+{
+    channel_body<true>(m, gains, u_r, u_t, dphi_r, dphi_t, Hmat);
 }
 
 inline int grid_for(long long n, int cap = 4096) { return (int)std::min<long long>((n + 255) / 256, cap); }
@@ -206,10 +224,14 @@ struct GivenChannel {
     double *sigma_max;
 };
 
-// a tracked channel: the arguments of jstsp_build_trials_tracked_c32 that place a frame in its sequence
+// a tracked channel: the arguments of jstsp_build_trials_tracked_c32 that place a frame in its sequence, and those of
+// jstsp_build_trials_tracked_drift_c32 that make its angles walk (drifting == 0: the geometry is fixed and the rest is not read)
 struct TrackedChannel {
     int frame;
     double corr;
+    int drifting;
+    double drift;
+    double *dphi_r, *dphi_t;
 };
 
 // The cut and scale of a supplied channel for trials [trial0, trial0 + batch) (csrc/inputgen.hip), ONE implementation for the trial

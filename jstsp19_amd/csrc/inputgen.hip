@@ -13,6 +13,8 @@
 //                                      given_channel_sigma_kernel (norm(H_l), the non-finite / zero flag), given_channel_pack_kernel
 //   wideband_mmwave_channel.m:19-24 over a sequence of frames (jstsp_build_trials_tracked_c32) -> tracked_gain_kernel: fixed angles,
 //                                      gains by a first-order autoregression in closed form; channel_kernel on (g_f, u_r, u_t)
+//   wideband_mmwave_channel.m:56-62 with angles that walk (jstsp_build_trials_tracked_drift_c32) -> drift_walk_kernel: phi_f - phi_0,
+//                                      channel_drift_kernel on (g_f, phi_f)
 //
 // Random numbers: Philox4x32-10, key = mix(seed, sweep index, global trial index), counter =
 // (element index, stream id) — a trial's inputs do not depend on the batch it is drawn in or
@@ -73,6 +75,29 @@ __global__ __launch_bounds__(64) void tracked_gain_kernel(Model m, uint64_t seed
         if (s == 0.0) break;                        // corr = 1: only w_0 has a coefficient
     }
     gains[(size_t)t * m.L * m.Np + i] = make_float2((float)ax, (float)ay);
+}
+
+// ---- angle offsets of frame f of a drifting sequence (jstsp_build_trials_tracked_drift_c32): a random walk per path and array
+//      end, phi_f = phi_0 + drift * sum_{k=1..f} z_k, z_k[p] the first component of normal2 on the Philox word at element
+//      p + (k << 32) of the stream ST_UR (receive) / ST_UT (transmit) - element p at k = 0 stays the uniform draw u of
+//      draw_small_kernel.  The widened fp32 normals are summed in float64 in ascending k and multiplied ONCE by drift, so the
+//      offsets are exactly linear in drift; the one addition to phi_0 is channel_drift_kernel's.  O(frame) Philox calls per angle;
+//      an offset is a function of (seed, sweep, trial, frame, drift) alone.  Grid (ceil(2*Np / 64), batch), one (path, end) per
+//      thread: i < Np receive, otherwise transmit.
+__global__ __launch_bounds__(64) void drift_walk_kernel(Model m, uint64_t seed, uint64_t sweep, long long trial0, int frame,
+                                                        double drift, double *dphi_r, double *dphi_t)
+{
+    const int t = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= 2 * m.Np) return;
+    const bool rx = i < m.Np;
+    const int p = rx ? i : i - m.Np;
+    const uint64_t key = mix_key(seed, sweep, (uint64_t)(trial0 + t));
+    double acc = 0.0;
+    for (int k = 1; k <= frame; ++k) {
+        const uint4 w = philox((uint64_t)p + ((uint64_t)k << 32), rx ? ST_UR : ST_UT, key);
+        acc += (double)normal2(w.x, w.y).x;
+    }
+    (rx ? dphi_r : dphi_t)[(size_t)t * m.Np + p] = drift * acc;
 }
 
 // ---- dictionaries (trial-independent): Dr, Dt (wideband_mmwave_channel.m:9-10), ZC beamformer (createBeamformer.m:15-16)
@@ -171,9 +196,7 @@ __global__ __launch_bounds__(256) void hyper_kernel(long long nm, long long nz, 
 __global__ __launch_bounds__(256) void sortkey_kernel(long long total, long long nz, const float2 *Zbar, uint64_t *keys)
 {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const float2 z = Zbar[i];
-        const float m2 = z.x * z.x + z.y * z.y;
-        keys[i] = ((uint64_t)(~__float_as_uint(m2)) << 32) | (uint64_t)(uint32_t)(i % nz);
+        keys[i] = ((uint64_t)support_key(Zbar[i]) << 32) | (uint64_t)(uint32_t)(i % nz);     // (support_key.h)
     }
 }
 __global__ __launch_bounds__(256) void sortidx_kernel(long long total, const uint64_t *keys, int32_t *indx)
@@ -302,6 +325,7 @@ template <class T> T *out_or_tmp(jstsp_ctx *ctx, T *user, size_t n, int memspace
 // (jstsp_build_trials_c32); otherwise the caller's taps, cut and scaled (plot_errorVSsnr_nyuwireless.m:62-68) - draw_small_kernel
 // and channel_kernel are then not launched.  tracked != NULL (with given == NULL): frame tracked->frame of a sequence whose geometry
 // is the drawn one and whose gains follow tracked_gain_kernel; noise, pilots and Omega take the frame into their sweep word.
+// tracked->drifting: the fourth source - the angles of that sequence walk (drift_walk_kernel) and channel_drift_kernel adds the offsets.
 // Everything after Hmat is the same code.
 int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx, long long trial0, int batch,
                       const GivenChannel *given, const TrackedChannel *tracked, const jstsp_trials *out, int memspace)
@@ -314,6 +338,8 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
                       "build_trials_tracked: corr must lie in [0, 1] (got %g)", tracked->corr);
         JSTSP_REQUIRE(tracked->frame >= 0 && tracked->frame <= 65535, JSTSP_E_ARG,
                       "build_trials_tracked: frame must lie in [0, 65535] (got %d)", tracked->frame);
+        JSTSP_REQUIRE(!tracked->drifting || (tracked->drift >= 0.0 && tracked->drift <= DBL_MAX), JSTSP_E_ARG,  // (a NaN fails both)
+                      "build_trials_tracked_drift: drift must be finite and >= 0 (got %g)", tracked->drift);
     }
     JSTSP_ENTER(ctx);
     Model m;
@@ -365,6 +391,8 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     need += GramWS::bytes(N, M, batch, true);
     if (out->indx_S) { acc(b * nZ * 8); acc(b * nZ * 8); acc(sort_tmp); acc((b + 1) * 8); acc(b * nZ * 4); }
     if (want_hbf) { acc(b * (size_t)m.Nr * Th * 8); acc((size_t)m.Nr * m.Gr * 8); acc(b * (size_t)m.G2 * Th * 8); }
+    const bool drifting = tracked && tracked->drifting;
+    if (drifting) { acc(b * m.Np * 8); acc(b * m.Np * 8); }
     // a supplied channel: given_channel_hmat checks its form, reserves the workspace with its own share on top, and decides the
     // refusals before any output is written
     float2 *Hgiven = nullptr;
@@ -395,6 +423,9 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     float2 *T1 = ar.get<float2>(b * (size_t)m.Gr * m.NtL);
     double *hyp = ar.get<double>(b * 3);
     float *lam = ar.get<float>(b * nG);
+    double *dphi_r = drifting ? out_or_tmp(ctx, tracked->dphi_r, b * m.Np, memspace) : nullptr,
+           *dphi_t = drifting ? out_or_tmp(ctx, tracked->dphi_t, b * m.Np, memspace) : nullptr;
+    JSTSP_REQUIRE(!drifting || (dphi_r && dphi_t), JSTSP_E_NOMEM, "build_trials: workspace exhausted");
     JSTSP_REQUIRE((given || (gains && u_r && u_t)) && noise && qam && psym && Dr && Dt && W && Hmat && Psi && R && WR && subY && Omega &&
                       A && (B || !out->B) && Zbar && T1 && hyp && lam,
                   JSTSP_E_NOMEM, "build_trials: workspace exhausted");
@@ -406,6 +437,9 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     if (tracked)                                // (w_0 of draw_small_kernel is overwritten by g_f; frame 0: by its own bits)
         tracked_gain_kernel<<<dim3((m.L * m.Np + 63) / 64, batch), 64, 0, st>>>(m, seed, sw, trial0, tracked->frame, tracked->corr,
                                                                                  gains);
+    if (drifting)
+        drift_walk_kernel<<<dim3((2 * m.Np + 63) / 64, batch), 64, 0, st>>>(m, seed, sw, trial0, tracked->frame, tracked->drift,
+                                                                            dphi_r, dphi_t);
     draw_noise_qam_kernel<<<dim3(grid_for((long long)std::max(nR, nQ), 1024), batch), 256, 0, st>>>(m, seed, swf, trial0,
                                                                                                       noise, qam, mp->shared_pilots, gauss, psym);
     omega_kernel<<<dim3(m.Tp, batch), 256, (size_t)m.Mr_e * 4, st>>>(m, seed, swf, trial0, Omega);
@@ -415,7 +449,9 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
     // createBeamformer.m: 'ZC' (:15-16, plot_errorVSsnr.m:124) or 'fft' / 'ps' (:5,:12-13 - the same unitary DFT matrix)
     dict_kernel<<<grid_for((long long)m.Nr * m.Nr), 256, 0, st>>>(m.Nr, m.Nr, mp->beamformer == JSTSP_BF_ZC ? 1 : 0, W);
     // ---- channel, pilots ------------------------------------------------------------------------
-    if (!given)                                 // (a supplied channel is in Hmat already)
+    if (drifting)
+        channel_drift_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, dphi_r, dphi_t, Hmat);
+    else if (!given)                            // (a supplied channel is in Hmat already)
         channel_kernel<<<dim3(grid_for((long long)nH, 64), batch), 256, lds_ch, st>>>(m, gains, u_r, u_t, Hmat);
     pilots_kernel<<<dim3(grid_for((long long)nPsi, 1024), batch), 256, 0, st>>>(m, psym, gauss ? 0.70710678f : 1.f, Psi);
     JSTSP_HIP(hipGetLastError());
@@ -502,6 +538,10 @@ int build_trials_impl(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int 
         JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(out->Y_hbf), Yh, b * (size_t)m.Nr * Th, memspace));
         JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(out->A_hbf), Ah, (size_t)m.Nr * m.Gr, memspace));
         JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(out->B_hbf), Bh, b * (size_t)m.G2 * Th, memspace));
+        if (drifting) {
+            JSTSP_TRY(stage_out(ctx, tracked->dphi_r, dphi_r, b * m.Np, memspace));
+            JSTSP_TRY(stage_out(ctx, tracked->dphi_t, dphi_t, b * m.Np, memspace));
+        }
     }
     // tau_Y, tau_Z, rho are host arrays in either memspace: the solver entry points take them from the host
     if (want_hyp) {
@@ -592,7 +632,15 @@ extern "C" int jstsp_build_trials_tracked_c32(jstsp_ctx *ctx, const jstsp_model 
                                               long long trial0, int batch, int frame, double corr, const jstsp_trials *out,
                                               int memspace)
 {
-    const TrackedChannel tr{frame, corr};
+    const TrackedChannel tr{frame, corr, 0, 0.0, nullptr, nullptr};
+    return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, &tr, out, memspace);
+}
+
+extern "C" int jstsp_build_trials_tracked_drift_c32(jstsp_ctx *ctx, const jstsp_model *mp, uint64_t seed, int sweep_idx,
+                                                    long long trial0, int batch, int frame, double corr, double drift,
+                                                    const jstsp_trials *out, double *dphi_r, double *dphi_t, int memspace)
+{
+    const TrackedChannel tr{frame, corr, 1, drift, dphi_r, dphi_t};
     return build_trials_impl(ctx, mp, seed, sweep_idx, trial0, batch, nullptr, &tr, out, memspace);
 }
 

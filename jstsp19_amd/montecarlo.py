@@ -874,10 +874,11 @@ def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, swee
 
 
 TRACKING_MODES = ("cold", "warm", "warm_vs")
+TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev")       # accepted beside the default three: they pass an indx_S
 
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
-                 precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None):
+                 precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -890,12 +891,19 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
       cold     from zero
       warm     from the previous frame's whole state [X | V1 | V2 | C | v | S]; each Imax is a chain of its own
       warm_vs  from the previous frame's v and S only (X = V1 = V2 = C = 0)
+    and, when asked for in ``modes``, the "Proposed - PAI" variants, which pass an ``indx_S``:
+      pai            from zero, with the frame's own ``indx_S`` from the builder (the genie of plot_errorVSsnr.m:143-145)
+      pai_prev       from zero, with ``support_order`` (``support_order_f64``) of the S this (mode, Imax) chain returned at the
+                     previous frame - what a receiver has; frame 0 is solved without ``indx_S``
+      warm_pai_prev  from the previous frame's whole state, ``indx_S`` as ``pai_prev``
+    ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
+    increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
     mode starts from zero, is not scored.  Single process: sequences are not sharded over ranks.
 
     Returns the dictionary tools/run_tracking.py prints - per (mode, Imax) ``mean_nmse`` over the scored frames, ``sem_over_seqs``,
     ``median_nmse``, ``mean_nmse_by_frame`` and ``estimates_per_s`` (solver time only, frame 0 left out) - plus
-    ``"channel": "device"``."""
+    ``"channel": "device"``, and ``"drift"`` when one was given."""
     import time
     import numpy as np
     from . import solvers as J
@@ -907,8 +915,12 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         raise ValueError("corr must lie in [0, 1], not %r" % (corr,))
     if precision not in ("f64", "f32"):
         raise ValueError("precision must be 'f64' or 'f32', not %r" % (precision,))
-    if not modes or any(m not in TRACKING_MODES for m in modes) or not imax or min(imax + [int(cold_imax)]) < 1:
-        raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (TRACKING_MODES,))
+    if not modes or any(m not in TRACKING_MODES + TRACKING_PAI_MODES for m in modes) or not imax or min(imax + [int(cold_imax)]) < 1:
+        raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (TRACKING_MODES + TRACKING_PAI_MODES,))
+    if drift is not None:
+        drift = float(drift)
+        if not (np.isfinite(drift) and drift >= 0.0):
+            raise ValueError("drift must be finite and >= 0, not %r" % (drift,))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -918,34 +930,43 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     wide = (lambda x: J.colmajor(x.to(torch.complex128))) if f64 else (lambda x: x)
     solve = J.proposed_algorithm_resume_f64 if f64 else J.proposed_algorithm_resume
     score = J.nmse_spectral_f64 if f64 else J.nmse_spectral
+    order = J.support_order_f64 if f64 else J.support_order
     keys = [("cold", i) for i in sorted(set(imax + [int(cold_imax)])) if "cold" in modes] + \
-           [(m, i) for m in ("warm", "warm_vs") if m in modes for i in imax]
+           [(m, i) for m in ("warm", "warm_vs") + TRACKING_PAI_MODES if m in modes for i in imax]
+    frame_kw = {} if drift is None else {"drift": drift}
     err = {k: [] for k in keys}                                     # per chunk: (scored frames, chunk) on the host
     secs = {k: 0.0 for k in keys}
     for t0 in range(0, n_seqs, batch):
         nb = min(batch, n_seqs - t0)
-        state = {}
+        state, prev_S = {}, {}
         e_dev = {k: [] for k in keys}
         for f in range(n_frames):
-            inp = build_trials(p, t0, nb, seed=seed, sweep_idx=sweep_idx, device=device, frame=f, corr=corr)
+            inp = build_trials(p, t0, nb, seed=seed, sweep_idx=sweep_idx, device=device, frame=f, corr=corr, **frame_kw)
             args = (wide(inp["subY"]), J.colmajor(inp["Omega"].to(torch.float64)) if f64 else inp["Omega"], wide(inp["A"]),
                     wide(inp["B"]))
             prm = (inp["tau_Y"].numpy(), inp["tau_Z"].numpy(), inp["rho"].numpy())
             zb = wide(inp["Zbar"])
             for k in keys:
                 mode, n_it = k
-                warm = mode != "cold"
+                warm = mode in ("warm", "warm_vs", "warm_pai_prev")
                 st = state.get(k) if warm else None
                 if st is not None and mode == "warm_vs":
                     st = st.clone()
                     st[:, :4 * nm] = 0
+                ix = {}
+                if mode == "pai":
+                    ix = {"indx_S": inp["indx_S"]}
+                elif mode in ("pai_prev", "warm_pai_prev") and k in prev_S:
+                    ix = {"indx_S": order(prev_S[k])}               # (not timed: the solver's rate is what estimates_per_s reports)
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
-                S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm)
+                S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm, **ix)
                 torch.cuda.synchronize(device)
                 dt = time.perf_counter() - c0
                 if warm:
                     state[k] = out
+                if mode in ("pai_prev", "warm_pai_prev"):
+                    prev_S[k] = S
                 if f:
                     secs[k] += dt
                     e_dev[k].append(torch.as_tensor(score(S, zb)).double())
@@ -960,6 +981,9 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 "median_nmse": float(np.median(e)), "mean_nmse_by_frame": [float(x) for x in e.mean(axis=1)],
                 "estimates_per_s": n_seqs * (n_frames - 1) / secs[k]}
 
-    return {"tool": "run_tracking", "precision": precision, "shape": [N, M, Gr, G2], "frames": n_frames, "seqs": n_seqs, "corr": corr,
-            "clusters": p.clusters, "rays": p.rays, "snr_db": p.snr_db, "seed": seed, "scored_frames": list(range(1, n_frames)),
-            "cold_imax": int(cold_imax), "results": [summary(k) for k in keys], "channel": "device"}
+    res = {"tool": "run_tracking", "precision": precision, "shape": [N, M, Gr, G2], "frames": n_frames, "seqs": n_seqs, "corr": corr,
+           "clusters": p.clusters, "rays": p.rays, "snr_db": p.snr_db, "seed": seed, "scored_frames": list(range(1, n_frames)),
+           "cold_imax": int(cold_imax), "results": [summary(k) for k in keys], "channel": "device"}
+    if drift is not None:
+        res["drift"] = drift
+    return res

@@ -34,7 +34,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
            "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64",
            "admm_state_elems", "proposed_algorithm_resume_f64", "proposed_algorithm_std_resume_f64",
-           "proposed_algorithm_resume", "proposed_algorithm_angles_resume"]
+           "proposed_algorithm_resume", "proposed_algorithm_angles_resume", "support_order", "support_order_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1534,3 +1534,35 @@ def rate_f64(S, Zbar, noise_var, *, ctx=None):
     e)))`` = ``log2(real(det(eye(R) + 1/R*Zbar*Zbar'/(noise_var + e))))`` with ``e`` the uncapped spectral-norm NMSE of ``S`` and R
     the rows of ``Zbar``.  Arguments and result as :func:`nmse_spectral_f64`; ``noise_var`` >= 0."""
     return _score_f64_call("jstsp_rate_f64", S, Zbar, (float(noise_var),), ctx)
+
+
+# ----------------------------------------------------------------------------- the order of a support
+def _support_order_call(entry, S, np_dtype, ctx):
+    a_S = _Arg(S, np_dtype, "S")
+    c, mem, dev = _ctx_for([a_S], ctx)
+    batch, Gr, G2 = a_S.batch, a_S.R, a_S.C
+    if mem == DEVICE:
+        import torch
+        out = torch.empty((batch, Gr * G2), dtype=torch.int32, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty((batch, Gr * G2), dtype=np.int32)
+        optr = out.ctypes.data
+    check(getattr(c._lib, entry)(c.handle, Gr, G2, batch, a_S.ptr, optr, mem), entry)
+    return out
+
+
+def support_order(S, *, ctx=None):
+    """``[~, indx_S] = sort(abs(vec(S)), 'descend')`` per trial (plot_errorVSsnr.m:143) on the device
+    (``jstsp_support_order_c32``, csrc/support.hip): what ``proposed_algorithm_angles`` takes as ``indx_S``, from an ``S`` that
+    need not be the true channel's - in a tracker, the previous frame's estimate.  ``S``: (Gr, G2) or (batch, Gr, G2), numpy or a
+    column-major torch CUDA tensor, complex64.  Returns int32 (batch, Gr*G2), 1-based column-major linear indices, where ``S``
+    lives.  The key is ``|z|^2`` in fp32 - the trial builder's, so ``support_order(Zbar)`` is ``build_trials``' ``indx_S`` on the
+    bits; equal keys (the exact zeros of a thresholded ``S``) come in ascending index, a NaN first, then Inf."""
+    return _support_order_call("jstsp_support_order_c32", S, np.complex64, ctx)
+
+
+def support_order_f64(S, *, ctx=None):
+    """:func:`support_order` for a complex128 ``S`` without narrowing (``jstsp_support_order_f64``): the key is ``|z|^2`` in
+    float64.  Arguments and result as :func:`support_order`."""
+    return _support_order_call("jstsp_support_order_f64", S, np.complex128, ctx)

@@ -163,7 +163,7 @@ def _channel_on_device(channel, device):
 
 def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, device=None, with_hbf=False,
                  want_draws=False, want_H=False, shared_pilots=False, ctx=None, pilots="qam4", channel=None,
-                 channel_normalize="reference", frame=0, corr=None):
+                 channel_normalize="reference", frame=0, corr=None, drift=None):
     """plot_errorVSsnr.m:57-136 for trials [trial0, trial0 + batch) on the HIP path
     (``jstsp_build_trials_c32``, csrc/inputgen.hip): draws, channel, pilots, measurement, A, B,
     hyper-parameters and indx_S are produced by the library's own kernels — nothing but the output
@@ -187,11 +187,24 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
     ``g_f = corr g_{f-1} + sqrt(1 - corr^2) w_f`` (in closed form: a frame depends on no earlier call), noise, pilots and Omega of
     the frame's own.  Frame 0 is the drawn call on the bits; ``want_draws`` returns the frame's ``gains``.  ``corr=None`` (the
     default) is the drawn call and takes no ``frame``; ``corr`` with ``channel=`` is a ``ValueError``.
+
+    ``drift``: a finite float >= 0 (it needs ``corr``) lets the angles of that sequence walk
+    (``jstsp_build_trials_tracked_drift_c32``): ``phi_f = phi_0 + drift * sum_{k=1..f} z_k``, z_k ~ N(0, 1) independent per path
+    and array end, ``drift`` the standard deviation of one frame's increment in radians.  ``u_r``, ``u_t`` stay the drawn call's;
+    ``want_draws`` also returns ``dphi_r``, ``dphi_t``, float64 ``(batch, Np)``: ``phi_f - phi_0``.  ``drift=0.0`` returns the
+    arrays of ``drift=None`` on the bits, and ``drift=None`` (the default) calls what was called before.  ``drift`` without
+    ``corr``, negative or non-finite is a ``ValueError``.
     """
     if corr is not None and channel is not None:
         raise ValueError("corr= (a tracked channel) and channel= (a supplied channel) exclude each other")
     if corr is None and frame != 0:
         raise ValueError("frame=%r needs corr=, the correlation of the sequence from one frame to the next" % (frame,))
+    if drift is not None:
+        if corr is None:
+            raise ValueError("drift=%r needs corr=: the angles walk along a tracked sequence" % (drift,))
+        drift = float(drift)
+        if not (math.isfinite(drift) and drift >= 0.0):
+            raise ValueError("drift must be finite and >= 0 (the standard deviation of one frame's angle increment), not %r" % (drift,))
     import ctypes as C
     import numpy as np
     from . import _lib
@@ -235,7 +248,14 @@ def build_trials(p: SweepParams, trial0, batch, *, seed=20190913, sweep_idx=0, d
         setattr(tr, k, v.data_ptr())
     for k, v in hyp.items():
         setattr(tr, k, v.ctypes.data_as(C.POINTER(C.c_double)))
-    if corr is not None:
+    if drift is not None:
+        dphi = {k: torch.empty((batch, Np), dtype=torch.float64, device=device) for k in ("dphi_r", "dphi_t")} if want_draws else {}
+        rc = c._lib.jstsp_build_trials_tracked_drift_c32(
+            c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0), int(batch), int(frame), float(corr), drift,
+            C.byref(tr), dphi["dphi_r"].data_ptr() if dphi else None, dphi["dphi_t"].data_ptr() if dphi else None, _lib.DEVICE)
+        _lib.check(rc, "jstsp_build_trials_tracked_drift_c32")
+        out.update(dphi)
+    elif corr is not None:
         rc = c._lib.jstsp_build_trials_tracked_c32(c.handle, C.byref(model), C.c_uint64(seed), int(sweep_idx), int(trial0),
                                                    int(batch), int(frame), float(corr), C.byref(tr), _lib.DEVICE)
         _lib.check(rc, "jstsp_build_trials_tracked_c32")

@@ -19,6 +19,10 @@ fp32 solver (proposed_algorithm_resume, nmse_spectral: its estimates/s are the o
   warm     from the previous frame's whole state [X | V1 | V2 | C | v | S]; each Imax is a chain of its own
   warm_vs  from the previous frame's v and S only (X = V1 = V2 = C = 0): the part of the state that lives in the angle-delay
            domain and does not depend on the frame's pilots and sampling pattern
+With --device-channel, --modes also takes the "Proposed - PAI" variants - pai: from zero with the frame's
+own true support order (the genie of plot_errorVSsnr.m:143-145); pai_prev: from zero with the order of the chain's previous
+estimate (support_order on the device); warm_pai_prev: the previous frame's whole state and that order - and --drift SIGMA lets the
+angles of every sequence walk, SIGMA radians of standard deviation per frame, so the support moves across the dictionary grid.
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -45,7 +49,14 @@ ap.add_argument("--small", action="store_true", help="Nt=4, Nr=32, L=4, T=35, Mr
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
 ap.add_argument("--device-channel", action="store_true", help="frames built by the library (montecarlo.run_tracking)")
 ap.add_argument("--sweep-idx", type=int, default=0, help="--device-channel: the sweep index of the sequences' Philox key")
+ap.add_argument("--drift", type=float, default=None, metavar="SIGMA",
+                help="--device-channel: random walk of every path angle, SIGMA rad per frame (default: fixed angles)")
+ap.add_argument("--modes", nargs="+", default=None,
+                choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev"),
+                help="--device-channel: the columns to run (default: cold warm warm_vs)")
 a = ap.parse_args()
+if (a.drift is not None or a.modes is not None) and not a.device_channel:
+    ap.error("--drift and --modes need --device-channel")
 
 p = SweepParams(Nt=4, Nr=32, L=4, T=35, Mr=4, snr_db=a.snr_db) if a.small else SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=a.snr_db)
 
@@ -59,8 +70,9 @@ def emit(res):
 
 if a.device_channel:
     from jstsp19_amd.montecarlo import run_tracking
+    kw = {} if a.modes is None else {"modes": tuple(a.modes)}
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
-                      seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0")))
+                      seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
 
 N, M, Gr, G2 = p.solver_shape
