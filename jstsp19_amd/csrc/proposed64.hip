@@ -356,50 +356,13 @@ int resume64_args(const char *nmf, int Imax, int it0, const void *state_in)
     return 0;
 }
 
-}  // namespace
-}  // namespace jstsp
-
-using namespace jstsp;
-
-extern "C" {
-
-int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y_, const double *tau, jstsp_c64 *X_, int memspace)
+// Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state) and of jstsp_proposed_resume_f64: iterations
+// it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the entry in every message; std_entry is where its 'std' refusal points.
+int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_,
+                  const double *Omega_, const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
+                  const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
 {
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
-    JSTSP_ENTER(ctx);
-    JSTSP_REQUIRE(Mr > 0 && Mt > 0 && batch > 0, JSTSP_E_SHAPE, "svt (float64): bad shape");
-    JSTSP_REQUIRE(Y_ && tau && X_, JSTSP_E_NULL, "svt (float64): NULL argument");
-    JSTSP_REQUIRE(std::min(Mr, Mt) <= P64_MAX_ORDER && batch <= 65535, JSTSP_E_UNSUPPORTED,
-                  "svt (float64): min(Mr, Mt) = %d, batch = %d: the float64 eigen-decomposition is limited to order %d (batch 65535)", std::min(Mr, Mt), batch,
-                  P64_MAX_ORDER);
-    hipStream_t st = ctx->stream;
-    const bool host = memspace == JSTSP_HOST;
-    const size_t nm = (size_t)Mr * Mt * batch;
-    const double *thr;
-    const double2 *Y;
-    double2 *X;
-    Svt64 sv;
-    Slab s(st);
-    JSTSP_TRY(ws64_open(s, "svt (float64)", batch, [&](Slab &w, int b) {
-        const size_t e = (size_t)Mr * Mt * b;
-        thr = w.in(tau, b, true);
-        Y = w.in(reinterpret_cast<const double2 *>(Y_), e, host);
-        X = w.out(reinterpret_cast<double2 *>(X_), e, host);
-        sv.layout(w, Mr, Mt, b);
-    }));
-    JSTSP_TRY(sv.apply(st, Y, thr, 1, X));
-    if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(X_), X, nm));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (also for a device call: tau was read from the caller's host array)
-    return 0;
-}
-
-int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
-                                 const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
-                                 const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
-                                 double *ce_out, int memspace)
-{
-    const char *nmf = "proposed_algorithm (float64)";
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
     JSTSP_ENTER(ctx);
@@ -407,171 +370,7 @@ int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
     JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
     JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
-                  "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use jstsp_proposed_algorithm_c64", nmf);
-    JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
-    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
-    f.make_par(tau_Y, tau_S, rho);
-    hipStream_t st = ctx->stream;
-    const size_t g1 = f.g1(), g = g1 * batch;
-    const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-
-    double2 *V, *S, *Res, *RRes, *T2, *GA, *GB;
-    Slab s(st);
-    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
-        const int bA = strideA ? b : 1, bB = strideB ? b : 1;
-        f.layout(w, b);
-        for (double2 **p : {&V, &S, &Res, &RRes, &T2}) *p = w.get<double2>(g1 * b);
-        GA = w.get<double2>((size_t)Gr * Gr * bA); GB = w.get<double2>((size_t)G2 * G2 * bB);
-        f.gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
-    }));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
-
-    JSTSP_HIP(hipMemsetAsync(V, 0, g * sizeof(double2), st));
-    JSTSP_TRY(f.begin(st));
-    const long long sNM = (long long)f.nm1(), sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
-    const Mat64 Am = f.Am(), Bm = f.Bm(), GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
-    double2 *T = f.T, *gws = f.gws;
-    JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr, gws));          // G_A = A^H A
-    JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, Bm, Bm, GB, (long long)G2 * G2, G2, gws));          // G_B = B B^H
-    for (int it = 0; it < Imax; ++it) {
-        JSTSP_TRY(f.head(st));
-        JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, M, N, batch, Am, Mat64{f.K, sNM, N}, T, (long long)Gr * M, Gr, gws));      // A^H K
-        JSTSP_TRY(zgemm64(st, 'N', 'C', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Bm, Res, sG, Gr, gws));     // ... B^H
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{V, sG, Gr}, T2, sG, Gr, gws));                   // G_A V
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
-        hipLaunchKernelGGL(sub64_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, Res, RRes);
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{Res, sG, Gr}, T2, sG, Gr, gws));                 // G_A Res
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
-        hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S, f.rank, f.mask_count(it),
-                           f.want_ce() ? f.ce3 : nullptr);
-        JSTSP_TRY(f.tail(st, S, it));
-    }
-    JSTSP_HIP(hipMemcpyAsync(f.Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
-    return f.deliver(s);
-}
-
-int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
-                           const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_,
-                           const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
-                           const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace)
-{
-    const char *nmf = "proposed_algorithm 'std' (float64)";
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
-    JSTSP_ENTER(ctx);
-    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
-    JSTSP_REQUIRE((strideA == 0 || strideA >= (long long)N * Gr) && (strideB == 0 || strideB >= (long long)G2 * M), JSTSP_E_SHAPE,
-                  "%s: a factor stride is 0 (shared) or at least the size of one factor", nmf);
-    JSTSP_REQUIRE(N >= Gr && M >= G2, JSTSP_E_UNSUPPORTED,
-                  "%s: K2 = kron(B.', A) must have full column rank (N >= Gr, M >= G2); the under-determined U\\(L\\k) of the reference "
-                  "returns a basic, not least-squares, solution", nmf);
-    JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
-    JSTSP_REQUIRE((PA_ || pinv64_shape_ok(N, Gr)) && (PB_ || pinv64_shape_ok(G2, M)), JSTSP_E_UNSUPPORTED,
-                  "%s: A %d x %d, B %d x %d: a factor the call inverts needs min(rows, cols) <= %d and max(rows, cols) <= %d", nmf, N, Gr, G2, M,
-                  PV_MAX_ORDER, PV_MAX_LONG);
-    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
-    f.make_par(tau_Y, tau_S, rho);
-    const bool host = f.host;
-    hipStream_t st = ctx->stream;
-    const size_t g1 = f.g1();
-    const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-
-    const double2 *PA, *PB;
-    double2 *V, *PAc = nullptr, *PBc = nullptr;
-    double *rcA = nullptr, *rcB = nullptr, *rcd;
-    int32_t *rkA = nullptr, *rkB = nullptr;
-    Pinv64 pvA, pvB;
-    Slab s(st);
-    JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
-        const int bA = strideA ? b : 1, bB = strideB ? b : 1;
-        f.layout(w, b);
-        if (PA_) PA = w.in(reinterpret_cast<const double2 *>(PA_), (size_t)Gr * N * bA, host);
-        else {
-            PA = PAc = w.get<double2>((size_t)Gr * N * bA); rcA = w.get<double>(bA); rkA = w.get<int32_t>(bA);
-            pvA.layout(w, N, Gr, bA);
-        }
-        if (PB_) PB = w.in(reinterpret_cast<const double2 *>(PB_), (size_t)M * G2 * bB, host);
-        else {
-            PB = PBc = w.get<double2>((size_t)M * G2 * bB); rcB = w.get<double>(bB); rkB = w.get<int32_t>(bB);
-            pvB.layout(w, G2, M, bB);
-        }
-        rcd = w.out(rcond_out, 2, host);
-        V = w.get<double2>(g1 * b);
-        const int shp[4][3] = {{Gr, M, N}, {Gr, G2, M}, {N, G2, Gr}, {N, M, G2}};
-        size_t e = 1;
-        for (const auto &q : shp) e = std::max(e, zgemm64_ws_elems(q[0], q[1], q[2], b));
-        f.gws = w.get<double2>(e);
-    }));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
-
-    // the factors: a shared one is inverted once for the call; one that is not of full column rank ends the call
-    if (PAc) JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, f.A, strideA, PAc, rcA, rkA));
-    if (PBc) JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, f.B, strideB, PBc, rcB, rkB));
-    for (int f = 0; f < 2; ++f) {
-        const int cnt = f ? nB : nA, full = f ? G2 : Gr;
-        const double *rc = f ? rcB : rcA;
-        const int32_t *rk = f ? rkB : rkA;
-        if (!rk) continue;
-        std::vector<int32_t> hk(cnt);
-        std::vector<double> hr(cnt);
-        JSTSP_HIP(hipMemcpyAsync(hk.data(), rk, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipMemcpyAsync(hr.data(), rc, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-        for (int t = 0; t < cnt; ++t) {
-            JSTSP_REQUIRE(hr[t] == hr[t], JSTSP_E_ILLCOND, "%s: factor %s of trial %d%s holds a NaN or Inf", nmf, f ? "B" : "A", t,
-                          cnt == 1 && batch > 1 ? " (shared by the batch)" : "");
-            JSTSP_REQUIRE(hk[t] >= full, JSTSP_E_ILLCOND,
-                          "%s: factor %s of trial %d%s has rank %d < %d (rcond of the kept part %.3g): K2 = kron(B.', A) is not of full column rank", nmf,
-                          f ? "B" : "A", t, cnt == 1 && batch > 1 ? " (shared by the batch)" : "", (int)hk[t], full, hr[t]);
-        }
-    }
-    if (rcond_out) {
-        if (rcA) JSTSP_TRY(pinv64_min(st, nA, rcA, rcd));
-        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd, __builtin_nan(""));
-        if (rcB) JSTSP_TRY(pinv64_min(st, nB, rcB, rcd + 1));
-        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd + 1, __builtin_nan(""));
-        JSTSP_HIP(hipGetLastError());
-    }
-
-    JSTSP_HIP(hipMemsetAsync(f.ce3, 0, batch * sizeof(double), st));                                   // convergence_error(:, 3) = 0 (:6)
-    JSTSP_TRY(f.begin(st));
-    const long long sNM = (long long)f.nm1(), sG = (long long)g1;
-    const Mat64 PAm{PA, strideA ? (long long)Gr * N : 0, Gr}, PBm{PB, strideB ? (long long)M * G2 : 0, M};
-    for (int it = 0; it < Imax; ++it) {
-        JSTSP_TRY(f.head(st));
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, M, N, batch, PAm, Mat64{f.K, sNM, N}, f.T, (long long)Gr * M, Gr, f.gws));     // pinv(A) K
-        JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, M, batch, Mat64{f.T, (long long)Gr * M, Gr}, PBm, V, sG, Gr, f.gws));      // ... pinv(B)   (:53)
-        hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, f.par, V, f.Sd, f.rank,
-                           f.mask_count(it));
-        JSTSP_TRY(f.tail(st, f.Sd, it));
-    }
-    if (host && rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
-    return f.deliver(s);
-}
-
-// elements of one trial's state block: [X | V1 | V2 | C] (N M each) then [v | S] (Gr G2 each); 0 for a bad shape
-size_t jstsp_admm_state_elems(int N, int M, int Gr, int G2)
-{
-    if (N <= 0 || M <= 0 || Gr <= 0 || G2 <= 0) return 0;
-    return 4 * (size_t)N * M + 2 * (size_t)Gr * G2;
-}
-
-// ---- the two solvers above, resumed: copies of their frames with the state loaded after begin() and stored before deliver() ----
-int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
-                              const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
-                              const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
-                              double *ce_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
-{
-    const char *nmf = "proposed_algorithm resume (float64)";
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
-    JSTSP_ENTER(ctx);
-    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
-                  "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use jstsp_proposed_std_resume_f64", nmf);
+                  "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use %s", nmf, std_entry);
     JSTSP_TRY(resume64_args(nmf, Imax, it0, state_in));
     JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
     Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
@@ -621,13 +420,39 @@ int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int 
     return f.deliver(s);
 }
 
-int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
-                                  const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_,
-                                  const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
-                                  const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out,
-                                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+// One side of Alg. 1's least-squares step: the rank and rcond of the cnt factors the call inverted (rk NULL: the caller gave pinv).
+// A factor that holds a NaN or is not of full column rank ends the call.
+int inverted64_check(hipStream_t st, const char *nmf, const char *side, int cnt, int full, int batch, const double *rc, const int32_t *rk)
 {
-    const char *nmf = "proposed_algorithm 'std' resume (float64)";
+    if (!rk) return 0;
+    std::vector<int32_t> hk(cnt);
+    std::vector<double> hr(cnt);
+    JSTSP_HIP(hipMemcpyAsync(hk.data(), rk, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    JSTSP_HIP(hipMemcpyAsync(hr.data(), rc, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+    JSTSP_HIP(hipStreamSynchronize(st));
+    const char *shared = cnt == 1 && batch > 1 ? " (shared by the batch)" : "";
+    for (int t = 0; t < cnt; ++t) {
+        JSTSP_REQUIRE(hr[t] == hr[t], JSTSP_E_ILLCOND, "%s: factor %s of trial %d%s holds a NaN or Inf", nmf, side, t, shared);
+        JSTSP_REQUIRE(hk[t] >= full, JSTSP_E_ILLCOND,
+                      "%s: factor %s of trial %d%s has rank %d < %d (rcond of the kept part %.3g): K2 = kron(B.', A) is not of full column rank", nmf,
+                      side, t, shared, (int)hk[t], full, hr[t]);
+    }
+    return 0;
+}
+// its entry of rcond_out: the smallest rcond over the factors the call inverted, NaN for a side that was given
+int rcond64_fill(hipStream_t st, int cnt, const double *rc, double *dst)
+{
+    if (rc) return pinv64_min(st, cnt, rc, dst);
+    hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, dst, __builtin_nan(""));
+    return 0;
+}
+
+// Alg. 1 ('std'), the body of jstsp_proposed_std_f64 (it0 = 0, no state) and of jstsp_proposed_std_resume_f64
+int admm64_std(jstsp_ctx *ctx, const char *nmf, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+               const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_, const jstsp_c64 *PB_, int Imax,
+               const double *tau_Y, const double *tau_S, const double *rho, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
+               double *ce_out, double *rcond_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+{
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
     JSTSP_ENTER(ctx);
@@ -684,29 +509,11 @@ int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, 
     // the factors: a shared one is inverted once for the call; one that is not of full column rank ends the call
     if (PAc) JSTSP_TRY(pinv64_run(st, pvA, N, Gr, nA, f.A, strideA, PAc, rcA, rkA));
     if (PBc) JSTSP_TRY(pinv64_run(st, pvB, G2, M, nB, f.B, strideB, PBc, rcB, rkB));
-    for (int side = 0; side < 2; ++side) {                         // 0: A, 1: B
-        const int cnt = side ? nB : nA, full = side ? G2 : Gr;
-        const double *rc = side ? rcB : rcA;
-        const int32_t *rk = side ? rkB : rkA;
-        if (!rk) continue;
-        std::vector<int32_t> hk(cnt);
-        std::vector<double> hr(cnt);
-        JSTSP_HIP(hipMemcpyAsync(hk.data(), rk, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipMemcpyAsync(hr.data(), rc, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-        for (int t = 0; t < cnt; ++t) {
-            JSTSP_REQUIRE(hr[t] == hr[t], JSTSP_E_ILLCOND, "%s: factor %s of trial %d%s holds a NaN or Inf", nmf, side ? "B" : "A", t,
-                          cnt == 1 && batch > 1 ? " (shared by the batch)" : "");
-            JSTSP_REQUIRE(hk[t] >= full, JSTSP_E_ILLCOND,
-                          "%s: factor %s of trial %d%s has rank %d < %d (rcond of the kept part %.3g): K2 = kron(B.', A) is not of full column rank", nmf,
-                          side ? "B" : "A", t, cnt == 1 && batch > 1 ? " (shared by the batch)" : "", (int)hk[t], full, hr[t]);
-        }
-    }
+    JSTSP_TRY(inverted64_check(st, nmf, "A", nA, Gr, batch, rcA, rkA));
+    JSTSP_TRY(inverted64_check(st, nmf, "B", nB, G2, batch, rcB, rkB));
     if (rcond_out) {
-        if (rcA) JSTSP_TRY(pinv64_min(st, nA, rcA, rcd));
-        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd, __builtin_nan(""));
-        if (rcB) JSTSP_TRY(pinv64_min(st, nB, rcB, rcd + 1));
-        else hipLaunchKernelGGL(fill64_kernel, dim3(1), dim3(64), 0, st, 1, rcd + 1, __builtin_nan(""));
+        JSTSP_TRY(rcond64_fill(st, nA, rcA, rcd));
+        JSTSP_TRY(rcond64_fill(st, nB, rcB, rcd + 1));
         JSTSP_HIP(hipGetLastError());
     }
 
@@ -728,6 +535,89 @@ int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, 
     if (sout) JSTSP_TRY(f.store_state(st, sout, V, f.Sd));
     if (sout && host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
     return f.deliver(s);
+}
+
+}  // namespace
+}  // namespace jstsp
+
+using namespace jstsp;
+
+extern "C" {
+
+int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y_, const double *tau, jstsp_c64 *X_, int memspace)
+{
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_ENTER(ctx);
+    JSTSP_REQUIRE(Mr > 0 && Mt > 0 && batch > 0, JSTSP_E_SHAPE, "svt (float64): bad shape");
+    JSTSP_REQUIRE(Y_ && tau && X_, JSTSP_E_NULL, "svt (float64): NULL argument");
+    JSTSP_REQUIRE(std::min(Mr, Mt) <= P64_MAX_ORDER && batch <= 65535, JSTSP_E_UNSUPPORTED,
+                  "svt (float64): min(Mr, Mt) = %d, batch = %d: the float64 eigen-decomposition is limited to order %d (batch 65535)", std::min(Mr, Mt), batch,
+                  P64_MAX_ORDER);
+    hipStream_t st = ctx->stream;
+    const bool host = memspace == JSTSP_HOST;
+    const size_t nm = (size_t)Mr * Mt * batch;
+    const double *thr;
+    const double2 *Y;
+    double2 *X;
+    Svt64 sv;
+    Slab s(st);
+    JSTSP_TRY(ws64_open(s, "svt (float64)", batch, [&](Slab &w, int b) {
+        const size_t e = (size_t)Mr * Mt * b;
+        thr = w.in(tau, b, true);
+        Y = w.in(reinterpret_cast<const double2 *>(Y_), e, host);
+        X = w.out(reinterpret_cast<double2 *>(X_), e, host);
+        sv.layout(w, Mr, Mt, b);
+    }));
+    JSTSP_TRY(sv.apply(st, Y, thr, 1, X));
+    if (host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(X_), X, nm));
+    JSTSP_HIP(hipStreamSynchronize(st));            // (also for a device call: tau was read from the caller's host array)
+    return 0;
+}
+
+int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                                 const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
+                                 const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
+                                 double *ce_out, int memspace)
+{
+    return admm64_approx(ctx, "proposed_algorithm (float64)", "jstsp_proposed_algorithm_c64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_,
+                         strideB, Imax, tau_Y, tau_S, rho, type, indx_S_, S_out, Y_out, ce_out, 0, nullptr, nullptr, memspace);
+}
+
+int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                           const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_,
+                           const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                           const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace)
+{
+    return admm64_std(ctx, "proposed_algorithm 'std' (float64)", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_, strideB, PA_, PB_, Imax, tau_Y,
+                      tau_S, rho, indx_S_, S_out, Y_out, ce_out, rcond_out, 0, nullptr, nullptr, memspace);
+}
+
+// elements of one trial's state block: [X | V1 | V2 | C] (N M each) then [v | S] (Gr G2 each); 0 for a bad shape
+size_t jstsp_admm_state_elems(int N, int M, int Gr, int G2)
+{
+    if (N <= 0 || M <= 0 || Gr <= 0 || G2 <= 0) return 0;
+    return 4 * (size_t)N * M + 2 * (size_t)Gr * G2;
+}
+
+// ---- the two solvers above, resumed: the same two bodies, admm64_approx and admm64_std, from the caller's it0 and state ----
+int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                              const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
+                              const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
+                              double *ce_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+{
+    return admm64_approx(ctx, "proposed_algorithm resume (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA,
+                         B_, strideB, Imax, tau_Y, tau_S, rho, type, indx_S_, S_out, Y_out, ce_out, it0, state_in, state_out, memspace);
+}
+
+int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                                  const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_,
+                                  const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                                  const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out,
+                                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+{
+    return admm64_std(ctx, "proposed_algorithm 'std' resume (float64)", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_, strideB, PA_, PB_, Imax,
+                      tau_Y, tau_S, rho, indx_S_, S_out, Y_out, ce_out, rcond_out, it0, state_in, state_out, memspace);
 }
 
 }  // extern "C"

@@ -152,6 +152,60 @@ def _indx_arg(indx_S, batch, n):
     return _Arg(ix2, np.int32, "indx_S")
 
 
+class _AdmmCall:
+    """What every ``proposed_algorithm*`` call builds first, for the solver's complex dtype ``cdt`` (complex128: the inputs are widened).
+    The constructor touches no device - the arguments and their shape checks, ``indx_S``, the strides of the dictionaries, the
+    per-trial scalars - so every ``ValueError`` of the arguments comes before the context; :meth:`open` makes the context and the
+    outputs ``S``, ``Y``, ``convergence_error``, :meth:`result` returns them to the caller."""
+
+    def __init__(self, cdt, subY, Omega, A, B, indx_S, tau_Y, tau_S, rho, Imax, PA=None, PB=None):
+        f64 = cdt == np.complex128
+        wide = _wide if f64 else (lambda x, real=False: x)
+        self.cdt = cdt
+        self.sub = _Arg(wide(subY), cdt, "subY")
+        self.om = _Arg(wide(Omega, real=True), np.float64 if f64 else np.float32, "Omega")
+        self.A = _Arg(wide(A), cdt, "A")
+        self.B = _Arg(wide(B), cdt, "B")
+        self.PA = _Arg(wide(PA), cdt, "PA", allow_none=True)
+        self.PB = _Arg(wide(PB), cdt, "PB", allow_none=True)
+        self.batch, self.N, self.M = batch, N, M = self.sub.batch, self.sub.R, self.sub.C
+        self.Gr, self.G2 = Gr, G2 = self.A.C, self.B.R
+        self.Imax = int(Imax)
+        if (self.om.batch, self.om.R, self.om.C) != (batch, N, M):
+            raise ValueError("Omega must have the shape of subY")
+        if self.A.R != N or self.B.C != M:
+            raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+        for a_P, a_F, nmP in ((self.PA, self.A, "PA"), (self.PB, self.B, "PB")):
+            if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
+                raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
+        self.ix = _indx_arg(indx_S, batch, Gr * G2)
+        self.sA = _shared_stride(self.A, N * Gr, batch, "A")
+        self.sB = _shared_stride(self.B, G2 * M, batch, "B")
+        self.tY, self.ptY = _scalars(tau_Y, batch, "tau_Y")
+        self.tS, self.ptS = _scalars(tau_S, batch, "tau_S")
+        self.rh, self.prh = _scalars(rho, batch, "rho")
+        # where a state of this call lives (:func:`_state_arg`), known before the context
+        self.state_mem, self.state_dev = DEVICE if self.sub.torch else HOST, getattr(self.sub, "device", None)
+
+    def open(self, want_ce, ctx):
+        self.ctx, self.mem, self.dev = _ctx_for([self.sub, self.om, self.A, self.B, self.PA, self.PB, self.ix], ctx)
+        tor = self.mem == DEVICE
+        self.pS, fS = _out(tor, self.batch, self.Gr, self.G2, self.cdt, self.dev)
+        self.pY, fY = _out(tor, self.batch, self.N, self.M, self.cdt, self.dev)
+        self.pce, fce = _out(tor, self.batch, self.Imax, 3, np.float64, self.dev) if want_ce else (None, None)
+        self._finish = (fS, fY, fce)
+
+    def c32_args(self, type):
+        """the argument list that the three fp32 entries share: the context's handle ... ce_out"""
+        tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
+        return (self.ctx.handle, self.N, self.M, self.Gr, self.G2, self.batch, self.sub.ptr, self.om.ptr, self.A.ptr, self.sA, self.B.ptr, self.sB,
+                self.Imax, self.ptY, self.ptS, self.prh, tcode, self.ix.ptr, self.pS, self.pY, self.pce)
+
+    def result(self):
+        sq = not self.sub.batched
+        return tuple(None if f is None else f(sq) for f in self._finish)
+
+
 def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None,
                        want_ce=True, ctx=None):
     """basic_system_functions/proposed_algorithm.m:1 — returns (S, Y, convergence_error).
@@ -159,36 +213,10 @@ def proposed_algorithm(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approxi
     ``convergence_error`` is (batch, Imax, 3) float64 (``None`` with ``want_ce=False``, the
     analogue of calling the MATLAB function with fewer than three outputs).
     """
-    a_sub = _Arg(subY, np.complex64, "subY")
-    a_om = _Arg(Omega, np.float32, "Omega")
-    a_A = _Arg(A, np.complex64, "A")
-    a_B = _Arg(B, np.complex64, "B")
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
-    a_ix = _indx_arg(indx_S, batch, Gr * G2)
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, ptY = _scalars(tau_Y, batch, "tau_Y")
-    tS, ptS = _scalars(tau_S, batch, "tau_S")
-    rh, prh = _scalars(rho, batch, "rho")
-    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex64, dev)
-    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex64, dev)
-    if want_ce:
-        pce, fce = _out(mem == DEVICE, batch, int(Imax), 3, np.float64, dev)
-    else:
-        pce, fce = None, None
-    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
-    rc = c._lib.jstsp_proposed_algorithm_c32(c.handle, N, M, Gr, G2, batch, a_sub.ptr, a_om.ptr, a_A.ptr, sA,
-                                             a_B.ptr, sB, int(Imax), ptY, ptS, prh, tcode, a_ix.ptr, pS, pY, pce,
-                                             mem)
-    check(rc, "jstsp_proposed_algorithm_c32")
-    sq = not a_sub.batched
-    return fS(sq), fY(sq), (fce(sq) if want_ce else None)
+    q = _AdmmCall(np.complex64, subY, Omega, A, B, indx_S, tau_Y, tau_S, rho, Imax)
+    q.open(want_ce, ctx)
+    check(q.ctx._lib.jstsp_proposed_algorithm_c32(*q.c32_args(type), q.mem), "jstsp_proposed_algorithm_c32")
+    return q.result()
 
 
 def proposed_algorithm_resume(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None, want_ce=True, ctx=None,
@@ -198,49 +226,19 @@ def proposed_algorithm_resume(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="
     call, ``state`` is complex64 ``(batch, admm_state_elems(N, M, Gr, G2))`` (always two-dimensional; ``None`` with
     ``return_state=False``), a new array of the kind of the inputs.  ``state=None``: from zero (``it0`` must be 0).  A split fp32
     solve is fp32-equivalent to the uninterrupted one, not bit-identical (the header says what is not carried)."""
-    a_sub = _Arg(subY, np.complex64, "subY")
-    a_om = _Arg(Omega, np.float32, "Omega")
-    a_A = _Arg(A, np.complex64, "A")
-    a_B = _Arg(B, np.complex64, "B")
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    Imax, it0 = int(Imax), int(it0)
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
+    q = _AdmmCall(np.complex64, subY, Omega, A, B, indx_S, tau_Y, tau_S, rho, Imax)
+    it0 = int(it0)
     if type not in ("approximate", "std"):
         raise ValueError("type must be 'approximate' or 'std'")
     if it0 < 0 or (state is None and it0 != 0):
         raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
-    ne = 4 * N * M + 2 * Gr * G2
-    p_in, keep_in = _state_arg(state, batch, ne, DEVICE if a_sub.torch else HOST, getattr(a_sub, "device", None), np.complex64)
-    a_ix = _indx_arg(indx_S, batch, Gr * G2)
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, ptY = _scalars(tau_Y, batch, "tau_Y")
-    tS, ptS = _scalars(tau_S, batch, "tau_S")
-    rh, prh = _scalars(rho, batch, "rho")
-    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex64, dev)
-    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex64, dev)
-    pce, fce = _out(mem == DEVICE, batch, Imax, 3, np.float64, dev) if want_ce else (None, None)
-    p_out, st_out = None, None
-    if return_state:
-        if mem == DEVICE:
-            import torch
-            st_out = torch.empty((batch, ne), dtype=torch.complex64, device=dev)
-            p_out = st_out.data_ptr()
-        else:
-            st_out = np.empty((batch, ne), dtype=np.complex64)
-            p_out = st_out.ctypes.data
-    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
-    rc = c._lib.jstsp_proposed_resume_c32(c.handle, N, M, Gr, G2, batch, a_sub.ptr, a_om.ptr, a_A.ptr, sA, a_B.ptr, sB, Imax, ptY, ptS, prh,
-                                          tcode, a_ix.ptr, pS, pY, pce, it0, p_in, p_out, mem)
-    check(rc, "jstsp_proposed_resume_c32")
+    ne = admm_state_elems(q.N, q.M, q.Gr, q.G2)
+    p_in, keep_in = _state_arg(state, q.batch, ne, q.state_mem, q.state_dev, np.complex64)
+    q.open(want_ce, ctx)
+    p_out, st_out = _state_out(return_state, q.batch, ne, q.mem, q.dev, np.complex64)
+    check(q.ctx._lib.jstsp_proposed_resume_c32(*q.c32_args(type), it0, p_in, p_out, q.mem), "jstsp_proposed_resume_c32")
     del keep_in
-    sq = not a_sub.batched
-    return fS(sq), fY(sq), (fce(sq) if want_ce else None), st_out
+    return q.result() + (st_out,)
 
 
 def proposed_algorithm_angles_resume(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type="approximate", greedy_nnz=None, *,
@@ -275,38 +273,13 @@ def proposed_algorithm_begin(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="a
     """The two-phase form of :func:`proposed_algorithm` for torch CUDA tensors (include/jstsp.h:
     jstsp_proposed_algorithm_begin_c32 / _end): enqueues the solve and returns a :class:`PendingSolve` without waiting for the
     GPU; ``handle.end()`` returns the outputs.  Between the two the host is free (e.g. to build the next batch)."""
-    a_sub = _Arg(subY, np.complex64, "subY")
-    a_om = _Arg(Omega, np.float32, "Omega")
-    a_A = _Arg(A, np.complex64, "A")
-    a_B = _Arg(B, np.complex64, "B")
-    a_ix = _Arg(None, np.int32, "indx_S", allow_none=True)
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
-    if indx_S is not None:
-        import torch
-        a_ix = _Arg(indx_S.reshape(batch, Gr * G2, 1).to(torch.int32).contiguous(), np.int32, "indx_S")
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
-    if mem != DEVICE:
+    q = _AdmmCall(np.complex64, subY, Omega, A, B, indx_S, tau_Y, tau_S, rho, Imax)
+    q.open(want_ce, ctx)
+    if q.mem != DEVICE:
         raise ValueError("proposed_algorithm_begin takes torch CUDA tensors (a host call has nothing to overlap: use proposed_algorithm)")
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, ptY = _scalars(tau_Y, batch, "tau_Y")
-    tS, ptS = _scalars(tau_S, batch, "tau_S")
-    rh, prh = _scalars(rho, batch, "rho")
-    pS, fS = _out(True, batch, Gr, G2, np.complex64, dev)
-    pY, fY = _out(True, batch, N, M, np.complex64, dev)
-    pce, fce = _out(True, batch, int(Imax), 3, np.float64, dev) if want_ce else (None, None)
-    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
     h = C.c_void_p()
-    check(c._lib.jstsp_proposed_algorithm_begin_c32(c.handle, N, M, Gr, G2, batch, a_sub.ptr, a_om.ptr, a_A.ptr, sA, a_B.ptr, sB,
-                                                    int(Imax), ptY, ptS, prh, tcode, a_ix.ptr, pS, pY, pce, C.byref(h)),
-          "jstsp_proposed_algorithm_begin_c32")
-    sq = not a_sub.batched
-    return PendingSolve(c, h, (a_sub, a_om, a_A, a_B, a_ix, tY, tS, rh), (fS(sq), fY(sq), (fce(sq) if want_ce else None)))
+    check(q.ctx._lib.jstsp_proposed_algorithm_begin_c32(*q.c32_args(type), C.byref(h)), "jstsp_proposed_algorithm_begin_c32")
+    return PendingSolve(q.ctx, h, (q.sub, q.om, q.A, q.B, q.ix, q.tY, q.tS, q.rh), q.result())
 
 
 def proposed_algorithm_angles(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type="approximate",
@@ -906,43 +879,10 @@ def proposed_algorithm_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="app
     nothing is narrowed.  Same arguments; complex64 / float32 inputs are widened exactly, the outputs are complex128
     (numpy in -> numpy out, torch CUDA tensors in -> torch CUDA tensors out).  ``'approximate'`` only.  A batch whose
     float64 workspace would exceed the library's limit is solved in chunks."""
-    a_sub = _Arg(_wide(subY), np.complex128, "subY")
-    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
-    a_A = _Arg(_wide(A), np.complex128, "A")
-    a_B = _Arg(_wide(B), np.complex128, "B")
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
     if type not in ("approximate", "std"):
         raise ValueError("type must be 'approximate' or 'std'")
-    a_ix = _indx_arg(indx_S, batch, Gr * G2)
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_ix], ctx)
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, _ = _scalars(tau_Y, batch, "tau_Y")
-    tS, _ = _scalars(tau_S, batch, "tau_S")
-    rh, _ = _scalars(rho, batch, "rho")
-    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
-    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
-    pce, fce = _out(mem == DEVICE, batch, int(Imax), 3, np.float64, dev) if want_ce else (None, None)
-    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD
-    # bytes of float64 state per trial (csrc/proposed64.hip): the N x M and Gr x G2 arrays, the staged copies of a host call
-    n = min(N, M)
-    per = 16 * (8 * N * M + 5 * Gr * G2 + Gr * M + N * G2 + 20 * n * n + (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0))
-    if mem == HOST:
-        per += 16 * (2 * N * M + Gr * G2 + (G2 * M if sB else 0) + (N * Gr if sA else 0)) + 8 * N * M
-    dp = C.POINTER(C.c_double)
-    for t0, nb in _f64_chunks(batch, per):
-        rc = c._lib.jstsp_proposed_algorithm_f64(
-            c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
-            _off(a_B.ptr, t0 * sB, 16), sB, int(Imax), tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp),
-            tcode, _off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * int(Imax), 8), mem)
-        check(rc, "jstsp_proposed_algorithm_f64")
-    sq = not a_sub.batched
-    return fS(sq), fY(sq), (fce(sq) if want_ce else None)
+    tcode = _lib.TYPE_APPROXIMATE if type == "approximate" else _lib.TYPE_STD          # ('std': the library refuses and says where to go)
+    return _admm_f64(False, False, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, tcode, indx_S, None, None, want_ce, False, ctx)[:3]
 
 
 def proposed_algorithm_angles_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, type="approximate",
@@ -960,57 +900,8 @@ def proposed_algorithm_std_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, in
     gives the bits of the ``None`` call - batched exactly as ``A`` / ``B`` are; a caller that solves several times on the same
     dictionaries inverts them once.  ``info=True`` also returns ``rcond``: float64 (2,), the smallest over the ``A`` and over the
     ``B`` factors the call inverted, NaN for a side that was given (the smallest over the chunks when the batch is chunked)."""
-    a_sub = _Arg(_wide(subY), np.complex128, "subY")
-    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
-    a_A = _Arg(_wide(A), np.complex128, "A")
-    a_B = _Arg(_wide(B), np.complex128, "B")
-    a_PA = _Arg(_wide(PA), np.complex128, "PA", allow_none=True)
-    a_PB = _Arg(_wide(PB), np.complex128, "PB", allow_none=True)
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
-    for a_P, a_F, nmP in ((a_PA, a_A, "PA"), (a_PB, a_B, "PB")):
-        if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
-            raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
-    a_ix = _indx_arg(indx_S, batch, Gr * G2)
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, _ = _scalars(tau_Y, batch, "tau_Y")
-    tS, _ = _scalars(tau_S, batch, "tau_S")
-    rh, _ = _scalars(rho, batch, "rho")
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_PA, a_PB, a_ix], ctx)
-    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
-    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
-    pce, fce = _out(mem == DEVICE, batch, int(Imax), 3, np.float64, dev) if want_ce else (None, None)
-    # bytes of float64 state per trial (csrc/proposed64.hip): the N x M arrays, V, the products, the svt, the Hestenes arrays of a
-    # per-trial factor, the staged copies of a host call
-    n = min(N, M)
-    per = 16 * (8 * N * M + 2 * Gr * G2 + Gr * M + N * G2 + 20 * n * n)
-    per += 16 * ((2 * N * Gr + 3 * Gr * Gr if sA and a_PA.ptr is None else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and a_PB.ptr is None else 0))
-    if mem == HOST:
-        per += 16 * (2 * N * M + Gr * G2 + 2 * (G2 * M if sB else 0) + 2 * (N * Gr if sA else 0)) + 8 * N * M
-    dp = C.POINTER(C.c_double)
-    rcs = []
-    for t0, nb in _f64_chunks(batch, per):
-        prc, rc1 = _vec_out(mem == DEVICE, 2, np.float64, dev) if info else (None, None)
-        rc = c._lib.jstsp_proposed_std_f64(
-            c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
-            _off(a_B.ptr, t0 * sB, 16), sB, _off(a_PA.ptr, t0 * (Gr * N if sA else 0), 16), _off(a_PB.ptr, t0 * (M * G2 if sB else 0), 16),
-            int(Imax), tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp),
-            _off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * int(Imax), 8), prc, mem)
-        check(rc, "jstsp_proposed_std_f64")
-        rcs.append(rc1)
-    sq = not a_sub.batched
-    out = (fS(sq), fY(sq), (fce(sq) if want_ce else None))
-    if not info:
-        return out
-    rcond = rcs[0]
-    for r in rcs[1:]:          # (min propagates NaN in numpy and in torch)
-        rcond = np.minimum(rcond, r) if mem == HOST else rcond.minimum(r)
-    return out + (rcond,)
+    out = _admm_f64(True, False, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, None, indx_S, PA, PB, want_ce, info, ctx)
+    return out[:3] + (out[4],) if info else out[:3]
 
 
 def proposed_algorithm_angles_std_f64(subY, Omega, indx_S, A, B, Imax, tau_Y, tau_S, rho, greedy_nnz=None, *, PA=None, PB=None,
@@ -1046,71 +937,77 @@ def _state_arg(state, batch, elems, mem, dev, np_dtype=np.complex128):
     return buf.ctypes.data, buf
 
 
-def _resume_f64(std, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, PA, PB, want_ce, ctx, state, it0, return_state):
-    """The resumed forms of :func:`proposed_algorithm_f64` (``std=False``) and :func:`proposed_algorithm_std_f64`."""
-    a_sub = _Arg(_wide(subY), np.complex128, "subY")
-    a_om = _Arg(_wide(Omega, real=True), np.float64, "Omega")
-    a_A = _Arg(_wide(A), np.complex128, "A")
-    a_B = _Arg(_wide(B), np.complex128, "B")
-    a_PA = _Arg(_wide(PA), np.complex128, "PA", allow_none=True)
-    a_PB = _Arg(_wide(PB), np.complex128, "PB", allow_none=True)
-    batch, N, M = a_sub.batch, a_sub.R, a_sub.C
-    Gr, G2 = a_A.C, a_B.R
-    Imax, it0 = int(Imax), int(it0)
-    if (a_om.batch, a_om.R, a_om.C) != (batch, N, M):
-        raise ValueError("Omega must have the shape of subY")
-    if a_A.R != N or a_B.C != M:
-        raise ValueError("size(A,1) must equal size(subY,1) and size(B,2) must equal size(subY,2)")
-    for a_P, a_F, nmP in ((a_PA, a_A, "PA"), (a_PB, a_B, "PB")):
-        if a_P.ptr is not None and ((a_P.R, a_P.C) != (a_F.C, a_F.R) or a_P.batched != a_F.batched or a_P.batch != a_F.batch):
-            raise ValueError("%s must have the shape of pinv(%s), batched as %s is" % (nmP, nmP[1], nmP[1]))
+def _state_out(wanted, batch, elems, mem, dev, np_dtype=np.complex128):
+    """A new ``(batch, elems)`` state array where the inputs live, as (pointer, array); (None, None) when none is wanted."""
+    if not wanted:
+        return None, None
+    if mem == DEVICE:
+        import torch
+        st = torch.empty((batch, elems), dtype=torch.complex128 if np_dtype == np.complex128 else torch.complex64, device=dev)
+        return st.data_ptr(), st
+    st = np.empty((batch, elems), dtype=np_dtype)
+    return st.ctypes.data, st
+
+
+def _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, own_PA, own_PB, host, resumed):
+    """Bytes of float64 state per trial of a float64 ``proposed_algorithm`` call (csrc/proposed64.hip), which sets the chunks of a large
+    batch: the N x M and Gr x G2 arrays, the products, the svt, the Grams of a per-trial dictionary, for Alg. 1 (``std``) the Hestenes
+    arrays of a per-trial factor the call inverts (``own_PA`` / ``own_PB``), and the staged copies of a host call.  The plain Alg. 1
+    call counts 2 Gr x G2 arrays and no Grams, the plain Alg. 2 call stages a per-trial dictionary once and the others twice, and only
+    a resumed call stages the two state blocks.  Above Gram order 64 a chunk's trials are swept together (include/jstsp.h), so a
+    change of these counts can change last bits."""
+    n, g = min(N, M), Gr * G2
+    plain_std = std and not resumed
+    per = 8 * N * M + (2 if plain_std else 5) * g + Gr * M + N * G2 + 20 * n * n
+    if not plain_std:
+        per += (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0)
+    if std:
+        per += (2 * N * Gr + 3 * Gr * Gr if sA and own_PA else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and own_PB else 0)
+    per *= 16
+    if host:
+        dicts = (G2 * M if sB else 0) + (N * Gr if sA else 0)
+        states = 2 * admm_state_elems(N, M, Gr, G2) if resumed else 0
+        per += 16 * (2 * N * M + g + (2 if std or resumed else 1) * dicts + states) + 8 * N * M
+    return per
+
+
+def _admm_f64(std, resumed, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, tcode, indx_S, PA, PB, want_ce, info, ctx, state=None, it0=0,
+              return_state=False):
+    """The frame of the four float64 ``proposed_algorithm`` functions: Alg. 1 (``std``) or Alg. 2, through the plain C entry or -
+    ``resumed`` - the one that takes ``it0`` and the states.  Returns ``(S, Y, ce, state, rcond)``; ``rcond`` with ``info`` (Alg. 1)."""
+    q = _AdmmCall(np.complex128, subY, Omega, A, B, indx_S, tau_Y, tau_S, rho, Imax, PA, PB)
+    N, M, Gr, G2, batch, Imax, sA, sB = q.N, q.M, q.Gr, q.G2, q.batch, q.Imax, q.sA, q.sB
+    it0 = int(it0)
     if it0 < 0 or (state is None and it0 != 0):
         raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
-    a_ix = _indx_arg(indx_S, batch, Gr * G2)
-    sA = _shared_stride(a_A, N * Gr, batch, "A")
-    sB = _shared_stride(a_B, G2 * M, batch, "B")
-    tY, _ = _scalars(tau_Y, batch, "tau_Y")
-    tS, _ = _scalars(tau_S, batch, "tau_S")
-    rh, _ = _scalars(rho, batch, "rho")
     ne = admm_state_elems(N, M, Gr, G2)
-    p_in, keep_in = _state_arg(state, batch, ne, DEVICE if a_sub.torch else HOST, getattr(a_sub, "device", None))
-    c, mem, dev = _ctx_for([a_sub, a_om, a_A, a_B, a_PA, a_PB, a_ix], ctx)
-    p_out, st_out = None, None
-    if return_state:
-        if mem == DEVICE:
-            import torch
-            st_out = torch.empty((batch, ne), dtype=torch.complex128, device=dev)
-            p_out = st_out.data_ptr()
-        else:
-            st_out = np.empty((batch, ne), dtype=np.complex128)
-            p_out = st_out.ctypes.data
-    pS, fS = _out(mem == DEVICE, batch, Gr, G2, np.complex128, dev)
-    pY, fY = _out(mem == DEVICE, batch, N, M, np.complex128, dev)
-    pce, fce = _out(mem == DEVICE, batch, Imax, 3, np.float64, dev) if want_ce else (None, None)
-    # bytes of float64 state per trial: those of the sibling (whichever is larger) and the staged state blocks of a host call
-    n = min(N, M)
-    per = 16 * (8 * N * M + 5 * Gr * G2 + Gr * M + N * G2 + 20 * n * n + (G2 * G2 if sB else 0) + (Gr * Gr if sA else 0))
-    if std:
-        per += 16 * ((2 * N * Gr + 3 * Gr * Gr if sA and a_PA.ptr is None else 0) + (2 * G2 * M + 3 * G2 * G2 if sB and a_PB.ptr is None else 0))
-    if mem == HOST:
-        per += 16 * (2 * N * M + Gr * G2 + 2 * (G2 * M if sB else 0) + 2 * (N * Gr if sA else 0) + 2 * ne) + 8 * N * M
+    p_in, keep_in = _state_arg(state, batch, ne, q.state_mem, q.state_dev)
+    q.open(want_ce, ctx)
+    mem = q.mem
+    p_out, st_out = _state_out(return_state, batch, ne, mem, q.dev)
+    per = _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, q.PA.ptr is None, q.PB.ptr is None, mem == HOST, resumed)
+    name = {(False, False): "jstsp_proposed_algorithm_f64", (False, True): "jstsp_proposed_resume_f64",
+            (True, False): "jstsp_proposed_std_f64", (True, True): "jstsp_proposed_std_resume_f64"}[bool(std), bool(resumed)]
     dp = C.POINTER(C.c_double)
+    rcs = []
     for t0, nb in _f64_chunks(batch, per):
-        head = (c.handle, N, M, Gr, G2, nb, _off(a_sub.ptr, t0 * N * M, 16), _off(a_om.ptr, t0 * N * M, 8), _off(a_A.ptr, t0 * sA, 16), sA,
-                _off(a_B.ptr, t0 * sB, 16), sB)
-        prm = (Imax, tY[t0:].ctypes.data_as(dp), tS[t0:].ctypes.data_as(dp), rh[t0:].ctypes.data_as(dp))
-        outs = (_off(a_ix.ptr, t0 * Gr * G2, 4), _off(pS, t0 * Gr * G2, 16), _off(pY, t0 * N * M, 16), _off(pce, t0 * 3 * Imax, 8))
-        tail = (it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16), mem)
+        prc, rc1 = _vec_out(mem == DEVICE, 2, np.float64, q.dev) if info else (None, None)
+        head = (q.ctx.handle, N, M, Gr, G2, nb, _off(q.sub.ptr, t0 * N * M, 16), _off(q.om.ptr, t0 * N * M, 8), _off(q.A.ptr, t0 * sA, 16), sA,
+                _off(q.B.ptr, t0 * sB, 16), sB)
+        prm = (Imax, q.tY[t0:].ctypes.data_as(dp), q.tS[t0:].ctypes.data_as(dp), q.rh[t0:].ctypes.data_as(dp))
+        outs = (_off(q.ix.ptr, t0 * Gr * G2, 4), _off(q.pS, t0 * Gr * G2, 16), _off(q.pY, t0 * N * M, 16), _off(q.pce, t0 * 3 * Imax, 8))
+        tail = ((it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16)) if resumed else ()) + (mem,)
         if std:
-            rc = c._lib.jstsp_proposed_std_resume_f64(*head, _off(a_PA.ptr, t0 * (Gr * N if sA else 0), 16),
-                                                      _off(a_PB.ptr, t0 * (M * G2 if sB else 0), 16), *prm, *outs, None, *tail)
-            check(rc, "jstsp_proposed_std_resume_f64")
+            args = head + (_off(q.PA.ptr, t0 * (Gr * N if sA else 0), 16), _off(q.PB.ptr, t0 * (M * G2 if sB else 0), 16)) + prm + outs + (prc,) + tail
         else:
-            rc = c._lib.jstsp_proposed_resume_f64(*head, *prm, _lib.TYPE_APPROXIMATE, *outs, *tail)
-            check(rc, "jstsp_proposed_resume_f64")
+            args = head + prm + (tcode,) + outs + tail
+        check(getattr(q.ctx._lib, name)(*args), name)
+        rcs.append(rc1)
     del keep_in
-    sq = not a_sub.batched
-    return fS(sq), fY(sq), (fce(sq) if want_ce else None), st_out
+    rcond = rcs[0]
+    for r in rcs[1:] if info else ():          # (min propagates NaN in numpy and in torch)
+        rcond = np.minimum(rcond, r) if mem == HOST else rcond.minimum(r)
+    return q.result() + (st_out, rcond)
 
 
 def proposed_algorithm_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, type="approximate", *, indx_S=None, want_ce=True, ctx=None,
@@ -1125,7 +1022,8 @@ def proposed_algorithm_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, ty
     may come from another problem of the same shape (a warm start); ``it0`` then only sets the mask count of ``indx_S``."""
     if type != "approximate":
         raise ValueError("type must be 'approximate' (Alg. 1: proposed_algorithm_std_resume_f64)")
-    return _resume_f64(False, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, None, None, want_ce, ctx, state, it0, return_state)
+    return _admm_f64(False, True, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, _lib.TYPE_APPROXIMATE, indx_S, None, None, want_ce, False, ctx,
+                     state, it0, return_state)[:4]
 
 
 def proposed_algorithm_std_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, indx_S=None, PA=None, PB=None, want_ce=True, ctx=None,
@@ -1133,7 +1031,8 @@ def proposed_algorithm_std_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho
     """:func:`proposed_algorithm_std_f64` resumed from a saved state (include/jstsp.h: jstsp_proposed_std_resume_f64); arguments
     and outputs as :func:`proposed_algorithm_resume_f64`, ``PA`` / ``PB`` as the sibling's.  Alg. 1 recomputes ``v`` in every
     iteration: the ``v`` of ``state`` is ignored."""
-    return _resume_f64(True, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, indx_S, PA, PB, want_ce, ctx, state, it0, return_state)
+    return _admm_f64(True, True, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, None, indx_S, PA, PB, want_ce, False, ctx, state, it0,
+                     return_state)[:4]
 
 
 def svt_f64(Y, tau, *, ctx=None):

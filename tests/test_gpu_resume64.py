@@ -19,7 +19,7 @@ from conftest import check_below, ce_rel, rel_err  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 TOL64_S, TOL64_CE = 1e-10, 1e-8
-E_ARG = -4
+E_ARG, E_UNSUPPORTED = -4, -3
 KINDS = ("approx", "angles", "std")
 CASES = [(n, sh, mem) for n in ("R1", "R2") for sh in (False, True) for mem in ("host", "device")]
 
@@ -213,6 +213,25 @@ def test_refusals():
         assert _raw(kind, "R1", False, "host", 2, 2 ** 31 - 2, st, None)[0] == E_ARG            # it0 + Imax beyond int
         assert _raw(kind, "R1", False, "host", 2, 3, None, None)[0] == E_ARG                    # from zero, it0 != 0
         assert _raw(kind, "R1", False, "host", 2, 2 ** 31 - 3, st, None)[0] == 0                # the last it0 that fits
+    # a bad call names the entry that was called, and the 'std' refusal of each Alg. 2 entry points to its own way out
+    last = lambda: J.load().jstsp_last_error().decode()
+    for kind, nmf in (("approx", "proposed_algorithm resume (float64)"), ("std", "proposed_algorithm 'std' resume (float64)")):
+        assert _raw(kind, "R1", False, "host", 2, -1, st, None)[0] == E_ARG
+        assert last().startswith(nmf + ": it0 = -1")
+    from jstsp19_amd import solvers as SV
+    N, M, Gr, G2 = P.SHAPES["R1"]
+    arrs, _, prm = _inputs("R1", False, "host")
+    a = [SV._Arg(x, np.float64 if k == 1 else np.complex128, "arg") for k, x in enumerate(arrs)]
+    c = SV._ctx_for(a, None)[0]
+    sc = [SV._scalars(v, P.BATCH, "s")[1] for v in prm]
+    outs = [SV._out(False, P.BATCH, r, cc, np.complex128) for r, cc in ((Gr, G2), (N, M))]
+    args = (c.handle, N, M, Gr, G2, P.BATCH, a[0].ptr, a[1].ptr, a[2].ptr, 0, a[3].ptr, G2 * M, 2, *sc, 1, None, outs[0][0], outs[1][0],
+            None)                                                                           # type = 1: 'std'; then memspace 0: host
+    assert c._lib.jstsp_proposed_algorithm_f64(*args, 0) == E_UNSUPPORTED
+    assert last().startswith("proposed_algorithm (float64): 'std' has no float64 path") and last().endswith(": use jstsp_proposed_algorithm_c64")
+    assert c._lib.jstsp_proposed_resume_f64(*args, 0, None, None, 0) == E_UNSUPPORTED
+    assert last().startswith("proposed_algorithm resume (float64): 'std' has no float64 path")
+    assert last().endswith(": use jstsp_proposed_std_resume_f64")
 
 
 # ---- 4. the sweep that paid for its iterations twice ------------------------------------------------------------------------------

@@ -42,8 +42,8 @@ def _up(x):
 
 def both(name, fn, *args, **kw):
     """fn on numpy arguments (host memspace) and on the same as torch tensors (device memspace)"""
-    for mem, a in (("host", args), ("device", tuple(_up(x) for x in args))):
-        out = fn(*a, **{k: _up(v) for k, v in kw.items()})
+    for mem, a, k in (("host", args, kw), ("device", tuple(_up(x) for x in args), {k: _up(v) for k, v in kw.items()})):
+        out = fn(*a, **k)
         for i, o in enumerate(out if isinstance(out, tuple) else (out,)):
             if o is not None:
                 yield "%s/%s/%d" % (name, mem, i), _np(o)
@@ -106,6 +106,23 @@ def admm_cases():
         a = (g["subY"], g["Omega"], g["A"], g["B"], int(g["Imax"]), float(g["tau_Y"]), float(g["tau_Z"]), float(g["rho"]))
         yield from both("alg2/%s/approximate" % name, J.proposed_algorithm_f64, *a)
         yield from both("alg2/%s/angles" % name, J.proposed_algorithm_f64, *a, indx_S=np.asarray(g["indx_S"]))
+    import resume_problems as RP                                    # the resumed entries: from zero, legs (2, 4), from a foreign state
+    for name, shared in ((n, s) for n in ("R1", "R2") for s in (False, True)):
+        p = RP.problem(name, shared)
+        a, prm = (p["subY"], p["Omega"], p["A"], p["B"]), (p["tau_Y"], p["tau_S"], p["rho"])
+        for kind in ("approx", "angles", "std"):
+            fn = J.proposed_algorithm_std_resume_f64 if kind == "std" else J.proposed_algorithm_resume_f64
+            kw = {"indx_S": p["indx_S"]} if kind == "angles" else {}
+            tag = "resume64/%s/%s/%s" % (name, "sharedB" if shared else "ownB", kind)
+            yield from both(tag + "/zero6", lambda *x, **k: fn(*x[:4], 6, *x[4:], **k), *a, *prm, **kw)
+
+            def legs(*x, **k):
+                first = fn(*x[:4], 2, *x[4:], **k)
+                return first + fn(*x[:4], 4, *x[4:], state=first[3], it0=2, **k)
+            yield from both(tag + "/legs24", legs, *a, *prm, **kw)
+            if (name, shared) != ("R2", True):                      # tests/test_gpu_resume64.py: test_from_the_halved_state_of_another_trial
+                st = 0.5 * np.roll(_np(fn(*a, 3, *prm, **kw)[3]), -1, axis=0)
+                yield from both(tag + "/halved", lambda *x, **k: fn(*x[:4], 3, *x[4:], it0=3, **k), *a, *prm, state=st, **kw)
 
 
 def refusal_cases():
@@ -117,6 +134,13 @@ def refusal_cases():
     entries["proposed_std_f64"] = lambda lib, h, mem, _: lib.jstsp_proposed_std_f64(
         h, 512, 512, 512, 512, big, p(one), p(one), p(one), 512 * 512, p(one), 512 * 512, None, None, 3, d(W.ONES), d(W.ONES), d(W.ONES), None,
         p(one), p(one), p(one), None, mem)
+    # the resumed entries, with both state blocks in the layout
+    entries["proposed_resume_f64"] = lambda lib, h, mem, _: lib.jstsp_proposed_resume_f64(
+        h, 512, 512, 512, 512, big, p(one), p(one), p(one), 512 * 512, p(one), 512 * 512, 3, d(W.ONES), d(W.ONES), d(W.ONES), 0, None,
+        p(one), p(one), p(one), 0, p(one), p(one), mem)
+    entries["proposed_std_resume_f64"] = lambda lib, h, mem, _: lib.jstsp_proposed_std_resume_f64(
+        h, 512, 512, 512, 512, big, p(one), p(one), p(one), 512 * 512, p(one), 512 * 512, None, None, 3, d(W.ONES), d(W.ONES), d(W.ONES), None,
+        p(one), p(one), p(one), None, 0, p(one), p(one), mem)
     for name in sorted(entries):
         for mem in (W.HOST, W.DEVICE):
             rc = entries[name](lib, ctx.handle, mem, True)
