@@ -659,6 +659,37 @@ int jstsp_build_trials_tracked_drift_c32(jstsp_ctx *ctx, const jstsp_model *mode
 int jstsp_support_order_c32(jstsp_ctx *ctx, int Gr, int G2, int batch, const jstsp_c32 *S, int32_t *indx_S, int memspace);
 int jstsp_support_order_f64(jstsp_ctx *ctx, int Gr, int G2, int batch, const double *S, int32_t *indx_S, int memspace);
 
+/* The order of a support widened over neighbouring angle cells (csrc/support.hip): a support prior that can follow a peak which
+ * moves a cell per frame.  S: Gr x (Gt*L) x batch as jstsp_support_order_* takes it, column c = l*Gt + g transmit cell g of delay
+ * tap l; indx_S: (Gr*Gt*L) x batch, 1-based column-major linear indices.  In the key space of csrc/support_key.h (key =
+ * ~bits(|z|^2), NaN -> 0, a smaller key is a larger magnitude):
+ *    own(r, l, g) = key(S(r, l*Gt + g))
+ *    nbr(r, l, g) = min over |dr| <= wr, |dg| <= wt of own((r + dr) mod Gr, l, (g + dg) mod Gt)
+ *  - Both angle grids are DFT grids (wideband_mmwave_channel.m:9-10), so the window is circular in r and in g; it never crosses
+ *    a delay block: g wraps inside its own l.
+ *  - primary = 0 ("neighbourhood"): ascending (nbr, own, index) - a strong entry, directly followed by its window in order of the
+ *    window entries' own magnitude.  primary = 1 ("ties"): ascending (own, nbr, index) - the plain order, equal own keys (the exact
+ *    zeros of a masked, thresholded S) ordered by their strongest neighbour instead of by index.
+ *  - wr = wt = 0: nbr == own, and either primary is jstsp_support_order_* on the bits (and takes its route).  A NaN propagates to
+ *    its window (key 0), as it would in MATLAB's max.
+ *  - Route: one kernel reads S once and writes own and nbr - per (trial, delay block, tile) the keys in LDS (64 x 64 at most),
+ *    the minimum along the rows, then along the columns; a block of at most 64 x 64 wraps by its LDS index, a larger one is
+ *    tiled with a halo read through the ring.  Then the _f64 route of jstsp_support_order_* with one more field: the own keys
+ *    sorted alone, class = lower bound in that list (nbr values are own keys), the words (class_a << 2w | class_b << w | index)
+ *    sorted over 3w bits.  An order is a function of its own trial alone: of no batch, no chunk and no memspace.  COST: two radix
+ *    sorts of Gr*Gt*L*batch 64-bit words in either precision; workspace 32 bytes per entry plus the sort's own.  Both memspaces.
+ *  - Refused, indx_S untouched: JSTSP_E_SHAPE - Gr, Gt, L or batch not positive, or Gr*Gt*L > 2^21 (3w <= 63 bits);
+ *    JSTSP_E_ARG - a negative radius; JSTSP_E_ARG - 2*wr+1 > Gr or 2*wt+1 > Gt (the window would meet itself round the ring);
+ *    JSTSP_E_ARG - primary not 0 or 1; JSTSP_E_NULL - a NULL array.
+ *  Asserted (tests/test_gpu_support_order_wide.py), exact against the numpy reference of tests/wide_ref.py in both precisions and
+ *  both primaries: engineered 6 x 4 x 3 trials (corner spikes, overlapping windows, ties, zeros, a NaN and an Inf) at five radii,
+ *  5 x 7 at the largest legal window, a 64 x 512 trial, a tiled 64 x 512 x 1 and a 150 x 70 x 1 block at a radius above one
+ *  launch's halo; radius 0 equal to jstsp_support_order_*; no batch or memspace dependence; the solver round trip; the refusals. */
+int jstsp_support_order_wide_c32(jstsp_ctx *ctx, int Gr, int Gt, int L, int batch, const jstsp_c32 *S,
+                                 int wr, int wt, int primary, int32_t *indx_S, int memspace);
+int jstsp_support_order_wide_f64(jstsp_ctx *ctx, int Gr, int Gt, int L, int batch, const double *S,
+                                 int wr, int wt, int primary, int32_t *indx_S, int memspace);
+
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
  * JSTSP_BF_QUANTIZED ('quantized') and JSTSP_BF_QUANTIZED4 ('quantized_4'): W (N x N, column-major, same memspace).  The

@@ -108,6 +108,8 @@ SIGNATURES = {
                                                      C.c_double, C.POINTER(Trials), c_void_p, c_void_p, c_int]),
     "jstsp_support_order_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     "jstsp_support_order_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    "jstsp_support_order_wide_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
+    "jstsp_support_order_wide_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "jstsp_beamformer_c32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int]),
     "jstsp_ase_c32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p,
                               c_int]),

@@ -874,11 +874,15 @@ def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, swee
 
 
 TRACKING_MODES = ("cold", "warm", "warm_vs")
-TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev")       # accepted beside the default three: they pass an indx_S
+# accepted beside the default three: they pass an indx_S (the last two: of support_order_wide*)
+TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev")
+_PREV_MODES = ("pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev")
+_WIDE_MODES = ("pai_wide_prev", "warm_pai_wide_prev")
 
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
-                 precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None):
+                 precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
+                 widen_primary="neighbourhood"):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -896,6 +900,9 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
       pai_prev       from zero, with ``support_order`` (``support_order_f64``) of the S this (mode, Imax) chain returned at the
                      previous frame - what a receiver has; frame 0 is solved without ``indx_S``
       warm_pai_prev  from the previous frame's whole state, ``indx_S`` as ``pai_prev``
+    and the same two with the order widened over neighbouring angle cells:
+      pai_wide_prev, warm_pai_wide_prev  ``pai_prev`` / ``warm_pai_prev`` with ``support_order_wide`` (``_f64``) at the radii
+                     ``widen = (wr, wt)`` and ``widen_primary`` ("neighbourhood" or "ties") in place of ``support_order``
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
@@ -903,7 +910,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
 
     Returns the dictionary tools/run_tracking.py prints - per (mode, Imax) ``mean_nmse`` over the scored frames, ``sem_over_seqs``,
     ``median_nmse``, ``mean_nmse_by_frame`` and ``estimates_per_s`` (solver time only, frame 0 left out) - plus
-    ``"channel": "device"``, and ``"drift"`` when one was given."""
+    ``"channel": "device"``, ``"drift"`` when one was given, and ``"widen"``, ``"widen_primary"`` when a wide mode was asked for."""
     import time
     import numpy as np
     from . import solvers as J
@@ -921,6 +928,17 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         drift = float(drift)
         if not (np.isfinite(drift) and drift >= 0.0):
             raise ValueError("drift must be finite and >= 0, not %r" % (drift,))
+    try:
+        wr, wt = (int(x) for x in widen)
+    except (TypeError, ValueError):
+        raise ValueError("widen must be a pair (wr, wt) of radii, not %r" % (widen,)) from None
+    if wr < 0 or wt < 0:
+        raise ValueError("widen must be a pair of radii >= 0, not %r" % (widen,))
+    if widen_primary not in ("neighbourhood", "ties"):
+        raise ValueError("widen_primary must be 'neighbourhood' or 'ties', not %r" % (widen_primary,))
+    if any(m in _WIDE_MODES for m in modes) and (2 * wr + 1 > p.Gr or 2 * wt + 1 > p.Gt):
+        raise ValueError("widen = %r: a window of %d x %d cells meets itself round the %d x %d angle grid"
+                         % ((wr, wt), 2 * wr + 1, 2 * wt + 1, p.Gr, p.Gt))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -931,6 +949,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     solve = J.proposed_algorithm_resume_f64 if f64 else J.proposed_algorithm_resume
     score = J.nmse_spectral_f64 if f64 else J.nmse_spectral
     order = J.support_order_f64 if f64 else J.support_order
+    order_wide = J.support_order_wide_f64 if f64 else J.support_order_wide
     keys = [("cold", i) for i in sorted(set(imax + [int(cold_imax)])) if "cold" in modes] + \
            [(m, i) for m in ("warm", "warm_vs") + TRACKING_PAI_MODES if m in modes for i in imax]
     frame_kw = {} if drift is None else {"drift": drift}
@@ -948,7 +967,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
             zb = wide(inp["Zbar"])
             for k in keys:
                 mode, n_it = k
-                warm = mode in ("warm", "warm_vs", "warm_pai_prev")
+                warm = mode in ("warm", "warm_vs", "warm_pai_prev", "warm_pai_wide_prev")
                 st = state.get(k) if warm else None
                 if st is not None and mode == "warm_vs":
                     st = st.clone()
@@ -956,7 +975,9 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 ix = {}
                 if mode == "pai":
                     ix = {"indx_S": inp["indx_S"]}
-                elif mode in ("pai_prev", "warm_pai_prev") and k in prev_S:
+                elif mode in _WIDE_MODES and k in prev_S:
+                    ix = {"indx_S": order_wide(prev_S[k], p.Gt, wr, wt, primary=widen_primary)}
+                elif mode in _PREV_MODES and k in prev_S:
                     ix = {"indx_S": order(prev_S[k])}               # (not timed: the solver's rate is what estimates_per_s reports)
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
@@ -965,7 +986,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 dt = time.perf_counter() - c0
                 if warm:
                     state[k] = out
-                if mode in ("pai_prev", "warm_pai_prev"):
+                if mode in _PREV_MODES:
                     prev_S[k] = S
                 if f:
                     secs[k] += dt
@@ -986,4 +1007,6 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
            "cold_imax": int(cold_imax), "results": [summary(k) for k in keys], "channel": "device"}
     if drift is not None:
         res["drift"] = drift
+    if any(m in _WIDE_MODES for m in modes):
+        res["widen"], res["widen_primary"] = [wr, wt], widen_primary
     return res

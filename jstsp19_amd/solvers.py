@@ -34,7 +34,8 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "OMP_f64", "omp_kron_f64", "sparse_admm_f64", "proposed_algorithm_std_f64", "proposed_algorithm_angles_std_f64",
            "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64",
            "admm_state_elems", "proposed_algorithm_resume_f64", "proposed_algorithm_std_resume_f64",
-           "proposed_algorithm_resume", "proposed_algorithm_angles_resume", "support_order", "support_order_f64"]
+           "proposed_algorithm_resume", "proposed_algorithm_angles_resume", "support_order", "support_order_f64",
+           "support_order_wide", "support_order_wide_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1465,3 +1466,45 @@ def support_order_f64(S, *, ctx=None):
     """:func:`support_order` for a complex128 ``S`` without narrowing (``jstsp_support_order_f64``): the key is ``|z|^2`` in
     float64.  Arguments and result as :func:`support_order`."""
     return _support_order_call("jstsp_support_order_f64", S, np.complex128, ctx)
+
+
+_WIDE_PRIMARY = {"neighbourhood": 0, "ties": 1}
+
+
+def _support_order_wide_call(entry, S, Gt, wr, wt, primary, np_dtype, ctx):
+    if primary not in _WIDE_PRIMARY:
+        raise ValueError("primary must be 'neighbourhood' or 'ties', not %r" % (primary,))
+    Gt, wr, wt = int(Gt), int(wr), int(wt)
+    a_S = _Arg(S, np_dtype, "S")
+    if Gt < 1 or a_S.C % Gt:
+        raise ValueError("Gt = %d must divide the %d columns of S (column l*Gt + g is transmit cell g of delay tap l)" % (Gt, a_S.C))
+    c, mem, dev = _ctx_for([a_S], ctx)
+    batch, Gr, G2 = a_S.batch, a_S.R, a_S.C
+    if mem == DEVICE:
+        import torch
+        out = torch.empty((batch, Gr * G2), dtype=torch.int32, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty((batch, Gr * G2), dtype=np.int32)
+        optr = out.ctypes.data
+    check(getattr(c._lib, entry)(c.handle, Gr, Gt, G2 // Gt, batch, a_S.ptr, wr, wt, _WIDE_PRIMARY[primary], optr, mem), entry)
+    return out
+
+
+def support_order_wide(S, Gt, wr=1, wt=1, *, primary="neighbourhood", ctx=None):
+    """:func:`support_order` widened over neighbouring angle cells (``jstsp_support_order_wide_c32``, csrc/support.hip): a support
+    that can follow a peak which moves a cell per frame.  ``S`` and the result as :func:`support_order`; column ``l*Gt + g`` of ``S``
+    is transmit cell ``g`` of delay tap ``l``, so ``Gt`` must divide the column count.  With ``own`` the key of an entry and ``nbr``
+    the smallest key (largest magnitude) of its ``(2 wr + 1) x (2 wt + 1)`` window - circular in both angle grids, inside its own
+    delay tap - the order is ascending ``(nbr, own, index)`` for ``primary="neighbourhood"`` (a strong entry, then its window) and
+    ``(own, nbr, index)`` for ``"ties"`` (the plain order; equal keys, the exact zeros of a thresholded ``S``, by their strongest
+    neighbour).  ``wr = wt = 0`` is :func:`support_order` on the bits.  ``ValueError`` for a ``Gt`` that does not divide the columns
+    or an unknown ``primary``, before anything touches a device; ``JstspError`` (code -4) for a negative radius or a window wider
+    than its grid, (code -2) for more than 2^21 entries per trial."""
+    return _support_order_wide_call("jstsp_support_order_wide_c32", S, Gt, wr, wt, primary, np.complex64, ctx)
+
+
+def support_order_wide_f64(S, Gt, wr=1, wt=1, *, primary="neighbourhood", ctx=None):
+    """:func:`support_order_wide` for a complex128 ``S`` without narrowing (``jstsp_support_order_wide_f64``): the key is ``|z|^2``
+    in float64.  Arguments and result as :func:`support_order_wide`."""
+    return _support_order_wide_call("jstsp_support_order_wide_f64", S, Gt, wr, wt, primary, np.complex128, ctx)

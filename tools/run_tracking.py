@@ -23,6 +23,9 @@ With --device-channel, --modes also takes the "Proposed - PAI" variants (DESIGN.
 own true support order (the genie of plot_errorVSsnr.m:143-145); pai_prev: from zero with the order of the chain's previous
 estimate (support_order on the device); warm_pai_prev: the previous frame's whole state and that order - and --drift SIGMA lets the
 angles of every sequence walk, SIGMA radians of standard deviation per frame, so the support moves across the dictionary grid.
+pai_wide_prev and warm_pai_wide_prev are pai_prev and warm_pai_prev with the order widened over the
+neighbouring angle cells (support_order_wide): --widen WR,WT cells each way on the receive and transmit grid, --widen-primary
+neighbourhood (a strong entry, then its window) or ties (the plain order, its exact zeros by their strongest neighbour).
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -52,11 +55,22 @@ ap.add_argument("--sweep-idx", type=int, default=0, help="--device-channel: the 
 ap.add_argument("--drift", type=float, default=None, metavar="SIGMA",
                 help="--device-channel: random walk of every path angle, SIGMA rad per frame (default: fixed angles)")
 ap.add_argument("--modes", nargs="+", default=None,
-                choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev"),
+                choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev"),
                 help="--device-channel: the columns to run (default: cold warm warm_vs)")
+ap.add_argument("--widen", default=None, metavar="WR,WT",
+                help="--device-channel: the radii of pai_wide_prev / warm_pai_wide_prev in grid cells (default: 1,1)")
+ap.add_argument("--widen-primary", choices=("neighbourhood", "ties"), default=None,
+                help="--device-channel: what the widened order sorts by first (default: neighbourhood)")
 a = ap.parse_args()
-if (a.drift is not None or a.modes is not None) and not a.device_channel:
-    ap.error("--drift and --modes need --device-channel")
+if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None) and not a.device_channel:
+    ap.error("--drift, --modes, --widen and --widen-primary need --device-channel")
+if a.widen is not None:
+    try:
+        a.widen = tuple(int(x) for x in a.widen.split(","))
+    except ValueError:
+        a.widen = ()
+    if len(a.widen) != 2 or min(a.widen) < 0:
+        ap.error("--widen takes two radii >= 0 as WR,WT")
 
 p = SweepParams(Nt=4, Nr=32, L=4, T=35, Mr=4, snr_db=a.snr_db) if a.small else SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=a.snr_db)
 
@@ -71,6 +85,10 @@ def emit(res):
 if a.device_channel:
     from jstsp19_amd.montecarlo import run_tracking
     kw = {} if a.modes is None else {"modes": tuple(a.modes)}
+    if a.widen is not None:
+        kw["widen"] = a.widen
+    if a.widen_primary is not None:
+        kw["widen_primary"] = a.widen_primary
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)

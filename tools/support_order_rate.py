@@ -2,7 +2,9 @@
 """What the runner's pai_prev modes pay per frame for the order of a support: support_order_f64 and
 support_order on 256 x (64 x 512), once on a solver's sparse S (proposed_algorithm_resume_f64, Imax 20, with the true indx_S: at
 most 110 non-zeros per trial) and once on a dense Zbar, timed by HIP events - beside the only alternative without them, a copy of
-S to the host and a stable numpy argsort of -|z|^2 per trial on 16 threads.  Prints ONE JSON line; no bound is asserted."""
+S to the host and a stable numpy argsort of -|z|^2 per trial on 16 threads.  In the same run, what the pai_wide_prev modes pay
+(DESIGN.md section 9q): support_order_wide_f64 and support_order_wide at Gt = 64 and --widen WR,WT (default 1,1), "neighbourhood"
+and "ties".  Prints ONE JSON line; no bound is asserted."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from concurrent.futures import ThreadPoolExecutor
@@ -16,8 +18,10 @@ ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--threads", type=int, default=16)
+ap.add_argument("--widen", default="1,1", metavar="WR,WT", help="the radii of the support_order_wide rows")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
 a = ap.parse_args()
+wr, wt = (int(x) for x in a.widen.split(","))
 
 p = SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=5.0)                  # BASELINE configs[1]: Gr x G2 = 64 x 512
 dev = torch.device("cuda:0")
@@ -70,7 +74,7 @@ def stats(ms):
             "p10_ms": float(np.percentile(ms, 10)), "p90_ms": float(np.percentile(ms, 90)), "reps": int(ms.size)}
 
 
-res = {"tool": "support_order_rate", "shape": [64, 512], "batch": a.batch, "threads": a.threads, "results": []}
+res = {"tool": "support_order_rate", "shape": [64, 512], "batch": a.batch, "threads": a.threads, "widen": [wr, wt], "results": []}
 for name, x in inputs.items():
     nnz = float((x != 0).sum(dim=(1, 2)).double().mean())
     narrow = J.colmajor(x.to(torch.complex64))
@@ -78,6 +82,11 @@ for name, x in inputs.items():
     same = bool(np.array_equal(J.support_order_f64(x).cpu().numpy(), href))
     for label, fn, arg in (("support_order_f64", J.support_order_f64, x), ("support_order", J.support_order, narrow)):
         res["results"].append(dict(input=name, mean_nonzeros_per_trial=nnz, method=label, **stats(device_ms(fn, arg))))
+    for primary in ("neighbourhood", "ties"):
+        for label, fn, arg in (("support_order_wide_f64", J.support_order_wide_f64, x), ("support_order_wide", J.support_order_wide, narrow)):
+            wide = lambda z, fn=fn, primary=primary: fn(z, p.Gt, wr, wt, primary=primary)
+            res["results"].append(dict(input=name, mean_nonzeros_per_trial=nnz, method=label, primary=primary,
+                                       **stats(device_ms(wide, arg))))
     res["results"].append(dict(input=name, mean_nonzeros_per_trial=nnz, method="d2h_plus_numpy_stable_argsort",
                                equals_support_order_f64=same, **stats(hms)))
 print(json.dumps(res))
