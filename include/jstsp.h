@@ -690,6 +690,30 @@ int jstsp_support_order_wide_c32(jstsp_ctx *ctx, int Gr, int Gt, int L, int batc
 int jstsp_support_order_wide_f64(jstsp_ctx *ctx, int Gr, int Gt, int L, int batch, const double *S,
                                  int wr, int wt, int primary, int32_t *indx_S, int memspace);
 
+/* The head of an order without the sort (csrc/support_top.hip, the kernel in csrc/support_top.h): indx_top(:, t), count x batch,
+ * 1-based, is the first `count` entries of jstsp_support_order_f64 of trial t, bit for bit.  V: Gr x G2 x batch interleaved
+ * (re, im) doubles, the memory of a jstsp_c64 array.
+ *  - Key and order: support_key(double2) of csrc/support_key.h, ascending key, equal keys in ascending index; a NaN first, then
+ *    +Inf - the order of jstsp_support_order_f64.
+ *  - 1 <= count <= min(Gr*G2, JSTSP_SUPPORT_TOP_MAX); JSTSP_E_ARG otherwise.  The other refusals are those of
+ *    jstsp_support_order_f64 (JSTSP_E_SHAPE, JSTSP_E_NULL, a bad memspace).  Nothing is written on a refusal.
+ *  - Route: one workgroup of 1024 threads per trial, one launch for the batch.  A radix select on the 64-bit key (eight
+ *    histogram passes, top byte first) gives the count-th key thr; the entries with key < thr are compacted into LDS; those with
+ *    key == thr are admitted in ascending index by an ordered ballot count until count is reached and written straight to
+ *    their places, so a tie class of any size - the exact zeros of a thresholded S - costs no LDS; the strict part is sorted in
+ *    LDS by (key, index) with a bitonic network.  Static LDS 48 KiB (4096 keys and indices) plus a histogram; no dynamic LDS.
+ *  - Every count is an integer sum in a fixed order: a trial's list depends on no batch and no memspace.
+ *  - No workspace on the device path; a JSTSP_HOST call stages V and the list in the context's arena, per chunk of at most
+ *    2^31 - 1 entries.  COST: ten reads of the trial, which stays in L2; no vendor sort.
+ *  - The same kernel has a second writer, rank[e] for every entry of the trial (position in the list, or 0x7fffffff): what
+ *    jstsp_proposed_refresh_f64 runs inside its loop.
+ *  Asserted (tests/test_gpu_support_top.py), exact against jstsp_support_order_f64(V)(1:count, :) and a stable host argsort:
+ *  engineered 6 x 4 x 3 trials with duplicate magnitudes across the threshold, a NaN and an +Inf; g = 1, 255, 257; count = 1 and
+ *  count = g; 64 x 128 with 6000 exact zeros at count 4096 (a tie class larger than the LDS list); 64 x 512 at counts 4096 and
+ *  510; values scaled by 2^+-500; an all-zero trial; no batch or memspace dependence; the refusals. */
+#define JSTSP_SUPPORT_TOP_MAX 4096
+int jstsp_support_top_f64(jstsp_ctx *ctx, int Gr, int G2, int batch, const double *V, int count, int32_t *indx_top, int memspace);
+
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
  * JSTSP_BF_QUANTIZED ('quantized') and JSTSP_BF_QUANTIZED4 ('quantized_4'): W (N x N, column-major, same memspace).  The
@@ -1187,6 +1211,42 @@ int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, 
                                   const int32_t *indx_S,
                                   jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out,
                                   int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace);
+
+/* ---- the float64 ADMM with its support refreshed from its own iterate (csrc/proposed64.hip) ------------
+ * Alg. 2 ('approximate') only: the body of jstsp_proposed_resume_f64 with a support policy.  A "Proposed - PAI" whose indx_S is
+ * the top of the solver's own v, taken inside the loop by the selection kernel of jstsp_support_top_f64: nothing comes back to the
+ * host and no vendor sort runs.  With g = Gr*G2, R = min(g, JSTSP_SUPPORT_TOP_MAX), i = it0 + it the global 1-based iteration
+ * and cnt(i) = min(10 + 5 i, g) (angles :36):
+ *  - refresh iterations: i > refresh_start and (i - refresh_start - 1) % refresh_period == 0 for refresh_period >= 1; only
+ *    i == refresh_start + 1 for refresh_period == 0.  A function of the global index, never of call boundaries.
+ *  - at a refresh iteration the gradient step runs without a mask (v and convergence_error(:, 3) do not depend on the mask), the
+ *    top R of the new v become the rank, and S = soft(v) .* [rank < cnt(i)] is rewritten from the stored v by the expression of
+ *    the step: the bits a masked step would have written.
+ *  - at every other iteration the step runs under the rank in force - that of the last refresh; before the first refresh of the
+ *    call that of indx_S, or none when indx_S is NULL.  indx_S: n_indx entries per trial, 1-based, stride n_indx; entries outside
+ *    1..g are ignored, entries that are not listed are never admitted.
+ *  - LIMIT: a refreshed order lists R entries and entries outside it are never admitted: for g > 4096 the mask stops growing at
+ *    4096 entries, from iteration 818 on (the reference runs 100).
+ *  - indx_out (R x batch, 1-based; NULL: not wanted): the list of the call's last refresh, written if and only if the call ran a
+ *    refresh - a function of it0, Imax, refresh_start and refresh_period.  A later leg passes it as indx_S with n_indx = R, the
+ *    same start and period and its own it0: legs return the bits of the uninterrupted call (for min(N, M) <= 64; above, the note
+ *    on the global Jacobi of jstsp_proposed_algorithm_f64 applies).
+ *  - JSTSP_E_ARG: refresh_start < 0, refresh_period < 0, n_indx outside 1..g with indx_S, n_indx != 0 without it; it0 and the
+ *    states as jstsp_proposed_resume_f64.  Limits, the workspace and its 24 GiB refusal are the family's; the rank array exists
+ *    in every call.  The other entries keep their bits: the policy is off for them.
+ * Asserted (tests/test_gpu_refresh64.py): with refresh_start >= it0 + Imax the bits of jstsp_proposed_resume_f64; for four
+ * policies S, Y, convergence_error, the state and the order equal to the chain of one-iteration calls of the existing entries
+ * with jstsp_support_order_f64 between them, bit for bit; legs that pass the order on; S and Y within 1e-10 of max|ref| and
+ * convergence_error within 1e-8 of tests/refresh_ref.py; the refusals. */
+int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                               const jstsp_c64 *subY, const double *Omega,
+                               const jstsp_c64 *A, long long strideA,
+                               const jstsp_c64 *B, long long strideB,
+                               int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                               const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                               jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                               int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out,
+                               int32_t *indx_out, int memspace);
 
 /* ---- joint OMP and matrix completion in float64 -----------------------------------------------------
  * The "OMP with MMV" column (plot_errorVSsnr.m:116-117) and the TSSR / "SVT-based" recipe (:151-162) evaluated in FLOAT64 on the

@@ -158,6 +158,14 @@ for _n, _sib in (("jstsp_proposed_resume_f64", "jstsp_proposed_algorithm_f64"), 
                  ("jstsp_proposed_resume_c32", "jstsp_proposed_algorithm_c32"), ("jstsp_proposed_resume_c64", "jstsp_proposed_algorithm_c64")):
     SIGNATURES[_n] = (c_int, SIGNATURES[_sib][1][:-1] + [c_int, c_void_p, c_void_p, c_int])
 
+# the head of an order by a selection kernel (csrc/support_top.hip), and the float64 ADMM that refreshes its support with it
+# (csrc/proposed64.hip): ... rho, indx_S, n_indx, refresh_start, refresh_period, S, Y, ce, it0, state_in, state_out, indx_out, memspace
+SUPPORT_TOP_MAX = 4096
+SIGNATURES["jstsp_support_top_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int])
+SIGNATURES["jstsp_proposed_refresh_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
+                                                    c_void_p, c_ll, c_int, c_dp, c_dp, c_dp, c_void_p, c_int, c_int, c_int,
+                                                    c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int])
+
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes
     # (pointers are void* here, so the two are one list)

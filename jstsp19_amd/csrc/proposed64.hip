@@ -26,7 +26,15 @@
 // rest of the iteration is the list above, kernel for kernel; G_A, G_B, the carried V, Res and RRes do not exist and
 // convergence_error(:, 3) stays 0 (:6).  The two entries share one host frame, Admm64 below: parameters, the shared layout, the
 // zeroing, head (Z, svt, X, K) and tail (A S B, C, V1, V2, convergence_error); each writes its own S-step between the two.
+//
+// jstsp_proposed_refresh_f64 - Alg. 2 with a support policy (Refresh64 below): at the refresh iterations the mask is the top of the
+// solver's own new v, taken by the selection kernel of support_top.h between the gradient step and A S B - one launch for the
+// batch, nothing read back, no vendor sort and none of its workspace inside the slab.  The body is admm64_approx; with no policy
+// (every other entry) not one launch differs.
+//  Asserted (tests/test_gpu_refresh64.py): without a refresh in the call the bits of jstsp_proposed_resume_f64; with one, the bits
+//  of the chain of one-iteration calls with jstsp_support_order_f64 between them; legs; tests/refresh_ref.py within 1e-10 / 1e-8.
 #include "pinv64.h"
+#include "support_top.h"
 #include "svt64.h"
 
 #include <algorithm>
@@ -105,16 +113,16 @@ __global__ __launch_bounds__(256) void sub64_kernel(long long n, double2 *R, con
     }
 }
 
-// rank[e] = position of entry e (0-based) in indx_S (1-based linear indices); an index outside 1 .. g is ignored
+// rank[e] = position of entry e (0-based) in indx_S (1-based linear indices, n per trial); an index outside 1 .. g is ignored
 __global__ __launch_bounds__(256) void rank64_init_kernel(long long n, int32_t *rank)
 {
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) rank[e] = 0x7fffffff;
 }
-__global__ __launch_bounds__(256) void rank64_kernel(int g, const int32_t *indx, int32_t *rank)
+__global__ __launch_bounds__(256) void rank64_kernel(int g, int n, const int32_t *indx, int32_t *rank)
 {
-    const long long o = (long long)blockIdx.y * g;
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < g; p += gridDim.x * 256) {
-        const int32_t e = indx[o + p] - 1;
+    const long long o = (long long)blockIdx.y * g, oi = (long long)blockIdx.y * n;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+        const int32_t e = indx[oi + p] - 1;
         if (e >= 0 && e < g) atomicMin(&rank[o + e], p);
     }
 }
@@ -232,6 +240,8 @@ struct Admm64 {
     const jstsp_c64 *subY_; const double *Omega_; const jstsp_c64 *A_, *B_; const int32_t *indx_;
     jstsp_c64 *S_out, *Y_out; double *ce_out;
     bool host;
+    int n_indx = 0;                                 // entries per trial of indx_ (0: all Gr G2, what every entry but the refreshed one passes)
+    bool refresh = false;                           // the refreshed solve: a rank array even without indx_
     std::vector<Par64> hp;                          // the arrays: parameters, shared inputs, outputs, state of the iteration
     const Par64 *par; const double2 *subY, *A, *B; const double *Omega; const int32_t *indx = nullptr;
     double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *T, *W, *gws = nullptr;
@@ -243,6 +253,7 @@ struct Admm64 {
     bool want_ce() const { return ce_out != nullptr; }
     size_t nm1() const { return (size_t)N * M; }
     size_t g1() const { return (size_t)Gr * G2; }
+    size_t n1() const { return n_indx ? (size_t)n_indx : g1(); }
     Mat64 Am() const { return Mat64{A, strideA, N}; }
     Mat64 Bm() const { return Mat64{B, strideB, G2}; }
     dim3 gnm() const { return egrid((long long)nm1(), batch); }
@@ -260,13 +271,13 @@ struct Admm64 {
         Omega = w.in(Omega_, enm, host);
         A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
         B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
-        if (angles()) indx = w.in(indx_, eg, host);
+        if (angles()) indx = w.in(indx_, n1() * b, host);
         Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
         Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
         ced = w.out(ce_out, (size_t)3 * Imax * b, host);
         for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
         T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
-        if (angles()) rank = w.get<int32_t>(eg);
+        if (angles() || refresh) rank = w.get<int32_t>(eg);
         for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
         sv.layout(w, N, M, b);
     }
@@ -277,7 +288,7 @@ struct Admm64 {
         for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm1() * batch * sizeof(double2), st));
         if (angles()) {
             hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
-            hipLaunchKernelGGL(rank64_kernel, egrid((long long)g1(), batch), dim3(256), 0, st, (int)g1(), indx, rank);
+            hipLaunchKernelGGL(rank64_kernel, egrid((long long)n1(), batch), dim3(256), 0, st, (int)g1(), (int)n1(), indx, rank);
         }
         return 0;
     }
@@ -356,12 +367,33 @@ int resume64_args(const char *nmf, int Imax, int it0, const void *state_in)
     return 0;
 }
 
-// Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state) and of jstsp_proposed_resume_f64: iterations
-// it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the entry in every message; std_entry is where its 'std' refusal points.
+// The support policy of jstsp_proposed_refresh_f64 (every other entry passes none, and the hook is off): at a refresh iteration -
+// a function of the GLOBAL 1-based index i = it0 + it, never of a call boundary - the gradient step runs without a mask, the
+// selection kernel of support_top.h ranks the top R = min(Gr G2, ST_MAX) entries of the new v, and soft_mask64_kernel rewrites S
+// from the stored v under that rank: the expression of step_v64_kernel on the value it stored, hence the bits a masked step would
+// have written.  The rank stays in force until the next refresh; before the call's first one the rank of indx_S is, or none.
+struct Refresh64 {
+    int n_indx, start, period;
+    int32_t *indx_out;
+    bool at(long long i) const { return i > start && (period ? (i - start - 1) % period == 0 : i == (long long)start + 1); }
+};
+
+int refresh64_args(const char *nmf, const Refresh64 &rf, const int32_t *indx_S, long long g)
+{
+    JSTSP_REQUIRE(rf.start >= 0 && rf.period >= 0, JSTSP_E_ARG, "%s: refresh_start = %d, refresh_period = %d: neither may be negative", nmf,
+                  rf.start, rf.period);
+    JSTSP_REQUIRE(indx_S ? rf.n_indx >= 1 && rf.n_indx <= g : rf.n_indx == 0, JSTSP_E_ARG,
+                  "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, rf.n_indx, g);
+    return 0;
+}
+
+// Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state), of jstsp_proposed_resume_f64 and - with a
+// support policy rf - of jstsp_proposed_refresh_f64: iterations it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the
+// entry in every message; std_entry is where its 'std' refusal points.
 int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_,
                   const double *Omega_, const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
                   const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
-                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace, const Refresh64 *rf = nullptr)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
@@ -373,11 +405,19 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
                   "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use %s", nmf, std_entry);
     JSTSP_TRY(resume64_args(nmf, Imax, it0, state_in));
     JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
+    if (rf) JSTSP_TRY(refresh64_args(nmf, *rf, indx_S_, (long long)Gr * G2));
     Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
     f.make_par(tau_Y, tau_S, rho);
     hipStream_t st = ctx->stream;
     const size_t g1 = f.g1(), g = g1 * batch;
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
+    const int R = (int)std::min<size_t>(g1, ST_MAX);               // entries of a refreshed order
+    bool runs_refresh = false;                                      // a function of it0, Imax, start and period alone
+    if (rf) {
+        f.n_indx = rf->n_indx; f.refresh = true;
+        for (int it = 0; it < Imax && !runs_refresh; ++it) runs_refresh = rf->at((long long)it0 + it + 1);
+    }
+    int32_t *top = nullptr;                                         // the list of the call's last refresh, for indx_out
 
     double2 *V, *S, *Res, *RRes, *T2, *GA, *GB, *sout = nullptr;
     const double2 *sin = nullptr;
@@ -390,6 +430,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         f.gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
         if (state_in) sin = w.in(reinterpret_cast<const double2 *>(state_in), f.state1() * b, f.host);
         if (state_out) sout = w.out(reinterpret_cast<double2 *>(state_out), f.state1() * b, f.host);
+        if (rf && rf->indx_out && runs_refresh) top = w.out(rf->indx_out, (size_t)R * b, f.host);
     }));
     JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
 
@@ -401,7 +442,9 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     double2 *T = f.T, *gws = f.gws;
     JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr, gws));          // G_A = A^H A
     JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, Bm, Bm, GB, (long long)G2 * G2, G2, gws));          // G_B = B B^H
+    bool in_force = f.angles();                                     // a rank masks S: that of indx_S, then that of the last refresh
     for (int it = 0; it < Imax; ++it) {
+        const bool fresh = rf && rf->at((long long)it0 + it + 1);
         JSTSP_TRY(f.head(st));
         JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, M, N, batch, Am, Mat64{f.K, sNM, N}, T, (long long)Gr * M, Gr, gws));      // A^H K
         JSTSP_TRY(zgemm64(st, 'N', 'C', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Bm, Res, sG, Gr, gws));     // ... B^H
@@ -410,13 +453,20 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         hipLaunchKernelGGL(sub64_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, Res, RRes);
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{Res, sG, Gr}, T2, sG, Gr, gws));                 // G_A Res
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
-        hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S, f.rank, f.mask_count(it0 + it),
-                           f.want_ce() ? f.ce3 : nullptr);
+        hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S,
+                           in_force && !fresh ? f.rank : (const int32_t *)nullptr, f.mask_count(it0 + it), f.want_ce() ? f.ce3 : nullptr);
+        if (fresh) {                                                // the order of the new v, and S again under it
+            hipLaunchKernelGGL(support_top_kernel, dim3(batch), dim3(ST_THREADS), 0, st, (int)g1, R, V, top, f.rank);
+            hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, f.par, V, S, f.rank,
+                               f.mask_count(it0 + it));
+            in_force = true;
+        }
         JSTSP_TRY(f.tail(st, S, it));
     }
     JSTSP_HIP(hipMemcpyAsync(f.Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
     if (sout) JSTSP_TRY(f.store_state(st, sout, V, S));
     if (sout && f.host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
+    if (top && f.host) JSTSP_TRY(s.copy_back(rf->indx_out, top, (size_t)R * batch));
     return f.deliver(s);
 }
 
@@ -608,6 +658,19 @@ int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int 
 {
     return admm64_approx(ctx, "proposed_algorithm resume (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA,
                          B_, strideB, Imax, tau_Y, tau_S, rho, type, indx_S_, S_out, Y_out, ce_out, it0, state_in, state_out, memspace);
+}
+
+// Alg. 2 with the support refreshed from its own iterate (Refresh64 above); the limit of a refreshed order is ST_MAX entries
+int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                               const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
+                               const double *tau_S, const double *rho, const int32_t *indx_S_, int n_indx, int refresh_start,
+                               int refresh_period, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, int it0, const jstsp_c64 *state_in,
+                               jstsp_c64 *state_out, int32_t *indx_out, int memspace)
+{
+    const Refresh64 rf{n_indx, refresh_start, refresh_period, indx_out};
+    return admm64_approx(ctx, "proposed_algorithm refresh (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_,
+                         strideA, B_, strideB, Imax, tau_Y, tau_S, rho, JSTSP_TYPE_APPROXIMATE, indx_S_, S_out, Y_out, ce_out, it0, state_in,
+                         state_out, memspace, &rf);
 }
 
 int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,

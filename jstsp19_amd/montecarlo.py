@@ -874,15 +874,17 @@ def run_rank(points, n_trials=1, *, n_keep=None, batch=4096, seed=20190913, swee
 
 
 TRACKING_MODES = ("cold", "warm", "warm_vs")
-# accepted beside the default three: they pass an indx_S (the last two: of support_order_wide*)
-TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev")
-_PREV_MODES = ("pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev")
+# accepted beside the default three: they pass an indx_S (the wide ones: of support_order_wide*) or refresh one inside the solver
+TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev", "refresh", "warm_refresh",
+                      "pai_prev_refresh")
+_PREV_MODES = ("pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev", "pai_prev_refresh")
 _WIDE_MODES = ("pai_wide_prev", "warm_pai_wide_prev")
+_REFRESH_MODES = ("refresh", "warm_refresh", "pai_prev_refresh")      # float64 only: proposed_algorithm_refresh_f64
 
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
                  precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
-                 widen_primary="neighbourhood"):
+                 widen_primary="neighbourhood", refresh=(0, 1)):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -903,6 +905,11 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     and the same two with the order widened over neighbouring angle cells:
       pai_wide_prev, warm_pai_wide_prev  ``pai_prev`` / ``warm_pai_prev`` with ``support_order_wide`` (``_f64``) at the radii
                      ``widen = (wr, wt)`` and ``widen_primary`` ("neighbourhood" or "ties") in place of ``support_order``
+    and (``precision="f64"`` only) the support refreshed from the solver's own iterate inside the loop, by
+    ``proposed_algorithm_refresh_f64`` at ``refresh = (start, period)``:
+      refresh           from zero, no order in force until the first refresh
+      warm_refresh      from the previous frame's whole state, no order in force until the first refresh
+      pai_prev_refresh  from zero, ``support_order_f64`` of the chain's previous S in force until the first refresh
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
@@ -910,7 +917,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
 
     Returns the dictionary tools/run_tracking.py prints - per (mode, Imax) ``mean_nmse`` over the scored frames, ``sem_over_seqs``,
     ``median_nmse``, ``mean_nmse_by_frame`` and ``estimates_per_s`` (solver time only, frame 0 left out) - plus
-    ``"channel": "device"``, ``"drift"`` when one was given, and ``"widen"``, ``"widen_primary"`` when a wide mode was asked for."""
+    ``"channel": "device"``, ``"drift"`` when one was given, and ``"widen"``, ``"widen_primary"`` when a wide mode was asked for and ``"refresh"`` when a refresh mode was."""
     import time
     import numpy as np
     from . import solvers as J
@@ -939,6 +946,14 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     if any(m in _WIDE_MODES for m in modes) and (2 * wr + 1 > p.Gr or 2 * wt + 1 > p.Gt):
         raise ValueError("widen = %r: a window of %d x %d cells meets itself round the %d x %d angle grid"
                          % ((wr, wt), 2 * wr + 1, 2 * wt + 1, p.Gr, p.Gt))
+    try:
+        r_start, r_period = (int(x) for x in refresh)
+    except (TypeError, ValueError):
+        raise ValueError("refresh must be a pair (start, period), not %r" % (refresh,)) from None
+    if r_start < 0 or r_period < 0:
+        raise ValueError("refresh must be a pair (start, period) >= 0, not %r" % (refresh,))
+    if precision != "f64" and any(m in _REFRESH_MODES for m in modes):
+        raise ValueError("the modes %r refresh the support inside the float64 solver: precision must be 'f64'" % (_REFRESH_MODES,))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -967,7 +982,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
             zb = wide(inp["Zbar"])
             for k in keys:
                 mode, n_it = k
-                warm = mode in ("warm", "warm_vs", "warm_pai_prev", "warm_pai_wide_prev")
+                warm = mode in ("warm", "warm_vs", "warm_pai_prev", "warm_pai_wide_prev", "warm_refresh")
                 st = state.get(k) if warm else None
                 if st is not None and mode == "warm_vs":
                     st = st.clone()
@@ -981,7 +996,11 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                     ix = {"indx_S": order(prev_S[k])}               # (not timed: the solver's rate is what estimates_per_s reports)
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
-                S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm, **ix)
+                if mode in _REFRESH_MODES:
+                    S, _, _, out, _ = J.proposed_algorithm_refresh_f64(*args, n_it, *prm, start=r_start, period=r_period, want_ce=False,
+                                                                       state=st, return_state=warm, **ix)
+                else:
+                    S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm, **ix)
                 torch.cuda.synchronize(device)
                 dt = time.perf_counter() - c0
                 if warm:
@@ -1009,4 +1028,6 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         res["drift"] = drift
     if any(m in _WIDE_MODES for m in modes):
         res["widen"], res["widen_primary"] = [wr, wt], widen_primary
+    if any(m in _REFRESH_MODES for m in modes):
+        res["refresh"] = [r_start, r_period]
     return res

@@ -35,7 +35,7 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64",
            "admm_state_elems", "proposed_algorithm_resume_f64", "proposed_algorithm_std_resume_f64",
            "proposed_algorithm_resume", "proposed_algorithm_angles_resume", "support_order", "support_order_f64",
-           "support_order_wide", "support_order_wide_f64"]
+           "support_order_wide", "support_order_wide_f64", "support_top_f64", "proposed_algorithm_refresh_f64"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -950,13 +950,13 @@ def _state_out(wanted, batch, elems, mem, dev, np_dtype=np.complex128):
     return st.ctypes.data, st
 
 
-def _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, own_PA, own_PB, host, resumed):
+def _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, own_PA, own_PB, host, resumed, *, refresh=False):
     """Bytes of float64 state per trial of a float64 ``proposed_algorithm`` call (csrc/proposed64.hip), which sets the chunks of a large
     batch: the N x M and Gr x G2 arrays, the products, the svt, the Grams of a per-trial dictionary, for Alg. 1 (``std``) the Hestenes
     arrays of a per-trial factor the call inverts (``own_PA`` / ``own_PB``), and the staged copies of a host call.  The plain Alg. 1
     call counts 2 Gr x G2 arrays and no Grams, the plain Alg. 2 call stages a per-trial dictionary once and the others twice, and only
     a resumed call stages the two state blocks.  Above Gram order 64 a chunk's trials are swept together (include/jstsp.h), so a
-    change of these counts can change last bits."""
+    change of these counts can change last bits.  ``refresh``: the refreshed solve's rank array and, staged, its two orders."""
     n, g = min(N, M), Gr * G2
     plain_std = std and not resumed
     per = 8 * N * M + (2 if plain_std else 5) * g + Gr * M + N * G2 + 20 * n * n
@@ -969,6 +969,8 @@ def _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, own_PA, own_PB, host, resumed):
         dicts = (G2 * M if sB else 0) + (N * Gr if sA else 0)
         states = 2 * admm_state_elems(N, M, Gr, G2) if resumed else 0
         per += 16 * (2 * N * M + g + (2 if std or resumed else 1) * dicts + states) + 8 * N * M
+    if refresh:
+        per += 4 * g + (4 * (g + min(g, _lib.SUPPORT_TOP_MAX)) if host else 0)
     return per
 
 
@@ -1034,6 +1036,74 @@ def proposed_algorithm_std_resume_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho
     iteration: the ``v`` of ``state`` is ignored."""
     return _admm_f64(True, True, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, None, indx_S, PA, PB, want_ce, False, ctx, state, it0,
                      return_state)[:4]
+
+
+# ----------------------------------------------------------------------------- float64 solver, support refreshed from its own iterate
+def _refresh_first(it0, Imax, start, period):
+    """The first refresh iteration (global, 1-based) among ``it0 + 1 ... it0 + Imax``, or ``None``: iteration ``i`` refreshes when
+    ``i > start`` and ``(i - start - 1) % period == 0`` (``period >= 1``), or only ``i == start + 1`` (``period == 0``)."""
+    lo, hi = it0 + 1, it0 + Imax
+    first = start + 1
+    if first < lo and period:
+        first += -(-(lo - first) // period) * period
+    return first if lo <= first <= hi else None
+
+
+def proposed_algorithm_refresh_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, start=0, period=1, indx_S=None, want_ce=True, ctx=None,
+                                   state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm_resume_f64` (Alg. 2) with its support refreshed from its own iterate inside the loop (include/jstsp.h:
+    jstsp_proposed_refresh_f64): at the global iterations ``i > start`` with ``(i - start - 1) % period == 0``
+    (``period=0``: only ``i == start + 1``) the mask becomes the top ``min(10 + 5 i, Gr*G2)`` of the new ``v``, and stays the top of
+    that ``v`` - growing by the iteration's count - until the next refresh.  Until the first refresh the order in force is
+    ``indx_S`` (1-based, ``(n,)`` or ``(batch, n)`` with ``1 <= n <= Gr*G2``; entries it does not list are never admitted), or none.
+    ``start=0, period=1`` needs no prior at all.  Returns ``(S, Y, ce, state, order)``: the first four as the sibling's, ``order``
+    int32 ``(batch, min(Gr*G2, 4096))`` the list of the call's last refresh where the inputs live - or, when the call ran no
+    refresh (a function of ``it0``, ``Imax``, ``start``, ``period``), the caller's ``indx_S`` as it was given.  A later leg passes
+    ``order`` as ``indx_S`` with the same ``start`` and ``period`` and its own ``it0`` and returns the bits of the uninterrupted call.
+    A refreshed order lists at most 4096 entries, so above ``Gr*G2 = 4096`` the mask stops growing at iteration 818.  A batch whose
+    float64 workspace would exceed the library's limit is solved in chunks."""
+    start, period, it0 = int(start), int(period), int(it0)
+    if start < 0 or period < 0:
+        raise ValueError("start and period must be >= 0, not %r and %r" % (start, period))
+    q = _AdmmCall(np.complex128, subY, Omega, A, B, None, tau_Y, tau_S, rho, Imax)
+    N, M, Gr, G2, batch, Imax, sA, sB = q.N, q.M, q.Gr, q.G2, q.batch, q.Imax, q.sA, q.sB
+    g = Gr * G2
+    R = min(g, _lib.SUPPORT_TOP_MAX)
+    n = 0
+    if indx_S is not None:
+        n = int(indx_S.shape[-1]) if len(indx_S.shape) else 0
+        size = int(indx_S.numel() if _is_torch(indx_S) else np.asarray(indx_S).size)
+        if not 1 <= n <= g or size != batch * n:
+            raise ValueError("indx_S must be (n,) or (batch, n) with 1 <= n <= Gr*G2 = %d and batch = %d, got shape %s"
+                             % (g, batch, tuple(indx_S.shape)))
+        q.ix = _indx_arg(indx_S, batch, n)
+    if it0 < 0 or (state is None and it0 != 0):
+        raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
+    ne = admm_state_elems(N, M, Gr, G2)
+    p_in, keep_in = _state_arg(state, batch, ne, q.state_mem, q.state_dev)
+    q.open(want_ce, ctx)
+    mem = q.mem
+    p_out, st_out = _state_out(return_state, batch, ne, mem, q.dev)
+    order, p_ord = indx_S, None
+    if _refresh_first(it0, Imax, start, period) is not None:
+        if mem == DEVICE:
+            import torch
+            order = torch.empty((batch, R), dtype=torch.int32, device=q.dev)
+            p_ord = order.data_ptr()
+        else:
+            order = np.empty((batch, R), dtype=np.int32)
+            p_ord = order.ctypes.data
+    per = _f64_admm_bytes(N, M, Gr, G2, sA, sB, False, True, True, mem == HOST, True, refresh=True)
+    dp = C.POINTER(C.c_double)
+    name = "jstsp_proposed_refresh_f64"
+    for t0, nb in _f64_chunks(batch, per):
+        check(getattr(q.ctx._lib, name)(
+            q.ctx.handle, N, M, Gr, G2, nb, _off(q.sub.ptr, t0 * N * M, 16), _off(q.om.ptr, t0 * N * M, 8), _off(q.A.ptr, t0 * sA, 16), sA,
+            _off(q.B.ptr, t0 * sB, 16), sB, Imax, q.tY[t0:].ctypes.data_as(dp), q.tS[t0:].ctypes.data_as(dp), q.rh[t0:].ctypes.data_as(dp),
+            _off(q.ix.ptr, t0 * n, 4), n, start, period, _off(q.pS, t0 * g, 16), _off(q.pY, t0 * N * M, 16), _off(q.pce, t0 * 3 * Imax, 8),
+            it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16), _off(p_ord, t0 * R, 4), mem), name)
+    del keep_in
+    return q.result() + (st_out, order)
 
 
 def svt_f64(Y, tau, *, ctx=None):
@@ -1466,6 +1536,28 @@ def support_order_f64(S, *, ctx=None):
     """:func:`support_order` for a complex128 ``S`` without narrowing (``jstsp_support_order_f64``): the key is ``|z|^2`` in
     float64.  Arguments and result as :func:`support_order`."""
     return _support_order_call("jstsp_support_order_f64", S, np.complex128, ctx)
+
+
+def support_top_f64(S, count, *, ctx=None):
+    """The first ``count`` entries of :func:`support_order_f64` per trial, bit for bit, without sorting the trial
+    (``jstsp_support_top_f64``, csrc/support_top.hip): one selection kernel - a radix select of the ``count``-th key, the ties in
+    index order, a sort of the selected entries in LDS - which is what :func:`proposed_algorithm_refresh_f64` runs inside its
+    loop.  ``S`` as :func:`support_order_f64` takes it; ``1 <= count <= min(Gr*G2, 4096)`` (``JstspError`` code -4 otherwise).
+    Returns int32 (batch, count), 1-based column-major linear indices, where ``S`` lives."""
+    count = int(count)
+    a_S = _Arg(S, np.complex128, "S")
+    c, mem, dev = _ctx_for([a_S], ctx)
+    batch, Gr, G2 = a_S.batch, a_S.R, a_S.C
+    rows = max(count, 1)
+    if mem == DEVICE:
+        import torch
+        out = torch.empty((batch, rows), dtype=torch.int32, device=dev)
+        optr = out.data_ptr()
+    else:
+        out = np.empty((batch, rows), dtype=np.int32)
+        optr = out.ctypes.data
+    check(c._lib.jstsp_support_top_f64(c.handle, Gr, G2, batch, a_S.ptr, count, optr, mem), "jstsp_support_top_f64")
+    return out
 
 
 _WIDE_PRIMARY = {"neighbourhood": 0, "ties": 1}

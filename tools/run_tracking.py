@@ -26,6 +26,10 @@ angles of every sequence walk, SIGMA radians of standard deviation per frame, so
 pai_wide_prev and warm_pai_wide_prev are pai_prev and warm_pai_prev with the order widened over the
 neighbouring angle cells (support_order_wide): --widen WR,WT cells each way on the receive and transmit grid, --widen-primary
 neighbourhood (a strong entry, then its window) or ties (the plain order, its exact zeros by their strongest neighbour).
+refresh, warm_refresh and pai_prev_refresh (float64 only) refresh the support from the solver's own iterate
+inside the loop (proposed_algorithm_refresh_f64) - from zero, from the previous frame's state, and from zero with the order of the
+chain's previous estimate in force until the first refresh: --refresh START,PERIOD, a refresh at the iterations i > START with
+(i - START - 1) % PERIOD == 0, PERIOD 0 for the one refresh at START + 1 (default: 0,1, every iteration).
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -55,15 +59,26 @@ ap.add_argument("--sweep-idx", type=int, default=0, help="--device-channel: the 
 ap.add_argument("--drift", type=float, default=None, metavar="SIGMA",
                 help="--device-channel: random walk of every path angle, SIGMA rad per frame (default: fixed angles)")
 ap.add_argument("--modes", nargs="+", default=None,
-                choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev"),
+                choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev", "refresh",
+                         "warm_refresh", "pai_prev_refresh"),
                 help="--device-channel: the columns to run (default: cold warm warm_vs)")
 ap.add_argument("--widen", default=None, metavar="WR,WT",
                 help="--device-channel: the radii of pai_wide_prev / warm_pai_wide_prev in grid cells (default: 1,1)")
 ap.add_argument("--widen-primary", choices=("neighbourhood", "ties"), default=None,
                 help="--device-channel: what the widened order sorts by first (default: neighbourhood)")
+ap.add_argument("--refresh", default=None, metavar="START,PERIOD",
+                help="--device-channel: the refresh schedule of refresh / warm_refresh / pai_prev_refresh (default: 0,1)")
 a = ap.parse_args()
-if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None) and not a.device_channel:
-    ap.error("--drift, --modes, --widen and --widen-primary need --device-channel")
+if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None or a.refresh is not None) \
+        and not a.device_channel:
+    ap.error("--drift, --modes, --widen, --widen-primary and --refresh need --device-channel")
+if a.refresh is not None:
+    try:
+        a.refresh = tuple(int(x) for x in a.refresh.split(","))
+    except ValueError:
+        a.refresh = ()
+    if len(a.refresh) != 2 or min(a.refresh) < 0:
+        ap.error("--refresh takes two integers >= 0 as START,PERIOD")
 if a.widen is not None:
     try:
         a.widen = tuple(int(x) for x in a.widen.split(","))
@@ -89,6 +104,8 @@ if a.device_channel:
         kw["widen"] = a.widen
     if a.widen_primary is not None:
         kw["widen_primary"] = a.widen_primary
+    if a.refresh is not None:
+        kw["refresh"] = a.refresh
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
