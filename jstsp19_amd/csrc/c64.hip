@@ -220,71 +220,62 @@ int jstsp_proposed_algorithm_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
     const size_t in_bytes = (size_t)batch * ((size_t)N * M * 24 + (strideB ? (size_t)G2 * M * 16 : 0));
     if (memspace == JSTSP_HOST && type == JSTSP_TYPE_APPROXIMATE && batch >= 128 && Imax > 1 && Y_out && tune().host_pipeline &&
         in_bytes >= ((size_t)512 << 20)) {
-        if (!ctx->helper) JSTSP_TRY(jstsp_create(ctx->device, &ctx->helper));
-        jstsp_ctx *cx[2] = {ctx, ctx->helper};
-        const size_t nm1 = (size_t)N * M, g1 = (size_t)Gr * G2;
-        const int h = ((batch / 2 + 7) / 8) * 8, cnt[2] = {h, batch - h}, t0[2] = {0, h};
-        Conv half0(cx[0], JSTSP_HOST), half1(cx[1], JSTSP_HOST);
-        Conv *cvk[2] = {&half0, &half1};
-        // (a failure inside the pipeline must not return while the other half still reads the caller's host arrays or writes its
-        //  outputs: both streams are drained first - as in the _c32 entry)
-        auto drained = [&](int rc) {
-            if (rc) for (int k = 0; k < 2; ++k) { DeviceScope ds(cx[k]->device); (void)hipStreamSynchronize(cx[k]->stream); }
-            return rc;
-        };
-#define JSTSP_TRY_PIPE(expr) do { int rc_ = drained(expr); if (rc_ != 0) return rc_; } while (0)
+        HostPipeline pipe;
+        JSTSP_TRY(pipe.open(ctx, batch));
+        jstsp_ctx *const *cx = pipe.cx;
+        const AdmmProblem64 all{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out,
+                                ce_out, 0, nullptr, nullptr, JSTSP_HOST};
+        const AdmmProblem64 half[2] = {all.sub(pipe.t0[0], pipe.cnt[0]), all.sub(pipe.t0[1], pipe.cnt[1])};      // the caller's arrays
+        const size_t nm1 = all.nm(), g1 = all.g();
+        Conv cvk[2] = {{cx[0], JSTSP_HOST}, {cx[1], JSTSP_HOST}};
         PendingSolve pend[2];
-        const jstsp_c32 *yk[2], *ak[2], *bk[2];
-        const float *ok[2];
-        const int32_t *ik[2];
+        AdmmProblem dev[2];                             // the halves with their inputs narrowed on the device, no outputs
         for (int k = 0; k < 2; ++k) {
-            Conv &c = *cvk[k];
-            yk[k] = c.in(subY + t0[k] * nm1, cnt[k] * nm1);
-            ok[k] = c.in_real(Omega + t0[k] * nm1, cnt[k] * nm1);
-            ak[k] = c.in_dict(A + (size_t)t0[k] * strideA, (size_t)N * Gr, strideA, cnt[k]);
+            Conv &c = cvk[k];
+            const AdmmProblem64 &h = half[k];
+            AdmmProblem &d = dev[k];
+            d.N = N; d.M = M; d.Gr = Gr; d.G2 = G2; d.batch = h.batch; d.strideA = strideA; d.strideB = strideB; d.Imax = Imax; d.type = type;
+            d.tau_Y = h.tau_Y; d.tau_S = h.tau_S; d.rho = h.rho; d.memspace = JSTSP_DEVICE;
+            d.subY = c.in(h.subY, h.batch * nm1);
+            d.Omega = c.in_real(h.Omega, h.batch * nm1);
+            d.A = c.in_dict(h.A, (size_t)N * Gr, strideA, h.batch);
             int hgt = 0;
-            bk[k] = c.in_dict_toeplitz(B + (size_t)t0[k] * strideB, G2, M, strideB, cnt[k], &hgt);
-            ik[k] = c.in_raw(indx_S ? indx_S + t0[k] * g1 : nullptr, cnt[k] * g1);
-            JSTSP_TRY_PIPE(c.rc);
+            d.B = c.in_dict_toeplitz(h.B, G2, M, strideB, h.batch, &hgt);
+            d.indx_S = c.in_raw(h.indx_S, h.batch * g1);
+            JSTSP_TRY_PIPE(pipe, c.rc);
             cx[k]->dict_block_hint = hgt;               // (consumed by the solve enqueued next on this context)
-            JSTSP_TRY_PIPE(proposed_enqueue_device(cx[k], N, M, Gr, G2, cnt[k], yk[k], ok[k], ak[k], strideA, bk[k], strideB, Imax, tau_Y + t0[k],
-                                              tau_S + t0[k], rho + t0[k], type, ik[k], ce_out != nullptr, &pend[k]));
+            JSTSP_TRY_PIPE(pipe, proposed_enqueue_device(cx[k], d, ce_out != nullptr, &pend[k]));
         }
-        int fallbacks = 0;
         for (int k = 0; k < 2; ++k) {
-            Conv &c = *cvk[k];
+            Conv &c = cvk[k];
+            const AdmmProblem64 &h = half[k];
             const PendingSolve &p = pend[k];
-            JSTSP_TRY_PIPE(c.deliver(reinterpret_cast<const float *>(p.dS), reinterpret_cast<double *>(S_out + t0[k] * g1), 2 * cnt[k] * g1));
-            JSTSP_TRY_PIPE(c.deliver(reinterpret_cast<const float *>(p.dY), reinterpret_cast<double *>(Y_out + t0[k] * nm1), 2 * cnt[k] * nm1));
+            JSTSP_TRY_PIPE(pipe, c.deliver(reinterpret_cast<const float *>(p.dS), reinterpret_cast<double *>(h.S_out), 2 * h.batch * g1));
+            JSTSP_TRY_PIPE(pipe, c.deliver(reinterpret_cast<const float *>(p.dY), reinterpret_cast<double *>(h.Y_out), 2 * h.batch * nm1));
             if (p.want_ce)
             {
-                const hipError_t e_ = hipMemcpyAsync(ce_out + (size_t)t0[k] * 3 * Imax, p.dce, (size_t)cnt[k] * 3 * Imax * sizeof(double),
-                                                     hipMemcpyDeviceToHost, cx[k]->stream);
+                const hipError_t e_ = hipMemcpyAsync(h.ce_out, p.dce, (size_t)h.batch * 3 * Imax * sizeof(double), hipMemcpyDeviceToHost, cx[k]->stream);
                 if (e_ != hipSuccess) set_error("proposed_algorithm: copying convergence_error failed: %s", hipGetErrorString(e_));
-                JSTSP_TRY_PIPE((int)e_);
+                JSTSP_TRY_PIPE(pipe, (int)e_);
             }
-            JSTSP_TRY_PIPE(c.rc);
+            JSTSP_TRY_PIPE(pipe, c.rc);
             std::vector<int> o;
-            JSTSP_TRY_PIPE(proposed_pending_flags(cx[k], p, &o));
-            for (size_t i = 0; i < o.size();) {            // runs of flagged trials again, without the fused pass
-                size_t j = i + 1;
-                while (j < o.size() && o[j] == o[j - 1] + 1) ++j;
-                const int r0 = o[i], nrun = (int)(j - i), tg = t0[k] + r0;
+            JSTSP_TRY_PIPE(pipe, read_flagged_trials(cx[k], p.ovf, h.batch, &o));
+            // runs of flagged trials again, without the fused pass, into freshly narrowed outputs
+            JSTSP_TRY(for_each_run(o, [&](int r0, int nrun) -> int {
+                const AdmmProblem64 to = h.sub(r0, nrun);
+                AdmmProblem run = dev[k].sub(r0, nrun);
                 Conv cr(cx[k], JSTSP_HOST);
-                jstsp_c32 *s = cr.out(S_out + tg * g1, nrun * g1), *yo = cr.out(Y_out + tg * nm1, nrun * nm1);
-                double *ce = cr.out_raw(ce_out ? ce_out + (size_t)tg * 3 * Imax : nullptr, (size_t)nrun * 3 * Imax);
-                JSTSP_TRY_PIPE(cr.rc);
-                JSTSP_TRY_PIPE(proposed_resolve_device(cx[k], N, M, Gr, G2, nrun, yk[k] + r0 * nm1, ok[k] + r0 * nm1, ak[k] + (size_t)r0 * strideA,
-                                                  strideA, bk[k] + (size_t)r0 * strideB, strideB, Imax, tau_Y + tg, tau_S + tg, rho + tg,
-                                                  type, ik[k] ? ik[k] + r0 * g1 : nullptr, s, yo, ce));
-                JSTSP_TRY_PIPE(cr.finish());
-                fallbacks += nrun;
-                i = j;
-            }
+                run.S_out = cr.out(to.S_out, nrun * g1); run.Y_out = cr.out(to.Y_out, nrun * nm1);
+                run.ce_out = cr.out_raw(to.ce_out, (size_t)nrun * 3 * Imax);
+                JSTSP_TRY_PIPE(pipe, cr.rc);
+                JSTSP_TRY_PIPE(pipe, proposed_resolve_device(cx[k], run));
+                JSTSP_TRY_PIPE(pipe, cr.finish());
+                pipe.fallbacks += nrun;
+                return 0;
+            }));
         }
-#undef JSTSP_TRY_PIPE
-        ctx->fused_fallbacks = fallbacks;
-        ctx->last_dict_block = (cx[0]->last_dict_block == cx[1]->last_dict_block) ? cx[0]->last_dict_block : 0;
+        pipe.close();
         return 0;
     }
     const size_t nm = (size_t)N * M * batch;

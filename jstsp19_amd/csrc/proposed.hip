@@ -53,10 +53,15 @@ static int gram3_nsplit(int N, int M, int G2, bool want_ce)
     return std::max(1, std::min(32, (M + chunk - 1) / chunk));
 }
 
-static size_t proposed_bytes(int N, int M, int Gr, int G2, int batch, int nA, int nB, bool angles,
-                             bool want_ce, int Imax)
+// The workspace of one call: every arena allocation of proposed_impl.  Besides the problem it depends on whether the fused pass
+// is wanted (in `fparts` column ranges per problem) and on the size of a JSTSP_HOST dictionary's compacted upload (0: none).
+static size_t proposed_bytes(const AdmmProblem &p, bool want_fused, int fparts, size_t compact_elems)
 {
-    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
+    const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2, batch = p.batch, Imax = std::max(p.Imax, 1);
+    const int nA = p.strideA ? batch : 1, nB = p.strideB ? batch : 1;
+    const bool angles = p.indx_S != nullptr, want_ce = p.ce_out != nullptr, approx = p.type == JSTSP_TYPE_APPROXIMATE;
+    const size_t nm = p.nm(), g = p.g(), ng = (size_t)N * G2, ne = p.state_elems();
+    const size_t szA = (size_t)p.strideA * (nA - 1) + (size_t)N * Gr, szB = (size_t)p.strideB * (nB - 1) + (size_t)G2 * M;
     size_t b = 0;
     b += rnd256(3 * batch * nm * sizeof(float2)) + 6 * rnd256(batch * nm * sizeof(float2));
     b += rnd256(batch * nm * sizeof(float));
@@ -76,13 +81,32 @@ static size_t proposed_bytes(int N, int M, int Gr, int G2, int batch, int nA, in
     if (use_hgemm(N, G2, M) && nB == 1 && hgemm_pair_shape(N, G2, batch))
         b += rnd256((size_t)batch * 2 * (4 * ((M + 63) / 64)) * 256 * sizeof(uint4));
     if (use_hgemm(Gr, G2, G2)) b += hgemm_pack_bytes(G2, G2, nB) + rnd256(2 * batch * sizeof(uint32_t));
+    if (!approx)        // 'std': pinv(A), pinv(B) where they fit the in-LDS kernel, the Gram inverses otherwise
+        b += (pinv_fits(N, Gr) ? rnd256((size_t)nA * Gr * N * sizeof(float2))
+                               : rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + hinv_bytes(Gr, nA)) +
+             (pinv_fits(G2, M) ? rnd256((size_t)nB * M * G2 * sizeof(float2))
+                               : rnd256((size_t)nB * G2 * G2 * sizeof(float2)) + hinv_bytes(G2, nB));
+    if (want_fused) b += fused_bytes(M, G2, nB, batch, fparts);
+    b += 1024;                                                                    // probe flags of the block-Toeplitz test
+    if (approx)      // low-order part of G_A, G_B's first block row (hi, lo)
+        b += rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + 2 * rnd256((size_t)nB * (G2 / 2 + 1) * G2 * sizeof(float2));
+    if (p.memspace == JSTSP_HOST) {      // the staged inputs, the compacted dictionary, the staged states of a resumed call
+        b += rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float)) + rnd256(szA * sizeof(float2)) +
+             rnd256(szB * sizeof(float2));
+        if (angles) b += rnd256(batch * g * sizeof(int32_t));
+        b += rnd256(compact_elems * sizeof(float2));
+        b += (p.state_in ? rnd256(batch * ne * sizeof(float2)) : 0) + (p.state_out ? rnd256(batch * ne * sizeof(float2)) : 0);
+    }
+    if (p.state_in) b += rnd256(batch * nm * sizeof(float2));       // subY + rho D of a resumed call's first iteration (resume.hip)
     return b;
 }
 
-static int proposed_alloc(Arena &a, ProposedWS &w, int N, int M, int Gr, int G2, int batch, int nA, int nB,
-                          bool angles, bool want_ce, int Imax)
+static int proposed_alloc(Arena &a, ProposedWS &w, const AdmmProblem &p)
 {
-    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
+    const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2, batch = p.batch, Imax = std::max(p.Imax, 1);
+    const int nA = p.strideA ? batch : 1, nB = p.strideB ? batch : 1;
+    const bool angles = p.indx_S != nullptr, want_ce = p.ce_out != nullptr;
+    const size_t nm = p.nm(), g = p.g(), ng = (size_t)N * G2;
     // X, V1, V2 in one block: the spectral norms of the three are one batched Gram over 3*batch matrices
     w.X = a.get<float2>(3 * batch * nm);
     w.V1 = w.X ? w.X + batch * nm : nullptr;
@@ -141,9 +165,6 @@ static int proposed_alloc(Arena &a, ProposedWS &w, int N, int M, int Gr, int G2,
 
 using namespace jstsp;
 
-// A JSTSP_HOST solve whose device work has been enqueued but whose results are still in the context's workspace: the halves of
-// a pipelined host call (jstsp_proposed_algorithm_c32 below).  proposed_finish copies them out, reads the overflow flags and
-// re-solves flagged trials.
 static bool tune_host_pipeline()
 {
     load_tuning();
@@ -152,18 +173,15 @@ static bool tune_host_pipeline()
 
 // One batched solve.  allow_fused = false: never the fused pass (the re-solve of trials whose predicted k scale
 // overflowed in it).  overflowed != NULL: receives the indices of such trials (their outputs are not to be used); reading
-// the per-trial flags costs ONE stream synchronisation at the end of a solve that used the fused pass.
-static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
-                         const jstsp_c32 *subY_, const float *Omega_,
-                         const jstsp_c32 *A_, long long strideA, const jstsp_c32 *B_,
-                         long long strideB, int Imax, const double *tau_Y,
-                         const double *tau_S, const double *rho, int type,
-                         const int32_t *indx_S_, jstsp_c32 *S_out, jstsp_c32 *Y_out,
-                         double *ce_out, int memspace, bool allow_fused, std::vector<int> *overflowed, PendingSolve *defer = nullptr,
-                         int it0 = 0, const jstsp_c32 *state_in = nullptr, jstsp_c32 *state_out = nullptr)
+// the per-trial flags costs ONE stream synchronisation at the end of a solve that used the fused pass.  defer != NULL: the
+// results stay in the context's workspace (the halves of a pipelined host call, the two-phase form); proposed_finish or the
+// caller copies them out and reads the flags.
+static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused, std::vector<int> *overflowed, PendingSolve *defer = nullptr)
 {
+    const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2, batch = p.batch, Imax = p.Imax, type = p.type, memspace = p.memspace, it0 = p.it0;
+    const long long strideA = p.strideA, strideB = p.strideB;
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL,
+    JSTSP_REQUIRE(p.subY && p.Omega && p.A && p.B && p.tau_Y && p.tau_S && p.rho && p.S_out, JSTSP_E_NULL,
                   "proposed_algorithm: NULL array argument");
     JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax >= 0, JSTSP_E_SHAPE,
                   "proposed_algorithm: bad shape N=%d M=%d Gr=%d G2=%d batch=%d Imax=%d", N, M, Gr, G2, batch,
@@ -182,19 +200,12 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
                   "under-determined U\\(L\\k) of the reference returns a basic, not least-squares, solution");
     JSTSP_ENTER(ctx);
 
-    const bool angles = indx_S_ != nullptr;
-    const bool want_ce = ce_out != nullptr;
+    const bool angles = p.indx_S != nullptr, want_ce = p.ce_out != nullptr;
     const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
     const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
     const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
 
-    size_t need = proposed_bytes(N, M, Gr, G2, batch, nA, nB, angles, want_ce, std::max(Imax, 1));
-    if (!approx)
-        need += (pinv_fits(N, Gr) ? rnd256((size_t)nA * Gr * N * sizeof(float2))
-                                  : rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + hinv_bytes(Gr, nA)) +
-                (pinv_fits(G2, M) ? rnd256((size_t)nB * M * G2 * sizeof(float2))
-                                  : rnd256((size_t)nB * G2 * G2 * sizeof(float2)) + hinv_bytes(G2, nB));
     // one pass over the dictionary per iteration (fused.hip); JSTSP_FUSED_PARTS = column ranges per problem
     // (measured at configs[1], 8 / 4 ranges: 4.42 / 4.34 ms per iteration - fewer partial sums to write and add)
     // (when M / 32 is not a multiple of 4: 2 ranges, or 1)
@@ -202,57 +213,44 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     const int ftiles = (M % 32 == 0) ? M / 32 : 0;
     const int fparts = tn.fused_parts > 0 ? tn.fused_parts : (ftiles % 4 == 0 ? 4 : (ftiles % 2 == 0 ? 2 : 1));
     const bool want_fused = allow_fused && tn.fused != 0 && approx && Imax > 1 && fused_shape_ok(N, M, G2, fparts);
-    if (want_fused) need += fused_bytes(M, G2, nB, batch, fparts);
-    need += 1024;                                                                 // probe flags of the block-Toeplitz test
-    if (approx)      // low-order part of G_A, G_B's first block row (hi, lo)
-        need += rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + 2 * rnd256((size_t)nB * (G2 / 2 + 1) * G2 * sizeof(float2));
     // a JSTSP_HOST dictionary of some size, one per trial, contiguous: tested for the block-Toeplitz structure on the host while
     // it is staged, and uploaded as its first block + leading columns (hostpack.hip)
     const bool host_compact = memspace == JSTSP_HOST && tn.host_compact != 0 && tn.toeplitz != 0 && nB > 1 && G2 >= 32 &&
                               strideB == (long long)G2 * M && (szB * sizeof(float2) >= ((size_t)64 << 20) || tn.host_compact >= 2) &&
                               (long long)G2 * M < (1ll << 31);       // (JSTSP_HOST_COMPACT=2: at any size - the tests)
     const size_t compact_elems = host_compact ? host_toeplitz_compact_elems(G2, M, nB) : 0;
-    if (memspace == JSTSP_HOST) {
-        need += rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float)) +
-                rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2));
-        if (angles) need += rnd256(batch * g * sizeof(int32_t));
-        need += rnd256(compact_elems * sizeof(float2));
-    }
-    // a resumed call (jstsp_proposed_resume_c32): subY + rho D of its first iteration (resume.hip), the staged state of a host call
-    const size_t ne = 4 * nm + 2 * g;
-    if (state_in) need += rnd256(batch * nm * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += (state_in ? rnd256(batch * ne * sizeof(float2)) : 0) + (state_out ? rnd256(batch * ne * sizeof(float2)) : 0);
-    JSTSP_TRY(ctx->arena.reserve(need));
+    const size_t ne = p.state_elems();
+    JSTSP_TRY(ctx->arena.reserve(proposed_bytes(p, want_fused, fparts, compact_elems)));
     ctx->arena.reset();
 
     const float2 *subY, *A, *B;
     const float *Omega;
     const int32_t *indx_S = nullptr;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(subY_), batch * nm, memspace, &subY));
-    JSTSP_TRY(stage_in(ctx, Omega_, batch * nm, memspace, &Omega));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
+    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(p.subY), batch * nm, memspace, &subY));
+    JSTSP_TRY(stage_in(ctx, p.Omega, batch * nm, memspace, &Omega));
+    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(p.A), szA, memspace, &A));
     int known_gt = ctx->dict_block_hint;        // (a caller that expanded a block-Toeplitz dictionary itself: c64.hip)
     ctx->dict_block_hint = 0;
     if (host_compact) {
         float2 *Bd = ctx->arena.get<float2>(szB), *Cd = ctx->arena.get<float2>(compact_elems);
         JSTSP_REQUIRE(Bd && Cd, JSTSP_E_NOMEM, "workspace exhausted while staging an input");
-        JSTSP_TRY(host_toeplitz_stage(ctx, reinterpret_cast<const float2 *>(B_), G2, M, nB, Bd, Cd, compact_elems, &known_gt));
-        if (!known_gt) JSTSP_HIP(hipMemcpyAsync(Bd, B_, szB * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+        JSTSP_TRY(host_toeplitz_stage(ctx, reinterpret_cast<const float2 *>(p.B), G2, M, nB, Bd, Cd, compact_elems, &known_gt));
+        if (!known_gt) JSTSP_HIP(hipMemcpyAsync(Bd, p.B, szB * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
         B = Bd;
     } else
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(B_), szB, memspace, &B));
-    if (angles) JSTSP_TRY(stage_in(ctx, indx_S_, batch * g, memspace, &indx_S));
+    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(p.B), szB, memspace, &B));
+    if (angles) JSTSP_TRY(stage_in(ctx, p.indx_S, batch * g, memspace, &indx_S));
     if (memspace == JSTSP_DEVICE)
         JSTSP_REQUIRE(((uintptr_t)subY % 16 == 0) && ((uintptr_t)Omega % 8 == 0), JSTSP_E_ARG,
                       "device arrays must be 16-byte aligned");
 
     ProposedWS w;
-    JSTSP_TRY(proposed_alloc(ctx->arena, w, N, M, Gr, G2, batch, nA, nB, angles, want_ce, std::max(Imax, 1)));
+    JSTSP_TRY(proposed_alloc(ctx->arena, w, p));
 
     // ---- per-problem scalars ------------------------------------------------------------------
     {
         std::vector<TrialParams> hp(batch);
-        for (int t = 0; t < batch; ++t) hp[t] = make_trial_params(rho[t], tau_Y[t], tau_S[t]);
+        for (int t = 0; t < batch; ++t) hp[t] = make_trial_params(p.rho[t], p.tau_Y[t], p.tau_S[t]);
         JSTSP_TRY(upload(ctx, w.prm, hp.data(), batch * sizeof(TrialParams)));
     }
 
@@ -278,8 +276,8 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     const float2 *sin = nullptr, *subY1 = subY;
     float2 *sout = nullptr;
     const bool explicit_c = !w.gz.left;             // (the element-wise update of that orientation takes C as an operand)
-    if (state_in) {
-        JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(state_in), batch * ne, memspace, &sin));
+    if (p.state_in) {
+        JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(p.state_in), batch * ne, memspace, &sin));
         float2 *sy1 = explicit_c ? nullptr : ctx->arena.get<float2>(batch * nm);
         JSTSP_REQUIRE(explicit_c || sy1, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (resumed state)");
         JSTSP_TRY(launch_resume_unpack(ctx, (long long)nm, (long long)g, batch, sin, w.X, w.V1, w.V2, w.C, w.V, w.S, subY, sy1, w.prm, explicit_c));
@@ -287,8 +285,8 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
         JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, Gr, batch, Am, Mat{w.S, (long long)g, Gr}, w.W, (long long)ng, N));
         JSTSP_TRY(gemm(ctx, 'N', 'N', N, M, G2, batch, Mat{w.W, (long long)ng, N}, Bm, w.Xs, (long long)nm, N, 1.f, nullptr, 0, 0, 0.f, GEMM_SYNTH));
     }
-    if (state_out) {
-        sout = memspace == JSTSP_DEVICE ? reinterpret_cast<float2 *>(state_out) : ctx->arena.get<float2>(batch * ne);
+    if (p.state_out) {
+        sout = memspace == JSTSP_DEVICE ? reinterpret_cast<float2 *>(p.state_out) : ctx->arena.get<float2>(batch * ne);
         JSTSP_REQUIRE(sout, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (resumed state)");
     }
     // JSTSP_TOEPLITZ (fused.hip): 0 - the dictionary is taken as unstructured; 1 - a block-Toeplitz one gets the compact HBM image
@@ -777,26 +775,21 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     }
     if (want_ce && Imax > 0) JSTSP_HIP(hipStreamWaitEvent(sm, ev_ce, 0));
     if (defer) {        // results stay in the workspace; copies, flags and recovery happen in proposed_finish
-        defer->active = true; defer->fused = fusedp; defer->want_ce = want_ce && Imax > 0; defer->batch = batch; defer->g = g; defer->nm = nm;
-        defer->Imax = Imax; defer->dS = w.S; defer->dY = w.Y; defer->dce = w.ce; defer->ovf = fusedp ? fw.ovf : nullptr;
+        defer->want_ce = want_ce && Imax > 0; defer->dS = w.S; defer->dY = w.Y; defer->dce = w.ce; defer->ovf = fusedp ? fw.ovf : nullptr;
         return 0;
     }
 
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(S_out), w.S, batch * g, memspace));
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Y_out), w.Y, batch * nm, memspace));
-    if (want_ce && Imax > 0) JSTSP_TRY(stage_out(ctx, ce_out, w.ce, (size_t)batch * 3 * Imax, memspace));
+    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.S_out), w.S, batch * g, memspace));
+    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.Y_out), w.Y, batch * nm, memspace));
+    if (want_ce && Imax > 0) JSTSP_TRY(stage_out(ctx, p.ce_out, w.ce, (size_t)batch * 3 * Imax, memspace));
     if (sout) {
         JSTSP_TRY(launch_resume_pack(ctx, (long long)nm, (long long)g, batch, w.X, w.V1, w.V2, explicit_c ? w.C : nullptr, w.V, w.S, sout));
-        if (memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(state_out), sout, batch * ne, memspace));
+        if (memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.state_out), sout, batch * ne, memspace));
     }
     if (fusedp && overflowed) {
         // Trials in which an entry of k left the f16 range of the scale predicted for it (growth beyond 2^(2 + kback) from
         // one iteration to the next): their results are wrong from that pass on.  The caller re-solves exactly those.
-        std::vector<uint32_t> flags(batch);
-        JSTSP_HIP(hipMemcpyAsync(flags.data(), fw.ovf, (size_t)batch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        JSTSP_HIP(hipStreamSynchronize(st));
-        for (int t = 0; t < batch; ++t)
-            if (flags[t]) overflowed->push_back(t);
+        JSTSP_TRY(read_flagged_trials(ctx, fw.ovf, batch, overflowed));
     }
     if (memspace == JSTSP_HOST) {
         JSTSP_HIP(hipStreamSynchronize(st));
@@ -806,40 +799,52 @@ static int proposed_impl(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
 }
 
 // Recovery: runs of consecutive flagged trials are solved again by the three-kernel iteration (every operand scale
-// there is the exact maximum of data that already exists: it cannot overflow), straight into the caller's arrays -
-// per-trial arrays are contiguous with the trial index slowest, so a sub-batch is a pointer offset in either memspace.
-static int resolve_overflowed(jstsp_ctx *ctx, const std::vector<int> &ovf, int N, int M, int Gr, int G2, const jstsp_c32 *subY,
-                              const float *Omega, const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB,
-                              int Imax, const double *tau_Y, const double *tau_S, const double *rho, int type,
-                              const int32_t *indx_S, jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, int memspace, int *count)
+// there is the exact maximum of data that already exists: it cannot overflow), straight into the caller's arrays - a
+// sub-batch of a problem is a problem in either memspace (AdmmProblem::sub); a resumed call's run starts from ITS state_in
+// at it0.  *count grows by the trials solved again.
+static int resolve_overflowed(jstsp_ctx *ctx, const AdmmProblem &p, const std::vector<int> &flagged, int *count)
 {
-    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2;
-    for (size_t i = 0; i < ovf.size();) {
-        size_t j = i + 1;
-        while (j < ovf.size() && ovf[j] == ovf[j - 1] + 1) ++j;
-        const int t0 = ovf[i], cnt = (int)(j - i);
-        JSTSP_TRY(proposed_impl(ctx, N, M, Gr, G2, cnt, subY + t0 * nm, Omega + t0 * nm, A + (size_t)t0 * strideA, strideA,
-                                B + (size_t)t0 * strideB, strideB, Imax, tau_Y + t0, tau_S + t0, rho + t0, type,
-                                indx_S ? indx_S + t0 * g : nullptr, S_out + t0 * g, Y_out ? Y_out + t0 * nm : nullptr,
-                                ce_out ? ce_out + (size_t)t0 * 3 * Imax : nullptr, memspace, false, nullptr));
+    return for_each_run(flagged, [&](int t0, int cnt) -> int {
+        JSTSP_TRY(proposed_impl(ctx, p.sub(t0, cnt), false, nullptr));
         *count += cnt;
-        i = j;
-    }
+        return 0;
+    });
+}
+
+int jstsp::read_flagged_trials(jstsp_ctx *ctx, const uint32_t *dev_flags, int batch, std::vector<int> *out)
+{
+    std::vector<uint32_t> flags(dev_flags ? batch : 0);
+    if (dev_flags) JSTSP_HIP(hipMemcpyAsync(flags.data(), dev_flags, (size_t)batch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    JSTSP_HIP(hipStreamSynchronize(ctx->stream));
+    flagged_trials(flags.data(), flags.size(), out);
     return 0;
 }
 
-// Second phase of a deferred JSTSP_HOST solve: device -> host copies of the outputs, the overflow flags, one synchronisation.
-static int proposed_finish(jstsp_ctx *ctx, const PendingSolve &p, jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, std::vector<int> *ovf)
+// Second phase of a deferred solve: the copies into the outputs of the problem it was enqueued for (on ctx->stream) ...
+static int deferred_copy_out(jstsp_ctx *ctx, const PendingSolve &d, const AdmmProblem &p)
+{
+    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.S_out), d.dS, p.batch * p.g(), p.memspace));
+    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.Y_out), d.dY, p.batch * p.nm(), p.memspace));
+    if (d.want_ce) JSTSP_TRY(stage_out(ctx, p.ce_out, d.dce, (size_t)p.batch * 3 * p.Imax, p.memspace));
+    return 0;
+}
+// ... and, for a JSTSP_HOST solve, the overflow flags with one synchronisation.
+static int proposed_finish(jstsp_ctx *ctx, const PendingSolve &d, const AdmmProblem &p, std::vector<int> *ovf)
 {
     JSTSP_ENTER(ctx);
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(S_out), p.dS, p.batch * p.g, JSTSP_HOST));
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Y_out), p.dY, p.batch * p.nm, JSTSP_HOST));
-    if (p.want_ce) JSTSP_TRY(stage_out(ctx, ce_out, p.dce, (size_t)p.batch * 3 * p.Imax, JSTSP_HOST));
-    std::vector<uint32_t> flags(p.ovf ? p.batch : 0);
-    if (p.ovf) JSTSP_HIP(hipMemcpyAsync(flags.data(), p.ovf, (size_t)p.batch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    JSTSP_HIP(hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < (int)flags.size(); ++t)
-        if (flags[t]) ovf->push_back(t);
+    JSTSP_TRY(deferred_copy_out(ctx, d, p));
+    return read_flagged_trials(ctx, d.ovf, p.batch, ovf);
+}
+
+// One solve in the caller's memspace with its recovery: the flagged trials again, and how many they were for
+// jstsp_last_fused_fallbacks.  (The entries zero that counter; proposed_impl never touches it.)
+static int solve_and_recover(jstsp_ctx *ctx, const AdmmProblem &p)
+{
+    std::vector<int> ovf;
+    JSTSP_TRY(proposed_impl(ctx, p, true, &ovf));
+    int fallbacks = 0;
+    JSTSP_TRY(resolve_overflowed(ctx, p, ovf, &fallbacks));
+    ctx->fused_fallbacks = fallbacks;
     return 0;
 }
 
@@ -851,58 +856,36 @@ extern "C" int jstsp_proposed_algorithm_c32(jstsp_ctx *ctx, int N, int M, int Gr
                                             const int32_t *indx_S, jstsp_c32 *S_out, jstsp_c32 *Y_out,
                                             double *ce_out, int memspace)
 {
-    std::vector<int> ovf;
     if (ctx) { ctx->fused_fallbacks = 0; ctx->last_dict_block = 0; }
-    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2;
+    const AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
+                        0, nullptr, nullptr, memspace};
     // JSTSP_HOST with a large batch: the two halves of the batch on two contexts of the device, so that the upload of the second
     // half (4.75 GiB per 256 trials at BASELINE configs[1], 57 GB/s) runs while the first half is being solved, and the download
     // of the first half while the second is.  A trial's result does not depend on what else is in its batch (tests), so the
     // outputs are those of the one-call form.  Measured at configs[1] (tools/host_path_rate.py): 256 trials 544 -> 594
     // channel-estimates/s, 128 trials 514 -> 540, 64 trials 466 -> 391 (a 32-trial solve no longer fills the chip): from 128 on.
-    const size_t in_bytes = (size_t)batch * (nm * 12 + (strideB ? (size_t)G2 * M * 8 : 0));
+    const size_t in_bytes = (size_t)batch * (p.nm() * 12 + (strideB ? (size_t)G2 * M * 8 : 0));
     const bool pipeline = ctx && memspace == JSTSP_HOST && type == JSTSP_TYPE_APPROXIMATE && batch >= 128 && Imax > 1 && Y_out &&
                           in_bytes >= ((size_t)256 << 20) && subY && Omega && A && B && tau_Y && tau_S && rho && S_out &&
                           tune_host_pipeline();
     if (pipeline) {
-        if (!ctx->helper) JSTSP_TRY(jstsp_create(ctx->device, &ctx->helper));
-        jstsp_ctx *cx[2] = {ctx, ctx->helper};
-        const int h = ((batch / 2 + 7) / 8) * 8, cnt[2] = {h, batch - h}, t0[2] = {0, h};
+        HostPipeline pipe;
+        JSTSP_TRY(pipe.open(ctx, batch));
+        const AdmmProblem half[2] = {p.sub(pipe.t0[0], pipe.cnt[0]), p.sub(pipe.t0[1], pipe.cnt[1])};
         PendingSolve pend[2];
-        // (a failure inside the pipeline - typically JSTSP_E_NOMEM for the helper's workspace - must not return while the other
-        //  half still reads the caller's host arrays or writes its outputs: both streams are drained first)
-        auto drained = [&](int rc) {
-            if (rc) for (int k = 0; k < 2; ++k) { DeviceScope ds(cx[k]->device); (void)hipStreamSynchronize(cx[k]->stream); }
-            return rc;
-        };
-#define JSTSP_TRY_PIPE(expr) do { int rc_ = drained(expr); if (rc_ != 0) return rc_; } while (0)
         for (int k = 0; k < 2; ++k) {
-            cx[k]->fused_fallbacks = 0; cx[k]->last_dict_block = 0;
-            JSTSP_TRY_PIPE(proposed_impl(cx[k], N, M, Gr, G2, cnt[k], subY + t0[k] * nm, Omega + t0[k] * nm, A + (size_t)t0[k] * strideA, strideA,
-                                    B + (size_t)t0[k] * strideB, strideB, Imax, tau_Y + t0[k], tau_S + t0[k], rho + t0[k], type,
-                                    indx_S ? indx_S + t0[k] * g : nullptr, S_out + t0[k] * g, Y_out + t0[k] * nm,
-                                    ce_out ? ce_out + (size_t)t0[k] * 3 * Imax : nullptr, JSTSP_HOST, true, nullptr, &pend[k]));
+            pipe.cx[k]->fused_fallbacks = 0; pipe.cx[k]->last_dict_block = 0;
+            JSTSP_TRY_PIPE(pipe, proposed_impl(pipe.cx[k], half[k], true, nullptr, &pend[k]));
         }
-        int fallbacks = 0;
         for (int k = 0; k < 2; ++k) {
             std::vector<int> o;
-            JSTSP_TRY_PIPE(proposed_finish(cx[k], pend[k], S_out + t0[k] * g, Y_out + t0[k] * nm, ce_out ? ce_out + (size_t)t0[k] * 3 * Imax : nullptr, &o));
-            JSTSP_TRY_PIPE(resolve_overflowed(cx[k], o, N, M, Gr, G2, subY + t0[k] * nm, Omega + t0[k] * nm, A + (size_t)t0[k] * strideA, strideA,
-                                         B + (size_t)t0[k] * strideB, strideB, Imax, tau_Y + t0[k], tau_S + t0[k], rho + t0[k], type,
-                                         indx_S ? indx_S + t0[k] * g : nullptr, S_out + t0[k] * g, Y_out + t0[k] * nm,
-                                         ce_out ? ce_out + (size_t)t0[k] * 3 * Imax : nullptr, JSTSP_HOST, &fallbacks));
+            JSTSP_TRY_PIPE(pipe, proposed_finish(pipe.cx[k], pend[k], half[k], &o));
+            JSTSP_TRY_PIPE(pipe, resolve_overflowed(pipe.cx[k], half[k], o, &pipe.fallbacks));
         }
-#undef JSTSP_TRY_PIPE
-        ctx->fused_fallbacks = fallbacks;
-        ctx->last_dict_block = (cx[0]->last_dict_block == cx[1]->last_dict_block) ? cx[0]->last_dict_block : 0;
+        pipe.close();
         return 0;
     }
-    JSTSP_TRY(proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type,
-                            indx_S, S_out, Y_out, ce_out, memspace, true, &ovf));
-    int fallbacks = 0;
-    JSTSP_TRY(resolve_overflowed(ctx, ovf, N, M, Gr, G2, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, S_out,
-                                 Y_out, ce_out, memspace, &fallbacks));
-    ctx->fused_fallbacks += fallbacks;
-    return 0;
+    return solve_and_recover(ctx, p);       // (the resumed entry below from zero, without a state)
 }
 
 // ---- resumed from a saved state (include/jstsp.h) ---------------------------------------------------------------------------------
@@ -922,13 +905,14 @@ extern "C" int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, i
                   it0, Imax);
     JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", it0);
     ctx->fused_fallbacks = 0; ctx->last_dict_block = 0;
-    const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ne = 4 * nm + 2 * g;
-    // state_out == state_in: the re-solve below needs the state the call started from
-    const jstsp_c32 *sin = state_in;
+    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
+                  it0, state_in, state_out, memspace};
+    const size_t ne = p.state_elems();
+    // state_out == state_in: the re-solve needs the state the call started from
     jstsp_c32 *keep_dev = nullptr;
     std::vector<jstsp_c32> keep_host;
     if (state_in && state_in == state_out) {
-        if (memspace == JSTSP_HOST) { keep_host.assign(state_in, state_in + (size_t)batch * ne); sin = keep_host.data(); }
+        if (memspace == JSTSP_HOST) { keep_host.assign(state_in, state_in + (size_t)batch * ne); p.state_in = keep_host.data(); }
         else {
             JSTSP_ENTER(ctx);
             JSTSP_HIP(hipMallocAsync((void **)&keep_dev, (size_t)batch * ne * sizeof(jstsp_c32), ctx->stream));
@@ -938,41 +922,20 @@ extern "C" int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, i
                 set_error("proposed_algorithm resume: copying the state failed: %s", hipGetErrorString(e));
                 return (int)e;
             }
-            sin = keep_dev;
+            p.state_in = keep_dev;
         }
     }
-    std::vector<int> ovf;
-    int rc = proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, S_out, Y_out,
-                           ce_out, memspace, true, &ovf, nullptr, it0, sin, state_out);
-    int fallbacks = 0;
-    for (size_t i = 0; !rc && i < ovf.size();) {
-        size_t j = i + 1;
-        while (j < ovf.size() && ovf[j] == ovf[j - 1] + 1) ++j;
-        const int t0 = ovf[i], cnt = (int)(j - i);
-        rc = proposed_impl(ctx, N, M, Gr, G2, cnt, subY + t0 * nm, Omega + t0 * nm, A + (size_t)t0 * strideA, strideA, B + (size_t)t0 * strideB, strideB,
-                           Imax, tau_Y + t0, tau_S + t0, rho + t0, type, indx_S ? indx_S + t0 * g : nullptr, S_out + t0 * g,
-                           Y_out ? Y_out + t0 * nm : nullptr, ce_out ? ce_out + (size_t)t0 * 3 * Imax : nullptr, memspace, false, nullptr, nullptr, it0,
-                           sin ? sin + t0 * ne : nullptr, state_out ? state_out + t0 * ne : nullptr);
-        fallbacks += cnt;
-        i = j;
-    }
+    const int rc = solve_and_recover(ctx, p);
     if (keep_dev) {
         JSTSP_ENTER(ctx);
         (void)hipFreeAsync(keep_dev, ctx->stream);
     }
-    ctx->fused_fallbacks = fallbacks;
     return rc;
 }
 
 // ---- the two-phase form for device arrays (include/jstsp.h) ---------------------------------------------------------------------
 struct jstsp_pending {
-    int N, M, Gr, G2, batch, Imax, type;
-    const jstsp_c32 *subY, *A, *B;
-    const float *Omega;
-    long long strideA, strideB;
-    const int32_t *indx_S;
-    jstsp_c32 *S_out, *Y_out;
-    double *ce_out;
+    AdmmProblem prob;                   // the call's problem; its tau_Y, tau_S, rho point into the copies below
     std::vector<double> tau_Y, tau_S, rho;
     uint32_t *flags = nullptr;          // pinned host copy of the per-trial overflow flags (NULL: the solve did not use the fused pass)
     hipEvent_t done = nullptr;
@@ -988,18 +951,16 @@ extern "C" int jstsp_proposed_algorithm_begin_c32(jstsp_ctx *ctx, int N, int M, 
     *pending = nullptr;
     ctx->fused_fallbacks = 0; ctx->last_dict_block = 0;
     PendingSolve ps;
-    JSTSP_TRY(proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, S_out,
-                            Y_out, ce_out, JSTSP_DEVICE, true, nullptr, &ps));
+    const AdmmProblem prob{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
+                           0, nullptr, nullptr, JSTSP_DEVICE};
+    JSTSP_TRY(proposed_impl(ctx, prob, true, nullptr, &ps));
     JSTSP_ENTER(ctx);
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(S_out), ps.dS, ps.batch * ps.g, JSTSP_DEVICE));
-    JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Y_out), ps.dY, ps.batch * ps.nm, JSTSP_DEVICE));
-    if (ps.want_ce) JSTSP_TRY(stage_out(ctx, ce_out, ps.dce, (size_t)ps.batch * 3 * ps.Imax, JSTSP_DEVICE));
+    JSTSP_TRY(deferred_copy_out(ctx, ps, prob));
     jstsp_pending *p = new (std::nothrow) jstsp_pending();
     JSTSP_REQUIRE(p, JSTSP_E_NOMEM, "proposed_algorithm_begin: out of host memory");
-    p->N = N; p->M = M; p->Gr = Gr; p->G2 = G2; p->batch = batch; p->Imax = Imax; p->type = type;
-    p->subY = subY; p->A = A; p->B = B; p->Omega = Omega; p->strideA = strideA; p->strideB = strideB; p->indx_S = indx_S;
-    p->S_out = S_out; p->Y_out = Y_out; p->ce_out = ce_out;
+    p->prob = prob;
     p->tau_Y.assign(tau_Y, tau_Y + batch); p->tau_S.assign(tau_S, tau_S + batch); p->rho.assign(rho, rho + batch);
+    p->prob.tau_Y = p->tau_Y.data(); p->prob.tau_S = p->tau_S.data(); p->prob.rho = p->rho.data();
     hipError_t e = hipSuccess;          // (positive status = the HIP error code, as everywhere in this ABI)
     if (ps.ovf) {
         e = hipHostMalloc((void **)&p->flags, (size_t)batch * sizeof(uint32_t), hipHostMallocDefault);
@@ -1028,13 +989,8 @@ extern "C" int jstsp_proposed_algorithm_end(jstsp_ctx *ctx, jstsp_pending *p, in
     const hipError_t e = hipEventSynchronize(p->done);
     if (e != hipSuccess) { set_error("proposed_algorithm_end: waiting for the solve failed: %s", hipGetErrorString(e)); rc = (int)e; }
     std::vector<int> ovf;
-    if (!rc && p->flags)
-        for (int t = 0; t < p->batch; ++t)
-            if (p->flags[t]) ovf.push_back(t);
-    if (!rc && !ovf.empty())
-        rc = resolve_overflowed(ctx, ovf, p->N, p->M, p->Gr, p->G2, p->subY, p->Omega, p->A, p->strideA, p->B, p->strideB, p->Imax,
-                                p->tau_Y.data(), p->tau_S.data(), p->rho.data(), p->type, p->indx_S, p->S_out, p->Y_out, p->ce_out,
-                                JSTSP_DEVICE, &count);
+    if (!rc && p->flags) flagged_trials(p->flags, (size_t)p->prob.batch, &ovf);      // (the pinned copy: no further copy or wait)
+    if (!rc) rc = resolve_overflowed(ctx, p->prob, ovf, &count);
     ctx->fused_fallbacks = count;
     if (fallbacks) *fallbacks = count;
     if (p->flags) (void)hipHostFree(p->flags);
@@ -1045,34 +1001,18 @@ extern "C" int jstsp_proposed_algorithm_end(jstsp_ctx *ctx, jstsp_pending *p, in
 
 namespace jstsp {
 // (solver_common.h: the phases of a pipelined host call for c64.hip, which stages - and narrows - its inputs itself)
-int proposed_enqueue_device(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
-                            const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
-                            const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
-                            bool want_ce, PendingSolve *out)
+int proposed_enqueue_device(jstsp_ctx *ctx, const AdmmProblem &p, bool want_ce, PendingSolve *out)
 {
     static jstsp_c32 sink_c;            // (a deferred solve never writes its output arguments; they only say what is wanted)
     static double sink_d;
     if (ctx) { ctx->fused_fallbacks = 0; ctx->last_dict_block = 0; }
-    return proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, &sink_c,
-                         &sink_c, want_ce ? &sink_d : nullptr, JSTSP_DEVICE, true, nullptr, out);
+    AdmmProblem q = p;
+    q.S_out = q.Y_out = &sink_c; q.ce_out = want_ce ? &sink_d : nullptr;
+    return proposed_impl(ctx, q, true, nullptr, out);
 }
-int proposed_pending_flags(jstsp_ctx *ctx, const PendingSolve &p, std::vector<int> *ovf)
+int proposed_resolve_device(jstsp_ctx *ctx, const AdmmProblem &run)
 {
-    JSTSP_ENTER(ctx);
-    std::vector<uint32_t> flags(p.ovf ? p.batch : 0);
-    if (p.ovf) JSTSP_HIP(hipMemcpyAsync(flags.data(), p.ovf, (size_t)p.batch * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    JSTSP_HIP(hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t < (int)flags.size(); ++t)
-        if (flags[t]) ovf->push_back(t);
-    return 0;
-}
-int proposed_resolve_device(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
-                            const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
-                            const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
-                            jstsp_c32 *S_dev, jstsp_c32 *Y_dev, double *ce_dev)
-{
-    return proposed_impl(ctx, N, M, Gr, G2, batch, subY, Omega, A, strideA, B, strideB, Imax, tau_Y, tau_S, rho, type, indx_S, S_dev,
-                         Y_dev, ce_dev, JSTSP_DEVICE, false, nullptr);
+    return proposed_impl(ctx, run, false, nullptr);
 }
 }  // namespace jstsp
 

@@ -117,27 +117,94 @@ int diag_check_host(jstsp_ctx *ctx, const char *what);
 // A proposed_algorithm solve whose device work has been enqueued but whose results are still in the context's workspace
 // (proposed.hip): the halves of a pipelined JSTSP_HOST call.  Valid until the next solve on that context.
 struct PendingSolve {
-    bool active = false, fused = false, want_ce = false;
-    int batch = 0;
-    size_t g = 0, nm = 0;
-    int Imax = 0;
+    bool want_ce = false;               // convergence_error was asked for and has rows (Imax > 0)
     const float2 *dS = nullptr, *dY = nullptr;
     const double *dce = nullptr;
-    const uint32_t *ovf = nullptr;
+    const uint32_t *ovf = nullptr;      // the per-trial overflow flags (NULL: the solve did not use the fused pass)
 };
-// The two phases for a caller that stages its own inputs (c64.hip): every array argument in device memory (tau_Y, tau_S, rho on
-// the host as always).  enqueue: the whole solve without its final copies and flag read; flags: the trials whose predicted k
-// scale overflowed in the fused pass (one stream synchronisation); resolve: such a run of trials again by the three-kernel
-// iteration, outputs to device arrays.
-int proposed_enqueue_device(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
-                            const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
-                            const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
-                            bool want_ce, PendingSolve *out);
-int proposed_pending_flags(jstsp_ctx *ctx, const PendingSolve &p, std::vector<int> *ovf);
-int proposed_resolve_device(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
-                            const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
-                            const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
-                            jstsp_c32 *S_dev, jstsp_c32 *Y_dev, double *ce_dev);
+// Everything a proposed_algorithm solve is given (the arguments of jstsp_proposed_resume_c32, include/jstsp.h; Cx / Re: complex / real
+// element).  Per-trial arrays are contiguous, trial index slowest: a sub-batch is this record with its pointers moved, by sub() only.
+template <class Cx, class Re> struct AdmmProblemOf {
+    int N = 0, M = 0, Gr = 0, G2 = 0, batch = 0;
+    const Cx *subY = nullptr; const Re *Omega = nullptr; const Cx *A = nullptr, *B = nullptr;
+    const double *tau_Y = nullptr, *tau_S = nullptr, *rho = nullptr;
+    long long strideA = 0, strideB = 0;          // elements between the dictionaries of two trials, 0 = one for the batch
+    int Imax = 0, type = 0;
+    const int32_t *indx_S = nullptr;
+    Cx *S_out = nullptr, *Y_out = nullptr; double *ce_out = nullptr;
+    int it0 = 0; const Cx *state_in = nullptr; Cx *state_out = nullptr;
+    int memspace = JSTSP_HOST;
+    size_t nm() const { return (size_t)N * M; }
+    size_t g() const { return (size_t)Gr * G2; }
+    size_t state_elems() const { return 4 * nm() + 2 * g(); }
+    // Trials t0 .. t0 + cnt - 1.  A NULL pointer stays NULL, a zero stride stays the shared dictionary.  No product wraps: the
+    // entries have checked every factor (positive shape, 0 <= t0 < batch, strides 0 or at least one dictionary), and each
+    // offset lies inside an array of `batch` such slices that the caller holds in memory.
+    AdmmProblemOf sub(int t0, int cnt) const
+    {
+        auto at = [t0](auto *p, size_t per) { return p ? p + (size_t)t0 * per : nullptr; };
+        AdmmProblemOf s = *this;
+        s.batch = cnt;
+        s.subY = at(subY, nm()); s.Omega = at(Omega, nm()); s.A = at(A, (size_t)strideA); s.B = at(B, (size_t)strideB);
+        s.tau_Y = at(tau_Y, 1); s.tau_S = at(tau_S, 1); s.rho = at(rho, 1); s.indx_S = at(indx_S, g());
+        s.S_out = at(S_out, g()); s.Y_out = at(Y_out, nm()); s.ce_out = at(ce_out, (size_t)3 * Imax);
+        s.state_in = at(state_in, state_elems()); s.state_out = at(state_out, state_elems());
+        return s;
+    }
+};
+using AdmmProblem = AdmmProblemOf<jstsp_c32, float>;          // what the solver takes
+using AdmmProblem64 = AdmmProblemOf<jstsp_c64, double>;       // the same arrays as the _c64 entries receive them (c64.hip)
+
+// Runs of consecutive trials in an ascending list of flagged ones: fn(first trial, count) for each, until one fails.
+template <class F> int for_each_run(const std::vector<int> &ovf, F &&fn)
+{
+    for (size_t i = 0, j; i < ovf.size(); i = j) {
+        j = i + 1;
+        while (j < ovf.size() && ovf[j] == ovf[j - 1] + 1) ++j;
+        JSTSP_TRY(fn(ovf[i], (int)(j - i)));
+    }
+    return 0;
+}
+// The indices of the set words of a host copy of the per-trial overflow flags, appended to *out.
+inline void flagged_trials(const uint32_t *flags, size_t n, std::vector<int> *out)
+{
+    for (size_t t = 0; t < n; ++t)
+        if (flags[t]) out->push_back((int)t);
+}
+// The same from the device array (NULL: the solve did not use the fused pass): one copy, ONE synchronisation of ctx->stream.
+int read_flagged_trials(jstsp_ctx *ctx, const uint32_t *dev_flags, int batch, std::vector<int> *out);
+
+// The frame of a JSTSP_HOST call that runs as two halves on two contexts of the device (proposed.hip, c64.hip): trials
+// t0[k] .. t0[k] + cnt[k] - 1 on cx[k]; close() leaves the call's fallbacks and dictionary block in the caller's context.
+struct HostPipeline {
+    jstsp_ctx *cx[2] = {nullptr, nullptr};
+    int t0[2] = {0, 0}, cnt[2] = {0, 0}, fallbacks = 0;
+    int open(jstsp_ctx *ctx, int batch)
+    {
+        if (!ctx->helper) JSTSP_TRY(jstsp_create(ctx->device, &ctx->helper));
+        cx[0] = ctx; cx[1] = ctx->helper;
+        t0[1] = cnt[0] = ((batch / 2 + 7) / 8) * 8; cnt[1] = batch - cnt[0];
+        return 0;
+    }
+    // (a failure inside the pipeline - typically JSTSP_E_NOMEM for the helper's workspace - must not return while the other
+    //  half still reads the caller's host arrays or writes its outputs: both streams are drained first)
+    int drained(int rc) const
+    {
+        if (rc) for (int k = 0; k < 2; ++k) { DeviceScope ds(cx[k]->device); (void)hipStreamSynchronize(cx[k]->stream); }
+        return rc;
+    }
+    void close() const
+    {
+        cx[0]->fused_fallbacks = fallbacks;
+        cx[0]->last_dict_block = (cx[0]->last_dict_block == cx[1]->last_dict_block) ? cx[0]->last_dict_block : 0;
+    }
+};
+#define JSTSP_TRY_PIPE(pipe, expr) do { int rc_ = (pipe).drained(expr); if (rc_ != 0) return rc_; } while (0)
+
+// For a caller that stages its own inputs (c64.hip), every array of the record in device memory.  enqueue: the whole solve without
+// its final copies and flag read (the record's outputs are not written); resolve: a run of flagged trials again, unfused.
+int proposed_enqueue_device(jstsp_ctx *ctx, const AdmmProblem &p, bool want_ce, PendingSolve *out);
+int proposed_resolve_device(jstsp_ctx *ctx, const AdmmProblem &run);
 
 // Host -> device scalar block.
 int upload(jstsp_ctx *ctx, void *dst, const void *src, size_t bytes);

@@ -113,6 +113,71 @@ def test_one_trial_whose_k_jumps_is_re_solved_alone_and_matches_the_oracle():
     assert n3 == 1 and _rel(S3, S1) < 1e-5
 
 
+TWO_RUNS = (1, 2, 4)            # a run of two flagged trials and a single one; trial 0 is healthy
+
+
+def _two_runs():
+    """_small() and an Omega with the entries of the test above in three of its six trials: (inputs, Omega, Imax)."""
+    import torch
+    inp = _small()
+    inp["rho"] = torch.from_numpy(inp["rho"].numpy().astype(np.float32).astype(np.float64))   # (Omega + 2 rho exact in fp32)
+    Om = inp["Omega"].clone()
+    for bad in TWO_RUNS:
+        zero = (Om[bad] == 0).nonzero()
+        for r, c in zero[torch.linspace(0, len(zero) - 1, 7).long()].tolist():
+            Om[bad, r, c] = -2.0 * float(inp["rho"][bad]) + 1e-3
+    return inp, Om, 6
+
+
+def test_two_runs_of_flagged_trials_are_re_solved_each_at_its_own_offset():
+    """Three trials whose k jumps, in two runs (1-2 and 4): every array of the second run's re-solve starts at that run's first
+    trial, in the plain call (device and host memspace), the begin / end form and a resumed call (3 healthy iterations, then 3 with
+    the modified Omega from their state).  Each equals the same call by the three-kernel iteration."""
+    import torch
+    import jstsp19_amd as J
+    inp, Om, IM = _two_runs()
+    hyp = [inp[k].numpy() for k in ("tau_Y", "tau_Z", "rho")]
+    dev = [inp["subY"], Om, inp["A"], inp["B"]]
+    host = [x.cpu().numpy() for x in dev]
+    ctx = J.default_context(0)
+
+    def plain(a):
+        return J.proposed_algorithm(*a, IM, *hyp, "approximate"), None
+
+    def begin_end(a):
+        h = J.proposed_algorithm_begin(*a, IM, *hyp, "approximate")
+        return h.end(), h
+
+    state = J.proposed_algorithm_resume(inp["subY"], inp["Omega"], inp["A"], inp["B"], IM // 2, *hyp, "approximate")[3]
+
+    def resumed(a):
+        return J.proposed_algorithm_resume(*a, IM - IM // 2, *hyp, "approximate", state=state, it0=IM // 2, return_state=False)[:3], None
+
+    def run(fn, a, env):
+        os.environ.update(env)
+        try:
+            r, h = fn(a)
+            torch.cuda.synchronize()
+            n = ctx.last_fused_fallbacks()
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+        assert h is None or h.fallbacks == n
+        return [x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in r], n
+
+    for name, fn, a in (("device", plain, dev), ("host", plain, host), ("begin/end", begin_end, dev), ("resumed", resumed, dev)):
+        (S1, Y1, c1), n1 = run(fn, a, {})
+        (S0, Y0, c0), n0 = run(fn, a, {"JSTSP_FUSED": "0"})
+        print(name, "re-solved", n1, "S", [_rel(S1[t], S0[t]) for t in range(6)], "Y", [_rel(Y1[t], Y0[t]) for t in range(6)])
+        assert n1 == 3 and n0 == 0, name
+        assert np.all(np.isfinite(S1)) and np.all(np.isfinite(Y1)), name
+        for t in TWO_RUNS:
+            assert _rel(S1[t], S0[t]) < 1e-6 and _rel(Y1[t], Y0[t]) < 1e-6, (name, t)
+        for t in range(6):
+            assert _rel(S1[t], S0[t]) < 1e-5, (name, t)
+        assert np.array_equal(np.isfinite(c1), np.isfinite(c0)), (name, np.argwhere(np.isfinite(c1) != np.isfinite(c0))[:8].tolist())
+
+
 def test_pipelined_host_call_equals_the_staged_one_and_recovers_per_half():
     """A JSTSP_HOST call of >= 128 problems runs as two halves on two internal contexts (proposed.hip): bit for bit the outputs of
     the single staged call, also when trials in BOTH halves overflow their predicted scale and are solved again."""

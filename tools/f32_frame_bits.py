@@ -1,0 +1,282 @@
+#!/usr/bin/env python
+"""Bits of the fp32 proposed_algorithm through every entry of its call frame (plain, begin/end, resumed, the _c64 forms, the
+pipelined host calls, the refusals), to hold one build of the library against another as tools/f64_bits.py does for float64:
+``--dump FILE`` writes, for every call, each output array (above 4 KiB: its SHA-256), the status with
+jstsp_last_fused_fallbacks, jstsp_last_dictionary_block and the workspace size, and the message of a refused call, from the
+library that JSTSP_LIB names (default: the one built in the tree); ``--against FILE`` runs the same calls and compares byte for
+byte.
+
+    JSTSP_LIB=/path/to/other/libjstsp_mi355x.so python tools/f32_frame_bits.py --dump other.npz
+    python tools/f32_frame_bits.py --against other.npz --report profiles/f32_frame_bits.json
+"""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+from jstsp19_amd import _lib  # noqa: E402
+
+if os.environ.get("JSTSP_LIB"):
+    _lib.LIB_PATH = os.environ["JSTSP_LIB"]
+
+import jstsp19_amd as J  # noqa: E402
+import torch  # noqa: E402
+from jstsp19_amd.system_model import SweepParams, build_trials  # noqa: E402
+
+DEV = torch.device("cuda:0")
+HOST, DEVICE = _lib.HOST, _lib.DEVICE
+FORCED = {"JSTSP_FUSED_KBACK": "-20"}           # every trial overflows its predicted k scale: one run of the whole batch
+UNFUSED = {"JSTSP_FUSED": "0"}
+ARGS = ("N", "M", "Gr", "G2", "batch", "subY", "Omega", "A", "strideA", "B", "strideB", "Imax", "tau_Y", "tau_S", "rho", "type", "indx_S",
+        "S", "Y", "ce")
+
+
+class Problem:
+    """The arrays of build_trials in the C ABI's layout on the host: complex64 / float32, and widened for the _c64 entries."""
+
+    def __init__(self, inp, Omega=None):
+        colm = lambda a: np.ascontiguousarray(np.swapaxes(a.cpu().numpy(), -1, -2))
+        self.batch, self.N, self.M = (int(v) for v in inp["subY"].shape)
+        self.Gr, self.G2 = int(inp["A"].shape[-1]), int(inp["B"].shape[-2])
+        self.arr = {"subY": colm(inp["subY"]), "Omega": colm(inp["Omega"] if Omega is None else Omega).astype(np.float32), "A": colm(inp["A"]),
+                    "B": colm(inp["B"]), "indx_S": np.ascontiguousarray(inp["indx_S"].cpu().numpy().astype(np.int32))}
+        self.scal = {k: np.ascontiguousarray(inp[s].numpy(), dtype=np.float64) for k, s in (("tau_Y", "tau_Y"), ("tau_S", "tau_Z"), ("rho", "rho"))}
+        self.strideA = 0 if inp["A"].ndim == 2 else self.N * self.Gr
+        self.strideB = 0 if inp["B"].ndim == 2 else self.G2 * self.M
+        self.state_elems = 4 * self.N * self.M + 2 * self.Gr * self.G2
+
+
+def _place(a, mem):
+    return a if mem == HOST else torch.from_numpy(a).to(DEV)
+
+
+def _ptr(x):
+    return None if x is None else (x.data_ptr() if torch.is_tensor(x) else x.ctypes.data)
+
+
+def _host(x):
+    return x.cpu().numpy() if torch.is_tensor(x) else x
+
+
+def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=None, env=None, **over):
+    """One call of jstsp_proposed_{algorithm,resume}_{c32,c64} on P; yields (name, array) for every output, the status and the
+    counters, and the message when the call was refused.  resume: dict(it0, state (host array or None), same (state_out is
+    state_in), out (a state is returned)).  over: arguments replaced by name (None: a NULL pointer)."""
+    lib, ctx = _lib.load(), _lib.default_context(0)
+    cdt, rdt = (np.complex128, np.float64) if c64 else (np.complex64, np.float32)
+    wide = lambda a: a.astype(rdt if a.dtype.kind == "f" else cdt)
+    ins = {k: _place(wide(P.arr[k]), mem) for k in ("subY", "Omega", "A", "B")}
+    ins["indx_S"] = _place(P.arr["indx_S"], mem) if indx else None
+    zeros = lambda n, dt: _place(np.zeros(max(int(n), 1), dt), mem)
+    outs = {"S": zeros(P.batch * P.Gr * P.G2, cdt), "Y": zeros(P.batch * P.N * P.M, cdt), "ce": zeros(P.batch * 3 * Imax, np.float64) if ce else None}
+    v = dict(N=P.N, M=P.M, Gr=P.Gr, G2=P.G2, batch=P.batch, strideA=P.strideA, strideB=P.strideB, Imax=Imax, type=type, memspace=mem)
+    v.update({k: _ptr(x) for k, x in list(ins.items()) + list(outs.items())})
+    v.update({k: a.ctypes.data_as(_lib.c_dp) for k, a in P.scal.items()})
+    v.update(over)
+    args = [ctx.handle] + [v[k] for k in ARGS]
+    name = "jstsp_proposed_%s_%s" % ("resume" if resume else "algorithm", "c64" if c64 else "c32")
+    if resume:
+        st = resume.get("state")
+        s_in = None if st is None else _place(np.ascontiguousarray(st, dtype=cdt), mem)
+        s_out = s_in if resume.get("same") else (zeros(P.batch * P.state_elems, cdt) if resume.get("out", True) else None)
+        outs["state"] = s_out
+        args += [resume["it0"], _ptr(s_in), _ptr(s_out)]
+    os.environ.update(env or {})
+    try:
+        rc = getattr(lib, name)(*args, v["memspace"])
+        torch.cuda.synchronize()
+        msg = lib.jstsp_last_error() if rc else b""
+        info = [rc, ctx.last_fused_fallbacks(), ctx.last_dictionary_block(), ctx.workspace_bytes()]     # (the workspace only grows)
+    finally:
+        for k in env or {}:
+            os.environ.pop(k, None)
+    res = {k: (None if x is None else _host(x)) for k, x in outs.items()}
+    for k, a in res.items():
+        if a is not None:
+            yield "%s/%s" % (tag, k), a
+    yield tag + "/status_fallbacks_block_workspace", np.array(info, np.int64)
+    if rc:
+        yield tag + "/message", np.frombuffer(msg, np.uint8)
+    call.last = res
+
+
+def small():
+    import test_gpu_overflow_recovery as T
+    return Problem(T._small())
+
+
+def toeplitz():
+    p = SweepParams(Nt=64, Nr=64, L=4, T=8, Mr=8, snr_db=5.0)
+    assert p.solver_shape == (64, 512, 64, 256)
+    return Problem(build_trials(p, 0, 5, seed=43))
+
+
+def plain_cases():
+    for sname, P in (("small", small()), ("toeplitz", toeplitz())):
+        for ename, env in (("default", {}), ("forced", FORCED), ("unfused", UNFUSED)):
+            for mem in (HOST, DEVICE):
+                for type in (_lib.TYPE_APPROXIMATE, _lib.TYPE_STD):
+                    for indx in (False, True):
+                        for ce in (False, True):
+                            for Imax in (0, 1, 2, 12):
+                                tag = "plain/%s/%s/mem%d/type%d/indx%d/ce%d/Imax%d" % (sname, ename, mem, type, indx, ce, Imax)
+                                yield from call(tag, P, Imax, mem, type=type, indx=indx, ce=ce, env=env)
+
+
+def two_run_cases():
+    """three flagged trials in two runs (tests/test_gpu_overflow_recovery.py): the offsets of a second run"""
+    import test_gpu_overflow_recovery as T
+    inp, Om, IM = T._two_runs()
+    P = Problem(inp, Om)
+    for mem in (HOST, DEVICE):
+        yield from call("two_runs/plain/mem%d" % mem, P, IM, mem)
+        yield from call("two_runs/plain_two_outputs/mem%d" % mem, P, IM, mem, ce=False)
+        healthy = Problem(inp)
+        list(call("-", healthy, IM // 2, mem, resume=dict(it0=0)))
+        st = call.last["state"]
+        yield from call("two_runs/resumed/mem%d" % mem, P, IM - IM // 2, mem, resume=dict(it0=IM // 2, state=st))
+        yield from call("two_runs/resumed_in_place/mem%d" % mem, P, IM - IM // 2, mem, resume=dict(it0=IM // 2, state=st.copy(), same=True))
+    r = J.proposed_algorithm_begin(inp["subY"], Om, inp["A"], inp["B"], IM, inp["tau_Y"].numpy(), inp["tau_Z"].numpy(), inp["rho"].numpy())
+    out = r.end()
+    for i, o in enumerate(out):
+        yield "two_runs/begin_end/%d" % i, o.cpu().numpy()
+    yield "two_runs/begin_end/fallbacks", np.array([r.fallbacks, J.default_context(0).last_fused_fallbacks()])
+
+
+def begin_end_cases():
+    import test_gpu_overflow_recovery as T
+    inp = T._small()
+    hyp = [inp[k].numpy() for k in ("tau_Y", "tau_Z", "rho")]
+    for ename, env in (("default", {}), ("forced", FORCED)):
+        for want_ce, indx in ((True, None), (False, None), (True, inp["indx_S"])):
+            os.environ.update(env)
+            try:
+                h = J.proposed_algorithm_begin(inp["subY"], inp["Omega"], inp["A"], inp["B"], 12, *hyp, want_ce=want_ce, indx_S=indx)
+                out = h.end()
+                torch.cuda.synchronize()
+            finally:
+                for k in env:
+                    os.environ.pop(k, None)
+            tag = "begin_end/%s/ce%d/indx%d" % (ename, want_ce, indx is not None)
+            for i, o in enumerate(out):
+                if o is not None:
+                    yield "%s/%d" % (tag, i), o.cpu().numpy()
+            ctx = J.default_context(0)
+            yield tag + "/fallbacks_block", np.array([h.fallbacks, ctx.last_fused_fallbacks(), ctx.last_dictionary_block()])
+
+
+def resume_cases():
+    P = small()
+    for c64 in (False, True):
+        for mem in (HOST, DEVICE):
+            for ename, env in (("default", {}), ("forced", FORCED)):
+                for indx in (False, True):
+                    tag = "resume/%s/mem%d/%s/indx%d" % ("c64" if c64 else "c32", mem, ename, indx)
+                    kw = dict(c64=c64, indx=indx, env=env)
+                    yield from call(tag + "/zero12", P, 12, mem, resume=dict(it0=0), **kw)
+                    yield from call(tag + "/leg1", P, 6, mem, resume=dict(it0=0), **kw)
+                    st = call.last["state"]
+                    yield from call(tag + "/leg2", P, 6, mem, resume=dict(it0=6, state=st), **kw)
+                    yield from call(tag + "/leg2_in_place", P, 6, mem, resume=dict(it0=6, state=st.copy(), same=True), **kw)
+                    yield from call(tag + "/leg2_no_state_out", P, 6, mem, ce=False, resume=dict(it0=6, state=st, out=False), **kw)
+            yield from call("resume/%s/mem%d/refused/negative_it0" % (c64, mem), P, 3, mem, c64=c64, resume=dict(it0=-1))
+            yield from call("resume/%s/mem%d/refused/it0_without_state" % (c64, mem), P, 3, mem, c64=c64, resume=dict(it0=2))
+            yield from call("resume/%s/mem%d/refused/Imax0" % (c64, mem), P, 0, mem, c64=c64, resume=dict(it0=0))
+            yield from call("resume/%s/mem%d/refused/it0_overflow" % (c64, mem), P, 3, mem, c64=c64, resume=dict(it0=2 ** 31 - 2))
+
+
+def c64_cases():
+    for sname, P in (("small", small()), ("toeplitz", toeplitz())):
+        for mem in (HOST, DEVICE):
+            for ename, env in (("default", {}), ("forced", FORCED), ("unfused", UNFUSED)):
+                for type, indx, ce in ((0, False, True), (0, True, True), (0, False, False), (1, False, True)):
+                    tag = "c64/%s/mem%d/%s/type%d/indx%d/ce%d" % (sname, mem, ename, type, indx, ce)
+                    yield from call(tag, P, 12, mem, c64=True, type=type, indx=indx, ce=ce, env=env)
+
+
+def pipelined_cases():
+    """the two-halves frame (tests/test_gpu_overflow_recovery.py): batch 128 is its threshold"""
+    p = SweepParams(Nt=64, Nr=64, L=8, T=64, Mr=8, snr_db=5.0)
+    P = Problem(build_trials(p, 0, 128, seed=11))
+    for c64 in (False, True):
+        for ename, env in (("default", {}), ("forced", FORCED), ("staged", {"JSTSP_HOST_PIPELINE": "0"})):
+            yield from call("pipelined/%s/%s" % ("c64" if c64 else "c32", ename), P, 12, HOST, c64=c64, env=env)
+        yield from call("pipelined/%s/forced_angles_two_outputs" % ("c64" if c64 else "c32"), P, 12, HOST, c64=c64, env=FORCED, indx=True, ce=False)
+
+
+def refusal_cases():
+    P = small()
+    for mem in (HOST, DEVICE):
+        for c64 in (False, True):
+            tag = "refused/%s/mem%d/" % ("c64" if c64 else "c32", mem)
+            for name in ("subY", "Omega", "A", "B", "tau_Y", "tau_S", "rho", "S"):
+                yield from call(tag + "null_" + name, P, 3, mem, c64=c64, **{name: None})
+            yield from call(tag + "bad_type", P, 3, mem, c64=c64, type=5)
+            if not c64:         # (the _c64 form narrows (batch - 1) strideA + N Gr elements before the stride is judged)
+                yield from call(tag + "strideA_too_small", P, 3, mem, strideA=1)
+            yield from call(tag + "strideB_too_small", P, 3, mem, c64=c64, strideB=1)
+            yield from call(tag + "bad_shape", P, 3, mem, c64=c64, N=0)
+            yield from call(tag + "negative_Imax", P, -1, mem, c64=c64)
+            yield from call(tag + "std_N_below_Gr", P, 3, mem, c64=c64, type=_lib.TYPE_STD, N=P.N // 2)
+            yield from call(tag + "bad_memspace", P, 3, mem, c64=c64, memspace=7)
+    lib, ctx = _lib.load(), _lib.default_context(0)
+    one = np.zeros(16, np.complex64)
+    vp = one.ctypes.data
+    rc = lib.jstsp_proposed_algorithm_c32(None, 2, 2, 2, 2, 1, vp, vp, vp, 0, vp, 0, 1, None, None, None, 0, None, vp, vp, None, HOST)
+    yield "refused/null_context", np.frombuffer(("%d: " % rc).encode() + lib.jstsp_last_error(), np.uint8)
+    h = C.c_void_p()
+    rc = lib.jstsp_proposed_algorithm_begin_c32(ctx.handle, 2, 2, 2, 2, 1, None, vp, vp, 0, vp, 0, 1, None, None, None, 0, None, vp, vp, None, C.byref(h))
+    yield "refused/begin_null_array", np.frombuffer(("%d: " % rc).encode() + lib.jstsp_last_error(), np.uint8)
+    rc = lib.jstsp_proposed_algorithm_end(ctx.handle, None, None)
+    yield "refused/end_null_handle", np.frombuffer(("%d: " % rc).encode() + lib.jstsp_last_error(), np.uint8)
+
+
+def cases():
+    _lib.default_context(0).use_torch_stream()
+    for gen in (plain_cases, two_run_cases, begin_end_cases, resume_cases, c64_cases, pipelined_cases, refusal_cases):
+        yield from gen()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--dump", metavar="FILE")
+    g.add_argument("--against", metavar="FILE")
+    ap.add_argument("--report", metavar="JSON", help="with --against: write the counts here")
+    a = ap.parse_args()
+    got, nbytes = {}, 0
+    for k, v in cases():
+        if k.startswith("-"):
+            continue
+        assert k not in got, k
+        v = np.ascontiguousarray(v)
+        nbytes += v.nbytes
+        # (the outputs of the pipelined calls alone are gigabytes: an array above 4 KiB is kept as the SHA-256 of its type, shape and bytes)
+        got[k] = v if v.nbytes <= 4096 else np.frombuffer(hashlib.sha256(repr((v.dtype.str, v.shape)).encode() + v.tobytes()).digest(), np.uint8)
+    if a.dump:
+        np.savez(a.dump, **got)
+        print(json.dumps({"library": os.path.relpath(_lib.LIB_PATH, ROOT), "arrays": len(got)}))
+        return 0
+    with np.load(a.against, allow_pickle=False) as z:
+        ref = {k: z[k] for k in z.files}
+    diff = sorted(k for k in set(ref) | set(got) if k not in ref or k not in got or ref[k].dtype != got[k].dtype or
+                  ref[k].shape != got[k].shape or ref[k].tobytes() != got[k].tobytes())
+    rep = {"library": os.path.relpath(_lib.LIB_PATH, ROOT), "against": os.path.basename(a.against), "arrays_compared": len(set(ref) | set(got)),
+           "bytes_compared": int(nbytes), "differences": len(diff), "differing": diff}
+    print(json.dumps(rep))
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump(rep, f, indent=1)
+            f.write("\n")
+    return 1 if diff else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
