@@ -374,16 +374,16 @@ static float mc_eig_stop()
 
 // One packed b operand for the batch and a shape hgemm_pair_kernel takes: the a operand (rows x Kd per problem, column-major, leading
 // dimension `rows`) in fragment order as well - the two-trials-per-workgroup kernel reads packed operands only (hgemm.hip)
-static size_t pair_apack_bytes(int Kd, int batch) { return rnd256((size_t)batch * 2 * (4 * ((Kd + 63) / 64)) * 256 * sizeof(uint4)); }
-static int pair_apack(jstsp_ctx *ctx, const float2 *Aop, long long sAt, int rows, int Kd, int batch, const uint32_t *amax, const HPack &bp,
-                      HGemmDesc &hd)
+// Its shape and array (none when its k padding differs from the b pack's), then the packing into it.
+static void pair_apack_take(Arena &a, HPack &ap, int Kd, int batch, const HPack &bp)
 {
-    HPack ap;
     ap.KS = 4 * ((Kd + 63) / 64); ap.JT = 2; ap.count = batch;
     ap.st = (long long)ap.JT * ap.KS * 256;
-    if (ap.KS != bp.KS) return 0;
-    ap.data = ctx->arena.get<uint4>((size_t)batch * ap.st);
-    JSTSP_REQUIRE(ap.data, JSTSP_E_NOMEM, "workspace exhausted (packed a operand)");
+    ap.data = ap.KS == bp.KS ? a.get<uint4>((size_t)batch * ap.st) : nullptr;
+}
+static int pair_apack(jstsp_ctx *ctx, const HPack &ap, const float2 *Aop, long long sAt, int rows, int Kd, const uint32_t *amax, HGemmDesc &hd)
+{
+    if (!ap.data) return 0;
     JSTSP_TRY(hgemm_repack(ctx, ap, Aop, sAt, rows, 1, 0, Kd, rows, amax));
     hd.Ap = ap.data; hd.sApt = ap.st; hd.aKS = ap.KS;
     return 0;
@@ -400,47 +400,41 @@ int jstsp_correlate_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
     JSTSP_REQUIRE(K_ && A_ && B_ && out, JSTSP_E_NULL, "correlate: NULL array argument");
     JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0, JSTSP_E_SHAPE, "correlate: bad shape");
     const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-    const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
-    size_t need = rnd256(batch * ng * sizeof(float2)) + rnd256(batch * g * sizeof(float2));
     const bool h2 = use_hgemm(N, G2, M);
     const int nB = strideB ? batch : 1;
-    if (h2) need += hgemm_pack_bytes(M, G2, nB) + rnd256(batch * sizeof(uint32_t)) + rnd256(batch * nm * sizeof(float2)) +
-                    rnd256((size_t)nB * G2 * M * sizeof(float2)) + rnd256((size_t)batch * N * sizeof(int32_t)) +
-                    rnd256((size_t)nB * G2 * sizeof(int32_t));
     const bool pair = h2 && !strideB && hgemm_pair_shape(N, G2, batch);
-    if (pair) need += pair_apack_bytes(M, batch);
-    if (memspace == JSTSP_HOST)
-        need += rnd256(batch * nm * sizeof(float2)) + rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *K, *A, *B;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(K_), batch * nm, memspace, &K));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(B_), szB, memspace, &B));
-    float2 *Tc = ctx->arena.get<float2>(batch * ng);
-    float2 *O = ctx->arena.get<float2>(batch * g);
-    JSTSP_REQUIRE(Tc && O, JSTSP_E_NOMEM, "correlate: workspace exhausted");
+    float2 *Tc, *O, *Ks = nullptr, *Bs = nullptr;
+    int32_t *eK = nullptr, *eB = nullptr;
+    uint32_t *amax = nullptr;
+    HPack pk, ap;
+    JSTSP_TRY(arena_open(ctx, "correlate", [&](Arena &a) {
+        K = a.in(as_f2(K_), batch * nm, memspace);
+        A = a.in(as_f2(A_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        B = a.in(as_f2(B_), dict_elems(strideB, (size_t)G2 * M, batch), memspace);
+        Tc = a.get<float2>(batch * ng);
+        O = a.get<float2>(batch * g);
+        if (!h2) return;
+        eK = a.get<int32_t>((size_t)batch * N); eB = a.get<int32_t>((size_t)nB * G2);
+        Ks = a.get<float2>(batch * nm); Bs = a.get<float2>((size_t)nB * G2 * M);
+        hgemm_pack_take(pk, a, M, G2, nB);
+        amax = a.get<uint32_t>(batch);
+        if (pair) pair_apack_take(a, ap, M, batch, pk);
+    }));
     // A^H (K B^H): the cheaper association (N*M*G2 + Gr*N*G2 MACs)
     if (h2) {
         // rows of K (index n) and rows of B (index g) are not contracted: equilibrate them (see axis_exp_kernel)
-        int32_t *eK = ctx->arena.get<int32_t>((size_t)batch * N), *eB = ctx->arena.get<int32_t>((size_t)nB * G2);
-        float2 *Ks = ctx->arena.get<float2>(batch * nm), *Bs = ctx->arena.get<float2>((size_t)nB * G2 * M);
-        JSTSP_REQUIRE(eK && eB && Ks && Bs, JSTSP_E_NOMEM, "correlate: workspace exhausted");
         const long long sBs = strideB ? (long long)G2 * M : 0;
         JSTSP_TRY(axis_exp(ctx, N, M, K, (long long)nm, batch, 0, eK));
         JSTSP_TRY(scale2(ctx, N, M, batch, K, (long long)nm, Ks, (long long)nm, eK, N, nullptr, 0, -1));
         JSTSP_TRY(axis_exp(ctx, G2, M, B, strideB, nB, 0, eB));
         JSTSP_TRY(scale2(ctx, G2, M, nB, B, strideB, Bs, sBs, eB, G2, nullptr, 0, -1));
         // b(k = m, j = g) = conj(B[g + G2 m]) packed once; a = K
-        HPack pk;
-        JSTSP_TRY(hgemm_pack(ctx, pk, ctx->arena, Bs, sBs, G2, 1, 1, M, G2, nB, (long long)G2 * M));
-        uint32_t *amax = ctx->arena.get<uint32_t>(batch);
-        JSTSP_REQUIRE(amax, JSTSP_E_NOMEM, "correlate: workspace exhausted");
+        JSTSP_TRY(hgemm_pack_fill(ctx, pk, Bs, sBs, G2, 1, 1, M, G2, (long long)G2 * M));
         JSTSP_TRY(hgemm_absmax(ctx, Ks, (long long)nm, (long long)nm, batch, amax));
         HGemmDesc hd{Ks, (long long)nm, N, amax, pk.data, strideB ? pk.st : 0, pk.bmax, strideB ? 1 : 0, pk.KS, pk.JT,
                      Tc, (long long)ng, N, N, G2, M, batch, EPI_NONE, nullptr, nullptr, nullptr};
-        if (pair) JSTSP_TRY(pair_apack(ctx, Ks, (long long)nm, N, M, batch, amax, pk, hd));
+        if (pair) JSTSP_TRY(pair_apack(ctx, ap, Ks, (long long)nm, N, M, amax, hd));
         JSTSP_TRY(launch_hgemm(ctx, hd, "correlate"));
         JSTSP_TRY(scale2(ctx, N, G2, batch, Tc, (long long)ng, Tc, (long long)ng, eK, N, eB, strideB ? G2 : 0, +1));
     } else
@@ -462,47 +456,42 @@ int jstsp_synthesize_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch
     JSTSP_REQUIRE(S_ && A_ && B_ && out, JSTSP_E_NULL, "synthesize: NULL array argument");
     JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0, JSTSP_E_SHAPE, "synthesize: bad shape");
     const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-    const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
-    size_t need = rnd256(batch * ng * sizeof(float2)) + rnd256(batch * nm * sizeof(float2));
     const bool h2 = use_hgemm(N, M, G2);
     const int nB = strideB ? batch : 1;
-    if (h2) need += hgemm_pack_bytes(G2, M, nB) + rnd256(batch * sizeof(uint32_t)) + rnd256((size_t)nB * G2 * M * sizeof(float2)) +
-                    rnd256((size_t)batch * N * sizeof(int32_t)) + rnd256((size_t)nB * M * sizeof(int32_t));
     const bool pair = h2 && !strideB && hgemm_pair_shape(N, M, batch);
-    if (pair) need += pair_apack_bytes(G2, batch);
-    if (memspace == JSTSP_HOST)
-        need += rnd256(batch * g * sizeof(float2)) + rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *S, *A, *B;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(S_), batch * g, memspace, &S));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(B_), szB, memspace, &B));
-    float2 *W = ctx->arena.get<float2>(batch * ng);
-    float2 *O = ctx->arena.get<float2>(batch * nm);
-    JSTSP_REQUIRE(W && O, JSTSP_E_NOMEM, "synthesize: workspace exhausted");
+    float2 *W, *O, *Bs = nullptr;
+    int32_t *eW = nullptr, *eB = nullptr;
+    uint32_t *amax = nullptr;
+    HPack pk, ap;
+    JSTSP_TRY(arena_open(ctx, "synthesize", [&](Arena &a) {
+        S = a.in(as_f2(S_), batch * g, memspace);
+        A = a.in(as_f2(A_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        B = a.in(as_f2(B_), dict_elems(strideB, (size_t)G2 * M, batch), memspace);
+        W = a.get<float2>(batch * ng);
+        O = a.get<float2>(batch * nm);
+        if (!h2) return;
+        eW = a.get<int32_t>((size_t)batch * N); eB = a.get<int32_t>((size_t)nB * M);
+        Bs = a.get<float2>((size_t)nB * G2 * M);
+        hgemm_pack_take(pk, a, G2, M, nB);
+        amax = a.get<uint32_t>(batch);
+        if (pair) pair_apack_take(a, ap, G2, batch, pk);
+    }));
     JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, Gr, batch, Mat{A, strideA, N}, Mat{S, (long long)g, Gr}, W,
                    (long long)ng, N));
     if (h2) {
         // rows of A S (index n) and columns of B (index m) are not contracted: equilibrate them (see axis_exp_kernel)
-        int32_t *eW = ctx->arena.get<int32_t>((size_t)batch * N), *eB = ctx->arena.get<int32_t>((size_t)nB * M);
-        float2 *Bs = ctx->arena.get<float2>((size_t)nB * G2 * M);
-        JSTSP_REQUIRE(eW && eB && Bs, JSTSP_E_NOMEM, "synthesize: workspace exhausted");
         const long long sBs = strideB ? (long long)G2 * M : 0;
         JSTSP_TRY(axis_exp(ctx, N, G2, W, (long long)ng, batch, 0, eW));
         JSTSP_TRY(scale2(ctx, N, G2, batch, W, (long long)ng, W, (long long)ng, eW, N, nullptr, 0, -1));
         JSTSP_TRY(axis_exp(ctx, G2, M, B, strideB, nB, 1, eB));
         JSTSP_TRY(scale2(ctx, G2, M, nB, B, strideB, Bs, sBs, nullptr, 0, eB, M, -1));
         // b(k = g, j = m) = B[g + G2 m] packed once; a = A S
-        HPack pk;
-        JSTSP_TRY(hgemm_pack(ctx, pk, ctx->arena, Bs, sBs, 1, G2, 0, G2, M, nB, (long long)G2 * M));
-        uint32_t *amax = ctx->arena.get<uint32_t>(batch);
-        JSTSP_REQUIRE(amax, JSTSP_E_NOMEM, "synthesize: workspace exhausted");
+        JSTSP_TRY(hgemm_pack_fill(ctx, pk, Bs, sBs, 1, G2, 0, G2, M, (long long)G2 * M));
         JSTSP_TRY(hgemm_absmax(ctx, W, (long long)ng, (long long)ng, batch, amax));
         HGemmDesc hd{W, (long long)ng, N, amax, pk.data, strideB ? pk.st : 0, pk.bmax, strideB ? 1 : 0, pk.KS, pk.JT,
                      O, (long long)nm, N, N, M, G2, batch, EPI_NONE, nullptr, nullptr, nullptr};
-        if (pair) JSTSP_TRY(pair_apack(ctx, W, (long long)ng, N, G2, batch, amax, pk, hd));
+        if (pair) JSTSP_TRY(pair_apack(ctx, ap, W, (long long)ng, N, G2, amax, hd));
         JSTSP_TRY(launch_hgemm(ctx, hd, "synthesize"));
         JSTSP_TRY(scale2(ctx, N, M, batch, O, (long long)nm, O, (long long)nm, eW, N, eB, strideB ? M : 0, +1));
     } else
@@ -529,42 +518,42 @@ int jstsp_ls_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
                   "ls: a factor too large for the float64 pinv kernel must have full rank (A: N >= Gr, B: M >= G2)");
     const size_t nm = (size_t)N * M, g = (size_t)Gr * G2, ng = (size_t)N * G2;
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-    const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
-    size_t need = 2 * rnd256(batch * ng * sizeof(float2)) + 3 * rnd256(batch * g * sizeof(float2));
-    need += pA ? rnd256((size_t)nA * Gr * N * sizeof(float2))
-               : 2 * rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + hinv_bytes(Gr, nA);
-    need += pB ? rnd256((size_t)nB * M * G2 * sizeof(float2))
-               : 2 * rnd256((size_t)nB * G2 * G2 * sizeof(float2)) + hinv_bytes(G2, nB);
-    if (memspace == JSTSP_HOST)
-        need += rnd256(batch * nm * sizeof(float2)) + rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
-    Arena &a = ctx->arena;
     const float2 *Y, *A, *B;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Y_), batch * nm, memspace, &Y));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(B_), szB, memspace, &B));
+    float2 *Tc, *Tc2, *R1, *S, *PB = nullptr, *GB = nullptr, *GBi = nullptr, *PA = nullptr, *GA = nullptr, *GAi = nullptr;
+    HinvWS hB, hA;
+    JSTSP_TRY(arena_open(ctx, "ls", [&](Arena &a) {
+        Y = a.in(as_f2(Y_), batch * nm, memspace);
+        A = a.in(as_f2(A_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        B = a.in(as_f2(B_), dict_elems(strideB, (size_t)G2 * M, batch), memspace);
+        Tc = a.get<float2>(batch * ng); Tc2 = a.get<float2>(batch * ng); R1 = a.get<float2>(batch * g);
+        S = a.get<float2>(batch * g);
+        // (the temporaries of an inverse are given back once it is enqueued: what follows lies over them, later in the stream)
+        if (pB) PB = a.get<float2>((size_t)nB * M * G2);
+        else {
+            GB = a.get<float2>((size_t)nB * G2 * G2); GBi = a.get<float2>((size_t)nB * G2 * G2);
+            const size_t mark = a.off;
+            hB.take(a, G2, nB);
+            a.off = mark;
+        }
+        if (pA) PA = a.get<float2>((size_t)nA * Gr * N);
+        else {
+            GA = a.get<float2>((size_t)nA * Gr * Gr); GAi = a.get<float2>((size_t)nA * Gr * Gr);
+            const size_t mark = a.off;
+            hA.take(a, Gr, nA);
+            a.off = mark;
+        }
+    }));
     JSTSP_TRY(diag_reset(ctx));
-    float2 *Tc = a.get<float2>(batch * ng), *Tc2 = a.get<float2>(batch * ng), *R1 = a.get<float2>(batch * g),
-           *S = a.get<float2>(batch * g);
-    JSTSP_REQUIRE(Tc && Tc2 && R1 && S, JSTSP_E_NOMEM, "ls: workspace exhausted");
     const Mat Am{A, strideA, N}, Bm{B, strideB, G2};
     const long long sg = (long long)g, sng = (long long)ng;
     // ---- B side: Tc = Y pinv(B)   (N x G2)
     if (pB) {
-        float2 *PB = a.get<float2>((size_t)nB * M * G2);
-        JSTSP_REQUIRE(PB, JSTSP_E_NOMEM, "ls: workspace exhausted");
         JSTSP_TRY(launch_pinv(ctx, G2, M, nB, B, strideB, G2, PB, (long long)M * G2, M));
         JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, M, batch, Mat{Y, (long long)nm, N}, Mat{PB, strideB ? (long long)M * G2 : 0, M},
                        Tc, sng, N, 1.f, nullptr, 0, 0, 0.f, GEMM_CORRELATE));
     } else {
-        float2 *GB = a.get<float2>((size_t)nB * G2 * G2), *GBi = a.get<float2>((size_t)nB * G2 * G2);
-        JSTSP_REQUIRE(GB && GBi, JSTSP_E_NOMEM, "ls: workspace exhausted");
         JSTSP_TRY(gemm(ctx, 'N', 'C', G2, G2, M, nB, Bm, Bm, GB, (long long)G2 * G2, G2));
-        const size_t mark = a.off;
-        JSTSP_TRY(hermitian_inverse(ctx, G2, nB, GB, GBi));
-        a.off = mark;
+        JSTSP_TRY(hermitian_inverse(ctx, G2, nB, GB, GBi, hB));
         JSTSP_TRY(gemm(ctx, 'N', 'C', N, G2, M, batch, Mat{Y, (long long)nm, N}, Bm, Tc2, sng, N, 1.f, nullptr, 0, 0, 0.f,
                        GEMM_CORRELATE));
         JSTSP_TRY(gemm(ctx, 'N', 'N', N, G2, G2, batch, Mat{Tc2, sng, N}, Mat{GBi, strideB ? (long long)G2 * G2 : 0, G2},
@@ -572,18 +561,12 @@ int jstsp_ls_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const 
     }
     // ---- A side: S = pinv(A) Tc   (Gr x G2)
     if (pA) {
-        float2 *PA = a.get<float2>((size_t)nA * Gr * N);
-        JSTSP_REQUIRE(PA, JSTSP_E_NOMEM, "ls: workspace exhausted");
         JSTSP_TRY(launch_pinv(ctx, N, Gr, nA, A, strideA, N, PA, (long long)Gr * N, Gr));
         JSTSP_TRY(gemm(ctx, 'N', 'N', Gr, G2, N, batch, Mat{PA, strideA ? (long long)Gr * N : 0, Gr}, Mat{Tc, sng, N}, S, sg,
                        Gr));
     } else {
-        float2 *GA = a.get<float2>((size_t)nA * Gr * Gr), *GAi = a.get<float2>((size_t)nA * Gr * Gr);
-        JSTSP_REQUIRE(GA && GAi, JSTSP_E_NOMEM, "ls: workspace exhausted");
         JSTSP_TRY(gemm(ctx, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr));
-        const size_t mark = a.off;
-        JSTSP_TRY(hermitian_inverse(ctx, Gr, nA, GA, GAi));
-        a.off = mark;
+        JSTSP_TRY(hermitian_inverse(ctx, Gr, nA, GA, GAi, hA));
         JSTSP_TRY(gemm(ctx, 'C', 'N', Gr, G2, N, batch, Am, Mat{Tc, sng, N}, R1, sg, Gr));
         JSTSP_TRY(gemm(ctx, 'N', 'N', Gr, G2, Gr, batch, Mat{GAi, strideA ? (long long)Gr * Gr : 0, Gr}, Mat{R1, sg, Gr}, S,
                        sg, Gr));
@@ -605,14 +588,12 @@ int jstsp_pinv_c32(jstsp_ctx *ctx, int rows, int cols, int batch, const jstsp_c3
     JSTSP_REQUIRE(pinv_fits(rows, cols), JSTSP_E_UNSUPPORTED,
                   "pinv: %d x %d does not fit the in-LDS float64 kernel ((max*min + min^2) * 16 B <= 156 KiB)", rows, cols);
     const size_t n = (size_t)rows * cols;
-    size_t need = rnd256(batch * n * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += rnd256(batch * n * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *A;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), batch * n, memspace, &A));
-    float2 *P = memspace == JSTSP_DEVICE ? reinterpret_cast<float2 *>(P_) : ctx->arena.get<float2>(batch * n);
-    JSTSP_REQUIRE(P, JSTSP_E_NOMEM, "pinv: workspace exhausted");
+    float2 *P;
+    JSTSP_TRY(arena_open(ctx, "pinv", [&](Arena &a) {
+        A = a.in(as_f2(A_), batch * n, memspace);
+        P = memspace == JSTSP_DEVICE ? as_f2(P_) : a.get<float2>(batch * n);
+    }));
     JSTSP_TRY(diag_reset(ctx));
     JSTSP_TRY(launch_pinv(ctx, rows, cols, batch, A, (long long)n, rows, P, (long long)n, cols));
     if (memspace == JSTSP_HOST) {
@@ -632,18 +613,16 @@ int jstsp_svt_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32 *Y_
     JSTSP_REQUIRE(std::min(Mr, Mt) <= 2048, JSTSP_E_UNSUPPORTED, "svt: min(Mr, Mt) = %d > 2048",
                   std::min(Mr, Mt));
     const size_t nm = (size_t)Mr * Mt;
-    size_t need = GramWS::bytes(Mr, Mt, batch, true) + rnd256(batch * sizeof(TrialParams)) +
-                  rnd256(batch * nm * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += rnd256(batch * nm * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *Y;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Y_), batch * nm, memspace, &Y));
-    TrialParams *prm = ctx->arena.get<TrialParams>(batch);
-    float2 *X = ctx->arena.get<float2>(batch * nm);
-    JSTSP_REQUIRE(prm && X, JSTSP_E_NOMEM, "svt: workspace exhausted");
+    TrialParams *prm;
+    float2 *X;
     GramWS w;
-    JSTSP_TRY(w.alloc(ctx->arena, Mr, Mt, batch, true));
+    JSTSP_TRY(arena_open(ctx, "svt", [&](Arena &a) {
+        Y = a.in(as_f2(Y_), batch * nm, memspace);
+        prm = a.get<TrialParams>(batch);
+        X = a.get<float2>(batch * nm);
+        (void)w.alloc(a, Mr, Mt, batch, true);
+    }));
     JSTSP_TRY(upload_tau_rho(ctx, batch, tau, nullptr, prm));
     JSTSP_TRY(svt_batched(ctx, w, Y, prm, nullptr, X));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(X_), X, batch * nm, memspace));
@@ -660,26 +639,25 @@ int jstsp_nmse_spectral_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp
     JSTSP_REQUIRE(R > 0 && C > 0 && batch > 0, JSTSP_E_SHAPE, "nmse: bad shape");
     JSTSP_REQUIRE(std::min(R, C) <= 2048, JSTSP_E_UNSUPPORTED, "nmse: min(R, C) = %d > 2048", std::min(R, C));
     const size_t n = (size_t)R * C;
-    size_t need = GramWS::bytes(R, C, batch, false) + 2 * rnd256(batch * n * sizeof(float2)) +
-                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double)) + rnd256((size_t)2 * batch * sizeof(uint32_t));
     const int ng = std::min(R, C);
     const bool big = ng > 128;                  // (block Jacobi with its basis: score_sigma_max_sq)
-    if (big) need += rnd256((size_t)batch * ng * ng * sizeof(float2)) + rnd256((size_t)batch * ng * sizeof(float));
-    if (memspace == JSTSP_HOST) need += 2 * rnd256(batch * n * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *S, *Zb;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(S_), batch * n, memspace, &S));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Zbar_), batch * n, memspace, &Zb));
-    float2 *D = ctx->arena.get<float2>(batch * n), *Zs = ctx->arena.get<float2>(batch * n);
-    uint32_t *mx = ctx->arena.get<uint32_t>((size_t)2 * batch);
-    float *num = ctx->arena.get<float>(batch), *den = ctx->arena.get<float>(batch);
-    double *o = ctx->arena.get<double>(batch);
-    float2 *U = big ? ctx->arena.get<float2>((size_t)batch * ng * ng) : nullptr;
-    float *lam = big ? ctx->arena.get<float>((size_t)batch * ng) : nullptr;
-    JSTSP_REQUIRE(D && Zs && mx && num && den && o && (!big || (U && lam)), JSTSP_E_NOMEM, "nmse: workspace exhausted");
+    float2 *D, *Zs, *U;
+    uint32_t *mx;
+    float *num, *den, *lam;
+    double *o;
     GramWS w;
-    JSTSP_TRY(w.alloc(ctx->arena, R, C, batch, false));
+    JSTSP_TRY(arena_open(ctx, "nmse", [&](Arena &a) {
+        S = a.in(as_f2(S_), batch * n, memspace);
+        Zb = a.in(as_f2(Zbar_), batch * n, memspace);
+        D = a.get<float2>(batch * n); Zs = a.get<float2>(batch * n);
+        mx = a.get<uint32_t>((size_t)2 * batch);
+        num = a.get<float>(batch); den = a.get<float>(batch);
+        o = a.get<double>(batch);
+        U = big ? a.get<float2>((size_t)batch * ng * ng) : nullptr;
+        lam = big ? a.get<float>((size_t)batch * ng) : nullptr;
+        (void)w.alloc(a, R, C, batch, false);
+    }));
     JSTSP_TRY(score_operands(ctx, (long long)n, batch, S, Zb, mx, D, Zs));
     JSTSP_TRY(score_sigma_max_sq(ctx, w, D, U, lam, num));
     JSTSP_TRY(score_sigma_max_sq(ctx, w, Zs, U, lam, den));
@@ -699,19 +677,17 @@ int jstsp_lambda_max_sequence_c32(jstsp_ctx *ctx, int n, int batch, int steps, c
     JSTSP_REQUIRE(G_ && lam, JSTSP_E_NULL, "lambda_max_sequence: NULL argument");
     JSTSP_REQUIRE(n > 0 && n <= 128 && batch > 0 && steps > 0, JSTSP_E_SHAPE, "lambda_max_sequence: 1 <= n <= 128, batch, steps > 0");
     const size_t nn = (size_t)n * n, tot = (size_t)steps * batch;
-    size_t need = rnd256((size_t)batch * lanczos_ne(n) * sizeof(float2)) + rnd256((size_t)batch * sizeof(int)) + rnd256(tot * sizeof(float));
-    if (memspace == JSTSP_HOST) need += rnd256(tot * nn * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *G;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(G_), tot * nn, memspace, &G));
+    float *o;
     GramWS w;                                   // (only the warm-start record and the shape are used)
     w.n = n; w.batch = batch; w.nsplit = 1;
     w.lz.ne = lanczos_ne(n);
-    w.lz.x = ctx->arena.get<float2>((size_t)batch * w.lz.ne);
-    w.lz.state = ctx->arena.get<int>((size_t)batch);
-    float *o = ctx->arena.get<float>(tot);
-    JSTSP_REQUIRE(w.lz.x && w.lz.state && o, JSTSP_E_NOMEM, "lambda_max_sequence: workspace exhausted");
+    JSTSP_TRY(arena_open(ctx, "lambda_max_sequence", [&](Arena &a) {
+        G = a.in(as_f2(G_), tot * nn, memspace);
+        w.lz.x = a.get<float2>((size_t)batch * w.lz.ne);
+        w.lz.state = a.get<int>((size_t)batch);
+        o = a.get<float>(tot);
+    }));
     JSTSP_TRY(lanczos_warm_reset(ctx, w));
     for (int s = 0; s < steps; ++s) {
         w.lz.call = s;
@@ -736,27 +712,25 @@ int jstsp_rate_c32(jstsp_ctx *ctx, int R, int C, int batch, const jstsp_c32 *S_,
     JSTSP_REQUIRE(std::min(R, C) <= 128, JSTSP_E_UNSUPPORTED, "rate: min(R, C) = %d > 128", std::min(R, C));
     const size_t n = (size_t)R * C;
     const int ng = std::min(R, C), ne = (ng + 1) & ~1;
-    size_t need = GramWS::bytes(R, C, batch, false) + 2 * rnd256(batch * n * sizeof(float2)) +
-                  2 * rnd256(batch * sizeof(float)) + rnd256(batch * sizeof(double)) + rnd256((size_t)2 * batch * sizeof(uint32_t)) +
-                  rnd256((size_t)batch * ng * ng * sizeof(float2)) + rnd256((size_t)batch * ng * sizeof(float)) + rnd256((size_t)batch * ng * sizeof(double)) +
-                  rnd256((size_t)batch * ne * ne * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += 2 * rnd256(batch * n * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *S, *Zb;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(S_), batch * n, memspace, &S));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Zbar_), batch * n, memspace, &Zb));
-    float2 *D = ctx->arena.get<float2>(batch * n), *Zs = ctx->arena.get<float2>(batch * n);
-    uint32_t *mx = ctx->arena.get<uint32_t>((size_t)2 * batch);
-    float *num = ctx->arena.get<float>(batch), *den = ctx->arena.get<float>(batch);
-    double *o = ctx->arena.get<double>(batch);
-    float2 *U = ctx->arena.get<float2>((size_t)batch * ng * ng);
-    float *lam = ctx->arena.get<float>((size_t)batch * ng);
-    double *lamd = ctx->arena.get<double>((size_t)batch * ng);
-    float2 *Vg = eig_needs_global_v(ng) ? ctx->arena.get<float2>((size_t)batch * ne * ne) : nullptr;
-    JSTSP_REQUIRE(D && Zs && mx && num && den && o && U && lam && lamd && (!eig_needs_global_v(ng) || Vg), JSTSP_E_NOMEM, "rate: workspace exhausted");
+    float2 *D, *Zs, *U, *Vg;
+    uint32_t *mx;
+    float *num, *den, *lam;
+    double *o, *lamd;
     GramWS w;
-    JSTSP_TRY(w.alloc(ctx->arena, R, C, batch, false));
+    JSTSP_TRY(arena_open(ctx, "rate", [&](Arena &a) {
+        S = a.in(as_f2(S_), batch * n, memspace);
+        Zb = a.in(as_f2(Zbar_), batch * n, memspace);
+        D = a.get<float2>(batch * n); Zs = a.get<float2>(batch * n);
+        mx = a.get<uint32_t>((size_t)2 * batch);
+        num = a.get<float>(batch); den = a.get<float>(batch);
+        o = a.get<double>(batch);
+        U = a.get<float2>((size_t)batch * ng * ng);
+        lam = a.get<float>((size_t)batch * ng);
+        lamd = a.get<double>((size_t)batch * ng);
+        Vg = eig_needs_global_v(ng) ? a.get<float2>((size_t)batch * ne * ne) : nullptr;
+        (void)w.alloc(a, R, C, batch, false);
+    }));
     JSTSP_TRY(score_operands(ctx, (long long)n, batch, S, Zb, mx, D, Zs));
     JSTSP_TRY(sigma_max_sq(ctx, w, D, num));
     JSTSP_TRY(sigma_max_sq(ctx, w, Zs, den));                     // leaves the Gram partials of the scaled Zbar in the workspace
@@ -781,20 +755,18 @@ int jstsp_mc_svt_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32 
     JSTSP_REQUIRE(std::min(Mr, Mt) <= 2048, JSTSP_E_UNSUPPORTED, "mc_svt: min(Mr, Mt) = %d > 2048",
                   std::min(Mr, Mt));
     const size_t nm = (size_t)Mr * Mt;
-    size_t need = GramWS::bytes(Mr, Mt, batch, true) + rnd256(batch * sizeof(TrialParams)) +
-                  2 * rnd256(batch * nm * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *OH;
     const float *Omega;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(OH_), batch * nm, memspace, &OH));
-    JSTSP_TRY(stage_in(ctx, Omega_, batch * nm, memspace, &Omega));
-    TrialParams *prm = ctx->arena.get<TrialParams>(batch);
-    float2 *Y = ctx->arena.get<float2>(batch * nm), *X = ctx->arena.get<float2>(batch * nm);
-    JSTSP_REQUIRE(prm && Y && X, JSTSP_E_NOMEM, "mc_svt: workspace exhausted");
+    TrialParams *prm;
+    float2 *Y, *X;
     GramWS w;
-    JSTSP_TRY(w.alloc(ctx->arena, Mr, Mt, batch, true));
+    JSTSP_TRY(arena_open(ctx, "mc_svt", [&](Arena &a) {
+        OH = a.in(as_f2(OH_), batch * nm, memspace);
+        Omega = a.in(Omega_, batch * nm, memspace);
+        prm = a.get<TrialParams>(batch);
+        Y = a.get<float2>(batch * nm); X = a.get<float2>(batch * nm);
+        (void)w.alloc(a, Mr, Mt, batch, true);
+    }));
     w.eig_stop = mc_eig_stop();
     JSTSP_TRY(upload_tau_rho(ctx, batch, tau, rho, prm));
     JSTSP_HIP(hipMemsetAsync(Y, 0, batch * nm * sizeof(float2), ctx->stream));     // mc_svt.m:5
@@ -823,31 +795,27 @@ int jstsp_mc_admm_c32(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c32
                   std::min(Mr, Mt));
     const size_t nm = (size_t)Mr * Mt;
     const bool want_ce = ce_out != nullptr;
-    size_t need = GramWS::bytes(Mr, Mt, batch, true) + rnd256(batch * sizeof(TrialParams)) +
-                  5 * rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float)) +
-                  2 * rnd256(batch * sizeof(float)) + rnd256((size_t)batch * std::max(Imax, 1) * sizeof(double));
-    if (want_ce) need += GramWS::bytes(Mr, Mt, batch, false);
-    if (memspace == JSTSP_HOST) need += 2 * rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *OH, *Htrue = nullptr;
     const float *Omega;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(OH_), batch * nm, memspace, &OH));
-    JSTSP_TRY(stage_in(ctx, Omega_, batch * nm, memspace, &Omega));
-    if (want_ce) JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Htrue_), batch * nm, memspace, &Htrue));
-    TrialParams *prm = ctx->arena.get<TrialParams>(batch);
-    float2 *X = ctx->arena.get<float2>(batch * nm), *Y = ctx->arena.get<float2>(batch * nm),
-           *Z = ctx->arena.get<float2>(batch * nm), *Zn = ctx->arena.get<float2>(batch * nm),
-           *D = ctx->arena.get<float2>(batch * nm);
-    float *invD = ctx->arena.get<float>(batch * nm);
-    float *num = ctx->arena.get<float>(batch), *den = ctx->arena.get<float>(batch);
-    double *ce = ctx->arena.get<double>((size_t)batch * std::max(Imax, 1));
-    JSTSP_REQUIRE(prm && X && Y && Z && Zn && D && invD && num && den && ce, JSTSP_E_NOMEM,
-                  "mc_admm: workspace exhausted");
+    TrialParams *prm;
+    float2 *X, *Y, *Z, *Zn, *D;
+    float *invD, *num, *den;
+    double *ce;
     GramWS w, wn;
-    JSTSP_TRY(w.alloc(ctx->arena, Mr, Mt, batch, true));
+    JSTSP_TRY(arena_open(ctx, "mc_admm", [&](Arena &a) {
+        OH = a.in(as_f2(OH_), batch * nm, memspace);
+        Omega = a.in(Omega_, batch * nm, memspace);
+        if (want_ce) Htrue = a.in(as_f2(Htrue_), batch * nm, memspace);
+        prm = a.get<TrialParams>(batch);
+        X = a.get<float2>(batch * nm); Y = a.get<float2>(batch * nm); Z = a.get<float2>(batch * nm);
+        Zn = a.get<float2>(batch * nm); D = a.get<float2>(batch * nm);
+        invD = a.get<float>(batch * nm);
+        num = a.get<float>(batch); den = a.get<float>(batch);
+        ce = a.get<double>((size_t)batch * std::max(Imax, 1));
+        (void)w.alloc(a, Mr, Mt, batch, true);
+        if (want_ce) (void)wn.alloc(a, Mr, Mt, batch, false);
+    }));
     w.eig_stop = mc_eig_stop();
-    if (want_ce) JSTSP_TRY(wn.alloc(ctx->arena, Mr, Mt, batch, false));
     JSTSP_TRY(upload_tau_rho(ctx, batch, tau, rho, prm));
     hipStream_t st = ctx->stream;
     JSTSP_HIP(hipMemsetAsync(X, 0, batch * nm * sizeof(float2), st));                // mc_admm.m:6-8
@@ -893,20 +861,15 @@ extern "C" int jstsp_gradient_head_c32(jstsp_ctx *ctx, int N, int Gr, int G2, in
     JSTSP_REQUIRE(batch > 0 && grad_head_shape_ok(N, Gr, G2), JSTSP_E_UNSUPPORTED,
                   "gradient_head: N = %d, Gr = %d, G2 = %d (needs N = Gr = 64, G2 a multiple of 64)", N, Gr, G2);
     const size_t ng = (size_t)N * G2, g = (size_t)Gr * G2;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-    const size_t szG = strideG ? (size_t)strideG * (batch - 1) + (size_t)Gr * Gr : (size_t)Gr * Gr;
-    size_t need = 2 * rnd256(batch * g * sizeof(float2));
-    if (memspace == JSTSP_HOST)
-        need += rnd256(batch * ng * sizeof(float2)) + rnd256(szA * sizeof(float2)) + rnd256(szG * sizeof(float2)) + rnd256(batch * g * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *Tc, *A, *GA, *RV = nullptr;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Tc_), batch * ng, memspace, &Tc));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(GA_), szG, memspace, &GA));
-    if (RV_) JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(RV_), batch * g, memspace, &RV));
-    float2 *Res = ctx->arena.get<float2>(batch * g), *P1 = ctx->arena.get<float2>(batch * g);
-    JSTSP_REQUIRE(Res && P1, JSTSP_E_NOMEM, "gradient_head: workspace exhausted");
+    float2 *Res, *P1;
+    JSTSP_TRY(arena_open(ctx, "gradient_head", [&](Arena &a) {
+        Tc = a.in(as_f2(Tc_), batch * ng, memspace);
+        A = a.in(as_f2(A_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        GA = a.in(as_f2(GA_), dict_elems(strideG, (size_t)Gr * Gr, batch), memspace);
+        if (RV_) RV = a.in(as_f2(RV_), batch * g, memspace);
+        Res = a.get<float2>(batch * g); P1 = a.get<float2>(batch * g);
+    }));
     JSTSP_TRY(launch_grad_head(ctx, G2, batch, Tc, (long long)ng, 0, 1, nullptr, nullptr, 0, A, strideA, GA, strideG, RV, nullptr, Res, P1, nullptr));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(Res_out), Res, batch * g, memspace));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(P1_out), P1, batch * g, memspace));

@@ -169,17 +169,37 @@ __device__ __forceinline__ float admm_z(const TrialParams &p, float x, float v1)
 #endif
 #endif
 
+// elements of a dictionary operand: `one` per problem, `stride` elements apart (0: one operand shared by the batch)
+inline size_t dict_elems(long long stride, size_t one, int batch) { return stride ? (size_t)stride * (batch - 1) + one : one; }
+
 // Grow-only device arena: one hipMalloc'd slab, bump allocation, reset per call.
+// A measuring arena (Arena::measuring()) has no memory and touches no HIP: get() only advances `off` and returns nullptr, so
+// the code that takes a call's arrays also states their size - `peak`, the high-water mark of `off`, which a caller may rewind
+// (solver_common.h: arena_open).  A get() that would pass `cap` of a real arena returns nullptr and sets `overrun`, which stays
+// set until the next reset(): a function that takes several arrays checks it once.
 struct Arena {
     char *base = nullptr;
-    size_t cap = 0, off = 0;
+    size_t cap = 0, off = 0, peak = 0;
+    bool measure = false, overrun = false;
+    hipStream_t st = nullptr;            // in(): the stream of the uploads
+    hipError_t err = hipSuccess;         //       the first upload that failed
+    static Arena measuring() { Arena m; m.measure = true; return m; }
     int reserve(size_t bytes);           // ensure capacity (may reallocate; invalidates pointers)
-    void reset() { off = 0; }
+    void reset() { off = peak = 0; overrun = false; err = hipSuccess; }
     template <class T> T *get(size_t n) {
         size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-        if (off + bytes > cap) return nullptr;
-        T *p = reinterpret_cast<T *>(base + off);
+        if (!measure && off + bytes > cap) { overrun = true; return nullptr; }
+        T *p = measure ? nullptr : reinterpret_cast<T *>(base + off);
         off += bytes;
+        if (off > peak) peak = off;
+        return p;
+    }
+    // an input of n elements: the caller's array when it is on the device, otherwise a copy staged here (uploaded when the arena
+    // has memory, in the order of the calls)
+    template <class T> const T *in(const T *caller, size_t n, int memspace) {
+        if (memspace == JSTSP_DEVICE) return caller;
+        T *p = get<T>(n);
+        if (p && err == hipSuccess) err = hipMemcpyAsync(p, caller, n * sizeof(T), hipMemcpyHostToDevice, st);
         return p;
     }
     void release();
@@ -359,6 +379,10 @@ int hgemm_absmax(jstsp_ctx *ctx, const float2 *X, long long n, long long sXt, in
 // b(kk, j) = B[t*sBt + kk*sBk + j*sBj] (conjugated if conj), kk < Kd, j < J; each B[t] spans n_contig contiguous elements
 int hgemm_pack(jstsp_ctx *ctx, HPack &p, Arena &ar, const float2 *B, long long sBt, long long sBk, long long sBj,
                int conj, int Kd, int J, int count, long long n_contig, const uint32_t *bmax_known = nullptr);
+// its two halves: the shape of the pack and its arrays `data` and `bmax` (hgemm_pack_bytes measures this one); then the packing
+void hgemm_pack_take(HPack &p, Arena &ar, int Kd, int J, int count);
+int hgemm_pack_fill(jstsp_ctx *ctx, const HPack &p, const float2 *B, long long sBt, long long sBk, long long sBj, int conj, int Kd,
+                    int J, long long n_contig, const uint32_t *bmax_known = nullptr);
 int hgemm_repack(jstsp_ctx *ctx, const HPack &p, const float2 *B, long long sBt, long long sBk, long long sBj, int conj,
                  int Kd, int J, const uint32_t *bmax);
 int launch_hgemm(jstsp_ctx *ctx, const HGemmDesc &d, const char *prof_name = nullptr);

@@ -1206,8 +1206,10 @@ bool use_hgemm(long long m, long long n, long long k)
 
 size_t hgemm_pack_bytes(int Kd, int J, int count)
 {
-    const size_t KS = 4 * (size_t)((Kd + 63) / 64), JT = 4 * (size_t)((J + 127) / 128);
-    return rnd256((size_t)count * JT * KS * 4096) + rnd256((size_t)count * sizeof(uint32_t));
+    Arena m = Arena::measuring();
+    HPack p;
+    hgemm_pack_take(p, m, Kd, J, count);
+    return m.peak;
 }
 
 int hgemm_absmax(jstsp_ctx *ctx, const float2 *X, long long n, long long sXt, int count, uint32_t *amax)
@@ -1221,8 +1223,7 @@ int hgemm_absmax(jstsp_ctx *ctx, const float2 *X, long long n, long long sXt, in
     return 0;
 }
 
-int hgemm_pack(jstsp_ctx *ctx, HPack &p, Arena &ar, const float2 *B, long long sBt, long long sBk, long long sBj,
-               int conj, int Kd, int J, int count, long long n_contig, const uint32_t *bmax_known)
+void hgemm_pack_take(HPack &p, Arena &ar, int Kd, int J, int count)
 {
     p.KS = 4 * ((Kd + 63) / 64);           // k padded to 64: an even number of 32-k stages (hgemm2_kernel, PD = 2)
     p.JT = 4 * ((J + 127) / 128);          // j padded to the 128-wide tile of the 8-wave kernel
@@ -1230,15 +1231,23 @@ int hgemm_pack(jstsp_ctx *ctx, HPack &p, Arena &ar, const float2 *B, long long s
     p.st = (long long)p.JT * p.KS * 256;
     p.data = ar.get<uint4>((size_t)count * p.st);
     p.bmax = ar.get<uint32_t>(count);
-    JSTSP_REQUIRE(p.data && p.bmax, JSTSP_E_NOMEM, "workspace exhausted (packed dictionary)");
+}
+
+int hgemm_pack_fill(jstsp_ctx *ctx, const HPack &p, const float2 *B, long long sBt, long long sBk, long long sBj, int conj, int Kd,
+                    int J, long long n_contig, const uint32_t *bmax_known)
+{
     // (bmax_known: the maxima of the same array from an earlier pack in the other orientation - one pass over it less)
-    if (bmax_known) JSTSP_HIP(hipMemcpyAsync(p.bmax, bmax_known, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    else JSTSP_TRY(hgemm_absmax(ctx, B, n_contig, sBt, count, p.bmax));
-    const long long slots = (long long)p.JT * p.KS * 64;
-    pack_b_kernel<<<dim3((unsigned)((slots + 255) / 256), count), 256, 0, ctx->stream>>>(B, sBt, sBk, sBj, conj, Kd, J,
-                                                                                         p.KS, p.JT, p.bmax, p.data);
-    JSTSP_HIP(hipGetLastError());
-    return 0;
+    if (bmax_known) JSTSP_HIP(hipMemcpyAsync(p.bmax, bmax_known, (size_t)p.count * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    else JSTSP_TRY(hgemm_absmax(ctx, B, n_contig, sBt, p.count, p.bmax));
+    return hgemm_repack(ctx, p, B, sBt, sBk, sBj, conj, Kd, J, p.bmax);
+}
+
+int hgemm_pack(jstsp_ctx *ctx, HPack &p, Arena &ar, const float2 *B, long long sBt, long long sBk, long long sBj,
+               int conj, int Kd, int J, int count, long long n_contig, const uint32_t *bmax_known)
+{
+    hgemm_pack_take(p, ar, Kd, J, count);
+    JSTSP_REQUIRE(p.data && p.bmax, JSTSP_E_NOMEM, "workspace exhausted (packed dictionary)");
+    return hgemm_pack_fill(ctx, p, B, sBt, sBk, sBj, conj, Kd, J, n_contig, bmax_known);
 }
 
 // Re-pack into an existing HPack (same shape) with operand maxima that are already on the device.

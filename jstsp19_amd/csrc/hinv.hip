@@ -106,33 +106,42 @@ __global__ __launch_bounds__(256) void two_i_minus_kernel(int n, float2 *P)
     }
 }
 
-size_t hinv_bytes(int n, int count)
+void HinvWS::take(Arena &a, int n, int count)
 {
     const size_t nn = (size_t)n * n;
+    T1 = a.get<float2>(count * nn);
+    T2 = a.get<float2>(count * nn);
+    lam = a.get<float>((size_t)count * n);
     const int ne = (n + 1) & ~1;
-    size_t b = 2 * rnd256(count * nn * sizeof(float2)) + rnd256((size_t)count * n * sizeof(float));
-    if (n <= 128 && eig_needs_global_v(n)) b += rnd256((size_t)count * ne * ne * sizeof(float2));
-    return b;
+    Vg = (n <= 128 && eig_needs_global_v(n)) ? a.get<float2>((size_t)count * ne * ne) : nullptr;
+}
+
+size_t hinv_bytes(int n, int count)
+{
+    Arena m = Arena::measuring();
+    HinvWS w;
+    w.take(m, n, count);
+    return m.peak;
+}
+
+int hermitian_inverse(jstsp_ctx *ctx, int n, int count, const float2 *G, float2 *Ginv)
+{
+    HinvWS w;
+    w.take(ctx->arena, n, count);
+    JSTSP_REQUIRE(!ctx->arena.overrun, JSTSP_E_NOMEM, "hermitian_inverse: workspace exhausted");
+    return hermitian_inverse(ctx, n, count, G, Ginv, w);
 }
 
 // Ginv[t] = G[t]^-1 for `count` Hermitian positive-definite n x n matrices.
-int hermitian_inverse(jstsp_ctx *ctx, int n, int count, const float2 *G, float2 *Ginv)
+int hermitian_inverse(jstsp_ctx *ctx, int n, int count, const float2 *G, float2 *Ginv, const HinvWS &w)
 {
     const size_t nn = (size_t)n * n;
-    Arena &a = ctx->arena;
     JSTSP_TRY(ensure_diag(ctx));
-    float2 *T1 = a.get<float2>(count * nn), *T2 = a.get<float2>(count * nn);
-    float *lam = a.get<float>((size_t)count * n);
-    JSTSP_REQUIRE(T1 && T2 && lam, JSTSP_E_NOMEM, "hermitian_inverse: workspace exhausted");
+    float2 *T1 = w.T1, *T2 = w.T2, *Vg = w.Vg;
+    float *lam = w.lam;
     const long long s = (long long)nn;
     const dim3 grid((unsigned)std::min<size_t>((nn + 255) / 256, 64), (unsigned)count);
     if (n <= 128) {
-        float2 *Vg = nullptr;
-        if (eig_needs_global_v(n)) {
-            const int ne = (n + 1) & ~1;
-            Vg = a.get<float2>((size_t)count * ne * ne);
-            JSTSP_REQUIRE(Vg, JSTSP_E_NOMEM, "hermitian_inverse: workspace exhausted");
-        }
         JSTSP_TRY(launch_eig(ctx, EIG_VECS, n, count, G, s, 1, 0, nullptr, nullptr, T1, lam, Vg));   // T1 = U
         hipLaunchKernelGGL(scale_cols_inv_kernel, grid, dim3(256), 0, ctx->stream, n, T1, lam, T2, ctx->diag + 2);   // T2 = U / lam
         JSTSP_HIP(hipGetLastError());

@@ -252,24 +252,18 @@ extern "C" int jstsp_mmv_omp_c32(jstsp_ctx *ctx, int N, int Gr, int S, int batch
     JSTSP_REQUIRE(strideA == 0 || strideA >= (long long)N * Gr, JSTSP_E_SHAPE, "strideA too small");
     JSTSP_ENTER(ctx);
     const int Kc = std::min(K, std::min(N, Gr));                   // at most min(N, Gr) independent atoms
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
     const size_t ns = (size_t)N * S, gs = (size_t)Gr * S;
-    size_t need = rnd256(batch * ns * sizeof(float2)) + rnd256((size_t)batch * N * Kc * sizeof(float2)) +
-                  rnd256((size_t)batch * Kc * Kc * sizeof(float2)) + rnd256((size_t)batch * Kc * S * sizeof(float2)) +
-                  rnd256(batch * gs * sizeof(float2)) + rnd256((size_t)batch * Kc * sizeof(int32_t)) +
-                  rnd256((size_t)batch * sizeof(int32_t));
-    if (memspace == JSTSP_HOST) need += rnd256(szA * sizeof(float2)) + rnd256(batch * ns * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
-    Arena &ar = ctx->arena;
     const float2 *A, *Y;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Y_), batch * ns, memspace, &Y));
-    float2 *R = ar.get<float2>(batch * ns), *Q = ar.get<float2>((size_t)batch * N * Kc),
-           *Rt = ar.get<float2>((size_t)batch * Kc * Kc), *T = ar.get<float2>((size_t)batch * Kc * S),
-           *Z = ar.get<float2>(batch * gs);
-    int32_t *io = ar.get<int32_t>((size_t)batch * Kc), *cnt = ar.get<int32_t>(batch);
-    JSTSP_REQUIRE(R && Q && Rt && T && Z && io && cnt, JSTSP_E_NOMEM, "mmv_omp: workspace exhausted");
+    float2 *R, *Q, *Rt, *T, *Z;
+    int32_t *io, *cnt;
+    JSTSP_TRY(arena_open(ctx, "mmv_omp", [&](Arena &ar) {
+        A = ar.in(as_f2(A_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        Y = ar.in(as_f2(Y_), batch * ns, memspace);
+        R = ar.get<float2>(batch * ns); Q = ar.get<float2>((size_t)batch * N * Kc);
+        Rt = ar.get<float2>((size_t)batch * Kc * Kc); T = ar.get<float2>((size_t)batch * Kc * S);
+        Z = ar.get<float2>(batch * gs);
+        io = ar.get<int32_t>((size_t)batch * Kc); cnt = ar.get<int32_t>(batch);
+    }));
     const size_t sh = 256 * sizeof(float) + (size_t)Gr * (sizeof(float) + sizeof(int)) + 16 + 8 * sizeof(double);
     JSTSP_HIP(hipFuncSetAttribute((const void *)mmv_omp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
     hipLaunchKernelGGL(mmv_omp_kernel, dim3(batch), dim3(256), sh, ctx->stream, N, Gr, S, Kc, pnorm, A, strideA, Y, R, Q,

@@ -836,7 +836,7 @@ __global__ __launch_bounds__(NT) void omp_gram_kernel(int size_d, int m, int Gr,
         }
 }
 
-static int omp_alloc(Arena &a, OmpState &s, int meas, int m, int batch)
+static void omp_alloc(Arena &a, OmpState &s, int meas, int m, int batch)
 {
     s.Qb = a.get<float2>((size_t)batch * meas * m);
     s.Rm = a.get<float2>((size_t)batch * m * m);
@@ -847,15 +847,6 @@ static int omp_alloc(Arena &a, OmpState &s, int meas, int m, int batch)
     s.mult = a.get<int>((size_t)batch * m);
     s.nu = a.get<int>(batch);
     s.sel = a.get<int>((size_t)batch * m);
-    JSTSP_REQUIRE(s.Qb && s.Rm && s.z && s.r && s.w && s.uniq && s.mult && s.nu && s.sel, JSTSP_E_NOMEM,
-                  "OMP: workspace exhausted");
-    return 0;
-}
-static size_t omp_bytes(int meas, int m, int batch)
-{
-    return rnd256((size_t)batch * meas * m * sizeof(float2)) + rnd256((size_t)batch * m * m * sizeof(float2)) +
-           rnd256((size_t)batch * m * sizeof(float2)) + 2 * rnd256((size_t)batch * meas * sizeof(float2)) +
-           3 * rnd256((size_t)batch * m * sizeof(int)) + rnd256(batch * sizeof(int));
 }
 
 }  // namespace jstsp
@@ -902,22 +893,19 @@ int jstsp_omp_c32(jstsp_ctx *ctx, int meas, int size_d, int batch, const jstsp_c
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
     JSTSP_REQUIRE(strideA == 0 || strideA >= (long long)meas * size_d, JSTSP_E_SHAPE, "strideA too small");
     JSTSP_ENTER(ctx);
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)meas * size_d : (size_t)meas * size_d;
-    size_t need = omp_bytes(meas, m, batch) + rnd256((size_t)batch * size_d * sizeof(float2)) * 2 +
-                  rnd256((size_t)batch * m * sizeof(int32_t)) + rnd256((size_t)batch * meas * m * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += rnd256(szA * sizeof(float2)) + rnd256((size_t)batch * meas * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *A, *v;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(A_), szA, memspace, &A));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(v_), (size_t)batch * meas, memspace, &v));
     OmpState s;
-    JSTSP_TRY(omp_alloc(ctx->arena, s, meas, m, batch));
-    float2 *corr = ctx->arena.get<float2>((size_t)batch * size_d);
-    float2 *xh = ctx->arena.get<float2>((size_t)batch * size_d);
-    int32_t *io = ctx->arena.get<int32_t>((size_t)batch * m);
-    float2 *to = target_out ? ctx->arena.get<float2>((size_t)batch * meas * m) : nullptr;
-    JSTSP_REQUIRE(corr && xh && io && (!target_out || to), JSTSP_E_NOMEM, "OMP: workspace exhausted");
+    float2 *corr, *xh, *to;
+    int32_t *io;
+    JSTSP_TRY(arena_open(ctx, "OMP", [&](Arena &a) {
+        A = a.in(as_f2(A_), dict_elems(strideA, (size_t)meas * size_d, batch), memspace);
+        v = a.in(as_f2(v_), (size_t)batch * meas, memspace);
+        omp_alloc(a, s, meas, m, batch);
+        corr = a.get<float2>((size_t)batch * size_d);
+        xh = a.get<float2>((size_t)batch * size_d);
+        io = a.get<int32_t>((size_t)batch * m);
+        to = target_out ? a.get<float2>((size_t)batch * meas * m) : nullptr;
+    }));
     hipStream_t st = ctx->stream;
     JSTSP_HIP(hipMemcpyAsync(s.r, v, (size_t)batch * meas * sizeof(float2), hipMemcpyDeviceToDevice, st));   // r = v (:10)
     JSTSP_HIP(hipMemsetAsync(s.nu, 0, batch * sizeof(int), st));
@@ -970,46 +958,51 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, 
     JSTSP_REQUIRE(m <= 1024, JSTSP_E_UNSUPPORTED, "omp_kron: m = %d > 1024", m);
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
     JSTSP_ENTER(ctx);
+    // what both routes below share: the staged inputs, the correlation's temporary, and with the split-f16 correlation the
+    // dictionary factor packed once (hgemm.hip) and the maxima of its other operand
+    const int meas = N * M, size_d = Gr * G2, nB = strideB ? batch : 1;
+    const size_t ng = (size_t)N * G2;
+    const bool h2 = use_hgemm(N, G2, M);
+    const float2 *Af, *Bf, *y;
+    float2 *xh, *Tc;
+    int32_t *io;
+    HPack pk;
+    uint32_t *rmax = nullptr;
+    auto inputs = [&](Arena &a) {
+        Af = a.in(as_f2(Af_), dict_elems(strideA, (size_t)N * Gr, batch), memspace);
+        Bf = a.in(as_f2(Bf_), dict_elems(strideB, (size_t)G2 * M, batch), memspace);
+        y = a.in(as_f2(y_), (size_t)batch * meas, memspace);
+    };
+    auto packed = [&](Arena &a) {
+        if (!h2) return;
+        hgemm_pack_take(pk, a, M, G2, nB);
+        rmax = a.get<uint32_t>(batch);
+    };
     {
         // Coefficient-domain OMP (omp_gram_kernel): one correlation, the two factor Grams, one kernel for all m
         // iterations.  The measurement-space Gram-Schmidt below when the Cholesky factor does not fit in LDS.
         const size_t lds = (size_t)m * m * 16 + 3 * (size_t)m * 16 + 3 * (size_t)m * 4;
         if (lds <= 150 * 1024) {
-            const int size_d = Gr * G2, nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-            const size_t nm = (size_t)N * M, ng = (size_t)N * G2, g = (size_t)size_d;
-            const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-            const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
-            const bool h2 = use_hgemm(N, G2, M);
-            size_t need = 3 * rnd256(batch * g * sizeof(float2)) + rnd256(batch * ng * sizeof(float2)) +
-                          rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + rnd256((size_t)nB * G2 * G2 * sizeof(float2)) +
-                          rnd256((size_t)batch * m * sizeof(int32_t));
-            if (h2) need += hgemm_pack_bytes(M, G2, nB) + rnd256(batch * sizeof(uint32_t));
-            if (memspace == JSTSP_HOST)
-                need += rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2)) + rnd256(batch * nm * sizeof(float2));
-            JSTSP_TRY(ctx->arena.reserve(need));
-            ctx->arena.reset();
-            const float2 *Af, *Bf, *y;
-            JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Af_), szA, memspace, &Af));
-            JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Bf_), szB, memspace, &Bf));
-            JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(y_), batch * nm, memspace, &y));
-            Arena &ar = ctx->arena;
-            float2 *c0 = ar.get<float2>(batch * g), *cw = ar.get<float2>(batch * g), *xh = ar.get<float2>(batch * g);
-            float2 *Tc = ar.get<float2>(batch * ng);
-            float2 *GA = ar.get<float2>((size_t)nA * Gr * Gr), *GB = ar.get<float2>((size_t)nB * G2 * G2);
-            int32_t *io = ar.get<int32_t>((size_t)batch * m);
-            JSTSP_REQUIRE(c0 && cw && xh && Tc && GA && GB && io, JSTSP_E_NOMEM, "omp_kron: workspace exhausted");
+            const int nA = strideA ? batch : 1;
+            const size_t nm = (size_t)meas, g = (size_t)size_d;
+            float2 *c0, *cw, *GA, *GB;
+            JSTSP_TRY(arena_open(ctx, "omp_kron", [&](Arena &a) {
+                inputs(a);
+                c0 = a.get<float2>(batch * g); cw = a.get<float2>(batch * g); xh = a.get<float2>(batch * g);
+                Tc = a.get<float2>(batch * ng);
+                GA = a.get<float2>((size_t)nA * Gr * Gr); GB = a.get<float2>((size_t)nB * G2 * G2);
+                io = a.get<int32_t>((size_t)batch * m);
+                packed(a);
+            }));
             const Mat Am{Af, strideA, N}, Bm{Bf, strideB, G2}, Ym{y, (long long)nm, N};
             JSTSP_TRY(gemm(ctx, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr));                 // G_A = Af^H Af
             if (h2) {
-                HPack pk;
-                JSTSP_TRY(hgemm_pack(ctx, pk, ar, Bf, strideB, G2, 1, 1, M, G2, nB, (long long)G2 * M));
+                JSTSP_TRY(hgemm_pack_fill(ctx, pk, Bf, strideB, G2, 1, 1, M, G2, (long long)G2 * M));
                 HGemmDesc hb{Bf, strideB, G2, pk.bmax, pk.data, pk.st, pk.bmax, 1, pk.KS, pk.JT, GB,
                              (long long)G2 * G2, G2, G2, G2, M, nB, EPI_NONE, nullptr, nullptr, nullptr};
                 JSTSP_TRY(launch_hgemm(ctx, hb, nullptr));                                                      // G_B = Bf Bf^H
-                uint32_t *ymax = ar.get<uint32_t>(batch);
-                JSTSP_REQUIRE(ymax, JSTSP_E_NOMEM, "omp_kron: workspace exhausted");
-                JSTSP_TRY(hgemm_absmax(ctx, y, (long long)nm, (long long)nm, batch, ymax));
-                HGemmDesc hc{y, (long long)nm, N, ymax, pk.data, strideB ? pk.st : 0, pk.bmax, strideB ? 1 : 0, pk.KS,
+                JSTSP_TRY(hgemm_absmax(ctx, y, (long long)nm, (long long)nm, batch, rmax));
+                HGemmDesc hc{y, (long long)nm, N, rmax, pk.data, strideB ? pk.st : 0, pk.bmax, strideB ? 1 : 0, pk.KS,
                              pk.JT, Tc, (long long)ng, N, N, G2, M, batch, EPI_NONE, nullptr, nullptr, nullptr};
                 JSTSP_TRY(launch_hgemm(ctx, hc, "correlate"));                                                  // Y Bf^H
             } else {
@@ -1031,41 +1024,22 @@ int jstsp_omp_kron_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, 
             return 0;
         }
     }
-    const int meas = N * M, size_d = Gr * G2;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)N * Gr : (size_t)N * Gr;
-    const size_t szB = strideB ? (size_t)strideB * (batch - 1) + (size_t)G2 * M : (size_t)G2 * M;
-    const size_t ng = (size_t)N * G2;
-    size_t need = omp_bytes(meas, m, batch) + 2 * rnd256((size_t)batch * size_d * sizeof(float2)) +
-                  rnd256((size_t)batch * ng * sizeof(float2)) + rnd256((size_t)batch * m * sizeof(int32_t));
-    const bool h2 = use_hgemm(N, G2, M);         // split-f16 correlation, dictionary factor packed once (hgemm.hip)
-    const int nB = strideB ? batch : 1;
-    if (h2) need += hgemm_pack_bytes(M, G2, nB) + rnd256(batch * sizeof(uint32_t));
-    if (memspace == JSTSP_HOST)
-        need += rnd256(szA * sizeof(float2)) + rnd256(szB * sizeof(float2)) + rnd256((size_t)batch * meas * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
-    const float2 *Af, *Bf, *y;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Af_), szA, memspace, &Af));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Bf_), szB, memspace, &Bf));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(y_), (size_t)batch * meas, memspace, &y));
     OmpState s;
-    JSTSP_TRY(omp_alloc(ctx->arena, s, meas, m, batch));
-    float2 *corr = ctx->arena.get<float2>((size_t)batch * size_d);
-    float2 *xh = ctx->arena.get<float2>((size_t)batch * size_d);
-    float2 *Tc = ctx->arena.get<float2>((size_t)batch * ng);
-    int32_t *io = ctx->arena.get<int32_t>((size_t)batch * m);
-    JSTSP_REQUIRE(corr && xh && Tc && io, JSTSP_E_NOMEM, "omp_kron: workspace exhausted");
+    float2 *corr;
+    JSTSP_TRY(arena_open(ctx, "omp_kron", [&](Arena &a) {
+        inputs(a);
+        omp_alloc(a, s, meas, m, batch);
+        corr = a.get<float2>((size_t)batch * size_d);
+        xh = a.get<float2>((size_t)batch * size_d);
+        Tc = a.get<float2>((size_t)batch * ng);
+        io = a.get<int32_t>((size_t)batch * m);
+        packed(a);
+    }));
     hipStream_t st = ctx->stream;
     JSTSP_HIP(hipMemcpyAsync(s.r, y, (size_t)batch * meas * sizeof(float2), hipMemcpyDeviceToDevice, st));
     JSTSP_HIP(hipMemsetAsync(s.nu, 0, batch * sizeof(int), st));
     JSTSP_HIP(hipMemsetAsync(s.Rm, 0, (size_t)batch * m * m * sizeof(float2), st));
-    HPack pk;
-    uint32_t *rmax = nullptr;
-    if (h2) {
-        JSTSP_TRY(hgemm_pack(ctx, pk, ctx->arena, Bf, strideB, G2, 1, 1, M, G2, nB, (long long)G2 * M));
-        rmax = ctx->arena.get<uint32_t>(batch);
-        JSTSP_REQUIRE(rmax, JSTSP_E_NOMEM, "omp_kron: workspace exhausted");
-    }
+    if (h2) JSTSP_TRY(hgemm_pack_fill(ctx, pk, Bf, strideB, G2, 1, 1, M, G2, (long long)G2 * M));
     bool reg_step = batch <= 64 && meas <= 2048;
     int qc = reg_step ? omp_reg_qcols(meas, m) : 0;
     if (qc < 0) { reg_step = false; qc = 0; }

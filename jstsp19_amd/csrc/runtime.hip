@@ -172,20 +172,10 @@ static int pick_nsplit(int n, int kc, int batch)
 
 size_t GramWS::bytes(int rows, int cols, int batch, bool need_q, int force_nsplit)
 {
-    const int n = std::min(rows, cols), kc = std::max(rows, cols);
-    const int ns = force_nsplit > 0 ? force_nsplit : pick_nsplit(n, kc, batch);
-    size_t b = rnd256((size_t)batch * ns * n * n * sizeof(float2));
-    if (!need_q && n <= 128) b += rnd256((size_t)batch * lanczos_ne(n) * sizeof(float2)) + rnd256((size_t)batch * sizeof(int));
-    if (need_q) {
-        b += rnd256((size_t)batch * n * n * sizeof(float2));
-        if (n <= 64) b += rnd256((size_t)batch * eig_fast_ne(n) * eig_fast_ne(n) * sizeof(float2));
-        else b += 2 * rnd256((size_t)batch * n * n * sizeof(float2));       // warm-start basis + transform temporary
-        if (n > 64 && eig_needs_global_v(n)) {
-            const int ne = (n + 1) & ~1;
-            b += rnd256((size_t)batch * ne * ne * sizeof(float2));
-        }
-    }
-    return b;
+    Arena m = Arena::measuring();
+    GramWS w;
+    (void)w.alloc(m, rows, cols, batch, need_q, force_nsplit);
+    return m.peak;
 }
 
 int GramWS::alloc(Arena &a, int rows_, int cols_, int batch_, bool need_q, int force_nsplit)
@@ -195,32 +185,27 @@ int GramWS::alloc(Arena &a, int rows_, int cols_, int batch_, bool need_q, int f
     left = rows <= cols;
     nsplit = force_nsplit > 0 ? force_nsplit : pick_nsplit(n, std::max(rows, cols), batch);
     Gpart = a.get<float2>((size_t)batch * nsplit * n * n);
-    JSTSP_REQUIRE(Gpart, JSTSP_E_NOMEM, "workspace exhausted (Gram partials)");
     Q = nullptr; Vg = nullptr; Uwarm = nullptr; Twarm = nullptr; warm = 0;
     lz = LanczosWarm();
     if (!need_q && n <= 128) {
         lz.ne = lanczos_ne(n);
         lz.x = a.get<float2>((size_t)batch * lz.ne);
         lz.state = a.get<int>((size_t)batch);
-        JSTSP_REQUIRE(lz.x && lz.state, JSTSP_E_NOMEM, "workspace exhausted (Lanczos warm-start vectors)");
     }
     if (need_q) {
         Q = a.get<float2>((size_t)batch * n * n);
-        JSTSP_REQUIRE(Q, JSTSP_E_NOMEM, "workspace exhausted (SVT projector)");
         if (n <= 64) {
             Uwarm = a.get<float2>((size_t)batch * eig_fast_ne(n) * eig_fast_ne(n));
-            JSTSP_REQUIRE(Uwarm, JSTSP_E_NOMEM, "workspace exhausted (warm-start basis)");
         } else {
-            Uwarm = a.get<float2>((size_t)batch * n * n);
+            Uwarm = a.get<float2>((size_t)batch * n * n);       // warm-start basis + transform temporary
             Twarm = a.get<float2>((size_t)batch * n * n);
-            JSTSP_REQUIRE(Uwarm && Twarm, JSTSP_E_NOMEM, "workspace exhausted (warm-start basis)");
         }
         if (n > 64 && eig_needs_global_v(n)) {
             const int ne = (n + 1) & ~1;
             Vg = a.get<float2>((size_t)batch * ne * ne);
-            JSTSP_REQUIRE(Vg, JSTSP_E_NOMEM, "workspace exhausted (eigenvectors)");
         }
     }
+    JSTSP_REQUIRE(!a.overrun, JSTSP_E_NOMEM, "workspace exhausted (Gram workspace)");
     return 0;
 }
 

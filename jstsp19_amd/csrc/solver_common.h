@@ -100,8 +100,16 @@ struct StreamScope {
 // lam[t] = sigma_max(Z_t)^2   (lanczos: the per-iteration convergence-error curves; Householder + Sturm otherwise)
 int sigma_max_sq(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, float *lam, bool lanczos = false);
 
-// Ginv[t] = G[t]^-1 for `count` Hermitian PD n x n matrices (hinv.hip); workspace from ctx->arena.
-size_t hinv_bytes(int n, int count);
+// Ginv[t] = G[t]^-1 for `count` Hermitian PD n x n matrices (hinv.hip).  Its temporaries are taken first (take) and used
+// afterwards (the call with a HinvWS); the call without one takes them from ctx->arena itself.  A caller may rewind the arena to
+// where it stood before take() once the inverse has been enqueued.
+struct HinvWS {
+    float2 *T1 = nullptr, *T2 = nullptr, *Vg = nullptr;
+    float *lam = nullptr;
+    void take(Arena &a, int n, int count);
+};
+size_t hinv_bytes(int n, int count);        // what take() takes
+int hermitian_inverse(jstsp_ctx *ctx, int n, int count, const float2 *G, float2 *Ginv, const HinvWS &w);
 int hermitian_inverse(jstsp_ctx *ctx, int n, int count, const float2 *G, float2 *Ginv);
 
 // pinv of small matrices in float64 (pinv.hip): P[t] (cols x rows) = pinv(A[t]) (rows x cols) when the matrix fits in LDS
@@ -229,6 +237,32 @@ template <class T> int stage_out(jstsp_ctx *ctx, T *dst, const T *dev, size_t n,
     return 0;
 }
 inline size_t rnd256(size_t b) { return (b + 255) & ~size_t(255); }
+inline const float2 *as_f2(const jstsp_c32 *p) { return reinterpret_cast<const float2 *>(p); }
+inline float2 *as_f2(jstsp_c32 *p) { return reinterpret_cast<float2 *>(p); }
+
+// Opens the workspace of a call on the context's arena: layout(Arena &) takes every array of the call, staged inputs (Arena::in)
+// included, and nothing else - no HIP call, no launch.  It runs on a measuring arena, the arena is grown to the measured peak,
+// and the same function then hands out the arrays and uploads the inputs of a host call.  There is no second statement of the
+// size; two passes that disagree are an internal error, found here by one comparison instead of a check per array.
+template <class Layout> int arena_open(jstsp_ctx *ctx, const char *nm, Layout &&layout)
+{
+    Arena m = Arena::measuring();
+    layout(m);
+    Arena &a = ctx->arena;
+    JSTSP_TRY(a.reserve(m.peak));
+    a.reset();
+    a.st = ctx->stream;
+    layout(a);
+    JSTSP_REQUIRE(!a.overrun && a.off == m.off && a.peak == m.peak, JSTSP_E_NOMEM,
+                  "%s: internal error: the workspace was measured as %zu bytes (ending at %zu) and laid out as %zu (ending at %zu)%s", nm,
+                  m.peak, m.off, a.peak, a.off, a.overrun ? ", past its end" : "");
+    if (a.err != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);    // (the uploads before it may still read the caller's arrays)
+        set_error("%s: staging an input on the device failed: %s", nm, hipGetErrorString(a.err));
+        return (int)a.err;
+    }
+    return 0;
+}
 
 // Host-side staging of a block-Toeplitz dictionary (hostpack.hip): T = float2 or double2 (narrowed while copying).
 // *gt_out = the block height when the compact route was taken (Bdev then receives the expanded array on ctx->stream), 0 otherwise

@@ -61,40 +61,28 @@ extern "C" int jstsp_sparse_admm_c32(jstsp_ctx *ctx, int Mr, int Mt, int Gr, int
     const float rho = 0.01f, tau_s = 0.0001f;                                 // :12-13
     const int ner = (Mr + 1) & ~1, net = (Mt + 1) & ~1;
 
-    size_t need = (want_ce ? 8 : 7) * rnd256(batch * nm * sizeof(float2)) + 2 * rnd256((size_t)Mr * Mr * sizeof(float2)) +
-                  2 * rnd256((size_t)Mt * Mt * sizeof(float2)) + rnd256(Mr * sizeof(float)) +
-                  rnd256(Mt * sizeof(float)) + rnd256((size_t)ner * ner * sizeof(float2)) +
-                  rnd256((size_t)net * net * sizeof(float2)) + 2 * rnd256(batch * sizeof(float)) +
-                  rnd256((size_t)batch * std::max(Imax, 1) * sizeof(double));
-    if (want_ce) need += GramWS::bytes(Mr, Mt, batch, false);
-    if (memspace == JSTSP_HOST)
-        need += 2 * rnd256(batch * nm * sizeof(float2)) + rnd256((size_t)Mr * Gr * sizeof(float2)) +
-                rnd256((size_t)Mt * Gt * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
-    Arena &a = ctx->arena;
     const float2 *OH, *Dr, *Dt, *Htrue = nullptr;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(OH_), batch * nm, memspace, &OH));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Dr_), (size_t)Mr * Gr, memspace, &Dr));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Dt_), (size_t)Mt * Gt, memspace, &Dt));
-    if (want_ce) JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Htrue_), batch * nm, memspace, &Htrue));
-
-    float2 *R = a.get<float2>(batch * nm), *Z = a.get<float2>(batch * nm), *S = a.get<float2>(batch * nm),
-           *RHS = a.get<float2>(batch * nm), *P = a.get<float2>(batch * nm), *AhOH = a.get<float2>(batch * nm),
-           *Dd = a.get<float2>(batch * nm);
-    float2 *Gr_ = a.get<float2>((size_t)Mr * Mr), *Ur = a.get<float2>((size_t)Mr * Mr);
-    float2 *Gt_ = a.get<float2>((size_t)Mt * Mt), *Ut = a.get<float2>((size_t)Mt * Mt);
-    float *lr = a.get<float>(Mr), *lt = a.get<float>(Mt);
-    float2 *Vgr = a.get<float2>((size_t)ner * ner), *Vgt = a.get<float2>((size_t)net * net);
-    float *num = a.get<float>(batch), *den = a.get<float>(batch);
-    double *ce = a.get<double>((size_t)batch * std::max(Imax, 1));
-    JSTSP_REQUIRE(R && Z && S && RHS && P && AhOH && Dd && Gr_ && Ur && Gt_ && Ut && lr && lt && Vgr && Vgt &&
-                      num && den && ce,
-                  JSTSP_E_NOMEM, "sparse_admm: workspace exhausted");
-    float2 *P2 = want_ce ? a.get<float2>(batch * nm) : nullptr;        // the error chain's own temporary (it runs beside the solve)
-    JSTSP_REQUIRE(!want_ce || P2, JSTSP_E_NOMEM, "sparse_admm: workspace exhausted");
+    float2 *R, *Z, *S, *RHS, *P, *AhOH, *Dd, *Gr_, *Ur, *Gt_, *Ut, *Vgr, *Vgt, *P2;
+    float *lr, *lt, *num, *den;
+    double *ce;
     GramWS wn;
-    if (want_ce) JSTSP_TRY(wn.alloc(a, Mr, Mt, batch, false));
+    JSTSP_TRY(arena_open(ctx, "sparse_admm", [&](Arena &a) {
+        OH = a.in(as_f2(OH_), batch * nm, memspace);
+        Dr = a.in(as_f2(Dr_), (size_t)Mr * Gr, memspace);
+        Dt = a.in(as_f2(Dt_), (size_t)Mt * Gt, memspace);
+        if (want_ce) Htrue = a.in(as_f2(Htrue_), batch * nm, memspace);
+        R = a.get<float2>(batch * nm); Z = a.get<float2>(batch * nm); S = a.get<float2>(batch * nm);
+        RHS = a.get<float2>(batch * nm); P = a.get<float2>(batch * nm); AhOH = a.get<float2>(batch * nm);
+        Dd = a.get<float2>(batch * nm);
+        Gr_ = a.get<float2>((size_t)Mr * Mr); Ur = a.get<float2>((size_t)Mr * Mr);
+        Gt_ = a.get<float2>((size_t)Mt * Mt); Ut = a.get<float2>((size_t)Mt * Mt);
+        lr = a.get<float>(Mr); lt = a.get<float>(Mt);
+        Vgr = a.get<float2>((size_t)ner * ner); Vgt = a.get<float2>((size_t)net * net);
+        num = a.get<float>(batch); den = a.get<float>(batch);
+        ce = a.get<double>((size_t)batch * std::max(Imax, 1));
+        P2 = want_ce ? a.get<float2>(batch * nm) : nullptr;         // the error chain's own temporary (it runs beside the solve)
+        if (want_ce) (void)wn.alloc(a, Mr, Mt, batch, false);
+    }));
     hipStream_t st = ctx->stream;
     const long long snm = (long long)nm, tot = (long long)batch * nm;
 

@@ -23,32 +23,41 @@ namespace jstsp {
 
 static inline dim3 gsz(long long n) { return dim3((unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096))); }
 
-static int vamp_run(jstsp_ctx *ctx, int Na, int Gr, int G2, int batch, const float2 *Y, const float2 *Af,
+// the arrays of vamp_run
+struct VampWS {
+    float2 *r1, *x1, *r2, *x2, *u3, *p1, *p2, *z2, *z2o, *Ar2, *E, *T1, *T2, *tq, *tdq, *AAh, *Ua, *Ub, *Vga, *Vgb;
+    float *q, *dq, *lamA, *lamB;
+    VampScal *sc;
+    void take(Arena &a, int Na, int Gr, int G2, int batch, int nA, int nG)
+    {
+        const size_t bN = (size_t)batch * Gr * G2, bM = (size_t)batch * Na * G2;
+        r1 = a.get<float2>(bN); x1 = a.get<float2>(bN); r2 = a.get<float2>(bN); x2 = a.get<float2>(bN); u3 = a.get<float2>(bN);
+        p1 = a.get<float2>(bM); p2 = a.get<float2>(bM); z2 = a.get<float2>(bM); z2o = a.get<float2>(bM); Ar2 = a.get<float2>(bM);
+        E = a.get<float2>(bM); T1 = a.get<float2>(bM); T2 = a.get<float2>(bM); tq = a.get<float2>(bM); tdq = a.get<float2>(bM);
+        q = a.get<float>(bM); dq = a.get<float>(bM);
+        AAh = a.get<float2>((size_t)nA * Na * Na); Ua = a.get<float2>((size_t)nA * Na * Na);
+        Ub = a.get<float2>((size_t)nG * G2 * G2);
+        lamA = a.get<float>((size_t)nA * Na); lamB = a.get<float>((size_t)nG * G2);
+        const int Da = std::min(Na, Gr), nea = (Da + 1) & ~1, neb = (G2 + 1) & ~1;     // (Da: the order of the decomposition)
+        // (orders above 128 go to the block Jacobi of eig_large.hip, which brings its own stream-ordered temporaries)
+        Vga = a.get<float2>(Da <= 128 ? (size_t)nA * nea * nea : 16); Vgb = a.get<float2>(G2 <= 128 ? (size_t)nG * neb * neb : 16);
+        sc = a.get<VampScal>(batch);
+    }
+};
+
+static int vamp_run(jstsp_ctx *ctx, const VampWS &w, int Na, int Gr, int G2, int batch, const float2 *Y, const float2 *Af,
                     long long sA, const float2 *Gb, long long sG, double sigma, double Lnz, int nit, double damp,
                     float2 *Xout)
 {
-    Arena &a = ctx->arena;
     const int Nc = Gr * G2, Mc = Na * G2;
     const bool tall = Na > Gr;                     // M > N: VampGlmEst.m:407-411 with V, d from eig(A'A) (:196-218)
     const int Da = tall ? Gr : Na, Dc = tall ? Nc : Mc;
     const int nA = sA ? batch : 1, nG = sG ? batch : 1;
     const size_t bN = (size_t)batch * Nc, bM = (size_t)batch * Mc;
-    float2 *r1 = a.get<float2>(bN), *x1 = a.get<float2>(bN), *r2 = a.get<float2>(bN), *x2 = a.get<float2>(bN),
-           *u3 = a.get<float2>(bN);
-    float2 *p1 = a.get<float2>(bM), *p2 = a.get<float2>(bM), *z2 = a.get<float2>(bM), *z2o = a.get<float2>(bM),
-           *Ar2 = a.get<float2>(bM), *E = a.get<float2>(bM), *T1 = a.get<float2>(bM), *T2 = a.get<float2>(bM),
-           *tq = a.get<float2>(bM), *tdq = a.get<float2>(bM);
-    float *q = a.get<float>(bM), *dq = a.get<float>(bM);
-    float2 *AAh = a.get<float2>((size_t)nA * Na * Na), *Ua = a.get<float2>((size_t)nA * Na * Na);
-    float2 *Ub = a.get<float2>((size_t)nG * G2 * G2);
-    float *lamA = a.get<float>((size_t)nA * Na), *lamB = a.get<float>((size_t)nG * G2);
-    const int nea = (Da + 1) & ~1, neb = (G2 + 1) & ~1;     // order of the decomposition (Da), as vamp_bytes() budgets it
-    // (orders above 128 go to the block Jacobi of eig_large.hip, which brings its own stream-ordered temporaries)
-    float2 *Vga = a.get<float2>(Da <= 128 ? (size_t)nA * nea * nea : 16), *Vgb = a.get<float2>(G2 <= 128 ? (size_t)nG * neb * neb : 16);
-    VampScal *sc = a.get<VampScal>(batch);
-    JSTSP_REQUIRE(r1 && x1 && r2 && x2 && u3 && p1 && p2 && z2 && z2o && Ar2 && E && T1 && T2 && tq && tdq && q && dq &&
-                      AAh && Ua && Ub && lamA && lamB && Vga && Vgb && sc,
-                  JSTSP_E_NOMEM, "vamp: workspace exhausted");
+    float2 *r1 = w.r1, *x1 = w.x1, *r2 = w.r2, *x2 = w.x2, *u3 = w.u3, *p1 = w.p1, *p2 = w.p2, *z2 = w.z2, *z2o = w.z2o, *Ar2 = w.Ar2,
+           *E = w.E, *T1 = w.T1, *T2 = w.T2, *tq = w.tq, *tdq = w.tdq, *AAh = w.AAh, *Ua = w.Ua, *Ub = w.Ub, *Vga = w.Vga, *Vgb = w.Vgb;
+    float *q = w.q, *dq = w.dq, *lamA = w.lamA, *lamB = w.lamB;
+    VampScal *sc = w.sc;
     hipStream_t st = ctx->stream;
     // ---- decompositions (the `svd(B)` of vamp.m:32 in factored complex form)
     const Mat Am{Af, sA, Na}, Gm{Gb, sG, G2};
@@ -110,17 +119,6 @@ static int vamp_run(jstsp_ctx *ctx, int Na, int Gr, int G2, int batch, const flo
     return 0;
 }
 
-static size_t vamp_bytes(int Na, int Gr, int G2, int batch, int nA, int nG)
-{
-    const size_t bN = (size_t)batch * Gr * G2, bM = (size_t)batch * Na * G2;
-    const int Da = std::min(Na, Gr), nea = (Da + 1) & ~1, neb = (G2 + 1) & ~1;
-    return 6 * rnd256(bN * sizeof(float2)) + 10 * rnd256(bM * sizeof(float2)) + 2 * rnd256(bM * sizeof(float)) +
-           2 * rnd256((size_t)nA * Na * Na * sizeof(float2)) + rnd256((size_t)nG * G2 * G2 * sizeof(float2)) +
-           rnd256((size_t)nA * Na * sizeof(float)) + rnd256((size_t)nG * G2 * sizeof(float)) +
-           rnd256((Da <= 128 ? (size_t)nA * nea * nea : 16) * sizeof(float2)) + rnd256((G2 <= 128 ? (size_t)nG * neb * neb : 16) * sizeof(float2)) +
-           rnd256(batch * sizeof(VampScal)) + 4096;
-}
-
 }  // namespace jstsp
 
 using namespace jstsp;
@@ -143,20 +141,18 @@ int jstsp_vamp_kron_c32(jstsp_ctx *ctx, int Na, int Gr, int G2, int batch, const
     JSTSP_REQUIRE(sigma > 0 && Lnz > 0 && Lnz < 2.0 * Gr * G2, JSTSP_E_ARG, "vamp: need sigma > 0 and 0 < L < nx");
     JSTSP_ENTER(ctx);
     const int nA = strideA ? batch : 1, nG = strideG ? batch : 1;
-    const size_t szA = strideA ? (size_t)strideA * (batch - 1) + (size_t)Na * Gr : (size_t)Na * Gr;
-    const size_t szG = strideG ? (size_t)strideG * (batch - 1) + (size_t)G2 * G2 : (size_t)G2 * G2;
     const size_t bN = (size_t)batch * Gr * G2, bM = (size_t)batch * Na * G2;
-    size_t need = vamp_bytes(Na, Gr, G2, batch, nA, nG) + rnd256(bN * sizeof(float2));
-    if (memspace == JSTSP_HOST) need += rnd256(bM * sizeof(float2)) + rnd256(szA * sizeof(float2)) + rnd256(szG * sizeof(float2));
-    JSTSP_TRY(ctx->arena.reserve(need));
-    ctx->arena.reset();
     const float2 *Y, *Af, *Gb;
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Y_), bM, memspace, &Y));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Af_), szA, memspace, &Af));
-    JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(Gb_), szG, memspace, &Gb));
-    float2 *X = ctx->arena.get<float2>(bN);
-    JSTSP_REQUIRE(X, JSTSP_E_NOMEM, "vamp: workspace exhausted");
-    JSTSP_TRY(vamp_run(ctx, Na, Gr, G2, batch, Y, Af, strideA, Gb, strideG, sigma, Lnz, nit, 0.85, X));   // damp: vamp.m:11
+    float2 *X;
+    VampWS w;
+    JSTSP_TRY(arena_open(ctx, "vamp", [&](Arena &a) {
+        Y = a.in(as_f2(Y_), bM, memspace);
+        Af = a.in(as_f2(Af_), dict_elems(strideA, (size_t)Na * Gr, batch), memspace);
+        Gb = a.in(as_f2(Gb_), dict_elems(strideG, (size_t)G2 * G2, batch), memspace);
+        X = a.get<float2>(bN);
+        w.take(a, Na, Gr, G2, batch, nA, nG);
+    }));
+    JSTSP_TRY(vamp_run(ctx, w, Na, Gr, G2, batch, Y, Af, strideA, Gb, strideG, sigma, Lnz, nit, 0.85, X));   // damp: vamp.m:11
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(X_out), X, bN, memspace));
     if (memspace == JSTSP_HOST) JSTSP_HIP(hipStreamSynchronize(ctx->stream));
     return 0;

@@ -117,9 +117,6 @@ __device__ __forceinline__ double cgs2_append(double2 *q, const double2 *Q, int 
 }
 
 // ---- workspace: one stream-ordered slab, bump allocation -----------------------------------------------------------------------
-// elements of a dictionary operand: `one` per problem, `stride` elements apart (0: one operand shared by the batch)
-inline size_t dict_elems(long long stride, size_t one, int batch) { return stride ? (size_t)stride * (batch - 1) + one : one; }
-
 // An entry point states its arrays once, as a function of (Slab &, batch).  On a slab without memory (before reserve()) that
 // function only measures: get() advances the offset and returns nullptr, in() uploads nothing.  After reserve() the same calls
 // hand out the arrays, 256-byte aligned, and in() uploads in the order of the calls.  ws64_open() runs the two passes.
