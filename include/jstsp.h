@@ -713,6 +713,16 @@ int jstsp_support_order_wide_f64(jstsp_ctx *ctx, int Gr, int Gt, int L, int batc
  *  510; values scaled by 2^+-500; an all-zero trial; no batch or memspace dependence; the refusals. */
 #define JSTSP_SUPPORT_TOP_MAX 4096
 int jstsp_support_top_f64(jstsp_ctx *ctx, int Gr, int G2, int batch, const double *V, int count, int32_t *indx_top, int memspace);
+/* The same for an fp32 S (Gr x G2 x batch jstsp_c32): the first `count` entries of jstsp_support_order_c32 of each trial, bit for
+ * bit.  One template body with the float64 kernel; the key is the 32-bit support_key(float2) of csrc/support_key.h - the trial
+ * builder's indx_S and jstsp_support_order_c32's - so the radix select takes four passes, and the static LDS is 32 KiB (4096 keys
+ * and 4096 indices of 4 bytes) plus the histogram.  count, the refusals and their messages, the staging of a JSTSP_HOST call and
+ * the second writer (rank) are those of jstsp_support_top_f64; jstsp_proposed_refresh_c32 runs the kernel inside its loop.
+ *  Asserted (tests/test_gpu_support_top32.py), exact against jstsp_support_order_c32(S)(1:count, :) and a stable host argsort of
+ *  the fp32 key: g = 12, 1000, 1025, 8192, 32768 at count 1, 40, g (g <= 4096) and 4096; duplicate magnitudes across the
+ *  threshold, a zero tie class larger than count, NaN entries, a strict part of 4095 entries; no batch or memspace dependence;
+ *  the refusals. */
+int jstsp_support_top_c32(jstsp_ctx *ctx, int Gr, int G2, int batch, const jstsp_c32 *S, int count, int32_t *indx_top, int memspace);
 
 /* ---- achievable spectral efficiency of the combiners (plot_capacity.m, plot_ee.m; csrc/capacity.hip) ----------------------
  * createBeamformer(N, kind) (createBeamformer.m:5-32) for kind = JSTSP_BF_ZC ('ZC'), JSTSP_BF_DFT ('fft' = 'ps'),
@@ -1243,6 +1253,49 @@ int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
                                const jstsp_c64 *A, long long strideA,
                                const jstsp_c64 *B, long long strideB,
                                int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                               const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                               jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                               int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out,
+                               int32_t *indx_out, int memspace);
+
+/* ---- the fp32 ADMM with its support refreshed from its own iterate (csrc/proposed.hip) ------------------
+ * jstsp_proposed_resume_c32 with the support policy of jstsp_proposed_refresh_f64 above: the same schedule on the global
+ * iteration index, the same R = min(Gr*G2, JSTSP_SUPPORT_TOP_MAX) and its LIMIT, the same indx_S (n_indx entries per trial, stride
+ * n_indx), the same indx_out (R x batch, written if and only if the call runs a refresh).  What is the fp32 solver's own:
+ *  - type: JSTSP_TYPE_APPROXIMATE only; JSTSP_TYPE_STD is refused with JSTSP_E_UNSUPPORTED.
+ *  - a refresh iteration, all on the context's main stream in front of the A S product: the gradient step without a mask, the
+ *    selection kernel of jstsp_support_top_c32 on the new v (rank for every entry; the list when indx_out is wanted), and
+ *    S = soft(v) .* [rank < cnt(i)] rewritten from the stored v by the step's own expression - the bits a masked step would have
+ *    written.  v, Y and convergence_error of that iteration do not depend on the mask.  Beside a resident eigen-decomposition (the
+ *    fused pass with convergence_error, Gr*G2 >= 8192) the selection runs as a 512-thread workgroup, as the step does; the lists
+ *    do not depend on the workgroup's size.
+ *  - the key is the fp32 |v|^2 of jstsp_support_order_c32: indx_out == jstsp_support_top_c32(v, R) of the state's v on the bits.
+ *  - one staged solve in either memspace, state_out may be state_in, and a trial flagged by the fused pass is solved again from
+ *    its state_in at it0 under the same policy, as in jstsp_proposed_resume_c32; the indx_out of such a trial comes from the
+ *    re-solve.  As for every split fp32 solve, legs are fp32-equivalent to the uninterrupted call, not bit-identical.
+ *  - JSTSP_E_ARG: refresh_start < 0, refresh_period < 0, n_indx outside 1..Gr*G2 with indx_S, n_indx != 0 without it, it0 < 0 or
+ *    it0 != 0 without state_in.  Every message starts with "proposed_algorithm refresh: "; nothing is written on a refusal.
+ *  - without a refresh in the call the launches, allocations apart from the rank array, and bits are those of
+ *    jstsp_proposed_resume_c32.  No other entry passes a policy: their launches and bits are unchanged.
+ * jstsp_proposed_refresh_c64 is the entry at the reference's element type, narrowed and widened as jstsp_proposed_resume_c64.
+ * Asserted (tests/test_gpu_refresh32.py): on the window kernel, the general fused pass, JSTSP_FUSED=0 and an unfused shape - no
+ * refresh: the bits of the resumed entries; one refresh at the call's last iteration: v and Y of the plain call, indx_out ==
+ * jstsp_support_top_c32(v, R), S the plain S on the head and zero elsewhere, bit for bit; legs against the whole call and
+ * tests/refresh_ref.py within the fp32 solver's tolerances; the re-solve; NaN isolation; memspaces; the refusals; the _c64 form. */
+int jstsp_proposed_refresh_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                               const jstsp_c32 *subY, const float *Omega,
+                               const jstsp_c32 *A, long long strideA,
+                               const jstsp_c32 *B, long long strideB,
+                               int Imax, const double *tau_Y, const double *tau_S, const double *rho, int type,
+                               const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                               jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out,
+                               int it0, const jstsp_c32 *state_in, jstsp_c32 *state_out,
+                               int32_t *indx_out, int memspace);
+int jstsp_proposed_refresh_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                               const jstsp_c64 *subY, const double *Omega,
+                               const jstsp_c64 *A, long long strideA,
+                               const jstsp_c64 *B, long long strideB,
+                               int Imax, const double *tau_Y, const double *tau_S, const double *rho, int type,
                                const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
                                jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
                                int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out,

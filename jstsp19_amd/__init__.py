@@ -15,6 +15,7 @@ from .solvers import (OMP, sparse_sca_estim, cawgn_estim_out, gradient_head, ls_
                       svd_f64, lowrank_f64, svd_tall_f64, lowrank_tall_f64, nmse_spectral_f64, rate_f64,
                       admm_state_elems, proposed_algorithm_resume_f64, proposed_algorithm_std_resume_f64,
                       proposed_algorithm_resume, proposed_algorithm_angles_resume, support_order, support_order_f64,
-                      support_order_wide, support_order_wide_f64, support_top_f64, proposed_algorithm_refresh_f64)
+                      support_order_wide, support_order_wide_f64, support_top_f64, proposed_algorithm_refresh_f64,
+                      support_top, proposed_algorithm_refresh)
 
 __version__ = "0.1.0"

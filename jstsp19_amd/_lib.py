@@ -165,6 +165,13 @@ SIGNATURES["jstsp_support_top_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_
 SIGNATURES["jstsp_proposed_refresh_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
                                                     c_void_p, c_ll, c_int, c_dp, c_dp, c_dp, c_void_p, c_int, c_int, c_int,
                                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int])
+# the same in fp32 (csrc/support_top.hip, csrc/proposed.hip, csrc/c64.hip): the float64 lists, with `type` after rho as in
+# jstsp_proposed_resume_c32 ('std' is refused)
+SIGNATURES["jstsp_support_top_c32"] = SIGNATURES["jstsp_support_top_f64"]
+for _n in ("jstsp_proposed_refresh_c32", "jstsp_proposed_refresh_c64"):
+    SIGNATURES[_n] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
+                              c_void_p, c_ll, c_int, c_dp, c_dp, c_dp, c_int, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int])
 
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes

@@ -2,6 +2,7 @@
 // (proposed_algorithm.m:35-69, proposed_algorithm_angles.m:36,68).  All HBM-bound: each
 // kernel makes one pass over its operands with 16-byte (two complex) accesses per lane.
 #include "common.h"
+#include "support_top.h"
 #include <algorithm>
 
 namespace jstsp {
@@ -277,12 +278,12 @@ __global__ void rank_init_kernel(long long n, int32_t *rank)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) rank[i] = 0x7fffffff;
 }
-__global__ void rank_scatter_kernel(int g, const int32_t *indx, int32_t *rank)
+__global__ void rank_scatter_kernel(int g, const int32_t *indx, int n, int32_t *rank)
 {
     const int t = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < g) {
-        const int pos = indx[(long long)t * g + p] - 1;
+    if (p < n) {
+        const int pos = indx[(long long)t * n + p] - 1;
         if (pos >= 0 && pos < g) atomicMin(&rank[(long long)t * g + pos], p);
     }
 }
@@ -366,13 +367,24 @@ int launch_inv_d(jstsp_ctx *ctx, long long nm, int batch, const float *Omega, fl
     JSTSP_HIP(hipGetLastError());
     return 0;
 }
-int launch_rank_from_index(jstsp_ctx *ctx, int g, int batch, const int32_t *indx, int32_t *rank)
+int launch_rank_from_index(jstsp_ctx *ctx, int g, int batch, const int32_t *indx, int n, int32_t *rank)
 {
-    const long long n = (long long)g * batch;
-    hipLaunchKernelGGL(rank_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
+    const long long total = (long long)g * batch;
+    hipLaunchKernelGGL(rank_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, total,
                        rank);
-    hipLaunchKernelGGL(rank_scatter_kernel, dim3((g + 255) / 256, batch), dim3(256), 0, ctx->stream, g,
-                       indx, rank);
+    hipLaunchKernelGGL(rank_scatter_kernel, dim3((n + 255) / 256, batch), dim3(256), 0, ctx->stream, g,
+                       indx, n, rank);
+    JSTSP_HIP(hipGetLastError());
+    return 0;
+}
+int launch_support_top(jstsp_ctx *ctx, int g, int batch, int count, const float2 *V, int32_t *list, int32_t *rank, int waves8)
+{
+    // waves8: as launch_step_v - the refresh runs between the step and the A S product, where on the svt_split path an
+    // eigen-decomposition is resident on the side stream (the lists do not depend on the workgroup's size)
+    if (g >= 8192 && waves8)
+        hipLaunchKernelGGL((support_top_kernel<float2, 512>), dim3(batch), dim3(512), 0, ctx->stream, g, count, V, list, rank);
+    else
+        hipLaunchKernelGGL((support_top_kernel<float2, ST_THREADS>), dim3(batch), dim3(ST_THREADS), 0, ctx->stream, g, count, V, list, rank);
     JSTSP_HIP(hipGetLastError());
     return 0;
 }

@@ -439,7 +439,11 @@ int launch_soft(jstsp_ctx *ctx, int g, int batch, const float2 *V, float2 *S, co
                 int cnt, const TrialParams *prm);
 int launch_inv_d(jstsp_ctx *ctx, long long nm, int batch, const float *Omega, float scale2rho,
                  const TrialParams *prm, float *invD);
-int launch_rank_from_index(jstsp_ctx *ctx, int g, int batch, const int32_t *indx, int32_t *rank);
+// rank[pos] = first position of linear index pos + 1 among the n entries per trial of indx (pitch n; 0x7fffffff: not listed)
+int launch_rank_from_index(jstsp_ctx *ctx, int g, int batch, const int32_t *indx, int n, int32_t *rank);
+// the selection kernel of support_top.h on the fp32 v: rank (and list, 1-based, `count` per trial; may be NULL) of the top `count`
+// entries of each trial; waves8 as launch_step_v's (a 512-thread workgroup beside a resident eigen-decomposition)
+int launch_support_top(jstsp_ctx *ctx, int g, int batch, int count, const float2 *V, int32_t *list, int32_t *rank, int waves8);
 int launch_eye_minus(jstsp_ctx *ctx, int n, int count, const float2 *Q, float2 *P);
 int launch_ce_ratio(jstsp_ctx *ctx, int batch, const float *lamV1, const float *lamV2,
                     const float *lamX, double *ce, int Imax, int it);

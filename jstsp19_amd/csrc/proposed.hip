@@ -69,7 +69,7 @@ static size_t proposed_bytes(const AdmmProblem &p, bool want_fused, int fparts, 
     b += 2 * rnd256(batch * ng * sizeof(float2));
     b += rnd256((size_t)nA * Gr * Gr * sizeof(float2)) + rnd256((size_t)nB * G2 * G2 * sizeof(float2));
     b += rnd256(batch * sizeof(TrialParams));
-    if (angles) b += rnd256(batch * g * sizeof(int32_t));
+    if (angles || p.policy) b += rnd256(batch * g * sizeof(int32_t));      // the rank: of indx_S, then of a policy's refreshes
     b += rnd256((size_t)batch * 3 * Imax * sizeof(double));
     b += rnd256(3 * (size_t)batch * sizeof(float));
     const int ns3 = gram3_nsplit(N, M, G2, want_ce);
@@ -93,7 +93,8 @@ static size_t proposed_bytes(const AdmmProblem &p, bool want_fused, int fparts, 
     if (p.memspace == JSTSP_HOST) {      // the staged inputs, the compacted dictionary, the staged states of a resumed call
         b += rnd256(batch * nm * sizeof(float2)) + rnd256(batch * nm * sizeof(float)) + rnd256(szA * sizeof(float2)) +
              rnd256(szB * sizeof(float2));
-        if (angles) b += rnd256(batch * g * sizeof(int32_t));
+        if (angles) b += rnd256(batch * p.listed() * sizeof(int32_t));
+        if (p.policy && p.indx_out) b += rnd256(batch * p.R() * sizeof(int32_t));       // the staged list of the last refresh
         b += rnd256(compact_elems * sizeof(float2));
         b += (p.state_in ? rnd256(batch * ne * sizeof(float2)) : 0) + (p.state_out ? rnd256(batch * ne * sizeof(float2)) : 0);
     }
@@ -121,12 +122,12 @@ static int proposed_alloc(Arena &a, ProposedWS &w, const AdmmProblem &p)
     w.Tc = a.get<float2>(batch * ng); w.W = a.get<float2>(batch * ng);
     w.GA = a.get<float2>((size_t)nA * Gr * Gr); w.GB = a.get<float2>((size_t)nB * G2 * G2);
     w.prm = a.get<TrialParams>(batch);
-    w.rank = angles ? a.get<int32_t>(batch * g) : nullptr;
+    w.rank = (angles || p.policy) ? a.get<int32_t>(batch * g) : nullptr;
     w.ce = a.get<double>((size_t)batch * 3 * Imax);
     w.lam = a.get<float>(3 * (size_t)batch);
     JSTSP_REQUIRE(w.X && w.V1 && w.V2 && w.C && w.Xs && w.Y && w.ZK && w.Zb && w.Zb2 && w.invD && w.V && w.RV && w.Res &&
                       w.RRes && w.S && w.P1 && w.Tc && w.W && w.GA && w.GB && w.prm && w.ce && w.lam &&
-                      (!angles || w.rank),
+                      (!(angles || p.policy) || w.rank),
                   JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted");
     const int ns3 = gram3_nsplit(N, M, G2, want_ce);
     JSTSP_TRY(w.gz.alloc(a, N, M, batch, true, ns3));
@@ -239,7 +240,7 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
         B = Bd;
     } else
     JSTSP_TRY(stage_in(ctx, reinterpret_cast<const float2 *>(p.B), szB, memspace, &B));
-    if (angles) JSTSP_TRY(stage_in(ctx, p.indx_S, batch * g, memspace, &indx_S));
+    if (angles) JSTSP_TRY(stage_in(ctx, p.indx_S, batch * p.listed(), memspace, &indx_S));
     if (memspace == JSTSP_DEVICE)
         JSTSP_REQUIRE(((uintptr_t)subY % 16 == 0) && ((uintptr_t)Omega % 8 == 0), JSTSP_E_ARG,
                       "device arrays must be 16-byte aligned");
@@ -268,7 +269,18 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
     JSTSP_TRY(launch_inv_d(ctx, (long long)nm, batch, Omega, 2.f, w.prm, w.invD));
     // (the fused pass forms 1 / (Omega + 2 rho) itself, as two floats, when it can read Omega with its 16-byte loads)
     const bool omega_direct = ((uintptr_t)Omega % 16 == 0) && (nm % 4 == 0);
-    if (angles) JSTSP_TRY(launch_rank_from_index(ctx, (int)g, batch, indx_S, w.rank));
+    if (angles) JSTSP_TRY(launch_rank_from_index(ctx, (int)g, batch, indx_S, (int)p.listed(), w.rank));
+    // A support policy (jstsp_proposed_refresh_c32; every other entry passes none): at a refresh iteration the step runs without a
+    // mask, the selection kernel ranks the top R of the new v and soft_kernel rewrites S from the stored v under that rank -
+    // step_v_kernel's expression on the value it stored, hence the bits a masked step would have written.  The rank stays in force
+    // until the next refresh; before the call's first one the rank of indx_S is, or none.  `top`: the list of the last refresh.
+    const int R = (int)p.R();
+    int32_t *top = nullptr;
+    if (p.policy && p.indx_out && p.runs_refresh()) {
+        top = memspace == JSTSP_DEVICE ? p.indx_out : ctx->arena.get<int32_t>((size_t)batch * R);
+        JSTSP_REQUIRE(top, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (refreshed order)");
+    }
+    bool in_force = angles;                     // a rank masks S
 
     const Mat Am{A, strideA, N}, Bm{B, strideB, G2};
     // a resumed call: the iterate from the caller's state instead of zeros, Xs = A S B from the loaded S.  The loop does not carry
@@ -683,7 +695,8 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
             uint32_t *const nx_zero = (fusedp && tn.grad_fused != 0 && it + 1 < Imax) ? kmax0 + (size_t)((it + 1) & 1) * 8 * (size_t)batch : nullptr;
             if (nx_zero && it > 0 && want_ce) JSTSP_HIP(hipStreamWaitEvent(sm, ev_gv2, 0));
             next_zeroed = nx_zero != nullptr;
-            JSTSP_TRY(launch_step_v(ctx, (int)g, batch, w.Res, w.RRes, w.V, w.S, w.rank, (int)cnt_ll, w.prm, w.ce,
+            const bool fresh = p.refresh_at((long long)it0 + it + 1);
+            JSTSP_TRY(launch_step_v(ctx, (int)g, batch, w.Res, w.RRes, w.V, w.S, in_force && !fresh ? w.rank : nullptr, (int)cnt_ll, w.prm, w.ce,
                                     Imax, it, early_next ? nullptr : w.RV, svt_split, nx_zero));
             if (early_next) {
                 JSTSP_HIP(hipEventRecord(ev_v, sm));
@@ -693,6 +706,13 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
                 JSTSP_TRY(second_factor(w.RV, nullptr, true));
                 JSTSP_HIP(hipEventRecord(ev_rv, s2));
                 rv_early = true;
+            }
+            if (fresh) {
+                // the order of the new v and S again under it, on the main stream in front of the A S product.  The early R v
+                // on s2 (ev_v) only reads V, as these two do; nothing else touches w.rank or w.S before the product.
+                JSTSP_TRY(launch_support_top(ctx, (int)g, batch, R, w.V, top, w.rank, svt_split));
+                JSTSP_TRY(launch_soft(ctx, (int)g, batch, w.V, w.S, w.rank, (int)cnt_ll, w.prm));
+                in_force = true;
             }
         } else {
             //    v = U\(L\k) = pinv(A) K pinv(B)   [ = G_A^-1 (A^H Tc) G_B^-1 on the Gram route: GA / GB hold the inverses ]  (:53)
@@ -782,6 +802,7 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.S_out), w.S, batch * g, memspace));
     JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.Y_out), w.Y, batch * nm, memspace));
     if (want_ce && Imax > 0) JSTSP_TRY(stage_out(ctx, p.ce_out, w.ce, (size_t)batch * 3 * Imax, memspace));
+    if (top && memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, p.indx_out, top, (size_t)batch * R, memspace));
     if (sout) {
         JSTSP_TRY(launch_resume_pack(ctx, (long long)nm, (long long)g, batch, w.X, w.V1, w.V2, explicit_c ? w.C : nullptr, w.V, w.S, sout));
         if (memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, reinterpret_cast<float2 *>(p.state_out), sout, batch * ne, memspace));
@@ -888,6 +909,38 @@ extern "C" int jstsp_proposed_algorithm_c32(jstsp_ctx *ctx, int N, int M, int Gr
     return solve_and_recover(ctx, p);       // (the resumed entry below from zero, without a state)
 }
 
+// The body of the resumed entries: one staged solve with its recovery.  state_out == state_in: the re-solve needs the state the
+// call started from, so a copy is taken first.
+static int resumed_solve(jstsp_ctx *ctx, const char *nmf, AdmmProblem &p)
+{
+    const int batch = p.batch, memspace = p.memspace;
+    const jstsp_c32 *state_in = p.state_in;
+    ctx->fused_fallbacks = 0; ctx->last_dict_block = 0;
+    const size_t ne = p.state_elems();
+    jstsp_c32 *keep_dev = nullptr;
+    std::vector<jstsp_c32> keep_host;
+    if (state_in && state_in == p.state_out) {
+        if (memspace == JSTSP_HOST) { keep_host.assign(state_in, state_in + (size_t)batch * ne); p.state_in = keep_host.data(); }
+        else {
+            JSTSP_ENTER(ctx);
+            JSTSP_HIP(hipMallocAsync((void **)&keep_dev, (size_t)batch * ne * sizeof(jstsp_c32), ctx->stream));
+            const hipError_t e = hipMemcpyAsync(keep_dev, state_in, (size_t)batch * ne * sizeof(jstsp_c32), hipMemcpyDeviceToDevice, ctx->stream);
+            if (e != hipSuccess) {
+                (void)hipFreeAsync(keep_dev, ctx->stream);
+                set_error("%s: copying the state failed: %s", nmf, hipGetErrorString(e));
+                return (int)e;
+            }
+            p.state_in = keep_dev;
+        }
+    }
+    const int rc = solve_and_recover(ctx, p);
+    if (keep_dev) {
+        JSTSP_ENTER(ctx);
+        (void)hipFreeAsync(keep_dev, ctx->stream);
+    }
+    return rc;
+}
+
 // ---- resumed from a saved state (include/jstsp.h) ---------------------------------------------------------------------------------
 // Iterations it0 + 1 ... it0 + Imax from state_in.  One staged solve in either memspace (no two-halves host pipeline).  A trial
 // whose k scale overflowed in a pass is solved again from ITS state_in at it0 by the three-kernel iteration; state_in is read
@@ -904,33 +957,41 @@ extern "C" int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, i
     JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int",
                   it0, Imax);
     JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", it0);
-    ctx->fused_fallbacks = 0; ctx->last_dict_block = 0;
     AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
                   it0, state_in, state_out, memspace};
-    const size_t ne = p.state_elems();
-    // state_out == state_in: the re-solve needs the state the call started from
-    jstsp_c32 *keep_dev = nullptr;
-    std::vector<jstsp_c32> keep_host;
-    if (state_in && state_in == state_out) {
-        if (memspace == JSTSP_HOST) { keep_host.assign(state_in, state_in + (size_t)batch * ne); p.state_in = keep_host.data(); }
-        else {
-            JSTSP_ENTER(ctx);
-            JSTSP_HIP(hipMallocAsync((void **)&keep_dev, (size_t)batch * ne * sizeof(jstsp_c32), ctx->stream));
-            const hipError_t e = hipMemcpyAsync(keep_dev, state_in, (size_t)batch * ne * sizeof(jstsp_c32), hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) {
-                (void)hipFreeAsync(keep_dev, ctx->stream);
-                set_error("proposed_algorithm resume: copying the state failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            p.state_in = keep_dev;
-        }
-    }
-    const int rc = solve_and_recover(ctx, p);
-    if (keep_dev) {
-        JSTSP_ENTER(ctx);
-        (void)hipFreeAsync(keep_dev, ctx->stream);
-    }
-    return rc;
+    return resumed_solve(ctx, "proposed_algorithm resume", p);
+}
+
+// ---- resumed, with the support refreshed from the solver's own iterate (include/jstsp.h) -------------------------------------------
+// jstsp_proposed_resume_c32 with a support policy in its problem record (solver_common.h): the schedule, the limit R and indx_out
+// are those of jstsp_proposed_refresh_f64.  'approximate' only ('std' is refused).  One staged solve; a flagged trial is solved again from its
+// state_in at it0 under the same policy, and its indx_out comes from that re-solve (AdmmProblem::sub moves both lists).
+extern "C" int jstsp_proposed_refresh_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
+                                          const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
+                                          const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S, int n_indx,
+                                          int refresh_start, int refresh_period, jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, int it0,
+                                          const jstsp_c32 *state_in, jstsp_c32 *state_out, int32_t *indx_out, int memspace)
+{
+    const char *nmf = "proposed_algorithm refresh";
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: ctx is NULL", nmf);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace %d", nmf, memspace);
+    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
+    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31), JSTSP_E_SHAPE, "%s: Gr * G2 = %lld exceeds 2^31 - 1", nmf, (long long)Gr * G2);
+    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
+    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
+                  "%s: 'std' recomputes v by least squares in every iteration and has no refreshed form: use jstsp_proposed_resume_c32", nmf);
+    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf, it0, Imax);
+    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, it0);
+    JSTSP_REQUIRE(refresh_start >= 0 && refresh_period >= 0, JSTSP_E_ARG, "%s: refresh_start = %d, refresh_period = %d: neither may be negative", nmf,
+                  refresh_start, refresh_period);
+    const long long g = (long long)Gr * G2;
+    JSTSP_REQUIRE(indx_S ? n_indx >= 1 && n_indx <= g : n_indx == 0, JSTSP_E_ARG,
+                  "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
+    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
+                  it0, state_in, state_out, memspace};
+    p.policy = true; p.n_indx = n_indx; p.start = refresh_start; p.period = refresh_period; p.indx_out = indx_out;
+    return resumed_solve(ctx, nmf, p);
 }
 
 // ---- the two-phase form for device arrays (include/jstsp.h) ---------------------------------------------------------------------

@@ -456,7 +456,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S,
                            in_force && !fresh ? f.rank : (const int32_t *)nullptr, f.mask_count(it0 + it), f.want_ce() ? f.ce3 : nullptr);
         if (fresh) {                                                // the order of the new v, and S again under it
-            hipLaunchKernelGGL(support_top_kernel, dim3(batch), dim3(ST_THREADS), 0, st, (int)g1, R, V, top, f.rank);
+            hipLaunchKernelGGL(support_top_kernel<double2>, dim3(batch), dim3(ST_THREADS), 0, st, (int)g1, R, V, top, f.rank);
             hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, f.par, V, S, f.rank,
                                f.mask_count(it0 + it));
             in_force = true;

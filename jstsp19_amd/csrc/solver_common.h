@@ -142,9 +142,24 @@ template <class Cx, class Re> struct AdmmProblemOf {
     Cx *S_out = nullptr, *Y_out = nullptr; double *ce_out = nullptr;
     int it0 = 0; const Cx *state_in = nullptr; Cx *state_out = nullptr;
     int memspace = JSTSP_HOST;
+    // The support policy of jstsp_proposed_refresh_c32 (include/jstsp.h; every other entry passes none): indx_S lists n_indx entries
+    // per trial, the global 1-based iteration i refreshes the rank from the solver's own v when refresh_at(i), and the list of the
+    // call's last refresh goes to indx_out (R() entries per trial; NULL: not wanted).
+    bool policy = false;
+    int n_indx = 0, start = 0, period = 0;
+    int32_t *indx_out = nullptr;
     size_t nm() const { return (size_t)N * M; }
     size_t g() const { return (size_t)Gr * G2; }
     size_t state_elems() const { return 4 * nm() + 2 * g(); }
+    size_t listed() const { return policy ? (size_t)n_indx : g(); }                  // entries per trial of indx_S
+    size_t R() const { return std::min<size_t>(g(), JSTSP_SUPPORT_TOP_MAX); }       // entries of a refreshed order
+    bool refresh_at(long long i) const { return policy && i > start && (period ? (i - start - 1) % period == 0 : i == (long long)start + 1); }
+    bool runs_refresh() const          // a function of it0, Imax, start and period alone
+    {
+        for (int it = 0; it < Imax; ++it)
+            if (refresh_at((long long)it0 + it + 1)) return true;
+        return false;
+    }
     // Trials t0 .. t0 + cnt - 1.  A NULL pointer stays NULL, a zero stride stays the shared dictionary.  No product wraps: the
     // entries have checked every factor (positive shape, 0 <= t0 < batch, strides 0 or at least one dictionary), and each
     // offset lies inside an array of `batch` such slices that the caller holds in memory.
@@ -154,7 +169,8 @@ template <class Cx, class Re> struct AdmmProblemOf {
         AdmmProblemOf s = *this;
         s.batch = cnt;
         s.subY = at(subY, nm()); s.Omega = at(Omega, nm()); s.A = at(A, (size_t)strideA); s.B = at(B, (size_t)strideB);
-        s.tau_Y = at(tau_Y, 1); s.tau_S = at(tau_S, 1); s.rho = at(rho, 1); s.indx_S = at(indx_S, g());
+        s.tau_Y = at(tau_Y, 1); s.tau_S = at(tau_S, 1); s.rho = at(rho, 1); s.indx_S = at(indx_S, listed());
+        s.indx_out = at(indx_out, R());
         s.S_out = at(S_out, g()); s.Y_out = at(Y_out, nm()); s.ce_out = at(ce_out, (size_t)3 * Imax);
         s.state_in = at(state_in, state_elems()); s.state_out = at(state_out, state_elems());
         return s;

@@ -884,7 +884,7 @@ _REFRESH_MODES = ("refresh", "warm_refresh", "pai_prev_refresh")      # float64 
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
                  precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
-                 widen_primary="neighbourhood", refresh=(0, 1)):
+                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -910,6 +910,8 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
       refresh           from zero, no order in force until the first refresh
       warm_refresh      from the previous frame's whole state, no order in force until the first refresh
       pai_prev_refresh  from zero, ``support_order_f64`` of the chain's previous S in force until the first refresh
+    ``refresh_f32=True`` (``precision="f32"`` only) runs these three through the fp32 solver instead, by
+    ``proposed_algorithm_refresh`` with ``support_order`` for the prior; without it ``precision="f32"`` refuses them as before.
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
@@ -952,7 +954,9 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         raise ValueError("refresh must be a pair (start, period), not %r" % (refresh,)) from None
     if r_start < 0 or r_period < 0:
         raise ValueError("refresh must be a pair (start, period) >= 0, not %r" % (refresh,))
-    if precision != "f64" and any(m in _REFRESH_MODES for m in modes):
+    if refresh_f32 and precision != "f32":
+        raise ValueError("refresh_f32 runs the refresh modes on the fp32 solver: precision must be 'f32', not %r" % (precision,))
+    if precision != "f64" and not refresh_f32 and any(m in _REFRESH_MODES for m in modes):
         raise ValueError("the modes %r refresh the support inside the float64 solver: precision must be 'f64'" % (_REFRESH_MODES,))
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -962,6 +966,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     f64 = precision == "f64"
     wide = (lambda x: J.colmajor(x.to(torch.complex128))) if f64 else (lambda x: x)
     solve = J.proposed_algorithm_resume_f64 if f64 else J.proposed_algorithm_resume
+    solve_refresh = J.proposed_algorithm_refresh_f64 if f64 else J.proposed_algorithm_refresh
     score = J.nmse_spectral_f64 if f64 else J.nmse_spectral
     order = J.support_order_f64 if f64 else J.support_order
     order_wide = J.support_order_wide_f64 if f64 else J.support_order_wide
@@ -997,8 +1002,8 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
                 if mode in _REFRESH_MODES:
-                    S, _, _, out, _ = J.proposed_algorithm_refresh_f64(*args, n_it, *prm, start=r_start, period=r_period, want_ce=False,
-                                                                       state=st, return_state=warm, **ix)
+                    S, _, _, out, _ = solve_refresh(*args, n_it, *prm, start=r_start, period=r_period, want_ce=False, state=st,
+                                                    return_state=warm, **ix)
                 else:
                     S, _, _, out = solve(*args, n_it, *prm, want_ce=False, state=st, return_state=warm, **ix)
                 torch.cuda.synchronize(device)
@@ -1030,4 +1035,6 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         res["widen"], res["widen_primary"] = [wr, wt], widen_primary
     if any(m in _REFRESH_MODES for m in modes):
         res["refresh"] = [r_start, r_period]
+        if refresh_f32:
+            res["refresh_f32"] = True
     return res

@@ -35,7 +35,8 @@ __all__ = ["proposed_algorithm", "proposed_algorithm_angles", "svt", "mc_svt", "
            "svd_f64", "lowrank_f64", "svd_tall_f64", "lowrank_tall_f64", "nmse_spectral_f64", "rate_f64",
            "admm_state_elems", "proposed_algorithm_resume_f64", "proposed_algorithm_std_resume_f64",
            "proposed_algorithm_resume", "proposed_algorithm_angles_resume", "support_order", "support_order_f64",
-           "support_order_wide", "support_order_wide_f64", "support_top_f64", "proposed_algorithm_refresh_f64"]
+           "support_order_wide", "support_order_wide_f64", "support_top_f64", "proposed_algorithm_refresh_f64",
+           "support_top", "proposed_algorithm_refresh"]
 
 
 # ----------------------------------------------------------------------------- array plumbing
@@ -1049,6 +1050,59 @@ def _refresh_first(it0, Imax, start, period):
     return first if lo <= first <= hi else None
 
 
+def _refresh_open(cdt, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, start, period, indx_S, want_ce, ctx, state, it0, return_state):
+    """What the two refreshed wrappers do before their library call, for the solver's complex dtype ``cdt``: every ``ValueError`` of
+    the arguments (before any device call), then the context, the outputs, the states and ``order`` - a new (batch, R) array when the
+    call runs a refresh, else ``indx_S`` as given.  Returns ``(q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord)``."""
+    start, period, it0 = int(start), int(period), int(it0)
+    if start < 0 or period < 0:
+        raise ValueError("start and period must be >= 0, not %r and %r" % (start, period))
+    q = _AdmmCall(cdt, subY, Omega, A, B, None, tau_Y, tau_S, rho, Imax)
+    batch, g = q.batch, q.Gr * q.G2
+    R = min(g, _lib.SUPPORT_TOP_MAX)
+    n = 0
+    if indx_S is not None:
+        n = int(indx_S.shape[-1]) if len(indx_S.shape) else 0
+        size = int(indx_S.numel() if _is_torch(indx_S) else np.asarray(indx_S).size)
+        if not 1 <= n <= g or size != batch * n:
+            raise ValueError("indx_S must be (n,) or (batch, n) with 1 <= n <= Gr*G2 = %d and batch = %d, got shape %s"
+                             % (g, batch, tuple(indx_S.shape)))
+        q.ix = _indx_arg(indx_S, batch, n)
+    if it0 < 0 or (state is None and it0 != 0):
+        raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
+    ne = admm_state_elems(q.N, q.M, q.Gr, q.G2)
+    p_in, keep_in = _state_arg(state, batch, ne, q.state_mem, q.state_dev, cdt)
+    q.open(want_ce, ctx)
+    p_out, st_out = _state_out(return_state, batch, ne, q.mem, q.dev, cdt)
+    order, p_ord = indx_S, None
+    if _refresh_first(it0, q.Imax, start, period) is not None:
+        if q.mem == DEVICE:
+            import torch
+            order = torch.empty((batch, R), dtype=torch.int32, device=q.dev)
+            p_ord = order.data_ptr()
+        else:
+            order = np.empty((batch, R), dtype=np.int32)
+            p_ord = order.ctypes.data
+    return q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord
+
+
+def proposed_algorithm_refresh(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, start=0, period=1, indx_S=None, want_ce=True, ctx=None,
+                               state=None, it0=0, return_state=True):
+    """:func:`proposed_algorithm_refresh_f64` on the fp32 solver (include/jstsp.h: jstsp_proposed_refresh_c32):
+    :func:`proposed_algorithm_resume` ('approximate') with its support refreshed from its own iterate inside the loop, by the
+    schedule, ``indx_S`` and limit of the float64 sibling.  Returns ``(S, Y, ce, state, order)``: complex64 arrays as the resumed
+    call's, ``order`` int32 ``(batch, min(Gr*G2, 4096))`` the list of the call's last refresh - :func:`support_top` of that
+    iteration's ``v`` - or, when the call ran no refresh, the caller's ``indx_S`` as it was given.  Legs that pass ``order`` on are
+    fp32-equivalent to the uninterrupted call, not bit-identical, as every split fp32 solve."""
+    q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord = _refresh_open(
+        np.complex64, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, start, period, indx_S, want_ce, ctx, state, it0, return_state)
+    name = "jstsp_proposed_refresh_c32"
+    args = q.c32_args("approximate")         # (... rho, type, indx_S, S, Y, ce)
+    check(getattr(q.ctx._lib, name)(*args[:-3], n, start, period, *args[-3:], it0, p_in, p_out, p_ord, q.mem), name)
+    del keep_in
+    return q.result() + (st_out, order)
+
+
 def proposed_algorithm_refresh_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, start=0, period=1, indx_S=None, want_ce=True, ctx=None,
                                    state=None, it0=0, return_state=True):
     """:func:`proposed_algorithm_resume_f64` (Alg. 2) with its support refreshed from its own iterate inside the loop (include/jstsp.h:
@@ -1062,37 +1116,10 @@ def proposed_algorithm_refresh_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *
     ``order`` as ``indx_S`` with the same ``start`` and ``period`` and its own ``it0`` and returns the bits of the uninterrupted call.
     A refreshed order lists at most 4096 entries, so above ``Gr*G2 = 4096`` the mask stops growing at iteration 818.  A batch whose
     float64 workspace would exceed the library's limit is solved in chunks."""
-    start, period, it0 = int(start), int(period), int(it0)
-    if start < 0 or period < 0:
-        raise ValueError("start and period must be >= 0, not %r and %r" % (start, period))
-    q = _AdmmCall(np.complex128, subY, Omega, A, B, None, tau_Y, tau_S, rho, Imax)
-    N, M, Gr, G2, batch, Imax, sA, sB = q.N, q.M, q.Gr, q.G2, q.batch, q.Imax, q.sA, q.sB
-    g = Gr * G2
-    R = min(g, _lib.SUPPORT_TOP_MAX)
-    n = 0
-    if indx_S is not None:
-        n = int(indx_S.shape[-1]) if len(indx_S.shape) else 0
-        size = int(indx_S.numel() if _is_torch(indx_S) else np.asarray(indx_S).size)
-        if not 1 <= n <= g or size != batch * n:
-            raise ValueError("indx_S must be (n,) or (batch, n) with 1 <= n <= Gr*G2 = %d and batch = %d, got shape %s"
-                             % (g, batch, tuple(indx_S.shape)))
-        q.ix = _indx_arg(indx_S, batch, n)
-    if it0 < 0 or (state is None and it0 != 0):
-        raise ValueError("it0 must be >= 0, and 0 when there is no state to start from")
-    ne = admm_state_elems(N, M, Gr, G2)
-    p_in, keep_in = _state_arg(state, batch, ne, q.state_mem, q.state_dev)
-    q.open(want_ce, ctx)
-    mem = q.mem
-    p_out, st_out = _state_out(return_state, batch, ne, mem, q.dev)
-    order, p_ord = indx_S, None
-    if _refresh_first(it0, Imax, start, period) is not None:
-        if mem == DEVICE:
-            import torch
-            order = torch.empty((batch, R), dtype=torch.int32, device=q.dev)
-            p_ord = order.data_ptr()
-        else:
-            order = np.empty((batch, R), dtype=np.int32)
-            p_ord = order.ctypes.data
+    q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord = _refresh_open(
+        np.complex128, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, start, period, indx_S, want_ce, ctx, state, it0, return_state)
+    N, M, Gr, G2, batch, Imax, sA, sB, mem = q.N, q.M, q.Gr, q.G2, q.batch, q.Imax, q.sA, q.sB, q.mem
+    g, ne, R = Gr * G2, admm_state_elems(N, M, Gr, G2), min(Gr * G2, _lib.SUPPORT_TOP_MAX)
     per = _f64_admm_bytes(N, M, Gr, G2, sA, sB, False, True, True, mem == HOST, True, refresh=True)
     dp = C.POINTER(C.c_double)
     name = "jstsp_proposed_refresh_f64"
@@ -1544,8 +1571,21 @@ def support_top_f64(S, count, *, ctx=None):
     index order, a sort of the selected entries in LDS - which is what :func:`proposed_algorithm_refresh_f64` runs inside its
     loop.  ``S`` as :func:`support_order_f64` takes it; ``1 <= count <= min(Gr*G2, 4096)`` (``JstspError`` code -4 otherwise).
     Returns int32 (batch, count), 1-based column-major linear indices, where ``S`` lives."""
+    return _support_top_call("jstsp_support_top_f64", S, count, np.complex128, ctx)
+
+
+def support_top(S, count, *, ctx=None):
+    """The first ``count`` entries of :func:`support_order` per trial, bit for bit, without sorting the trial
+    (``jstsp_support_top_c32``): :func:`support_top_f64`'s selection kernel on the 32-bit key ``|z|^2`` in fp32, which is what
+    :func:`proposed_algorithm_refresh` runs inside its loop.  ``S`` as :func:`support_order` takes it (complex64);
+    ``1 <= count <= min(Gr*G2, 4096)`` (``JstspError`` code -4 otherwise).  Returns int32 (batch, count), 1-based column-major
+    linear indices, where ``S`` lives."""
+    return _support_top_call("jstsp_support_top_c32", S, count, np.complex64, ctx)
+
+
+def _support_top_call(entry, S, count, np_dtype, ctx):
     count = int(count)
-    a_S = _Arg(S, np.complex128, "S")
+    a_S = _Arg(S, np_dtype, "S")
     c, mem, dev = _ctx_for([a_S], ctx)
     batch, Gr, G2 = a_S.batch, a_S.R, a_S.C
     rows = max(count, 1)
@@ -1556,7 +1596,7 @@ def support_top_f64(S, count, *, ctx=None):
     else:
         out = np.empty((batch, rows), dtype=np.int32)
         optr = out.ctypes.data
-    check(c._lib.jstsp_support_top_f64(c.handle, Gr, G2, batch, a_S.ptr, count, optr, mem), "jstsp_support_top_f64")
+    check(getattr(c._lib, entry)(c.handle, Gr, G2, batch, a_S.ptr, count, optr, mem), entry)
     return out
 
 

@@ -29,7 +29,8 @@ neighbourhood (a strong entry, then its window) or ties (the plain order, its ex
 refresh, warm_refresh and pai_prev_refresh (float64 only) refresh the support from the solver's own iterate
 inside the loop (proposed_algorithm_refresh_f64) - from zero, from the previous frame's state, and from zero with the order of the
 chain's previous estimate in force until the first refresh: --refresh START,PERIOD, a refresh at the iterations i > START with
-(i - START - 1) % PERIOD == 0, PERIOD 0 for the one refresh at START + 1 (default: 0,1, every iteration).
+(i - START - 1) % PERIOD == 0, PERIOD 0 for the one refresh at START + 1 (default: 0,1, every iteration).  With --precision f32,
+--refresh-f32 runs the three on the fp32 solver (proposed_algorithm_refresh).
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -68,10 +69,12 @@ ap.add_argument("--widen-primary", choices=("neighbourhood", "ties"), default=No
                 help="--device-channel: what the widened order sorts by first (default: neighbourhood)")
 ap.add_argument("--refresh", default=None, metavar="START,PERIOD",
                 help="--device-channel: the refresh schedule of refresh / warm_refresh / pai_prev_refresh (default: 0,1)")
+ap.add_argument("--refresh-f32", action="store_true",
+                help="--device-channel --precision f32: the refresh modes on the fp32 solver (proposed_algorithm_refresh)")
 a = ap.parse_args()
-if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None or a.refresh is not None) \
-        and not a.device_channel:
-    ap.error("--drift, --modes, --widen, --widen-primary and --refresh need --device-channel")
+if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None or a.refresh is not None
+        or a.refresh_f32) and not a.device_channel:
+    ap.error("--drift, --modes, --widen, --widen-primary, --refresh and --refresh-f32 need --device-channel")
 if a.refresh is not None:
     try:
         a.refresh = tuple(int(x) for x in a.refresh.split(","))
@@ -106,6 +109,8 @@ if a.device_channel:
         kw["widen_primary"] = a.widen_primary
     if a.refresh is not None:
         kw["refresh"] = a.refresh
+    if a.refresh_f32:
+        kw["refresh_f32"] = True
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
