@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """Bits of the fp32 proposed_algorithm through every entry of its call frame (plain, begin/end, resumed, the _c64 forms, the
-pipelined host calls, the refusals), to hold one build of the library against another as tools/f64_bits.py does for float64:
+pipelined host calls, the refusals, the refreshed entry) and every branch of its driver (branch_cases), to hold one build of
+the library against another as tools/f64_bits.py does for float64:
 ``--dump FILE`` writes, for every call, each output array (above 4 KiB: its SHA-256), the status with
 jstsp_last_fused_fallbacks, jstsp_last_dictionary_block and the workspace size, and the message of a refused call, from the
 library that JSTSP_LIB names (default: the one built in the tree); ``--against FILE`` runs the same calls and compares byte for
-byte.
+byte, except that the workspace may be smaller than the other library's (reported as ``workspace_smaller``), never larger;
+``--trace-call NAME`` runs one call alone, for a kernel trace of it.
 
     JSTSP_LIB=/path/to/other/libjstsp_mi355x.so python tools/f32_frame_bits.py --dump other.npz
     python tools/f32_frame_bits.py --against other.npz --report profiles/f32_frame_bits.json
+    rocprofv3 --kernel-trace --stats -- python tools/f32_frame_bits.py --trace-call small_ce
 """
 import argparse
 import ctypes as C
@@ -65,15 +68,18 @@ def _host(x):
     return x.cpu().numpy() if torch.is_tensor(x) else x
 
 
-def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=None, env=None, **over):
-    """One call of jstsp_proposed_{algorithm,resume}_{c32,c64} on P; yields (name, array) for every output, the status and the
-    counters, and the message when the call was refused.  resume: dict(it0, state (host array or None), same (state_out is
-    state_in), out (a state is returned)).  over: arguments replaced by name (None: a NULL pointer)."""
+def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=None, refresh=None, env=None, **over):
+    """One call of jstsp_proposed_{algorithm,resume,refresh}_{c32,c64} on P; yields (name, array) for every output, the status and
+    the counters, and the message when the call was refused.  resume: dict(it0, state (host array or None), same (state_out is
+    state_in), out (a state is returned)).  refresh: (start, period) of jstsp_proposed_refresh_c32, which takes resume too (default:
+    from zero); indx: True the whole order of P, an int its first so many entries (refresh only).  over: arguments replaced by name
+    (None: a NULL pointer)."""
     lib, ctx = _lib.load(), _lib.default_context(0)
     cdt, rdt = (np.complex128, np.float64) if c64 else (np.complex64, np.float32)
     wide = lambda a: a.astype(rdt if a.dtype.kind == "f" else cdt)
     ins = {k: _place(wide(P.arr[k]), mem) for k in ("subY", "Omega", "A", "B")}
-    ins["indx_S"] = _place(P.arr["indx_S"], mem) if indx else None
+    n_indx = 0 if not indx else (P.Gr * P.G2 if indx is True else int(indx))
+    ins["indx_S"] = _place(np.ascontiguousarray(P.arr["indx_S"][:, :n_indx]), mem) if indx else None
     zeros = lambda n, dt: _place(np.zeros(max(int(n), 1), dt), mem)
     outs = {"S": zeros(P.batch * P.Gr * P.G2, cdt), "Y": zeros(P.batch * P.N * P.M, cdt), "ce": zeros(P.batch * 3 * Imax, np.float64) if ce else None}
     v = dict(N=P.N, M=P.M, Gr=P.Gr, G2=P.G2, batch=P.batch, strideA=P.strideA, strideB=P.strideB, Imax=Imax, type=type, memspace=mem)
@@ -81,13 +87,17 @@ def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=No
     v.update({k: a.ctypes.data_as(_lib.c_dp) for k, a in P.scal.items()})
     v.update(over)
     args = [ctx.handle] + [v[k] for k in ARGS]
-    name = "jstsp_proposed_%s_%s" % ("resume" if resume else "algorithm", "c64" if c64 else "c32")
+    if refresh:
+        resume = resume or dict(it0=0)
+        outs["order"] = zeros(P.batch * min(P.Gr * P.G2, _lib.SUPPORT_TOP_MAX), np.int32)
+        args[-3:-3] = [n_indx, refresh[0], refresh[1]]          # (... type, indx_S, n_indx, start, period, S, Y, ce)
+    name = "jstsp_proposed_%s_%s" % ("refresh" if refresh else "resume" if resume else "algorithm", "c64" if c64 else "c32")
     if resume:
         st = resume.get("state")
         s_in = None if st is None else _place(np.ascontiguousarray(st, dtype=cdt), mem)
         s_out = s_in if resume.get("same") else (zeros(P.batch * P.state_elems, cdt) if resume.get("out", True) else None)
         outs["state"] = s_out
-        args += [resume["it0"], _ptr(s_in), _ptr(s_out)]
+        args += [resume["it0"], _ptr(s_in), _ptr(s_out)] + ([_ptr(outs["order"])] if refresh else [])
     os.environ.update(env or {})
     try:
         rc = getattr(lib, name)(*args, v["memspace"])
@@ -238,9 +248,116 @@ def refusal_cases():
     yield "refused/end_null_handle", np.frombuffer(("%d: " % rc).encode() + lib.jstsp_last_error(), np.uint8)
 
 
+def random_problem(N, M, Gr, G2, batch=3, seed=7):
+    """A random complex64 problem of a shape build_trials does not make: a sparse S0 seen through normalised Gaussian A (shared) and
+    B (per trial) under a random mask, with a random order as indx_S."""
+    r = np.random.default_rng([seed, N, M, Gr, G2])
+    cn = lambda *s: torch.from_numpy(((r.standard_normal(s) + 1j * r.standard_normal(s)) / np.sqrt(2)).astype(np.complex64))
+    A, B = cn(N, Gr) / np.sqrt(N), cn(batch, G2, M) / np.sqrt(M)
+    S0 = cn(batch, Gr, G2) * torch.from_numpy(r.random((batch, Gr, G2)) < 4.0 / (Gr * G2) + 0.05)
+    Om = torch.from_numpy((r.random((batch, N, M)) < 0.6).astype(np.float32))
+    subY = (Om * (A @ S0 @ B + 0.05 * cn(batch, N, M))).to(torch.complex64)
+    order = np.stack([r.permutation(Gr * G2) + 1 for _ in range(batch)]).astype(np.int32)
+    hyp = lambda lo: torch.from_numpy(lo * (1.0 + 0.25 * r.random(batch)))
+    return Problem(dict(subY=subY, Omega=Om, A=A, B=B, indx_S=torch.from_numpy(order), tau_Y=hyp(0.05), tau_Z=hyp(0.02), rho=hyp(0.5)))
+
+
+def shared_b(P):
+    """P with the dictionary of its first trial for the whole batch (strideB = 0)"""
+    Q = Problem.__new__(Problem)
+    Q.__dict__.update(P.__dict__)
+    Q.arr = dict(P.arr, B=np.ascontiguousarray(P.arr["B"][0]))
+    Q.strideB = 0
+    return Q
+
+
+def toeplitz256():
+    p = SweepParams(Nt=64, Nr=64, L=4, T=8, Mr=8, snr_db=5.0)
+    return shared_b(Problem(build_trials(p, 0, 256, seed=43)))
+
+
+# The branches of the solver that the two shapes above (fused-pass shapes, N = 64 <= M, batch 5-6, A shared, B per trial) never reach:
+# shape -> what it is for.  Which branch a shape takes depends on the library's tuning; --trace-call runs one call alone for a kernel trace.
+BRANCH_SHAPES = {
+    (8, 16, 8, 16): "no split-f16 path, cgemm epilogues",
+    (16, 8, 8, 8): "N > M: svt_apply / update_x / update_c with an explicit C",
+    (64, 1024, 64, 64): "split-f16 products and the epilogues' maxima, no fused pass",
+    (128, 256, 128, 128): "N > 64; 'std' with both factors by the Gram inverse",
+}
+SWITCHES = (("JSTSP_OVERLAP", "0"), ("JSTSP_OVERLAP", "1"), ("JSTSP_TOEPLITZ", "0"), ("JSTSP_TOEPLITZ", "1"), ("JSTSP_FUSED", "2"), ("JSTSP_H2", "0"))
+
+
+def branch_cases():
+    for shape, what in BRANCH_SHAPES.items():
+        P = random_problem(*shape)
+        for Imax in (1, 2, 6):
+            for mem in (HOST, DEVICE):
+                for ce in (False, True):
+                    for indx in (False, True):
+                        for type in (_lib.TYPE_APPROXIMATE, _lib.TYPE_STD):         # ('std' is admissible at all four: N >= Gr, M >= G2)
+                            tag = "branch/%dx%dx%dx%d/Imax%d/mem%d/ce%d/indx%d/type%d" % (shape + (Imax, mem, ce, indx, type))
+                            yield from call(tag, P, Imax, mem, type=type, indx=indx, ce=ce)
+    P = random_problem(16, 8, 8, 8)
+    for mem in (HOST, DEVICE):
+        for indx in (False, True):
+            for type in (_lib.TYPE_APPROXIMATE, _lib.TYPE_STD):
+                tag = "branch/16x8x8x8/resumed/mem%d/indx%d/type%d" % (mem, indx, type)
+                yield from call(tag + "/leg1", P, 3, mem, type=type, indx=indx, resume=dict(it0=0))
+                st = call.last["state"]
+                yield from call(tag + "/leg2", P, 3, mem, type=type, indx=indx, resume=dict(it0=3, state=st))
+    S, T = small(), toeplitz()
+    for Imax in (1, 2, 6):
+        for ce in (False, True):
+            for indx in (False, True):
+                tail = "Imax%d/ce%d/indx%d" % (Imax, ce, indx)
+                # (build_trials makes B per trial: the shapes above run with strideB != 0 throughout; one dictionary for the batch here)
+                for mem in (HOST, DEVICE):
+                    yield from call("branch/small_shared_B/mem%d/%s" % (mem, tail), shared_b(S), Imax, mem, indx=indx, ce=ce)
+                yield from call("branch/small_host_compact/" + tail, S, Imax, HOST, indx=indx, ce=ce, env={"JSTSP_HOST_COMPACT": "2"})
+                for sname, P in (("small", S), ("toeplitz", T)):
+                    for k, v in SWITCHES:
+                        for mem in (HOST, DEVICE):
+                            yield from call("branch/%s/%s=%s/mem%d/%s" % (sname, k, v, mem, tail), P, Imax, mem, indx=indx, ce=ce, env={k: v})
+    P = toeplitz256()           # one dictionary for 256 trials: the pair kernel on K in fragment order
+    for mem in (HOST, DEVICE):
+        for ce in (False, True):
+            for ename, env in (("default", {}), ("unfused", UNFUSED)):
+                yield from call("branch/toeplitz256_shared_B/%s/mem%d/ce%d" % (ename, mem, ce), P, 2, mem, ce=ce, env=env)
+
+
+def refresh_cases():
+    """jstsp_proposed_refresh_c32 on the small shape: from zero, and a second leg from the returned state"""
+    P = small()
+    for mem in (HOST, DEVICE):
+        for pol in ((0, 1), (3, 2), (2, 0)):
+            for indx in (False, 40):
+                for ename, env in (("default", {}), ("forced", FORCED)):
+                    if env and pol != (3, 2):
+                        continue
+                    tag = "refresh/mem%d/start%d_period%d/indx%d/%s" % (mem, pol[0], pol[1], indx, ename)
+                    yield from call(tag + "/leg1", P, 6, mem, indx=indx, refresh=pol, env=env)
+                    st = call.last["state"]
+                    yield from call(tag + "/leg2", P, 6, mem, indx=indx, refresh=pol, resume=dict(it0=6, state=st), env=env)
+                    yield from call(tag + "/leg2_two_outputs", P, 6, mem, indx=indx, ce=False, refresh=pol, resume=dict(it0=6, state=st, out=False), env=env)
+
+
+# single calls for a kernel trace (one process per call): name -> (problem, arguments of call())
+TRACE_CALLS = {
+    "small_ce": (small, dict(Imax=6)),
+    "small_unfused": (small, dict(Imax=6, env=UNFUSED)),
+    "16x8x8x8": (lambda: random_problem(16, 8, 8, 8), dict(Imax=6)),
+    "refresh_0_1": (small, dict(Imax=6, refresh=(0, 1))),
+    "8x16x8x16": (lambda: random_problem(8, 16, 8, 16), dict(Imax=6)),
+    "64x1024x64x64": (lambda: random_problem(64, 1024, 64, 64), dict(Imax=6)),
+    "128x256x128x128_std": (lambda: random_problem(128, 256, 128, 128), dict(Imax=6, type=1)),
+    "small_host_compact": (small, dict(Imax=6, mem=HOST, env={"JSTSP_HOST_COMPACT": "2"})),
+    "toeplitz256_shared_B": (toeplitz256, dict(Imax=2)),
+}
+
+
 def cases():
     _lib.default_context(0).use_torch_stream()
-    for gen in (plain_cases, two_run_cases, begin_end_cases, resume_cases, c64_cases, pipelined_cases, refusal_cases):
+    for gen in (plain_cases, two_run_cases, begin_end_cases, resume_cases, c64_cases, pipelined_cases, refusal_cases, branch_cases, refresh_cases):
         yield from gen()
 
 
@@ -249,13 +366,23 @@ def main():
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--dump", metavar="FILE")
     g.add_argument("--against", metavar="FILE")
+    g.add_argument("--trace-call", choices=sorted(TRACE_CALLS), help="run this one call and nothing else (under a kernel trace)")
     ap.add_argument("--report", metavar="JSON", help="with --against: write the counts here")
     a = ap.parse_args()
+    if a.trace_call:
+        _lib.default_context(0).use_torch_stream()
+        make, kw = TRACE_CALLS[a.trace_call]
+        kw = dict(dict(mem=DEVICE), **kw)
+        out = dict(call(a.trace_call, make(), kw.pop("Imax"), kw.pop("mem"), **kw))
+        print(json.dumps({"call": a.trace_call, "status_fallbacks_block_workspace": out[a.trace_call + "/status_fallbacks_block_workspace"].tolist()}))
+        return 0
     got, nbytes = {}, 0
     for k, v in cases():
         if k.startswith("-"):
             continue
         assert k not in got, k
+        if len(got) % 500 == 0:
+            print("%d arrays, at %s" % (len(got), k), file=sys.stderr, flush=True)
         v = np.ascontiguousarray(v)
         nbytes += v.nbytes
         # (the outputs of the pipelined calls alone are gigabytes: an array above 4 KiB is kept as the SHA-256 of its type, shape and bytes)
@@ -266,10 +393,15 @@ def main():
         return 0
     with np.load(a.against, allow_pickle=False) as z:
         ref = {k: z[k] for k in z.files}
+    # the workspace (last word of a call's record: the context's, which only grows) may be smaller than the other library's, never larger
+    WS = "/status_fallbacks_block_workspace"
+    smaller = {k: [int(ref[k][-1]), int(got[k][-1])] for k in got if k.endswith(WS) and k in ref and got[k][-1] < ref[k][-1]}
+    for k in smaller:
+        got[k] = np.append(got[k][:-1], ref[k][-1])
     diff = sorted(k for k in set(ref) | set(got) if k not in ref or k not in got or ref[k].dtype != got[k].dtype or
                   ref[k].shape != got[k].shape or ref[k].tobytes() != got[k].tobytes())
     rep = {"library": os.path.relpath(_lib.LIB_PATH, ROOT), "against": os.path.basename(a.against), "arrays_compared": len(set(ref) | set(got)),
-           "bytes_compared": int(nbytes), "differences": len(diff), "differing": diff}
+           "bytes_compared": int(nbytes), "differences": len(diff), "differing": diff, "workspace_smaller": smaller}
     print(json.dumps(rep))
     if a.report:
         with open(a.report, "w") as f:
