@@ -1258,6 +1258,50 @@ int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
                                int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out,
                                int32_t *indx_out, int memspace);
 
+/* ---- the float64 ADMM that stops each trial when its iterate has settled (csrc/proposed64.hip) ----------
+ * Alg. 2 ('approximate') only: the body, the limits and the arguments of jstsp_proposed_refresh_f64 (refresh_period < 0: no
+ * support policy, the body of jstsp_proposed_resume_f64; indx_S then has n_indx entries per trial, 0 meaning Gr*G2), with a
+ * stopping rule on convergence_error(i, 3) = ||v_i - v_{i-1}||^2 / ||v_{i-1}||^2 (proposed_algorithm.m:51), the column the
+ * gradient step already sums per trial in one workgroup.
+ *  - THE RULE: trial t runs the global iterations it0 + 1, ...; it stops after the first iteration i with i - it0 >= min_iters and
+ *    ce(i, 3) <= tol[t], failing that after it0 + Imax.  Memoryless - a function of i, it0 and the iterate - so a trial that came
+ *    back unstopped is resumed by a later call and legs compose.  tol: batch doubles on the host, as tau_Y; a tol[t] that is zero,
+ *    negative or NaN never stops its trial, nor does the Inf of iteration 1 from a zero state, nor a NaN.  min_iters >= 1.
+ *  - iters_out[t] (required, int32): the iterations this call ran for trial t, 1 .. Imax.  ce3_out[t] (optional): ce(., 3) of its
+ *    last iteration; the rule stopped the trial exactly when iters_out[t] >= min_iters && ce3_out[t] <= tol[t].
+ *  - S_out, Y_out, state_out, indx_out hold what the loop held after the trial's LAST iteration; the rows of ce_out after it are
+ *    NaN.  indx_out (R x batch) is written when the call can run a refresh within Imax; the row of a trial that stopped before
+ *    its first refresh is all zeros (no 1-based list holds a zero): the order in force for it is still the caller's indx_S.
+ *  - THE CONTRACT, for min(N, M) <= 64: for every trial S, Y, the state, the order and the rows of ce are the bits
+ *    jstsp_proposed_refresh_f64 (without a policy jstsp_proposed_resume_f64) returns for that trial ALONE with Imax =
+ *    iters_out[t] - whatever the batch around it, whatever `check`, in both memspaces.  Above order 64 the global Jacobi sweeps a
+ *    call's matrices together (the note of jstsp_proposed_algorithm_f64): iters_out and the values to rounding, not the bits.
+ *  - Mechanism: a stopped trial costs nothing further.  A test kernel sets a flag per slot after every iteration, a capture
+ *    kernel writes what has JUST stopped to the trial's own place in the outputs (a trial is captured at the iteration where it
+ *    stops, so `check` never changes a result), and every `check` >= 1 iterations an ordered count over the flags gives the
+ *    survivors' new slots: the host reads one int (one stream synchronisation per `check` iterations), a gather kernel moves every
+ *    per-trial array of the survivors to the front of a shadow set - never in place, never writing a caller's array - once at
+ *    least a sixteenth of the slots have stopped (moving the survivors costs about a sixth of an iteration), and every later
+ *    launch is sized to the count; the call returns when it is zero.  With no positive tol nothing is read back, no shadow
+ *    set exists, and the call is the sibling on the bits with iters_out = Imax.
+ *  - Workspace: the sibling's plus the shadow set (one more copy of X, V1, V2, C, A S B, v, S, subY, Omega, the rank, per-trial
+ *    dictionaries and their Grams; two of the inputs in a JSTSP_DEVICE call), measured with the rest; the 24 GiB refusal applies.
+ *  - JSTSP_E_NULL: tol or iters_out NULL; JSTSP_E_ARG: min_iters < 1, check < 1; everything the siblings refuse.
+ * Asserted (tests/test_gpu_until64.py): iters against tests/until_ref.py, whose decisions all keep a margin of 1e-3 from their
+ * threshold (tests/test_until_ref.py); per trial the bits of the sibling run alone over iters[t] iterations, for check 1, 3, 64,
+ * both memspaces, B shared and per trial, indx_S and two policies; a batch of duplicates; warm starts, min_iters and legs; tol = 0;
+ * a NaN trial; a batch that leaves the loop early; the refusals. */
+int jstsp_proposed_until_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                             const jstsp_c64 *subY, const double *Omega,
+                             const jstsp_c64 *A, long long strideA,
+                             const jstsp_c64 *B, long long strideB,
+                             int Imax, const double *tau_Y, const double *tau_S, const double *rho,
+                             const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                             const double *tol, int min_iters, int check,
+                             jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                             int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out,
+                             int32_t *iters_out, double *ce3_out, int memspace);
+
 /* ---- the fp32 ADMM with its support refreshed from its own iterate (csrc/proposed.hip) ------------------
  * jstsp_proposed_resume_c32 with the support policy of jstsp_proposed_refresh_f64 above: the same schedule on the global
  * iteration index, the same R = min(Gr*G2, JSTSP_SUPPORT_TOP_MAX) and its LIMIT, the same indx_S (n_indx entries per trial, stride

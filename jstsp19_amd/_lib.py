@@ -165,6 +165,10 @@ SIGNATURES["jstsp_support_top_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_
 SIGNATURES["jstsp_proposed_refresh_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
                                                     c_void_p, c_ll, c_int, c_dp, c_dp, c_dp, c_void_p, c_int, c_int, c_int,
                                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int])
+# the float64 ADMM with a stopping rule (csrc/proposed64.hip): the refreshed entry's list with tol, min_iters, check after
+# refresh_period and iters_out, ce3_out before memspace
+SIGNATURES["jstsp_proposed_until_f64"] = (c_int, SIGNATURES["jstsp_proposed_refresh_f64"][1][:20] + [c_dp, c_int, c_int]
+                                          + SIGNATURES["jstsp_proposed_refresh_f64"][1][20:-1] + [c_void_p, c_void_p, c_int])
 # the same in fp32 (csrc/support_top.hip, csrc/proposed.hip, csrc/c64.hip): the float64 lists, with `type` after rho as in
 # jstsp_proposed_resume_c32 ('std' is refused)
 SIGNATURES["jstsp_support_top_c32"] = SIGNATURES["jstsp_support_top_f64"]

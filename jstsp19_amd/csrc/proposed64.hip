@@ -33,12 +33,30 @@
 // (every other entry) not one launch differs.
 //  Asserted (tests/test_gpu_refresh64.py): without a refresh in the call the bits of jstsp_proposed_resume_f64; with one, the bits
 //  of the chain of one-iteration calls with jstsp_support_order_f64 between them; legs; tests/refresh_ref.py within 1e-10 / 1e-8.
+//
+// jstsp_proposed_until_f64 - Alg. 2 that stops each trial when its own iterate has settled (Until64 below):
+// trial t stops after the first iteration i with i - it0 >= min_iters and convergence_error(i, 3) <= tol[t], the column that
+// step_v64_kernel writes per trial in one workgroup.  The body is admm64_approx again, with four more kernels and nothing changed
+// in the others:
+//   stop test   one thread per slot after the iteration's tail: flag, iters and ce3_out through the slot -> trial map;
+//   capture     the same iteration, for the slots whose flag was just set: S, the iteration's Y, the packed state and the order go
+//               to the trial's own place in the outputs.  So a trial is CAPTURED AT THE ITERATION WHERE IT STOPS, whatever `check`
+//               is; a stopped trial that runs on until the next compaction writes nothing more (its rows of ce stay NaN);
+//   compact     every `check` iterations: an ordered ballot count over the flags gives each survivor's new slot and the active
+//               count, the one int the host reads (one stream synchronisation per `check` iterations);
+//   gather      one launch moves every per-trial array of the survivors to its new slot in a SHADOW set (never in place; the
+//               caller's device inputs are only read), the host swaps the pointers and sizes every later launch to the count.
+//               It runs when at least a sixteenth of the slots have stopped since the last one (UNTIL_GATHER_SHARE below).
+// A trial's bits depend neither on its slot nor on its batch (min(N, M) <= 64), so they are those of the sibling run for that
+// trial alone over iters[t] iterations.  With no positive tol nothing is read back and the launches added are the map's
+// initialisation and the last iteration's test and capture.
 #include "pinv64.h"
 #include "support_top.h"
 #include "svt64.h"
 
 #include <algorithm>
 #include <climits>
+#include <functional>
 #include <vector>
 
 namespace jstsp {
@@ -222,6 +240,118 @@ __global__ __launch_bounds__(256) void state_pack64_kernel(long long nm, long lo
     }
 }
 
+// ---- the stopping rule of jstsp_proposed_until_f64 ---------------------------------------------------------------------------------
+// flag of a slot: 0 running, 1 stopped by this iteration (the capture kernel's cue), 2 stopped earlier and not yet compacted away
+__global__ __launch_bounds__(256) void until_init64_kernel(int batch, long long nce, int32_t *map, int32_t *flag, double *ce)
+{
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i0 < batch) { map[i0] = (int32_t)i0; flag[i0] = 0; }
+    for (long long e = i0; e < nce; e += (long long)gridDim.x * 256) ce[e] = __builtin_nan("");
+}
+
+// ce(i, 1:3) of the running slots, through the map (the rows of a stopped trial stay NaN)
+__global__ __launch_bounds__(256) void ce64_map_kernel(int nact, int Imax, int it, const double *lx, const double *l1, const double *l2, const double *ce3,
+                                                       const int32_t *map, const int32_t *flag, double *ce)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nact || flag[s] != 0) return;
+    double *c = ce + (long long)map[s] * 3 * Imax + it;
+    c[0] = l1[s] / lx[s]; c[Imax] = l2[s] / lx[s]; c[2 * Imax] = ce3[s];
+}
+
+// after iteration k of the call (1-based): a running slot stops when k >= min_iters and ce3 <= tol (tol > 0; false for a NaN or
+// an Inf on the left), or when the iteration was the call's last
+__global__ __launch_bounds__(256) void until_test64_kernel(int nact, int k, int min_iters, int last, const double *ce3, const double *tol,
+                                                           const int32_t *map, int32_t *flag, int32_t *iters, double *ce3_out)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nact) return;
+    const int32_t f = flag[s];
+    if (f == 1) flag[s] = 2;
+    if (f != 0) return;
+    const double c = ce3[s], tl = tol[s];
+    if (!(last || (k >= min_iters && tl > 0.0 && c <= tl))) return;
+    const int32_t t = map[s];
+    flag[s] = 1; iters[t] = k;
+    if (ce3_out) ce3_out[t] = c;
+}
+
+// the slots the test has just stopped: S, Y, the state block (state_pack64_kernel's layout) and the order, to trial map[slot]
+__global__ __launch_bounds__(256) void until_capture64_kernel(long long nm, long long g, int R, State64 w, const double2 *Y, const int32_t *top, int have_top,
+                                                              const int32_t *flag, const int32_t *map, double2 *S_out, double2 *Y_out, double2 *state,
+                                                              int32_t *top_out)
+{
+    const int s = blockIdx.y;
+    if (flag[s] != 1) return;
+    const long long t = map[s], e0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+    const double2 *Ss = w.a[5] + s * g;
+    for (long long e = e0; e < g; e += step) S_out[t * g + e] = Ss[e];
+    if (Y_out)
+        for (long long e = e0; e < nm; e += step) Y_out[t * nm + e] = Y[s * nm + e];
+    if (state) {
+        double2 *dst = state + t * (4 * nm + 2 * g);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const long long len = k < 4 ? nm : g;
+            const double2 *src = w.a[k] + s * len;
+            for (long long e = e0; e < len; e += step) dst[e] = src[e];
+            dst += len;
+        }
+    }
+    if (top_out)
+        for (long long e = e0; e < R; e += step) top_out[t * R + e] = have_top ? top[(long long)s * R + e] : 0;
+}
+
+// newslot[s] = the number of running slots below s (-1 for a stopped one), *count = the number of running slots; one workgroup
+__global__ __launch_bounds__(ST_THREADS) void until_compact64_kernel(int nact, const int32_t *flag, int32_t *newslot, int32_t *count)
+{
+    __shared__ int wsum[2][ST_THREADS / 64];
+    int base = 0;
+    for (int c = 0; c < nact; c += ST_THREADS) {
+        const int i = c + threadIdx.x;
+        const bool keep = i < nact && flag[i] == 0;
+        int r, r2, tot, tot2;
+        st_block_rank2<ST_THREADS>(keep, false, wsum, r, r2, tot, tot2);
+        if (i < nact) newslot[i] = keep ? base + r : -1;
+        base += tot;
+    }
+    if (threadIdx.x == 0) *count = base;
+}
+
+// every per-trial array of the survivors from its slot to its new one, between two buffers (src != dst); one launch
+struct GItem64 {
+    const void *src; void *dst;
+    long long n, stride;                // elements per trial, elements between trials
+    int esz;                            // 16 (double2), 8 (double) or 4 (int32_t)
+};
+constexpr int UNTIL_ITEMS = 20;
+// A gather streams every array of every survivor once - measured at BASELINE configs[1], 256 trials, about a sixth of an iteration
+// (profiles/until64_rate.json) - while a stopped slot that runs on costs 1 / active of one per iteration: the survivors are moved
+// only when at least one slot in UNTIL_GATHER_SHARE has stopped since the last gather.
+constexpr int UNTIL_GATHER_SHARE = 16;
+struct Gather64 {
+    GItem64 it[UNTIL_ITEMS];
+    int cnt;
+};
+template <class T>
+__device__ __forceinline__ void gather_one(const GItem64 &q, long long from, long long to)
+{
+    const T *src = static_cast<const T *>(q.src) + from * q.stride;
+    T *dst = static_cast<T *>(q.dst) + to * q.stride;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < q.n; e += (long long)gridDim.x * 256) dst[e] = src[e];
+}
+__global__ __launch_bounds__(256) void until_gather64_kernel(Gather64 gt, const int32_t *newslot)
+{
+    const int32_t to = newslot[blockIdx.y];
+    if (to < 0) return;
+    for (int k = 0; k < gt.cnt; ++k) {
+        const GItem64 &q = gt.it[k];
+        if (q.esz == 16) gather_one<double2>(q, blockIdx.y, to);
+        else if (q.esz == 8) gather_one<double>(q, blockIdx.y, to);
+        else gather_one<int32_t>(q, blockIdx.y, to);
+    }
+}
+
 // elements of the scratch array that the split products of one solve share (the largest need among its products)
 size_t solver_ws_elems(int N, int M, int Gr, int G2, int batch, int nA, int nB)
 {
@@ -247,6 +377,7 @@ struct Admm64 {
     double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *T, *W, *gws = nullptr;
     double *ced, *lx, *l1, *l2, *ce3;
     int32_t *rank = nullptr;
+    const int32_t *map = nullptr, *flag = nullptr;  // jstsp_proposed_until_f64: slot -> trial and the slots' flags (ce goes through them)
     Svt64 sv;
 
     bool angles() const { return indx_ != nullptr; }
@@ -311,7 +442,8 @@ struct Admm64 {
             JSTSP_TRY(sv.lambda_max(st, X, lx));
             JSTSP_TRY(sv.lambda_max(st, V1, l1));
             JSTSP_TRY(sv.lambda_max(st, V2, l2));
-            hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
+            if (map) hipLaunchKernelGGL(ce64_map_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, map, flag, ced);
+            else hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
         }
         JSTSP_HIP(hipGetLastError());
         return 0;
@@ -387,13 +519,57 @@ int refresh64_args(const char *nmf, const Refresh64 &rf, const int32_t *indx_S, 
     return 0;
 }
 
-// Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state), of jstsp_proposed_resume_f64 and - with a
-// support policy rf - of jstsp_proposed_refresh_f64: iterations it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the
-// entry in every message; std_entry is where its 'std' refusal points.
+// The stopping rule of jstsp_proposed_until_f64 (every other entry passes none, and not one launch differs): the head of this file
+// says what runs; tol holds one double per trial on the host.
+struct Until64 {
+    const double *tol;
+    int min_iters, check;
+    int32_t *iters_out;
+    double *ce3_out;
+    int n_indx;                                     // without a policy: entries per trial of indx_S (0: all Gr G2)
+};
+
+// One per-trial array that a compaction moves: `cur` is the pointer the loop uses (the caller's own array for a device input until
+// the first gather), alt the buffer the next gather writes, spare the second buffer of an array whose first `cur` is not the slab's.
+struct Shadow64 {
+    std::function<const void *()> cur;
+    std::function<void(void *)> set;
+    void *alt, *spare;
+    long long n, stride; int esz;
+    bool owned;                                     // cur points into the slab: it becomes the next alt
+    GItem64 item() const { return GItem64{cur(), alt, n, stride, esz}; }
+    void swap()
+    {
+        void *old = const_cast<void *>(cur());
+        set(alt);
+        alt = owned ? old : spare;
+        owned = true;
+    }
+};
+template <class T> Shadow64 shadow_of(T *&p, void *alt, void *spare, long long n, long long stride, int esz, bool owned)
+{
+    return Shadow64{[&p] { return static_cast<const void *>(p); }, [&p](void *q) { p = static_cast<T *>(q); }, alt, spare, n, stride, esz, owned};
+}
+
+int until64_args(const char *nmf, const Until64 &un, const int32_t *indx_S, long long g)
+{
+    JSTSP_REQUIRE(un.tol && un.iters_out, JSTSP_E_NULL, "%s: tol and iters_out are required", nmf);
+    JSTSP_REQUIRE(un.min_iters >= 1 && un.check >= 1, JSTSP_E_ARG, "%s: min_iters = %d, check = %d: both must be at least 1", nmf, un.min_iters,
+                  un.check);
+    JSTSP_REQUIRE(un.n_indx >= 0 && (indx_S || un.n_indx == 0) && un.n_indx <= g, JSTSP_E_ARG,
+                  "%s: n_indx = %d: need 0 (all) or 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, un.n_indx, g);
+    return 0;
+}
+
+// Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state), of jstsp_proposed_resume_f64, - with a
+// support policy rf - of jstsp_proposed_refresh_f64 and - with a stopping rule un - of jstsp_proposed_until_f64: iterations
+// it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the entry in every message; std_entry is where its 'std' refusal
+// points.
 int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_,
                   const double *Omega_, const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
                   const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
-                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace, const Refresh64 *rf = nullptr)
+                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace, const Refresh64 *rf = nullptr,
+                  const Until64 *un = nullptr)
 {
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
     JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
@@ -406,21 +582,30 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     JSTSP_TRY(resume64_args(nmf, Imax, it0, state_in));
     JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
     if (rf) JSTSP_TRY(refresh64_args(nmf, *rf, indx_S_, (long long)Gr * G2));
+    if (un) JSTSP_TRY(until64_args(nmf, *un, indx_S_, (long long)Gr * G2));
     Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
     f.make_par(tau_Y, tau_S, rho);
     hipStream_t st = ctx->stream;
-    const size_t g1 = f.g1(), g = g1 * batch;
+    const size_t g1 = f.g1();
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
     const int R = (int)std::min<size_t>(g1, ST_MAX);               // entries of a refreshed order
     bool runs_refresh = false;                                      // a function of it0, Imax, start and period alone
     if (rf) {
         f.n_indx = rf->n_indx; f.refresh = true;
         for (int it = 0; it < Imax && !runs_refresh; ++it) runs_refresh = rf->at((long long)it0 + it + 1);
-    }
+    } else if (un) f.n_indx = un->n_indx;
     int32_t *top = nullptr;                                         // the list of the call's last refresh, for indx_out
+    const bool want_top = rf && rf->indx_out && runs_refresh;
 
     double2 *V, *S, *Res, *RRes, *T2, *GA, *GB, *sout = nullptr;
     const double2 *sin = nullptr;
+    // the stopping rule's arrays: tol, slot -> trial, flags, new slots, the active count; the outputs; the order by slot and by trial
+    bool rule_on = false;                                           // some tol is positive: trials can stop, and the loop compacts
+    for (int t = 0; un && t < batch; ++t) rule_on = rule_on || un->tol[t] > 0.0;
+    const double *tolp = nullptr;
+    int32_t *map = nullptr, *flag = nullptr, *newslot = nullptr, *count = nullptr, *itd = nullptr, *top_out = nullptr;
+    double *c3d = nullptr;
+    std::vector<Shadow64> sh;
     Slab s(st);
     JSTSP_TRY(ws64_open(s, nmf, batch, [&](Slab &w, int b) {
         const int bA = strideA ? b : 1, bB = strideB ? b : 1;
@@ -430,21 +615,63 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         f.gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
         if (state_in) sin = w.in(reinterpret_cast<const double2 *>(state_in), f.state1() * b, f.host);
         if (state_out) sout = w.out(reinterpret_cast<double2 *>(state_out), f.state1() * b, f.host);
-        if (rf && rf->indx_out && runs_refresh) top = w.out(rf->indx_out, (size_t)R * b, f.host);
+        if (want_top) top = w.out(rf->indx_out, (size_t)R * b, f.host);
+        if (!un) return;
+        tolp = w.in(un->tol, b, true);
+        for (int32_t **p : {&map, &flag, &newslot}) *p = w.get<int32_t>(b);
+        count = w.get<int32_t>(1);
+        itd = w.out(un->iters_out, b, f.host);
+        if (un->ce3_out) c3d = w.out(un->ce3_out, b, f.host);
+        if (want_top) { top_out = top; top = w.get<int32_t>((size_t)R * b); }   // the loop's list is by slot; the caller's by trial
+        if (!rule_on) return;
+        // the shadow set of a compaction: every array that lives from one iteration to the next, and the inputs
+        sh.clear();
+        const long long nm = (long long)f.nm1(), gl = (long long)g1;
+        auto add = [&](auto *&p, long long n, long long stride, size_t total, int esz, bool owned) {
+            const size_t words = (total * esz + 15) / 16;
+            void *alt = w.get<double2>(words), *spare = owned ? nullptr : (void *)w.get<double2>(words);
+            sh.push_back(shadow_of(p, alt, spare, n, stride, esz, owned));
+        };
+        for (double2 **p : {&f.X, &f.V1, &f.V2, &f.Cm, &f.Xs}) add(*p, nm, nm, (size_t)nm * b, 16, true);
+        for (double2 **p : {&V, &S}) add(*p, gl, gl, (size_t)gl * b, 16, true);
+        add(f.subY, nm, nm, (size_t)nm * b, 16, f.host);
+        add(f.Omega, nm, nm, (size_t)nm * b, 8, f.host);
+        add(f.par, 5, 5, (size_t)5 * b, 8, true);
+        add(tolp, 1, 1, b, 8, true);
+        add(map, 1, 1, b, 4, true);
+        if (f.angles() || f.refresh) add(f.rank, gl, gl, (size_t)gl * b, 4, true);
+        if (want_top) add(top, R, R, (size_t)R * b, 4, true);
+        if (strideA) {
+            add(f.A, (long long)N * Gr, strideA, dict_elems(strideA, (size_t)N * Gr, b), 16, f.host);
+            add(GA, (long long)Gr * Gr, (long long)Gr * Gr, (size_t)Gr * Gr * b, 16, true);
+        }
+        if (strideB) {
+            add(f.B, (long long)G2 * M, strideB, dict_elems(strideB, (size_t)G2 * M, b), 16, f.host);
+            add(GB, (long long)G2 * G2, (long long)G2 * G2, (size_t)G2 * G2 * b, 16, true);
+        }
     }));
-    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
+    static_assert(sizeof(Par64) == 5 * sizeof(double), "the gather moves a Par64 as five doubles");
+    JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp and tol are read from the host: copied before the call returns on any path)
 
-    if (!sin) JSTSP_HIP(hipMemsetAsync(V, 0, g * sizeof(double2), st));
+    if (!sin) JSTSP_HIP(hipMemsetAsync(V, 0, g1 * batch * sizeof(double2), st));
     JSTSP_TRY(f.begin(st));
     if (sin) JSTSP_TRY(f.load_state(st, sin, V, S));               // (state_out may be state_in: read whole before anything is written)
     const long long sNM = (long long)f.nm1(), sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
-    const Mat64 Am = f.Am(), Bm = f.Bm(), GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
     double2 *T = f.T, *gws = f.gws;
-    JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, Am, Am, GA, (long long)Gr * Gr, Gr, gws));          // G_A = A^H A
-    JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, Bm, Bm, GB, (long long)G2 * G2, G2, gws));          // G_B = B B^H
+    JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, f.Am(), f.Am(), GA, (long long)Gr * Gr, Gr, gws));      // G_A = A^H A
+    JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, f.Bm(), f.Bm(), GB, (long long)G2 * G2, G2, gws));      // G_B = B B^H
+    if (un) {
+        hipLaunchKernelGGL(until_init64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch,
+                           f.want_ce() ? (long long)3 * Imax * batch : 0ll, map, flag, f.ced);
+        f.map = map; f.flag = flag;
+    }
     bool in_force = f.angles();                                     // a rank masks S: that of indx_S, then that of the last refresh
+    bool listed = false;                                            // the call has run a refresh: `top` holds a list
     for (int it = 0; it < Imax; ++it) {
         const bool fresh = rf && rf->at((long long)it0 + it + 1);
+        const int batch = f.batch;                                  // the trials still in the loop (the call's batch without a rule)
+        const size_t g = g1 * batch;
+        const Mat64 Am = f.Am(), Bm = f.Bm(), GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
         JSTSP_TRY(f.head(st));
         JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, M, N, batch, Am, Mat64{f.K, sNM, N}, T, (long long)Gr * M, Gr, gws));      // A^H K
         JSTSP_TRY(zgemm64(st, 'N', 'C', Gr, G2, M, batch, Mat64{T, (long long)Gr * M, Gr}, Bm, Res, sG, Gr, gws));     // ... B^H
@@ -454,15 +681,55 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, Gr, batch, GAm, Mat64{Res, sG, Gr}, T2, sG, Gr, gws));                 // G_A Res
         JSTSP_TRY(zgemm64(st, 'N', 'N', Gr, G2, G2, batch, Mat64{T2, sG, Gr}, GBm, RRes, sG, Gr, gws));                // ... G_B
         hipLaunchKernelGGL(step_v64_kernel, dim3(batch), dim3(256), 0, st, (int)g1, f.par, Res, RRes, V, S,
-                           in_force && !fresh ? f.rank : (const int32_t *)nullptr, f.mask_count(it0 + it), f.want_ce() ? f.ce3 : nullptr);
+                           in_force && !fresh ? f.rank : (const int32_t *)nullptr, f.mask_count(it0 + it), f.want_ce() || un ? f.ce3 : nullptr);
         if (fresh) {                                                // the order of the new v, and S again under it
             hipLaunchKernelGGL(support_top_kernel<double2>, dim3(batch), dim3(ST_THREADS), 0, st, (int)g1, R, V, top, f.rank);
             hipLaunchKernelGGL(soft_mask64_kernel, egrid((long long)g1, batch), dim3(256), 0, st, (long long)g1, f.par, V, S, f.rank,
                                f.mask_count(it0 + it));
-            in_force = true;
+            in_force = listed = true;
         }
         JSTSP_TRY(f.tail(st, S, it));
+        if (!un) continue;
+        // ---- the stopping rule: test, capture what has just stopped, and every `check` iterations compact the survivors ----
+        const bool last = it == Imax - 1;
+        if (!rule_on && !last) continue;                            // no trial can stop before the last iteration
+        hipLaunchKernelGGL(until_test64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, it + 1, un->min_iters, (int)last, f.ce3, tolp, map,
+                           flag, itd, c3d);
+        // (few workgroups per slot: in most iterations every one of them only reads its flag)
+        hipLaunchKernelGGL(until_capture64_kernel, dim3(std::min(egrid((long long)std::max(f.nm1(), g1), 1).x, 64u), batch), dim3(256), 0, st, sNM, sG, R,
+                           State64{{f.X, f.V1, f.V2, f.Cm, V, S}}, f.Y, top, (int)listed, flag, map, f.Sd, Y_out ? f.Yd : (double2 *)nullptr, sout,
+                           top_out);
+        JSTSP_HIP(hipGetLastError());
+        if (last || (it + 1) % un->check) continue;
+        int32_t left = 0;                                           // the one number that comes back, once per `check` iterations
+        hipLaunchKernelGGL(until_compact64_kernel, dim3(1), dim3(ST_THREADS), 0, st, batch, flag, newslot, count);
+        JSTSP_HIP(hipMemcpyAsync(&left, count, sizeof left, hipMemcpyDeviceToHost, st));
+        JSTSP_HIP(hipStreamSynchronize(st));
+        if (left == 0) break;                                       // every trial has stopped and is captured
+        if ((batch - left) * UNTIL_GATHER_SHARE < batch) continue;  // too few have stopped to pay for moving the others
+        Gather64 gt;
+        gt.cnt = 0;
+        for (const Shadow64 &q : sh) gt.it[gt.cnt++] = q.item();
+        hipLaunchKernelGGL(until_gather64_kernel, egrid((long long)std::max(f.nm1(), g1), batch), dim3(256), 0, st, gt, newslot);
+        JSTSP_HIP(hipGetLastError());
+        for (Shadow64 &q : sh) q.swap();
+        JSTSP_HIP(hipMemsetAsync(flag, 0, (size_t)left * sizeof(int32_t), st));
+        f.map = map; f.batch = f.sv.batch = left;
     }
+    if (un) {                                       // every trial was captured into the outputs at its own last iteration
+        if (f.host) {
+            JSTSP_TRY(s.copy_back(un->iters_out, itd, (size_t)batch));
+            if (c3d) JSTSP_TRY(s.copy_back(un->ce3_out, c3d, (size_t)batch));
+            if (top_out) JSTSP_TRY(s.copy_back(rf->indx_out, top_out, (size_t)R * batch));
+            if (sout) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
+            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), f.Sd, g1 * batch));
+            if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), f.Yd, f.nm1() * batch));
+            if (f.want_ce()) JSTSP_TRY(s.copy_back(ce_out, f.ced, (size_t)3 * Imax * batch));
+            JSTSP_HIP(hipStreamSynchronize(st));
+        }
+        return 0;
+    }
+    const size_t g = g1 * batch;
     JSTSP_HIP(hipMemcpyAsync(f.Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
     if (sout) JSTSP_TRY(f.store_state(st, sout, V, S));
     if (sout && f.host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
@@ -671,6 +938,21 @@ int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
     return admm64_approx(ctx, "proposed_algorithm refresh (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_,
                          strideA, B_, strideB, Imax, tau_Y, tau_S, rho, JSTSP_TYPE_APPROXIMATE, indx_S_, S_out, Y_out, ce_out, it0, state_in,
                          state_out, memspace, &rf);
+}
+
+// Alg. 2 that stops each trial when its own iterate has settled (Until64 above); refresh_period < 0: no support policy
+int jstsp_proposed_until_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
+                             const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
+                             const double *tau_S, const double *rho, const int32_t *indx_S_, int n_indx, int refresh_start, int refresh_period,
+                             const double *tol, int min_iters, int check, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, int it0,
+                             const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out, int32_t *iters_out, double *ce3_out, int memspace)
+{
+    const bool policy = refresh_period >= 0;
+    const Refresh64 rf{n_indx, refresh_start, refresh_period, indx_out};
+    const Until64 un{tol, min_iters, check, iters_out, ce3_out, policy ? 0 : n_indx};
+    return admm64_approx(ctx, "proposed_algorithm until (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA,
+                         B_, strideB, Imax, tau_Y, tau_S, rho, JSTSP_TYPE_APPROXIMATE, indx_S_, S_out, Y_out, ce_out, it0, state_in, state_out,
+                         memspace, policy ? &rf : nullptr, &un);
 }
 
 int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,

@@ -880,11 +880,14 @@ TRACKING_PAI_MODES = ("pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm
 _PREV_MODES = ("pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev", "pai_prev_refresh")
 _WIDE_MODES = ("pai_wide_prev", "warm_pai_wide_prev")
 _REFRESH_MODES = ("refresh", "warm_refresh", "pai_prev_refresh")      # float64 only: proposed_algorithm_refresh_f64
+# float64 only, with stop=(tol, min_iters): one solve per frame at cold_imax by proposed_algorithm_until_f64, each trial stopped
+# when its iterate has settled
+TRACKING_UNTIL_MODES = ("cold_until", "warm_until", "refresh_until", "warm_refresh_until")
 
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
                  precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
-                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False):
+                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False, stop=None):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -912,6 +915,11 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
       pai_prev_refresh  from zero, ``support_order_f64`` of the chain's previous S in force until the first refresh
     ``refresh_f32=True`` (``precision="f32"`` only) runs these three through the fp32 solver instead, by
     ``proposed_algorithm_refresh`` with ``support_order`` for the prior; without it ``precision="f32"`` refuses them as before.
+    and (``precision="f64"`` only, selected by ``stop = (tol, min_iters)`` or ``stop = tol``) the stopping
+    rule of ``proposed_algorithm_until_f64``: ONE solve per frame with ``Imax = cold_imax``, each trial stopped at its own iteration:
+      cold_until, warm_until                  ``cold`` / ``warm`` with the rule
+      refresh_until, warm_refresh_until       ``refresh`` / ``warm_refresh`` with the rule
+    Their results also carry ``mean_iters``, ``median_iters``, ``max_iters`` and ``mean_iters_by_frame`` over the scored frames.
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
@@ -931,8 +939,22 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         raise ValueError("corr must lie in [0, 1], not %r" % (corr,))
     if precision not in ("f64", "f32"):
         raise ValueError("precision must be 'f64' or 'f32', not %r" % (precision,))
-    if not modes or any(m not in TRACKING_MODES + TRACKING_PAI_MODES for m in modes) or not imax or min(imax + [int(cold_imax)]) < 1:
-        raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (TRACKING_MODES + TRACKING_PAI_MODES,))
+    every = TRACKING_MODES + TRACKING_PAI_MODES + TRACKING_UNTIL_MODES
+    if not modes or any(m not in every for m in modes) or not imax or min(imax + [int(cold_imax)]) < 1:
+        raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (every,))
+    until = [m for m in TRACKING_UNTIL_MODES if m in modes]
+    stop_tol = stop_min = None
+    if until:
+        if precision != "f64":
+            raise ValueError("the modes %r stop inside the float64 solver: precision must be 'f64'" % (TRACKING_UNTIL_MODES,))
+        if stop is None:
+            raise ValueError("the modes %r need stop=(tol, min_iters)" % (TRACKING_UNTIL_MODES,))
+        try:
+            stop_tol, stop_min = (float(stop[0]), int(stop[1])) if np.ndim(stop) else (float(stop), 2)
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("stop must be tol or a pair (tol, min_iters), not %r" % (stop,)) from None
+        if not stop_tol > 0.0 or stop_min < 1:
+            raise ValueError("stop = %r: need tol > 0 and min_iters >= 1" % (stop,))
     if drift is not None:
         drift = float(drift)
         if not (np.isfinite(drift) and drift >= 0.0):
@@ -971,14 +993,16 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     order = J.support_order_f64 if f64 else J.support_order
     order_wide = J.support_order_wide_f64 if f64 else J.support_order_wide
     keys = [("cold", i) for i in sorted(set(imax + [int(cold_imax)])) if "cold" in modes] + \
-           [(m, i) for m in ("warm", "warm_vs") + TRACKING_PAI_MODES if m in modes for i in imax]
+           [(m, i) for m in ("warm", "warm_vs") + TRACKING_PAI_MODES if m in modes for i in imax] + [(m, int(cold_imax)) for m in until]
     frame_kw = {} if drift is None else {"drift": drift}
     err = {k: [] for k in keys}                                     # per chunk: (scored frames, chunk) on the host
     secs = {k: 0.0 for k in keys}
+    its = {k: [] for k in keys if k[0] in until}                    # per chunk: iterations, (scored frames, chunk) on the host
     for t0 in range(0, n_seqs, batch):
         nb = min(batch, n_seqs - t0)
         state, prev_S = {}, {}
         e_dev = {k: [] for k in keys}
+        i_dev = {k: [] for k in its}
         for f in range(n_frames):
             inp = build_trials(p, t0, nb, seed=seed, sweep_idx=sweep_idx, device=device, frame=f, corr=corr, **frame_kw)
             args = (wide(inp["subY"]), J.colmajor(inp["Omega"].to(torch.float64)) if f64 else inp["Omega"], wide(inp["A"]),
@@ -987,7 +1011,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
             zb = wide(inp["Zbar"])
             for k in keys:
                 mode, n_it = k
-                warm = mode in ("warm", "warm_vs", "warm_pai_prev", "warm_pai_wide_prev", "warm_refresh")
+                warm = mode in ("warm", "warm_vs", "warm_pai_prev", "warm_pai_wide_prev", "warm_refresh", "warm_until", "warm_refresh_until")
                 st = state.get(k) if warm else None
                 if st is not None and mode == "warm_vs":
                     st = st.clone()
@@ -1001,7 +1025,11 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                     ix = {"indx_S": order(prev_S[k])}               # (not timed: the solver's rate is what estimates_per_s reports)
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
-                if mode in _REFRESH_MODES:
+                if mode in until:
+                    S, _, _, out, _, n_ran, _ = J.proposed_algorithm_until_f64(
+                        *args, n_it, *prm, tol=stop_tol, min_iters=stop_min, refresh=(r_start, r_period) if "refresh" in mode else None,
+                        state=st, return_state=warm)
+                elif mode in _REFRESH_MODES:
                     S, _, _, out, _ = solve_refresh(*args, n_it, *prm, start=r_start, period=r_period, want_ce=False, state=st,
                                                     return_state=warm, **ix)
                 else:
@@ -1015,16 +1043,25 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 if f:
                     secs[k] += dt
                     e_dev[k].append(torch.as_tensor(score(S, zb)).double())
+                    if mode in until:
+                        i_dev[k].append(n_ran)
         for k in keys:
             err[k].append(torch.stack(e_dev[k]).cpu().numpy())
+        for k in its:
+            its[k].append(torch.stack(i_dev[k]).cpu().numpy())
 
     def summary(k):
         e = np.concatenate(err[k], axis=1)                          # (scored frames, seqs)
         per_seq = e.mean(axis=0)
-        return {"mode": k[0], "Imax": k[1], "mean_nmse": float(e.mean()),
-                "sem_over_seqs": float(per_seq.std(ddof=1) / np.sqrt(len(per_seq))) if len(per_seq) > 1 else None,
-                "median_nmse": float(np.median(e)), "mean_nmse_by_frame": [float(x) for x in e.mean(axis=1)],
-                "estimates_per_s": n_seqs * (n_frames - 1) / secs[k]}
+        out = {"mode": k[0], "Imax": k[1], "mean_nmse": float(e.mean()),
+               "sem_over_seqs": float(per_seq.std(ddof=1) / np.sqrt(len(per_seq))) if len(per_seq) > 1 else None,
+               "median_nmse": float(np.median(e)), "mean_nmse_by_frame": [float(x) for x in e.mean(axis=1)],
+               "estimates_per_s": n_seqs * (n_frames - 1) / secs[k]}
+        if k in its:
+            n = np.concatenate(its[k], axis=1)                      # (scored frames, seqs)
+            out.update(mean_iters=float(n.mean()), median_iters=float(np.median(n)), max_iters=int(n.max()),
+                       mean_iters_by_frame=[float(x) for x in n.mean(axis=1)])
+        return out
 
     res = {"tool": "run_tracking", "precision": precision, "shape": [N, M, Gr, G2], "frames": n_frames, "seqs": n_seqs, "corr": corr,
            "clusters": p.clusters, "rays": p.rays, "snr_db": p.snr_db, "seed": seed, "scored_frames": list(range(1, n_frames)),
@@ -1033,7 +1070,9 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         res["drift"] = drift
     if any(m in _WIDE_MODES for m in modes):
         res["widen"], res["widen_primary"] = [wr, wt], widen_primary
-    if any(m in _REFRESH_MODES for m in modes):
+    if until:
+        res["stop"] = [stop_tol, stop_min]
+    if any(m in _REFRESH_MODES for m in modes) or any("refresh" in m for m in until):
         res["refresh"] = [r_start, r_period]
         if refresh_f32:
             res["refresh_f32"] = True

@@ -975,6 +975,18 @@ def _f64_admm_bytes(N, M, Gr, G2, sA, sB, std, own_PA, own_PB, host, resumed, *,
     return per
 
 
+def _f64_until_bytes(N, M, Gr, G2, sA, sB, host):
+    """Bytes per trial of a ``proposed_algorithm_until_f64`` call: the refreshed, resumed Alg. 2 call of :func:`_f64_admm_bytes` plus
+    what the stopping rule's compaction adds (csrc/proposed64.hip, Shadow64) - a second copy of X, V1, V2, C, A S B, v, S and the
+    rank, one of subY, Omega and a per-trial dictionary (two for a device call: the caller's own arrays are never written), the
+    Grams of a per-trial dictionary, the order by slot and its shadow, and the small per-trial arrays."""
+    g, twice = Gr * G2, 1 if host else 2
+    per = _f64_admm_bytes(N, M, Gr, G2, sA, sB, False, True, True, host, True, refresh=True)
+    per += 16 * (5 * N * M + 2 * g) + 24 * N * M * twice + 4 * g + 8 * min(g, _lib.SUPPORT_TOP_MAX) + 1024
+    per += 16 * ((N * Gr * twice + Gr * Gr if sA else 0) + (G2 * M * twice + G2 * G2 if sB else 0))
+    return per
+
+
 def _admm_f64(std, resumed, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, tcode, indx_S, PA, PB, want_ce, info, ctx, state=None, it0=0,
               return_state=False):
     """The frame of the four float64 ``proposed_algorithm`` functions: Alg. 1 (``std``) or Alg. 2, through the plain C entry or -
@@ -1131,6 +1143,51 @@ def proposed_algorithm_refresh_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *
             it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16), _off(p_ord, t0 * R, 4), mem), name)
     del keep_in
     return q.result() + (st_out, order)
+
+
+# ----------------------------------------------------------------------------- float64 solver, each trial stopped when it has settled
+def proposed_algorithm_until_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, tol, min_iters=2, check=1, indx_S=None, refresh=None,
+                                 state=None, it0=0, want_ce=False, return_state=True, type="approximate", ctx=None):
+    """:func:`proposed_algorithm_refresh_f64` - with ``refresh=None`` :func:`proposed_algorithm_resume_f64` - with a stopping rule
+    (include/jstsp.h: jstsp_proposed_until_f64): trial ``t`` stops after the first iteration ``i`` of the call
+    with ``i >= min_iters`` and ``convergence_error[i, 2] = |v_i - v_{i-1}|^2 / |v_{i-1}|^2 <= tol[t]``, failing that after ``Imax``.
+    ``tol``: a scalar or ``(batch,)``; an entry that is zero, negative or NaN never stops its trial.  ``refresh``: ``None`` or
+    ``(start, period)``.  ``check``: the iterations between two compactions of the batch, each of which reads one number back; it
+    never changes a result (the default is the fastest measured at BASELINE configs[1]: DESIGN.md section 9t).  Returns ``(S, Y, ce, state, order, iters, ce3)``: the first five as the sibling's for every trial
+    alone over ``iters[t]`` iterations (bit for bit for ``min(N, M) <= 64``); rows of ``ce`` after ``iters[t]`` are NaN; a row of
+    ``order`` is all zeros for a trial that stopped before its first refresh; ``iters`` int32 ``(batch,)`` and ``ce3`` float64
+    ``(batch,)`` - the last iteration's ``ce[:, 2]`` - live where the inputs live.  The rule is memoryless, so an unstopped trial
+    (``iters[t] == Imax`` and ``ce3[t] > tol[t]``) is resumed by a later call with ``state`` and ``it0``.  Alg. 2 only."""
+    if type != "approximate":
+        raise ValueError("type must be 'approximate': the stopping rule reads the gradient step of Alg. 2")
+    min_iters, check_every, it0, Imax = int(min_iters), int(check), int(it0), int(Imax)
+    if min_iters < 1 or check_every < 1:
+        raise ValueError("min_iters and check must be >= 1, not %r and %r" % (min_iters, check_every))
+    if refresh is None:
+        start, period = it0 + max(Imax, 0), 0               # (for the checks below: a schedule that never refreshes in this call)
+    else:
+        start, period = refresh
+    q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord = _refresh_open(
+        np.complex128, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, start, period, indx_S, want_ce, ctx, state, it0, return_state)
+    if refresh is None:
+        start, period = 0, -1
+    N, M, Gr, G2, batch, Imax, sA, sB, mem = q.N, q.M, q.Gr, q.G2, q.batch, q.Imax, q.sA, q.sB, q.mem
+    tl, _ = _scalars(tol, batch, "tol")
+    g, ne, R = Gr * G2, admm_state_elems(N, M, Gr, G2), min(Gr * G2, _lib.SUPPORT_TOP_MAX)
+    p_it, iters = _vec_out(mem == DEVICE, batch, np.int32, q.dev)
+    p_c3, ce3 = _vec_out(mem == DEVICE, batch, np.float64, q.dev)
+    per = _f64_until_bytes(N, M, Gr, G2, sA, sB, mem == HOST)
+    dp = C.POINTER(C.c_double)
+    name = "jstsp_proposed_until_f64"
+    for t0, nb in _f64_chunks(batch, per):
+        _lib.check(getattr(q.ctx._lib, name)(
+            q.ctx.handle, N, M, Gr, G2, nb, _off(q.sub.ptr, t0 * N * M, 16), _off(q.om.ptr, t0 * N * M, 8), _off(q.A.ptr, t0 * sA, 16), sA,
+            _off(q.B.ptr, t0 * sB, 16), sB, Imax, q.tY[t0:].ctypes.data_as(dp), q.tS[t0:].ctypes.data_as(dp), q.rh[t0:].ctypes.data_as(dp),
+            _off(q.ix.ptr, t0 * n, 4), n, start, period, tl[t0:].ctypes.data_as(dp), min_iters, check_every,
+            _off(q.pS, t0 * g, 16), _off(q.pY, t0 * N * M, 16), _off(q.pce, t0 * 3 * Imax, 8),
+            it0, _off(p_in, t0 * ne, 16), _off(p_out, t0 * ne, 16), _off(p_ord, t0 * R, 4), _off(p_it, t0, 4), _off(p_c3, t0, 8), mem), name)
+    del keep_in
+    return q.result() + (st_out, order, iters, ce3)
 
 
 def svt_f64(Y, tau, *, ctx=None):

@@ -31,6 +31,10 @@ inside the loop (proposed_algorithm_refresh_f64) - from zero, from the previous 
 chain's previous estimate in force until the first refresh: --refresh START,PERIOD, a refresh at the iterations i > START with
 (i - START - 1) % PERIOD == 0, PERIOD 0 for the one refresh at START + 1 (default: 0,1, every iteration).  With --precision f32,
 --refresh-f32 runs the three on the fp32 solver (proposed_algorithm_refresh).
+cold_until, warm_until, refresh_until and warm_refresh_until (float64 only) are cold, warm, refresh and
+warm_refresh with the stopping rule of proposed_algorithm_until_f64: --stop TOL[,MIN] stops each trial after its first iteration
+i >= MIN (default 2) with |v_i - v_{i-1}|^2 / |v_{i-1}|^2 <= TOL; one solve per frame at --cold-imax, and the result also carries
+the mean, median and largest number of iterations.  --stop without --modes runs these four.
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -61,8 +65,8 @@ ap.add_argument("--drift", type=float, default=None, metavar="SIGMA",
                 help="--device-channel: random walk of every path angle, SIGMA rad per frame (default: fixed angles)")
 ap.add_argument("--modes", nargs="+", default=None,
                 choices=("cold", "warm", "warm_vs", "pai", "pai_prev", "warm_pai_prev", "pai_wide_prev", "warm_pai_wide_prev", "refresh",
-                         "warm_refresh", "pai_prev_refresh"),
-                help="--device-channel: the columns to run (default: cold warm warm_vs)")
+                         "warm_refresh", "pai_prev_refresh", "cold_until", "warm_until", "refresh_until", "warm_refresh_until"),
+                help="--device-channel: the columns to run (default: cold warm warm_vs; with --stop the four *_until modes)")
 ap.add_argument("--widen", default=None, metavar="WR,WT",
                 help="--device-channel: the radii of pai_wide_prev / warm_pai_wide_prev in grid cells (default: 1,1)")
 ap.add_argument("--widen-primary", choices=("neighbourhood", "ties"), default=None,
@@ -71,7 +75,21 @@ ap.add_argument("--refresh", default=None, metavar="START,PERIOD",
                 help="--device-channel: the refresh schedule of refresh / warm_refresh / pai_prev_refresh (default: 0,1)")
 ap.add_argument("--refresh-f32", action="store_true",
                 help="--device-channel --precision f32: the refresh modes on the fp32 solver (proposed_algorithm_refresh)")
+ap.add_argument("--stop", default=None, metavar="TOL[,MIN]",
+                help="--device-channel: the stopping rule of the *_until modes (tolerance and, default 2, the fewest iterations)")
 a = ap.parse_args()
+if a.stop is not None:
+    if not a.device_channel:
+        ap.error("--stop needs --device-channel")
+    try:
+        parts = a.stop.split(",")
+        a.stop = (float(parts[0]), int(parts[1]) if len(parts) > 1 else 2)
+    except ValueError:
+        a.stop = (0.0, 0)
+    if len(parts) > 2 or not a.stop[0] > 0.0 or a.stop[1] < 1:
+        ap.error("--stop takes TOL > 0 and optionally MIN >= 1 as TOL[,MIN]")
+    if a.modes is None:
+        a.modes = ["cold_until", "warm_until", "refresh_until", "warm_refresh_until"]
 if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None or a.refresh is not None
         or a.refresh_f32) and not a.device_channel:
     ap.error("--drift, --modes, --widen, --widen-primary, --refresh and --refresh-f32 need --device-channel")
@@ -111,6 +129,8 @@ if a.device_channel:
         kw["refresh"] = a.refresh
     if a.refresh_f32:
         kw["refresh_f32"] = True
+    if a.stop is not None:
+        kw["stop"] = a.stop
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
