@@ -1345,6 +1345,59 @@ int jstsp_proposed_refresh_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
                                int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out,
                                int32_t *indx_out, int memspace);
 
+/* ---- the fp32 ADMM that stops each trial when its iterate has settled (csrc/proposed.hip, csrc/until.hip) ----
+ * jstsp_proposed_refresh_c32 (refresh_period < 0: no support policy, the body of jstsp_proposed_resume_c32; indx_S then has n_indx
+ * entries per trial, 0 meaning Gr*G2) with the stopping rule of jstsp_proposed_until_f64 above, word for word: THE RULE, tol
+ * (batch doubles on the host; zero, negative or NaN never stops), min_iters, iters_out (required), ce3_out (optional) and what
+ * S_out, Y_out, state_out, indx_out and the rows of ce_out hold are described there.  What is the fp32 solver's own:
+ *  - type: JSTSP_TYPE_APPROXIMATE only; JSTSP_TYPE_STD is refused with JSTSP_E_UNSUPPORTED.
+ *  - ce(i, 3) is the double the gradient step's kernel writes per trial in one workgroup, in a fixed order; nothing new is summed.
+ *  - NO COMPACTION: a stopped trial runs on in its batch until every trial has stopped, and nothing it writes later is returned.
+ *    So neither `check` nor the other trials' tol can change a trial's result - to the bit - and what the rule saves is the
+ *    iterations after max(iters_out); the gap between mean and max is what a compaction would still buy.
+ *  - Mechanism, all on the context's main stream: after the gradient step (and a refresh's rewrite of S) one thread per trial
+ *    tests row i of ce(:, 3); the trials it has just stopped - all that still run, in the call's last iteration - are captured in
+ *    two halves, S, v, the order, Y, X, V1 in front of the synthesis (the pass at the end of the iteration overwrites X and V1
+ *    with those of i + 1) and V2, C behind it, into the caller's arrays (JSTSP_DEVICE) or their staging.  Under a live rule Y is
+ *    stored by every iteration instead of the last one only.  Every `check` >= 1 iterations one kernel counts the running trials,
+ *    the host reads that int with one synchronisation and leaves the loop at zero, after the main stream has waited for both side
+ *    streams; then the rows of ce_out after iters_out[t] are set to NaN.  The default of the Python wrapper is check = 1,
+ *    the fastest of 1, 2, 4, 8, 16 at BASELINE configs[1] (DESIGN.md section 9u has the measurement).
+ *  - a trial flagged by the fused pass AT THE ITERATION WHERE IT STOPPED is solved again from its state_in under the same rule
+ *    (a flag it raises later, running on, concerns iterations that are not returned).
+ *  - with no positive tol nothing is read back, Y is stored as in the sibling, and the call is the sibling on the bits with
+ *    iters_out = Imax.  No other entry passes a rule: their launches and bits are unchanged.
+ *  - against the sibling run for one trial alone with Imax = iters_out[t]: fp32-equivalent (within the fp32 solver's tolerances),
+ *    the order equal.  Measured per branch: the bits are equal on the three-kernel iteration and on a shape
+ *    without a pass, not behind a fused pass, where the sibling's last iteration ends in the unfused synthesis and the stopped
+ *    trial's in a pass.
+ *  - JSTSP_E_NULL: tol or iters_out NULL; JSTSP_E_ARG: min_iters < 1, check < 1; everything the siblings refuse.
+ * jstsp_proposed_until_c64 is the entry at the reference's element type, narrowed and widened as jstsp_proposed_refresh_c64.
+ * Asserted (tests/test_gpu_until32.py): iters against tests/until_ref.py on the window kernel, the general pass, JSTSP_FUSED=0 and
+ * an unfused shape, whose decisions keep a margin of 5e-2 (tests/test_until32_ref.py); values within the fp32 solver's tolerances
+ * of the reference and of the sibling; check 1, 3, 64, other trials' tol and duplicates on the bytes; tol <= 0 or NaN: the
+ * sibling's bytes; the early exit and the call after it; the re-solve; min_iters, warm starts, legs, a NaN trial; the refusals. */
+int jstsp_proposed_until_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                             const jstsp_c32 *subY, const float *Omega,
+                             const jstsp_c32 *A, long long strideA,
+                             const jstsp_c32 *B, long long strideB,
+                             int Imax, const double *tau_Y, const double *tau_S, const double *rho, int type,
+                             const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                             const double *tol, int min_iters, int check,
+                             jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out,
+                             int it0, const jstsp_c32 *state_in, jstsp_c32 *state_out, int32_t *indx_out,
+                             int32_t *iters_out, double *ce3_out, int memspace);
+int jstsp_proposed_until_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                             const jstsp_c64 *subY, const double *Omega,
+                             const jstsp_c64 *A, long long strideA,
+                             const jstsp_c64 *B, long long strideB,
+                             int Imax, const double *tau_Y, const double *tau_S, const double *rho, int type,
+                             const int32_t *indx_S, int n_indx, int refresh_start, int refresh_period,
+                             const double *tol, int min_iters, int check,
+                             jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                             int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out,
+                             int32_t *iters_out, double *ce3_out, int memspace);
+
 /* ---- joint OMP and matrix completion in float64 -----------------------------------------------------
  * The "OMP with MMV" column (plot_errorVSsnr.m:116-117) and the TSSR / "SVT-based" recipe (:151-162) evaluated in FLOAT64 on the
  * device - unlike jstsp_mmv_omp_c64 / jstsp_mc_svt_c64 / jstsp_mc_admm_c64, which narrow the same arrays to the fp32 kernels.

@@ -176,6 +176,11 @@ for _n in ("jstsp_proposed_refresh_c32", "jstsp_proposed_refresh_c64"):
     SIGNATURES[_n] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll,
                               c_void_p, c_ll, c_int, c_dp, c_dp, c_dp, c_int, c_void_p, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int])
+# the fp32 ADMM with a stopping rule (csrc/proposed.hip, csrc/until.hip, csrc/c64.hip): the refreshed entry's list with tol, min_iters,
+# check after refresh_period and iters_out, ce3_out before memspace
+for _n in ("jstsp_proposed_until_c32", "jstsp_proposed_until_c64"):
+    SIGNATURES[_n] = (c_int, SIGNATURES["jstsp_proposed_refresh_c32"][1][:21] + [c_dp, c_int, c_int]
+                      + SIGNATURES["jstsp_proposed_refresh_c32"][1][21:-1] + [c_void_p, c_void_p, c_int])
 
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes

@@ -350,6 +350,40 @@ int jstsp_proposed_refresh_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
     return cv.finish();
 }
 
+// jstsp_proposed_until_c32 at the reference's element type, as jstsp_proposed_refresh_c64 above: tol stays on the host, iters_out
+// (int32) and ce3_out (double) pass through unconverted
+int jstsp_proposed_until_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY, const double *Omega,
+                             const jstsp_c64 *A, long long strideA, const jstsp_c64 *B, long long strideB, int Imax, const double *tau_Y,
+                             const double *tau_S, const double *rho, int type, const int32_t *indx_S, int n_indx, int refresh_start,
+                             int refresh_period, const double *tol, int min_iters, int check, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
+                             int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out, int32_t *iters_out, double *ce3_out,
+                             int memspace)
+{
+    C64_BEGIN(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, "proposed_algorithm until");
+    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "proposed_algorithm until: NULL argument");
+    JSTSP_REQUIRE(tol && iters_out, JSTSP_E_NULL, "proposed_algorithm until: tol and iters_out are required");
+    const long long g = (long long)Gr * G2;
+    JSTSP_REQUIRE(n_indx >= 0 && (indx_S || n_indx == 0) && n_indx <= g, JSTSP_E_ARG,
+                  "proposed_algorithm until: n_indx = %d: need 0 <= n_indx <= Gr * G2 = %lld, and 0 without indx_S", n_indx, g);
+    AdmmProblem probe;                              // (the schedule: whether the call writes indx_out)
+    probe.policy = true; probe.start = refresh_start; probe.period = refresh_period; probe.it0 = it0; probe.Imax = Imax;
+    const bool writes_order = indx_out && refresh_start >= 0 && refresh_period >= 0 && it0 >= 0 && probe.runs_refresh();
+    const size_t nm = (size_t)N * M * batch, ne = (4 * (size_t)N * M + 2 * (size_t)g) * batch;
+    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch), *b = cv.in_dict(B, (size_t)G2 * M, strideB, batch),
+                    *si = cv.in(state_in, ne);
+    const float *om = cv.in_real(Omega, nm);
+    const int32_t *ix = cv.in_raw(indx_S, (size_t)(n_indx ? n_indx : g) * batch);
+    jstsp_c32 *s = cv.out(S_out, (size_t)g * batch), *yo = cv.out(Y_out, nm), *so = cv.out(state_out, ne);
+    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
+    int32_t *io = writes_order ? cv.out_raw(indx_out, std::min<size_t>((size_t)g, JSTSP_SUPPORT_TOP_MAX) * batch) : nullptr;
+    int32_t *itd = cv.out_raw(iters_out, (size_t)batch);
+    double *c3 = cv.out_raw(ce3_out, (size_t)batch);
+    JSTSP_TRY(cv.rc);
+    JSTSP_TRY(jstsp_proposed_until_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S, rho, type, ix, n_indx,
+                                       refresh_start, refresh_period, tol, min_iters, check, s, yo, ce, it0, si, so, io, itd, c3, JSTSP_DEVICE));
+    return cv.finish();
+}
+
 int jstsp_svt_c64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y, const double *tau, jstsp_c64 *X,
                   int memspace)
 {

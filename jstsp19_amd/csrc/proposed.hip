@@ -48,6 +48,7 @@ struct ProposedWS {
     int32_t *top = nullptr;         // the list of a support policy's last refresh
     bool toep_probed = false;
     FusedWS fw;
+    UntilWS un;                     // the stopping rule of jstsp_proposed_until_c32 (until.hip); empty for every other entry
 };
 
 // k-split of the fused three-Gram pass (hgram3_kernel: G_x, G_v1 and G_z from one read of X and V1): chunks of at most
@@ -75,6 +76,8 @@ struct AdmmPlan {
     bool host_compact; size_t compact_elems;      // a JSTSP_HOST dictionary uploaded as first block + leading columns (hostpack.hip)
     bool overlap, grad_fused;             // side streams; the fused launches of the gradient step (gradstep.hip)
     int toep_env, fused_kback;            // JSTSP_TOEPLITZ, JSTSP_FUSED_KBACK
+    bool until, live;                     // the call returns iters / ce3 (jstsp_proposed_until_c32); some tol is positive: trials can stop early
+    bool want_top;                        // a support policy whose call runs a refresh and whose list is wanted
     // -- after proposed_alloc --
     bool fz, explicit_c;                  // Y = Z - Q Z orientation: fused epilogues; the other one carries C as an operand
     bool hmax;                            // the epilogues also deliver max|X|, |V1|, |V2|, |Znext|: split-f16 Grams
@@ -110,6 +113,8 @@ static AdmmPlan make_plan(const AdmmProblem &p, const Tuning &tn, bool allow_fus
     // JSTSP_OVERLAP; by default the side streams are on where the work between two passes is three short independent chains
     pl.overlap = tn.overlap >= 0 ? tn.overlap != 0 : pl.want_fused;
     pl.grad_fused = tn.grad_fused != 0; pl.toep_env = tn.toeplitz; pl.fused_kback = tn.fused_kback;
+    pl.until = p.until(); pl.live = p.live();
+    pl.want_top = p.policy && p.indx_out && p.runs_refresh();
     return pl;
 }
 
@@ -168,6 +173,20 @@ static int proposed_alloc(Arena &a, ProposedWS &w, const AdmmProblem &p, const A
         }
     } else if (pl.h2g)
         w.pmax = a.get<uint32_t>(2 * batch);
+    if (pl.until) {
+        // the rule's per-trial words; under a live rule also where a stopped trial is captured: the caller's arrays, or - a host
+        // call - what finish_solve stages out in place of w.S / w.Y (the state and the order: setup_resumed, setup_scalars), and
+        // the list the loop's own refreshes go on writing
+        UntilWS &u = w.un;
+        u.flag = a.get<int32_t>(batch); u.iters = a.get<int32_t>(batch); u.left = a.get<int32_t>(1);
+        u.ce3 = a.get<double>(batch); u.tol = a.get<double>(batch); u.ovf = a.get<uint32_t>(batch);
+        if (pl.live) {
+            const bool host = p.memspace == JSTSP_HOST;
+            u.S = host ? a.get<float2>(batch * g) : as_f2(p.S_out);
+            u.Y = !p.Y_out ? nullptr : host ? a.get<float2>(batch * nm) : as_f2(p.Y_out);
+            if (pl.want_top) u.top_loop = a.get<int32_t>(batch * pl.R);
+        }
+    }
     JSTSP_REQUIRE(!a.overrun, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted");
     return 0;
 }
@@ -281,9 +300,14 @@ static int setup_scalars(jstsp_ctx *ctx, const AdmmProblem &p, const AdmmPlan &p
     JSTSP_HIP(hipMemsetAsync(w.ce, 0, (size_t)batch * 3 * pl.Imax1 * sizeof(double), st));   // ce(:,3) stays 0 for 'std' (:6)
     JSTSP_TRY(launch_inv_d(ctx, (long long)p.nm(), batch, w.Omega, 2.f, w.prm, w.invD));
     if (pl.angles) JSTSP_TRY(launch_rank_from_index(ctx, (int)p.g(), batch, w.indx_S, (int)p.listed(), w.rank));
-    if (p.policy && p.indx_out && p.runs_refresh()) {
+    if (pl.want_top) {
         w.top = p.memspace == JSTSP_DEVICE ? p.indx_out : ctx->arena.get<int32_t>((size_t)batch * pl.R);
         JSTSP_REQUIRE(w.top, JSTSP_E_NOMEM, "proposed_algorithm: workspace exhausted (refreshed order)");
+        if (pl.live) { w.un.top = w.top; w.top = w.un.top_loop; }      // a stopped trial's list is captured; the loop writes its own
+    }
+    if (pl.until) {
+        JSTSP_TRY(upload(ctx, w.un.tol, p.tol, batch * sizeof(double)));
+        JSTSP_TRY(launch_until_init(ctx, batch, w.un));
     }
     return 0;
 }
@@ -445,6 +469,7 @@ struct AdmmLoop {
     bool passed = false;                    // X, V1, k-partials of this iteration came from the previous pass
     bool rv_early = false;                  // R v of this iteration is being recomputed on s2 (issued by the previous iteration)
     bool in_force = pl.angles;              // a rank masks S
+    bool listed = false;                    // the call has run a refresh: w.top holds a list
     // of the iteration in progress
     int it = 0, apply_no = 0, cnt = 0;      // cnt: entries of the mask (angles)
     float2 *Zc = nullptr, *Zn = nullptr;
@@ -494,7 +519,7 @@ struct AdmmLoop {
             dq.e_r0 = w.V2; dq.e_r2 = w.Xs; dq.e_r3 = first_resumed ? w.subY1 : w.subY; dq.e_f0 = w.invD;
             dq.e_w3 = (it + 1 < Imax && (!pl.zfly || pl.fusedp)) ? Zn : nullptr;      // (the fused pass reads the stored Z)
             if (pl.zfly && it > 0) { dq.B = w.X; dq.B2 = w.V1; }      // Z = X - V1/rho in the panel loader (it == 0: Z = 0 in Zc)
-            dq.epi_store_c = (it + 1 == Imax);          // Y itself is only an output of the last iteration
+            dq.epi_store_c = (it + 1 == Imax) || pl.live;    // Y itself is only an output of a trial's last iteration
             if (pl.h2) {                                // max|K| for the split-f16 correlation, from the same epilogue
                 dq.amax_out = w.kmax;
                 if (N <= 64) { dq.amax_x = w.nmax; dq.amax_v1 = w.nmax + batch; dq.amax_z = w.zmax; }
@@ -665,8 +690,44 @@ struct AdmmLoop {
             // on s2 (ev_v) only reads V, as these two do; nothing else touches w.rank or w.S before the product.
             JSTSP_TRY(launch_support_top(ctx, (int)sg, batch, pl.R, w.V, w.top, w.rank, svt_split));
             JSTSP_TRY(launch_soft(ctx, (int)sg, batch, w.V, w.S, w.rank, cnt, w.prm));
-            in_force = true;
+            in_force = listed = true;
         }
+        return 0;
+    }
+
+    // -- the stopping rule of jstsp_proposed_until_c32 (until.hip; every other entry: not one launch).  All of it
+    //    on the main stream.  stop_test sits behind the gradient step - and behind a refresh's rewrite of S and the rank - and in
+    //    front of the synthesis: one thread per trial reads row it of ce(:, 3), and the trials it has just stopped (every running
+    //    one in the call's last iteration) are captured in two halves.  Here: S, v, the order, Y of this iteration - which a live
+    //    rule makes update_x and every pass store - and X, V1, which the pass at the end of this iteration overwrites with those
+    //    of it + 1; also the pass's overflow flag as it stands: a flag the trial raises later, running on, concerns only
+    //    iterations that are not returned (the pass of iteration it raises it for the k of it + 1; its V2 does not depend on the
+    //    k scale: fused.hip).  capture_tail, behind the synthesis: V2 (and C), which exist only there.
+    int stop_test(bool last)
+    {
+        JSTSP_TRY(launch_until_test(ctx, batch, it + 1, p.min_iters, last, w.ce, Imax, it, pl.fusedp ? w.fw.ovf : nullptr, w.un));
+        if (!pl.live) return 0;
+        return launch_until_capture_head(ctx, snm, sg, pl.R, batch, w.X, w.V1, w.Y, w.V, w.S, listed, w.un, w.sout);
+    }
+    int capture_tail()
+    {
+        if (!w.sout) return 0;
+        return launch_until_capture_tail(ctx, snm, sg, batch, w.V2, pl.explicit_c ? w.C : nullptr, w.un, w.sout);
+    }
+    // every `check` iterations: the one int the host reads, with one synchronisation of the main stream
+    int running(int *left)
+    {
+        JSTSP_TRY(launch_until_count(ctx, batch, w.un));
+        JSTSP_HIP(hipMemcpyAsync(left, w.un.left, sizeof(int), hipMemcpyDeviceToHost, sm));
+        JSTSP_HIP(hipStreamSynchronize(sm));
+        return 0;
+    }
+    // A loop that leaves before Imax leaves work on the side streams that reads the workspace (the norms and the early R v on s2,
+    // whatever s1 still holds): the main stream waits for both before anything is copied out or the next call reuses the arena.
+    int join_side_streams()
+    {
+        if (s1 != sm) { JSTSP_HIP(hipEventRecord(ev_x, s1)); JSTSP_HIP(hipStreamWaitEvent(sm, ev_x, 0)); }
+        if (s2 != sm) { JSTSP_HIP(hipEventRecord(ev_c, s2)); JSTSP_HIP(hipStreamWaitEvent(sm, ev_c, 0)); }
         return 0;
     }
 
@@ -708,7 +769,7 @@ struct AdmmLoop {
                          M, G2, batch, pl.fparts,
                          fw.Wqp, Zbuf[(it + 1) & 1], w.zmax,
                          (fw.v2 && pl.zfly) ? nullptr : Zbuf[it & 1],      // (window kernel: Z comes from the staged X, V1)
-                         (it + 2 == Imax) ? w.Y : nullptr, pl.fused_kback,
+                         (it + 2 == Imax || pl.live) ? w.Y : nullptr, pl.fused_kback,
                          fw.Ec, strideB ? fw.sEc : 0, fw.gt ? 31 - __builtin_clz((unsigned)fw.gt) : 0, fw.ecols, fw.ehalo,
                          fw.v2, fw.XsD, fw.Kf, w.omega_direct ? 1 : 0};
             JSTSP_TRY(launch_fused_pass(ctx, fd));
@@ -768,13 +829,27 @@ static int deferred_copy_out(jstsp_ctx *ctx, const PendingSolve &d, const AdmmPr
 static int finish_solve(jstsp_ctx *ctx, const AdmmProblem &p, const AdmmPlan &pl, ProposedWS &w, std::vector<int> *overflowed, PendingSolve *defer)
 {
     const int batch = p.batch, memspace = p.memspace;
-    const PendingSolve d{pl.want_ce && p.Imax > 0, w.S, w.Y, w.ce, pl.fusedp ? w.fw.ovf : nullptr};
+    // (under a live stopping rule every trial was captured at its own last iteration: S, Y, the order and the flags are the
+    //  captured ones - in a device call already in the caller's arrays - and the state is packed)
+    const bool live = pl.live;
+    const PendingSolve d{pl.want_ce && p.Imax > 0, live ? w.un.S : w.S, live ? w.un.Y : w.Y, w.ce,
+                         pl.fusedp ? (live ? w.un.ovf : w.fw.ovf) : nullptr};
     if (defer) { *defer = d; return 0; }
-    JSTSP_TRY(deferred_copy_out(ctx, d, p));
-    if (w.top && memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, p.indx_out, w.top, (size_t)batch * pl.R, memspace));
+    if (live && d.want_ce) JSTSP_TRY(launch_until_mask_ce(ctx, batch, p.Imax, w.un, w.ce));
+    if (live && memspace == JSTSP_DEVICE) {
+        if (d.want_ce) JSTSP_TRY(stage_out(ctx, p.ce_out, d.dce, (size_t)batch * 3 * p.Imax, memspace));
+    } else
+        JSTSP_TRY(deferred_copy_out(ctx, d, p));
+    const int32_t *top = live ? w.un.top : w.top;
+    if (top && memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, p.indx_out, top, (size_t)batch * pl.R, memspace));
     if (w.sout) {
-        JSTSP_TRY(launch_resume_pack(ctx, (long long)p.nm(), (long long)p.g(), batch, w.X, w.V1, w.V2, pl.explicit_c ? w.C : nullptr, w.V, w.S, w.sout));
+        if (!live)
+            JSTSP_TRY(launch_resume_pack(ctx, (long long)p.nm(), (long long)p.g(), batch, w.X, w.V1, w.V2, pl.explicit_c ? w.C : nullptr, w.V, w.S, w.sout));
         if (memspace == JSTSP_HOST) JSTSP_TRY(stage_out(ctx, as_f2(p.state_out), w.sout, batch * p.state_elems(), memspace));
+    }
+    if (pl.until) {
+        JSTSP_TRY(stage_out(ctx, p.iters_out, (const int32_t *)w.un.iters, (size_t)batch, memspace));
+        JSTSP_TRY(stage_out(ctx, p.ce3_out, (const double *)w.un.ce3, (size_t)batch, memspace));
     }
     if (d.ovf && overflowed) JSTSP_TRY(read_flagged_trials(ctx, d.ovf, batch, overflowed));
     if (memspace == JSTSP_HOST) {
@@ -810,20 +885,30 @@ static int proposed_impl(jstsp_ctx *ctx, const AdmmProblem &p, bool allow_fused,
     // convergence_error(:,1:2): lambda_max of three Grams per trial and iteration, each warm-started from its own Ritz vector
     // of the previous iteration (eig2.hip); the record starts empty
     if (pl.want_ce) JSTSP_TRY(lanczos_warm_reset(ctx, w.gn));
+    bool left_early = false;            // a live stopping rule: every trial had stopped before Imax
     for (int it = 0; it < p.Imax; ++it) {
+        const bool last = it + 1 == p.Imax;
         JSTSP_TRY(L.begin(it));
         JSTSP_TRY(L.update_x());
         if (it + 1 < p.Imax) JSTSP_TRY(L.side_chain(L.svt_split ? 1 : 0));
         JSTSP_TRY(L.gram_xv());
         JSTSP_TRY(L.correlate());
         JSTSP_TRY(pl.approx ? L.gradient_step() : L.least_squares_step());
+        if (pl.until && (pl.live || last)) JSTSP_TRY(L.stop_test(last));
         // (the last iteration of a two-output call on the fused path: Xs only feeds X, V2 and convergence_error, none of which
         //  is returned - S is final, Y was stored by the last pass; a call that returns its state needs the last V2)
         if (L.xs_unused()) break;
         JSTSP_TRY(L.synthesize());
         if (pl.want_ce) JSTSP_TRY(L.norms());
+        if (!pl.live) continue;
+        JSTSP_TRY(L.capture_tail());
+        if (last || (it + 1) % p.check) continue;
+        int left = 0;
+        JSTSP_TRY(L.running(&left));
+        if (left == 0) { left_early = true; break; }
     }
-    if (pl.want_ce && p.Imax > 0) JSTSP_HIP(hipStreamWaitEvent(L.sm, L.ev_ce, 0));
+    if (left_early) JSTSP_TRY(L.join_side_streams());
+    else if (pl.want_ce && p.Imax > 0) JSTSP_HIP(hipStreamWaitEvent(L.sm, L.ev_ce, 0));
     return finish_solve(ctx, p, pl, w, overflowed, defer);
 }
 
@@ -991,6 +1076,47 @@ extern "C" int jstsp_proposed_refresh_c32(jstsp_ctx *ctx, int N, int M, int Gr, 
     AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
                   it0, state_in, state_out, memspace};
     p.policy = true; p.n_indx = n_indx; p.start = refresh_start; p.period = refresh_period; p.indx_out = indx_out;
+    return resumed_solve(ctx, nmf, p);
+}
+
+// ---- resumed, each trial stopped when its iterate has settled (include/jstsp.h) ------------------------------
+// jstsp_proposed_refresh_c32 - with refresh_period < 0 jstsp_proposed_resume_c32 - with the stopping rule in its problem record
+// (solver_common.h; AdmmLoop::stop_test says what runs where).  A flagged trial is solved again under the same rule.
+extern "C" int jstsp_proposed_until_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
+                                        const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
+                                        const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S, int n_indx,
+                                        int refresh_start, int refresh_period, const double *tol, int min_iters, int check, jstsp_c32 *S_out,
+                                        jstsp_c32 *Y_out, double *ce_out, int it0, const jstsp_c32 *state_in, jstsp_c32 *state_out,
+                                        int32_t *indx_out, int32_t *iters_out, double *ce3_out, int memspace)
+{
+    const char *nmf = "proposed_algorithm until";
+    const bool policy = refresh_period >= 0;
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: ctx is NULL", nmf);
+    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace %d", nmf, memspace);
+    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
+    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31), JSTSP_E_SHAPE, "%s: Gr * G2 = %lld exceeds 2^31 - 1", nmf, (long long)Gr * G2);
+    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE(tol && iters_out, JSTSP_E_NULL, "%s: tol and iters_out are required", nmf);
+    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
+    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
+                  "%s: the rule reads the gradient step of Alg. 2; 'std' recomputes v by least squares and has none: use jstsp_proposed_resume_c32", nmf);
+    JSTSP_REQUIRE(min_iters >= 1 && check >= 1, JSTSP_E_ARG, "%s: min_iters = %d, check = %d: both must be at least 1", nmf, min_iters, check);
+    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf, it0, Imax);
+    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, it0);
+    JSTSP_REQUIRE(!policy || refresh_start >= 0, JSTSP_E_ARG, "%s: refresh_start = %d: may not be negative (refresh_period < 0: no policy)", nmf,
+                  refresh_start);
+    const long long g = (long long)Gr * G2;
+    if (policy)
+        JSTSP_REQUIRE(indx_S ? n_indx >= 1 && n_indx <= g : n_indx == 0, JSTSP_E_ARG,
+                      "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
+    else
+        JSTSP_REQUIRE(n_indx >= 0 && (indx_S || n_indx == 0) && n_indx <= g, JSTSP_E_ARG,
+                      "%s: n_indx = %d: need 0 (all) or 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
+    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
+                  it0, state_in, state_out, memspace};
+    p.n_indx = n_indx;
+    if (policy) { p.policy = true; p.start = refresh_start; p.period = refresh_period; p.indx_out = indx_out; }
+    p.tol = tol; p.min_iters = min_iters; p.check = check; p.iters_out = iters_out; p.ce3_out = ce3_out;
     return resumed_solve(ctx, nmf, p);
 }
 

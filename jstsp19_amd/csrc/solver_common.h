@@ -77,6 +77,28 @@ int launch_resume_fix_k(jstsp_ctx *ctx, long long n, float2 *K, const float2 *D)
 int launch_resume_pack(jstsp_ctx *ctx, long long nm, long long g, int batch, const float2 *X, const float2 *V1, const float2 *V2, const float2 *Cb,
                        const float2 *V, const float2 *S, float2 *state);
 
+// until.hip: the stopping rule of jstsp_proposed_until_c32 (proposed.hip says where each runs).  flag[t]: 0 running, 1 stopped by
+// this iteration (the captures' cue), 2 stopped earlier.
+struct UntilWS {
+    int32_t *flag = nullptr, *iters = nullptr, *left = nullptr;     // per trial, per trial, the one int the host reads
+    double *ce3 = nullptr, *tol = nullptr;
+    uint32_t *ovf = nullptr;                        // the pass's overflow flag of a trial as it stood when the trial stopped
+    float2 *S = nullptr, *Y = nullptr;              // where a stopped trial's S and Y go: the caller's arrays, or their staging
+    int32_t *top = nullptr;                         // ... and its order; the state goes to ProposedWS::sout
+    int32_t *top_loop = nullptr;                    // the list the loop's refreshes write (a stopped trial runs on and rewrites its row)
+};
+int launch_until_init(jstsp_ctx *ctx, int batch, const UntilWS &u);
+// after iteration k (1-based) of the call, row `it` of ce (batch x 3 x Imax): stops the running trials the rule says, all when `last`
+int launch_until_test(jstsp_ctx *ctx, int batch, int k, int min_iters, bool last, const double *ce, int Imax, int it, const uint32_t *ovf_now,
+                      const UntilWS &u);
+// the trials with flag 1: S, Y, [X | V1 | . | . | v | S] of the state, the order (zeros when no refresh has run: have_top false)
+int launch_until_capture_head(jstsp_ctx *ctx, long long nm, long long g, int R, int batch, const float2 *X, const float2 *V1, const float2 *Y,
+                              const float2 *V, const float2 *S, bool have_top, const UntilWS &u, float2 *state);
+// ... and behind the synthesis [. | . | V2 | C | . | .] of the state; Cb as launch_resume_pack's
+int launch_until_capture_tail(jstsp_ctx *ctx, long long nm, long long g, int batch, const float2 *V2, const float2 *Cb, const UntilWS &u, float2 *state);
+int launch_until_count(jstsp_ctx *ctx, int batch, const UntilWS &u);        // *left = trials still running
+int launch_until_mask_ce(jstsp_ctx *ctx, int batch, int Imax, const UntilWS &u, double *ce);   // rows after iters[t]: NaN
+
 // Gram partials of problems [t0, t0 + count) only (same workspace layout as gram_partials).
 int gram_partials_range(jstsp_ctx *ctx, const GramWS &w, const float2 *Z, long long sZt, int t0, int count,
                         const uint32_t *amax = nullptr, const float2 *Z2 = nullptr,
@@ -148,10 +170,23 @@ template <class Cx, class Re> struct AdmmProblemOf {
     bool policy = false;
     int n_indx = 0, start = 0, period = 0;
     int32_t *indx_out = nullptr;
+    // The stopping rule of jstsp_proposed_until_c32 (include/jstsp.h; every other entry passes none: iters_out == NULL): trial t stops
+    // after the first iteration k of the call with k >= min_iters and ce(k, 3) <= tol[t] (host doubles, as tau_Y); every `check`
+    // iterations the host reads how many trials still run.  live(): some tol is positive, so a trial can stop before Imax.
+    const double *tol = nullptr;
+    int min_iters = 0, check = 0;
+    int32_t *iters_out = nullptr; double *ce3_out = nullptr;
+    bool until() const { return iters_out != nullptr; }
+    bool live() const
+    {
+        for (int t = 0; until() && tol && t < batch; ++t)
+            if (tol[t] > 0.0) return true;
+        return false;
+    }
     size_t nm() const { return (size_t)N * M; }
     size_t g() const { return (size_t)Gr * G2; }
     size_t state_elems() const { return 4 * nm() + 2 * g(); }
-    size_t listed() const { return policy ? (size_t)n_indx : g(); }                  // entries per trial of indx_S
+    size_t listed() const { return n_indx ? (size_t)n_indx : g(); }                  // entries per trial of indx_S (0: every entry)
     size_t R() const { return std::min<size_t>(g(), JSTSP_SUPPORT_TOP_MAX); }       // entries of a refreshed order
     bool refresh_at(long long i) const { return policy && i > start && (period ? (i - start - 1) % period == 0 : i == (long long)start + 1); }
     bool runs_refresh() const          // a function of it0, Imax, start and period alone
@@ -171,6 +206,7 @@ template <class Cx, class Re> struct AdmmProblemOf {
         s.subY = at(subY, nm()); s.Omega = at(Omega, nm()); s.A = at(A, (size_t)strideA); s.B = at(B, (size_t)strideB);
         s.tau_Y = at(tau_Y, 1); s.tau_S = at(tau_S, 1); s.rho = at(rho, 1); s.indx_S = at(indx_S, listed());
         s.indx_out = at(indx_out, R());
+        s.tol = at(tol, 1); s.iters_out = at(iters_out, 1); s.ce3_out = at(ce3_out, 1);
         s.S_out = at(S_out, g()); s.Y_out = at(Y_out, nm()); s.ce_out = at(ce_out, (size_t)3 * Imax);
         s.state_in = at(state_in, state_elems()); s.state_out = at(state_out, state_elems());
         return s;

@@ -887,7 +887,7 @@ TRACKING_UNTIL_MODES = ("cold_until", "warm_until", "refresh_until", "warm_refre
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
                  precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
-                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False, stop=None):
+                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False, stop=None, until_f32=False):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -919,6 +919,8 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     rule of ``proposed_algorithm_until_f64``: ONE solve per frame with ``Imax = cold_imax``, each trial stopped at its own iteration:
       cold_until, warm_until                  ``cold`` / ``warm`` with the rule
       refresh_until, warm_refresh_until       ``refresh`` / ``warm_refresh`` with the rule
+    ``until_f32=True`` (``precision="f32"`` only, with ``stop``) runs these four through the fp32 solver
+    instead, by ``proposed_algorithm_until``; without it ``precision="f32"`` refuses them as before.
     Their results also carry ``mean_iters``, ``median_iters``, ``max_iters`` and ``mean_iters_by_frame`` over the scored frames.
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
@@ -944,8 +946,12 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         raise ValueError("modes must be a non-empty subset of %r, and every Imax >= 1" % (every,))
     until = [m for m in TRACKING_UNTIL_MODES if m in modes]
     stop_tol = stop_min = None
+    if until_f32 and precision != "f32":
+        raise ValueError("until_f32 runs the *_until modes on the fp32 solver: precision must be 'f32', not %r" % (precision,))
+    if until_f32 and stop is None:
+        raise ValueError("until_f32 needs stop=(tol, min_iters): it selects the solver of the modes %r" % (TRACKING_UNTIL_MODES,))
     if until:
-        if precision != "f64":
+        if precision != "f64" and not until_f32:
             raise ValueError("the modes %r stop inside the float64 solver: precision must be 'f64'" % (TRACKING_UNTIL_MODES,))
         if stop is None:
             raise ValueError("the modes %r need stop=(tol, min_iters)" % (TRACKING_UNTIL_MODES,))
@@ -989,6 +995,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     wide = (lambda x: J.colmajor(x.to(torch.complex128))) if f64 else (lambda x: x)
     solve = J.proposed_algorithm_resume_f64 if f64 else J.proposed_algorithm_resume
     solve_refresh = J.proposed_algorithm_refresh_f64 if f64 else J.proposed_algorithm_refresh
+    solve_until = J.proposed_algorithm_until_f64 if f64 else J.proposed_algorithm_until
     score = J.nmse_spectral_f64 if f64 else J.nmse_spectral
     order = J.support_order_f64 if f64 else J.support_order
     order_wide = J.support_order_wide_f64 if f64 else J.support_order_wide
@@ -1026,7 +1033,7 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                 torch.cuda.synchronize(device)
                 c0 = time.perf_counter()
                 if mode in until:
-                    S, _, _, out, _, n_ran, _ = J.proposed_algorithm_until_f64(
+                    S, _, _, out, _, n_ran, _ = solve_until(
                         *args, n_it, *prm, tol=stop_tol, min_iters=stop_min, refresh=(r_start, r_period) if "refresh" in mode else None,
                         state=st, return_state=warm)
                 elif mode in _REFRESH_MODES:
@@ -1072,6 +1079,8 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         res["widen"], res["widen_primary"] = [wr, wt], widen_primary
     if until:
         res["stop"] = [stop_tol, stop_min]
+        if until_f32:
+            res["until_f32"] = True
     if any(m in _REFRESH_MODES for m in modes) or any("refresh" in m for m in until):
         res["refresh"] = [r_start, r_period]
         if refresh_f32:

@@ -1190,6 +1190,42 @@ def proposed_algorithm_until_f64(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, 
     return q.result() + (st_out, order, iters, ce3)
 
 
+UNTIL_CHECK_F32 = 1     # iterations between two reads of the running count: the fastest measured
+
+
+def proposed_algorithm_until(subY, Omega, A, B, Imax, tau_Y, tau_S, rho, *, tol, min_iters=2, check=UNTIL_CHECK_F32, indx_S=None,
+                             refresh=None, state=None, it0=0, want_ce=False, return_state=True, type="approximate", ctx=None):
+    """:func:`proposed_algorithm_until_f64` on the fp32 solver (include/jstsp.h: jstsp_proposed_until_c32):
+    :func:`proposed_algorithm_refresh` - with ``refresh=None`` :func:`proposed_algorithm_resume` ('approximate') - where trial ``t``
+    stops after the first iteration ``i`` of the call with ``i >= min_iters`` and ``convergence_error[i, 2] <= tol[t]``, failing
+    that after ``Imax``.  The arguments and the returned ``(S, Y, ce, state, order, iters, ce3)`` are the float64 sibling's, in
+    complex64.  The fp32 batch is not compacted: a stopped trial runs on until every trial has stopped, so ``check`` - the iterations
+    between two reads of the running count - and the other trials' ``tol`` never change a trial's result, to the bit; against
+    the sibling run for that trial alone over ``iters[t]`` iterations the values are fp32-equivalent.  Alg. 2 only."""
+    if type != "approximate":
+        raise ValueError("type must be 'approximate': the stopping rule reads the gradient step of Alg. 2")
+    min_iters, check_every, it0, Imax = int(min_iters), int(check), int(it0), int(Imax)
+    if min_iters < 1 or check_every < 1:
+        raise ValueError("min_iters and check must be >= 1, not %r and %r" % (min_iters, check_every))
+    if refresh is None:
+        start, period = it0 + max(Imax, 0), 0               # (for the checks below: a schedule that never refreshes in this call)
+    else:
+        start, period = refresh
+    tl, ptl = _scalars(tol, int(subY.shape[0]) if len(subY.shape) == 3 else 1, "tol")      # (refused before the context, as the rest)
+    q, n, start, period, it0, p_in, keep_in, p_out, st_out, order, p_ord = _refresh_open(
+        np.complex64, subY, Omega, A, B, Imax, tau_Y, tau_S, rho, start, period, indx_S, want_ce, ctx, state, it0, return_state)
+    if refresh is None:
+        start, period = 0, -1
+    p_it, iters = _vec_out(q.mem == DEVICE, q.batch, np.int32, q.dev)
+    p_c3, ce3 = _vec_out(q.mem == DEVICE, q.batch, np.float64, q.dev)
+    name = "jstsp_proposed_until_c32"
+    args = q.c32_args("approximate")         # (... rho, type, indx_S, S, Y, ce)
+    _lib.check(getattr(q.ctx._lib, name)(*args[:-3], n, start, period, ptl, min_iters, check_every, *args[-3:], it0, p_in, p_out, p_ord,
+                                         p_it, p_c3, q.mem), name)
+    del keep_in, tl
+    return q.result() + (st_out, order, iters, ce3)
+
+
 def svt_f64(Y, tau, *, ctx=None):
     """benchmark_algorithms/svt.m:1 in float64 on the device (jstsp_svt_f64); complex128 out."""
     a_Y = _Arg(_wide(Y), np.complex128, "Y")

@@ -34,7 +34,8 @@ chain's previous estimate in force until the first refresh: --refresh START,PERI
 cold_until, warm_until, refresh_until and warm_refresh_until (float64 only) are cold, warm, refresh and
 warm_refresh with the stopping rule of proposed_algorithm_until_f64: --stop TOL[,MIN] stops each trial after its first iteration
 i >= MIN (default 2) with |v_i - v_{i-1}|^2 / |v_{i-1}|^2 <= TOL; one solve per frame at --cold-imax, and the result also carries
-the mean, median and largest number of iterations.  --stop without --modes runs these four.
+the mean, median and largest number of iterations.  --stop without --modes runs these four.  With --precision f32, --until-f32
+runs them on the fp32 solver (proposed_algorithm_until).
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -75,6 +76,8 @@ ap.add_argument("--refresh", default=None, metavar="START,PERIOD",
                 help="--device-channel: the refresh schedule of refresh / warm_refresh / pai_prev_refresh (default: 0,1)")
 ap.add_argument("--refresh-f32", action="store_true",
                 help="--device-channel --precision f32: the refresh modes on the fp32 solver (proposed_algorithm_refresh)")
+ap.add_argument("--until-f32", action="store_true",
+                help="--device-channel --precision f32 --stop: the *_until modes on the fp32 solver (proposed_algorithm_until)")
 ap.add_argument("--stop", default=None, metavar="TOL[,MIN]",
                 help="--device-channel: the stopping rule of the *_until modes (tolerance and, default 2, the fewest iterations)")
 a = ap.parse_args()
@@ -91,8 +94,8 @@ if a.stop is not None:
     if a.modes is None:
         a.modes = ["cold_until", "warm_until", "refresh_until", "warm_refresh_until"]
 if (a.drift is not None or a.modes is not None or a.widen is not None or a.widen_primary is not None or a.refresh is not None
-        or a.refresh_f32) and not a.device_channel:
-    ap.error("--drift, --modes, --widen, --widen-primary, --refresh and --refresh-f32 need --device-channel")
+        or a.refresh_f32 or a.until_f32) and not a.device_channel:
+    ap.error("--drift, --modes, --widen, --widen-primary, --refresh, --refresh-f32 and --until-f32 need --device-channel")
 if a.refresh is not None:
     try:
         a.refresh = tuple(int(x) for x in a.refresh.split(","))
@@ -131,6 +134,8 @@ if a.device_channel:
         kw["refresh_f32"] = True
     if a.stop is not None:
         kw["stop"] = a.stop
+    if a.until_f32:
+        kw["until_f32"] = True
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
