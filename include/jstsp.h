@@ -1302,6 +1302,45 @@ int jstsp_proposed_until_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int b
                              int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out,
                              int32_t *iters_out, double *ce3_out, int memspace);
 
+/* ---- a float64 least-squares re-fit of an estimate on its support (csrc/refit64.hip) -------------------
+ * A stage AFTER a solve, not a solver: the ADMM takes one steepest-descent step per iteration (proposed_algorithm.m:47-51), so its
+ * S is not the least-squares fit on its own strong entries.  A few conjugate-gradient steps on the normal equations of
+ * min ||Omega .* (A S B) - subY||_F, restricted to K entries of S, finish that.  Layouts, strides (0 = shared), memspaces and the
+ * 24 GiB workspace refusal are those of jstsp_proposed_resume_f64; there is no eigen-decomposition, so min(N, M) is not limited.
+ * Per trial, with g = Gr*G2:
+ *  - support T: with indx_S (1-based, n_indx entries per trial, stride n_indx; K <= n_indx <= g) its first K entries, entries
+ *    outside 1..g ignored; with indx_S == NULL (n_indx == 0) the first K entries of jstsp_support_order_f64(S_in), taken by the
+ *    selection kernel of jstsp_support_top_f64 (ascending key, equal keys in ascending index; K <= JSTSP_SUPPORT_TOP_MAX).
+ *    K == g: no mask, with or without indx_S.  m is the indicator of T.
+ *  - G(x) = m .* (A^H ((Omega .* Omega) .* (A x B)) B^H) + lam x;  b = m .* (A^H (Omega .* subY) B^H).
+ *  - x = m .* S_in; r = b - G(x); p = r; gamma_0 = gamma = <r, r>; for k = 1 .. iters: q = G(p); delta = Re<p, q>;
+ *    alpha = gamma / delta; x += alpha p; r -= alpha q; gamma' = <r, r>; p = r + (gamma' / gamma) p; gamma = gamma'.
+ *  - a trial FREEZES at the first k at whose start gamma == 0 or (tol > 0 and) gamma <= tol^2 gamma_0, or whose delta is not
+ *    positive and finite (a NaN trial; lam = 0 and a direction in the null space).  Its x stays as it is.  The flag and the scalars
+ *    live on the device: nothing is read back inside the loop, with or without tol.
+ *  - S_out = x (S_out may be S_in).  iters_out (int32 per trial, NULL: not wanted): the steps taken, 0 .. iters.  resid_out
+ *    ((iters + 1) x batch doubles, NULL: not wanted): gamma_0 .. gamma_iters, NaN after the trial's last step.
+ *  - K and iters are regularisers (K = g with many steps fits the noise): both are the caller's, neither has a default here.
+ *  - every sum runs in a fixed order inside one workgroup per trial and the products are those of jstsp_correlate_f64 /
+ *    jstsp_synthesize_f64: a repeated call returns the same bits, and a trial's bits depend neither on its batch mates, nor on a
+ *    shared or per-trial dictionary, nor on the memspace.  A NaN stays in its own trial.
+ *  - Refused, outputs untouched: JSTSP_E_ARG - K < 1, K > g, K > JSTSP_SUPPORT_TOP_MAX without indx_S (unless K == g), n_indx
+ *    outside K..g with indx_S or non-zero without it, iters < 1, lam or tol negative or NaN, a bad memspace; JSTSP_E_NULL - ctx,
+ *    subY, Omega, A, B, S_in or S_out NULL; JSTSP_E_SHAPE - a non-positive size, a non-zero stride shorter than its factor;
+ *    JSTSP_E_UNSUPPORTED - 2^31 or more entries in one trial's array, batch > 65535, a workspace above 24 GiB.
+ * Asserted (tests/test_gpu_refit64.py) on the problems of tests/resume_problems.py, K in {4, 40, g}, iters in {1, 6}, lam in
+ * {0, 0.1}, and one 64 x 256, 64 x 128 trial at K = 4096: S_out within 1e-10 of max|ref| and resid within 1e-8 of
+ * tests/refit_ref.py (at K = 4 only, entries below 1e-10 gamma_0 against that floor), iters_out equal; the same bits from a repeated call, a
+ * trial alone, the other memspace and indx_S = jstsp_support_order_f64(S_in); the objective does not increase; the zero problem,
+ * a NaN trial, tol, every refusal. */
+int jstsp_refit_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch,
+                    const jstsp_c64 *subY, const double *Omega,
+                    const jstsp_c64 *A, long long strideA,
+                    const jstsp_c64 *B, long long strideB,
+                    const jstsp_c64 *S_in, const int32_t *indx_S, int n_indx, int K,
+                    int iters, double lam, double tol,
+                    jstsp_c64 *S_out, double *resid_out, int32_t *iters_out, int memspace);
+
 /* ---- the fp32 ADMM with its support refreshed from its own iterate (csrc/proposed.hip) ------------------
  * jstsp_proposed_resume_c32 with the support policy of jstsp_proposed_refresh_f64 above: the same schedule on the global
  * iteration index, the same R = min(Gr*G2, JSTSP_SUPPORT_TOP_MAX) and its LIMIT, the same indx_S (n_indx entries per trial, stride

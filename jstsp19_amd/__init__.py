@@ -16,6 +16,6 @@ from .solvers import (OMP, sparse_sca_estim, cawgn_estim_out, gradient_head, ls_
                       admm_state_elems, proposed_algorithm_resume_f64, proposed_algorithm_std_resume_f64,
                       proposed_algorithm_resume, proposed_algorithm_angles_resume, support_order, support_order_f64,
                       support_order_wide, support_order_wide_f64, support_top_f64, proposed_algorithm_refresh_f64,
-                      support_top, proposed_algorithm_refresh, proposed_algorithm_until_f64, proposed_algorithm_until)
+                      support_top, proposed_algorithm_refresh, proposed_algorithm_until_f64, proposed_algorithm_until, refit_f64)
 
 __version__ = "0.1.0"

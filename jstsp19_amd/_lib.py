@@ -182,6 +182,12 @@ for _n in ("jstsp_proposed_until_c32", "jstsp_proposed_until_c64"):
     SIGNATURES[_n] = (c_int, SIGNATURES["jstsp_proposed_refresh_c32"][1][:21] + [c_dp, c_int, c_int]
                       + SIGNATURES["jstsp_proposed_refresh_c32"][1][21:-1] + [c_void_p, c_void_p, c_int])
 
+# the float64 least-squares re-fit of an estimate on its support (csrc/refit64.hip): ... B, strideB, S_in, indx_S, n_indx, K, iters,
+# lam, tol, S_out, resid_out, iters_out, memspace
+SIGNATURES["jstsp_refit_f64"] = (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_ll,
+                                         c_void_p, c_void_p, c_int, c_int, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p,
+                                         c_int])
+
 for _n in ("mmv_omp", "mc_svt", "mc_admm"):
     # joint OMP and matrix completion in float64 (csrc/mmv_omp64.hip, csrc/mc64.hip): the argument lists of the _c32 / _c64 namesakes
     # (pointers are void* here, so the two are one list)

@@ -887,7 +887,7 @@ TRACKING_UNTIL_MODES = ("cold_until", "warm_until", "refresh_until", "warm_refre
 
 def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50, 100), cold_imax=100, modes=TRACKING_MODES,
                  precision="f64", batch=16, seed=20190913, sweep_idx=0, device=None, drift=None, widen=(1, 1),
-                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False, stop=None, until_f32=False):
+                 widen_primary="neighbourhood", refresh=(0, 1), refresh_f32=False, stop=None, until_f32=False, refit=None):
     """What a warm start of the ADMM buys on a slowly varying channel (DESIGN.md sections 9n, 9o): the loop of
     tools/run_tracking.py on frames the library builds.  ``n_seqs`` independent sequences of ``n_frames`` frames at point ``p``;
     sequence t, frame f is ``build_trials(p, t, 1, seed=seed, sweep_idx=sweep_idx, frame=f, corr=corr)`` - fixed angles, path gains
@@ -922,6 +922,11 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     ``until_f32=True`` (``precision="f32"`` only, with ``stop``) runs these four through the fp32 solver
     instead, by ``proposed_algorithm_until``; without it ``precision="f32"`` refuses them as before.
     Their results also carry ``mean_iters``, ``median_iters``, ``max_iters`` and ``mean_iters_by_frame`` over the scored frames.
+    ``refit = (K, iters)`` (``precision="f64"`` only): the S that is scored is also re-fitted on its ``K``
+    largest entries by ``iters`` conjugate-gradient steps of ``refit_f64`` and scored again; every (mode, Imax) row then also
+    carries ``mean_nmse_refit``, ``mean_nmse_refit_by_frame`` and ``refit_estimates_per_s`` (the re-fit's own time).  The re-fitted
+    S is only scored: it is never fed back into a state or into a previous-estimate order, so every other number of the result is
+    what it is with ``refit=None``.
     ``drift``: a float lets the angles of every sequence walk (``build_trials(..., drift=)``: standard deviation of one frame's
     increment, radians), so the support moves; ``None`` (the default) builds the frames that were built before.
     States, estimates and scores stay on the device; the scores come to the host once per chunk of sequences.  Frame 0, where every
@@ -961,6 +966,17 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
             raise ValueError("stop must be tol or a pair (tol, min_iters), not %r" % (stop,)) from None
         if not stop_tol > 0.0 or stop_min < 1:
             raise ValueError("stop = %r: need tol > 0 and min_iters >= 1" % (stop,))
+    if refit is not None:
+        try:
+            refit_K, refit_iters = (int(x) for x in refit)
+        except (TypeError, ValueError):
+            raise ValueError("refit must be a pair (K, iters), not %r" % (refit,)) from None
+        if precision != "f64":
+            raise ValueError("refit re-fits in float64 (refit_f64): precision must be 'f64', not %r" % (precision,))
+        g_all = p.solver_shape[2] * p.solver_shape[3]
+        if not 1 <= refit_K <= g_all or (refit_K > J._lib.SUPPORT_TOP_MAX and refit_K != g_all) or refit_iters < 1:
+            raise ValueError("refit = %r: need 1 <= K <= min(Gr*G2, %d) or K = Gr*G2 = %d, and iters >= 1"
+                             % (refit, J._lib.SUPPORT_TOP_MAX, g_all))
     if drift is not None:
         drift = float(drift)
         if not (np.isfinite(drift) and drift >= 0.0):
@@ -1005,11 +1021,14 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
     err = {k: [] for k in keys}                                     # per chunk: (scored frames, chunk) on the host
     secs = {k: 0.0 for k in keys}
     its = {k: [] for k in keys if k[0] in until}                    # per chunk: iterations, (scored frames, chunk) on the host
+    err_fit = {k: [] for k in keys if refit is not None}            # the re-fitted S, scored as err is
+    secs_fit = {k: 0.0 for k in err_fit}
     for t0 in range(0, n_seqs, batch):
         nb = min(batch, n_seqs - t0)
         state, prev_S = {}, {}
         e_dev = {k: [] for k in keys}
         i_dev = {k: [] for k in its}
+        f_dev = {k: [] for k in err_fit}
         for f in range(n_frames):
             inp = build_trials(p, t0, nb, seed=seed, sweep_idx=sweep_idx, device=device, frame=f, corr=corr, **frame_kw)
             args = (wide(inp["subY"]), J.colmajor(inp["Omega"].to(torch.float64)) if f64 else inp["Omega"], wide(inp["A"]),
@@ -1052,10 +1071,19 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
                     e_dev[k].append(torch.as_tensor(score(S, zb)).double())
                     if mode in until:
                         i_dev[k].append(n_ran)
+                    if refit is not None:                           # (after everything the chain keeps: S itself goes on unchanged)
+                        torch.cuda.synchronize(device)
+                        c0 = time.perf_counter()
+                        S_fit, _ = J.refit_f64(*args, S, refit_K, refit_iters)
+                        torch.cuda.synchronize(device)
+                        secs_fit[k] += time.perf_counter() - c0
+                        f_dev[k].append(torch.as_tensor(score(S_fit, zb)).double())
         for k in keys:
             err[k].append(torch.stack(e_dev[k]).cpu().numpy())
         for k in its:
             its[k].append(torch.stack(i_dev[k]).cpu().numpy())
+        for k in err_fit:
+            err_fit[k].append(torch.stack(f_dev[k]).cpu().numpy())
 
     def summary(k):
         e = np.concatenate(err[k], axis=1)                          # (scored frames, seqs)
@@ -1068,6 +1096,10 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
             n = np.concatenate(its[k], axis=1)                      # (scored frames, seqs)
             out.update(mean_iters=float(n.mean()), median_iters=float(np.median(n)), max_iters=int(n.max()),
                        mean_iters_by_frame=[float(x) for x in n.mean(axis=1)])
+        if k in err_fit:
+            ef = np.concatenate(err_fit[k], axis=1)                 # (scored frames, seqs)
+            out.update(mean_nmse_refit=float(ef.mean()), mean_nmse_refit_by_frame=[float(x) for x in ef.mean(axis=1)],
+                       refit_estimates_per_s=n_seqs * (n_frames - 1) / secs_fit[k])
         return out
 
     res = {"tool": "run_tracking", "precision": precision, "shape": [N, M, Gr, G2], "frames": n_frames, "seqs": n_seqs, "corr": corr,
@@ -1077,6 +1109,8 @@ def run_tracking(p: SweepParams, n_seqs, n_frames, corr, *, imax=(10, 20, 30, 50
         res["drift"] = drift
     if any(m in _WIDE_MODES for m in modes):
         res["widen"], res["widen_primary"] = [wr, wt], widen_primary
+    if refit is not None:
+        res["refit"] = [refit_K, refit_iters]
     if until:
         res["stop"] = [stop_tol, stop_min]
         if until_f32:

@@ -36,6 +36,8 @@ warm_refresh with the stopping rule of proposed_algorithm_until_f64: --stop TOL[
 i >= MIN (default 2) with |v_i - v_{i-1}|^2 / |v_{i-1}|^2 <= TOL; one solve per frame at --cold-imax, and the result also carries
 the mean, median and largest number of iterations.  --stop without --modes runs these four.  With --precision f32, --until-f32
 runs them on the fp32 solver (proposed_algorithm_until).
+--refit K,ITERS (float64 only) also re-fits every scored estimate on its K largest entries by ITERS
+conjugate-gradient steps (refit_f64) and scores it again: mean_nmse_refit, mean_nmse_refit_by_frame, refit_estimates_per_s per row.
 A warm chain at Imax n has run n iterations in every earlier frame as well: by frame f it has accumulated f n iterations on a
 channel that is corr^k-correlated with the one k frames back.  So the result is also given frame by frame: frame 2 (index 1) is
 the warm start proper - n iterations on the previous frame plus n on this one - and the later frames show what accumulates.
@@ -80,7 +82,18 @@ ap.add_argument("--until-f32", action="store_true",
                 help="--device-channel --precision f32 --stop: the *_until modes on the fp32 solver (proposed_algorithm_until)")
 ap.add_argument("--stop", default=None, metavar="TOL[,MIN]",
                 help="--device-channel: the stopping rule of the *_until modes (tolerance and, default 2, the fewest iterations)")
+ap.add_argument("--refit", default=None, metavar="K,ITERS",
+                help="--device-channel: also score every estimate after a float64 re-fit on its K largest entries, ITERS steps")
 a = ap.parse_args()
+if a.refit is not None:
+    if not a.device_channel:
+        ap.error("--refit needs --device-channel")
+    try:
+        a.refit = tuple(int(x) for x in a.refit.split(","))
+    except ValueError:
+        a.refit = ()
+    if len(a.refit) != 2 or min(a.refit) < 1:
+        ap.error("--refit takes two integers >= 1 as K,ITERS")
 if a.stop is not None:
     if not a.device_channel:
         ap.error("--stop needs --device-channel")
@@ -136,6 +149,8 @@ if a.device_channel:
         kw["stop"] = a.stop
     if a.until_f32:
         kw["until_f32"] = True
+    if a.refit is not None:
+        kw["refit"] = a.refit
     emit(run_tracking(p, a.seqs, a.frames, a.corr, imax=a.imax, cold_imax=a.cold_imax, precision=a.precision, batch=a.seqs,
                       seed=a.seed, sweep_idx=a.sweep_idx, device=torch.device("cuda:0"), drift=a.drift, **kw))
     sys.exit(0)
