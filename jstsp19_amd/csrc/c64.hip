@@ -164,6 +164,44 @@ int enter(jstsp_ctx *ctx, int memspace)
     return 0;
 }
 
+// The record of a _c64 entry as the fp32 solver takes it, memspace JSTSP_DEVICE: every input the record names narrowed by cv (int32
+// lists pass through; the per-trial doubles stay on the host), every output a buffer that cv.finish() delivers - outputs = false:
+// inputs only (the halves of the pipelined call deliver their own).  indx_out is staged only if the call runs a refresh: it is
+// written if and only if it does.  hgt != NULL: B by the block-Toeplitz-aware staging, *hgt the block height for the solver's hint.
+AdmmProblem stage_record(Conv &cv, const AdmmProblem64 &h, int *hgt = nullptr, bool outputs = true)
+{
+    AdmmProblem d;
+    d.N = h.N; d.M = h.M; d.Gr = h.Gr; d.G2 = h.G2; d.batch = h.batch; d.strideA = h.strideA; d.strideB = h.strideB; d.Imax = h.Imax; d.type = h.type;
+    d.tau_Y = h.tau_Y; d.tau_S = h.tau_S; d.rho = h.rho; d.it0 = h.it0; d.memspace = JSTSP_DEVICE;
+    d.policy = h.policy; d.n_indx = h.n_indx; d.start = h.start; d.period = h.period;
+    d.rule = h.rule; d.tol = h.tol; d.min_iters = h.min_iters; d.check = h.check;
+    const size_t b = (size_t)h.batch;
+    d.subY = cv.in(h.subY, h.nm() * b);
+    d.A = cv.in_dict(h.A, (size_t)h.N * h.Gr, h.strideA, h.batch);
+    d.B = hgt ? cv.in_dict_toeplitz(h.B, h.G2, h.M, h.strideB, h.batch, hgt) : cv.in_dict(h.B, (size_t)h.G2 * h.M, h.strideB, h.batch);
+    d.state_in = cv.in(h.state_in, h.state_elems() * b);
+    d.Omega = cv.in_real(h.Omega, h.nm() * b);
+    d.indx_S = cv.in_raw(h.indx_S, h.listed() * b);
+    if (!outputs) return d;
+    d.S_out = cv.out(h.S_out, h.g() * b); d.Y_out = cv.out(h.Y_out, h.nm() * b); d.state_out = cv.out(h.state_out, h.state_elems() * b);
+    d.ce_out = cv.out_raw(h.ce_out, (size_t)h.Imax * 3 * b);
+    const bool writes_order = h.indx_out && h.start >= 0 && h.period >= 0 && h.it0 >= 0 && h.runs_refresh();
+    if (writes_order) d.indx_out = cv.out_raw(h.indx_out, h.R() * b);
+    d.iters_out = cv.out_raw(h.iters_out, b); d.ce3_out = cv.out_raw(h.ce3_out, b);
+    return d;
+}
+
+// A resumed _c64 entry behind its own checks: the fp32 entry of the same name on the staged record, then the outputs
+int resumed_c64(jstsp_ctx *ctx, Conv &cv, const AdmmProblem64 &h)
+{
+    AdmmProblem d = stage_record(cv, h);
+    JSTSP_TRY(cv.rc);
+    JSTSP_TRY(proposed_resumed_entry(ctx, d));
+    JSTSP_TRY(cv.finish());
+    if (h.memspace == JSTSP_HOST && h.type != JSTSP_TYPE_APPROXIMATE) JSTSP_TRY(diag_check_host(ctx, "proposed_algorithm 'std'"));
+    return 0;
+}
+
 }  // namespace
 }  // namespace jstsp
 
@@ -174,6 +212,11 @@ using namespace jstsp;
     JSTSP_ENTER(ctx);                                                                           \
     JSTSP_REQUIRE(shape_ok, JSTSP_E_SHAPE, what ": bad shape");                                 \
     Conv cv(ctx, memspace)
+
+// the record of a resumed entry from its arguments, in the caller's memspace
+#define C64_RECORD                                                                                                                          \
+    AdmmProblem64 h{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out, it0, \
+                    state_in, state_out, memspace}
 
 extern "C" {
 
@@ -217,14 +260,14 @@ int jstsp_proposed_algorithm_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
                   "proposed_algorithm: NULL argument");
     // JSTSP_HOST with a large batch: two halves on two contexts, as the _c32 entry does (proposed.hip) - the upload and narrowing
     // of the second half (doubles: 9.5 GiB per 256 trials at BASELINE configs[1]) run while the first half is being solved.
+    const AdmmProblem64 all{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out,
+                            ce_out, 0, nullptr, nullptr, memspace};
     const size_t in_bytes = (size_t)batch * ((size_t)N * M * 24 + (strideB ? (size_t)G2 * M * 16 : 0));
     if (memspace == JSTSP_HOST && type == JSTSP_TYPE_APPROXIMATE && batch >= 128 && Imax > 1 && Y_out && tune().host_pipeline &&
         in_bytes >= ((size_t)512 << 20)) {
         HostPipeline pipe;
         JSTSP_TRY(pipe.open(ctx, batch));
         jstsp_ctx *const *cx = pipe.cx;
-        const AdmmProblem64 all{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out,
-                                ce_out, 0, nullptr, nullptr, JSTSP_HOST};
         const AdmmProblem64 half[2] = {all.sub(pipe.t0[0], pipe.cnt[0]), all.sub(pipe.t0[1], pipe.cnt[1])};      // the caller's arrays
         const size_t nm1 = all.nm(), g1 = all.g();
         Conv cvk[2] = {{cx[0], JSTSP_HOST}, {cx[1], JSTSP_HOST}};
@@ -232,16 +275,9 @@ int jstsp_proposed_algorithm_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
         AdmmProblem dev[2];                             // the halves with their inputs narrowed on the device, no outputs
         for (int k = 0; k < 2; ++k) {
             Conv &c = cvk[k];
-            const AdmmProblem64 &h = half[k];
             AdmmProblem &d = dev[k];
-            d.N = N; d.M = M; d.Gr = Gr; d.G2 = G2; d.batch = h.batch; d.strideA = strideA; d.strideB = strideB; d.Imax = Imax; d.type = type;
-            d.tau_Y = h.tau_Y; d.tau_S = h.tau_S; d.rho = h.rho; d.memspace = JSTSP_DEVICE;
-            d.subY = c.in(h.subY, h.batch * nm1);
-            d.Omega = c.in_real(h.Omega, h.batch * nm1);
-            d.A = c.in_dict(h.A, (size_t)N * Gr, strideA, h.batch);
             int hgt = 0;
-            d.B = c.in_dict_toeplitz(h.B, G2, M, strideB, h.batch, &hgt);
-            d.indx_S = c.in_raw(h.indx_S, h.batch * g1);
+            d = stage_record(c, half[k], &hgt, false);
             JSTSP_TRY_PIPE(pipe, c.rc);
             cx[k]->dict_block_hint = hgt;               // (consumed by the solve enqueued next on this context)
             JSTSP_TRY_PIPE(pipe, proposed_enqueue_device(cx[k], d, ce_out != nullptr, &pend[k]));
@@ -278,18 +314,12 @@ int jstsp_proposed_algorithm_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, i
         pipe.close();
         return 0;
     }
-    const size_t nm = (size_t)N * M * batch;
     int hgt = 0;
-    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch),
-                    *b = cv.in_dict_toeplitz(B, G2, M, strideB, batch, &hgt);
-    const float *om = cv.in_real(Omega, nm);
-    const int32_t *ix = cv.in_raw(indx_S, (size_t)Gr * G2 * batch);
-    jstsp_c32 *s = cv.out(S_out, (size_t)Gr * G2 * batch), *yo = cv.out(Y_out, nm);
-    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
+    const AdmmProblem d = stage_record(cv, all, &hgt);
     JSTSP_TRY(cv.rc);
     ctx->dict_block_hint = hgt;
-    JSTSP_TRY(jstsp_proposed_algorithm_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S,
-                                           rho, type, ix, s, yo, ce, JSTSP_DEVICE));
+    JSTSP_TRY(jstsp_proposed_algorithm_c32(ctx, N, M, Gr, G2, batch, d.subY, d.Omega, d.A, strideA, d.B, strideB, Imax, tau_Y, tau_S, rho, type,
+                                           d.indx_S, d.S_out, d.Y_out, d.ce_out, JSTSP_DEVICE));
     JSTSP_TRY(cv.finish());
     if (memspace == JSTSP_HOST && type != JSTSP_TYPE_APPROXIMATE) JSTSP_TRY(diag_check_host(ctx, "proposed_algorithm 'std'"));
     return 0;
@@ -304,19 +334,8 @@ int jstsp_proposed_resume_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int 
 {
     C64_BEGIN(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, "proposed_algorithm resume");
     JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "proposed_algorithm resume: NULL argument");
-    const size_t nm = (size_t)N * M * batch, ne = (4 * (size_t)N * M + 2 * (size_t)Gr * G2) * batch;
-    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch), *b = cv.in_dict(B, (size_t)G2 * M, strideB, batch),
-                    *si = cv.in(state_in, ne);
-    const float *om = cv.in_real(Omega, nm);
-    const int32_t *ix = cv.in_raw(indx_S, (size_t)Gr * G2 * batch);
-    jstsp_c32 *s = cv.out(S_out, (size_t)Gr * G2 * batch), *yo = cv.out(Y_out, nm), *so = cv.out(state_out, ne);
-    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
-    JSTSP_TRY(cv.rc);
-    JSTSP_TRY(jstsp_proposed_resume_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S, rho, type, ix, s, yo, ce,
-                                        it0, si, so, JSTSP_DEVICE));
-    JSTSP_TRY(cv.finish());
-    if (memspace == JSTSP_HOST && type != JSTSP_TYPE_APPROXIMATE) JSTSP_TRY(diag_check_host(ctx, "proposed_algorithm 'std'"));
-    return 0;
+    C64_RECORD;
+    return resumed_c64(ctx, cv, h);
 }
 
 // jstsp_proposed_refresh_c32 at the reference's element type, as jstsp_proposed_resume_c64 above: indx_S (n_indx per trial) and
@@ -330,24 +349,10 @@ int jstsp_proposed_refresh_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int
 {
     C64_BEGIN(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, "proposed_algorithm refresh");
     JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "proposed_algorithm refresh: NULL argument");
-    const long long g = (long long)Gr * G2;
-    JSTSP_REQUIRE(indx_S ? n_indx >= 1 && n_indx <= g : n_indx == 0, JSTSP_E_ARG,
-                  "proposed_algorithm refresh: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", n_indx, g);
-    AdmmProblem probe;                              // (the schedule: whether the call writes indx_out)
-    probe.policy = true; probe.start = refresh_start; probe.period = refresh_period; probe.it0 = it0; probe.Imax = Imax;
-    const bool writes_order = indx_out && refresh_start >= 0 && refresh_period >= 0 && it0 >= 0 && probe.runs_refresh();
-    const size_t nm = (size_t)N * M * batch, ne = (4 * (size_t)N * M + 2 * (size_t)g) * batch;
-    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch), *b = cv.in_dict(B, (size_t)G2 * M, strideB, batch),
-                    *si = cv.in(state_in, ne);
-    const float *om = cv.in_real(Omega, nm);
-    const int32_t *ix = cv.in_raw(indx_S, (size_t)n_indx * batch);
-    jstsp_c32 *s = cv.out(S_out, (size_t)g * batch), *yo = cv.out(Y_out, nm), *so = cv.out(state_out, ne);
-    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
-    int32_t *io = writes_order ? cv.out_raw(indx_out, std::min<size_t>((size_t)g, JSTSP_SUPPORT_TOP_MAX) * batch) : nullptr;
-    JSTSP_TRY(cv.rc);
-    JSTSP_TRY(jstsp_proposed_refresh_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S, rho, type, ix, n_indx,
-                                         refresh_start, refresh_period, s, yo, ce, it0, si, so, io, JSTSP_DEVICE));
-    return cv.finish();
+    C64_RECORD;
+    h.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    JSTSP_TRY(check_policy("proposed_algorithm refresh", h, false));        // (the list is sized by n_indx before the fp32 entry can refuse it)
+    return resumed_c64(ctx, cv, h);
 }
 
 // jstsp_proposed_until_c32 at the reference's element type, as jstsp_proposed_refresh_c64 above: tol stays on the host, iters_out
@@ -361,28 +366,15 @@ int jstsp_proposed_until_c64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int b
 {
     C64_BEGIN(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, "proposed_algorithm until");
     JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "proposed_algorithm until: NULL argument");
-    JSTSP_REQUIRE(tol && iters_out, JSTSP_E_NULL, "proposed_algorithm until: tol and iters_out are required");
-    const long long g = (long long)Gr * G2;
-    JSTSP_REQUIRE(n_indx >= 0 && (indx_S || n_indx == 0) && n_indx <= g, JSTSP_E_ARG,
-                  "proposed_algorithm until: n_indx = %d: need 0 <= n_indx <= Gr * G2 = %lld, and 0 without indx_S", n_indx, g);
-    AdmmProblem probe;                              // (the schedule: whether the call writes indx_out)
-    probe.policy = true; probe.start = refresh_start; probe.period = refresh_period; probe.it0 = it0; probe.Imax = Imax;
-    const bool writes_order = indx_out && refresh_start >= 0 && refresh_period >= 0 && it0 >= 0 && probe.runs_refresh();
-    const size_t nm = (size_t)N * M * batch, ne = (4 * (size_t)N * M + 2 * (size_t)g) * batch;
-    const jstsp_c32 *y = cv.in(subY, nm), *a = cv.in_dict(A, (size_t)N * Gr, strideA, batch), *b = cv.in_dict(B, (size_t)G2 * M, strideB, batch),
-                    *si = cv.in(state_in, ne);
-    const float *om = cv.in_real(Omega, nm);
-    const int32_t *ix = cv.in_raw(indx_S, (size_t)(n_indx ? n_indx : g) * batch);
-    jstsp_c32 *s = cv.out(S_out, (size_t)g * batch), *yo = cv.out(Y_out, nm), *so = cv.out(state_out, ne);
-    double *ce = cv.out_raw(ce_out, (size_t)Imax * 3 * batch);
-    int32_t *io = writes_order ? cv.out_raw(indx_out, std::min<size_t>((size_t)g, JSTSP_SUPPORT_TOP_MAX) * batch) : nullptr;
-    int32_t *itd = cv.out_raw(iters_out, (size_t)batch);
-    double *c3 = cv.out_raw(ce3_out, (size_t)batch);
-    JSTSP_TRY(cv.rc);
-    JSTSP_TRY(jstsp_proposed_until_c32(ctx, N, M, Gr, G2, batch, y, om, a, strideA, b, strideB, Imax, tau_Y, tau_S, rho, type, ix, n_indx,
-                                       refresh_start, refresh_period, tol, min_iters, check, s, yo, ce, it0, si, so, io, itd, c3, JSTSP_DEVICE));
-    return cv.finish();
+    C64_RECORD;
+    h.n_indx = n_indx;
+    if (refresh_period >= 0) h.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    h.set_rule(tol, min_iters, check, iters_out, ce3_out);
+    JSTSP_TRY(check_rule_arrays("proposed_algorithm until", h));
+    JSTSP_TRY(check_rule_list("proposed_algorithm until", h, "%s: n_indx = %d: need 0 <= n_indx <= Gr * G2 = %lld, and 0 without indx_S"));
+    return resumed_c64(ctx, cv, h);
 }
+#undef C64_RECORD
 
 int jstsp_svt_c64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y, const double *tau, jstsp_c64 *X,
                   int memspace)

@@ -1026,62 +1026,76 @@ static int resumed_solve(jstsp_ctx *ctx, const char *nmf, AdmmProblem &p)
     return rc;
 }
 
-// ---- resumed from a saved state (include/jstsp.h) ---------------------------------------------------------------------------------
-// Iterations it0 + 1 ... it0 + Imax from state_in.  One staged solve in either memspace (no two-halves host pipeline).  A trial
-// whose k scale overflowed in a pass is solved again from ITS state_in at it0 by the three-kernel iteration; state_in is read
-// again for that, so when the caller lets state_out be state_in a copy is taken first.
+// ---- resumed from a saved state, with a support policy, with a stopping rule (include/jstsp.h) -----------------------------------
+// jstsp_proposed_resume_c32: iterations it0 + 1 ... it0 + Imax from state_in.  One staged solve in either memspace (no two-halves
+// host pipeline).  A trial whose k scale overflowed in a pass is solved again from ITS state_in at it0 by the three-kernel iteration;
+// state_in is read again for that, so when the caller lets state_out be state_in a copy is taken first.
+// jstsp_proposed_refresh_c32: the same with a support policy in the record (solver_common.h): the schedule, the limit R and indx_out
+// are those of jstsp_proposed_refresh_f64.  'approximate' only.  A flagged trial is solved again from its state_in at it0 under the
+// same policy, and its indx_out comes from that re-solve (AdmmProblem::sub moves both lists).
+// jstsp_proposed_until_c32: either of the two with the stopping rule in the record (AdmmLoop::stop_test says
+// what runs where).  A flagged trial is solved again under the same rule.
+// The record says which entry it came through: a rule - until; else a policy - refresh; else resume.  Each keeps the order of its
+// checks; the solver's own (check_arguments) follow inside the solve.
+int jstsp::proposed_resumed_entry(jstsp_ctx *ctx, AdmmProblem &p)
+{
+    const bool plain = !p.rule && !p.policy;
+    const char *nmf = p.rule ? "proposed_algorithm until" : p.policy ? "proposed_algorithm refresh" : "proposed_algorithm resume";
+    const bool shape_ok = p.N > 0 && p.M > 0 && p.Gr > 0 && p.G2 > 0 && p.batch > 0 && p.Imax > 0;
+    if (plain) {
+        JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
+        JSTSP_REQUIRE(p.memspace == JSTSP_HOST || p.memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", p.memspace);
+        JSTSP_REQUIRE(shape_ok, JSTSP_E_SHAPE, "%s: bad shape", nmf);
+        JSTSP_TRY(check_resumed(nmf, p));
+        return resumed_solve(ctx, nmf, p);
+    }
+    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: ctx is NULL", nmf);
+    JSTSP_REQUIRE(p.memspace == JSTSP_HOST || p.memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace %d", nmf, p.memspace);
+    JSTSP_REQUIRE(shape_ok && p.strideA >= 0 && p.strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
+    JSTSP_REQUIRE((long long)p.Gr * p.G2 < (1ll << 31), JSTSP_E_SHAPE, "%s: Gr * G2 = %lld exceeds 2^31 - 1", nmf, (long long)p.Gr * p.G2);
+    JSTSP_REQUIRE(p.subY && p.Omega && p.A && p.B && p.tau_Y && p.tau_S && p.rho && p.S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    if (p.rule) JSTSP_TRY(check_rule_arrays(nmf, p));
+    JSTSP_REQUIRE(p.type == JSTSP_TYPE_APPROXIMATE || p.type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, p.type);
+    JSTSP_REQUIRE(p.type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
+                  p.rule ? "%s: the rule reads the gradient step of Alg. 2; 'std' recomputes v by least squares and has none: use jstsp_proposed_resume_c32"
+                         : "%s: 'std' recomputes v by least squares in every iteration and has no refreshed form: use jstsp_proposed_resume_c32",
+                  nmf);
+    if (p.rule) JSTSP_TRY(check_rule_counts(nmf, p));
+    JSTSP_TRY(check_resumed(nmf, p));
+    if (!p.rule) JSTSP_TRY(check_policy(nmf, p));
+    else if (p.policy) {
+        JSTSP_REQUIRE(p.start >= 0, JSTSP_E_ARG, "%s: refresh_start = %d: may not be negative (refresh_period < 0: no policy)", nmf, p.start);
+        JSTSP_TRY(check_policy(nmf, p, false));
+    } else JSTSP_TRY(check_rule_list(nmf, p));
+    return resumed_solve(ctx, nmf, p);
+}
+
+#define RESUMED_RECORD                                                                                                                      \
+    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out, it0, \
+                  state_in, state_out, memspace}
+
 extern "C" int jstsp_proposed_resume_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
                                          const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
                                          const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S,
                                          jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, int it0, const jstsp_c32 *state_in,
                                          jstsp_c32 *state_out, int memspace)
 {
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
-    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0, JSTSP_E_SHAPE, "proposed_algorithm resume: bad shape");
-    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int",
-                  it0, Imax);
-    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "proposed_algorithm resume: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", it0);
-    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
-                  it0, state_in, state_out, memspace};
-    return resumed_solve(ctx, "proposed_algorithm resume", p);
+    RESUMED_RECORD;
+    return proposed_resumed_entry(ctx, p);
 }
 
-// ---- resumed, with the support refreshed from the solver's own iterate (include/jstsp.h) -------------------------------------------
-// jstsp_proposed_resume_c32 with a support policy in its problem record (solver_common.h): the schedule, the limit R and indx_out
-// are those of jstsp_proposed_refresh_f64.  'approximate' only ('std' is refused).  One staged solve; a flagged trial is solved again from its
-// state_in at it0 under the same policy, and its indx_out comes from that re-solve (AdmmProblem::sub moves both lists).
 extern "C" int jstsp_proposed_refresh_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
                                           const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
                                           const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S, int n_indx,
                                           int refresh_start, int refresh_period, jstsp_c32 *S_out, jstsp_c32 *Y_out, double *ce_out, int it0,
                                           const jstsp_c32 *state_in, jstsp_c32 *state_out, int32_t *indx_out, int memspace)
 {
-    const char *nmf = "proposed_algorithm refresh";
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: ctx is NULL", nmf);
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace %d", nmf, memspace);
-    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31), JSTSP_E_SHAPE, "%s: Gr * G2 = %lld exceeds 2^31 - 1", nmf, (long long)Gr * G2);
-    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
-                  "%s: 'std' recomputes v by least squares in every iteration and has no refreshed form: use jstsp_proposed_resume_c32", nmf);
-    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf, it0, Imax);
-    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, it0);
-    JSTSP_REQUIRE(refresh_start >= 0 && refresh_period >= 0, JSTSP_E_ARG, "%s: refresh_start = %d, refresh_period = %d: neither may be negative", nmf,
-                  refresh_start, refresh_period);
-    const long long g = (long long)Gr * G2;
-    JSTSP_REQUIRE(indx_S ? n_indx >= 1 && n_indx <= g : n_indx == 0, JSTSP_E_ARG,
-                  "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
-    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
-                  it0, state_in, state_out, memspace};
-    p.policy = true; p.n_indx = n_indx; p.start = refresh_start; p.period = refresh_period; p.indx_out = indx_out;
-    return resumed_solve(ctx, nmf, p);
+    RESUMED_RECORD;
+    p.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    return proposed_resumed_entry(ctx, p);
 }
 
-// ---- resumed, each trial stopped when its iterate has settled (include/jstsp.h) ------------------------------
-// jstsp_proposed_refresh_c32 - with refresh_period < 0 jstsp_proposed_resume_c32 - with the stopping rule in its problem record
-// (solver_common.h; AdmmLoop::stop_test says what runs where).  A flagged trial is solved again under the same rule.
+// (refresh_period < 0: no policy - n_indx then counts the entries per trial of indx_S, 0 meaning all)
 extern "C" int jstsp_proposed_until_c32(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c32 *subY, const float *Omega,
                                         const jstsp_c32 *A, long long strideA, const jstsp_c32 *B, long long strideB, int Imax,
                                         const double *tau_Y, const double *tau_S, const double *rho, int type, const int32_t *indx_S, int n_indx,
@@ -1089,36 +1103,13 @@ extern "C" int jstsp_proposed_until_c32(jstsp_ctx *ctx, int N, int M, int Gr, in
                                         jstsp_c32 *Y_out, double *ce_out, int it0, const jstsp_c32 *state_in, jstsp_c32 *state_out,
                                         int32_t *indx_out, int32_t *iters_out, double *ce3_out, int memspace)
 {
-    const char *nmf = "proposed_algorithm until";
-    const bool policy = refresh_period >= 0;
-    JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "%s: ctx is NULL", nmf);
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "%s: bad memspace %d", nmf, memspace);
-    JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE((long long)Gr * G2 < (1ll << 31), JSTSP_E_SHAPE, "%s: Gr * G2 = %lld exceeds 2^31 - 1", nmf, (long long)Gr * G2);
-    JSTSP_REQUIRE(subY && Omega && A && B && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
-    JSTSP_REQUIRE(tol && iters_out, JSTSP_E_NULL, "%s: tol and iters_out are required", nmf);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
-                  "%s: the rule reads the gradient step of Alg. 2; 'std' recomputes v by least squares and has none: use jstsp_proposed_resume_c32", nmf);
-    JSTSP_REQUIRE(min_iters >= 1 && check >= 1, JSTSP_E_ARG, "%s: min_iters = %d, check = %d: both must be at least 1", nmf, min_iters, check);
-    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf, it0, Imax);
-    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, it0);
-    JSTSP_REQUIRE(!policy || refresh_start >= 0, JSTSP_E_ARG, "%s: refresh_start = %d: may not be negative (refresh_period < 0: no policy)", nmf,
-                  refresh_start);
-    const long long g = (long long)Gr * G2;
-    if (policy)
-        JSTSP_REQUIRE(indx_S ? n_indx >= 1 && n_indx <= g : n_indx == 0, JSTSP_E_ARG,
-                      "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
-    else
-        JSTSP_REQUIRE(n_indx >= 0 && (indx_S || n_indx == 0) && n_indx <= g, JSTSP_E_ARG,
-                      "%s: n_indx = %d: need 0 (all) or 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, n_indx, g);
-    AdmmProblem p{N, M, Gr, G2, batch, subY, Omega, A, B, tau_Y, tau_S, rho, strideA, strideB, Imax, type, indx_S, S_out, Y_out, ce_out,
-                  it0, state_in, state_out, memspace};
+    RESUMED_RECORD;
     p.n_indx = n_indx;
-    if (policy) { p.policy = true; p.start = refresh_start; p.period = refresh_period; p.indx_out = indx_out; }
-    p.tol = tol; p.min_iters = min_iters; p.check = check; p.iters_out = iters_out; p.ce3_out = ce3_out;
-    return resumed_solve(ctx, nmf, p);
+    if (refresh_period >= 0) p.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    p.set_rule(tol, min_iters, check, iters_out, ce3_out);
+    return proposed_resumed_entry(ctx, p);
 }
+#undef RESUMED_RECORD
 
 // ---- the two-phase form for device arrays (include/jstsp.h) ---------------------------------------------------------------------
 struct jstsp_pending {

@@ -27,14 +27,14 @@
 // convergence_error(:, 3) stays 0 (:6).  The two entries share one host frame, Admm64 below: parameters, the shared layout, the
 // zeroing, head (Z, svt, X, K) and tail (A S B, C, V1, V2, convergence_error); each writes its own S-step between the two.
 //
-// jstsp_proposed_refresh_f64 - Alg. 2 with a support policy (Refresh64 below): at the refresh iterations the mask is the top of the
+// jstsp_proposed_refresh_f64 - Alg. 2 with a support policy in its problem record (solver_common.h): at the refresh iterations the mask is the top of the
 // solver's own new v, taken by the selection kernel of support_top.h between the gradient step and A S B - one launch for the
 // batch, nothing read back, no vendor sort and none of its workspace inside the slab.  The body is admm64_approx; with no policy
 // (every other entry) not one launch differs.
 //  Asserted (tests/test_gpu_refresh64.py): without a refresh in the call the bits of jstsp_proposed_resume_f64; with one, the bits
 //  of the chain of one-iteration calls with jstsp_support_order_f64 between them; legs; tests/refresh_ref.py within 1e-10 / 1e-8.
 //
-// jstsp_proposed_until_f64 - Alg. 2 that stops each trial when its own iterate has settled (Until64 below):
+// jstsp_proposed_until_f64 - Alg. 2 that stops each trial when its own iterate has settled (the rule in its problem record):
 // trial t stops after the first iteration i with i - it0 >= min_iters and convergence_error(i, 3) <= tol[t], the column that
 // step_v64_kernel writes per trial in one workgroup.  The body is admm64_approx again, with four more kernels and nothing changed
 // in the others:
@@ -51,6 +51,7 @@
 // trial alone over iters[t] iterations.  With no positive tol nothing is read back and the launches added are the map's
 // initialisation and the last iteration's test and capture.
 #include "pinv64.h"
+#include "solver_common.h"
 #include "support_top.h"
 #include "svt64.h"
 
@@ -365,13 +366,9 @@ size_t solver_ws_elems(int N, int M, int Gr, int G2, int batch, int nA, int nB)
 // states its own arrays after layout() inside the same ws64_open() lambda (gws among them: it knows its products), and writes its
 // S-step inline between head() and tail().
 struct Admm64 {
-    int N, M, Gr, G2, batch, Imax;                  // the call
-    long long strideA, strideB;
-    const jstsp_c64 *subY_; const double *Omega_; const jstsp_c64 *A_, *B_; const int32_t *indx_;
-    jstsp_c64 *S_out, *Y_out; double *ce_out;
+    const AdmmProblem64 &p;                         // the call
+    int batch;                                      // the trials still in the loop: the call's, until the stopping rule compacts them
     bool host;
-    int n_indx = 0;                                 // entries per trial of indx_ (0: all Gr G2, what every entry but the refreshed one passes)
-    bool refresh = false;                           // the refreshed solve: a rank array even without indx_
     std::vector<Par64> hp;                          // the arrays: parameters, shared inputs, outputs, state of the iteration
     const Par64 *par; const double2 *subY, *A, *B; const double *Omega; const int32_t *indx = nullptr;
     double2 *Sd, *Yd, *X, *V1, *V2, *Cm, *Xs, *Y, *Z, *K, *T, *W, *gws = nullptr;
@@ -380,70 +377,74 @@ struct Admm64 {
     const int32_t *map = nullptr, *flag = nullptr;  // jstsp_proposed_until_f64: slot -> trial and the slots' flags (ce goes through them)
     Svt64 sv;
 
-    bool angles() const { return indx_ != nullptr; }
-    bool want_ce() const { return ce_out != nullptr; }
-    size_t nm1() const { return (size_t)N * M; }
-    size_t g1() const { return (size_t)Gr * G2; }
-    size_t n1() const { return n_indx ? (size_t)n_indx : g1(); }
-    Mat64 Am() const { return Mat64{A, strideA, N}; }
-    Mat64 Bm() const { return Mat64{B, strideB, G2}; }
-    dim3 gnm() const { return egrid((long long)nm1(), batch); }
-    int mask_count(int it) const { return (int)std::min<long long>(10 + 5ll * (it + 1), (long long)g1()); }     // angles :36
-
-    void make_par(const double *tau_Y, const double *tau_S, const double *rho)
+    explicit Admm64(const AdmmProblem64 &q) : p(q), batch(q.batch), host(q.memspace == JSTSP_HOST)
     {
-        for (int t = 0; t < batch; ++t) hp.push_back(Par64{rho[t], 1.0 / rho[t], rho[t] / (rho[t] + 1.0), tau_Y[t] / rho[t], tau_S[t] / rho[t]});
+        for (int t = 0; t < batch; ++t)
+            hp.push_back(Par64{p.rho[t], 1.0 / p.rho[t], p.rho[t] / (p.rho[t] + 1.0), p.tau_Y[t] / p.rho[t], p.tau_S[t] / p.rho[t]});
     }
+    bool angles() const { return p.indx_S != nullptr; }
+    bool want_ce() const { return p.ce_out != nullptr; }
+    Mat64 Am() const { return Mat64{A, p.strideA, p.N}; }
+    Mat64 Bm() const { return Mat64{B, p.strideB, p.G2}; }
+    dim3 gnm() const { return egrid((long long)p.nm(), batch); }
+    int mask_count(int it) const { return (int)std::min<long long>(10 + 5ll * (it + 1), (long long)p.g()); }     // angles :36
+
     void layout(Slab &w, int b)
     {
-        const size_t enm = nm1() * b, eg = g1() * b;
+        const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2;
+        const size_t enm = p.nm() * b, eg = p.g() * b;
         par = w.in(hp.data(), b, true);
-        subY = w.in(reinterpret_cast<const double2 *>(subY_), enm, host);
-        Omega = w.in(Omega_, enm, host);
-        A = w.in(reinterpret_cast<const double2 *>(A_), dict_elems(strideA, (size_t)N * Gr, b), host);
-        B = w.in(reinterpret_cast<const double2 *>(B_), dict_elems(strideB, (size_t)G2 * M, b), host);
-        if (angles()) indx = w.in(indx_, n1() * b, host);
-        Sd = w.out(reinterpret_cast<double2 *>(S_out), eg, host);
-        Yd = w.out(reinterpret_cast<double2 *>(Y_out), enm, host);
-        ced = w.out(ce_out, (size_t)3 * Imax * b, host);
-        for (double2 **p : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *p = w.get<double2>(enm);
+        subY = w.in(reinterpret_cast<const double2 *>(p.subY), enm, host);
+        Omega = w.in(p.Omega, enm, host);
+        A = w.in(reinterpret_cast<const double2 *>(p.A), dict_elems(p.strideA, (size_t)N * Gr, b), host);
+        B = w.in(reinterpret_cast<const double2 *>(p.B), dict_elems(p.strideB, (size_t)G2 * M, b), host);
+        if (angles()) indx = w.in(p.indx_S, p.listed() * b, host);
+        Sd = w.out(reinterpret_cast<double2 *>(p.S_out), eg, host);
+        Yd = w.out(reinterpret_cast<double2 *>(p.Y_out), enm, host);
+        ced = w.out(p.ce_out, (size_t)3 * p.Imax * b, host);
+        for (double2 **q : {&X, &V1, &V2, &Cm, &Xs, &Y, &Z, &K}) *q = w.get<double2>(enm);
         T = w.get<double2>((size_t)Gr * M * b); W = w.get<double2>((size_t)N * G2 * b);
-        if (angles() || refresh) rank = w.get<int32_t>(eg);
-        for (double **p : {&lx, &l1, &l2, &ce3}) *p = w.get<double>(b);
+        if (angles() || p.policy) rank = w.get<int32_t>(eg);          // (the refreshed solve: a rank array even without indx_S)
+        for (double **q : {&lx, &l1, &l2, &ce3}) *q = w.get<double>(b);
         sv.layout(w, N, M, b);
     }
     // X = V1 = V2 = C = Xs = 0; the rank of every entry in indx_S (_angles)
     int begin(hipStream_t st)
     {
-        const size_t g = g1() * batch;
-        for (double2 *p : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(p, 0, nm1() * batch * sizeof(double2), st));
+        const size_t g = p.g() * batch;
+        for (double2 *q : {X, V1, V2, Cm, Xs}) JSTSP_HIP(hipMemsetAsync(q, 0, p.nm() * batch * sizeof(double2), st));
         if (angles()) {
             hipLaunchKernelGGL(rank64_init_kernel, dim3((unsigned)std::min<size_t>((g + 255) / 256, 4096)), dim3(256), 0, st, (long long)g, rank);
-            hipLaunchKernelGGL(rank64_kernel, egrid((long long)n1(), batch), dim3(256), 0, st, (int)g1(), (int)n1(), indx, rank);
+            hipLaunchKernelGGL(rank64_kernel, egrid((long long)p.listed(), batch), dim3(256), 0, st, (int)p.g(), (int)p.listed(), indx, rank);
         }
         return 0;
     }
     // Z, Y = svt(Z), X; leaves K = X - V2/rho - C for the S-step                                                           (:35-43)
     int head(hipStream_t st)
     {
-        hipLaunchKernelGGL(form_z64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, X, V1, Z);
+        hipLaunchKernelGGL(form_z64_kernel, gnm(), dim3(256), 0, st, (long long)p.nm(), par, X, V1, Z);
         JSTSP_TRY(sv.apply(st, Z, &par->tY, (long long)(sizeof(Par64) / sizeof(double)), Y));          // :35
-        hipLaunchKernelGGL(update_x64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
+        hipLaunchKernelGGL(update_x64_kernel, gnm(), dim3(256), 0, st, (long long)p.nm(), par, V1, Y, subY, V2, Cm, Xs, Omega, X, K);
         return 0;
+    }
+    // Xs = A S B by two products
+    int synthesize(hipStream_t st, const double2 *S)
+    {
+        const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2;
+        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am(), Mat64{S, (long long)p.g(), Gr}, W, (long long)N * G2, N, gws));      // A S
+        return zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm(), Xs, (long long)p.nm(), N, gws);          // ... B
     }
     // Xs = A S B, C, V1, V2 and row `it` of convergence_error (its third column is what ce3 holds)                          (:58-69)
     int tail(hipStream_t st, const double2 *S, int it)
     {
-        const long long sNM = (long long)nm1(), sG = (long long)g1();
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am(), Mat64{S, sG, Gr}, W, (long long)N * G2, N, gws));      // A S
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm(), Xs, sNM, N, gws));      // ... B
-        hipLaunchKernelGGL(update_c64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), par, X, Xs, Y, Cm, V1, V2);
+        JSTSP_TRY(synthesize(st, S));
+        hipLaunchKernelGGL(update_c64_kernel, gnm(), dim3(256), 0, st, (long long)p.nm(), par, X, Xs, Y, Cm, V1, V2);
         if (want_ce()) {
             JSTSP_TRY(sv.lambda_max(st, X, lx));
             JSTSP_TRY(sv.lambda_max(st, V1, l1));
             JSTSP_TRY(sv.lambda_max(st, V2, l2));
-            if (map) hipLaunchKernelGGL(ce64_map_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, map, flag, ced);
-            else hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, Imax, it, lx, l1, l2, ce3, ced);
+            if (map) hipLaunchKernelGGL(ce64_map_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, p.Imax, it, lx, l1, l2, ce3, map, flag, ced);
+            else hipLaunchKernelGGL(ce64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, p.Imax, it, lx, l1, l2, ce3, ced);
         }
         JSTSP_HIP(hipGetLastError());
         return 0;
@@ -451,31 +452,27 @@ struct Admm64 {
     // Y to the caller; for a host call S (in Sd by now), Y and convergence_error go back and the stream is synchronised
     int deliver(const Slab &s)
     {
-        const size_t nm = nm1() * batch;
-        if (Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, s.st));
+        const size_t nm = p.nm() * batch;
+        if (p.Y_out) JSTSP_HIP(hipMemcpyAsync(Yd, Y, nm * sizeof(double2), hipMemcpyDeviceToDevice, s.st));
         if (host) {
-            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), Sd, g1() * batch));
-            if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), Yd, nm));
-            if (want_ce()) JSTSP_TRY(s.copy_back(ce_out, ced, (size_t)3 * Imax * batch));
+            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.S_out), Sd, p.g() * batch));
+            if (p.Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.Y_out), Yd, nm));
+            if (want_ce()) JSTSP_TRY(s.copy_back(p.ce_out, ced, (size_t)3 * p.Imax * batch));
             JSTSP_HIP(hipStreamSynchronize(s.st));
         }
         return 0;
     }
     // ---- a resumed call (jstsp_proposed_resume_f64, jstsp_proposed_std_resume_f64) ----
-    size_t state1() const { return 4 * nm1() + 2 * g1(); }
     // X, V1, V2, C, V, S from the caller's state and Xs = A S B by the two products of tail(): what begin() zeroes, loaded
     int load_state(hipStream_t st, const double2 *state, double2 *V, double2 *S)
     {
-        const long long sNM = (long long)nm1(), sG = (long long)g1();
-        hipLaunchKernelGGL(state_unpack64_kernel, gnm(), dim3(256), 0, st, sNM, sG, state, State64{{X, V1, V2, Cm, V, S}});
+        hipLaunchKernelGGL(state_unpack64_kernel, gnm(), dim3(256), 0, st, (long long)p.nm(), (long long)p.g(), state, State64{{X, V1, V2, Cm, V, S}});
         JSTSP_HIP(hipGetLastError());
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, G2, Gr, batch, Am(), Mat64{S, sG, Gr}, W, (long long)N * G2, N, gws));      // A S
-        JSTSP_TRY(zgemm64(st, 'N', 'N', N, M, G2, batch, Mat64{W, (long long)N * G2, N}, Bm(), Xs, sNM, N, gws));      // ... B
-        return 0;
+        return synthesize(st, S);
     }
     int store_state(hipStream_t st, double2 *state, double2 *V, double2 *S)
     {
-        hipLaunchKernelGGL(state_pack64_kernel, gnm(), dim3(256), 0, st, (long long)nm1(), (long long)g1(), State64{{X, V1, V2, Cm, V, S}}, state);
+        hipLaunchKernelGGL(state_pack64_kernel, gnm(), dim3(256), 0, st, (long long)p.nm(), (long long)p.g(), State64{{X, V1, V2, Cm, V, S}}, state);
         JSTSP_HIP(hipGetLastError());
         return 0;
     }
@@ -490,44 +487,6 @@ int admm64_limits(const char *nmf, int N, int M, int Gr, int G2, int batch)
                   "%s: more than 2^31 entries per trial or more than 65535 trials", nmf);
     return 0;
 }
-
-// the arguments a resumed call adds: iterations it0 + 1 .. it0 + Imax, from state_in (NULL: from zero, and then it0 is 0)
-int resume64_args(const char *nmf, int Imax, int it0, const void *state_in)
-{
-    JSTSP_REQUIRE(it0 >= 0 && it0 <= INT_MAX - Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf, it0, Imax);
-    JSTSP_REQUIRE(state_in || it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, it0);
-    return 0;
-}
-
-// The support policy of jstsp_proposed_refresh_f64 (every other entry passes none, and the hook is off): at a refresh iteration -
-// a function of the GLOBAL 1-based index i = it0 + it, never of a call boundary - the gradient step runs without a mask, the
-// selection kernel of support_top.h ranks the top R = min(Gr G2, ST_MAX) entries of the new v, and soft_mask64_kernel rewrites S
-// from the stored v under that rank: the expression of step_v64_kernel on the value it stored, hence the bits a masked step would
-// have written.  The rank stays in force until the next refresh; before the call's first one the rank of indx_S is, or none.
-struct Refresh64 {
-    int n_indx, start, period;
-    int32_t *indx_out;
-    bool at(long long i) const { return i > start && (period ? (i - start - 1) % period == 0 : i == (long long)start + 1); }
-};
-
-int refresh64_args(const char *nmf, const Refresh64 &rf, const int32_t *indx_S, long long g)
-{
-    JSTSP_REQUIRE(rf.start >= 0 && rf.period >= 0, JSTSP_E_ARG, "%s: refresh_start = %d, refresh_period = %d: neither may be negative", nmf,
-                  rf.start, rf.period);
-    JSTSP_REQUIRE(indx_S ? rf.n_indx >= 1 && rf.n_indx <= g : rf.n_indx == 0, JSTSP_E_ARG,
-                  "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, rf.n_indx, g);
-    return 0;
-}
-
-// The stopping rule of jstsp_proposed_until_f64 (every other entry passes none, and not one launch differs): the head of this file
-// says what runs; tol holds one double per trial on the host.
-struct Until64 {
-    const double *tol;
-    int min_iters, check;
-    int32_t *iters_out;
-    double *ce3_out;
-    int n_indx;                                     // without a policy: entries per trial of indx_S (0: all Gr G2)
-};
 
 // One per-trial array that a compaction moves: `cur` is the pointer the loop uses (the caller's own array for a device input until
 // the first gather), alt the buffer the next gather writes, spare the second buffer of an array whose first `cur` is not the slab's.
@@ -551,57 +510,45 @@ template <class T> Shadow64 shadow_of(T *&p, void *alt, void *spare, long long n
     return Shadow64{[&p] { return static_cast<const void *>(p); }, [&p](void *q) { p = static_cast<T *>(q); }, alt, spare, n, stride, esz, owned};
 }
 
-int until64_args(const char *nmf, const Until64 &un, const int32_t *indx_S, long long g)
-{
-    JSTSP_REQUIRE(un.tol && un.iters_out, JSTSP_E_NULL, "%s: tol and iters_out are required", nmf);
-    JSTSP_REQUIRE(un.min_iters >= 1 && un.check >= 1, JSTSP_E_ARG, "%s: min_iters = %d, check = %d: both must be at least 1", nmf, un.min_iters,
-                  un.check);
-    JSTSP_REQUIRE(un.n_indx >= 0 && (indx_S || un.n_indx == 0) && un.n_indx <= g, JSTSP_E_ARG,
-                  "%s: n_indx = %d: need 0 (all) or 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, un.n_indx, g);
-    return 0;
-}
-
 // Alg. 2 ('approximate'), the body of jstsp_proposed_algorithm_f64 (it0 = 0, no state), of jstsp_proposed_resume_f64, - with a
-// support policy rf - of jstsp_proposed_refresh_f64 and - with a stopping rule un - of jstsp_proposed_until_f64: iterations
-// it0 + 1 .. it0 + Imax from state_in, or from zero.  nmf names the entry in every message; std_entry is where its 'std' refusal
-// points.
-int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_,
-                  const double *Omega_, const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
-                  const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out,
-                  int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace, const Refresh64 *rf = nullptr,
-                  const Until64 *un = nullptr)
+// support policy in the record - of jstsp_proposed_refresh_f64 and - with a stopping rule in it - of jstsp_proposed_until_f64 (the
+// head of this file says what each adds): iterations it0 + 1 .. it0 + Imax from state_in, or from zero.  At a refresh iteration - a
+// function of the GLOBAL index, p.refresh_at(), never of a call boundary - the gradient step runs without a mask, the selection
+// kernel of support_top.h ranks the top R entries of the new v, and soft_mask64_kernel rewrites S from the stored v under that rank:
+// the expression of step_v64_kernel on the value it stored, hence the bits a masked step would have written.  nmf names the entry in
+// every message; std_entry is where its 'std' refusal points.
+int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, const AdmmProblem64 &p)
 {
+    const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2, batch = p.batch, Imax = p.Imax, it0 = p.it0;
+    const long long strideA = p.strideA, strideB = p.strideB;
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_REQUIRE(p.memspace == JSTSP_HOST || p.memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", p.memspace);
     JSTSP_ENTER(ctx);
     JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0 && strideA >= 0 && strideB >= 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE || type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, type);
-    JSTSP_REQUIRE(type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
+    JSTSP_REQUIRE(p.subY && p.Omega && p.A && p.B && p.tau_Y && p.tau_S && p.rho && p.S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE(p.type == JSTSP_TYPE_APPROXIMATE || p.type == JSTSP_TYPE_STD, JSTSP_E_ARG, "%s: bad type %d", nmf, p.type);
+    JSTSP_REQUIRE(p.type == JSTSP_TYPE_APPROXIMATE, JSTSP_E_UNSUPPORTED,
                   "%s: 'std' has no float64 path (its least-squares solve is fp32 work): use %s", nmf, std_entry);
-    JSTSP_TRY(resume64_args(nmf, Imax, it0, state_in));
+    JSTSP_TRY(check_resumed(nmf, p));
     JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
-    if (rf) JSTSP_TRY(refresh64_args(nmf, *rf, indx_S_, (long long)Gr * G2));
-    if (un) JSTSP_TRY(until64_args(nmf, *un, indx_S_, (long long)Gr * G2));
-    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
-    f.make_par(tau_Y, tau_S, rho);
+    if (p.policy) JSTSP_TRY(check_policy(nmf, p));
+    if (p.rule) {
+        JSTSP_TRY(check_rule_arrays(nmf, p));
+        JSTSP_TRY(check_rule_counts(nmf, p));
+        if (!p.policy) JSTSP_TRY(check_rule_list(nmf, p));
+    }
+    const bool un = p.rule, rule_on = p.live();                     // live: some tol is positive, trials can stop and the loop compacts
+    Admm64 f(p);
     hipStream_t st = ctx->stream;
-    const size_t g1 = f.g1();
+    const size_t g1 = p.g();
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
-    const int R = (int)std::min<size_t>(g1, ST_MAX);               // entries of a refreshed order
-    bool runs_refresh = false;                                      // a function of it0, Imax, start and period alone
-    if (rf) {
-        f.n_indx = rf->n_indx; f.refresh = true;
-        for (int it = 0; it < Imax && !runs_refresh; ++it) runs_refresh = rf->at((long long)it0 + it + 1);
-    } else if (un) f.n_indx = un->n_indx;
+    const int R = (int)p.R();                                       // entries of a refreshed order
     int32_t *top = nullptr;                                         // the list of the call's last refresh, for indx_out
-    const bool want_top = rf && rf->indx_out && runs_refresh;
+    const bool want_top = p.indx_out && p.runs_refresh();
 
     double2 *V, *S, *Res, *RRes, *T2, *GA, *GB, *sout = nullptr;
     const double2 *sin = nullptr;
     // the stopping rule's arrays: tol, slot -> trial, flags, new slots, the active count; the outputs; the order by slot and by trial
-    bool rule_on = false;                                           // some tol is positive: trials can stop, and the loop compacts
-    for (int t = 0; un && t < batch; ++t) rule_on = rule_on || un->tol[t] > 0.0;
     const double *tolp = nullptr;
     int32_t *map = nullptr, *flag = nullptr, *newslot = nullptr, *count = nullptr, *itd = nullptr, *top_out = nullptr;
     double *c3d = nullptr;
@@ -613,20 +560,20 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         for (double2 **p : {&V, &S, &Res, &RRes, &T2}) *p = w.get<double2>(g1 * b);
         GA = w.get<double2>((size_t)Gr * Gr * bA); GB = w.get<double2>((size_t)G2 * G2 * bB);
         f.gws = w.get<double2>(solver_ws_elems(N, M, Gr, G2, b, bA, bB));
-        if (state_in) sin = w.in(reinterpret_cast<const double2 *>(state_in), f.state1() * b, f.host);
-        if (state_out) sout = w.out(reinterpret_cast<double2 *>(state_out), f.state1() * b, f.host);
-        if (want_top) top = w.out(rf->indx_out, (size_t)R * b, f.host);
+        if (p.state_in) sin = w.in(reinterpret_cast<const double2 *>(p.state_in), p.state_elems() * b, f.host);
+        if (p.state_out) sout = w.out(reinterpret_cast<double2 *>(p.state_out), p.state_elems() * b, f.host);
+        if (want_top) top = w.out(p.indx_out, (size_t)R * b, f.host);
         if (!un) return;
-        tolp = w.in(un->tol, b, true);
+        tolp = w.in(p.tol, b, true);
         for (int32_t **p : {&map, &flag, &newslot}) *p = w.get<int32_t>(b);
         count = w.get<int32_t>(1);
-        itd = w.out(un->iters_out, b, f.host);
-        if (un->ce3_out) c3d = w.out(un->ce3_out, b, f.host);
+        itd = w.out(p.iters_out, b, f.host);
+        if (p.ce3_out) c3d = w.out(p.ce3_out, b, f.host);
         if (want_top) { top_out = top; top = w.get<int32_t>((size_t)R * b); }   // the loop's list is by slot; the caller's by trial
         if (!rule_on) return;
         // the shadow set of a compaction: every array that lives from one iteration to the next, and the inputs
         sh.clear();
-        const long long nm = (long long)f.nm1(), gl = (long long)g1;
+        const long long nm = (long long)p.nm(), gl = (long long)g1;
         auto add = [&](auto *&p, long long n, long long stride, size_t total, int esz, bool owned) {
             const size_t words = (total * esz + 15) / 16;
             void *alt = w.get<double2>(words), *spare = owned ? nullptr : (void *)w.get<double2>(words);
@@ -639,7 +586,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         add(f.par, 5, 5, (size_t)5 * b, 8, true);
         add(tolp, 1, 1, b, 8, true);
         add(map, 1, 1, b, 4, true);
-        if (f.angles() || f.refresh) add(f.rank, gl, gl, (size_t)gl * b, 4, true);
+        if (f.angles() || p.policy) add(f.rank, gl, gl, (size_t)gl * b, 4, true);
         if (want_top) add(top, R, R, (size_t)R * b, 4, true);
         if (strideA) {
             add(f.A, (long long)N * Gr, strideA, dict_elems(strideA, (size_t)N * Gr, b), 16, f.host);
@@ -656,7 +603,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     if (!sin) JSTSP_HIP(hipMemsetAsync(V, 0, g1 * batch * sizeof(double2), st));
     JSTSP_TRY(f.begin(st));
     if (sin) JSTSP_TRY(f.load_state(st, sin, V, S));               // (state_out may be state_in: read whole before anything is written)
-    const long long sNM = (long long)f.nm1(), sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
+    const long long sNM = (long long)p.nm(), sG = (long long)g1, sGA = strideA ? (long long)Gr * Gr : 0, sGB = strideB ? (long long)G2 * G2 : 0;
     double2 *T = f.T, *gws = f.gws;
     JSTSP_TRY(zgemm64(st, 'C', 'N', Gr, Gr, N, nA, f.Am(), f.Am(), GA, (long long)Gr * Gr, Gr, gws));      // G_A = A^H A
     JSTSP_TRY(zgemm64(st, 'N', 'C', G2, G2, M, nB, f.Bm(), f.Bm(), GB, (long long)G2 * G2, G2, gws));      // G_B = B B^H
@@ -668,7 +615,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     bool in_force = f.angles();                                     // a rank masks S: that of indx_S, then that of the last refresh
     bool listed = false;                                            // the call has run a refresh: `top` holds a list
     for (int it = 0; it < Imax; ++it) {
-        const bool fresh = rf && rf->at((long long)it0 + it + 1);
+        const bool fresh = p.refresh_at((long long)it0 + it + 1);
         const int batch = f.batch;                                  // the trials still in the loop (the call's batch without a rule)
         const size_t g = g1 * batch;
         const Mat64 Am = f.Am(), Bm = f.Bm(), GAm{GA, sGA, Gr}, GBm{GB, sGB, G2};
@@ -693,14 +640,14 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         // ---- the stopping rule: test, capture what has just stopped, and every `check` iterations compact the survivors ----
         const bool last = it == Imax - 1;
         if (!rule_on && !last) continue;                            // no trial can stop before the last iteration
-        hipLaunchKernelGGL(until_test64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, it + 1, un->min_iters, (int)last, f.ce3, tolp, map,
+        hipLaunchKernelGGL(until_test64_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, batch, it + 1, p.min_iters, (int)last, f.ce3, tolp, map,
                            flag, itd, c3d);
         // (few workgroups per slot: in most iterations every one of them only reads its flag)
-        hipLaunchKernelGGL(until_capture64_kernel, dim3(std::min(egrid((long long)std::max(f.nm1(), g1), 1).x, 64u), batch), dim3(256), 0, st, sNM, sG, R,
-                           State64{{f.X, f.V1, f.V2, f.Cm, V, S}}, f.Y, top, (int)listed, flag, map, f.Sd, Y_out ? f.Yd : (double2 *)nullptr, sout,
+        hipLaunchKernelGGL(until_capture64_kernel, dim3(std::min(egrid((long long)std::max(p.nm(), g1), 1).x, 64u), batch), dim3(256), 0, st, sNM, sG, R,
+                           State64{{f.X, f.V1, f.V2, f.Cm, V, S}}, f.Y, top, (int)listed, flag, map, f.Sd, p.Y_out ? f.Yd : (double2 *)nullptr, sout,
                            top_out);
         JSTSP_HIP(hipGetLastError());
-        if (last || (it + 1) % un->check) continue;
+        if (last || (it + 1) % p.check) continue;
         int32_t left = 0;                                           // the one number that comes back, once per `check` iterations
         hipLaunchKernelGGL(until_compact64_kernel, dim3(1), dim3(ST_THREADS), 0, st, batch, flag, newslot, count);
         JSTSP_HIP(hipMemcpyAsync(&left, count, sizeof left, hipMemcpyDeviceToHost, st));
@@ -710,7 +657,7 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
         Gather64 gt;
         gt.cnt = 0;
         for (const Shadow64 &q : sh) gt.it[gt.cnt++] = q.item();
-        hipLaunchKernelGGL(until_gather64_kernel, egrid((long long)std::max(f.nm1(), g1), batch), dim3(256), 0, st, gt, newslot);
+        hipLaunchKernelGGL(until_gather64_kernel, egrid((long long)std::max(p.nm(), g1), batch), dim3(256), 0, st, gt, newslot);
         JSTSP_HIP(hipGetLastError());
         for (Shadow64 &q : sh) q.swap();
         JSTSP_HIP(hipMemsetAsync(flag, 0, (size_t)left * sizeof(int32_t), st));
@@ -718,13 +665,13 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     }
     if (un) {                                       // every trial was captured into the outputs at its own last iteration
         if (f.host) {
-            JSTSP_TRY(s.copy_back(un->iters_out, itd, (size_t)batch));
-            if (c3d) JSTSP_TRY(s.copy_back(un->ce3_out, c3d, (size_t)batch));
-            if (top_out) JSTSP_TRY(s.copy_back(rf->indx_out, top_out, (size_t)R * batch));
-            if (sout) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
-            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(S_out), f.Sd, g1 * batch));
-            if (Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(Y_out), f.Yd, f.nm1() * batch));
-            if (f.want_ce()) JSTSP_TRY(s.copy_back(ce_out, f.ced, (size_t)3 * Imax * batch));
+            JSTSP_TRY(s.copy_back(p.iters_out, itd, (size_t)batch));
+            if (c3d) JSTSP_TRY(s.copy_back(p.ce3_out, c3d, (size_t)batch));
+            if (top_out) JSTSP_TRY(s.copy_back(p.indx_out, top_out, (size_t)R * batch));
+            if (sout) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.state_out), sout, p.state_elems() * batch));
+            JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.S_out), f.Sd, g1 * batch));
+            if (p.Y_out) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.Y_out), f.Yd, p.nm() * batch));
+            if (f.want_ce()) JSTSP_TRY(s.copy_back(p.ce_out, f.ced, (size_t)3 * Imax * batch));
             JSTSP_HIP(hipStreamSynchronize(st));
         }
         return 0;
@@ -732,8 +679,8 @@ int admm64_approx(jstsp_ctx *ctx, const char *nmf, const char *std_entry, int N,
     const size_t g = g1 * batch;
     JSTSP_HIP(hipMemcpyAsync(f.Sd, S, g * sizeof(double2), hipMemcpyDeviceToDevice, st));
     if (sout) JSTSP_TRY(f.store_state(st, sout, V, S));
-    if (sout && f.host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
-    if (top && f.host) JSTSP_TRY(s.copy_back(rf->indx_out, top, (size_t)R * batch));
+    if (sout && f.host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.state_out), sout, p.state_elems() * batch));
+    if (top && f.host) JSTSP_TRY(s.copy_back(p.indx_out, top, (size_t)R * batch));
     return f.deliver(s);
 }
 
@@ -764,32 +711,31 @@ int rcond64_fill(hipStream_t st, int cnt, const double *rc, double *dst)
     return 0;
 }
 
-// Alg. 1 ('std'), the body of jstsp_proposed_std_f64 (it0 = 0, no state) and of jstsp_proposed_std_resume_f64
-int admm64_std(jstsp_ctx *ctx, const char *nmf, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
-               const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, const jstsp_c64 *PA_, const jstsp_c64 *PB_, int Imax,
-               const double *tau_Y, const double *tau_S, const double *rho, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
-               double *ce_out, double *rcond_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
+// Alg. 1 ('std'), the body of jstsp_proposed_std_f64 (it0 = 0, no state) and of jstsp_proposed_std_resume_f64; PA_, PB_: the caller's
+// least-squares factors, or NULL
+int admm64_std(jstsp_ctx *ctx, const char *nmf, const AdmmProblem64 &p, const jstsp_c64 *PA_, const jstsp_c64 *PB_, double *rcond_out)
 {
+    const int N = p.N, M = p.M, Gr = p.Gr, G2 = p.G2, batch = p.batch, Imax = p.Imax, it0 = p.it0;
+    const long long strideA = p.strideA, strideB = p.strideB;
     JSTSP_REQUIRE(ctx, JSTSP_E_NULL, "ctx is NULL");
-    JSTSP_REQUIRE(memspace == JSTSP_HOST || memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", memspace);
+    JSTSP_REQUIRE(p.memspace == JSTSP_HOST || p.memspace == JSTSP_DEVICE, JSTSP_E_ARG, "bad memspace %d", p.memspace);
     JSTSP_ENTER(ctx);
     JSTSP_REQUIRE(N > 0 && M > 0 && Gr > 0 && G2 > 0 && batch > 0 && Imax > 0, JSTSP_E_SHAPE, "%s: bad shape", nmf);
-    JSTSP_REQUIRE(subY_ && Omega_ && A_ && B_ && tau_Y && tau_S && rho && S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
+    JSTSP_REQUIRE(p.subY && p.Omega && p.A && p.B && p.tau_Y && p.tau_S && p.rho && p.S_out, JSTSP_E_NULL, "%s: NULL argument", nmf);
     JSTSP_REQUIRE((strideA == 0 || strideA >= (long long)N * Gr) && (strideB == 0 || strideB >= (long long)G2 * M), JSTSP_E_SHAPE,
                   "%s: a factor stride is 0 (shared) or at least the size of one factor", nmf);
     JSTSP_REQUIRE(N >= Gr && M >= G2, JSTSP_E_UNSUPPORTED,
                   "%s: K2 = kron(B.', A) must have full column rank (N >= Gr, M >= G2); the under-determined U\\(L\\k) of the reference "
                   "returns a basic, not least-squares, solution", nmf);
-    JSTSP_TRY(resume64_args(nmf, Imax, it0, state_in));
+    JSTSP_TRY(check_resumed(nmf, p));
     JSTSP_TRY(admm64_limits(nmf, N, M, Gr, G2, batch));
     JSTSP_REQUIRE((PA_ || pinv64_shape_ok(N, Gr)) && (PB_ || pinv64_shape_ok(G2, M)), JSTSP_E_UNSUPPORTED,
                   "%s: A %d x %d, B %d x %d: a factor the call inverts needs min(rows, cols) <= %d and max(rows, cols) <= %d", nmf, N, Gr, G2, M,
                   PV_MAX_ORDER, PV_MAX_LONG);
-    Admm64 f{N, M, Gr, G2, batch, Imax, strideA, strideB, subY_, Omega_, A_, B_, indx_S_, S_out, Y_out, ce_out, memspace == JSTSP_HOST};
-    f.make_par(tau_Y, tau_S, rho);
+    Admm64 f(p);
     const bool host = f.host;
     hipStream_t st = ctx->stream;
-    const size_t g1 = f.g1();
+    const size_t g1 = p.g();
     const int nA = strideA ? batch : 1, nB = strideB ? batch : 1;
 
     const double2 *PA, *PB;
@@ -818,8 +764,8 @@ int admm64_std(jstsp_ctx *ctx, const char *nmf, int N, int M, int Gr, int G2, in
         size_t e = 1;
         for (const auto &q : shp) e = std::max(e, zgemm64_ws_elems(q[0], q[1], q[2], b));
         f.gws = w.get<double2>(e);
-        if (state_in) sin = w.in(reinterpret_cast<const double2 *>(state_in), f.state1() * b, host);
-        if (state_out) sout = w.out(reinterpret_cast<double2 *>(state_out), f.state1() * b, host);
+        if (p.state_in) sin = w.in(reinterpret_cast<const double2 *>(p.state_in), p.state_elems() * b, host);
+        if (p.state_out) sout = w.out(reinterpret_cast<double2 *>(p.state_out), p.state_elems() * b, host);
     }));
     JSTSP_HIP(hipStreamSynchronize(st));            // (f.hp is this call's own: copied before it goes out of scope on any path)
 
@@ -838,7 +784,7 @@ int admm64_std(jstsp_ctx *ctx, const char *nmf, int N, int M, int Gr, int G2, in
     JSTSP_TRY(f.begin(st));
     // (Alg. 1 does not carry V - :53 recomputes it: the V of the state is loaded and overwritten by the first iteration)
     if (sin) JSTSP_TRY(f.load_state(st, sin, V, f.Sd));            // (state_out may be state_in: read whole before anything is written)
-    const long long sNM = (long long)f.nm1(), sG = (long long)g1;
+    const long long sNM = (long long)p.nm(), sG = (long long)g1;
     const Mat64 PAm{PA, strideA ? (long long)Gr * N : 0, Gr}, PBm{PB, strideB ? (long long)M * G2 : 0, M};
     for (int it = 0; it < Imax; ++it) {
         JSTSP_TRY(f.head(st));
@@ -850,7 +796,7 @@ int admm64_std(jstsp_ctx *ctx, const char *nmf, int N, int M, int Gr, int G2, in
     }
     if (host && rcond_out) JSTSP_TRY(s.copy_back(rcond_out, rcd, 2));
     if (sout) JSTSP_TRY(f.store_state(st, sout, V, f.Sd));
-    if (sout && host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(state_out), sout, f.state1() * batch));
+    if (sout && host) JSTSP_TRY(s.copy_back(reinterpret_cast<double2 *>(p.state_out), sout, p.state_elems() * batch));
     return f.deliver(s);
 }
 
@@ -892,13 +838,18 @@ int jstsp_svt_f64(jstsp_ctx *ctx, int Mr, int Mt, int batch, const jstsp_c64 *Y_
     return 0;
 }
 
+// The six ADMM entries: each fills a problem record (solver_common.h) and calls its body.
+#define ADMM64_RECORD(type_, it0_, state_in_, state_out_)                                                                                   \
+    AdmmProblem64 p{N, M, Gr, G2, batch, subY_, Omega_, A_, B_, tau_Y, tau_S, rho, strideA, strideB, Imax, type_, indx_S_, S_out, Y_out, ce_out, \
+                    it0_, state_in_, state_out_, memspace}
+
 int jstsp_proposed_algorithm_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
                                  const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
                                  const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
                                  double *ce_out, int memspace)
 {
-    return admm64_approx(ctx, "proposed_algorithm (float64)", "jstsp_proposed_algorithm_c64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_,
-                         strideB, Imax, tau_Y, tau_S, rho, type, indx_S_, S_out, Y_out, ce_out, 0, nullptr, nullptr, memspace);
+    ADMM64_RECORD(type, 0, nullptr, nullptr);
+    return admm64_approx(ctx, "proposed_algorithm (float64)", "jstsp_proposed_algorithm_c64", p);
 }
 
 int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
@@ -906,8 +857,8 @@ int jstsp_proposed_std_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int bat
                            const jstsp_c64 *PB_, int Imax, const double *tau_Y, const double *tau_S, const double *rho,
                            const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out, int memspace)
 {
-    return admm64_std(ctx, "proposed_algorithm 'std' (float64)", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_, strideB, PA_, PB_, Imax, tau_Y,
-                      tau_S, rho, indx_S_, S_out, Y_out, ce_out, rcond_out, 0, nullptr, nullptr, memspace);
+    ADMM64_RECORD(JSTSP_TYPE_STD, 0, nullptr, nullptr);
+    return admm64_std(ctx, "proposed_algorithm 'std' (float64)", p, PA_, PB_, rcond_out);
 }
 
 // elements of one trial's state block: [X | V1 | V2 | C] (N M each) then [v | S] (Gr G2 each); 0 for a bad shape
@@ -923,36 +874,34 @@ int jstsp_proposed_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int 
                               const double *tau_S, const double *rho, int type, const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out,
                               double *ce_out, int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
 {
-    return admm64_approx(ctx, "proposed_algorithm resume (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA,
-                         B_, strideB, Imax, tau_Y, tau_S, rho, type, indx_S_, S_out, Y_out, ce_out, it0, state_in, state_out, memspace);
+    ADMM64_RECORD(type, it0, state_in, state_out);
+    return admm64_approx(ctx, "proposed_algorithm resume (float64)", "jstsp_proposed_std_resume_f64", p);
 }
 
-// Alg. 2 with the support refreshed from its own iterate (Refresh64 above); the limit of a refreshed order is ST_MAX entries
+// Alg. 2 with the support refreshed from its own iterate (the record's policy); the limit of a refreshed order is ST_MAX entries
 int jstsp_proposed_refresh_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
                                const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
                                const double *tau_S, const double *rho, const int32_t *indx_S_, int n_indx, int refresh_start,
                                int refresh_period, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, int it0, const jstsp_c64 *state_in,
                                jstsp_c64 *state_out, int32_t *indx_out, int memspace)
 {
-    const Refresh64 rf{n_indx, refresh_start, refresh_period, indx_out};
-    return admm64_approx(ctx, "proposed_algorithm refresh (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_,
-                         strideA, B_, strideB, Imax, tau_Y, tau_S, rho, JSTSP_TYPE_APPROXIMATE, indx_S_, S_out, Y_out, ce_out, it0, state_in,
-                         state_out, memspace, &rf);
+    ADMM64_RECORD(JSTSP_TYPE_APPROXIMATE, it0, state_in, state_out);
+    p.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    return admm64_approx(ctx, "proposed_algorithm refresh (float64)", "jstsp_proposed_std_resume_f64", p);
 }
 
-// Alg. 2 that stops each trial when its own iterate has settled (Until64 above); refresh_period < 0: no support policy
+// Alg. 2 that stops each trial when its own iterate has settled (the record's rule); refresh_period < 0: no support policy
 int jstsp_proposed_until_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
                              const jstsp_c64 *A_, long long strideA, const jstsp_c64 *B_, long long strideB, int Imax, const double *tau_Y,
                              const double *tau_S, const double *rho, const int32_t *indx_S_, int n_indx, int refresh_start, int refresh_period,
                              const double *tol, int min_iters, int check, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, int it0,
                              const jstsp_c64 *state_in, jstsp_c64 *state_out, int32_t *indx_out, int32_t *iters_out, double *ce3_out, int memspace)
 {
-    const bool policy = refresh_period >= 0;
-    const Refresh64 rf{n_indx, refresh_start, refresh_period, indx_out};
-    const Until64 un{tol, min_iters, check, iters_out, ce3_out, policy ? 0 : n_indx};
-    return admm64_approx(ctx, "proposed_algorithm until (float64)", "jstsp_proposed_std_resume_f64", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA,
-                         B_, strideB, Imax, tau_Y, tau_S, rho, JSTSP_TYPE_APPROXIMATE, indx_S_, S_out, Y_out, ce_out, it0, state_in, state_out,
-                         memspace, policy ? &rf : nullptr, &un);
+    ADMM64_RECORD(JSTSP_TYPE_APPROXIMATE, it0, state_in, state_out);
+    p.n_indx = n_indx;
+    if (refresh_period >= 0) p.set_policy(n_indx, refresh_start, refresh_period, indx_out);
+    p.set_rule(tol, min_iters, check, iters_out, ce3_out);
+    return admm64_approx(ctx, "proposed_algorithm until (float64)", "jstsp_proposed_std_resume_f64", p);
 }
 
 int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, int batch, const jstsp_c64 *subY_, const double *Omega_,
@@ -961,8 +910,9 @@ int jstsp_proposed_std_resume_f64(jstsp_ctx *ctx, int N, int M, int Gr, int G2, 
                                   const int32_t *indx_S_, jstsp_c64 *S_out, jstsp_c64 *Y_out, double *ce_out, double *rcond_out,
                                   int it0, const jstsp_c64 *state_in, jstsp_c64 *state_out, int memspace)
 {
-    return admm64_std(ctx, "proposed_algorithm 'std' resume (float64)", N, M, Gr, G2, batch, subY_, Omega_, A_, strideA, B_, strideB, PA_, PB_, Imax,
-                      tau_Y, tau_S, rho, indx_S_, S_out, Y_out, ce_out, rcond_out, it0, state_in, state_out, memspace);
+    ADMM64_RECORD(JSTSP_TYPE_STD, it0, state_in, state_out);
+    return admm64_std(ctx, "proposed_algorithm 'std' resume (float64)", p, PA_, PB_, rcond_out);
 }
 
 }  // extern "C"
+#undef ADMM64_RECORD

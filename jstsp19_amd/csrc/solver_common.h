@@ -2,6 +2,7 @@
 // spectral norms, host<->device staging.
 #pragma once
 #include "common.h"
+#include <climits>
 #include <vector>
 
 namespace jstsp {
@@ -173,9 +174,15 @@ template <class Cx, class Re> struct AdmmProblemOf {
     // The stopping rule of jstsp_proposed_until_c32 (include/jstsp.h; every other entry passes none: iters_out == NULL): trial t stops
     // after the first iteration k of the call with k >= min_iters and ce(k, 3) <= tol[t] (host doubles, as tau_Y); every `check`
     // iterations the host reads how many trials still run.  live(): some tol is positive, so a trial can stop before Imax.
+    bool rule = false;                           // the entry takes a rule: tol and iters_out are then required (check_rule_arrays)
     const double *tol = nullptr;
     int min_iters = 0, check = 0;
     int32_t *iters_out = nullptr; double *ce3_out = nullptr;
+    void set_policy(int n, int start_, int period_, int32_t *order_out) { policy = true; n_indx = n; start = start_; period = period_; indx_out = order_out; }
+    void set_rule(const double *tol_, int min_iters_, int check_, int32_t *iters, double *ce3)
+    {
+        rule = true; tol = tol_; min_iters = min_iters_; check = check_; iters_out = iters; ce3_out = ce3;
+    }
     bool until() const { return iters_out != nullptr; }
     bool live() const
     {
@@ -214,6 +221,50 @@ template <class Cx, class Re> struct AdmmProblemOf {
 };
 using AdmmProblem = AdmmProblemOf<jstsp_c32, float>;          // what the solver takes
 using AdmmProblem64 = AdmmProblemOf<jstsp_c64, double>;       // the same arrays as the _c64 entries receive them (c64.hip)
+
+// The argument checks that the entries of the family share - fp32, _c64 and float64 (proposed.hip, c64.hip, proposed64.hip) - each
+// worded once; nmf names the entry in the message.  An entry applies them in its own order between its own checks, so which
+// refusal wins for a given bad call is the entry's business.
+// ... the resumed pair: iterations it0 + 1 .. it0 + Imax, from state_in (NULL: from zero, and then it0 is 0)
+template <class Cx, class Re> int check_resumed(const char *nmf, const AdmmProblemOf<Cx, Re> &p)
+{
+    JSTSP_REQUIRE(p.it0 >= 0 && p.it0 <= INT_MAX - p.Imax, JSTSP_E_ARG, "%s: it0 = %d with Imax = %d: need 0 <= it0 and it0 + Imax within int", nmf,
+                  p.it0, p.Imax);
+    JSTSP_REQUIRE(p.state_in || p.it0 == 0, JSTSP_E_ARG, "%s: it0 = %d without state_in: a call from zero starts at iteration 1 (it0 = 0)", nmf, p.it0);
+    return 0;
+}
+// ... the support policy: its schedule, and its list (jstsp_proposed_until_c32 words the schedule's refusal itself: schedule = false)
+template <class Cx, class Re> int check_policy(const char *nmf, const AdmmProblemOf<Cx, Re> &p, bool schedule = true)
+{
+    JSTSP_REQUIRE(!schedule || (p.start >= 0 && p.period >= 0), JSTSP_E_ARG, "%s: refresh_start = %d, refresh_period = %d: neither may be negative", nmf,
+                  p.start, p.period);
+    JSTSP_REQUIRE(p.indx_S ? p.n_indx >= 1 && p.n_indx <= (long long)p.g() : p.n_indx == 0, JSTSP_E_ARG,
+                  "%s: n_indx = %d: need 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without", nmf, p.n_indx, (long long)p.g());
+    return 0;
+}
+// ... the stopping rule: its arrays, its counts, and the list of a call without a policy (fmt takes nmf, n_indx and Gr * G2: the _c64
+// entry, which judges the list before it narrows it, has words of its own)
+template <class Cx, class Re> int check_rule_arrays(const char *nmf, const AdmmProblemOf<Cx, Re> &p)
+{
+    JSTSP_REQUIRE(p.tol && p.iters_out, JSTSP_E_NULL, "%s: tol and iters_out are required", nmf);
+    return 0;
+}
+template <class Cx, class Re> int check_rule_counts(const char *nmf, const AdmmProblemOf<Cx, Re> &p)
+{
+    JSTSP_REQUIRE(p.min_iters >= 1 && p.check >= 1, JSTSP_E_ARG, "%s: min_iters = %d, check = %d: both must be at least 1", nmf, p.min_iters, p.check);
+    return 0;
+}
+template <class Cx, class Re>
+int check_rule_list(const char *nmf, const AdmmProblemOf<Cx, Re> &p,
+                    const char *fmt = "%s: n_indx = %d: need 0 (all) or 1 <= n_indx <= Gr * G2 = %lld with indx_S, and 0 without")
+{
+    JSTSP_REQUIRE(p.n_indx >= 0 && (p.indx_S || p.n_indx == 0) && p.n_indx <= (long long)p.g(), JSTSP_E_ARG, fmt, nmf, p.n_indx, (long long)p.g());
+    return 0;
+}
+
+// jstsp_proposed_resume_c32, _refresh_c32 (the record has a policy) and _until_c32 (it has a rule) behind their C prototypes
+// (proposed.hip): that entry's checks in its order, then one staged solve with its recovery.  c64.hip calls it with the narrowed record.
+int proposed_resumed_entry(jstsp_ctx *ctx, AdmmProblem &p);
 
 // Runs of consecutive trials in an ascending list of flagged ones: fn(first trial, count) for each, until one fails.
 template <class F> int for_each_run(const std::vector<int> &ovf, F &&fn)

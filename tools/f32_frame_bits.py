@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Bits of the fp32 proposed_algorithm through every entry of its call frame (plain, begin/end, resumed, the _c64 forms, the
-pipelined host calls, the refusals, the refreshed entry) and every branch of its driver (branch_cases), to hold one build of
+pipelined host calls, the refusals, the refreshed and the until entries) and every branch of its driver (branch_cases), to hold one build of
 the library against another as tools/f64_bits.py does for float64:
 ``--dump FILE`` writes, for every call, each output array (above 4 KiB: its SHA-256), the status with
 jstsp_last_fused_fallbacks, jstsp_last_dictionary_block and the workspace size, and the message of a refused call, from the
@@ -68,12 +68,13 @@ def _host(x):
     return x.cpu().numpy() if torch.is_tensor(x) else x
 
 
-def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=None, refresh=None, env=None, **over):
-    """One call of jstsp_proposed_{algorithm,resume,refresh}_{c32,c64} on P; yields (name, array) for every output, the status and
+def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=None, refresh=None, until=None, env=None, **over):
+    """One call of jstsp_proposed_{algorithm,resume,refresh,until}_{c32,c64} on P; yields (name, array) for every output, the status and
     the counters, and the message when the call was refused.  resume: dict(it0, state (host array or None), same (state_out is
     state_in), out (a state is returned)).  refresh: (start, period) of jstsp_proposed_refresh_c32, which takes resume too (default:
-    from zero); indx: True the whole order of P, an int its first so many entries (refresh only).  over: arguments replaced by name
-    (None: a NULL pointer)."""
+    from zero); indx: True the whole order of P, an int its first so many entries (refresh and until only).  until: dict(tol, min_iters, check)
+    of jstsp_proposed_until_c32, which takes refresh (default: no policy) and resume too.  over: arguments replaced by name (None: a
+    NULL pointer)."""
     lib, ctx = _lib.load(), _lib.default_context(0)
     cdt, rdt = (np.complex128, np.float64) if c64 else (np.complex64, np.float32)
     wide = lambda a: a.astype(rdt if a.dtype.kind == "f" else cdt)
@@ -87,17 +88,23 @@ def call(tag, P, Imax, mem, *, c64=False, type=0, indx=False, ce=True, resume=No
     v.update({k: a.ctypes.data_as(_lib.c_dp) for k, a in P.scal.items()})
     v.update(over)
     args = [ctx.handle] + [v[k] for k in ARGS]
-    if refresh:
+    if refresh or until:
         resume = resume or dict(it0=0)
         outs["order"] = zeros(P.batch * min(P.Gr * P.G2, _lib.SUPPORT_TOP_MAX), np.int32)
-        args[-3:-3] = [n_indx, refresh[0], refresh[1]]          # (... type, indx_S, n_indx, start, period, S, Y, ce)
-    name = "jstsp_proposed_%s_%s" % ("refresh" if refresh else "resume" if resume else "algorithm", "c64" if c64 else "c32")
+        start, period = refresh or (0, -1)                      # (a negative period: the until entry without a policy)
+        args[-3:-3] = [n_indx, start, period]                   # (... type, indx_S, n_indx, start, period, [rule,] S, Y, ce)
+    if until:
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(until["tol"], np.float64), (P.batch,)))
+        outs["iters"], outs["ce3"] = zeros(P.batch, np.int32), zeros(P.batch, np.float64)
+        args[-3:-3] = [tol.ctypes.data_as(_lib.c_dp), until.get("min_iters", 2), until.get("check", 1)]
+    name = "jstsp_proposed_%s_%s" % ("until" if until else "refresh" if refresh else "resume" if resume else "algorithm", "c64" if c64 else "c32")
     if resume:
         st = resume.get("state")
         s_in = None if st is None else _place(np.ascontiguousarray(st, dtype=cdt), mem)
         s_out = s_in if resume.get("same") else (zeros(P.batch * P.state_elems, cdt) if resume.get("out", True) else None)
         outs["state"] = s_out
-        args += [resume["it0"], _ptr(s_in), _ptr(s_out)] + ([_ptr(outs["order"])] if refresh else [])
+        args += [resume["it0"], _ptr(s_in), _ptr(s_out)] + ([_ptr(outs["order"])] if refresh or until else [])
+        args += [_ptr(outs["iters"]), _ptr(outs["ce3"])] if until else []
     os.environ.update(env or {})
     try:
         rc = getattr(lib, name)(*args, v["memspace"])
@@ -341,6 +348,37 @@ def refresh_cases():
                     yield from call(tag + "/leg2_two_outputs", P, 6, mem, indx=indx, ce=False, refresh=pol, resume=dict(it0=6, state=st, out=False), env=env)
 
 
+def until_cases():
+    """jstsp_proposed_until_c32 / _c64 on the small shape, with and without a policy, with no positive tol and with one: from zero,
+    and a second leg from the returned state"""
+    P = small()
+    for c64 in (False, True):
+        for mem in (HOST, DEVICE):
+            for pol in (None, (3, 2)):
+                for tol in (0.0, (1e-1, 1e-2)):
+                    for indx in (False, 40):
+                        tag = "until/%s/mem%d/%s/tol%d/indx%d" % ("c64" if c64 else "c32", mem, "start%d_period%d" % pol if pol else "no_policy",
+                                                                 tol != 0.0, indx)
+                        rule = dict(tol=np.resize(np.asarray(tol, np.float64), P.batch), min_iters=2, check=3)
+                        kw = dict(c64=c64, indx=indx, refresh=pol, until=rule)
+                        yield from call(tag + "/leg1", P, 8, mem, **kw)
+                        st = call.last["state"]
+                        yield from call(tag + "/leg2", P, 8, mem, resume=dict(it0=8, state=st), **kw)
+            yield from call("until/%s/mem%d/forced" % ("c64" if c64 else "c32", mem), P, 8, mem, c64=c64, env=FORCED,
+                            until=dict(tol=1e-2, min_iters=2, check=3))
+
+
+def entry_refusal_cases():
+    """status, message and the outputs written (none) of every row of tests/test_gpu_admm_refusals.py for the fp32 entries"""
+    import test_gpu_admm_refusals as R
+    for name in sorted(n for n, e in R.ENTRIES.items() if e[1] != "f64"):
+        for mem in (HOST, DEVICE):
+            c = R.Call(name, mem)
+            for label, over, _ in R.rows_for(name):
+                rc, msg, written = c(over)
+                yield "entry_refused/%s/mem%d/%s" % (name, mem, label), np.frombuffer(("%d: %s %s" % (rc, msg, sorted(written))).encode(), np.uint8)
+
+
 # single calls for a kernel trace (one process per call): name -> (problem, arguments of call())
 TRACE_CALLS = {
     "small_ce": (small, dict(Imax=6)),
@@ -357,7 +395,8 @@ TRACE_CALLS = {
 
 def cases():
     _lib.default_context(0).use_torch_stream()
-    for gen in (plain_cases, two_run_cases, begin_end_cases, resume_cases, c64_cases, pipelined_cases, refusal_cases, branch_cases, refresh_cases):
+    for gen in (plain_cases, two_run_cases, begin_end_cases, resume_cases, c64_cases, pipelined_cases, refusal_cases, branch_cases, refresh_cases, until_cases,
+                entry_refusal_cases):
         yield from gen()
 
 

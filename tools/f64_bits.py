@@ -125,6 +125,44 @@ def admm_cases():
                 yield from both(tag + "/halved", lambda *x, **k: fn(*x[:4], 3, *x[4:], it0=3, **k), *a, *prm, state=st, **kw)
 
 
+def policy_cases():
+    """jstsp_proposed_refresh_f64 on the policies of tests/test_gpu_refresh64.py (from zero, and a second leg from the returned state
+    and order) and jstsp_proposed_until_f64 on the configurations and tolerances of tests/until_ref.py, at three values of `check`"""
+    import test_gpu_refresh64 as TR
+    import test_gpu_until64 as TU
+    import until_ref as U
+    for name, shared in (("R1", False), ("R1", True), ("R2", False)):
+        for mem in ("host", "device"):
+            for start, period, prior in TR.POLICIES:
+                tag = "refresh64/%s/%s/%s/start%d_period%d_prior%d" % (name, "sharedB" if shared else "ownB", mem, start, period, prior)
+                leg1 = TR._refresh(name, shared, mem, 3, start, period, prior)
+                leg2 = TR._refresh(name, shared, mem, 3, start, period, prior, state=leg1[3], it0=3)
+                for i, o in enumerate(tuple(leg1) + tuple(leg2)):
+                    if o is not None:
+                        yield "%s/%d" % (tag, i), _np(o)
+    for name, shared, use_indx, refresh in U.CONFIGS:
+        for mem in ("host", "device"):
+            for tname, tols in sorted(U.TOLS.items()) + [("none", (0.0, 0.0, 0.0))]:
+                for check in TU.CHECKS if tname == "abc" else (3,):
+                    tag = "until64/%s/%s/indx%d/%s/%s/%s/check%d" % (name, "sharedB" if shared else "ownB", use_indx, refresh, mem, tname, check)
+                    out = TU._until(name, shared, mem, np.asarray(tols, np.float64), use_indx=use_indx, refresh=refresh, min_iters=U.MIN_ITERS,
+                                    check=check)
+                    for i, o in enumerate(out):
+                        if o is not None:
+                            yield "%s/%d" % (tag, i), o
+
+
+def entry_refusal_cases():
+    """status, message and the outputs written (none) of every row of tests/test_gpu_admm_refusals.py for the float64 entries"""
+    import test_gpu_admm_refusals as R
+    for name in sorted(n for n, e in R.ENTRIES.items() if e[1] == "f64"):
+        for mem in (R.HOST, R.DEVICE):
+            c = R.Call(name, mem)
+            for label, over, _ in R.rows_for(name):
+                rc, msg, written = c(over)
+                yield "entry_refused/%s/mem%d/%s" % (name, mem, label), np.frombuffer(("%d: %s %s" % (rc, msg, sorted(written))).encode(), np.uint8)
+
+
 def refusal_cases():
     """the message of every refused big shape: it names the largest batch that fits, i.e. the measured workspace"""
     import test_gpu_f64_workspace as W
@@ -149,7 +187,7 @@ def refusal_cases():
 
 
 def cases():
-    for gen in (omp_cases, mmv_cases, admm_cases, refusal_cases):
+    for gen in (omp_cases, mmv_cases, admm_cases, policy_cases, refusal_cases, entry_refusal_cases):
         yield from gen()
 
 
